@@ -22,7 +22,10 @@ value = guest cycles of the execution x steps / max-over-ranks wall time.   scal
 --batch B: B independent single-shard proofs (the example input with distinct gen_id each), round-robin over the
 ranks, no collective on the data path (BASELINE configs[4], "replicas only").
 
-Extra objects on the JSON line (rank 0 prints exactly one line):
+A plain run sets up, warms up, times --steps steps and prints the headline line.  --full adds, outside the timed
+region, the check that the configuration's proof verifies and the extra objects below (rank 0 prints exactly one line):
+  config        resident_single_shard_cycles_per_s, executor_fast_pass_cycles_per_s, executor_trace_mode_cycles_per_s_per_thread
+  stage_ms, whole_shard  per-stage HIP-event times and the whole-shard byte model of one single-shard proof
   roofline      the dominant HBM-classified kernel family, K1 coset LDE: algorithmic bytes (12 B per trace element:
                 read N, write 2N words per column) / summed duration of its launches inside one prove, HIP events on
                 the prover's own stream; "alu_bound_exception" carries the Poseidon2 commitment kernels (K2/K3)
@@ -31,6 +34,8 @@ Extra objects on the JSON line (rank 0 prints exactly one line):
                 prover handles on the GPU
   cpu_baseline  the oracle's CPU prover (tests/_oracle_prover.py over oracle/*.c, OpenMP) on two bounded samples of the
                 same guest (smaller iteration constants), production parameters; value = marginal cycles/s
+
+--dump-outputs DIR: after the timed steps, the proof(s) the last timed step produced (see dump_outputs).
 """
 import argparse
 import hashlib
@@ -131,6 +136,25 @@ def cpu_baseline(stdin_buf, sizes):
     }
 
 
+DUMP_WORDS = 3 << 20   # proof words kept: value + position as float64 = 48 MiB
+
+
+def dump_outputs(path, proofs):
+    """What the last timed step hands its caller: the proof container(s), in order.  proof_words.npy = their 32-bit words
+    (concatenated) as float64, which holds every u32 exactly; beyond DUMP_WORDS words a fixed seeded sample of them, whose
+    positions are proof_words_index.npy; proof_bytes.npy = the length of each proof."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    words = np.frombuffer(b"".join(proofs), np.uint32)
+    idx = np.arange(words.size)
+    if words.size > DUMP_WORDS:
+        idx = np.sort(np.random.default_rng(0).choice(words.size, DUMP_WORDS, replace=False))
+    np.save(os.path.join(path, "proof_words.npy"), words[idx].astype(np.float64))
+    np.save(os.path.join(path, "proof_words_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(path, "proof_bytes.npy"), np.array([len(p) for p in proofs], np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -151,7 +175,12 @@ def main():
                     "(95 = a little over 1 M cycles: the fixed costs are then below a fifth of the larger sample)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-reference-example", action="store_true", help="skip the extra object with BASELINE configs[1] taken literally")
+    ap.add_argument("--full", action="store_true", help="also verify the configuration's proof and measure the secondary figures "
+                    "(resident rate, executor rates, roofline, stage times, reference_example, CPU baseline); off: the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the proof(s) of the last timed step to DIR/*.npy (dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     global SHA_PRECOMPILES, CURVE_PRECOMPILES
     SHA_PRECOMPILES = args.sha_precompiles
     CURVE_PRECOMPILES = args.curve_precompiles
@@ -194,7 +223,7 @@ def main():
         inputs = [workload_stdin(args.participants, instance=i) for i in range(args.batch)]
         mine = ranks.shard_of(args.batch)
         # correctness outside the timed region: this rank's first proof verifies with the public values the guest must commit
-        if mine:
+        if args.full and mine:
             proof, rep = prover.prove_core(pk, [inputs[mine[0]]])
             ok, ec, pv, why = capi.verify(vk, proof, 100, 16)
             assert ok and ec == 0 and pv == guests.dkg_like_expected(inputs[mine[0]], "finalization", *consts, curve_precompiles=CURVE_PRECOMPILES), f"bench proof rejected: {why}"
@@ -207,16 +236,19 @@ def main():
             h = capi.Prover(cfg)
             lanes.append((h, h.setup(elf)[0]))
         cyc_mine = 0
+        last = {}   # --dump-outputs: proof i of the last timed step
 
-        def step():
+        def step(keep=False):
             nonlocal cyc_mine
             done = [0] * len(lanes)
 
             def lane(k):
                 h, hpk = lanes[k]
                 for i in mine[k::len(lanes)]:
-                    _, rep = h.prove_core(hpk, [inputs[i]])
+                    proof, rep = h.prove_core(hpk, [inputs[i]])
                     done[k] += int(rep["cycles"])
+                    if keep:
+                        last[i] = proof
 
             th = [threading.Thread(target=lane, args=(k,)) for k in range(len(lanes))]
             for t in th:
@@ -229,11 +261,13 @@ def main():
             step()
         barrier()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
-            step()
+        for s in range(args.steps):
+            step(keep=bool(args.dump_outputs) and s == args.steps - 1)
         prover.sync()
         barrier()
         dt = ranks.max_over_ranks(time.perf_counter() - t0)
+        if args.dump_outputs:
+            outputs = ranks.gather_proofs(args.batch, [last[i] for i in mine])
         t = torch.tensor([float(cyc_mine)], dtype=torch.float64, device=coll)
         if ranks.dist:
             ranks.dist.all_reduce(t)
@@ -252,7 +286,6 @@ def main():
         consts = fit_constants(stdin_buf, total_shards, args.sig_iters)
         elf = guests.dkg_like("finalization", *consts, **guest_kw())
         pk, vk = prover.setup(elf)
-        want_pv = guests.dkg_like_expected(stdin_buf, "finalization", *consts, curve_precompiles=CURVE_PRECOMPILES)
         state = {}
 
         def prove_once(want_bytes):
@@ -264,28 +297,36 @@ def main():
             proofs = [prover.prove_shard(pk, job, i, ch, want_bytes=want_bytes) for i in mine]     # phase 2
             state.update(cycles=int(rep["cycles"]), n_shards=n, exec_wait=prover.job_exec_wait(job))
             if want_bytes:
-                allp = ranks.gather_proofs(n, proofs)
-                full = prover.assemble(job, allp)
-                prover.job_free(job)
-                return full
+                return job, proofs      # assembled (and the job freed) by assemble(), outside any timed region
             prover.job_free(job)
             return None
 
-        # correctness outside the timed region: the proof this configuration produces must verify
-        full = prove_once(True)
-        if rank == 0:
-            ok, ec, pv, why = capi.verify(vk, full, 100, 16)
-            assert ok and pv == want_pv and ec == 0, f"bench proof rejected: {why}"
-        del full
+        def assemble(held):
+            job, proofs = held
+            full = prover.assemble(job, ranks.gather_proofs(state["n_shards"], proofs))
+            prover.job_free(job)
+            return full
+
+        if args.full:
+            # correctness outside the timed region: the proof this configuration produces must verify
+            full = assemble(prove_once(True))
+            if rank == 0:
+                want_pv = guests.dkg_like_expected(stdin_buf, "finalization", *consts, curve_precompiles=CURVE_PRECOMPILES)
+                ok, ec, pv, why = capi.verify(vk, full, 100, 16)
+                assert ok and pv == want_pv and ec == 0, f"bench proof rejected: {why}"
+            del full
         for _ in range(args.warmup):
             prove_once(False)
         barrier()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
-            prove_once(False)
+        for s in range(args.steps):
+            # --dump-outputs: the last timed step also copies its shard proofs out of the prover (host memory only)
+            held = prove_once(bool(args.dump_outputs) and s == args.steps - 1)
         prover.sync()
         barrier()
         dt = ranks.max_over_ranks(time.perf_counter() - t0)
+        if args.dump_outputs:
+            outputs = [assemble(held)]
         cycles, n_shards = state["cycles"], state["n_shards"]
         extra["executor_wait_seconds_per_step_rank0"] = state["exec_wait"]
         extra["proofs_per_hour"] = args.steps * 3600.0 / dt
@@ -295,47 +336,81 @@ def main():
                     "finalization-shaped synthetic guest tests/guests.py:dkg_like%r: %d shards of 2^21 RV32IM cycles; the reference's own guest ELF is "
                     "prebuilt machine code and is not run (it would be 511 shards on this input, SURVEY.md App. B.3)" % (tuple(consts), n_shards))
         parallelism = "one execution, shard i on GPU i mod %d; all-gather of 52-byte shard headers between the two phases" % world
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outputs)
 
-    # ---- secondary figures on one single-shard execution: resident prove rate, kernel-family timing (profile handle)
-    #      (always on the reference's example input: an n = 255 input does not fit one shard)
-    stdin_buf = workload_stdin(0)
-    one = fit_constants(stdin_buf, 1)
-    elf1 = guests.dkg_like("finalization", *one, **guest_kw())
-    pk1, _ = prover.setup(elf1)
-    job1, rep1 = prover.prepare(pk1, [stdin_buf])
-    prover.prove_job(pk1, job1, want_bytes=False)
-    prover.sync()
-    t1 = time.perf_counter()
-    for _ in range(3):
+    full_figures = {}
+    if args.full:
+        # ---- secondary figures on one single-shard execution: resident prove rate, kernel-family timing (profile handle)
+        #      (always on the reference's example input: an n = 255 input does not fit one shard)
+        stdin_buf = workload_stdin(0)
+        one = fit_constants(stdin_buf, 1)
+        elf1 = guests.dkg_like("finalization", *one, **guest_kw())
+        pk1, _ = prover.setup(elf1)
+        job1, rep1 = prover.prepare(pk1, [stdin_buf])
         prover.prove_job(pk1, job1, want_bytes=False)
-    prover.sync()
-    resident = 3 * int(rep1["cycles"]) / (time.perf_counter() - t1)
-    prover.job_free(job1)
-    prover.pk_free(pk1)
-    # the host executor alone on this box's cores (the sequential fast pass is the Amdahl term of the N-GPU prove)
-    extra["executor_fast_pass_cycles_per_s"] = capi.exec_rate(elf1, [stdin_buf], LOG_SHARD, False)
-    extra["executor_trace_mode_cycles_per_s_per_thread"] = capi.exec_rate(elf1, [stdin_buf], LOG_SHARD, True)
-    prof = capi.Prover('{"device": %d, "fri_queries": 100, "pow_bits": 16, "profile": 1}' % local)
-    ppk, _ = prof.setup(elf1)
-    pjob, _ = prof.prepare(ppk, [stdin_buf])
-    prof.prove_job(ppk, pjob, want_bytes=False)
-    prof.prove_job(ppk, pjob, want_bytes=False)
-    stage = prof.stage_ms()
-    ks = prof.kernel_stats()
-    prof.job_free(pjob)
-    prof.pk_free(ppk)
-    prof.close()
-    lde_gbps = ks["lde_alg_bytes"] / (ks["lde_ms"] * 1e-3) / 1e9 if ks["lde_ms"] else 0.0
-    # compulsory streams of the whole shard, each counted once
-    shard_alg = 36 * ks["cells_main"] + 36 * ks["cells_perm"] + 28 * ks["cells_quotient"] + 24 * ks["cells_prep"]
-    pmc = {}
-    for name in ("r3_pmc_k1_traffic.json", "r2_pmc_k1_traffic.json", "r1c_pmc_k1_traffic.json"):
-        try:
-            pmc = json.load(open(os.path.join(ROOT, "profiles", name)))
-            pmc["_file"] = name
-            break
-        except OSError:
-            pass
+        prover.sync()
+        t1 = time.perf_counter()
+        for _ in range(3):
+            prover.prove_job(pk1, job1, want_bytes=False)
+        prover.sync()
+        resident = 3 * int(rep1["cycles"]) / (time.perf_counter() - t1)
+        prover.job_free(job1)
+        prover.pk_free(pk1)
+        # the host executor alone on this box's cores (the sequential fast pass is the Amdahl term of the N-GPU prove)
+        extra["executor_fast_pass_cycles_per_s"] = capi.exec_rate(elf1, [stdin_buf], LOG_SHARD, False)
+        extra["executor_trace_mode_cycles_per_s_per_thread"] = capi.exec_rate(elf1, [stdin_buf], LOG_SHARD, True)
+        prof = capi.Prover('{"device": %d, "fri_queries": 100, "pow_bits": 16, "profile": 1}' % local)
+        ppk, _ = prof.setup(elf1)
+        pjob, _ = prof.prepare(ppk, [stdin_buf])
+        prof.prove_job(ppk, pjob, want_bytes=False)
+        prof.prove_job(ppk, pjob, want_bytes=False)
+        stage = prof.stage_ms()
+        ks = prof.kernel_stats()
+        prof.job_free(pjob)
+        prof.pk_free(ppk)
+        prof.close()
+        lde_gbps = ks["lde_alg_bytes"] / (ks["lde_ms"] * 1e-3) / 1e9 if ks["lde_ms"] else 0.0
+        # compulsory streams of the whole shard, each counted once
+        shard_alg = 36 * ks["cells_main"] + 36 * ks["cells_perm"] + 28 * ks["cells_quotient"] + 24 * ks["cells_prep"]
+        pmc = {}
+        for name in ("r3_pmc_k1_traffic.json", "r2_pmc_k1_traffic.json", "r1c_pmc_k1_traffic.json"):
+            try:
+                pmc = json.load(open(os.path.join(ROOT, "profiles", name)))
+                pmc["_file"] = name
+                break
+            except OSError:
+                pass
+        extra["resident_single_shard_cycles_per_s"] = resident
+        extra["resident_note"] = "K0..K9 of one ~2^21-cycle shard (the reference's example input) whose cycle records are already in HBM (round 1's headline figure), for comparison"
+        full_figures = {
+            "roofline": {
+                "bound": "hbm",
+                "kernel": "K1 coset LDE (ntt_strided_v4_kernel<true> + lde_block2_kernel + ntt_strided_v4_kernel<false>), %d calls per proof" % ks["lde_calls"],
+                "achieved": lde_gbps,
+                "peak": HBM_PEAK_GBPS,
+                "unit": "GB/s",
+                "frac": lde_gbps / HBM_PEAK_GBPS,
+                "traffic": pmc.get("k1_hbm_bytes_per_proof"),
+                "traffic_source": "profiles/%s (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate passes, gfx950 FETCH_SIZE x2 correction applied "
+                                  "where the guide prescribes it); bytes per single-shard proof, like alg_bytes_per_proof" % pmc.get("_file", "(none)"),
+                "alg_bytes_per_proof": ks["lde_alg_bytes"],
+                "ms_per_proof": ks["lde_ms"],
+            },
+            "alu_bound_exception": {
+                "kernel": "K2+K3 Poseidon2 trace commitments (merkle_leaves_kernel + merkle_level_kernel + merkle_top_kernel)",
+                "ms_per_proof": ks["merkle_ms"],
+                "gperm_per_s": ks["merkle_perms"] / (ks["merkle_ms"] * 1e-3) / 1e9 if ks["merkle_ms"] else 0.0,
+            },
+            "stage_ms": stage,
+            "whole_shard": {
+                "alg_bytes": shard_alg,
+                "formula": "36 M + 36 P + 28 Q + 24 Pre (field elements of the main / permutation / quotient / preprocessed traces)",
+                "cells": {k: ks["cells_" + k] for k in ("main", "perm", "quotient", "prep")},
+                "achieved_GBps_resident": shard_alg * resident / max(int(rep1["cycles"]), 1) / 1e9,
+                "frac_of_hbm_peak_resident": shard_alg * resident / max(int(rep1["cycles"]), 1) / 1e9 / HBM_PEAK_GBPS,
+            },
+        }
 
     out = {
         "metric": "SP1 prover cycles/sec + proofs/hour, finalization_prove at 1/2/4/8 MI355X",
@@ -364,44 +439,17 @@ def main():
             "pow_bits": 16,
             "log_blowup": 1,
             "parallelism": parallelism,
-            "resident_single_shard_cycles_per_s": resident,
-            "resident_note": "K0..K9 of one ~2^21-cycle shard (the reference's example input) whose cycle records are already in HBM (round 1's headline figure), for comparison",
         }, **extra),
-        "roofline": {
-            "bound": "hbm",
-            "kernel": "K1 coset LDE (ntt_strided_v4_kernel<true> + lde_block2_kernel + ntt_strided_v4_kernel<false>), %d calls per proof" % ks["lde_calls"],
-            "achieved": lde_gbps,
-            "peak": HBM_PEAK_GBPS,
-            "unit": "GB/s",
-            "frac": lde_gbps / HBM_PEAK_GBPS,
-            "traffic": pmc.get("k1_hbm_bytes_per_proof"),
-            "traffic_source": "profiles/%s (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate passes, gfx950 FETCH_SIZE x2 correction applied "
-                              "where the guide prescribes it); bytes per single-shard proof, like alg_bytes_per_proof" % pmc.get("_file", "(none)"),
-            "alg_bytes_per_proof": ks["lde_alg_bytes"],
-            "ms_per_proof": ks["lde_ms"],
-        },
-        "alu_bound_exception": {
-            "kernel": "K2+K3 Poseidon2 trace commitments (merkle_leaves_kernel + merkle_level_kernel + merkle_top_kernel)",
-            "ms_per_proof": ks["merkle_ms"],
-            "gperm_per_s": ks["merkle_perms"] / (ks["merkle_ms"] * 1e-3) / 1e9 if ks["merkle_ms"] else 0.0,
-        },
-        "stage_ms": stage,
-        "whole_shard": {
-            "alg_bytes": shard_alg,
-            "formula": "36 M + 36 P + 28 Q + 24 Pre (field elements of the main / permutation / quotient / preprocessed traces)",
-            "cells": {k: ks["cells_" + k] for k in ("main", "perm", "quotient", "prep")},
-            "achieved_GBps_resident": shard_alg * resident / max(int(rep1["cycles"]), 1) / 1e9,
-            "frac_of_hbm_peak_resident": shard_alg * resident / max(int(rep1["cycles"]), 1) / 1e9 / HBM_PEAK_GBPS,
-        },
     }
+    out.update(full_figures)
     if rank == 0:
-        if not args.no_reference_example and world == 1 and not args.batch:
+        if args.full and not args.no_reference_example and world == 1 and not args.batch:
             # BASELINE configs[1] taken literally (single shard, the reference's example input through the re-stated
             # finalization guest, tests/guests_finalization.py): whole-call latency, and proofs/hour with three handles
             from tools import bench_reference_guest
 
             out["reference_example"] = bench_reference_guest.measure(reps=5, handles=8)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(stdin_buf, args.cpu_sizes)
         print(json.dumps(out), flush=True)
     prover.pk_free(pk)

@@ -161,7 +161,7 @@ def test_finalization_guest_with_sha_precompiles(gpu):
 
 def test_bench_batch_mode_line():
     """bench.py --batch (BASELINE configs[4], replicas only) end to end, small B"""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "2", "--steps", "1", "--warmup", "0", "--no-cpu-baseline"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "2", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])

@@ -3,8 +3,8 @@
 
   python tools/collect_profiles.py TAG STATS_DIR FETCH_DIR WRITE_DIR N_PROOFS_PMC
 
-STATS_DIR  : rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --no-cpu-baseline
-FETCH_DIR  : rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -- python3 bench.py --no-cpu-baseline --steps 1 --warmup 0
+STATS_DIR  : rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --no-cpu-baseline
+FETCH_DIR  : rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -- python3 bench.py --full --no-cpu-baseline --steps 1 --warmup 0
 WRITE_DIR  : same with --pmc WRITE_SIZE (separate pass, as MI355X_MICROARCH.md prescribes)
 N_PROOFS_PMC: proofs of the bench shard in each PMC process (1 verified + warm-up + timed + 1 end-to-end + 2 profiled)
 
