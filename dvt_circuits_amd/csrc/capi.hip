@@ -160,6 +160,11 @@ int dvt_prover_create(const char *cfg_json, dvt_prover **out) {
     p->log_shard = (uint32_t)cfg_int(cfg_json, "log_shard_size", 21);
     p->keep_phase1 = cfg_int(cfg_json, "keep_phase1", 1) != 0;
     p->exec_threads = (uint32_t)std::max(0, cfg_int(cfg_json, "exec_threads", 0));
+    p->eng.parts_parallel_log = cfg_int(cfg_json, "parts_parallel_log", (int)PARTS_PARALLEL_LOG);
+    if (p->eng.parts_parallel_log < -1 || p->eng.parts_parallel_log > (int)PARTS_PARALLEL_LOG) {
+        delete p;
+        return fail(nullptr, DVT_ERR_INPUT, "parts_parallel_log must be -1..%u", PARTS_PARALLEL_LOG);
+    }
     if (p->log_shard < 4 || p->log_shard > 22) { delete p; return fail(nullptr, DVT_ERR_INPUT, "log_shard_size must be 4..22"); }
     if (p->cfg.num_queries == 0 || p->cfg.num_queries > 1024 || p->cfg.pow_bits > 30) {
         delete p;

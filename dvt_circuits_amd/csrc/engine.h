@@ -170,6 +170,9 @@ class Engine {
     std::string err;
     StageTimes times;
     bool profile = false;
+    // tables of at most 2^parts_parallel_log rows take the part-parallel K4 / K5 launches (stark.cuh); -1 = none.
+    // At most PARTS_PARALLEL_LOG: the d_parts scratch is sized for that height.
+    int parts_parallel_log = (int)PARTS_PARALLEL_LOG;
 
     hipError_t init(int dev);
     void shutdown();

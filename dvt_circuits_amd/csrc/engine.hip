@@ -587,7 +587,7 @@ bool Engine::prove_shard(const ProvingKey &pk, const std::vector<ChipTrace> &tra
         uint32_t *totals, *scan_scratch;
         ALLOC(totals, uint32_t, 4 * s.n);
         PermArgs pa{s.main, s.prep, d_pub, s.perm, totals, d_beta, d_beta_f64, perm_alpha, s.log_n};
-        if (s.log_n <= PARTS_PARALLEL_LOG) pa.partial = d_parts;   // (tall tables: measured, no gain - 68.14 against 68.09 M cycles/s)
+        if ((int)s.log_n <= parts_parallel_log) pa.partial = d_parts;   // (tall tables: measured, no gain - 68.14 against 68.09 M cycles/s)
         HIPCHK(s.d->launch_perm(stream, pa));
         ALLOC(scan_scratch, uint32_t, prefix_sum_scratch_words(4, s.n));
         HIPCHK(launch_prefix_sum_columns(stream, totals, 4, s.n, scan_scratch));
@@ -645,7 +645,7 @@ bool Engine::prove_shard(const ProvingKey &pk, const std::vector<ChipTrace> &tra
         qa.log_n = s.log_n;
         qa.tabs = tabs;
         qa.sel = selector_table(qa);
-        if (s.log_n <= PARTS_PARALLEL_LOG) qa.partial = d_parts;
+        if ((int)s.log_n <= parts_parallel_log) qa.partial = d_parts;
         HIPCHK(s.d->launch_quotient(stream, qa));
         HIPCHK(lde(s.quot, d_scratch, s.quot_lde, 4, s.log_n, 1));
         HIPCHK(lde(s.quot + 4 * s.n, d_scratch, s.quot_lde + 8 * s.n, 4, s.log_n, 2));

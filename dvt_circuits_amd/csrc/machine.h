@@ -79,7 +79,7 @@ hipError_t launch_quotient_t(hipStream_t st, const QuotientArgs &a) {
     size_t m = (size_t)2 << a.log_n;
     constexpr int NP = Air::N_PARTS + (Air::N_INTERACTIONS > 0 ? Air::N_LPARTS : 0);
     if constexpr (NP > 2 && NP <= PARTS_MAX && Air::MAIN_W >= 128) {   // (the wide chips: the others' groups are few and short)
-        if (a.partial && a.log_n <= PARTS_PARALLEL_LOG) {
+        if (a.partial) {
             quotient_parts_kernel<Air><<<dim3((unsigned)((m + 255) / 256), NP), 256, 0, st>>>(a);
             sum_parts_kernel<0><<<(unsigned)((4 * m + 255) / 256), 256, 0, st>>>(a.partial, NP, 4 * m, a.out);
             return hipGetLastError();

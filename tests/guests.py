@@ -1338,3 +1338,72 @@ def u256_ops(bad=None):
         exp += words_of(x * y % (m or 1 << 256), 8)
     _finish(a, out, 32 * len(cases))
     return a.elf(), b"".join(struct.pack("<I", v) for v in exp)
+
+
+TALL_CHIPS = ("fp_op", "fp2_op", "bls_g1", "secp_k1", "u256_mul")
+
+
+def tall_precompiles(chip, calls=(1 << 15) + 8):
+    """One precompile called `calls` times in a loop (8 calls per iteration), so that the chip's table in a single shard is
+    taller than 2^15 rows (one row per call) and K4 / K5 take the row-parallel launches (dvt_circuits_amd/csrc/machine.h)
+    instead of the part-parallel ones of short tables.  a0 / a1 stay loaded across the calls (ECALL leaves them alone).
+      bls_g1 / secp_k1: P <- P + G chained from 2G, every eighth call P <- 2P;
+      fp_op / fp2_op:   x <- x * y, with x <- x + y and x <- x - y in between;
+      u256_mul:         x <- x * y mod m on the BLS12-381 scalar field.
+    Returns (elf, expected result bytes): the final operand goes to fd 1, its checksum() to the public values."""
+    assert chip in TALL_CHIPS and calls % 8 == 0
+    a = Asm()
+    if chip in ("bls_g1", "secp_k1"):
+        G, mod, W, c_add, c_dbl = ((BLS_G1, BLS_P, 12, SYS_BLS12381_ADD, SYS_BLS12381_DOUBLE) if chip == "bls_g1" else
+                                   (SECP_G, SECP_P, 8, SYS_SECP256K1_ADD, SYS_SECP256K1_DOUBLE))
+        pw = lambda pt: words_of(pt[0], W) + words_of(pt[1], W)
+        x = ec_double(G, mod)
+        codes = [c_add] * 7 + [c_dbl]
+        xw, yw = pw(x), pw(G)
+        for _ in range(calls // 8):
+            for _ in range(7):
+                assert x[0] != G[0]           # ADD of P = +-G would trap
+                x = ec_add(x, G, mod)
+            x = ec_double(x, mod)
+        res = pw(x)
+    elif chip in ("fp_op", "fp2_op"):
+        p = BLS_P
+        base = SYS_BLS12381_FP_ADD if chip == "fp_op" else SYS_BLS12381_FP2_ADD
+        codes = [base + 2, base, base + 2, base + 1] * 2          # mul, add, mul, sub
+        if chip == "fp_op":
+            x, y = (p * 7) // 11, 0x1234567 << 300 | 0xABCDEF
+            f = {0: lambda u: (u + y) % p, 1: lambda u: (u - y) % p, 2: lambda u: u * y % p}
+            xw, yw = words_of(x, 12), words_of(y, 12)
+        else:
+            x, y = ((p * 7) // 11, (p + 1) // 2), (0x1234567 << 300 | 0xABCDEF, p - 2)
+            f = {0: lambda u: ((u[0] + y[0]) % p, (u[1] + y[1]) % p), 1: lambda u: ((u[0] - y[0]) % p, (u[1] - y[1]) % p),
+                 2: lambda u: ((u[0] * y[0] - u[1] * y[1]) % p, (u[0] * y[1] + u[1] * y[0]) % p)}
+            xw, yw = words_of(x[0], 12) + words_of(x[1], 12), words_of(y[0], 12) + words_of(y[1], 12)
+        for _ in range(calls // 8):
+            for c in codes:
+                x = f[c - base](x)
+        res = words_of(x, 12) if chip == "fp_op" else words_of(x[0], 12) + words_of(x[1], 12)
+    else:
+        x, y, m = (1 << 255) - 19, 0xC0FFEE << 200 | 12345, BLS_R
+        codes = [SYS_UINT256_MUL] * 8
+        xw, yw = words_of(x, 8), words_of(y, 8) + words_of(m, 8)
+        for _ in range(calls):
+            x = x * y % m
+        res = words_of(x, 8)
+    out = a.dword("out", xw + [0] * 4)
+    yp = a.dword("y", yw)
+    a.li("a0", out)
+    a.li("a1", yp)
+    a.li("s0", calls // 8)
+    a.label("tall")
+    for c in codes:
+        if c == SYS_BLS12381_DOUBLE or c == SYS_SECP256K1_DOUBLE:
+            a.li("a1", 0)
+        a.li("t0", c)
+        a.ecall()
+        if c == SYS_BLS12381_DOUBLE or c == SYS_SECP256K1_DOUBLE:
+            a.li("a1", yp)
+    a.addi("s0", "s0", -1)
+    a.bne("s0", "zero", "tall")
+    _finish(a, out, 4 * len(res))
+    return a.elf(), b"".join(struct.pack("<I", v) for v in res)

@@ -57,3 +57,28 @@ def test_k0_device_traces_equal_host_traces(which, log_shard):
     p.job_free(job)
     p.pk_free(pk)
     p.close()
+
+
+def test_k0_tall_bigop_table_equals_host_rows():
+    """k0_bigop_rows_kernel with more than 2^15 calls of one precompile in a shard (a 2^16-row bls_g1 table), against the
+    product's host-side expansion (the Python model is too slow at this size; it covers the same rows on the short guests
+    above)"""
+    from dvt_circuits_amd import capi
+
+    elf, _ = guests.tall_precompiles("bls_g1")
+    p = capi.Prover('{"fri_queries": 8, "pow_bits": 4, "log_shard_size": 17}')
+    pk, _ = p.setup(elf)
+    job, rep = p.prepare(pk, [])
+    assert p.job_shards(job) == 1
+    host, hpubs, _ = capi.rv32_debug_traces(elf, [], 17, 0)
+    dev, dpubs = p.debug_device_traces(pk, job, 0)
+    assert (dpubs == hpubs).all() and len(host) == len(dev)
+    assert any(h["chip_id"] == 11 and h["log_n"] >= 16 for h in host)
+    for h, d in zip(host, dev):
+        assert h["chip_id"] == d["chip_id"] and h["log_n"] == d["log_n"]
+        diff = np.argwhere(h["main"] != d["main"])
+        detail = [(int(c), int(r), int(h["main"][c, r]), int(d["main"][c, r])) for c, r in diff[:12]]
+        assert diff.size == 0, f"chip {h['chip_id']}: {len(diff)} mismatches, first (col,row,host,dev): {detail}"
+    p.job_free(job)
+    p.pk_free(pk)
+    p.close()

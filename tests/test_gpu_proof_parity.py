@@ -34,9 +34,20 @@ def split_container(proof: bytes):
     return ec, pv, shards
 
 
+_oracle_cache = {}
+
+
 def oracle_prove_execution(elf, stdin, log_shard):
     """the oracle side end to end: the traces come from the oracle's own guest machine + row expansion
-    (oracle/rv32_model.py), not from the product's executor"""
+    (oracle/rv32_model.py), not from the product's executor.  Deterministic, so its result is kept for the session:
+    other files check other prover configurations against the same executions."""
+    key = (bytes(elf), tuple(bytes(b) for b in stdin), log_shard)
+    if key not in _oracle_cache:
+        _oracle_cache[key] = _oracle_prove_execution(elf, stdin, log_shard)
+    return list(_oracle_cache[key])
+
+
+def _oracle_prove_execution(elf, stdin, log_shard):
     from oracle import rv32_model
 
     run = rv32_model.Run(elf, stdin, log_shard)

@@ -175,3 +175,55 @@ def test_merkle_full_size_root_of_subtrees(gpu, oracle):
     while len(cur) > 1:
         cur = [oracle.compress(cur[i], cur[i + len(cur) // 2]) for i in range(len(cur) // 2)]
     assert (layers[-1] == cur[0]).all()
+
+
+# K8: the FRI fold (dvt_stage_fri_fold) against the oracle's restatement (oracle/stark_oracle.c orc_fri_fold), word for
+# word.  log_m 1: one output, no twiddle; 9 / 10: exactly one / two 256-thread blocks; 23: the entry's maximum.
+@pytest.mark.parametrize("log_m", [1, 2, 8, 9, 10, 17, 23])
+@pytest.mark.parametrize("with_ro", [False, True])
+def test_fri_fold_matches_oracle(gpu, oracle, log_m, with_ro):
+    from tests import _oracle_prover
+
+    lib = _oracle_prover._lib(oracle)
+    u32p = _oracle_prover.u32p
+    rng = np.random.default_rng(10 * log_m + with_ro)
+    m = 1 << log_m
+    v = rng.integers(0, P, (m, 4), dtype=np.uint32)
+    v[0], v[-1] = 0, P - 1                                          # edge values in both halves
+    v[m // 2 - 1, :2], v[m // 2, 2:] = P - 1, 0
+    ro = rng.integers(0, P, (m // 2, 4), dtype=np.uint32) if with_ro else None
+    if with_ro:
+        ro[0], ro[-1] = P - 1, 0
+    t_v = dev(v)
+    gpu.to_internal(t_v)
+    t_ro = None
+    if with_ro:
+        t_ro = dev(ro)
+        gpu.to_internal(t_ro)
+    betas = [rng.integers(0, P, 4, dtype=np.uint32), np.array([0, 0, 0, 0], np.uint32), np.array([1, 0, 0, 0], np.uint32),
+             np.array([P - 1, 0, 1, P - 1], np.uint32), np.array([P - 1] * 4, np.uint32)]
+    for beta in betas if log_m < 17 else betas[:2]:
+        t_out = dev(np.zeros((m // 2, 4), np.uint32))
+        gpu.fri_fold(t_v, t_out, beta.tolist(), log_m, t_ro)
+        gpu.from_internal(t_out)
+        gpu.sync()
+        want = np.zeros((m // 2, 4), np.uint32)
+        lib.orc_fri_fold(v.ctypes.data_as(u32p), log_m, np.ascontiguousarray(beta).ctypes.data_as(u32p),
+                         ro.ctypes.data_as(u32p) if with_ro else None, want.ctypes.data_as(u32p))
+        got = host(t_out).reshape(-1, 4)
+        bad = np.nonzero((got != want).any(axis=1))[0]
+        assert bad.size == 0, f"beta {beta.tolist()}: {bad.size} of {m // 2} outputs differ, first at {int(bad[0])}: {got[bad[0]].tolist()} != {want[bad[0]].tolist()}"
+
+
+def test_fri_fold_rejects_bad_arguments(gpu):
+    import ctypes
+
+    from dvt_circuits_amd import capi
+
+    # buffers sized for the largest log_m passed, so that a missing check could not write out of bounds
+    t_v, t_out = dev(np.zeros(4 << 24, np.uint32)), dev(np.zeros(2 << 24, np.uint32))
+    for log_m, beta in ((0, [1, 2, 3, 4]), (24, [1, 2, 3, 4]), (4, [1, P, 3, 4]), (4, [0, 0, 0, P])):
+        b = (ctypes.c_uint32 * 4)(*beta)
+        rc = gpu.lib.dvt_stage_fri_fold(gpu.h, t_v.data_ptr(), t_out.data_ptr(), None, b, log_m)
+        assert rc == capi.DVT_ERR_INPUT, (log_m, beta, rc)
+    gpu.sync()
