@@ -72,6 +72,10 @@ def load():
     lib.dvt_stage_merkle_commit.argtypes = [vp, C.POINTER(DevMatrix), sz, vp]
     lib.dvt_stage_poseidon2_permute.argtypes = [vp, vp, sz]
     lib.dvt_stage_fri_fold.argtypes = [vp, vp, vp, vp, u32p, u32]
+    lib.dvt_stage_logup_running_sum.argtypes = [vp, vp, vp, u32, u32p]
+    lib.dvt_stage_open.argtypes = [vp, C.POINTER(DevMatrix), sz, u32p, u32p]
+    lib.dvt_stage_reduced_opening.argtypes = [vp, C.POINTER(vp), u32, u32, u32, u32p, u32p, u32p, u32p, vp]
+    lib.dvt_stage_pow_grind.argtypes = [vp, u32p, u32, u32, u32p]
     lib.dvt_machine_setup.argtypes = [vp, C.c_char_p, C.POINTER(HostTrace), sz, C.POINTER(vp), C.POINTER(u8p), C.POINTER(sz)]
     lib.dvt_pk_free.argtypes = [vp, vp]
     lib.dvt_pk_free.restype = None
@@ -318,6 +322,47 @@ class Prover:
         assert t_v.numel() == 4 << log_m and t_out.numel() == 2 << log_m
         b = (C.c_uint32 * 4)(*[int(x) for x in beta])
         self.check(self.lib.dvt_stage_fri_fold(self.h, t_v.data_ptr(), t_out.data_ptr(), t_ro.data_ptr() if t_ro is not None else None, b, log_m))
+
+    def logup_running_sum(self, t_totals, t_phi, log_n):
+        """K4 tail: t_totals [4][2^log_n] (overwritten by its prefix sums) -> t_phi; returns the cumulative sum (canonical)."""
+        assert t_totals.numel() == 4 << log_n and t_phi.numel() == 4 << log_n
+        cum = (C.c_uint32 * 4)()
+        self.check(self.lib.dvt_stage_logup_running_sum(self.h, t_totals.data_ptr(), t_phi.data_ptr(), log_n, cum))
+        return list(cum)
+
+    def open(self, mats, z):
+        """K6: mats = list of (tensor [width][height], width, log_height) of one height; returns [columns][2][4] canonical
+        words: each column's value at z and at z * w_n."""
+        arr = (DevMatrix * len(mats))()
+        for i, (t, w, lh) in enumerate(mats):
+            assert t.numel() == w << lh
+            arr[i] = DevMatrix(t.data_ptr(), w, lh)
+        ncols = sum(w for _, w, _ in mats)
+        out = np.zeros((max(ncols, 1), 2, 4), np.uint32)
+        zz = (C.c_uint32 * 4)(*[int(x) for x in z])
+        self.check(self.lib.dvt_stage_open(self.h, arr, len(mats), zz, out.ctypes.data_as(u32p)))
+        return out[:ncols]
+
+    def reduced_opening(self, cols, n_two, log_m, alpha, open_local, open_next, zeta, t_out):
+        """K7: cols = list of device columns (tensors of 2^log_m words), the first n_two opened at two points;
+        open_local [n_all][4] / open_next [n_two][4] canonical; t_out [2^log_m][4]."""
+        assert all(t.numel() == 1 << log_m for t in cols) and t_out.numel() == 4 << log_m
+        n_all = len(cols)
+        ptrs = (C.c_void_p * max(n_all, 1))(*[t.data_ptr() for t in cols])
+        ol = np.ascontiguousarray(np.asarray(open_local, np.uint32).reshape(-1, 4)) if n_all else np.zeros((1, 4), np.uint32)
+        on = np.ascontiguousarray(np.asarray(open_next, np.uint32).reshape(-1, 4)) if n_two else np.zeros((1, 4), np.uint32)
+        assert ol.shape[0] >= n_all and on.shape[0] >= n_two
+        a = (C.c_uint32 * 4)(*[int(x) for x in alpha])
+        ze = (C.c_uint32 * 4)(*[int(x) for x in zeta])
+        self.check(self.lib.dvt_stage_reduced_opening(self.h, ptrs, n_two, n_all, log_m, a, ol.ctypes.data_as(u32p),
+                                                      on.ctypes.data_as(u32p), ze, t_out.data_ptr()))
+
+    def pow_grind(self, state, pos, bits):
+        """K9: the smallest proof-of-work witness for 16 canonical state words, the witness in word pos."""
+        st = (C.c_uint32 * 16)(*[int(x) for x in state])
+        w = C.c_uint32()
+        self.check(self.lib.dvt_stage_pow_grind(self.h, st, pos, bits, C.byref(w)))
+        return w.value
 
     # ---- machine level
     def machine_setup(self, machine: str, prep):

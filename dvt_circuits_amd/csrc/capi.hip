@@ -269,6 +269,127 @@ int dvt_stage_fri_fold(dvt_prover *p, const uint32_t *d_v, uint32_t *d_out, cons
     return DVT_OK;
 }
 
+// device scratch of a stage entry point from the handle's buffer cache, given back at scope exit (stream-ordered: the next
+// user of a cached buffer runs on the same stream)
+struct StageBuf {
+    DevPool &pool;
+    void *ptr = nullptr;
+    ~StageBuf() { pool.free(ptr); }
+};
+static bool ext_from_canonical(const uint32_t w[4], Fp4 *out) {
+    for (int k = 0; k < 4; k++) {
+        if (w[k] >= P) return false;
+        out->c[k] = Fp::from_canonical(w[k]);
+    }
+    return true;
+}
+static bool overlap(const void *a, const void *b, size_t bytes) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + bytes && y < x + bytes;
+}
+constexpr size_t STAGE_MAX_COLS = 1u << 16;   // column pointers and alpha powers of one call go through the 16 MB upload ring
+
+int dvt_stage_logup_running_sum(dvt_prover *p, uint32_t *d_totals, uint32_t *d_phi, uint32_t log_n, uint32_t cum[4]) {
+    if (!p || !d_totals || !d_phi || !cum) return fail(p, DVT_ERR_INPUT, "null argument");
+    if (log_n > 22) return fail(p, DVT_ERR_INPUT, "log_n %u > 22", log_n);
+    const size_t n = (size_t)1 << log_n;
+    if (overlap(d_totals, d_phi, 16 * n)) return fail(p, DVT_ERR_INPUT, "totals and phi overlap");
+    std::lock_guard<std::mutex> lk(p->mu);
+    HIP_TRY(p, hipSetDevice(p->eng.device));
+    StageBuf scratch{p->eng.pool}, d_cum{p->eng.pool};
+    HIP_TRY(p, p->eng.pool.alloc_bytes(&scratch.ptr, prefix_sum_scratch_words(4, n) * 4));
+    HIP_TRY(p, p->eng.pool.alloc_bytes(&d_cum.ptr, 16));
+    uint32_t w[4];
+    if (!p->eng.logup_running_sum(d_totals, static_cast<uint32_t *>(scratch.ptr), d_phi, log_n, static_cast<uint32_t *>(d_cum.ptr)) ||
+        !p->eng.download(w, d_cum.ptr, sizeof w))
+        return fail(p, DVT_ERR_DEVICE, "%s", p->eng.err.c_str());
+    for (int k = 0; k < 4; k++) cum[k] = Fp::raw(w[k]).canonical();
+    return DVT_OK;
+}
+
+int dvt_stage_open(dvt_prover *p, const dvt_dev_matrix *mats, size_t n, const uint32_t z[4], uint32_t *out) {
+    if (!p || !mats || !n || !z || !out) return fail(p, DVT_ERR_INPUT, "null argument");
+    const uint32_t log_n = mats[0].log_height;
+    if (log_n > 22) return fail(p, DVT_ERR_INPUT, "log_height %u > 22", log_n);
+    std::vector<uint64_t> ptrs;
+    for (size_t i = 0; i < n; i++) {
+        if (mats[i].log_height != log_n) return fail(p, DVT_ERR_INPUT, "matrices of different heights");
+        if (mats[i].width && !mats[i].d_data) return fail(p, DVT_ERR_INPUT, "null matrix data");
+        if (ptrs.size() + mats[i].width > STAGE_MAX_COLS) return fail(p, DVT_ERR_INPUT, "more than %zu columns", STAGE_MAX_COLS);
+        for (uint32_t c = 0; c < mats[i].width; c++) ptrs.push_back((uint64_t)(uintptr_t)(mats[i].d_data + ((size_t)c << log_n)));
+    }
+    Fp4 zz;
+    if (!ext_from_canonical(z, &zz)) return fail(p, DVT_ERR_INPUT, "z not canonical");
+    const uint32_t width = (uint32_t)ptrs.size();
+    if (!width) return DVT_OK;
+    std::lock_guard<std::mutex> lk(p->mu);
+    HIP_TRY(p, hipSetDevice(p->eng.device));
+    Engine &e = p->eng;
+    StageBuf w{e.pool}, partial{e.pool}, res{e.pool};
+    HIP_TRY(p, e.pool.alloc_bytes(&w.ptr, sizeof(Fp4) << log_n));
+    HIP_TRY(p, e.pool.alloc_bytes(&partial.ptr, sizeof(Fp4) * open_row_blocks(log_n) * width * 2));
+    HIP_TRY(p, e.pool.alloc_bytes(&res.ptr, sizeof(Fp4) * width * 2));
+    auto d_cols = reinterpret_cast<const uint32_t *const *>(e.upload(ptrs.data(), ptrs.size() * 8));
+    if (!d_cols) return fail(p, DVT_ERR_DEVICE, "%s", e.err.c_str());
+    Fp4 scale;
+    if (!e.open_point(zz, log_n, static_cast<Fp4 *>(w.ptr), &scale)) return fail(p, DVT_ERR_DEVICE, "%s", e.err.c_str());
+    HIP_TRY(p, launch_open_columns(e.stream, d_cols, width, log_n, static_cast<Fp4 *>(w.ptr), static_cast<Fp4 *>(partial.ptr),
+                                   static_cast<Fp4 *>(res.ptr)));
+    std::vector<Fp4> h(2 * (size_t)width);
+    if (!e.download(h.data(), res.ptr, h.size() * sizeof(Fp4))) return fail(p, DVT_ERR_DEVICE, "%s", e.err.c_str());
+    for (size_t i = 0; i < h.size(); i++) {
+        const Fp4 v = h[i] * scale;
+        for (int k = 0; k < 4; k++) out[4 * i + k] = v.c[k].canonical();
+    }
+    return DVT_OK;
+}
+
+int dvt_stage_reduced_opening(dvt_prover *p, const uint32_t *const *cols, uint32_t n_two, uint32_t n_all, uint32_t log_m,
+                              const uint32_t alpha[4], const uint32_t *open_local, const uint32_t *open_next, const uint32_t zeta[4],
+                              uint32_t *d_out) {
+    if (!p || !cols || !alpha || !open_local || (n_two && !open_next) || !zeta || !d_out) return fail(p, DVT_ERR_INPUT, "null argument");
+    if (log_m < 1 || log_m > 23) return fail(p, DVT_ERR_INPUT, "log_m out of range");
+    if (n_all < 1 || n_all > STAGE_MAX_COLS || n_two > n_all) return fail(p, DVT_ERR_INPUT, "n_two %u / n_all %u out of range", n_two, n_all);
+    Fp4 al, ze;
+    if (!ext_from_canonical(alpha, &al) || !ext_from_canonical(zeta, &ze)) return fail(p, DVT_ERR_INPUT, "alpha or zeta not canonical");
+    std::vector<uint64_t> ptrs(n_all);
+    std::vector<Fp4> local(n_all), next(n_two);
+    for (uint32_t c = 0; c < n_all; c++) {
+        if (!cols[c]) return fail(p, DVT_ERR_INPUT, "null column %u", c);
+        ptrs[c] = (uint64_t)(uintptr_t)cols[c];
+        if (!ext_from_canonical(open_local + 4 * (size_t)c, &local[c]) || (c < n_two && !ext_from_canonical(open_next + 4 * (size_t)c, &next[c])))
+            return fail(p, DVT_ERR_INPUT, "opened value of column %u not canonical", c);
+    }
+    std::lock_guard<std::mutex> lk(p->mu);
+    HIP_TRY(p, hipSetDevice(p->eng.device));
+    Engine &e = p->eng;
+    std::vector<Fp4> apow;
+    std::vector<double> apow_d;
+    fri_alpha_powers(al, n_all, &apow, &apow_d);
+    auto d_apow = reinterpret_cast<const double *>(e.upload(apow_d.data(), apow_d.size() * sizeof(double)));
+    auto d_cols = reinterpret_cast<const uint32_t *const *>(d_apow ? e.upload(ptrs.data(), ptrs.size() * 8) : nullptr);
+    if (!d_cols || !e.reduced_opening(d_cols, n_two, n_all, log_m, apow, d_apow, local.data(), next.data(), ze, reinterpret_cast<Fp4 *>(d_out)))
+        return fail(p, DVT_ERR_DEVICE, "%s", e.err.c_str());
+    return DVT_OK;
+}
+
+int dvt_stage_pow_grind(dvt_prover *p, const uint32_t state[16], uint32_t pos, uint32_t bits, uint32_t *witness) {
+    if (!p || !state || !witness) return fail(p, DVT_ERR_INPUT, "null argument");
+    if (pos >= 8) return fail(p, DVT_ERR_INPUT, "pos %u >= 8", pos);
+    if (bits > 30) return fail(p, DVT_ERR_INPUT, "bits %u > 30", bits);
+    uint32_t st16[16];
+    for (int k = 0; k < 16; k++) {
+        if (state[k] >= P) return fail(p, DVT_ERR_INPUT, "state not canonical");
+        st16[k] = Fp::from_canonical(state[k]).v;
+    }
+    std::lock_guard<std::mutex> lk(p->mu);
+    HIP_TRY(p, hipSetDevice(p->eng.device));
+    StageBuf found{p->eng.pool};
+    HIP_TRY(p, p->eng.pool.alloc_bytes(&found.ptr, 4));
+    if (!p->eng.pow_grind(st16, pos, bits, static_cast<uint32_t *>(found.ptr), witness)) return fail(p, DVT_ERR_DEVICE, "%s", p->eng.err.c_str());
+    return DVT_OK;
+}
+
 // ------------------------------------------------------------------ machine level
 int dvt_machine_setup(dvt_prover *p, const char *machine, const dvt_host_trace *prep, size_t nprep, dvt_pk **pk_out,
                       uint8_t **vk, size_t *vk_len) {

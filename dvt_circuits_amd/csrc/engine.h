@@ -197,6 +197,23 @@ class Engine {
     // LDEs and the tree stay in HBM (hipMalloc'ed into *keep) for prove_shard(..., cached = keep)
     bool commit_main_root(const ProvingKey &pk, const std::vector<ChipTrace> &traces, Digest *root, MainCache *keep = nullptr);
 
+    // ---- host side of the K4 running sum, K6, K7 and the K9 grind: prove_shard and the stage entry points (capi.hip) both
+    // go through these.  Device words are in Montgomery form.
+    // K4 tail: d_totals ([4][2^log_n] row totals) is overwritten by its inclusive prefix sums S; d_phi ([4][2^log_n])
+    // receives phi[r] = S[r-1] - r S[n-1] / n and cum_out (device-writable, may be null) the four words of S[n-1].
+    // d_scratch holds prefix_sum_scratch_words(4, 2^log_n) words.
+    bool logup_running_sum(uint32_t *d_totals, uint32_t *d_scratch, uint32_t *d_phi, uint32_t log_n, uint32_t *cum_out);
+    // K6: the weights of the point z over H (2^log_n rows) into d_w ([2^log_n]); *scale = (z^n - 1) / n, the factor that
+    // turns the sums of launch_open_columns into p(z) and p(z w_n)
+    bool open_point(Fp4 z, uint32_t log_n, Fp4 *d_w, Fp4 *scale);
+    // K7: the FRI input d_out ([2^log_m]) of the n_all LDE columns d_cols of one height, the first n_two opened at zeta and
+    // zeta w_{m/2}.  apow / d_apow: fri_alpha_powers of at least n_all columns; local [n_all] and next [n_two]: the opened values.
+    bool reduced_opening(const uint32_t *const *d_cols, uint32_t n_two, uint32_t n_all, uint32_t log_m, const std::vector<Fp4> &apow,
+                         const double *d_apow, const Fp4 *local, const Fp4 *next, Fp4 zeta, Fp4 *d_out);
+    // K9: the smallest w such that the permutation of st16 (Montgomery words) with word pos = w has (word 7 mod 2^bits) == 0,
+    // in batches of increasing candidates; d_found: one device word of scratch
+    bool pow_grind(const uint32_t st16[16], uint32_t pos, uint32_t bits, uint32_t *d_found, uint32_t *witness);
+
     Arena arena;
     DevPool pool;
     // K5 selector tables, one per trace height this prover has seen ([3][2N] words each, stark.cuh QuotientArgs::sel)
@@ -213,6 +230,10 @@ class Engine {
     size_t ring_bytes = 0, ring_pos = 0;
     bool fail(const char *fmt, ...);
 };
+
+// K7 batching powers alpha^0 .. alpha^n_cols (alpha^n_cols weighs the second point), and the same as [n_cols + 1][4]
+// centred canonical doubles: the operand of reduced_opening_kernel
+void fri_alpha_powers(Fp4 alpha, size_t n_cols, std::vector<Fp4> *pows, std::vector<double> *pows_f64);
 #endif
 
 }  // namespace dvt

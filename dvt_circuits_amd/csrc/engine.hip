@@ -289,6 +289,53 @@ std::vector<Fp4> ext_powers(Fp4 base, size_t n, bool from_one) {
     for (size_t i = 0; i < n; i++) { v[i] = x; x = x * base; }
     return v;
 }
+}  // namespace
+
+void fri_alpha_powers(Fp4 alpha, size_t n_cols, std::vector<Fp4> *pows, std::vector<double> *pows_f64) {
+    *pows = ext_powers(alpha, n_cols + 1, true);
+    pows_f64->resize(4 * pows->size());
+    for (size_t c = 0; c < pows->size(); c++)
+        for (int k = 0; k < 4; k++) (*pows_f64)[4 * c + k] = centred_canonical((*pows)[c].c[k]);
+}
+
+bool Engine::logup_running_sum(uint32_t *d_totals, uint32_t *d_scratch, uint32_t *d_phi, uint32_t log_n, uint32_t *cum_out) {
+    HIPCHK(launch_prefix_sum_columns(stream, d_totals, 4, (size_t)1 << log_n, d_scratch));
+    HIPCHK(launch_phi_from_prefix_sums(stream, d_totals, d_phi, log_n, cum_out));
+    return true;
+}
+bool Engine::open_point(Fp4 z, uint32_t log_n, Fp4 *d_w, Fp4 *scale) {
+    HIPCHK(launch_open_weights(stream, tabs, z, log_n, d_w));
+    const size_t n = (size_t)1 << log_n;
+    *scale = (pow(z, n) - Fp::one()) * inv(Fp::from_canonical((uint32_t)(n % P)));
+    return true;
+}
+bool Engine::reduced_opening(const uint32_t *const *d_cols, uint32_t n_two, uint32_t n_all, uint32_t log_m, const std::vector<Fp4> &apow,
+                             const double *d_apow, const Fp4 *local, const Fp4 *next, Fp4 zeta, Fp4 *d_out) {
+    if (apow.size() <= n_all || n_two > n_all) return fail("reduced opening: %u columns, %u at two points, %zu powers", n_all, n_two, apow.size());
+    // sum_c alpha^c p_c(zeta) over all columns, and alpha^c p_c(zeta_next) over the two-point columns (which come first)
+    Fp4 sz_all = Fp4::zero(), sz_two = Fp4::zero();
+    for (uint32_t c = 0; c < n_all; c++) sz_all += apow[c] * local[c];
+    for (uint32_t c = 0; c < n_two; c++) sz_two += apow[c] * next[c];
+    const Fp4 zeta_next = zeta * two_adic_generator(log_m - 1);   // the trace domain has half the height of its LDE
+    HIPCHK(launch_reduced_opening(stream, tabs, d_cols, n_two, n_all, log_m, d_apow, sz_all, sz_two, zeta, zeta_next, apow[n_all], d_out));
+    return true;
+}
+bool Engine::pow_grind(const uint32_t st16[16], uint32_t pos, uint32_t bits, uint32_t *d_found, uint32_t *witness) {
+    uint32_t found = 0xffffffffu;
+    // batches of 4 x the expected number of tries (the smallest witness is wanted, so batches go in order): the first
+    // one succeeds with probability 1 - e^-4; a fixed 2^22-candidate batch cost 0.6 ms at 16 bits for nothing
+    const uint32_t batch = bits + 2 >= 22 ? 1u << 22 : (bits + 2 < 12 ? 1u << 12 : 1u << (bits + 2));
+    for (uint32_t base = 0; found == 0xffffffffu && base < P - batch; base += batch) {
+        HIPCHK(hipMemsetAsync(d_found, 0xff, 4, stream));
+        HIPCHK(launch_pow_grind(stream, st16, pos, bits, base, batch, d_found));
+        if (!download(&found, d_found, 4)) return false;
+    }
+    if (found == 0xffffffffu) return fail("prove: no proof-of-work witness found");
+    *witness = found;
+    return true;
+}
+
+namespace {
 struct EventTimer {
     hipEvent_t a = nullptr, b = nullptr;
     hipStream_t st;
@@ -590,11 +637,10 @@ bool Engine::prove_shard(const ProvingKey &pk, const std::vector<ChipTrace> &tra
         if ((int)s.log_n <= parts_parallel_log) pa.partial = d_parts;   // (tall tables: measured, no gain - 68.14 against 68.09 M cycles/s)
         HIPCHK(s.d->launch_perm(stream, pa));
         ALLOC(scan_scratch, uint32_t, prefix_sum_scratch_words(4, s.n));
-        HIPCHK(launch_prefix_sum_columns(stream, totals, 4, s.n, scan_scratch));
         // the cumulative sum is only needed for the transcript, after the permutation tree: the kernel writes its four
         // words into the tail of the pinned staging buffer, read after the next synchronisation
         uint32_t *cw = reinterpret_cast<uint32_t *>(h_down + DOWN_BYTES - 4096) + 4 * n_cumsum++;
-        HIPCHK(launch_phi_from_prefix_sums(stream, totals, s.perm + (bw - 4) * s.n, s.log_n, cw));
+        if (!logup_running_sum(totals, scan_scratch, s.perm + (bw - 4) * s.n, s.log_n, cw)) return false;
         HIPCHK(lde(s.perm, d_scratch, s.perm_lde, (uint32_t)bw, s.log_n, 0));
         mats.push_back({s.perm_lde, (uint32_t)bw, s.log_n + 1});
         perm_hmax = std::max(perm_hmax, s.log_n + 1);
@@ -719,10 +765,9 @@ bool Engine::prove_shard(const ProvingKey &pk, const std::vector<ChipTrace> &tra
             o.chip_id = (uint32_t)s.id;
             o.log_n = s.log_n;
             o.cumsum = s.cumsum;
-            Fp ninv = inv(Fp::from_canonical((uint32_t)(s.n % P)));
             // trace matrices: point zeta over H
-            HIPCHK(launch_open_weights(stream, tabs, zeta, s.log_n, d_w));
-            Fp4 scale = (pow(zeta, s.n) - Fp::one()) * ninv;
+            Fp4 scale;
+            if (!open_point(zeta, s.log_n, d_w, &scale)) return false;
             if (s.d->prep_w && !note(s.prep, s.d->prep_w, scale, &o.prep_l, &o.prep_n)) return false;
             if (!note(s.main, s.d->main_w, scale, &o.main_l, &o.main_n)) return false;
             if (s.d->perm_ext_w && !note(s.perm, 4 * s.d->perm_ext_w, scale, &o.perm_l, &o.perm_n)) return false;
@@ -732,8 +777,8 @@ bool Engine::prove_shard(const ProvingKey &pk, const std::vector<ChipTrace> &tra
             for (int c = 0; c < 2; c++) {
                 Fp sc = c == 0 ? g : g * two_adic_generator(s.log_n + 1);
                 Fp4 y = zeta * inv(sc);
-                HIPCHK(launch_open_weights(stream, tabs, y, s.log_n, d_w));
-                Fp4 qs = (pow(y, s.n) - Fp::one()) * ninv;
+                Fp4 qs;
+                if (!open_point(y, s.log_n, d_w, &qs)) return false;
                 if (!note(s.quot + (size_t)4 * c * s.n, 4, qs, &quot_vals[2 * k + c], nullptr) || !open_noted(s)) return false;
             }
         }
@@ -800,33 +845,32 @@ bool Engine::prove_shard(const ProvingKey &pk, const std::vector<ChipTrace> &tra
             cols_by_h[h] = fri_columns(m, refs, h, &n_two_by_h[h]);
             max_cols_h = std::max(max_cols_h, cols_by_h[h].size());
         }
-        std::vector<Fp4> apow = ext_powers(alpha_fri, max_cols_h + 1, true);
-        std::vector<double> apow_d(4 * apow.size());
-        for (size_t c = 0; c < apow.size(); c++)
-            for (int k = 0; k < 4; k++) apow_d[4 * c + k] = centred_canonical(apow[c].c[k]);
+        std::vector<Fp4> apow;
+        std::vector<double> apow_d;
+        fri_alpha_powers(alpha_fri, max_cols_h, &apow, &apow_d);
         const double *d_apow = reinterpret_cast<const double *>(upload(apow_d.data(), apow_d.size() * sizeof(double)));
         if (!d_apow) return false;
         // pointer tables of every height in one upload (see the openings above), then the launches
         std::vector<uint64_t> all_ptrs;
         std::vector<size_t> ptr_at(hmax + 1, 0);
-        std::vector<Fp4> sz_all_h(hmax + 1, Fp4::zero()), sz_two_h(hmax + 1, Fp4::zero());
+        // the values every column of a height was opened to, at zeta and (two-point columns, which come first) at the next point
+        std::vector<std::vector<Fp4>> local_h(hmax + 1), next_h(hmax + 1);
         for (uint32_t h = 1; h <= hmax; h++) {
             auto &cols = cols_by_h[h];
             ptr_at[h] = all_ptrs.size();
-            Fp4 sz_all = Fp4::zero(), sz_two = Fp4::zero();
             for (size_t c = 0; c < cols.size(); c++) {
                 const ColRef &r = cols[c];
                 const TreeMat &tmx = tree_mats[r.tree][r.mat];
                 all_ptrs.push_back((uint64_t)(uintptr_t)(tmx.lde + ((size_t)r.col << h)));
                 const ChipOpening &o = pf.chips[r.chip_pos];
                 const std::vector<Fp4> &loc = r.tree == 0 ? o.prep_l : r.tree == 1 ? o.main_l : r.tree == 2 ? o.perm_l : o.quot;
-                sz_all += apow[c] * loc[r.col];
+                local_h[h].push_back(loc[r.col]);
                 if (r.tree < 3) {
                     const std::vector<Fp4> &nx = r.tree == 0 ? o.prep_n : r.tree == 1 ? o.main_n : o.perm_n;
-                    sz_two += apow[c] * nx[r.col];
+                    next_h[h].push_back(nx[r.col]);
                 }
             }
-            sz_all_h[h] = sz_all; sz_two_h[h] = sz_two;
+            if (next_h[h].size() != n_two_by_h[h]) return fail("prove: internal error, FRI column order");
         }
         auto d_all_cols = reinterpret_cast<const uint32_t *const *>(upload(all_ptrs.data(), all_ptrs.size() * 8));
         if (!d_all_cols) return false;
@@ -834,9 +878,9 @@ bool Engine::prove_shard(const ProvingKey &pk, const std::vector<ChipTrace> &tra
             auto &cols = cols_by_h[h];
             if (cols.empty()) continue;
             ALLOC(ro[h], Fp4, (size_t)1 << h);
-            Fp4 zeta_next = zeta * two_adic_generator(h - 1);
-            HIPCHK(launch_reduced_opening(stream, tabs, d_all_cols + ptr_at[h], n_two_by_h[h], (uint32_t)cols.size(), h, d_apow, sz_all_h[h], sz_two_h[h],
-                                          zeta, zeta_next, apow[cols.size()], ro[h]));
+            if (!reduced_opening(d_all_cols + ptr_at[h], n_two_by_h[h], (uint32_t)cols.size(), h, apow, d_apow, local_h[h].data(),
+                                 next_h[h].data(), zeta, ro[h]))
+                return false;
         }
     }
 
@@ -898,16 +942,8 @@ bool Engine::prove_shard(const ProvingKey &pk, const std::vector<ChipTrace> &tra
         uint32_t pos = (uint32_t)ch.input.size();
         uint32_t *d_found;
         ALLOC(d_found, uint32_t, 1);
-        uint32_t found = 0xffffffffu;
-        // batches of 4 x the expected number of tries (the smallest witness is wanted, so batches go in order): the first
-        // one succeeds with probability 1 - e^-4; a fixed 2^22-candidate batch cost 0.6 ms at 16 bits for nothing
-        const uint32_t batch = cfg.pow_bits + 2 >= 22 ? 1u << 22 : (cfg.pow_bits + 2 < 12 ? 1u << 12 : 1u << (cfg.pow_bits + 2));
-        for (uint32_t base = 0; found == 0xffffffffu && base < P - batch; base += batch) {
-            HIPCHK(hipMemsetAsync(d_found, 0xff, 4, stream));
-            HIPCHK(launch_pow_grind(stream, st16, pos, cfg.pow_bits, base, batch, d_found));
-            if (!download(&found, d_found, 4)) return false;
-        }
-        if (found == 0xffffffffu) return fail("prove: no proof-of-work witness found");
+        uint32_t found;
+        if (!pow_grind(st16, pos, cfg.pow_bits, d_found, &found)) return false;
         pf.pow_witness = Fp::from_canonical(found);
         if (!ch.check_witness(cfg.pow_bits, pf.pow_witness)) return fail("prove: internal error, grind witness rejected by transcript");
     }

@@ -98,6 +98,30 @@ int dvt_stage_poseidon2_permute(dvt_prover *p, uint32_t *d_states, size_t n);
 int dvt_stage_fri_fold(dvt_prover *p, const uint32_t *d_v, uint32_t *d_out, const uint32_t *d_ro,
                        const uint32_t beta[4], uint32_t log_m);
 
+/* The stages below run the prover's own host code (the same calls as a shard proof).  Field values
+ * passed through host arrays are canonical words; extension elements are 4 words.  log_n <= 22. */
+/* K4 tail: the LogUp running-sum column.  d_totals [4][2^log_n] holds one F_p^4 row total per row
+ * and is overwritten by its inclusive prefix sums S; d_phi [4][2^log_n] (not overlapping d_totals)
+ * receives phi[r] = S[r-1] - r S[n-1] / n (phi[0] = 0) and cum the cumulative sum S[n-1].
+ * Synchronises the stream. */
+int dvt_stage_logup_running_sum(dvt_prover *p, uint32_t *d_totals, uint32_t *d_phi, uint32_t log_n, uint32_t cum[4]);
+/* K6: the values at z and at z*w_n of the polynomials that interpolate the columns of n matrices
+ * of one height 2^log_height over the subgroup H (at most 65536 columns in all), opened by one launch
+ * as a shard proof opens a chip's matrices.  out [columns][2][4], column order of mats.  Synchronises
+ * the stream. */
+int dvt_stage_open(dvt_prover *p, const dvt_dev_matrix *mats, size_t n, const uint32_t z[4], uint32_t *out);
+/* K7: the FRI input of one height.  cols: host array of n_all (1..65536) device columns of
+ * 2^log_m words (1 <= log_m <= 23), the LDE on 31*<w_m>; the first n_two were opened at zeta and
+ * zeta * w_{m/2}.  open_local [n_all][4], open_next [n_two][4]; d_out [2^log_m][4] receives
+ *   sum_c alpha^c (p_c(x) - p_c(zeta)) / (x - zeta)
+ *   + alpha^n_all sum_{c < n_two} alpha^c (p_c(x) - p_c(zeta w_{m/2})) / (x - zeta w_{m/2}). */
+int dvt_stage_reduced_opening(dvt_prover *p, const uint32_t *const *cols, uint32_t n_two, uint32_t n_all, uint32_t log_m,
+                              const uint32_t alpha[4], const uint32_t *open_local, const uint32_t *open_next,
+                              const uint32_t zeta[4], uint32_t *d_out);
+/* K9: the smallest proof-of-work witness w: the Poseidon2 permutation of state with state[pos] = w
+ * (pos < 8) has word 7 divisible by 2^bits (bits <= 30).  Synchronises the stream. */
+int dvt_stage_pow_grind(dvt_prover *p, const uint32_t state[16], uint32_t pos, uint32_t bits, uint32_t *witness);
+
 /* ------------------------------------------------- machine-level entry points
  * A "machine" is a fixed list of chips (AIRs) compiled into the library:
  * "toy" (engine unit tests) and "rv32" (the RISC-V core machine).  Traces are

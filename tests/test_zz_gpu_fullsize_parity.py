@@ -121,3 +121,30 @@ def test_full_size_shard_with_precompile_chips_equals_oracle():
     _same(gpu[0], cpu[0], "shard 0")
     p.pk_free(pk)
     p.close()
+
+
+def test_one_shard_at_the_maximum_size_equals_oracle():
+    """log_shard_size 22, the largest the prover, the setup and the verifier accept: the two-shard guest above in ONE shard
+    of ~2^22 cycles, so that the LDE of 2^22-row tables (the generic NTT kernel), Merkle trees of 2^23 leaves, FRI from
+    log_m 23, the openings of 2^22 rows and the 2^22-row running sum all enter a proof that must equal the oracle's"""
+    import bench
+    from dvt_circuits_amd import capi
+
+    buf = bench.workload_stdin()
+    consts = bench.fit_constants(buf, 2)
+    elf = guests.dkg_like("finalization", *consts)
+    p = capi.Prover('{"log_shard_size": 22}')
+    pk, vk = p.setup(elf)
+    proof, rep = p.prove_core(pk, [buf])
+    assert (2 << 21) - 65536 < rep["cycles"] <= 1 << 22
+    ok, ec, pv, why = capi.verify(vk, proof)
+    assert ok and pv == guests.dkg_like_expected(buf, "finalization", *consts), why
+    ec, pv2, gpu = _gpu_shards(proof)
+    assert len(gpu) == 1
+    chips, pubs, n_shards = capi.rv32_debug_traces(elf, [buf], 22)
+    assert n_shards == 1 and max(c["main"].shape[1] for c in chips) == 1 << 22
+    gc = _oracle_prover.global_challenges(_oracle_prover.prep_root_of(chips), [_oracle_prover.main_root(chips) + [int(x) for x in pubs]])
+    shard_cpu, _ = _oracle_prover.prove_shard("rv32", chips, pubs, 100, 16, perm_challenges=gc)
+    _same(gpu[0], shard_cpu, "shard 0")
+    p.pk_free(pk)
+    p.close()
