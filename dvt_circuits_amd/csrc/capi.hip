@@ -12,6 +12,7 @@
 #include <cstring>
 #include <deque>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -23,8 +24,16 @@
 
 using namespace dvt;
 
+constexpr int MAX_LANES = 3;
+struct Phase2Pipe;
+
 struct dvt_prover {
-    Engine eng;
+    Engine eng;                       // lane 0: phase 1, the stage entry points and (with one lane) phase 2
+    // Further prover lanes (phase 2 only): own stream, ring, arena, pool and tables each, sharing the proving key's read-only
+    // device buffers.  Created on the first job that holds at least two shards.
+    int lanes = 2;
+    std::unique_ptr<Engine> more[MAX_LANES - 1];
+    std::unique_ptr<Phase2Pipe> pipe;   // the phase-2 pipeline of the current job, if one runs (see Phase2Pipe)
     StarkConfig cfg;
     uint32_t log_shard = 21;          // cycles per shard = 2^log_shard (SP1's default shard size)
     uint64_t max_cycles = 1ull << 36;
@@ -40,6 +49,57 @@ struct dvt_prover {
     std::string err;
     std::mutex mu;
 };
+
+// Phase 2 of a job's shards, run ahead of the caller on the prover lanes: one worker thread per lane takes the next shard in
+// job order (that shard then stays on that lane), at most `lanes` shards past the last one the caller asked for.  Worker
+// threads never touch p->err: each slot keeps its own result.  Everything here is guarded by mu; the API thread holds the
+// prover's mutex while it creates, claims from or drains the pipeline.
+struct Phase2Pipe {
+    struct Slot {
+        size_t shard = 0;               // index into the job's shards
+        int state = 0;                  // 0 waiting, 1 running, 2 done
+        bool claimed = false;
+        int rc = 0;
+        std::string err;
+        std::vector<uint32_t> words;
+    };
+    dvt_job *job = nullptr;
+    const dvt_pk *pk = nullptr;
+    uint32_t ch[8] = {};                // the challenges, canonical
+    std::vector<Slot> slots;            // in proving order
+    size_t next = 0;                    // the next slot a worker starts
+    size_t limit = 0;                   // slots below this may start
+    bool stop = false, failed = false;
+    std::mutex mu;
+    std::condition_variable cv;
+    std::vector<std::thread> workers;
+};
+
+static Engine &lane_engine(dvt_prover *p, int k) { return k == 0 ? p->eng : *p->more[k - 1]; }
+
+// Stops the pipeline (running shards finish, nothing new starts; unclaimed results are discarded) and waits for every lane's
+// stream.  With first_err != nullptr: the error of the lowest failed slot, if any.  Caller holds p->mu.
+static int pipe_drain(dvt_prover *p, std::string *first_err = nullptr) {
+    if (!p->pipe) return DVT_OK;
+    Phase2Pipe &pp = *p->pipe;
+    {
+        std::lock_guard<std::mutex> lk(pp.mu);
+        pp.stop = true;
+        pp.cv.notify_all();
+    }
+    for (auto &t : pp.workers) t.join();
+    int rc = DVT_OK;
+    for (auto &s : pp.slots)
+        if (s.state == 2 && s.rc && !s.claimed) {
+            rc = s.rc;
+            if (first_err) *first_err = s.err;
+            break;
+        }
+    for (int k = 0; k < p->lanes; k++)
+        if (k == 0 || p->more[k - 1]) (void)hipStreamSynchronize(lane_engine(p, k).stream);
+    p->pipe.reset();
+    return rc;
+}
 struct dvt_pk {
     ProvingKey key;
     bool is_rv32 = false;
@@ -154,6 +214,7 @@ int dvt_prover_create(const char *cfg_json, dvt_prover **out) {
     if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
         return fail(nullptr, DVT_ERR_DEVICE, "device %d is %s; this library is built for gfx950 only", dev, prop.gcnArchName);
     dvt_prover *p = new dvt_prover();
+    p->eng.device = dev;
     p->cfg.num_queries = (uint32_t)cfg_int(cfg_json, "fri_queries", 100);
     p->cfg.pow_bits = (uint32_t)cfg_int(cfg_json, "pow_bits", 16);
     p->eng.profile = cfg_int(cfg_json, "profile", 0) != 0;
@@ -164,6 +225,19 @@ int dvt_prover_create(const char *cfg_json, dvt_prover **out) {
     if (p->eng.parts_parallel_log < -1 || p->eng.parts_parallel_log > (int)PARTS_PARALLEL_LOG) {
         delete p;
         return fail(nullptr, DVT_ERR_INPUT, "parts_parallel_log must be -1..%u", PARTS_PARALLEL_LOG);
+    }
+    {
+        // phase-2 lanes: the config key, else DVT_LANES (same-process A/B measurements), else 2; profile mode times stages
+        // with events on one stream and keeps one lane
+        const char *env = getenv("DVT_LANES");
+        const int dflt = env && *env ? atoi(env) : 2;
+        p->lanes = cfg_int(cfg_json, "lanes", dflt);
+        if (p->lanes < 1 || p->lanes > MAX_LANES) {
+            const int bad = p->lanes;
+            delete p;
+            return fail(nullptr, DVT_ERR_INPUT, "lanes must be 1..%d (got %d)", MAX_LANES, bad);
+        }
+        if (p->eng.profile) p->lanes = 1;
     }
     if (p->log_shard < 4 || p->log_shard > 22) { delete p; return fail(nullptr, DVT_ERR_INPUT, "log_shard_size must be 4..22"); }
     if (p->cfg.num_queries == 0 || p->cfg.num_queries > 1024 || p->cfg.pow_bits > 30) {
@@ -184,11 +258,23 @@ int dvt_prover_create(const char *cfg_json, dvt_prover **out) {
 void dvt_prover_destroy(dvt_prover *p) {
     if (!p) return;
     (void)hipSetDevice(p->eng.device);
+    {
+        std::lock_guard<std::mutex> lk(p->mu);
+        (void)pipe_drain(p);
+    }
     if (p->copy_stream) { (void)hipStreamSynchronize(p->copy_stream); (void)hipStreamDestroy(p->copy_stream); }
     for (auto b : p->pinned) (void)hipHostFree(b);
     if (p->aux_pinned) (void)hipHostFree(p->aux_pinned);
+    for (auto &e : p->more)
+        if (e) e->shutdown();
     p->eng.shutdown();
     delete p;
+}
+
+// entry points that do not otherwise take the prover's mutex: stop a running phase-2 pipeline before using lane 0
+static void quiesce(dvt_prover *p) {
+    std::lock_guard<std::mutex> lk(p->mu);
+    (void)pipe_drain(p);
 }
 
 const char *dvt_last_error(const dvt_prover *p) { return p ? p->err.c_str() : g_create_err.c_str(); }
@@ -197,6 +283,7 @@ void *dvt_stream(dvt_prover *p) { return p ? (void *)p->eng.stream : nullptr; }
 
 int dvt_sync(dvt_prover *p) {
     if (!p) return DVT_ERR_INPUT;
+    quiesce(p);
     HIP_TRY(p, hipSetDevice(p->eng.device));
     HIP_TRY(p, hipStreamSynchronize(p->eng.stream));
     return DVT_OK;
@@ -204,12 +291,14 @@ int dvt_sync(dvt_prover *p) {
 
 int dvt_dev_to_internal(dvt_prover *p, uint32_t *d, size_t n) {
     if (!p || (!d && n)) return fail(p, DVT_ERR_INPUT, "null argument");
+    quiesce(p);
     HIP_TRY(p, hipSetDevice(p->eng.device));
     HIP_TRY(p, launch_to_internal(p->eng.stream, d, n));
     return DVT_OK;
 }
 int dvt_dev_from_internal(dvt_prover *p, uint32_t *d, size_t n) {
     if (!p || (!d && n)) return fail(p, DVT_ERR_INPUT, "null argument");
+    quiesce(p);
     HIP_TRY(p, hipSetDevice(p->eng.device));
     HIP_TRY(p, launch_from_internal(p->eng.stream, d, n));
     return DVT_OK;
@@ -221,6 +310,7 @@ int dvt_stage_coset_lde(dvt_prover *p, uint32_t *d_in, uint32_t *d_scratch, uint
     if (width && (!d_in || !d_out)) return fail(p, DVT_ERR_INPUT, "null matrix");
     if (log_n > 22) return fail(p, DVT_ERR_INPUT, "log_n %u > 22", log_n);
     if (shift_mode > 2) return fail(p, DVT_ERR_INPUT, "shift_mode %u", shift_mode);
+    quiesce(p);
     HIP_TRY(p, hipSetDevice(p->eng.device));
     HIP_TRY(p, launch_coset_lde(p->eng.stream, p->eng.tabs, d_in, d_scratch, d_out, width, log_n, shift_mode));
     return DVT_OK;
@@ -236,6 +326,7 @@ int dvt_stage_merkle_commit(dvt_prover *p, const dvt_dev_matrix *mats, size_t n,
     if (!p) return DVT_ERR_INPUT;
     if (!mats || !n || !d_digests) return fail(p, DVT_ERR_INPUT, "null argument");
     std::lock_guard<std::mutex> lk(p->mu);
+    (void)pipe_drain(p);
     HIP_TRY(p, hipSetDevice(p->eng.device));
     std::vector<Engine::DevMat> dm;
     for (size_t i = 0; i < n; i++) {
@@ -249,6 +340,7 @@ int dvt_stage_merkle_commit(dvt_prover *p, const dvt_dev_matrix *mats, size_t n,
 
 int dvt_stage_poseidon2_permute(dvt_prover *p, uint32_t *d_states, size_t n) {
     if (!p || (!d_states && n)) return fail(p, DVT_ERR_INPUT, "null argument");
+    quiesce(p);
     HIP_TRY(p, hipSetDevice(p->eng.device));
     HIP_TRY(p, launch_poseidon2_permute(p->eng.stream, d_states, n));
     return DVT_OK;
@@ -263,6 +355,7 @@ int dvt_stage_fri_fold(dvt_prover *p, const uint32_t *d_v, uint32_t *d_out, cons
         if (beta[k] >= P) return fail(p, DVT_ERR_INPUT, "beta not canonical");
         b.c[k] = Fp::from_canonical(beta[k]);
     }
+    quiesce(p);
     HIP_TRY(p, hipSetDevice(p->eng.device));
     HIP_TRY(p, launch_fri_fold(p->eng.stream, p->eng.tabs, reinterpret_cast<const Fp4 *>(d_v), reinterpret_cast<Fp4 *>(d_out),
                                reinterpret_cast<const Fp4 *>(d_ro), b, log_m));
@@ -295,6 +388,7 @@ int dvt_stage_logup_running_sum(dvt_prover *p, uint32_t *d_totals, uint32_t *d_p
     const size_t n = (size_t)1 << log_n;
     if (overlap(d_totals, d_phi, 16 * n)) return fail(p, DVT_ERR_INPUT, "totals and phi overlap");
     std::lock_guard<std::mutex> lk(p->mu);
+    (void)pipe_drain(p);
     HIP_TRY(p, hipSetDevice(p->eng.device));
     StageBuf scratch{p->eng.pool}, d_cum{p->eng.pool};
     HIP_TRY(p, p->eng.pool.alloc_bytes(&scratch.ptr, prefix_sum_scratch_words(4, n) * 4));
@@ -323,6 +417,7 @@ int dvt_stage_open(dvt_prover *p, const dvt_dev_matrix *mats, size_t n, const ui
     const uint32_t width = (uint32_t)ptrs.size();
     if (!width) return DVT_OK;
     std::lock_guard<std::mutex> lk(p->mu);
+    (void)pipe_drain(p);
     HIP_TRY(p, hipSetDevice(p->eng.device));
     Engine &e = p->eng;
     StageBuf w{e.pool}, partial{e.pool}, res{e.pool};
@@ -361,6 +456,7 @@ int dvt_stage_reduced_opening(dvt_prover *p, const uint32_t *const *cols, uint32
             return fail(p, DVT_ERR_INPUT, "opened value of column %u not canonical", c);
     }
     std::lock_guard<std::mutex> lk(p->mu);
+    (void)pipe_drain(p);
     HIP_TRY(p, hipSetDevice(p->eng.device));
     Engine &e = p->eng;
     std::vector<Fp4> apow;
@@ -383,6 +479,7 @@ int dvt_stage_pow_grind(dvt_prover *p, const uint32_t state[16], uint32_t pos, u
         st16[k] = Fp::from_canonical(state[k]).v;
     }
     std::lock_guard<std::mutex> lk(p->mu);
+    (void)pipe_drain(p);
     HIP_TRY(p, hipSetDevice(p->eng.device));
     StageBuf found{p->eng.pool};
     HIP_TRY(p, p->eng.pool.alloc_bytes(&found.ptr, 4));
@@ -395,6 +492,7 @@ int dvt_machine_setup(dvt_prover *p, const char *machine, const dvt_host_trace *
                       uint8_t **vk, size_t *vk_len) {
     if (!p || !pk_out) return fail(p, DVT_ERR_INPUT, "null argument");
     std::lock_guard<std::mutex> lk(p->mu);
+    (void)pipe_drain(p);
     const MachineDesc *m = machine_by_name(machine);
     if (!m) return fail(p, DVT_ERR_INPUT, "unknown machine '%s'", machine ? machine : "(null)");
     std::vector<ChipRef> refs;
@@ -431,6 +529,7 @@ int dvt_machine_setup(dvt_prover *p, const char *machine, const dvt_host_trace *
 void dvt_pk_free(dvt_prover *p, dvt_pk *pk) {
     if (!p || !pk) return;
     std::lock_guard<std::mutex> lk(p->mu);
+    (void)pipe_drain(p);
     p->eng.free_key(&pk->key);
     if (pk->d_instrs) (void)hipFree(pk->d_instrs);
     if (pk->d_prog_row) (void)hipFree(pk->d_prog_row);
@@ -441,6 +540,7 @@ int dvt_machine_prove(dvt_prover *p, const dvt_pk *pk, const dvt_host_trace *mai
                       uint8_t **proof, size_t *proof_len) {
     if (!p || !pk || !main || !nmain || !proof || !proof_len || (npub && !pubs)) return fail(p, DVT_ERR_INPUT, "null argument");
     std::lock_guard<std::mutex> lk(p->mu);
+    (void)pipe_drain(p);
     const MachineDesc *m = pk->key.vk.machine;
     HIP_TRY(p, hipSetDevice(p->eng.device));
     std::vector<uint32_t *> dev(nmain, nullptr);
@@ -591,13 +691,16 @@ struct dvt_job {
     std::vector<uint8_t> public_values;
     size_t n_total = 0, first = 0, stride = 1;   // shards of the execution / which of them this job holds
     std::vector<ShardJob> shards;
-    uint32_t *d_cpu = nullptr, *d_byte = nullptr, *d_prog = nullptr;  // working buffers (largest shard)
-    uint32_t work_log_cpu = 0;
+    struct Work {   // K0 working buffers of one lane (largest shard seen), from that lane's pool
+        uint32_t *d_cpu = nullptr, *d_byte = nullptr, *d_prog = nullptr;
+        uint32_t log_cpu = 0;
+    } work[MAX_LANES];
     size_t byte_words = 0, prog_words = 0;
     double t_exec_wait = 0;   // seconds the GPU thread spent waiting for the executor inside prepare
     ShardJob *at(size_t pos) { return pos >= first && (pos - first) % stride == 0 && (pos - first) / stride < shards.size() ? &shards[(pos - first) / stride] : nullptr; }
 };
 
+// (the caller has drained the phase-2 pipeline: the phase-1 buffers go back to lane 0's pool only after every lane is done)
 static void job_release(dvt_prover *p, dvt_job *j) {
     if (!j) return;
     DevPool &pool = p->eng.pool;
@@ -607,32 +710,59 @@ static void job_release(dvt_prover *p, dvt_job *j) {
         for (uint32_t *d : {s.d_cpu, s.d_byte, s.d_prog}) pool.free(d);
         s.cache.release();
     }
-    pool.free(j->d_cpu);
-    pool.free(j->d_byte);
-    pool.free(j->d_prog);
+    for (int k = 0; k < MAX_LANES; k++) {
+        auto &w = j->work[k];
+        if (!w.d_cpu && !w.d_byte && !w.d_prog) continue;
+        DevPool &lp = lane_engine(p, k).pool;
+        for (uint32_t *d : {w.d_cpu, w.d_byte, w.d_prog}) lp.free(d);
+    }
     delete j;
 }
 
+// A lane's view of the prover for K0 and phase 2: its engine, and an error string of its own (worker threads never write
+// p->err).  The API thread runs lane 0 through the wrappers below, which copy the error into p->err.
+struct LaneCtx {
+    dvt_prover *p;
+    int k;
+    Engine &eng;
+    std::string err;
+};
+static int lfail(LaneCtx &c, int code, const char *fmt, ...) {
+    char buf[600];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    c.err = buf;
+    return code;
+}
+#define HIP_TRY_L(c, expr)                                                                            \
+    do {                                                                                              \
+        hipError_t e_ = (expr);                                                                       \
+        if (e_ != hipSuccess) return lfail(c, DVT_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); \
+    } while (0)
+
 // K0 of a shard (into the shard's own buffers when it has them, else the job's working buffers); fills the chip
 // trace list of that shard.  `reuse`: phase 2 takes the traces phase 1 left behind instead of generating them again.
-static int shard_traces(dvt_prover *p, const dvt_pk *pk, dvt_job *j, ShardJob &s, std::vector<ChipTrace> *traces, bool reuse) {
-    hipStream_t st = p->eng.stream;
+static int shard_traces_on(LaneCtx &c, const dvt_pk *pk, dvt_job *j, ShardJob &s, std::vector<ChipTrace> *traces, bool reuse) {
+    hipStream_t st = c.eng.stream;
+    dvt_job::Work &w = j->work[c.k];
     const MachineDesc *m = machine_rv32();
-    if (!s.d_cpu && (!j->d_cpu || j->work_log_cpu < s.log_n[RV32_CHIP_CPU])) {   // working buffers, sized for the largest shard seen
-        HIP_TRY(p, hipStreamSynchronize(st));
-        for (uint32_t **d : {&j->d_cpu, &j->d_byte, &j->d_prog}) { p->eng.pool.free(*d); *d = nullptr; }
-        j->work_log_cpu = s.log_n[RV32_CHIP_CPU];
-        HIP_TRY(p, p->eng.pool.alloc(&j->d_cpu, ((size_t)RV32_CPU_MAIN_W << j->work_log_cpu) * 4));
-        HIP_TRY(p, p->eng.pool.alloc(&j->d_byte, j->byte_words * 4));
-        HIP_TRY(p, p->eng.pool.alloc(&j->d_prog, j->prog_words * 4));
+    if (!s.d_cpu && (!w.d_cpu || w.log_cpu < s.log_n[RV32_CHIP_CPU])) {   // working buffers, sized for the largest shard seen
+        HIP_TRY_L(c, hipStreamSynchronize(st));
+        for (uint32_t **d : {&w.d_cpu, &w.d_byte, &w.d_prog}) { c.eng.pool.free(*d); *d = nullptr; }
+        w.log_cpu = s.log_n[RV32_CHIP_CPU];
+        HIP_TRY_L(c, c.eng.pool.alloc(&w.d_cpu, ((size_t)RV32_CPU_MAIN_W << w.log_cpu) * 4));
+        HIP_TRY_L(c, c.eng.pool.alloc(&w.d_byte, j->byte_words * 4));
+        HIP_TRY_L(c, c.eng.pool.alloc(&w.d_prog, j->prog_words * 4));
     }
-    uint32_t *cpu = s.d_cpu ? s.d_cpu : j->d_cpu, *byte = s.d_cpu ? s.d_byte : j->d_byte, *prog = s.d_cpu ? s.d_prog : j->d_prog;
+    uint32_t *cpu = s.d_cpu ? s.d_cpu : w.d_cpu, *byte = s.d_cpu ? s.d_byte : w.d_byte, *prog = s.d_cpu ? s.d_prog : w.d_prog;
     if (!(reuse && s.d_cpu && s.traces_valid)) {
         bool ok = hipMemcpyAsync(byte, s.d_aux[RV32_CHIP_BYTE], j->byte_words * 4, hipMemcpyDeviceToDevice, st) == hipSuccess &&
                   hipMemcpyAsync(prog, s.d_aux[RV32_CHIP_PROGRAM], j->prog_words * 4, hipMemcpyDeviceToDevice, st) == hipSuccess &&
                   rv32::launch_k0_cpu_rows(st, s.d_recs, s.n_recs, s.index, s.next_pc, pk->d_instrs, pk->d_prog_row, cpu, s.log_n[RV32_CHIP_CPU], byte, prog) == hipSuccess &&
                   launch_to_internal(st, byte, j->byte_words) == hipSuccess && launch_to_internal(st, prog, j->prog_words) == hipSuccess;
-        if (!ok) return fail(p, DVT_ERR_DEVICE, "trace generation (K0) failed: %s", hipGetErrorString(hipGetLastError()));
+        if (!ok) return lfail(c, DVT_ERR_DEVICE, "trace generation (K0) failed: %s", hipGetErrorString(hipGetLastError()));
         s.traces_valid = s.d_cpu != nullptr;
     }
     traces->clear();
@@ -642,6 +772,13 @@ static int shard_traces(dvt_prover *p, const dvt_pk *pk, dvt_job *j, ShardJob &s
         traces->push_back({c, s.log_n[c], ptr});
     }
     return DVT_OK;
+}
+
+static int shard_traces(dvt_prover *p, const dvt_pk *pk, dvt_job *j, ShardJob &s, std::vector<ChipTrace> *traces, bool reuse) {
+    LaneCtx c{p, 0, p->eng, {}};
+    const int rc = shard_traces_on(c, pk, j, s, traces, reuse);
+    if (rc) p->err = c.err;
+    return rc;
 }
 
 // phase 1 of a shard: K0 + K1..K3 of the main traces -> header
@@ -656,7 +793,14 @@ static int shard_commit(dvt_prover *p, const dvt_pk *pk, dvt_job *j, ShardJob &s
     size_t free_b = 0, total_b = 0;
     if (p->keep_phase1 && !s.cache.tree) { (void)hipMemGetInfo(&free_b, &total_b); free_b += p->eng.pool.cached_bytes; }   // (only the first commit of a shard asks)
     lap("memory asked");
-    MainCache *keep = p->keep_phase1 && (s.cache.tree || free_b > ((size_t)24 << 30)) ? &s.cache : nullptr;
+    // the further lanes' phase-2 arenas are not there yet on the first job: leave room for them (lane 0's arena is the measure
+    // of one), so that the kept caches do not take what the second lane's working set then cannot get
+    size_t lane_room = 0;
+    for (int k = 1; k < p->lanes; k++) {
+        const size_t have = p->more[k - 1] ? p->more[k - 1]->arena.cap : 0;
+        if (p->eng.arena.cap > have) lane_room += p->eng.arena.cap - have;
+    }
+    MainCache *keep = p->keep_phase1 && (s.cache.tree || free_b > ((size_t)24 << 30) + lane_room) ? &s.cache : nullptr;
     if (keep && !s.d_cpu) {
         DevPool &pool = p->eng.pool;
         bool ok = pool.alloc(&s.d_cpu, ((size_t)RV32_CPU_MAIN_W << s.log_n[RV32_CHIP_CPU]) * 4) == hipSuccess && pool.alloc(&s.d_byte, j->byte_words * 4) == hipSuccess &&
@@ -680,22 +824,29 @@ static int shard_commit(dvt_prover *p, const dvt_pk *pk, dvt_job *j, ShardJob &s
 }
 
 // phase 2 of a shard: K0..K9 with the common challenges -> shard proof words
-static int shard_prove(dvt_prover *p, const dvt_pk *pk, dvt_job *j, ShardJob &s, const PermChallenges &gc, std::vector<uint32_t> *words) {
+// (on any lane: the shard's phase-1 buffers came from lane 0's pool and are only read here)
+static int shard_prove_on(LaneCtx &c, const dvt_pk *pk, dvt_job *j, ShardJob &s, const PermChallenges &gc, std::vector<uint32_t> *words) {
     std::vector<ChipTrace> traces;
-    int rc = shard_traces(p, pk, j, s, &traces, s.cache.valid);
+    int rc = shard_traces_on(c, pk, j, s, &traces, s.cache.valid);
     if (rc) return rc;
     ShardProof sp;
-    bool ok = p->eng.prove_shard(pk->key, traces, s.pubs, p->cfg, &sp, &gc, &s.cache);
-    (void)hipStreamSynchronize(p->eng.stream);
+    bool ok = c.eng.prove_shard(pk->key, traces, s.pubs, c.p->cfg, &sp, &gc, &s.cache);
+    (void)hipStreamSynchronize(c.eng.stream);
     s.cache.valid = false;  // the buffers stay for the next commit of this shard (released with the job)
     s.traces_valid = false;
     s.header_valid = false;
-    if (!ok) return fail(p, DVT_ERR_DEVICE, "%s", p->eng.err.c_str());
+    if (!ok) return lfail(c, DVT_ERR_DEVICE, "%s", c.eng.err.c_str());
     WordWriter w;
     w.w.reserve((size_t)1 << 20);  // a shard proof is about 2.4 MB at 100 queries
     write_shard_proof(w, sp);
     *words = std::move(w.w);
     return DVT_OK;
+}
+static int shard_prove(dvt_prover *p, const dvt_pk *pk, dvt_job *j, ShardJob &s, const PermChallenges &gc, std::vector<uint32_t> *words) {
+    LaneCtx c{p, 0, p->eng, {}};
+    const int rc = shard_prove_on(c, pk, j, s, gc, words);
+    if (rc) p->err = c.err;
+    return rc;
 }
 
 // ------------------------------------------------------------------ the prepare pipeline
@@ -1045,6 +1196,103 @@ static std::vector<uint32_t> assemble_container(const dvt_job *j, const std::vec
     return w.w;
 }
 
+// ------------------------------------------------------------------ the phase-2 pipeline (Phase2Pipe)
+// the further lanes' engines, made on the first job that has at least two shards to prove
+static int ensure_lanes(dvt_prover *p) {
+    for (int k = 1; k < p->lanes; k++) {
+        if (p->more[k - 1]) continue;
+        std::unique_ptr<Engine> e(new Engine());
+        e->profile = false;
+        e->parts_parallel_log = p->eng.parts_parallel_log;
+        const hipError_t r = e->init(p->eng.device);
+        if (r != hipSuccess) {
+            e->shutdown();
+            return fail(p, DVT_ERR_DEVICE, "prover lane %d: %s", k, hipGetErrorString(r));
+        }
+        p->more[k - 1] = std::move(e);
+    }
+    return DVT_OK;
+}
+
+static void pipe_worker(dvt_prover *p, Phase2Pipe *pp, PermChallenges gc, int k) {
+    LaneCtx c{p, k, lane_engine(p, k), {}};
+    const hipError_t dev = hipSetDevice(p->eng.device);
+    for (;;) {
+        size_t i;
+        {
+            std::unique_lock<std::mutex> lk(pp->mu);
+            pp->cv.wait(lk, [&] { return pp->stop || pp->failed || pp->next >= pp->slots.size() || pp->next < pp->limit; });
+            if (pp->stop || pp->failed || pp->next >= pp->slots.size()) return;
+            i = pp->next++;
+            pp->slots[i].state = 1;
+        }
+        std::vector<uint32_t> words;
+        c.err.clear();
+        const int rc = dev != hipSuccess ? lfail(c, DVT_ERR_DEVICE, "hipSetDevice: %s", hipGetErrorString(dev))
+                                         : shard_prove_on(c, pp->pk, pp->job, pp->job->shards[pp->slots[i].shard], gc, &words);
+        std::lock_guard<std::mutex> lk(pp->mu);
+        Phase2Pipe::Slot &s = pp->slots[i];
+        s.rc = rc;
+        s.err = std::move(c.err);
+        s.words = std::move(words);
+        s.state = 2;
+        if (rc) pp->failed = true;   // the other lanes stop at their next shard boundary
+        pp->cv.notify_all();
+    }
+}
+
+// Starts the pipeline over the job's shards with a valid header, in job order from shard index k0 (which must be one of
+// them).  Returns DVT_OK with p->pipe set; DVT_OK without a pipeline when there is nothing to run ahead (one lane, or
+// fewer than two such shards).  Caller holds p->mu; no pipeline runs.
+static int pipe_start(dvt_prover *p, const dvt_pk *pk, dvt_job *j, size_t k0, const PermChallenges &gc) {
+    if (p->lanes < 2 || k0 >= j->shards.size() || !j->shards[k0].header_valid) return DVT_OK;
+    std::vector<size_t> order;
+    for (size_t k = k0; k < j->shards.size(); k++)
+        if (j->shards[k].header_valid) order.push_back(k);
+    if (order.size() < 2) return DVT_OK;
+    int rc = ensure_lanes(p);
+    if (rc) return rc;
+    HIP_TRY(p, hipStreamSynchronize(p->eng.stream));   // phase 1 (lane 0) is complete before another lane reads its buffers
+    std::unique_ptr<Phase2Pipe> pp(new Phase2Pipe());
+    pp->job = j;
+    pp->pk = pk;
+    for (int k = 0; k < 4; k++) { pp->ch[k] = gc.alpha.c[k].canonical(); pp->ch[4 + k] = gc.beta.c[k].canonical(); }
+    pp->slots.resize(order.size());
+    for (size_t i = 0; i < order.size(); i++) pp->slots[i].shard = order[i];
+    pp->limit = (size_t)p->lanes;   // (the caller claims slot 0 next)
+    const int n_workers = (int)std::min<size_t>((size_t)p->lanes, order.size());
+    for (int k = 0; k < n_workers; k++) pp->workers.emplace_back(pipe_worker, p, pp.get(), gc, k);
+    p->pipe = std::move(pp);
+    return DVT_OK;
+}
+
+// the slot of job shard index k in the running pipeline, or -1
+static long pipe_slot_of(const Phase2Pipe &pp, size_t k) {
+    for (size_t i = 0; i < pp.slots.size(); i++)
+        if (pp.slots[i].shard == k) return pp.slots[i].claimed ? -1 : (long)i;
+    return -1;
+}
+
+// Waits for a slot's words.  On a failure the pipeline is drained and the error of the lowest failed shard is reported.
+static int pipe_claim(dvt_prover *p, size_t slot, std::vector<uint32_t> *words) {
+    Phase2Pipe &pp = *p->pipe;
+    {
+        std::unique_lock<std::mutex> lk(pp.mu);
+        pp.limit = std::max(pp.limit, slot + (size_t)p->lanes);
+        pp.cv.notify_all();
+        pp.cv.wait(lk, [&] { return pp.slots[slot].state == 2 || (pp.failed && pp.slots[slot].state == 0); });
+        Phase2Pipe::Slot &s = pp.slots[slot];
+        if (s.state == 2 && s.rc == 0) {
+            s.claimed = true;
+            *words = std::move(s.words);
+            return DVT_OK;
+        }
+    }
+    std::string why;
+    const int rc = pipe_drain(p, &why);
+    return fail(p, rc ? rc : DVT_ERR_DEVICE, "%s", rc ? why.c_str() : "phase-2 pipeline stopped");
+}
+
 // both phases on one GPU (no lock); the job must hold every shard of the execution
 static int job_prove(dvt_prover *p, const dvt_pk *pk, dvt_job *j, uint8_t **proof, size_t *proof_len) {
     HIP_TRY(p, hipSetDevice(p->eng.device));
@@ -1060,10 +1308,13 @@ static int job_prove(dvt_prover *p, const dvt_pk *pk, dvt_job *j, uint8_t **proo
     }
     PermChallenges gc = global_challenges(pk->key.vk, headers.data(), n);
     std::vector<std::vector<uint32_t>> shards(n);
+    int rc = pipe_start(p, pk, j, 0, gc);
+    if (rc) return rc;
     for (size_t i = 0; i < n; i++) {
-        int rc = shard_prove(p, pk, j, j->shards[i], gc, &shards[i]);
+        rc = p->pipe ? pipe_claim(p, i, &shards[i]) : shard_prove(p, pk, j, j->shards[i], gc, &shards[i]);
         if (rc) return rc;
     }
+    (void)pipe_drain(p);
     (void)hipStreamSynchronize(p->eng.stream);
     if (!proof) return DVT_OK;  // timing runs may discard the bytes
     *proof = copy_out(assemble_container(j, shards), proof_len);
@@ -1076,6 +1327,7 @@ extern "C" {
 int dvt_setup(dvt_prover *p, const uint8_t *elf, size_t elf_len, dvt_pk **pk_out, uint8_t **vk, size_t *vk_len) {
     if (!p || !elf || !pk_out) return fail(p, DVT_ERR_INPUT, "null argument");
     std::lock_guard<std::mutex> lk(p->mu);
+    (void)pipe_drain(p);
     dvt_pk *pk = new dvt_pk();
     std::string err;
     if (!rv32::load_elf(elf, elf_len, &pk->prog, &err)) { delete pk; return fail(p, DVT_ERR_INPUT, "ELF: %s", err.c_str()); }
@@ -1159,16 +1411,19 @@ int dvt_rv32_prepare_part(dvt_prover *p, const dvt_pk *pk, const dvt_buf *stdin_
     if (!p || !pk || !job || (nbuf && !stdin_bufs)) return fail(p, DVT_ERR_INPUT, "null argument");
     if (!pk->is_rv32) return fail(p, DVT_ERR_INPUT, "proving key was not made by dvt_setup");
     std::lock_guard<std::mutex> lk(p->mu);
+    (void)pipe_drain(p);
     return job_prepare(p, pk, stdin_bufs, nbuf, first, stride, job, report);
 }
 int dvt_rv32_prove_job(dvt_prover *p, const dvt_pk *pk, dvt_job *job, uint8_t **proof, size_t *proof_len) {
     if (!p || !pk || !job || (proof && !proof_len)) return fail(p, DVT_ERR_INPUT, "null argument");
     std::lock_guard<std::mutex> lk(p->mu);
+    (void)pipe_drain(p);
     return job_prove(p, pk, job, proof, proof_len);
 }
 void dvt_job_free(dvt_prover *p, dvt_job *job) {
     if (!p || !job) return;
     std::lock_guard<std::mutex> lk(p->mu);
+    (void)pipe_drain(p);
     (void)hipSetDevice(p->eng.device);
     job_release(p, job);
 }
@@ -1180,6 +1435,7 @@ int dvt_rv32_commit_shard(dvt_prover *p, const dvt_pk *pk, dvt_job *job, size_t 
     ShardJob *s = job->at(shard);
     if (!s) return fail(p, DVT_ERR_INPUT, "shard %zu is not held by this job", shard);
     std::lock_guard<std::mutex> lk(p->mu);
+    (void)pipe_drain(p);
     HIP_TRY(p, hipSetDevice(p->eng.device));
     if (!s->header_valid) {   // (the prepare pipeline already ran phase 1; a second proof of the same job runs it again)
         int rc = shard_commit(p, pk, job, *s);
@@ -1204,15 +1460,31 @@ int dvt_rv32_prove_shard(dvt_prover *p, const dvt_pk *pk, dvt_job *job, size_t s
     ShardJob *s = job->at(shard);
     if (!s) return fail(p, DVT_ERR_INPUT, "shard %zu is not held by this job", shard);
     std::lock_guard<std::mutex> lk(p->mu);
-    HIP_TRY(p, hipSetDevice(p->eng.device));
     PermChallenges gc;
     for (int k = 0; k < 4; k++) {
-        if (challenges[k] >= P || challenges[4 + k] >= P) return fail(p, DVT_ERR_INPUT, "challenge not canonical");
+        if (challenges[k] >= P || challenges[4 + k] >= P) {
+            (void)pipe_drain(p);
+            return fail(p, DVT_ERR_INPUT, "challenge not canonical");
+        }
         gc.alpha.c[k] = Fp::from_canonical(challenges[k]);
         gc.beta.c[k] = Fp::from_canonical(challenges[4 + k]);
     }
+    // phase 2 runs ahead on the prover lanes: the first call of a job starts the pipeline, later calls with the same
+    // challenges collect from it; anything else drains it and takes the one-lane path
+    const size_t k = (size_t)(s - job->shards.data());
+    long slot = -1;
+    if (p->pipe) {
+        if (p->pipe->job == job && p->pipe->pk == pk && !memcmp(p->pipe->ch, challenges, sizeof p->pipe->ch)) slot = pipe_slot_of(*p->pipe, k);
+        if (slot < 0) (void)pipe_drain(p);
+    }
+    HIP_TRY(p, hipSetDevice(p->eng.device));
+    if (!p->pipe) {
+        int rc = pipe_start(p, pk, job, k, gc);
+        if (rc) return rc;
+        if (p->pipe) slot = 0;
+    }
     std::vector<uint32_t> words;
-    int rc = shard_prove(p, pk, job, *s, gc, &words);
+    int rc = slot >= 0 ? pipe_claim(p, (size_t)slot, &words) : shard_prove(p, pk, job, *s, gc, &words);
     if (rc || !proof) return rc;
     *proof = copy_out(words, proof_len);
     return *proof ? DVT_OK : fail(p, DVT_ERR_DEVICE, "out of host memory");
@@ -1234,10 +1506,12 @@ int dvt_prove_core(dvt_prover *p, const dvt_pk *pk, const dvt_buf *stdin_bufs, s
     if (!p || !pk || !proof || !proof_len || (nbuf && !stdin_bufs)) return fail(p, DVT_ERR_INPUT, "null argument");
     if (!pk->is_rv32) return fail(p, DVT_ERR_INPUT, "proving key was not made by dvt_setup");
     std::lock_guard<std::mutex> lk(p->mu);
+    (void)pipe_drain(p);
     dvt_job *j = nullptr;
     int rc = job_prepare(p, pk, stdin_bufs, nbuf, 0, 1, &j, report);
     if (rc) return rc;
     rc = job_prove(p, pk, j, proof, proof_len);
+    (void)pipe_drain(p);
     job_release(p, j);
     return rc;
 }
@@ -1396,6 +1670,7 @@ int dvt_rv32_debug_traces(const uint8_t *elf, size_t elf_len, const dvt_buf *std
 int dvt_rv32_debug_device_traces(dvt_prover *p, const dvt_pk *pk, dvt_job *j, size_t shard, uint32_t **blob, size_t *blob_words) {
     if (!p || !pk || !j || !blob || !blob_words || !j->at(shard)) return fail(p, DVT_ERR_INPUT, "bad argument");
     std::lock_guard<std::mutex> lk(p->mu);
+    (void)pipe_drain(p);
     HIP_TRY(p, hipSetDevice(p->eng.device));
     std::vector<ChipTrace> traces;
     ShardJob &sj = *j->at(shard);

@@ -27,6 +27,8 @@
 // registers, three stages (radix 8) per LDS round trip: a thread gathers the 8
 // words of a group, does 12 butterflies, scatters them back — one barrier per three
 // stages instead of per stage.
+#include <atomic>
+
 #include "kernels.h"
 #include "poseidon2_f64.cuh"
 
@@ -658,12 +660,13 @@ hipError_t launch_coset_lde(hipStream_t st, const NttTables &tabs, uint32_t *d_i
         const uint32_t *p2_in = log_n1 ? d_scratch : d_in;
         uint32_t done = 0;
         if (log_n2 == 12 && width >= 2) {   // column pairs through the two-column kernel
-            static bool attr_set = false;
+            // (atomic: the prover lanes launch from several host threads; setting the attribute twice is harmless)
+            static std::atomic<bool> attr_set{false};
             const size_t lds2 = ((size_t)(2u << log_n2) * 2 + (1u << log_n2)) * 4;   // 64 KB of int2 + 16 KB of twiddles
-            if (!attr_set) {
+            if (!attr_set.load(std::memory_order_acquire)) {
                 hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(lde_block2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
                 if (e != hipSuccess) return e;
-                attr_set = true;
+                attr_set.store(true, std::memory_order_release);
             }
             dim3 grid2(1u << log_n1, width / 2);
             lde_block2_kernel<<<grid2, 512, lds2, st>>>(p2_in, d_out, log_n, log_n1, shift_mode, tabs);

@@ -50,7 +50,11 @@ typedef struct dvt_pk dvt_pk;
  * (0 = from the host's core count).  keep_phase1 = 0 makes phase 2 of a shard recompute K0 and the main-trace commitment
  * instead of keeping them in HBM (about 3 GB per 2^21-cycle shard) between the two phases.  parts_parallel_log: tables of
  * at most 2^parts_parallel_log rows compute their LogUp rows (K4) and quotient (K5) one constraint group per thread, taller
- * ones one row per thread; -1 = never, at most 15 (DVT_ERR_INPUT above).  The proof bytes do not depend on it. */
+ * ones one row per thread; -1 = never, at most 15 (DVT_ERR_INPUT above).  The proof bytes do not depend on it.
+ * "lanes" (1..3, default 2; without the key the environment variable DVT_LANES sets the default; anything else is
+ * DVT_ERR_INPUT): prover lanes that run phase 2 of different shards of one job at the same time, each with its own HIP
+ * stream, device arena and buffer cache.  The further lanes are created on the first job that holds at least two shards;
+ * "profile":1 forces one lane.  The proof bytes do not depend on it. */
 int dvt_prover_create(const char *cfg_json, dvt_prover **out);
 void dvt_prover_destroy(dvt_prover *p);
 /* last error text of this handle (or of the failed create when p == NULL) */
@@ -205,7 +209,14 @@ int dvt_prove_core(dvt_prover *p, const dvt_pk *pk, const dvt_buf *stdin_bufs, s
  *   commit_shard   header of shard i (global position in the execution); phase 1 = K0 + K1..K3 of the
  *                  main traces runs here only if the pipeline's result has been consumed by an earlier proof
  *   challenges     host-only: the common challenges from ALL headers (in shard order)
- *   prove_shard    phase 2 of shard i: K0..K9 with those challenges -> shard proof bytes
+ *   prove_shard    phase 2 of shard i: K0..K9 with those challenges -> shard proof bytes.  With more than one lane
+ *                  the first call of a job starts a pipeline that proves the job's held shards with a valid header, in
+ *                  job order from i, on the lanes, at most `lanes` shards past the last one asked for; the call returns
+ *                  when shard i is done, and later calls with the SAME challenges collect their shard from the pipeline.
+ *                  A call with other challenges, or for a shard the pipeline does not hold, stops it first (unclaimed
+ *                  results are discarded) and then counts as a first call (a shard whose phase-1 result was consumed is
+ *                  proven on lane 0 alone).  dvt_job_free, commit_shard, prepare, the stage entry points, dvt_sync and every
+ *                  other call on the handle stop it too.  An error is that of the lowest failed shard.
  *   assemble       container (what proof.save would write) from the shard proofs, in order
  * dvt_rv32_prove_job runs everything on the handle's GPU; proof may be NULL to discard the bytes. */
 typedef struct dvt_job dvt_job;
