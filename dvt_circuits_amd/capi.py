@@ -12,6 +12,8 @@ LIB_PATH = os.path.join(HERE, "libdvt_prover.so")
 CSRC = os.path.join(HERE, "csrc")
 
 DVT_OK, DVT_ERR_GUEST, DVT_ERR_INPUT, DVT_ERR_DEVICE, DVT_ERR_UNSUPPORTED, DVT_ERR_REJECTED = 0, 1, 2, 3, 4, 5
+PATHS = {"default": 0, "rows": 1, "parts": 2}             # DVT_PATH_* (K4 / K5 launches)
+SELECTORS = {"table": 0, "kernel": 1}                     # DVT_SELECTORS_*
 u32p = C.POINTER(C.c_uint32)
 u8p = C.POINTER(C.c_uint8)
 
@@ -76,6 +78,8 @@ def load():
     lib.dvt_stage_open.argtypes = [vp, C.POINTER(DevMatrix), sz, u32p, u32p]
     lib.dvt_stage_reduced_opening.argtypes = [vp, C.POINTER(vp), u32, u32, u32, u32p, u32p, u32p, u32p, vp]
     lib.dvt_stage_pow_grind.argtypes = [vp, u32p, u32, u32, u32p]
+    lib.dvt_stage_perm.argtypes = [vp, C.c_char_p, u32, vp, vp, u32, u32p, u32p, u32p, u32, vp, u32p]
+    lib.dvt_stage_quotient.argtypes = [vp, C.c_char_p, u32, vp, vp, vp, u32, u32p, u32p, u32p, u32p, u32p, u32, u32, vp]
     lib.dvt_machine_setup.argtypes = [vp, C.c_char_p, C.POINTER(HostTrace), sz, C.POINTER(vp), C.POINTER(u8p), C.POINTER(sz)]
     lib.dvt_pk_free.argtypes = [vp, vp]
     lib.dvt_pk_free.restype = None
@@ -363,6 +367,28 @@ class Prover:
         w = C.c_uint32()
         self.check(self.lib.dvt_stage_pow_grind(self.h, st, pos, bits, C.byref(w)))
         return w.value
+
+    def perm(self, machine, chip, t_main, t_prep, log_n, pubs, perm_alpha, beta, t_perm, path="default"):
+        """K4 of one chip: device matrices in Montgomery form (t_prep / t_perm None when the width is 0); the batch
+        columns and phi go to t_perm; returns the cumulative sum (canonical)."""
+        u4 = lambda v: (C.c_uint32 * 4)(*[int(x) for x in v])
+        pv = (C.c_uint32 * max(len(pubs), 1))(*[int(x) for x in pubs])
+        cum = (C.c_uint32 * 4)()
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        self.check(self.lib.dvt_stage_perm(self.h, machine.encode(), chip, ptr(t_main), ptr(t_prep), log_n, pv, u4(perm_alpha), u4(beta),
+                                           PATHS[path], ptr(t_perm), cum))
+        return list(cum)
+
+    def quotient(self, machine, chip, t_main_lde, t_prep_lde, t_perm_lde, log_n, pubs, perm_alpha, beta, alpha, cum, t_out,
+                 path="default", selectors="table"):
+        """K5 of one chip: LDEs in Montgomery form (None when the width is 0) -> t_out [2][4][2^log_n]."""
+        u4 = lambda v: (C.c_uint32 * 4)(*[int(x) for x in v])
+        pv = (C.c_uint32 * max(len(pubs), 1))(*[int(x) for x in pubs])
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        assert t_out.numel() == 8 << log_n
+        self.check(self.lib.dvt_stage_quotient(self.h, machine.encode(), chip, ptr(t_main_lde), ptr(t_prep_lde), ptr(t_perm_lde), log_n,
+                                               pv, u4(perm_alpha), u4(beta), u4(alpha), u4(cum), PATHS[path], SELECTORS[selectors],
+                                               t_out.data_ptr()))
 
     # ---- machine level
     def machine_setup(self, machine: str, prep):

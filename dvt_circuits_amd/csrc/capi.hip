@@ -376,10 +376,11 @@ static bool ext_from_canonical(const uint32_t w[4], Fp4 *out) {
     }
     return true;
 }
-static bool overlap(const void *a, const void *b, size_t bytes) {
+static bool overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
     const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + bytes && y < x + bytes;
+    return x < y + b_bytes && y < x + a_bytes;
 }
+static bool overlap(const void *a, const void *b, size_t bytes) { return overlap(a, bytes, b, bytes); }
 constexpr size_t STAGE_MAX_COLS = 1u << 16;   // column pointers and alpha powers of one call go through the 16 MB upload ring
 
 int dvt_stage_logup_running_sum(dvt_prover *p, uint32_t *d_totals, uint32_t *d_phi, uint32_t log_n, uint32_t cum[4]) {
@@ -484,6 +485,121 @@ int dvt_stage_pow_grind(dvt_prover *p, const uint32_t state[16], uint32_t pos, u
     StageBuf found{p->eng.pool};
     HIP_TRY(p, p->eng.pool.alloc_bytes(&found.ptr, 4));
     if (!p->eng.pow_grind(st16, pos, bits, static_cast<uint32_t *>(found.ptr), witness)) return fail(p, DVT_ERR_DEVICE, "%s", p->eng.err.c_str());
+    return DVT_OK;
+}
+
+// ---- K4 / K5 of one chip: the argument checks both entries share
+struct ChipStageArgs {
+    const ChipDesc *d = nullptr;
+    std::vector<uint32_t> pub;   // Montgomery words, at least one
+    Fp4 perm_alpha, beta;
+};
+static int chip_stage_args(dvt_prover *p, const char *machine, uint32_t chip, uint32_t log_n, const uint32_t *pub,
+                           const uint32_t perm_alpha[4], const uint32_t beta[4], uint32_t path, ChipStageArgs *out) {
+    const MachineDesc *m = machine_by_name(machine);
+    if (!m) return fail(p, DVT_ERR_INPUT, "unknown machine '%s'", machine ? machine : "(null)");
+    if (chip >= (uint32_t)m->n_chips) return fail(p, DVT_ERR_INPUT, "chip %u out of range (%d chips)", chip, m->n_chips);
+    out->d = &m->chips[chip];
+    if (log_n > 22) return fail(p, DVT_ERR_INPUT, "log_n %u > 22", log_n);
+    if (path > DVT_PATH_PARTS) return fail(p, DVT_ERR_INPUT, "path %u", path);
+    if (path == DVT_PATH_PARTS && log_n > PARTS_PARALLEL_LOG)
+        return fail(p, DVT_ERR_INPUT, "the part-parallel launches take at most 2^%u rows", PARTS_PARALLEL_LOG);
+    if (!perm_alpha || !beta || (out->d->n_pub && !pub)) return fail(p, DVT_ERR_INPUT, "null argument");
+    if (!ext_from_canonical(perm_alpha, &out->perm_alpha) || !ext_from_canonical(beta, &out->beta))
+        return fail(p, DVT_ERR_INPUT, "perm_alpha or beta not canonical");
+    out->pub.assign(std::max(out->d->n_pub, 1), 0);
+    for (int k = 0; k < out->d->n_pub; k++) {
+        if (pub[k] >= P) return fail(p, DVT_ERR_INPUT, "public value %d not canonical", k);
+        out->pub[k] = Fp::from_canonical(pub[k]).v;
+    }
+    return DVT_OK;
+}
+// the part-parallel scratch of a K4 / K5 call, or nullptr (the per-row / per-part launches); words per row of the scratch
+static int chip_stage_parts(dvt_prover *p, uint32_t path, bool has_parts, uint32_t log_n, size_t words_per_row, StageBuf *buf,
+                            uint32_t **d_parts) {
+    *d_parts = nullptr;
+    if (path == DVT_PATH_PARTS && !has_parts) return fail(p, DVT_ERR_INPUT, "this chip has no part-parallel launch");
+    const bool parts = path == DVT_PATH_PARTS || (path == DVT_PATH_DEFAULT && (int)log_n <= p->eng.parts_parallel_log);
+    if (!parts || !has_parts) return DVT_OK;
+    HIP_TRY(p, p->eng.pool.alloc_bytes(&buf->ptr, (size_t)PARTS_MAX * words_per_row * 4 << log_n));
+    *d_parts = static_cast<uint32_t *>(buf->ptr);
+    return DVT_OK;
+}
+
+int dvt_stage_perm(dvt_prover *p, const char *machine, uint32_t chip, const uint32_t *d_main, const uint32_t *d_prep, uint32_t log_n,
+                   const uint32_t *pub, const uint32_t perm_alpha[4], const uint32_t beta[4], uint32_t path, uint32_t *d_perm,
+                   uint32_t cum[4]) {
+    if (!p) return DVT_ERR_INPUT;
+    ChipStageArgs a;
+    if (int rc = chip_stage_args(p, machine, chip, log_n, pub, perm_alpha, beta, path, &a)) return rc;
+    const ChipDesc &d = *a.d;
+    const size_t n = (size_t)1 << log_n, perm_bytes = 16 * (size_t)d.perm_ext_w * n;
+    if (!d_main || (d.prep_w && !d_prep) || (d.perm_ext_w && !d_perm) || !cum) return fail(p, DVT_ERR_INPUT, "null argument");
+    if (d.perm_ext_w && (overlap(d_perm, perm_bytes, d_main, 4 * d.main_w * n) || (d.prep_w && overlap(d_perm, perm_bytes, d_prep, 4 * d.prep_w * n))))
+        return fail(p, DVT_ERR_INPUT, "perm overlaps main or prep");
+    std::lock_guard<std::mutex> lk(p->mu);
+    (void)pipe_drain(p);
+    HIP_TRY(p, hipSetDevice(p->eng.device));
+    Engine &e = p->eng;
+    StageBuf parts{e.pool}, totals{e.pool}, scan{e.pool}, d_cum{e.pool};
+    uint32_t *d_parts;
+    if (int rc = chip_stage_parts(p, path, d.perm_parts, log_n, 4, &parts, &d_parts)) return rc;
+    if (!d.perm_ext_w) {   // no interactions: no permutation trace, cumulative sum 0
+        for (int k = 0; k < 4; k++) cum[k] = 0;
+        return DVT_OK;
+    }
+    HIP_TRY(p, e.pool.alloc_bytes(&totals.ptr, 16 * n));
+    HIP_TRY(p, e.pool.alloc_bytes(&scan.ptr, prefix_sum_scratch_words(4, n) * 4));
+    HIP_TRY(p, e.pool.alloc_bytes(&d_cum.ptr, 16));
+    int n_beta, n_alpha;
+    challenge_power_counts(machine_by_name(machine), &n_beta, &n_alpha);
+    Engine::ChipInputs in{d_main, d.prep_w ? d_prep : nullptr, nullptr, log_n, a.perm_alpha, nullptr, nullptr};
+    in.pub = static_cast<const uint32_t *>(e.upload_vec(a.pub));
+    uint32_t w[4];
+    if (!in.pub || !e.upload_powers(a.beta, n_beta, false, &in.beta_pows, &in.beta_f64) ||
+        !e.perm_chip(d, in, d_parts, static_cast<uint32_t *>(totals.ptr), static_cast<uint32_t *>(scan.ptr), d_perm,
+                     static_cast<uint32_t *>(d_cum.ptr)) ||
+        !e.download(w, d_cum.ptr, sizeof w))
+        return fail(p, DVT_ERR_DEVICE, "%s", e.err.c_str());
+    for (int k = 0; k < 4; k++) cum[k] = Fp::raw(w[k]).canonical();
+    return DVT_OK;
+}
+
+int dvt_stage_quotient(dvt_prover *p, const char *machine, uint32_t chip, const uint32_t *d_main_lde, const uint32_t *d_prep_lde,
+                       const uint32_t *d_perm_lde, uint32_t log_n, const uint32_t *pub, const uint32_t perm_alpha[4],
+                       const uint32_t beta[4], const uint32_t alpha[4], const uint32_t cum[4], uint32_t path, uint32_t selectors,
+                       uint32_t *d_out) {
+    if (!p) return DVT_ERR_INPUT;
+    ChipStageArgs a;
+    if (int rc = chip_stage_args(p, machine, chip, log_n, pub, perm_alpha, beta, path, &a)) return rc;
+    const ChipDesc &d = *a.d;
+    Fp4 al, cs;
+    if (!alpha || !cum) return fail(p, DVT_ERR_INPUT, "null argument");
+    if (!ext_from_canonical(alpha, &al) || !ext_from_canonical(cum, &cs)) return fail(p, DVT_ERR_INPUT, "alpha or cum not canonical");
+    if (selectors > DVT_SELECTORS_IN_KERNEL) return fail(p, DVT_ERR_INPUT, "selectors %u", selectors);
+    if (!d_main_lde || (d.prep_w && !d_prep_lde) || (d.perm_ext_w && !d_perm_lde) || !d_out) return fail(p, DVT_ERR_INPUT, "null argument");
+    const size_t m = (size_t)2 << log_n, out_bytes = 16 * m;
+    if (overlap(d_out, out_bytes, d_main_lde, 4 * d.main_w * m) || (d.prep_w && overlap(d_out, out_bytes, d_prep_lde, 4 * d.prep_w * m)) ||
+        (d.perm_ext_w && overlap(d_out, out_bytes, d_perm_lde, 16 * d.perm_ext_w * m)))
+        return fail(p, DVT_ERR_INPUT, "out overlaps an input");
+    std::lock_guard<std::mutex> lk(p->mu);
+    (void)pipe_drain(p);
+    HIP_TRY(p, hipSetDevice(p->eng.device));
+    Engine &e = p->eng;
+    StageBuf parts{e.pool};
+    uint32_t *d_parts;
+    if (int rc = chip_stage_parts(p, path, d.quot_parts, log_n, 8, &parts, &d_parts)) return rc;
+    int n_beta, n_alpha;
+    challenge_power_counts(machine_by_name(machine), &n_beta, &n_alpha);
+    Engine::ChipInputs in{d_main_lde, d.prep_w ? d_prep_lde : nullptr, nullptr, log_n, a.perm_alpha, nullptr, nullptr};
+    in.pub = static_cast<const uint32_t *>(e.upload_vec(a.pub));
+    const Fp4 *d_alpha;
+    const double *d_alpha_f64;
+    if (!in.pub || !e.upload_powers(a.beta, n_beta, false, &in.beta_pows, &in.beta_f64) ||
+        !e.upload_powers(al, n_alpha, true, &d_alpha, &d_alpha_f64) ||
+        !e.quotient_chip(d, in, d.perm_ext_w ? d_perm_lde : nullptr, cs, d_alpha, d_alpha_f64, selectors == DVT_SELECTORS_TABLE, d_parts,
+                         d_out))
+        return fail(p, DVT_ERR_DEVICE, "%s", e.err.c_str());
     return DVT_OK;
 }
 

@@ -214,6 +214,28 @@ class Engine {
     // in batches of increasing candidates; d_found: one device word of scratch
     bool pow_grind(const uint32_t st16[16], uint32_t pos, uint32_t bits, uint32_t *d_found, uint32_t *witness);
 
+    // ---- host side of one chip's K4 and K5 (prove_shard and dvt_stage_perm / dvt_stage_quotient)
+    // the powers base^0 .. base^(n-1) (from_one) or base^1 .. base^n uploaded as Montgomery words and as centred canonical
+    // doubles (the operands of the exact FP64 dot products of K4 / K5, f64dot.cuh)
+    bool upload_powers(Fp4 base, size_t n, bool from_one, const Fp4 **d_pows, const double **d_pows_f64);
+    struct ChipInputs {
+        const uint32_t *main, *prep, *pub;   // device, Montgomery: trace (K4) or LDE (K5) columns, public values
+        uint32_t log_n;                      // of the trace
+        Fp4 perm_alpha;
+        const Fp4 *beta_pows;                // upload_powers(beta, .., false)
+        const double *beta_f64;
+    };
+    // K4: d_perm ([4 perm_ext_w][2^log_n]) receives the batch columns and phi, cum_out (device-writable) the four words of the
+    // cumulative sum.  d_parts: the part-parallel scratch ([PARTS_MAX][4][2^log_n]) or nullptr for the per-row launch;
+    // d_totals [4][2^log_n] and d_scan (prefix_sum_scratch_words(4, 2^log_n)) are scratch.
+    bool perm_chip(const ChipDesc &d, const ChipInputs &in, uint32_t *d_parts, uint32_t *d_totals, uint32_t *d_scan, uint32_t *d_perm,
+                   uint32_t *cum_out);
+    // K5: the quotient chunks d_out ([2][4][2^log_n]) from the LDEs in `in` and perm_lde; cumsum is the chip's cumulative sum.
+    // sel_table: read the selectors from this prover's per-height table (else selectors_of_row in the kernel); d_parts: the
+    // part-parallel scratch ([PARTS_MAX][2][4][2^log_n]) or nullptr for one launch per part.
+    bool quotient_chip(const ChipDesc &d, const ChipInputs &in, const uint32_t *perm_lde, Fp4 cumsum, const Fp4 *alpha_pows,
+                       const double *alpha_f64, bool sel_table, uint32_t *d_parts, uint32_t *d_out);
+
     Arena arena;
     DevPool pool;
     // K5 selector tables, one per trace height this prover has seen ([3][2N] words each, stark.cuh QuotientArgs::sel)
@@ -234,6 +256,8 @@ class Engine {
 // K7 batching powers alpha^0 .. alpha^n_cols (alpha^n_cols weighs the second point), and the same as [n_cols + 1][4]
 // centred canonical doubles: the operand of reduced_opening_kernel
 void fri_alpha_powers(Fp4 alpha, size_t n_cols, std::vector<Fp4> *pows, std::vector<double> *pows_f64);
+// how many beta and alpha powers a shard of machine m uploads for K4 / K5: the largest arity and folded count of its chips
+void challenge_power_counts(const MachineDesc *m, int *n_beta, int *n_alpha);
 #endif
 
 }  // namespace dvt

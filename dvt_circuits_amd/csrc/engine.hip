@@ -303,6 +303,51 @@ bool Engine::logup_running_sum(uint32_t *d_totals, uint32_t *d_scratch, uint32_t
     HIPCHK(launch_phi_from_prefix_sums(stream, d_totals, d_phi, log_n, cum_out));
     return true;
 }
+void challenge_power_counts(const MachineDesc *m, int *n_beta, int *n_alpha) {
+    *n_beta = *n_alpha = 1;
+    for (int i = 0; i < m->n_chips; i++) {
+        *n_beta = std::max(*n_beta, m->chips[i].max_arity);
+        *n_alpha = std::max(*n_alpha, m->chips[i].n_folded);
+    }
+}
+bool Engine::upload_powers(Fp4 base, size_t n, bool from_one, const Fp4 **d_pows, const double **d_pows_f64) {
+    const std::vector<Fp4> v = ext_powers(base, n, from_one);
+    std::vector<double> d(4 * v.size());
+    for (size_t i = 0; i < v.size(); i++)
+        for (int k = 0; k < 4; k++) d[4 * i + k] = centred_canonical(v[i].c[k]);
+    *d_pows = upload_vec(v);
+    *d_pows_f64 = *d_pows ? reinterpret_cast<const double *>(upload(d.data(), d.size() * sizeof(double))) : nullptr;
+    return *d_pows_f64 != nullptr;
+}
+bool Engine::perm_chip(const ChipDesc &d, const ChipInputs &in, uint32_t *d_parts, uint32_t *d_totals, uint32_t *d_scan, uint32_t *d_perm,
+                       uint32_t *cum_out) {
+    const size_t bw = 4 * (size_t)d.perm_ext_w, n = (size_t)1 << in.log_n;
+    PermArgs pa{in.main, in.prep, in.pub, d_perm, d_totals, in.beta_pows, in.beta_f64, in.perm_alpha, in.log_n};
+    pa.partial = d_parts;
+    HIPCHK(d.launch_perm(stream, pa));
+    return logup_running_sum(d_totals, d_scan, d_perm + (bw - 4) * n, in.log_n, cum_out);
+}
+bool Engine::quotient_chip(const ChipDesc &d, const ChipInputs &in, const uint32_t *perm_lde, Fp4 cumsum, const Fp4 *alpha_pows,
+                           const double *alpha_f64, bool sel_table, uint32_t *d_parts, uint32_t *d_out) {
+    const size_t n = (size_t)1 << in.log_n;
+    const Fp g = Fp::from_canonical(COSET_SHIFT);
+    QuotientArgs qa;
+    qa.main_lde = in.main; qa.prep_lde = in.prep; qa.perm_lde = perm_lde; qa.pub = in.pub; qa.out = d_out;
+    qa.alpha_pows = alpha_pows; qa.beta_pows = in.beta_pows; qa.alpha_d = alpha_f64; qa.beta_d = in.beta_f64;
+    qa.perm_alpha = in.perm_alpha; qa.cum_over_n = cumsum * inv(Fp::from_canonical((uint32_t)n));
+    Fp gn = pow(g, n);
+    qa.z_even = gn - Fp::one();
+    qa.z_odd = -gn - Fp::one();
+    qa.zinv_even = inv(qa.z_even);
+    qa.zinv_odd = inv(qa.z_odd);
+    qa.w_inv = inv(two_adic_generator(in.log_n));
+    qa.log_n = in.log_n;
+    qa.tabs = tabs;
+    qa.sel = sel_table ? selector_table(qa) : nullptr;
+    qa.partial = d_parts;
+    HIPCHK(d.launch_quotient(stream, qa));
+    return true;
+}
 bool Engine::open_point(Fp4 z, uint32_t log_n, Fp4 *d_w, Fp4 *scale) {
     HIPCHK(launch_open_weights(stream, tabs, z, log_n, d_w));
     const size_t n = (size_t)1 << log_n;
@@ -603,23 +648,11 @@ bool Engine::prove_shard(const ProvingKey &pk, const std::vector<ChipTrace> &tra
         perm_alpha = ch.sample_ext();
         beta = ch.sample_ext();
     }
-    int max_arity = 1, max_folded = 1;
-    for (int i = 0; i < m->n_chips; i++) {
-        max_arity = std::max(max_arity, m->chips[i].max_arity);
-        max_folded = std::max(max_folded, m->chips[i].n_folded);
-    }
-    std::vector<Fp4> beta_pows = ext_powers(beta, max_arity, false);
-    const Fp4 *d_beta = upload_vec(beta_pows);
-    if (!d_beta) return false;
-    // the same powers as centred doubles: operands of the exact FP64 dot products of K4 / K5 (f64dot.cuh)
-    auto upload_centred = [&](const std::vector<Fp4> &v) -> const double * {
-        std::vector<double> d(4 * v.size());
-        for (size_t i = 0; i < v.size(); i++)
-            for (int k = 0; k < 4; k++) d[4 * i + k] = centred_canonical(v[i].c[k]);
-        return reinterpret_cast<const double *>(upload(d.data(), d.size() * sizeof(double)));
-    };
-    const double *d_beta_f64 = upload_centred(beta_pows);
-    if (!d_beta_f64) return false;
+    int max_arity, max_folded;
+    challenge_power_counts(m, &max_arity, &max_folded);
+    const Fp4 *d_beta;
+    const double *d_beta_f64;
+    if (!upload_powers(beta, max_arity, false, &d_beta, &d_beta_f64)) return false;
     mats.clear();
     uint32_t perm_hmax = 0;
     size_t n_cumsum = 0;
@@ -633,14 +666,13 @@ bool Engine::prove_shard(const ProvingKey &pk, const std::vector<ChipTrace> &tra
         ALLOC(s.perm_lde, uint32_t, bw * 2 * s.n);
         uint32_t *totals, *scan_scratch;
         ALLOC(totals, uint32_t, 4 * s.n);
-        PermArgs pa{s.main, s.prep, d_pub, s.perm, totals, d_beta, d_beta_f64, perm_alpha, s.log_n};
-        if ((int)s.log_n <= parts_parallel_log) pa.partial = d_parts;   // (tall tables: measured, no gain - 68.14 against 68.09 M cycles/s)
-        HIPCHK(s.d->launch_perm(stream, pa));
         ALLOC(scan_scratch, uint32_t, prefix_sum_scratch_words(4, s.n));
         // the cumulative sum is only needed for the transcript, after the permutation tree: the kernel writes its four
         // words into the tail of the pinned staging buffer, read after the next synchronisation
         uint32_t *cw = reinterpret_cast<uint32_t *>(h_down + DOWN_BYTES - 4096) + 4 * n_cumsum++;
-        if (!logup_running_sum(totals, scan_scratch, s.perm + (bw - 4) * s.n, s.log_n, cw)) return false;
+        const ChipInputs in{s.main, s.prep, d_pub, s.log_n, perm_alpha, d_beta, d_beta_f64};
+        // (tall tables: measured, no gain from the part-parallel launch - 68.14 against 68.09 M cycles/s)
+        if (!perm_chip(*s.d, in, (int)s.log_n <= parts_parallel_log ? d_parts : nullptr, totals, scan_scratch, s.perm, cw)) return false;
         HIPCHK(lde(s.perm, d_scratch, s.perm_lde, (uint32_t)bw, s.log_n, 0));
         mats.push_back({s.perm_lde, (uint32_t)bw, s.log_n + 1});
         perm_hmax = std::max(perm_hmax, s.log_n + 1);
@@ -669,30 +701,18 @@ bool Engine::prove_shard(const ProvingKey &pk, const std::vector<ChipTrace> &tra
 
     // ---- 3. quotient (K5) + chunk LDE + commit
     Fp4 alpha = ch.sample_ext();
-    std::vector<Fp4> alpha_pows = ext_powers(alpha, max_folded, true);
-    const Fp4 *d_alpha = upload_vec(alpha_pows);
-    const double *d_alpha_f64 = upload_centred(alpha_pows);
-    if (!d_alpha || !d_alpha_f64) return false;
+    const Fp4 *d_alpha;
+    const double *d_alpha_f64;
+    if (!upload_powers(alpha, max_folded, true, &d_alpha, &d_alpha_f64)) return false;
     mats.clear();
     const Fp g = Fp::from_canonical(COSET_SHIFT);
     for (auto &s : cs) {
         ALLOC(s.quot, uint32_t, 8 * s.n);
         ALLOC(s.quot_lde, uint32_t, 16 * s.n);
-        QuotientArgs qa;
-        qa.main_lde = s.main_lde; qa.prep_lde = s.prep_lde; qa.perm_lde = s.perm_lde; qa.pub = d_pub; qa.out = s.quot;
-        qa.alpha_pows = d_alpha; qa.beta_pows = d_beta; qa.alpha_d = d_alpha_f64; qa.beta_d = d_beta_f64;
-        qa.perm_alpha = perm_alpha; qa.cum_over_n = s.cumsum * inv(Fp::from_canonical((uint32_t)s.n));
-        Fp gn = pow(g, s.n);
-        qa.z_even = gn - Fp::one();
-        qa.z_odd = -gn - Fp::one();
-        qa.zinv_even = inv(qa.z_even);
-        qa.zinv_odd = inv(qa.z_odd);
-        qa.w_inv = inv(two_adic_generator(s.log_n));
-        qa.log_n = s.log_n;
-        qa.tabs = tabs;
-        qa.sel = selector_table(qa);
-        if ((int)s.log_n <= parts_parallel_log) qa.partial = d_parts;
-        HIPCHK(s.d->launch_quotient(stream, qa));
+        const ChipInputs in{s.main_lde, s.prep_lde, d_pub, s.log_n, perm_alpha, d_beta, d_beta_f64};
+        if (!quotient_chip(*s.d, in, s.perm_lde, s.cumsum, d_alpha, d_alpha_f64, true, (int)s.log_n <= parts_parallel_log ? d_parts : nullptr,
+                           s.quot))
+            return false;
         HIPCHK(lde(s.quot, d_scratch, s.quot_lde, 4, s.log_n, 1));
         HIPCHK(lde(s.quot + 4 * s.n, d_scratch, s.quot_lde + 8 * s.n, 4, s.log_n, 2));
         mats.push_back({s.quot_lde, 8, s.log_n + 1});

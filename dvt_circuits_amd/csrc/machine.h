@@ -36,6 +36,7 @@ struct ChipDesc {
     int main_w, prep_w, n_pub, n_constraints, n_interactions, max_arity;
     int perm_ext_w;  // extension columns of the permutation trace (0 if no interactions)
     int n_folded;    // number of alpha powers consumed
+    bool perm_parts, quot_parts;   // has the part-parallel K4 / K5 launch (launch_perm_t / launch_quotient_t with a.partial)
     hipError_t (*launch_perm)(hipStream_t, const PermArgs &);
     hipError_t (*launch_quotient)(hipStream_t, const QuotientArgs &);
     Fp4 (*verify_eval)(const VerifierAccess &, const VerifierPoint &);
@@ -54,10 +55,17 @@ const MachineDesc *machine_by_name(const char *name);
 
 #if defined(__HIPCC__)
 template <class Air>
+constexpr bool perm_parts_parallel() { return Air::N_INTERACTIONS > 0 && Air::N_LPARTS > 1 && Air::N_LPARTS <= PARTS_MAX; }
+template <class Air>
+constexpr bool quot_parts_parallel() {
+    constexpr int NP = Air::N_PARTS + (Air::N_INTERACTIONS > 0 ? Air::N_LPARTS : 0);
+    return NP > 2 && NP <= PARTS_MAX && Air::MAIN_W >= 128;   // (the wide chips: the others' groups are few and short)
+}
+template <class Air>
 hipError_t launch_perm_t(hipStream_t st, const PermArgs &a) {
     if (Air::N_INTERACTIONS == 0) return hipSuccess;
     size_t n = (size_t)1 << a.log_n;
-    if constexpr (Air::N_LPARTS > 1 && Air::N_LPARTS <= PARTS_MAX) {
+    if constexpr (perm_parts_parallel<Air>()) {
         if (a.partial) {
             perm_rows_parts_kernel<Air><<<dim3((unsigned)((n + 255) / 256), Air::N_LPARTS), 256, 0, st>>>(a);
             sum_parts_kernel<0><<<(unsigned)((4 * n + 255) / 256), 256, 0, st>>>(a.partial, Air::N_LPARTS, 4 * n, a.totals);
@@ -78,7 +86,7 @@ template <class Air>
 hipError_t launch_quotient_t(hipStream_t st, const QuotientArgs &a) {
     size_t m = (size_t)2 << a.log_n;
     constexpr int NP = Air::N_PARTS + (Air::N_INTERACTIONS > 0 ? Air::N_LPARTS : 0);
-    if constexpr (NP > 2 && NP <= PARTS_MAX && Air::MAIN_W >= 128) {   // (the wide chips: the others' groups are few and short)
+    if constexpr (quot_parts_parallel<Air>()) {
         if (a.partial) {
             quotient_parts_kernel<Air><<<dim3((unsigned)((m + 255) / 256), NP), 256, 0, st>>>(a);
             sum_parts_kernel<0><<<(unsigned)((4 * m + 255) / 256), 256, 0, st>>>(a.partial, NP, 4 * m, a.out);
@@ -104,7 +112,7 @@ template <class Air>
 constexpr ChipDesc make_chip_desc() {
     return ChipDesc{Air::NAME, Air::MAIN_W, Air::PREP_W, Air::N_PUB, Air::N_CONSTRAINTS, Air::N_INTERACTIONS,
                     Air::MAX_ARITY, PermShape<Air>::EXT_W, PermShape<Air>::N_FOLDED,
-                    &launch_perm_t<Air>, &launch_quotient_t<Air>, &verify_eval_t<Air>};
+                    perm_parts_parallel<Air>(), quot_parts_parallel<Air>(), &launch_perm_t<Air>, &launch_quotient_t<Air>, &verify_eval_t<Air>};
 }
 #endif
 

@@ -125,6 +125,30 @@ int dvt_stage_reduced_opening(dvt_prover *p, const uint32_t *const *cols, uint32
 /* K9: the smallest proof-of-work witness w: the Poseidon2 permutation of state with state[pos] = w
  * (pos < 8) has word 7 divisible by 2^bits (bits <= 30).  Synchronises the stream. */
 int dvt_stage_pow_grind(dvt_prover *p, const uint32_t state[16], uint32_t pos, uint32_t bits, uint32_t *witness);
+/* K4 and K5 of one chip of a machine ("rv32" or "toy", chip = its index), as a shard proof runs them.  Device matrices
+ * hold Montgomery words (dvt_dev_to_internal), column-major; pub holds the chip's public values.  path selects the
+ * launches: DVT_PATH_DEFAULT what a proof on this handle launches at this height, DVT_PATH_ROWS the per-row K4 kernel /
+ * one K5 launch per part, DVT_PATH_PARTS the part-parallel launches (refused for a chip without them, and above 2^15
+ * rows: their scratch is sized for that height at most). */
+#define DVT_PATH_DEFAULT 0u
+#define DVT_PATH_ROWS 1u
+#define DVT_PATH_PARTS 2u
+/* K4: d_main [main_w][2^log_n], d_prep [prep_w][2^log_n] (may be NULL when prep_w = 0) -> d_perm
+ * [4 perm_ext_w][2^log_n] (the batch columns, then phi; may be NULL when the chip has no interactions) and cum, the
+ * chip's cumulative sum.  Synchronises the stream. */
+int dvt_stage_perm(dvt_prover *p, const char *machine, uint32_t chip, const uint32_t *d_main, const uint32_t *d_prep, uint32_t log_n,
+                   const uint32_t *pub, const uint32_t perm_alpha[4], const uint32_t beta[4], uint32_t path, uint32_t *d_perm,
+                   uint32_t cum[4]);
+/* K5 selectors: the handle's cached table of this height, or computed in the kernel */
+#define DVT_SELECTORS_TABLE 0u
+#define DVT_SELECTORS_IN_KERNEL 1u
+/* K5: the LDEs d_main_lde [main_w][2^(log_n+1)], d_prep_lde [prep_w][..], d_perm_lde [4 perm_ext_w][..] (on 31*<w_2N>;
+ * the last two may be NULL when their width is 0) -> d_out [2][4][2^log_n], the quotient's two chunks (even and odd LDE
+ * rows) as a shard proof lays them out.  cum: the chip's cumulative sum. */
+int dvt_stage_quotient(dvt_prover *p, const char *machine, uint32_t chip, const uint32_t *d_main_lde, const uint32_t *d_prep_lde,
+                       const uint32_t *d_perm_lde, uint32_t log_n, const uint32_t *pub, const uint32_t perm_alpha[4],
+                       const uint32_t beta[4], const uint32_t alpha[4], const uint32_t cum[4], uint32_t path, uint32_t selectors,
+                       uint32_t *d_out);
 
 /* ------------------------------------------------- machine-level entry points
  * A "machine" is a fixed list of chips (AIRs) compiled into the library:
