@@ -190,6 +190,20 @@ def verify(vk: bytes, proof: bytes, fri_queries=100, pow_bits=16):
     return rc == DVT_OK, ec.value, out, _take_str(lib, why)
 
 
+def split_container(proof: bytes):
+    """The parts of a core proof ("DVC3" container, csrc/proof.h) -> (exit_code, public value bytes, [shard proof bytes])."""
+    w = np.frombuffer(proof, np.uint32)
+    assert w[0] == 0x33435644
+    n, ec, pvl = int(w[1]), int(w[2]), int(w[3])
+    at = 4 + (pvl + 3) // 4
+    shards = []
+    for _ in range(n):
+        shards.append(w[at + 1:at + 1 + int(w[at])].tobytes())
+        at += 1 + len(shards[-1]) // 4
+    assert at == len(w)
+    return ec, w[4:4 + (pvl + 3) // 4].tobytes()[:pvl], shards
+
+
 def _parse_blob(w):
     nch = int(w[0])
     meta = w[1:1 + 4 * nch].reshape(nch, 4)

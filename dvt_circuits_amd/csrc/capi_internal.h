@@ -1,0 +1,157 @@
+// Private to the C-ABI layer: what capi.hip (the handle, the stage and machine-level entry points) and capi_rv32.hip
+// (the rv32 boundary: setup, the job and its pipelines, prove, assemble, verify) share.
+#pragma once
+#include "../../include/dvt_prover.h"
+
+#include <condition_variable>
+#include <cstdlib>
+#include <cstring>
+#include <functional>
+#include <memory>
+#include <mutex>
+#include <thread>
+
+#include "engine.h"
+#include "rv32.h"
+
+constexpr int MAX_LANES = 3;
+
+// what dvt_rv32_prove_shard is about to collect from a running phase-2 pipeline
+struct PipeClaim {
+    const dvt_job *job;
+    const dvt_pk *pk;
+    const uint32_t *ch;   // the challenges, canonical
+    size_t shard;         // index into the job's shards
+};
+
+// Phase 2 of a job's shards, run ahead of the caller on the prover lanes: one worker thread per lane takes the next shard in
+// job order (that shard then stays on that lane), at most `lanes` shards past the last one the caller asked for.  Worker
+// threads never touch p->err: each slot keeps its own result.  Everything here is guarded by mu; the API thread holds the
+// prover's mutex while it creates, claims from or drains the pipeline.
+struct Phase2Pipe {
+    struct Slot {
+        size_t shard = 0;               // index into the job's shards
+        int state = 0;                  // 0 waiting, 1 running, 2 done
+        bool claimed = false;
+        int rc = 0;
+        std::string err;
+        std::vector<uint32_t> words;
+    };
+    dvt_job *job = nullptr;
+    const dvt_pk *pk = nullptr;
+    uint32_t ch[8] = {};                // the challenges, canonical
+    std::vector<Slot> slots;            // in proving order
+    size_t next = 0;                    // the next slot a worker starts
+    size_t limit = 0;                   // slots below this may start
+    bool stop = false, failed = false;
+    std::mutex mu;
+    std::condition_variable cv;
+    std::vector<std::thread> workers;
+
+    // the unclaimed slot of the claimed shard when this pipeline proves that job under that key and those challenges, else -1
+    long slot_of(const PipeClaim &c) const {
+        if (c.job != job || c.pk != pk || memcmp(c.ch, ch, sizeof ch)) return -1;
+        for (size_t i = 0; i < slots.size(); i++)
+            if (slots[i].shard == c.shard) return slots[i].claimed ? -1 : (long)i;
+        return -1;
+    }
+};
+
+struct dvt_prover {
+    dvt::Engine eng;                  // lane 0: phase 1, the stage entry points and (with one lane) phase 2
+    // Further prover lanes (phase 2 only): own stream, ring, arena, pool and tables each, sharing the proving key's read-only
+    // device buffers.  Created on the first job that holds at least two shards.
+    int lanes = 2;
+    std::unique_ptr<dvt::Engine> more[MAX_LANES - 1];
+    std::unique_ptr<Phase2Pipe> pipe;   // the phase-2 pipeline of the current job, if one runs (see Phase2Pipe)
+    dvt::StarkConfig cfg;
+    uint32_t log_shard = 21;          // cycles per shard = 2^log_shard (SP1's default shard size)
+    uint64_t max_cycles = 1ull << 36;
+    bool keep_phase1 = true;          // keep K0 output, main LDEs and tree of phase 1 in HBM for phase 2 ("keep_phase1": 0 recomputes)
+    uint32_t exec_threads = 0;        // trace-mode executor threads of the prove pipeline ("exec_threads", 0 = from the host's core count)
+    hipStream_t copy_stream = nullptr;            // record uploads overlap the previous shard's kernels
+    std::vector<dvt::rv32::CycleRec *> pinned;    // pinned staging buffers of 2^log_shard records each, reused across calls
+    // Pinned staging of everything else a shard uploads (auxiliary traces, precompile calls).  Handing the runtime PAGEABLE
+    // memory makes it pin the pages on the fly; when the vectors are freed afterwards the driver quiesces every queue of the
+    // process to drop that mapping - measured as a 20-30 ms stall of the GPU right before phase 1 of a single-shard proof.
+    uint8_t *aux_pinned = nullptr;
+    size_t aux_pinned_bytes = 0;
+    std::string err;
+    std::mutex mu;
+};
+
+struct dvt_pk {
+    dvt::ProvingKey key;
+    bool is_rv32 = false;
+    dvt::rv32::Program prog;
+    dvt::rv32::HostPrep prep;
+    dvt::rv32::Instr *d_instrs = nullptr;   // device copy of prog.instrs (K0)
+    uint32_t *d_prog_row = nullptr;    // instruction index -> program-table row
+};
+
+namespace dvt {   // (the helpers the two units share stay out of the library's global namespace)
+inline Engine &lane_engine(dvt_prover *p, int k) { return k == 0 ? p->eng : *p->more[k - 1]; }
+
+// ---- errors: every message of the ABI layer goes through one formatter into one string
+int fail(std::string &err, int code, const char *fmt, ...) __attribute__((format(printf, 3, 4)));
+// into p->err; with p == nullptr into the calling thread's creation error (dvt_last_error(NULL))
+int fail(dvt_prover *p, int code, const char *fmt, ...) __attribute__((format(printf, 3, 4)));
+// an engine call failed: its message, as DVT_ERR_DEVICE
+inline int engine_fail(std::string &err, const Engine &e) { return fail(err, DVT_ERR_DEVICE, "%s", e.err.c_str()); }
+#define HIP_TRY(to, expr)                                                                              \
+    do {                                                                                               \
+        hipError_t e_ = (expr);                                                                        \
+        if (e_ != hipSuccess) return fail(to, DVT_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); \
+    } while (0)
+
+// Stops the pipeline (running shards finish, nothing new starts; unclaimed results are discarded) and waits for every lane's
+// stream.  With first_err != nullptr: the error of the lowest failed slot, if any.  Caller holds p->mu.
+int pipe_drain(dvt_prover *p, std::string *first_err = nullptr);
+
+// Built first by every entry point that works on a handle: holds p->mu for the whole call, drains the phase-2 pipeline and
+// selects the handle's device (rc: DVT_ERR_DEVICE when that fails).  With a claim (dvt_rv32_prove_shard only) a pipeline
+// that holds the claimed shard keeps running, and `slot` is that shard's slot.
+struct Guard {
+    std::lock_guard<std::mutex> lk;
+    long slot = -1;
+    int rc;
+    explicit Guard(dvt_prover *p, const PipeClaim *claim = nullptr);
+};
+
+// A lane's view of the prover for K0 and phase 2: its engine, and the error string it reports to (p->err for lane 0 on the
+// API thread; a pipeline worker's own string, which its slot keeps: worker threads never write p->err).  Passed as
+// `const Lane &`: what it refers to stays writable.
+struct Lane {
+    dvt_prover *p;
+    int k;
+    Engine &eng;
+    std::string &err;
+};
+inline Lane lane0(dvt_prover *p) { return {p, 0, p->eng, p->err}; }
+
+// a library-allocated copy of w (release with dvt_free); *len = its bytes
+inline uint8_t *copy_out(const std::vector<uint32_t> &w, size_t *len) {
+    uint8_t *b = (uint8_t *)malloc(w.size() * 4 + 1);
+    if (!b) return nullptr;
+    memcpy(b, w.data(), w.size() * 4);
+    *len = w.size() * 4;
+    return b;
+}
+// the one teardown of a proving key, complete or half built by a setup
+void pk_release(dvt_prover *p, dvt_pk *pk);
+// the end of every setup: with rc == DVT_OK the vk (when asked for) and the key go to the caller; otherwise, or when the vk
+// cannot be copied out, the key is released.  Returns the setup's code.
+int setup_finish(dvt_prover *p, dvt_pk *pk, int rc, dvt_pk **pk_out, uint8_t **vk, size_t *vk_len);
+// the verifying key's encoding ("DVK1")
+std::vector<uint32_t> vk_words(const VerifyingKey &vk);
+bool vk_parse(const uint8_t *b, size_t len, VerifyingKey *vk);
+// verify entry points: the reason (strdup'ed, when the caller asks for one) and the code
+inline int reject(char **reason, int code, const std::string &why) {
+    if (reason) *reason = strdup(why.c_str());
+    return code;
+}
+// Their common part: the proof's bytes as words, read by `check` (a reader over the words, the reason to fill -> a code)
+// inside a try-block: a malformed proof throws, and its message is the reason.
+int verify_words(const uint8_t *proof, size_t len, int len_code, char **reason,
+                 const std::function<int(WordReader &, std::string &)> &check);
+}  // namespace dvt

@@ -1,0 +1,1050 @@
+// The rv32 boundary of the C ABI (include/dvt_prover.h): setup from an ELF, execute, the job (the prepare pipeline and
+// phase 1, the phase-2 pipeline on the prover lanes), the prove entry points, assemble, verify and the debug hooks.
+#include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <cstdio>
+#include <deque>
+#include <map>
+
+#include "capi_internal.h"
+#include "poseidon2_f64.cuh"
+#include "sha256.h"
+
+using namespace dvt;
+
+namespace {
+constexpr uint32_t N_PUB = rv32::N_PUBLIC;           // start_pc, next_pc, exit_code, shard, is_last
+constexpr uint32_t HEADER_WORDS = 8 + N_PUB;         // per-shard commitment header: main root + public values (canonical)
+constexpr uint32_t PV_BUS = 5;                       // tools/airgen/rv32.py BUSES["sys"]
+using Clock = std::chrono::steady_clock;
+
+double ms_since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
+std::vector<std::vector<uint8_t>> collect_stdin(const dvt_buf *bufs, size_t n) {
+    std::vector<std::vector<uint8_t>> v(n);
+    for (size_t i = 0; i < n; i++)
+        if (bufs[i].len) v[i].assign(bufs[i].data, bufs[i].data + bufs[i].len);
+    return v;
+}
+uint8_t *dup_bytes(const std::vector<uint8_t> &v, size_t *len) {
+    uint8_t *b = (uint8_t *)malloc(v.size() + 1);
+    if (b && !v.empty()) memcpy(b, v.data(), v.size());
+    if (len) *len = v.size();
+    return b;
+}
+// LogUp challenges common to all shards: transcript over the key and every shard's header
+PermChallenges global_challenges(const VerifyingKey &vk, const uint32_t *headers, size_t n) {
+    Challenger g;
+    g.observe(vk.prep_root);
+    g.observe_u32((uint32_t)n);
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t *h = headers + i * HEADER_WORDS;
+        for (uint32_t k = 0; k < 8; k++) g.observe(Fp::from_canonical(h[k]));
+        g.observe_u32(N_PUB);
+        for (uint32_t k = 0; k < N_PUB; k++) g.observe(Fp::from_canonical(h[8 + k] % P));
+    }
+    PermChallenges c;
+    c.alpha = g.sample_ext();
+    c.beta = g.sample_ext();
+    return c;
+}
+// SP1's committed-value digest: word k = little-endian u32 of bytes 4k..4k+3 of SHA-256(public-value bytes)
+// (an empty stream commits 42c4b0e3 141cfc98 ... = sha256("") read as LE words)
+void pv_digest_words(const std::vector<uint8_t> &pv, uint32_t out[8]) {
+    uint8_t dg[32];
+    sha256(pv.data(), pv.size(), dg);
+    for (int k = 0; k < 8; k++) out[k] = dg[4 * k] | (dg[4 * k + 1] << 8) | (dg[4 * k + 2] << 16) | ((uint32_t)dg[4 * k + 3] << 24);
+}
+}  // namespace
+
+struct ShardJob {
+    uint32_t index = 0;       // shard number (1-based) = position in the execution + 1
+    size_t n_recs = 0;
+    uint32_t next_pc = 0;
+    rv32::CycleRec *d_recs = nullptr;
+    uint32_t log_n[rv32::N_CHIPS] = {};
+    bool present[rv32::N_CHIPS] = {};
+    uint32_t *d_aux[rv32::N_CHIPS] = {};  // main traces except cpu
+    std::vector<Fp> pubs;
+    MainCache cache;  // phase-1 LDEs + tree of the main traces, consumed by phase 2
+    // K0 output of this shard kept from phase 1 to phase 2 (with the cache, while HBM allows); otherwise the
+    // job's working buffers are used and phase 2 runs K0 again
+    uint32_t *d_cpu = nullptr, *d_byte = nullptr, *d_prog = nullptr;
+    bool traces_valid = false;
+    uint32_t header[HEADER_WORDS] = {};
+    bool header_valid = false;   // phase 1 ran (inside the prepare pipeline, or by commit_shard) and no phase 2 has consumed it
+};
+// one prepared execution: cut into shards by the executor; the shards this job owns (first, first + stride, ...) are
+// resident in HBM, ready for K0..K9
+struct dvt_job {
+    int exit_code = -1;
+    uint64_t cycles = 0;
+    std::vector<uint8_t> public_values;
+    size_t n_total = 0, first = 0, stride = 1;   // shards of the execution / which of them this job holds
+    std::vector<ShardJob> shards;
+    struct Work {   // K0 working buffers of one lane (largest shard seen), from that lane's pool
+        uint32_t *d_cpu = nullptr, *d_byte = nullptr, *d_prog = nullptr;
+        uint32_t log_cpu = 0;
+    } work[MAX_LANES];
+    size_t byte_words = 0, prog_words = 0;
+    double t_exec_wait = 0;   // seconds the GPU thread spent waiting for the executor inside prepare
+    ShardJob *at(size_t pos) { return pos >= first && (pos - first) % stride == 0 && (pos - first) / stride < shards.size() ? &shards[(pos - first) / stride] : nullptr; }
+};
+
+// (no phase-2 pipeline runs: the phase-1 buffers go back to lane 0's pool only after every lane is done)
+static void job_release(dvt_prover *p, dvt_job *j) {
+    if (!j) return;
+    DevPool &pool = p->eng.pool;
+    for (auto &s : j->shards) {
+        pool.free(s.d_recs);
+        for (auto &d : s.d_aux) pool.free(d);
+        for (uint32_t *d : {s.d_cpu, s.d_byte, s.d_prog}) pool.free(d);
+        s.cache.release();
+    }
+    for (int k = 0; k < MAX_LANES; k++) {
+        auto &w = j->work[k];
+        if (!w.d_cpu && !w.d_byte && !w.d_prog) continue;
+        DevPool &lp = lane_engine(p, k).pool;
+        for (uint32_t *d : {w.d_cpu, w.d_byte, w.d_prog}) lp.free(d);
+    }
+    delete j;
+}
+
+// K0 of a shard (into the shard's own buffers when it has them, else the job's working buffers); fills the chip
+// trace list of that shard.  `reuse`: phase 2 takes the traces phase 1 left behind instead of generating them again.
+static int shard_traces(const Lane &c, const dvt_pk *pk, dvt_job *j, ShardJob &s, std::vector<ChipTrace> *traces, bool reuse) {
+    hipStream_t st = c.eng.stream;
+    dvt_job::Work &w = j->work[c.k];
+    const MachineDesc *m = machine_rv32();
+    if (!s.d_cpu && (!w.d_cpu || w.log_cpu < s.log_n[RV32_CHIP_CPU])) {   // working buffers, sized for the largest shard seen
+        HIP_TRY(c.err, hipStreamSynchronize(st));
+        for (uint32_t **d : {&w.d_cpu, &w.d_byte, &w.d_prog}) { c.eng.pool.free(*d); *d = nullptr; }
+        w.log_cpu = s.log_n[RV32_CHIP_CPU];
+        HIP_TRY(c.err, c.eng.pool.alloc(&w.d_cpu, ((size_t)RV32_CPU_MAIN_W << w.log_cpu) * 4));
+        HIP_TRY(c.err, c.eng.pool.alloc(&w.d_byte, j->byte_words * 4));
+        HIP_TRY(c.err, c.eng.pool.alloc(&w.d_prog, j->prog_words * 4));
+    }
+    uint32_t *cpu = s.d_cpu ? s.d_cpu : w.d_cpu, *byte = s.d_cpu ? s.d_byte : w.d_byte, *prog = s.d_cpu ? s.d_prog : w.d_prog;
+    if (!(reuse && s.d_cpu && s.traces_valid)) {
+        bool ok = hipMemcpyAsync(byte, s.d_aux[RV32_CHIP_BYTE], j->byte_words * 4, hipMemcpyDeviceToDevice, st) == hipSuccess &&
+                  hipMemcpyAsync(prog, s.d_aux[RV32_CHIP_PROGRAM], j->prog_words * 4, hipMemcpyDeviceToDevice, st) == hipSuccess &&
+                  rv32::launch_k0_cpu_rows(st, s.d_recs, s.n_recs, s.index, s.next_pc, pk->d_instrs, pk->d_prog_row, cpu, s.log_n[RV32_CHIP_CPU], byte, prog) == hipSuccess &&
+                  launch_to_internal(st, byte, j->byte_words) == hipSuccess && launch_to_internal(st, prog, j->prog_words) == hipSuccess;
+        if (!ok) return fail(c.err, DVT_ERR_DEVICE, "trace generation (K0) failed: %s", hipGetErrorString(hipGetLastError()));
+        s.traces_valid = s.d_cpu != nullptr;
+    }
+    traces->clear();
+    for (int c = 0; c < m->n_chips; c++) {
+        if (!s.present[c]) continue;
+        const uint32_t *ptr = c == RV32_CHIP_CPU ? cpu : c == RV32_CHIP_BYTE ? byte : c == RV32_CHIP_PROGRAM ? prog : s.d_aux[c];
+        traces->push_back({c, s.log_n[c], ptr});
+    }
+    return DVT_OK;
+}
+
+// phase 1 of a shard (lane 0): K0 + K1..K3 of the main traces -> header
+static int shard_commit(const Lane &c, const dvt_pk *pk, dvt_job *j, ShardJob &s) {
+    dvt_prover *p = c.p;
+    std::vector<ChipTrace> traces;
+    const bool time_stages = getenv("DVT_TIME_PREPARE") != nullptr;
+    const auto t0 = Clock::now();
+    auto lap = [&](const char *what) {
+        if (time_stages) fprintf(stderr, "[commit] %s at %.2f ms (pool misses so far %zu)\n", what, ms_since(t0), c.eng.pool.misses);
+    };
+    // keep the phase-1 results in HBM while they fit (about 3 GB per 2^21-cycle shard); otherwise phase 2 recomputes
+    size_t free_b = 0, total_b = 0;
+    if (p->keep_phase1 && !s.cache.tree) { (void)hipMemGetInfo(&free_b, &total_b); free_b += c.eng.pool.cached_bytes; }   // (only the first commit of a shard asks)
+    lap("memory asked");
+    // the further lanes' phase-2 arenas are not there yet on the first job: leave room for them (lane 0's arena is the measure
+    // of one), so that the kept caches do not take what the second lane's working set then cannot get
+    size_t lane_room = 0;
+    for (int k = 1; k < p->lanes; k++) {
+        const size_t have = p->more[k - 1] ? p->more[k - 1]->arena.cap : 0;
+        if (c.eng.arena.cap > have) lane_room += c.eng.arena.cap - have;
+    }
+    MainCache *keep = p->keep_phase1 && (s.cache.tree || free_b > ((size_t)24 << 30) + lane_room) ? &s.cache : nullptr;
+    if (keep && !s.d_cpu) {
+        DevPool &pool = c.eng.pool;
+        bool ok = pool.alloc(&s.d_cpu, ((size_t)RV32_CPU_MAIN_W << s.log_n[RV32_CHIP_CPU]) * 4) == hipSuccess && pool.alloc(&s.d_byte, j->byte_words * 4) == hipSuccess &&
+                  pool.alloc(&s.d_prog, j->prog_words * 4) == hipSuccess;
+        if (!ok) {  // not fatal: fall back to the shared working buffers
+            (void)hipGetLastError();
+            for (uint32_t **d : {&s.d_cpu, &s.d_byte, &s.d_prog}) { pool.free(*d); *d = nullptr; }
+        }
+    }
+    lap("trace buffers");
+    int rc = shard_traces(c, pk, j, s, &traces, false);
+    if (rc) return rc;
+    lap("K0 launched");
+    Digest root;
+    if (!c.eng.commit_main_root(pk->key, traces, &root, keep)) return engine_fail(c.err, c.eng);
+    lap("main root");
+    for (int k = 0; k < 8; k++) s.header[k] = root.d[k].canonical();
+    for (uint32_t k = 0; k < N_PUB; k++) s.header[8 + k] = s.pubs[k].canonical();
+    s.header_valid = true;
+    return DVT_OK;
+}
+
+// phase 2 of a shard: K0..K9 with the common challenges -> shard proof words
+// (on any lane: the shard's phase-1 buffers came from lane 0's pool and are only read here)
+static int shard_prove(const Lane &c, const dvt_pk *pk, dvt_job *j, ShardJob &s, const PermChallenges &gc, std::vector<uint32_t> *words) {
+    std::vector<ChipTrace> traces;
+    int rc = shard_traces(c, pk, j, s, &traces, s.cache.valid);
+    if (rc) return rc;
+    ShardProof sp;
+    bool ok = c.eng.prove_shard(pk->key, traces, s.pubs, c.p->cfg, &sp, &gc, &s.cache);
+    (void)hipStreamSynchronize(c.eng.stream);
+    s.cache.valid = false;  // the buffers stay for the next commit of this shard (released with the job)
+    s.traces_valid = false;
+    s.header_valid = false;
+    if (!ok) return engine_fail(c.err, c.eng);
+    WordWriter w;
+    w.w.reserve((size_t)1 << 20);  // a shard proof is about 2.4 MB at 100 queries
+    write_shard_proof(w, sp);
+    *words = std::move(w.w);
+    return DVT_OK;
+}
+
+// ------------------------------------------------------------------ the prepare pipeline
+// One sequential FAST pass of the guest finds the shard boundaries and snapshots the machine there; trace-mode
+// executor threads re-run the owned shards from the snapshots into pinned buffers and build the small auxiliary
+// traces; the calling thread uploads shard i+1 on the copy stream while the GPU runs phase 1 (K0 + K1..K3 of the main
+// traces) of shard i.  (reference src/main.rs:461-466: prove() executes AND proves in one call.)
+namespace {
+struct ReadyShard {
+    rv32::CycleRec *buf = nullptr;
+    rv32::ShardMeta meta{};
+    rv32::HostTraces aux;
+    rv32::BigOpBatches big;   // the precompile calls of the shard: their chips' rows are built on the GPU
+    std::string err;
+    bool unsupported = false;
+};
+// what the fast pass found about the whole execution
+struct FastPass {
+    size_t n_total = 0;
+    std::vector<rv32::MemInitRow> mem_rows;
+    int exit_code = -1;
+    bool halted = false, unsupported = false;
+    uint64_t cycles = 0;
+    std::string error, unsupported_what;
+    std::vector<uint8_t> public_values;
+    uint32_t committed[8] = {}, committed_mask = 0;
+};
+
+// The executor side of a prepare, host threads only (no HIP calls): the fast pass and the trace-mode workers.  It hands
+// out the ready shard at a position and takes pinned buffers back; finish() (or the destructor) aborts and joins the threads.
+struct Executor {
+    std::mutex mu;
+    std::condition_variable cv;
+    std::deque<std::pair<size_t, rv32::Snapshot>> snaps;
+    bool snaps_closed = false, fast_done = false;
+    std::atomic<bool> abort{false};   // (also read outside the mutex by a worker that is about to build auxiliary traces)
+    std::vector<rv32::CycleRec *> free_bufs;
+    std::map<size_t, ReadyShard> ready;
+    FastPass fast;
+    rv32::CurveLog curve_log;
+    std::vector<std::thread> threads;   // the fast pass, then the workers
+
+    // the threads run the guest over `inputs`, which must outlive the executor; they start on the pinned buffers `bufs`
+    Executor(const dvt_pk *pk, const std::vector<std::vector<uint8_t>> &inputs, uint32_t log_shard, uint64_t max_cycles, size_t first,
+             size_t stride, unsigned n_workers, const std::vector<rv32::CycleRec *> &bufs, bool time_stages)
+        : free_bufs(bufs) {
+        threads.emplace_back([=, &inputs] {
+            rv32::Vm vm(pk->prog, &inputs, log_shard);
+            vm.curve_log = &curve_log;
+            struct Close { rv32::CurveLog &l; ~Close() { l.closed.store(true, std::memory_order_release); } } close_log{curve_log};
+            size_t pos = 0;
+            for (;; pos++) {
+                if (pos % stride == first) {
+                    rv32::Snapshot snap = vm.snapshot();
+                    std::unique_lock<std::mutex> lk(mu);
+                    cv.wait(lk, [&] { return snaps.size() < 2 * (size_t)n_workers + 2 || abort; });
+                    if (abort) break;
+                    snaps.emplace_back(pos, std::move(snap));
+                    cv.notify_all();
+                }
+                vm.run_shard(false, nullptr, max_cycles);
+                if (!vm.error.empty() || vm.halted || !vm.next_shard()) break;
+            }
+            std::vector<rv32::MemInitRow> rows;
+            if (vm.halted) rows = vm.mem_rows();
+            std::lock_guard<std::mutex> lk(mu);
+            fast.n_total = pos + 1;
+            fast.mem_rows = std::move(rows);
+            fast.exit_code = vm.exit_code; fast.halted = vm.halted; fast.cycles = vm.cycles; fast.error = vm.error;
+            fast.unsupported = vm.unsupported; fast.unsupported_what = vm.unsupported_what;
+            fast.public_values = std::move(vm.public_values);
+            for (int k = 0; k < 8; k++) fast.committed[k] = vm.committed[k];
+            fast.committed_mask = vm.committed_mask;
+            fast_done = snaps_closed = true;
+            cv.notify_all();
+        });
+        for (unsigned w = 0; w < n_workers; w++) threads.emplace_back([=, &inputs] {
+            for (;;) {
+                rv32::CycleRec *buf = nullptr;
+                size_t pos = 0;
+                rv32::Snapshot snap;
+                {
+                    // a buffer first, then the OLDEST snapshot: buffers are handed out in shard order, so the shard the GPU
+                    // thread waits for always has one
+                    std::unique_lock<std::mutex> lk(mu);
+                    cv.wait(lk, [&] { return abort || ((!snaps.empty() || snaps_closed) && (!free_bufs.empty() || snaps.empty())); });
+                    if (abort || snaps.empty()) return;
+                    buf = free_bufs.back();
+                    free_bufs.pop_back();
+                    pos = snaps.front().first;
+                    snap = std::move(snaps.front().second);
+                    snaps.pop_front();
+                    cv.notify_all();
+                }
+                ReadyShard r;
+                r.buf = buf;
+                const auto tw0 = Clock::now();
+                {
+                    rv32::Vm vm(pk->prog, &inputs, log_shard, snap);
+                    vm.curve_log = &curve_log;
+                    snap = rv32::Snapshot();
+                    rv32::ShardOut so;
+                    so.recs = buf;
+                    vm.run_shard(true, &so, max_cycles);
+                    const auto tw1 = Clock::now();
+                    r.meta = rv32::ShardMeta{so.index, so.start_pc, so.next_pc, so.n_recs};
+                    if (!vm.error.empty()) { r.err = vm.error; r.unsupported = vm.unsupported; }
+                    else {
+                        const std::vector<rv32::MemInitRow> *rows = nullptr;
+                        int ec = 0;
+                        if (vm.halted) {   // the last shard carries the mem_init table: final memory state of the fast pass
+                            std::unique_lock<std::mutex> lk(mu);
+                            cv.wait(lk, [&] { return fast_done || abort; });
+                            rows = &fast.mem_rows;
+                            ec = fast.exit_code;
+                        }
+                        std::string e;
+                        const auto tw2 = Clock::now();
+                        if (!abort && !rv32::build_aux_host(r.meta, so.alu, so.sha_ext, so.sha_cmp, so.big, rows, ec, pk->prep, &r.aux, &e, &r.big)) r.err = e;
+                        if (time_stages) {
+                            auto ms = [](Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+                            fprintf(stderr, "[prepare] shard %u: traced execution %.2f ms, wait for the fast pass %.2f ms, auxiliary traces %.2f ms\n", so.index, ms(tw0, tw1), ms(tw1, tw2),
+                                    ms(tw2, Clock::now()));
+                        }
+                    }
+                }
+                std::lock_guard<std::mutex> lk(mu);
+                ready[pos] = std::move(r);
+                cv.notify_all();
+            }
+        });
+    }
+    ~Executor() { finish(); }
+
+    // the ready shard at position pos; false when the execution has no shard there or the fast pass stopped on an error
+    bool take(size_t pos, ReadyShard *r, double *waited) {
+        std::unique_lock<std::mutex> lk(mu);
+        const auto t0 = Clock::now();
+        cv.wait(lk, [&] { return ready.count(pos) || (fast_done && pos >= fast.n_total) || (fast_done && !fast.error.empty()); });
+        *waited += std::chrono::duration<double>(Clock::now() - t0).count();
+        auto it = ready.find(pos);
+        if (it == ready.end()) return false;
+        *r = std::move(it->second);
+        ready.erase(it);
+        return true;
+    }
+    void give_back(rv32::CycleRec *b) {
+        std::lock_guard<std::mutex> lk(mu);
+        free_bufs.push_back(b);
+        cv.notify_all();
+    }
+    // stops and joins the threads: what the fast pass found is final
+    FastPass &finish() {
+        {
+            std::lock_guard<std::mutex> lk(mu);
+            abort = true;   // (everything is done on the success path; on errors this stops the threads)
+            cv.notify_all();
+        }
+        for (auto &t : threads)
+            if (t.joinable()) t.join();
+        return fast;
+    }
+};
+
+// what a chip of a ready shard uploads: its calls / events when K0 of the chip runs on the GPU (true), else the rows the
+// executor thread built (false)
+bool events_of(const ReadyShard &r, int c, const void **src, size_t *bytes) {
+    if (!r.big.ev[c].empty()) { *src = r.big.ev[c].data(); *bytes = r.big.ev[c].size() * sizeof(rv32::BigOpEvent); return true; }
+    if (c == RV32_CHIP_SHIFT && !r.big.shifts.empty()) { *src = r.big.shifts.data(); *bytes = r.big.shifts.size() * sizeof(rv32::AluEvent); return true; }
+    if (c == RV32_CHIP_MEM_INIT && r.big.mem_rows && !r.big.mem_rows->empty()) { *src = r.big.mem_rows->data(); *bytes = r.big.mem_rows->size() * sizeof(rv32::MemInitRow); return true; }
+    return false;
+}
+}  // namespace
+
+// upload of one ready shard into a new shard of the job: records on the copy stream (pinned source, overlaps the compute
+// stream; `ev` is recorded after them), the small auxiliary traces on the compute stream
+static int upload_shard(const Lane &lane, ReadyShard &r, dvt_job *j, hipEvent_t ev) {
+    dvt_prover *p = lane.p;
+    Engine &e = lane.eng;
+    const MachineDesc *m = machine_rv32();
+    j->shards.emplace_back();
+    ShardJob &s = j->shards.back();
+    s.index = r.meta.index; s.n_recs = r.meta.n_recs; s.next_pc = r.meta.next_pc;
+    for (int c = 0; c < m->n_chips; c++) { s.log_n[c] = r.aux.log_n[c]; s.present[c] = r.aux.present[c]; }
+    HIP_TRY(lane.err, e.pool.alloc(&s.d_recs, s.n_recs * sizeof(rv32::CycleRec)));
+    HIP_TRY(lane.err, hipMemcpyAsync(s.d_recs, r.buf, s.n_recs * sizeof(rv32::CycleRec), hipMemcpyHostToDevice, p->copy_stream));
+    HIP_TRY(lane.err, hipEventRecord(ev, p->copy_stream));
+    uint32_t *d_calls[rv32::N_CHIPS] = {};   // per precompile chip: [error word, padding to 16 bytes, the calls]
+    size_t stage_bytes = 0;
+    for (int c = 0; c < m->n_chips; c++) {
+        if (c == RV32_CHIP_CPU || !s.present[c]) continue;
+        const void *src = nullptr;
+        size_t bytes = 0;
+        if (!events_of(r, c, &src, &bytes)) bytes = r.aux.main[c].size() * 4;
+        stage_bytes += (bytes + 255) & ~(size_t)255;
+    }
+    if (stage_bytes > p->aux_pinned_bytes) {
+        HIP_TRY(lane.err, hipStreamSynchronize(e.stream));
+        if (p->aux_pinned) HIP_TRY(lane.err, hipHostFree(p->aux_pinned));
+        p->aux_pinned = nullptr; p->aux_pinned_bytes = 0;
+        HIP_TRY(lane.err, hipHostMalloc(&p->aux_pinned, stage_bytes + stage_bytes / 4));
+        p->aux_pinned_bytes = stage_bytes + stage_bytes / 4;
+    }
+    size_t stage_at = 0;
+    auto staged = [&](const void *src, size_t bytes) -> const void * {
+        uint8_t *dst = p->aux_pinned + stage_at;
+        memcpy(dst, src, bytes);
+        stage_at += (bytes + 255) & ~(size_t)255;
+        return dst;
+    };
+    size_t n_events[rv32::N_CHIPS] = {};
+    for (int c = 0; c < m->n_chips; c++) {
+        if (c == RV32_CHIP_CPU || !s.present[c]) continue;
+        const void *src = nullptr;
+        size_t bytes = 0;
+        if (events_of(r, c, &src, &bytes)) {   // K0 of this chip on the GPU (after the byte counts are in): [error word, padding to 16 bytes, the events]
+            const size_t words = (size_t)m->chips[c].main_w << s.log_n[c];
+            HIP_TRY(lane.err, e.pool.alloc(&s.d_aux[c], words * 4));
+            HIP_TRY(lane.err, hipMemsetAsync(s.d_aux[c], 0, words * 4, e.stream));
+            HIP_TRY(lane.err, e.pool.alloc(&d_calls[c], 16 + bytes));
+            HIP_TRY(lane.err, hipMemsetAsync(d_calls[c], 0, 16, e.stream));
+            HIP_TRY(lane.err, hipMemcpyAsync(d_calls[c] + 4, staged(src, bytes), bytes, hipMemcpyHostToDevice, e.stream));
+            n_events[c] = c == RV32_CHIP_SHIFT ? r.big.shifts.size() : c == RV32_CHIP_MEM_INIT ? r.big.mem_rows->size() : r.big.ev[c].size();
+            continue;
+        }
+        size_t words = r.aux.main[c].size();
+        HIP_TRY(lane.err, e.pool.alloc(&s.d_aux[c], words * 4));
+        HIP_TRY(lane.err, hipMemcpyAsync(s.d_aux[c], staged(r.aux.main[c].data(), words * 4), words * 4, hipMemcpyHostToDevice, e.stream));
+        // byte / program multiplicities stay plain integers until K0 has added the cpu rows' lookups
+        if (c != RV32_CHIP_BYTE && c != RV32_CHIP_PROGRAM) HIP_TRY(lane.err, launch_to_internal(e.stream, s.d_aux[c], words));
+    }
+    for (int c = 0; c < m->n_chips; c++) {
+        if (!d_calls[c]) continue;
+        const size_t words = (size_t)m->chips[c].main_w << s.log_n[c];
+        if (c == RV32_CHIP_SHIFT) {   // (these two write Montgomery words themselves)
+            HIP_TRY(lane.err, rv32::launch_k0_shift_rows(e.stream, reinterpret_cast<const rv32::AluEvent *>(d_calls[c] + 4), n_events[c], s.d_aux[c], s.log_n[c], s.d_aux[RV32_CHIP_BYTE]));
+        } else if (c == RV32_CHIP_MEM_INIT) {
+            HIP_TRY(lane.err, rv32::launch_k0_mem_init_rows(e.stream, reinterpret_cast<const rv32::MemInitRow *>(d_calls[c] + 4), n_events[c], s.d_aux[c], s.log_n[c], s.d_aux[RV32_CHIP_BYTE]));
+        } else {
+            HIP_TRY(lane.err, rv32::launch_k0_bigop_rows(e.stream, c, reinterpret_cast<const rv32::BigOpEvent *>(d_calls[c] + 4), (uint32_t)n_events[c], s.index,
+                                                       s.d_aux[c], s.log_n[c], s.d_aux[RV32_CHIP_BYTE], d_calls[c]));
+            HIP_TRY(lane.err, launch_to_internal(e.stream, s.d_aux[c], words));
+        }
+    }
+    HIP_TRY(lane.err, hipStreamSynchronize(e.stream));   // (the staging buffer is reused by the next shard; the error words below)
+    for (int c = 0; c < m->n_chips; c++) {
+        if (!d_calls[c]) continue;
+        uint32_t row_err = 0;
+        const hipError_t he = hipMemcpy(&row_err, d_calls[c], 4, hipMemcpyDeviceToHost);
+        e.pool.free(d_calls[c]);
+        HIP_TRY(lane.err, he);
+        if (row_err) return fail(lane.err, DVT_ERR_DEVICE, "K0 of chip %s: %s", m->chips[c].name, rv32::bigop_row_error_text(row_err));
+    }
+    for (auto x : r.aux.pubs) s.pubs.push_back(Fp::from_canonical(x));
+    return DVT_OK;
+}
+
+// Phase 1 of the job's shards in execution order, as the executor hands them over: the records of shard i+1 come in on the
+// copy stream while the GPU runs phase 1 of shard i.  Every pinned buffer goes back to the executor.
+static int commit_overlapped(const Lane &c, const dvt_pk *pk, dvt_job *j, Executor &ex, bool time_stages, Clock::time_point t_begin) {
+    int rc = DVT_OK;
+    hipEvent_t ev = nullptr;
+    (void)hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+    bool have_prev = false;
+    rv32::CycleRec *prev_buf = nullptr;
+    for (size_t pos = j->first; rc == DVT_OK; pos += j->stride) {
+        ReadyShard r;
+        const bool got = ex.take(pos, &r, &j->t_exec_wait);
+        if (got && !r.err.empty()) {
+            rc = r.unsupported ? fail(c.err, DVT_ERR_UNSUPPORTED, "no chip for an instruction of the guest (%s)", r.err.c_str())
+                               : fail(c.err, DVT_ERR_GUEST, "guest trapped: %s", r.err.c_str());
+            ex.give_back(r.buf);
+            break;
+        }
+        if (time_stages && got) fprintf(stderr, "[prepare] %.2f ms: shard at position %zu ready\n", ms_since(t_begin), pos);
+        if (got) rc = upload_shard(c, r, j, ev);
+        if (time_stages && got) fprintf(stderr, "[prepare] %.2f ms: uploaded\n", ms_since(t_begin));
+        // phase 1 of the previous shard runs while the copy engine brings this one in
+        if (rc == DVT_OK && have_prev) {
+            ShardJob &ps = j->shards[j->shards.size() - (got ? 2 : 1)];
+            rc = shard_commit(c, pk, j, ps);
+            ex.give_back(prev_buf);
+        }
+        if (!got) { have_prev = false; break; }
+        if (rc == DVT_OK) {
+            // the event is re-recorded per shard: wait for this copy before the buffer can be reused / the event re-armed.
+            // (the host waits, so the compute stream needs no dependency on the copy stream)
+            if (hipEventSynchronize(ev) != hipSuccess) rc = fail(c.err, DVT_ERR_DEVICE, "record upload failed");
+        }
+        have_prev = true;
+        prev_buf = r.buf;
+    }
+    if (rc == DVT_OK && have_prev) {
+        rc = shard_commit(c, pk, j, j->shards.back());
+        ex.give_back(prev_buf);
+    }
+    if (time_stages) fprintf(stderr, "[prepare] %.2f ms: phase 1 of the last shard done\n", ms_since(t_begin));
+    (void)hipEventDestroy(ev);
+    return rc;
+}
+
+// the verdict on the execution once the executor has stopped, given what phase 1 returned
+static int prepare_verdict(std::string &err, const FastPass &f, int rc) {
+    if (rc == DVT_ERR_GUEST && f.unsupported) return fail(err, DVT_ERR_UNSUPPORTED, "no chip for %s", f.unsupported_what.c_str());
+    if (rc) return rc;
+    if (!f.error.empty()) return fail(err, DVT_ERR_GUEST, "guest trapped: %s", f.error.c_str());
+    if (f.unsupported) return fail(err, DVT_ERR_UNSUPPORTED, "no chip for %s", f.unsupported_what.c_str());
+    if (f.exit_code != 0) return fail(err, DVT_ERR_GUEST, "guest halted with exit code %d", f.exit_code);
+    uint32_t want[8];
+    pv_digest_words(f.public_values, want);
+    bool ok = f.committed_mask == 0xff;
+    for (int k = 0; ok && k < 8; k++) ok = f.committed[k] == want[k];
+    if (!ok) return fail(err, DVT_ERR_GUEST, "guest did not COMMIT the SHA-256 digest of the %zu public-value bytes it wrote to fd 3", f.public_values.size());
+    return DVT_OK;
+}
+
+static int job_prepare(dvt_prover *p, const dvt_pk *pk, const dvt_buf *stdin_bufs, size_t nbuf, size_t first, size_t stride, dvt_job **out,
+                       dvt_report *report) {
+    if (stride == 0 || first >= stride) return fail(p, DVT_ERR_INPUT, "bad shard partition %zu / %zu", first, stride);
+    unsigned hw = std::thread::hardware_concurrency();
+    const unsigned n_workers = p->exec_threads ? p->exec_threads : std::max(1u, std::min(6u, hw > 3 ? hw - 2 : 1u));
+    // pinned staging: one buffer per worker + two in flight on the GPU side
+    const size_t want_bufs = n_workers + 2;
+    while (p->pinned.size() < want_bufs) {
+        rv32::CycleRec *b = nullptr;
+        HIP_TRY(p, hipHostMalloc(&b, sizeof(rv32::CycleRec) << p->log_shard));
+        p->pinned.push_back(b);
+    }
+    const bool time_stages = getenv("DVT_TIME_PREPARE") != nullptr;   // (stderr: where the host side of a prepare goes)
+    const auto t_begin = Clock::now();
+    const std::vector<std::vector<uint8_t>> inputs = collect_stdin(stdin_bufs, nbuf);
+    Executor ex(pk, inputs, p->log_shard, p->max_cycles, first, stride, n_workers, p->pinned, time_stages);
+    dvt_job *j = new dvt_job();
+    j->first = first; j->stride = stride;
+    j->byte_words = (size_t)rv32::N_BYTE_OPS * 65536;
+    j->prog_words = (size_t)1 << pk->prep.log_n[RV32_CHIP_PROGRAM];
+    int rc = commit_overlapped(lane0(p), pk, j, ex, time_stages, t_begin);
+    FastPass &f = ex.finish();
+    if (time_stages) fprintf(stderr, "[prepare] %.2f ms: threads joined\n", ms_since(t_begin));
+    if (report) {
+        report->cycles = f.cycles;
+        report->exit_code = f.halted ? f.exit_code : -1;
+        report->halted = f.halted;
+        report->unprovable = f.unsupported;
+    }
+    rc = prepare_verdict(p->err, f, rc);
+    if (rc) { job_release(p, j); return rc; }
+    j->exit_code = f.exit_code;
+    j->cycles = f.cycles;
+    j->public_values = std::move(f.public_values);
+    j->n_total = f.n_total;
+    *out = j;
+    return DVT_OK;
+}
+
+// ------------------------------------------------------------------ the phase-2 pipeline (Phase2Pipe)
+// the further lanes' engines, made on the first job that has at least two shards to prove
+static int ensure_lanes(dvt_prover *p) {
+    for (int k = 1; k < p->lanes; k++) {
+        if (p->more[k - 1]) continue;
+        std::unique_ptr<Engine> e(new Engine());
+        e->profile = false;
+        e->parts_parallel_log = p->eng.parts_parallel_log;
+        const hipError_t r = e->init(p->eng.device);
+        if (r != hipSuccess) {
+            e->shutdown();
+            return fail(p, DVT_ERR_DEVICE, "prover lane %d: %s", k, hipGetErrorString(r));
+        }
+        p->more[k - 1] = std::move(e);
+    }
+    return DVT_OK;
+}
+
+static void pipe_worker(dvt_prover *p, Phase2Pipe *pp, PermChallenges gc, int k) {
+    std::string err;
+    const Lane c{p, k, lane_engine(p, k), err};
+    const hipError_t dev = hipSetDevice(p->eng.device);
+    for (;;) {
+        size_t i;
+        {
+            std::unique_lock<std::mutex> lk(pp->mu);
+            pp->cv.wait(lk, [&] { return pp->stop || pp->failed || pp->next >= pp->slots.size() || pp->next < pp->limit; });
+            if (pp->stop || pp->failed || pp->next >= pp->slots.size()) return;
+            i = pp->next++;
+            pp->slots[i].state = 1;
+        }
+        std::vector<uint32_t> words;
+        err.clear();
+        const int rc = dev != hipSuccess ? fail(err, DVT_ERR_DEVICE, "hipSetDevice: %s", hipGetErrorString(dev))
+                                         : shard_prove(c, pp->pk, pp->job, pp->job->shards[pp->slots[i].shard], gc, &words);
+        std::lock_guard<std::mutex> lk(pp->mu);
+        Phase2Pipe::Slot &s = pp->slots[i];
+        s.rc = rc;
+        s.err = std::move(err);
+        s.words = std::move(words);
+        s.state = 2;
+        if (rc) pp->failed = true;   // the other lanes stop at their next shard boundary
+        pp->cv.notify_all();
+    }
+}
+
+// Starts the pipeline over the job's shards with a valid header, in job order from shard index k0 (which must be one of
+// them).  Returns DVT_OK with p->pipe set; DVT_OK without a pipeline when there is nothing to run ahead (one lane, or
+// fewer than two such shards).  Caller holds p->mu; no pipeline runs.
+static int pipe_start(dvt_prover *p, const dvt_pk *pk, dvt_job *j, size_t k0, const PermChallenges &gc) {
+    if (p->lanes < 2 || k0 >= j->shards.size() || !j->shards[k0].header_valid) return DVT_OK;
+    std::vector<size_t> order;
+    for (size_t k = k0; k < j->shards.size(); k++)
+        if (j->shards[k].header_valid) order.push_back(k);
+    if (order.size() < 2) return DVT_OK;
+    int rc = ensure_lanes(p);
+    if (rc) return rc;
+    HIP_TRY(p, hipStreamSynchronize(p->eng.stream));   // phase 1 (lane 0) is complete before another lane reads its buffers
+    std::unique_ptr<Phase2Pipe> pp(new Phase2Pipe());
+    pp->job = j;
+    pp->pk = pk;
+    for (int k = 0; k < 4; k++) { pp->ch[k] = gc.alpha.c[k].canonical(); pp->ch[4 + k] = gc.beta.c[k].canonical(); }
+    pp->slots.resize(order.size());
+    for (size_t i = 0; i < order.size(); i++) pp->slots[i].shard = order[i];
+    pp->limit = (size_t)p->lanes;   // (the caller claims slot 0 next)
+    const int n_workers = (int)std::min<size_t>((size_t)p->lanes, order.size());
+    for (int k = 0; k < n_workers; k++) pp->workers.emplace_back(pipe_worker, p, pp.get(), gc, k);
+    p->pipe = std::move(pp);
+    return DVT_OK;
+}
+
+// Waits for a slot's words.  Taking the last unclaimed slot ends the pipeline (nothing is left to run ahead).  On a failure
+// the pipeline is drained and the error of the lowest failed shard is reported.
+static int pipe_claim(dvt_prover *p, size_t slot, std::vector<uint32_t> *words) {
+    Phase2Pipe &pp = *p->pipe;
+    bool ok, last;
+    {
+        std::unique_lock<std::mutex> lk(pp.mu);
+        pp.limit = std::max(pp.limit, slot + (size_t)p->lanes);
+        pp.cv.notify_all();
+        pp.cv.wait(lk, [&] { return pp.slots[slot].state == 2 || (pp.failed && pp.slots[slot].state == 0); });
+        Phase2Pipe::Slot &s = pp.slots[slot];
+        ok = s.state == 2 && s.rc == 0;
+        if (ok) {
+            s.claimed = true;
+            *words = std::move(s.words);
+        }
+        last = std::all_of(pp.slots.begin(), pp.slots.end(), [](const Phase2Pipe::Slot &x) { return x.claimed; });
+    }
+    if (ok) {
+        if (last) (void)pipe_drain(p);
+        return DVT_OK;
+    }
+    std::string why;
+    const int rc = pipe_drain(p, &why);
+    return fail(p, rc ? rc : DVT_ERR_DEVICE, "%s", rc ? why.c_str() : "phase-2 pipeline stopped");
+}
+
+// both phases on one GPU; the job must hold every shard of the execution.  Leaves no pipeline running.
+static int job_prove(dvt_prover *p, const dvt_pk *pk, dvt_job *j, uint8_t **proof, size_t *proof_len) {
+    const size_t n = j->shards.size();
+    if (n != j->n_total) return fail(p, DVT_ERR_INPUT, "this job holds %zu of the execution's %zu shards: prove them shard by shard", n, j->n_total);
+    const Lane c = lane0(p);
+    std::vector<uint32_t> headers(n * HEADER_WORDS);
+    for (size_t i = 0; i < n; i++) {
+        if (!j->shards[i].header_valid) {
+            int rc = shard_commit(c, pk, j, j->shards[i]);
+            if (rc) return rc;
+        }
+        memcpy(headers.data() + i * HEADER_WORDS, j->shards[i].header, sizeof(uint32_t) * HEADER_WORDS);
+    }
+    PermChallenges gc = global_challenges(pk->key.vk, headers.data(), n);
+    std::vector<std::vector<uint32_t>> shards(n);
+    int rc = pipe_start(p, pk, j, 0, gc);
+    if (rc) return rc;
+    for (size_t i = 0; i < n; i++) {   // (every shard is in the pipeline when one runs: its last claim ends it)
+        rc = p->pipe ? pipe_claim(p, i, &shards[i]) : shard_prove(c, pk, j, j->shards[i], gc, &shards[i]);
+        if (rc) return rc;
+    }
+    (void)hipStreamSynchronize(p->eng.stream);
+    if (!proof) return DVT_OK;  // timing runs may discard the bytes
+    *proof = copy_out(write_core_proof({(uint32_t)j->exit_code, j->public_values, std::move(shards)}), proof_len);
+    if (!*proof) return fail(p, DVT_ERR_DEVICE, "out of host memory");
+    return DVT_OK;
+}
+
+// The rv32 checks of a parsed container: shard chaining through the public values, the chip set of every shard, each
+// shard's proof under the common challenges, and the COMMIT-digest balance.  "" or why the proof is rejected.
+static std::string verify_core(const VerifyingKey &key, const CoreProof &cp, const StarkConfig &cfg) {
+    const size_t nshards = cp.shards.size();
+    std::vector<ShardProof> sps(nshards);
+    for (size_t i = 0; i < nshards; i++) {
+        WordReader sr(cp.shards[i].data(), cp.shards[i].size());
+        sps[i] = read_shard_proof(sr);
+        if (sr.p != sr.end) return "trailing words after a shard proof";
+    }
+    // shard chaining through the public values
+    std::vector<uint32_t> headers(nshards * HEADER_WORDS);
+    for (size_t i = 0; i < nshards; i++) {
+        const ShardProof &sp = sps[i];
+        if (sp.public_values.size() != N_PUB) return "wrong number of public values";
+        uint32_t pubv[N_PUB];
+        for (uint32_t k = 0; k < N_PUB; k++) pubv[k] = sp.public_values[k].canonical();
+        const bool last = i + 1 == nshards;
+        if (pubv[3] != i + 1) return "shard index out of sequence";
+        if (pubv[4] != (last ? 1u : 0u)) return "is_last flag does not match the shard's position";
+        if (i == 0 && pubv[0] != key.extra[0] % P) return "first shard does not start at the entry point";
+        if (i > 0 && pubv[0] != sps[i - 1].public_values[1].canonical()) return "shards do not chain (pc)";
+        // only a HALT row has next_pc = HALT_PC (tools/airgen/rv32.py): control flow that merely reaches address 0 does not count
+        if (last && pubv[1] != rv32::HALT_PC) return "execution did not halt";
+        if (!last && pubv[1] == rv32::HALT_PC) return "halt before the last shard";
+        if (last && pubv[2] != cp.exit_code % P) return "exit code mismatch";
+        // chip set: program, byte, cpu, mem_image always; mem_init in the last shard only; shift / muldiv when the shard uses them
+        bool have[rv32::N_CHIPS] = {};
+        for (auto &c : sp.chips) {
+            if (c.chip_id >= (uint32_t)rv32::N_CHIPS) return "chip id out of range";
+            have[c.chip_id] = true;
+        }
+        for (int c : {RV32_CHIP_PROGRAM, RV32_CHIP_BYTE, RV32_CHIP_CPU, RV32_CHIP_MEM_IMAGE})
+            if (!have[c]) return "a mandatory chip is missing from a shard";
+        if (have[RV32_CHIP_MEM_INIT] != last) return "mem_init must be part of exactly the last shard";
+        for (int k = 0; k < 8; k++) headers[i * HEADER_WORDS + k] = sp.main_root.d[k].canonical();
+        for (uint32_t k = 0; k < N_PUB; k++) headers[i * HEADER_WORDS + 8 + k] = pubv[k];
+    }
+    PermChallenges gc = global_challenges(key, headers.data(), nshards);
+    Fp4 total = Fp4::zero();
+    for (size_t i = 0; i < nshards; i++) {
+        Fp4 t;
+        std::string why = verify_shard(key, sps[i], cfg, &gc, &t);
+        if (!why.empty()) return "shard " + std::to_string(i + 1) + ": " + why;
+        total += t;
+    }
+    // The receiving side of the COMMIT rows' sys-bus tuples is supplied here, from the claimed bytes: an SP1 guest commits
+    // the eight words of SHA-256(public-value bytes) with COMMIT(k, word k); the cpu chip sends
+    // (t0 bytes = 0x10 0 0 0, a0 bytes = k 0 0 0, a1 bytes = the bytes of digest word k, 0, 0), tuple k contributes
+    // 1 / (alpha + bus + beta 0x10 + beta^5 k + beta^9 b0 + ... + beta^12 b3).
+    uint8_t dg[32];
+    sha256(cp.public_values.data(), cp.public_values.size(), dg);
+    Fp4 bp[13];
+    bp[1] = gc.beta;
+    for (int k = 2; k < 13; k++) bp[k] = bp[k - 1] * gc.beta;
+    Fp4 expect = Fp4::zero();
+    for (uint32_t k = 0; k < 8; k++) {
+        Fp4 d = gc.alpha + Fp::from_canonical(PV_BUS) + bp[1] * Fp::from_canonical(rv32::SYS_COMMIT) + bp[5] * Fp::from_canonical(k);
+        for (int b = 0; b < 4; b++) d += bp[9 + b] * Fp::from_canonical(dg[4 * k + b]);
+        expect += inv(d);
+    }
+    if (total != expect) return "LogUp cumulative sums do not cancel across the shards (memory bus or public-values digest)";
+    return "";
+}
+
+static std::vector<uint32_t> trace_blob(const rv32::HostTraces &T, const rv32::HostPrep *prep) {
+    const MachineDesc *m = machine_rv32();
+    std::vector<uint32_t> w;
+    uint32_t present = 0;
+    for (int c = 0; c < m->n_chips; c++) present += T.present[c];
+    w.push_back(present);
+    for (int c = 0; c < m->n_chips; c++)
+        if (T.present[c]) { w.push_back(c); w.push_back(T.log_n[c]); w.push_back(m->chips[c].main_w); w.push_back(prep ? m->chips[c].prep_w : 0); }
+    w.push_back((uint32_t)T.pubs.size());
+    w.insert(w.end(), T.pubs.begin(), T.pubs.end());
+    for (int c = 0; c < m->n_chips; c++) {
+        if (!T.present[c]) continue;
+        w.insert(w.end(), T.main[c].begin(), T.main[c].end());
+        if (prep) w.insert(w.end(), prep->prep[c].begin(), prep->prep[c].end());
+    }
+    return w;
+}
+
+extern "C" {
+
+int dvt_setup(dvt_prover *p, const uint8_t *elf, size_t elf_len, dvt_pk **pk_out, uint8_t **vk, size_t *vk_len) {
+    if (!p || !elf || !pk_out) return fail(p, DVT_ERR_INPUT, "null argument");
+    Guard g(p); if (g.rc) return g.rc;
+    dvt_pk *pk = new dvt_pk();
+    std::string err;
+    if (!rv32::load_elf(elf, elf_len, &pk->prog, &err)) return setup_finish(p, pk, fail(p, DVT_ERR_INPUT, "ELF: %s", err.c_str()), pk_out, vk, vk_len);
+    rv32::build_prep(pk->prog, &pk->prep);
+    pk->is_rv32 = true;
+    std::vector<ChipRef> refs;
+    std::vector<std::vector<uint32_t>> host;
+    for (int c : {RV32_CHIP_PROGRAM, RV32_CHIP_BYTE, RV32_CHIP_MEM_IMAGE}) {
+        refs.push_back({c, pk->prep.log_n[c]});
+        host.push_back(pk->prep.prep[c]);
+    }
+    if (!p->eng.setup(machine_rv32(), refs, host, &pk->key)) return setup_finish(p, pk, engine_fail(p->err, p->eng), pk_out, vk, vk_len);
+    pk->key.vk.extra = {pk->prog.entry};
+    std::vector<uint32_t> rowmap = rv32::program_row_map(pk->prog);
+    size_t ib = pk->prog.instrs.size() * sizeof(rv32::Instr);
+    if (hipMalloc(&pk->d_instrs, ib) != hipSuccess || hipMalloc(&pk->d_prog_row, rowmap.size() * 4) != hipSuccess ||
+        hipMemcpy(pk->d_instrs, pk->prog.instrs.data(), ib, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(pk->d_prog_row, rowmap.data(), rowmap.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
+        return setup_finish(p, pk, fail(p, DVT_ERR_DEVICE, "uploading the program table failed"), pk_out, vk, vk_len);
+    return setup_finish(p, pk, DVT_OK, pk_out, vk, vk_len);
+}
+
+int dvt_execute_io(const uint8_t *elf, size_t elf_len, const dvt_buf *stdin_bufs, size_t nbuf, uint64_t max_cycles,
+                   uint8_t **public_values, size_t *pv_len, uint8_t **stdout_bytes, size_t *stdout_len, dvt_report *report, char **err_text) {
+    if (err_text) *err_text = nullptr;
+    if (public_values) *public_values = nullptr;
+    if (stdout_bytes) *stdout_bytes = nullptr;
+    if (!elf || (nbuf && !stdin_bufs)) return DVT_ERR_INPUT;
+    rv32::Program prog;
+    std::string err;
+    if (!rv32::load_elf(elf, elf_len, &prog, &err)) {
+        if (err_text) *err_text = strdup(("ELF: " + err).c_str());
+        return DVT_ERR_INPUT;
+    }
+    rv32::ExecResult res;
+    rv32::execute(prog, collect_stdin(stdin_bufs, nbuf), false, max_cycles ? max_cycles : ~0ull, 21, &res);
+    if (report) {
+        report->cycles = res.cycles;
+        report->exit_code = res.halted ? res.exit_code : -1;
+        report->halted = res.halted;
+        report->unprovable = res.unsupported;
+    }
+    if (public_values) *public_values = dup_bytes(res.public_values, pv_len);
+    if (stdout_bytes) *stdout_bytes = dup_bytes(res.stdout_bytes, stdout_len);
+    if (!res.error.empty()) {
+        if (err_text) *err_text = strdup(res.error.c_str());
+        return DVT_ERR_GUEST;
+    }
+    if (res.exit_code != 0) {
+        if (err_text) *err_text = strdup("guest halted with a non-zero exit code");
+        return DVT_ERR_GUEST;
+    }
+    return DVT_OK;
+}
+int dvt_execute(const uint8_t *elf, size_t elf_len, const dvt_buf *stdin_bufs, size_t nbuf, uint64_t max_cycles,
+                uint8_t **public_values, size_t *pv_len, dvt_report *report, char **err_text) {
+    return dvt_execute_io(elf, elf_len, stdin_bufs, nbuf, max_cycles, public_values, pv_len, nullptr, nullptr, report, err_text);
+}
+
+int dvt_rv32_prepare(dvt_prover *p, const dvt_pk *pk, const dvt_buf *stdin_bufs, size_t nbuf, dvt_job **job, dvt_report *report) {
+    return dvt_rv32_prepare_part(p, pk, stdin_bufs, nbuf, 0, 1, job, report);
+}
+int dvt_rv32_prepare_part(dvt_prover *p, const dvt_pk *pk, const dvt_buf *stdin_bufs, size_t nbuf, size_t first, size_t stride, dvt_job **job,
+                          dvt_report *report) {
+    if (!p || !pk || !job || (nbuf && !stdin_bufs)) return fail(p, DVT_ERR_INPUT, "null argument");
+    if (!pk->is_rv32) return fail(p, DVT_ERR_INPUT, "proving key was not made by dvt_setup");
+    Guard g(p); if (g.rc) return g.rc;
+    return job_prepare(p, pk, stdin_bufs, nbuf, first, stride, job, report);
+}
+int dvt_rv32_prove_job(dvt_prover *p, const dvt_pk *pk, dvt_job *job, uint8_t **proof, size_t *proof_len) {
+    if (!p || !pk || !job || (proof && !proof_len)) return fail(p, DVT_ERR_INPUT, "null argument");
+    Guard g(p); if (g.rc) return g.rc;
+    return job_prove(p, pk, job, proof, proof_len);
+}
+void dvt_job_free(dvt_prover *p, dvt_job *job) {
+    if (!p || !job) return;
+    Guard g(p);
+    job_release(p, job);
+}
+size_t dvt_rv32_job_shards(const dvt_job *job) { return job ? job->n_total : 0; }
+double dvt_rv32_job_exec_wait_seconds(const dvt_job *job) { return job ? job->t_exec_wait : 0.0; }
+
+int dvt_rv32_commit_shard(dvt_prover *p, const dvt_pk *pk, dvt_job *job, size_t shard, uint32_t *header) {
+    if (!p || !pk || !job || !header) return fail(p, DVT_ERR_INPUT, "bad argument");
+    ShardJob *s = job->at(shard);
+    if (!s) return fail(p, DVT_ERR_INPUT, "shard %zu is not held by this job", shard);
+    Guard g(p); if (g.rc) return g.rc;
+    if (!s->header_valid) {   // (the prepare pipeline already ran phase 1; a second proof of the same job runs it again)
+        int rc = shard_commit(lane0(p), pk, job, *s);
+        if (rc) return rc;
+    }
+    memcpy(header, s->header, sizeof(uint32_t) * HEADER_WORDS);
+    return DVT_OK;
+}
+uint32_t dvt_rv32_header_words(void) { return HEADER_WORDS; }
+int dvt_rv32_challenges(const uint8_t *vk, size_t vk_len, const uint32_t *headers, size_t n, uint32_t out[8]) {
+    VerifyingKey key;
+    if (!vk || !headers || !out || !n || !vk_parse(vk, vk_len, &key)) return DVT_ERR_INPUT;
+    for (size_t i = 0; i < n * HEADER_WORDS; i++)
+        if (headers[i] >= P && (i % HEADER_WORDS) < 8) return DVT_ERR_INPUT;
+    PermChallenges c = global_challenges(key, headers, n);
+    for (int k = 0; k < 4; k++) { out[k] = c.alpha.c[k].canonical(); out[4 + k] = c.beta.c[k].canonical(); }
+    return DVT_OK;
+}
+int dvt_rv32_prove_shard(dvt_prover *p, const dvt_pk *pk, dvt_job *job, size_t shard, const uint32_t challenges[8], uint8_t **proof,
+                         size_t *proof_len) {
+    if (!p || !pk || !job || !challenges || (proof && !proof_len)) return fail(p, DVT_ERR_INPUT, "bad argument");
+    ShardJob *s = job->at(shard);
+    if (!s) return fail(p, DVT_ERR_INPUT, "shard %zu is not held by this job", shard);
+    PermChallenges gc;
+    for (int k = 0; k < 4; k++) {
+        if (challenges[k] >= P || challenges[4 + k] >= P) return fail(p, DVT_ERR_INPUT, "challenge not canonical");
+        gc.alpha.c[k] = Fp::from_canonical(challenges[k]);
+        gc.beta.c[k] = Fp::from_canonical(challenges[4 + k]);
+    }
+    // phase 2 runs ahead on the prover lanes: the first call of a job starts the pipeline, later calls with the same
+    // challenges collect from it; anything else drains it (the guard) and takes the one-lane path
+    const size_t k = (size_t)(s - job->shards.data());
+    const PipeClaim claim{job, pk, challenges, k};
+    Guard g(p, &claim); if (g.rc) return g.rc;
+    long slot = g.slot;
+    if (!p->pipe) {
+        int rc = pipe_start(p, pk, job, k, gc);
+        if (rc) return rc;
+        if (p->pipe) slot = 0;
+    }
+    std::vector<uint32_t> words;
+    int rc = slot >= 0 ? pipe_claim(p, (size_t)slot, &words) : shard_prove(lane0(p), pk, job, *s, gc, &words);
+    if (rc || !proof) return rc;
+    *proof = copy_out(words, proof_len);
+    return *proof ? DVT_OK : fail(p, DVT_ERR_DEVICE, "out of host memory");
+}
+int dvt_rv32_assemble(const dvt_job *job, const uint8_t *const *shard_proofs, const size_t *lens, size_t n, uint8_t **proof, size_t *proof_len) {
+    if (!job || !shard_proofs || !lens || !proof || !proof_len || n != job->n_total) return DVT_ERR_INPUT;
+    std::vector<std::vector<uint32_t>> shards(n);
+    for (size_t i = 0; i < n; i++) {
+        if (lens[i] % 4 || !shard_proofs[i]) return DVT_ERR_INPUT;
+        shards[i].resize(lens[i] / 4);
+        memcpy(shards[i].data(), shard_proofs[i], lens[i]);
+    }
+    *proof = copy_out(write_core_proof({(uint32_t)job->exit_code, job->public_values, std::move(shards)}), proof_len);
+    return *proof ? DVT_OK : DVT_ERR_DEVICE;
+}
+
+int dvt_prove_core(dvt_prover *p, const dvt_pk *pk, const dvt_buf *stdin_bufs, size_t nbuf, uint8_t **proof, size_t *proof_len,
+                   dvt_report *report) {
+    if (!p || !pk || !proof || !proof_len || (nbuf && !stdin_bufs)) return fail(p, DVT_ERR_INPUT, "null argument");
+    if (!pk->is_rv32) return fail(p, DVT_ERR_INPUT, "proving key was not made by dvt_setup");
+    Guard g(p); if (g.rc) return g.rc;
+    dvt_job *j = nullptr;
+    int rc = job_prepare(p, pk, stdin_bufs, nbuf, 0, 1, &j, report);
+    if (rc) return rc;
+    rc = job_prove(p, pk, j, proof, proof_len);
+    job_release(p, j);
+    return rc;
+}
+
+int dvt_verify(const uint8_t *vk, size_t vk_len, const uint8_t *proof, size_t proof_len, uint32_t fri_queries, uint32_t pow_bits,
+               int32_t *exit_code, uint8_t **public_values, size_t *pv_len, char **reason) {
+    if (reason) *reason = nullptr;
+    if (public_values) *public_values = nullptr;
+    if (!vk || !proof) return reject(reason, DVT_ERR_INPUT, "null argument");
+    VerifyingKey key;
+    if (!vk_parse(vk, vk_len, &key) || key.machine != machine_rv32() || key.extra.size() != 1) return reject(reason, DVT_ERR_INPUT, "malformed verifying key");
+    return verify_words(proof, proof_len, DVT_ERR_REJECTED, reason, [&](WordReader &r, std::string &why) {
+        // the caller states the FRI parameters it accepts; refuse settings that verify nothing
+        // (blow-up 2: one bit of security per query, plus the proof-of-work bits)
+        if (fri_queries == 0 || fri_queries > 1024 || pow_bits > 30) {
+            why = "fri_queries must be 1..1024 and pow_bits <= 30";
+            return DVT_ERR_INPUT;
+        }
+        const CoreProof cp = read_core_proof(r);
+        why = verify_core(key, cp, StarkConfig{fri_queries, pow_bits});
+        if (!why.empty()) return DVT_ERR_REJECTED;
+        if (exit_code) *exit_code = (int32_t)cp.exit_code;
+        if (public_values) *public_values = dup_bytes(cp.public_values, pv_len);
+        return DVT_OK;
+    });
+}
+
+int dvt_rv32_debug_traces(const uint8_t *elf, size_t elf_len, const dvt_buf *stdin_bufs, size_t nbuf, uint32_t log_shard, uint32_t shard,
+                          uint32_t *n_shards, uint32_t **blob, size_t *blob_words, char **err_text) {
+    if (err_text) *err_text = nullptr;
+    if (!elf || !blob || !blob_words) return DVT_ERR_INPUT;
+    auto bad = [&](int code, const std::string &m) { if (err_text) *err_text = strdup(m.c_str()); return code; };
+    rv32::Program prog;
+    std::string err;
+    if (!rv32::load_elf(elf, elf_len, &prog, &err)) return bad(DVT_ERR_INPUT, "ELF: " + err);
+    rv32::HostPrep prep;
+    rv32::build_prep(prog, &prep);
+    rv32::ExecResult res;
+    rv32::execute(prog, collect_stdin(stdin_bufs, nbuf), true, 1ull << 32, log_shard ? log_shard : 21, &res);
+    if (!res.error.empty()) return bad(DVT_ERR_GUEST, res.error);
+    if (n_shards) *n_shards = (uint32_t)res.shards.size();
+    rv32::HostTraces T;
+    if (!rv32::build_traces_host(prog, res, shard, prep, &T, &err)) return bad(DVT_ERR_UNSUPPORTED, err);
+    const std::vector<uint32_t> w = trace_blob(T, &prep);
+    if (!(*blob = reinterpret_cast<uint32_t *>(copy_out(w, blob_words)))) return bad(DVT_ERR_DEVICE, "out of host memory");
+    *blob_words = w.size();
+    return DVT_OK;
+}
+
+// test hook: run K0 on shard `shard` of a prepared job and return the device-generated main traces (canonical),
+// same blob layout as dvt_rv32_debug_traces but without preprocessed columns (prep_width = 0)
+int dvt_rv32_debug_device_traces(dvt_prover *p, const dvt_pk *pk, dvt_job *j, size_t shard, uint32_t **blob, size_t *blob_words) {
+    if (!p || !pk || !j || !blob || !blob_words || !j->at(shard)) return fail(p, DVT_ERR_INPUT, "bad argument");
+    Guard g(p); if (g.rc) return g.rc;
+    std::vector<ChipTrace> traces;
+    ShardJob &sj = *j->at(shard);
+    int rc = shard_traces(lane0(p), pk, j, sj, &traces, false);
+    if (rc) return rc;
+    HIP_TRY(p, hipStreamSynchronize(p->eng.stream));
+    const MachineDesc *m = machine_rv32();
+    rv32::HostTraces T;
+    for (int c = 0; c < rv32::N_CHIPS; c++) T.present[c] = false;
+    for (auto &t : traces) {
+        size_t words = (size_t)m->chips[t.chip_id].main_w << t.log_n;
+        T.present[t.chip_id] = true;
+        T.log_n[t.chip_id] = t.log_n;
+        T.main[t.chip_id].resize(words);
+        HIP_TRY(p, hipMemcpy(T.main[t.chip_id].data(), t.d_main, words * 4, hipMemcpyDeviceToHost));
+        for (auto &x : T.main[t.chip_id]) x = Fp::raw(x).canonical();
+    }
+    for (auto x : sj.pubs) T.pubs.push_back(x.canonical());
+    const std::vector<uint32_t> w = trace_blob(T, nullptr);
+    if (!(*blob = reinterpret_cast<uint32_t *>(copy_out(w, blob_words)))) return fail(p, DVT_ERR_DEVICE, "out of host memory");
+    *blob_words = w.size();
+    return DVT_OK;
+}
+
+// measurement hook (host only): guest cycles per second of the executor alone, fast mode (trace = 0: what the
+// sequential pass of the prove pipeline runs) or trace mode (one 48-byte record per cycle into a reused buffer)
+double dvt_debug_exec_rate(const uint8_t *elf, size_t elf_len, const dvt_buf *stdin_bufs, size_t nbuf, uint32_t log_shard, int trace) {
+    rv32::Program prog;
+    std::string err;
+    if (!elf || !rv32::load_elf(elf, elf_len, &prog, &err)) return 0.0;
+    const std::vector<std::vector<uint8_t>> inputs = collect_stdin(stdin_bufs, nbuf);
+    std::vector<rv32::CycleRec> buf;
+    if (trace) buf.resize((size_t)1 << log_shard);
+    rv32::ShardOut out;
+    out.recs = buf.data();
+    const auto t0 = Clock::now();
+    rv32::Vm vm(prog, &inputs, log_shard);
+    for (;;) {
+        vm.run_shard(trace != 0, &out, ~0ull);
+        if (vm.halted || !vm.error.empty() || !vm.next_shard()) break;
+    }
+    const double dt = std::chrono::duration<double>(Clock::now() - t0).count();
+    return vm.halted ? (double)vm.cycles / dt : 0.0;
+}
+
+// test hook (host only): the FP64 formulation of Poseidon2 that the hashing kernels run, evaluated on the host
+// (IEEE doubles + fma, the same arithmetic) against the integer permutation on n pseudo-random and edge-case states,
+// through the same Montgomery conversions the kernels use.  Returns the number of differing words.
+uint64_t dvt_debug_p2_f64_selfcheck(uint32_t n, uint32_t seed) {
+    uint64_t bad = 0, x = 0x9e3779b97f4a7c15ull ^ seed;
+    for (uint32_t t = 0; t < n; t++) {
+        Fp a[16];
+        double b[16];
+        for (int i = 0; i < 16; i++) {
+            x ^= x << 13; x ^= x >> 7; x ^= x << 17;
+            uint32_t v = (uint32_t)(x % P);
+            if (t < 4) v = t == 0 ? 0 : t == 1 ? P - 1 : t == 2 ? (P - 1) / 2 + (i & 1) : (i ? P - i : 1);
+            a[i] = Fp::from_canonical(v);
+            b[i] = p2f::from_mont(a[i].v);
+        }
+        for (int rep = 0; rep < 3; rep++) {  // chained: the second and third calls start from lazy (signed) outputs
+            p2_permute(a);
+            p2f::permute(b);
+            for (int i = 0; i < 16; i++) bad += (a[i].v != p2f::to_mont(b[i])) + (a[i].canonical() != p2f::to_canonical(b[i]));
+        }
+    }
+    return bad;
+}
+
+}  // extern "C"

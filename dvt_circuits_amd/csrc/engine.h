@@ -248,7 +248,7 @@ class Engine {
   private:
     char *d_ring = nullptr, *h_ring = nullptr;
     char *h_down = nullptr;  // pinned staging for downloads (roots, opened values, query data): no pageable-memory path
-    static constexpr size_t DOWN_BYTES = 16u << 20;   // (every download of a proof goes through this pinned buffer: see the note on pageable memory in capi.hip)
+    static constexpr size_t DOWN_BYTES = 16u << 20;   // (every download of a proof goes through this pinned buffer: see the note on pageable memory in capi_internal.h)
     size_t ring_bytes = 0, ring_pos = 0;
     bool fail(const char *fmt, ...);
 };

@@ -128,4 +128,63 @@ inline ShardProof read_shard_proof(WordReader &r) {
     return p;
 }
 
+// The rv32 proof container ("DVC3"): the guest's exit code, its public-value bytes (little-endian, zero-padded to whole
+// words) and the shard proofs in shard order, each preceded by its length in words.
+constexpr uint32_t CORE_PROOF_MAGIC = 0x33435644u;  // "DVC3"
+
+struct CoreProof {
+    uint32_t exit_code = 0;
+    std::vector<uint8_t> public_values;
+    std::vector<std::vector<uint32_t>> shards;   // the words of each shard proof
+};
+
+inline std::vector<uint32_t> write_core_proof(const CoreProof &c) {
+    WordWriter w;
+    w.u32(CORE_PROOF_MAGIC);
+    w.u32((uint32_t)c.shards.size());
+    w.u32(c.exit_code);
+    const auto &pv = c.public_values;
+    w.u32((uint32_t)pv.size());
+    for (size_t i = 0; i < pv.size(); i += 4) {
+        uint32_t v = 0;
+        for (size_t k = 0; k < 4 && i + k < pv.size(); k++) v |= (uint32_t)pv[i + k] << (8 * k);
+        w.u32(v);
+    }
+    for (auto &s : c.shards) {
+        w.u32((uint32_t)s.size());
+        w.w.insert(w.w.end(), s.begin(), s.end());
+    }
+    return w.w;
+}
+
+// (untrusted input: throws on anything but the one encoding of a container; the shard proofs are not parsed here)
+inline CoreProof read_core_proof(WordReader &r) {
+    CoreProof c;
+    if (r.u32() != CORE_PROOF_MAGIC) throw std::runtime_error("bad container magic");
+    const uint32_t nshards = r.len(1 << 16);
+    if (nshards == 0) throw std::runtime_error("no shards");
+    c.exit_code = r.u32();
+    const uint32_t pvl = r.len(1 << 24);
+    // the AIR pins exit codes below 2^24 (the code itself, not a residue): a container word ec + p would pass the
+    // comparison mod p of the verifier and be reported to the caller as is
+    if (c.exit_code >> 24) throw std::runtime_error("exit code out of range");
+    c.public_values.resize(pvl);
+    for (uint32_t i = 0; i < pvl; i += 4) {
+        uint32_t v = r.u32();
+        for (uint32_t k = 0; k < 4; k++) {
+            if (i + k < pvl) c.public_values[i + k] = (uint8_t)(v >> (8 * k));
+            else if ((v >> (8 * k)) & 0xff) throw std::runtime_error("non-zero padding after the public values");   // (one encoding per proof)
+        }
+    }
+    c.shards.resize(nshards);
+    for (auto &s : c.shards) {
+        uint32_t nw = r.len(1u << 30);
+        if ((size_t)(r.end - r.p) < nw) throw std::runtime_error("container truncated");
+        s.assign(r.p, r.p + nw);
+        r.p += nw;
+    }
+    if (r.p != r.end) throw std::runtime_error("trailing bytes after proof");
+    return c;
+}
+
 }  // namespace dvt

@@ -200,7 +200,7 @@ bool load_elf(const uint8_t *elf, size_t n, Program *out, std::string *err);
 //   fast   no per-cycle records: finds the shard boundaries and the architectural state there (snapshots)
 //   trace  one CycleRec per retired instruction + the events of the shift / muldiv chips
 // so that a long execution is cut into shards by ONE sequential fast pass while the shards are re-executed
-// from the snapshots in trace mode on other threads (capi.hip), overlapped with the GPU.
+// from the snapshots in trace mode on other threads (capi_rv32.hip), overlapped with the GPU.
 // Guest memory is paged copy-on-write: a snapshot shares every page the next shard does not touch.
 constexpr uint32_t PAGE_WORD_BITS = 12;
 // flags: 1 = accessed by a load / store, 2 = part of the program image; tsh = clk | shard << 32 of the last access

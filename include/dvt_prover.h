@@ -20,6 +20,8 @@
  *   - a dvt_prover is re-entrant per handle: one handle per caller thread (the
  *     reference's HTTP node calls prove() from concurrent tokio workers,
  *     src/service/node.rs:72-81); calls on one handle are serialised internally.
+ *     (dvt_stream, dvt_last_error and the dvt_last_* metrics only read the handle:
+ *     they are not serialised, and read what the last finished call left.)
  *   - "device field array": uint32_t words in HBM holding BabyBear elements in
  *     the library's internal (Montgomery) representation, COLUMN-MAJOR
  *     ([width][height], element (r,c) at c*height + r), natural row order.

@@ -5,6 +5,7 @@ Covers K1-K9 end to end (and K0 + multi-shard chaining through the rv32 cases)."
 import numpy as np
 import pytest
 
+from dvt_circuits_amd.capi import split_container
 from tests import _oracle_prover, guests, toy_traces
 
 pytestmark = pytest.mark.gpu
@@ -16,22 +17,6 @@ def first_diff(a: bytes, b: bytes):
     n = min(len(wa), len(wb))
     d = np.nonzero(wa[:n] != wb[:n])[0]
     return (int(d[0]) if len(d) else n), len(wa), len(wb)
-
-
-def split_container(proof: bytes):
-    """-> (exit_code, public value bytes, [shard proof bytes])"""
-    w = np.frombuffer(proof, np.uint32)
-    assert w[0] == 0x33435644
-    n, ec, pvl = int(w[1]), int(w[2]), int(w[3])
-    at = 4 + (pvl + 3) // 4
-    pv = w[4:at].tobytes()[:pvl]
-    shards = []
-    for _ in range(n):
-        ln = int(w[at])
-        shards.append(w[at + 1:at + 1 + ln].tobytes())
-        at += 1 + ln
-    assert at == len(w)
-    return ec, pv, shards
 
 
 _oracle_cache = {}

@@ -12,8 +12,9 @@ capi.rv32_debug_traces and requires all rv32 chips; the toy case covers the toy 
 import numpy as np
 import pytest
 
+from dvt_circuits_amd.capi import split_container
 from tests import guests, toy_traces
-from tests.test_gpu_proof_parity import Q, POW, first_diff, oracle_prove_execution, split_container
+from tests.test_gpu_proof_parity import Q, POW, first_diff, oracle_prove_execution
 
 FORCED = '"parts_parallel_log": -1'
 # guest, log_shard: the small shapes of test_gpu_proof_parity.py, one per chip family

@@ -42,7 +42,7 @@ def test_arith_guest_proof_verifies(gpu):
     # words of their SHA-256 digest, whose receiving side the verifier supplies), and the shard proofs
     words = np.frombuffer(proof, dtype=np.uint32).copy()
     rng = np.random.default_rng(3)
-    body = 4 + (len(pv) + 3) // 4
+    body = len(words) - sum(1 + len(s) // 4 for s in capi.split_container(proof)[2])   # the first shard's length word
     for pos in [1, 2, 3, 4, 5, body - 1, body, body + 1] + list(rng.integers(4, len(words), 20)):
         w = words.copy()
         w[pos] = (int(w[pos]) + 1) % 2013265921
@@ -108,8 +108,9 @@ def test_multi_shard_proof(gpu):
     assert p.assemble(job, shard_proofs) == proof
     # dropping, swapping or replaying a shard must be rejected
     assert not capi.verify(vk, p.assemble(job, shard_proofs[:1] + shard_proofs[2:] + shard_proofs[1:2]), Q, POW)[0]
-    at = 4 + (len(want) + 3) // 4
-    first_len = int(w[at])
+    shards = capi.split_container(proof)[2]
+    at = len(w) - sum(1 + len(s) // 4 for s in shards)   # the first shard's length word
+    first_len = len(shards[0]) // 4
     truncated = w.copy()
     truncated[1] = n - 1
     cut = np.concatenate([truncated[:at], truncated[at + 1 + first_len:]])

@@ -1,5 +1,5 @@
 """CPU test: the untrusted-input side of the library — dvt_verify's container parser
-(csrc/capi.hip, csrc/proof.h) and the shard verifier (csrc/verifier.hip) — built host-only with AddressSanitizer +
+(csrc/proof.h, csrc/capi_rv32.hip) and the shard verifier (csrc/verifier.hip) — built host-only with AddressSanitizer +
 UBSan (`make -C dvt_circuits_amd/csrc asan-fuzz`; sanitizers run on the CPU build only) and driven with byte mutations,
 truncations, splices and hostile length words of valid proofs (tools/fuzz/fuzz_verify.cpp).  Every outcome must be a clean
 DVT_ERR_REJECTED / DVT_ERR_INPUT; any memory error or undefined behaviour aborts the driver.

@@ -26,9 +26,9 @@ def test_full_size_shard_bytes_equal_oracle():
     assert (1 << 21) - 16384 < rep["cycles"] <= 1 << 21
     ok, ec, pv, why = capi.verify(vk, proof)
     assert ok and pv == guests.dkg_like_expected(buf, "finalization", *consts), why
-    w = np.frombuffer(proof, np.uint32)
-    assert int(w[1]) == 1
-    shard_gpu = w[4 + (len(pv) + 3) // 4 + 1:].tobytes()
+    _, _, gpu_shards = capi.split_container(proof)
+    assert len(gpu_shards) == 1
+    shard_gpu = gpu_shards[0]
     chips, pubs, n_shards = capi.rv32_debug_traces(elf, [buf])
     assert n_shards == 1 and max(c["main"].shape[1] for c in chips) == 1 << 21
     gc = _oracle_prover.global_challenges(_oracle_prover.prep_root_of(chips), [_oracle_prover.main_root(chips) + [int(x) for x in pubs]])
@@ -55,12 +55,6 @@ def _oracle_shards(elf, stdin, n_expected):
     return [_oracle_prover.prove_shard("rv32", chips, pubs, 100, 16, perm_challenges=gc)[0] for chips, pubs in shards]
 
 
-def _gpu_shards(proof):
-    from tests.test_gpu_proof_parity import split_container
-
-    return split_container(proof)
-
-
 def _same(a, b, what):
     wa, wb = np.frombuffer(a, np.uint32), np.frombuffer(b, np.uint32)
     n = min(len(wa), len(wb))
@@ -84,7 +78,7 @@ def test_two_full_shards_share_challenges_and_equal_oracle():
     assert (2 << 21) - 65536 < rep["cycles"] <= 2 << 21
     ok, ec, pv, why = capi.verify(vk, proof)
     assert ok and pv == guests.dkg_like_expected(buf, "finalization", *consts), why
-    ec, pv2, gpu = _gpu_shards(proof)
+    ec, pv2, gpu = capi.split_container(proof)
     assert len(gpu) == 2
     cpu = _oracle_shards(elf, [buf], 2)
     for i in range(2):
@@ -113,7 +107,7 @@ def test_full_size_shard_with_precompile_chips_equals_oracle():
     assert (1 << 21) - 65536 < rep["cycles"] <= 1 << 21
     ok, ec, pv, why = capi.verify(vk, proof)
     assert ok and pv == guests.dkg_like_expected(buf, "finalization", *consts, curve_precompiles=True), why
-    ec, pv2, gpu = _gpu_shards(proof)
+    ec, pv2, gpu = capi.split_container(proof)
     assert len(gpu) == 1
     chips, _, _ = capi.rv32_debug_traces(elf, [buf], 21, 0)
     assert {9 + 2, 7, 8} <= {c["chip_id"] for c in chips}          # bls_g1 (11), sha_extend (7), sha_compress (8) are present
@@ -139,7 +133,7 @@ def test_one_shard_at_the_maximum_size_equals_oracle():
     assert (2 << 21) - 65536 < rep["cycles"] <= 1 << 22
     ok, ec, pv, why = capi.verify(vk, proof)
     assert ok and pv == guests.dkg_like_expected(buf, "finalization", *consts), why
-    ec, pv2, gpu = _gpu_shards(proof)
+    ec, pv2, gpu = capi.split_container(proof)
     assert len(gpu) == 1
     chips, pubs, n_shards = capi.rv32_debug_traces(elf, [buf], 22)
     assert n_shards == 1 and max(c["main"].shape[1] for c in chips) == 1 << 22

@@ -7,8 +7,9 @@ product's host row expansion (capi.rv32_debug_traces): the Python model is too s
 are checked by tests/test_tall_precompile_guests.py (constraints) and tests/test_gpu_k0_parity.py (K0)."""
 import pytest
 
+from dvt_circuits_amd.capi import split_container
 from tests import _oracle_prover, guests
-from tests.test_gpu_proof_parity import first_diff, split_container
+from tests.test_gpu_proof_parity import first_diff
 
 pytestmark = pytest.mark.gpu
 Q, POW, LOG_SHARD = 6, 5, 17

@@ -1,5 +1,5 @@
-// Byte-mutation fuzz driver of the UNTRUSTED-input side of the library: dvt_verify (container parsing in csrc/capi.hip,
-// csrc/proof.h, the shard verifier csrc/verifier.hip).  Built host-only with AddressSanitizer + UBSan by
+// Byte-mutation fuzz driver of the UNTRUSTED-input side of the library: dvt_verify (container parsing in csrc/proof.h,
+// csrc/capi_rv32.hip, the shard verifier csrc/verifier.hip).  Built host-only with AddressSanitizer + UBSan by
 // `make -C dvt_circuits_amd/csrc asan-fuzz` (no GPU involved: sanitizers run on the CPU build only) and run by
 // tests/test_verify_fuzz.py on a proof fixture made on a GPU box (tools/make_proof_fixture.py).
 //
