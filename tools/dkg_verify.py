@@ -5,8 +5,11 @@ tools/gen_dkg_input.py emits inputs a DKG-verifying guest accepts, and pinned by
 (tests/golden/finalization_example.json = examples/finalization_test.json, finalization_no_auth_report1.json =
 test_vectors/no_auth/finalization/report-1.json, which the reference's harness expects to exit 0).
 
-verify_finalization(doc) returns None when the input is accepted, else the reason (the reference's error text class)."""
+verify_finalization(doc) returns None when the input is accepted, else the reason (the reference's error text class).
+verify_share(doc) restates the bad-share guest (reference crates/bad_share_exchange_prove/src/main.rs) and returns
+(exit_code, public_value_bytes), pinned by the reference's 10 no-auth share vectors (tests/golden/share_vectors/)."""
 import hashlib
+import struct
 
 from tools import bls12_381 as B
 
@@ -102,3 +105,48 @@ def verify_finalization(doc, check_signatures=True):
     except ValueError as e:
         return str(e)
     return None
+
+
+def share_public_values(doc) -> bytes:
+    """what the reference commits on a slashable share (main.rs:57-70): every base hash in input order, then the perpetrator's
+    secp256k1 key, each the way `sp1_zkvm::io::commit` serialises a raw type: u64-LE length || lowercase hex"""
+    out = b""
+    for h in doc["base_hashes"]:
+        out += struct.pack("<Q", 64) + h.lower().encode()
+    pk = doc["seeds_exchange_commitment"]["commitment"]["pubkey"].lower()
+    return out + struct.pack("<Q", len(pk)) + pk.encode()
+
+
+def verify_share(doc):
+    """-> (exit_code, public_value_bytes): 0 and the committed bytes when the share is provably bad (slashable), else 1 and b""
+    (the reference panics: a failed sanity check, a bad base pubkey, or a valid share).  No auth_commitment checks."""
+    ic = doc["initial_commitment"]
+    st = ic["settings"]
+    n, k = st["n"], st["k"]
+    hashes = [bytes.fromhex(h) for h in doc["base_hashes"]]
+    pks = [bytes.fromhex(p) for p in ic["base_pubkeys"]]
+    # sanity panics (main.rs:24-43)
+    if len(hashes) != n or n < k:
+        return 1, b""
+    if bytes.fromhex(ic["hash"]) not in hashes:
+        return 1, b""
+    if commitment_hash(bytes.fromhex(st["gen_id"]), n, k, pks) != bytes.fromhex(ic["hash"]):
+        return 1, b""
+    # verify_seed_exchange_commitment, no-auth branch (verification.rs:91-148)
+    ss = doc["seeds_exchange_commitment"]["ssecret"]
+    slashable = 0, share_public_values(doc)                              # main.rs:57-70: commit, return normally
+    sk = int.from_bytes(bytes.fromhex(ss["shared_secret"]), "big")       # big-endian scalar (bls_keys.rs:98-114)
+    if sk >= B.R:
+        return slashable
+    dst = bytes.fromhex(ss["dst_base_hash"])
+    ordered = sorted(hashes)                                              # get_index_in_commitments (verification.rs:50-66)
+    if dst not in ordered:
+        return slashable
+    dest_id = ordered.index(dst) + 1
+    try:
+        cfs = [B.g1_decompress(p) for p in pks]                           # `.expect("Invalid pubkey")`: a panic
+    except ValueError:
+        return 1, b""
+    if B.g1_compress(B.E1.mul(B.G1, sk)) != B.g1_compress(evaluate_polynomial(cfs, dest_id)):
+        return slashable
+    return 1, b""                                                         # "The seed exchange commitment is valid" (main.rs:81)
