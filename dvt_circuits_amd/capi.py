@@ -66,6 +66,10 @@ def load():
     lib.dvt_stream.argtypes = [vp]
     lib.dvt_stream.restype = vp
     lib.dvt_sync.argtypes = [vp]
+    lib.dvt_prover_device_count.argtypes = [vp]
+    lib.dvt_prover_device_count.restype = u32
+    lib.dvt_prover_device.argtypes = [vp, u32]
+    lib.dvt_prover_device.restype = C.c_int
     lib.dvt_dev_to_internal.argtypes = [vp, vp, sz]
     lib.dvt_dev_from_internal.argtypes = [vp, vp, sz]
     lib.dvt_stage_coset_lde.argtypes = [vp, vp, vp, vp, u32, u32, u32]
@@ -104,6 +108,8 @@ def load():
     lib.dvt_rv32_debug_traces.argtypes = [C.c_char_p, sz, C.POINTER(Buf), sz, u32, u32, u32p, C.POINTER(u32p), C.POINTER(sz), C.POINTER(C.c_char_p)]
     lib.dvt_rv32_job_shards.argtypes = [vp]
     lib.dvt_rv32_job_shards.restype = sz
+    lib.dvt_rv32_job_shard_member.argtypes = [vp, sz]
+    lib.dvt_rv32_job_shard_member.restype = C.c_int
     lib.dvt_rv32_commit_shard.argtypes = [vp, vp, vp, sz, u32p]
     lib.dvt_rv32_challenges.argtypes = [C.c_char_p, sz, u32p, sz, u32p]
     lib.dvt_rv32_prove_shard.argtypes = [vp, vp, vp, sz, u32p, C.POINTER(u8p), C.POINTER(sz)]
@@ -277,7 +283,7 @@ def machine_verify(vk: bytes, proof: bytes, fri_queries=100, pow_bits=16):
 
 
 class Prover:
-    """Owns one dvt_prover handle (one GPU)."""
+    """Owns one dvt_prover handle: one GPU, or with "devices": [d0, d1, ...] in the cfg one device member per entry."""
 
     def __init__(self, cfg: str = None):
         self.lib = load()
@@ -307,6 +313,14 @@ class Prover:
 
     def stream_ptr(self):
         return self.lib.dvt_stream(self.h)
+
+    def device_count(self):
+        """device members of the handle"""
+        return int(self.lib.dvt_prover_device_count(self.h))
+
+    def device(self, member):
+        """HIP device index of a member, -1 out of range"""
+        return int(self.lib.dvt_prover_device(self.h, member))
 
     # ---- stage-level helpers over torch int32 CUDA tensors (device memory plumbing only)
     def to_internal(self, t):
@@ -473,6 +487,10 @@ class Prover:
     # ---- shard-level API (multi-GPU: ranks own shards; the headers are the only thing exchanged)
     def job_shards(self, job):
         return int(self.lib.dvt_rv32_job_shards(job))
+
+    def job_shard_member(self, job, shard):
+        """the device member that holds a shard (global position), -1 when the job does not hold it"""
+        return int(self.lib.dvt_rv32_job_shard_member(job, shard))
 
     def commit_shard(self, pk, job, shard):
         h = np.zeros(HEADER_WORDS, np.uint32)

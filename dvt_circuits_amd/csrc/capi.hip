@@ -56,12 +56,29 @@ int pipe_drain(dvt_prover *p, std::string *first_err) {
     return rc;
 }
 
-Guard::Guard(dvt_prover *p, const PipeClaim *claim) : lk(p->mu) {
-    if (claim && p->pipe) slot = p->pipe->slot_of(*claim);
-    if (slot < 0) (void)pipe_drain(p);
-    const hipError_t e = hipSetDevice(p->eng.device);
-    rc = e == hipSuccess ? DVT_OK : fail(p, DVT_ERR_DEVICE, "hipSetDevice(p->eng.device): %s", hipGetErrorString(e));
+void pipe_drain_all(dvt_prover *p) {
+    for (size_t m = n_members(p); m-- > 0;) {
+        dvt_prover *mem = member(p, m);
+        if (!mem->pipe) continue;
+        if (m) (void)hipSetDevice(mem->eng.device);   // (the streams a drain waits for are that device's)
+        (void)pipe_drain(mem);
+        if (m) (void)hipSetDevice(p->eng.device);
+    }
 }
+
+int select_member(dvt_prover *p, size_t m) {
+    const hipError_t e = hipSetDevice(member(p, m)->eng.device);
+    return e == hipSuccess ? DVT_OK : fail(p, DVT_ERR_DEVICE, "hipSetDevice(%d): %s", member(p, m)->eng.device, hipGetErrorString(e));
+}
+
+Guard::Guard(dvt_prover *p, const PipeClaim *claim, size_t claim_member) : p(p), lk(p->mu) {
+    dvt_prover *mem = member(p, claim_member);
+    if (claim && mem->pipe) slot = mem->pipe->slot_of(*claim);
+    if (slot < 0) pipe_drain_all(p);
+    rc = select_member(p, 0);
+}
+
+// ---- the handle's config: a flat JSON object of integers, and one list of integers ("devices")
 
 static int cfg_int(const char *json, const char *key, int dflt) {
     if (!json) return dflt;
@@ -73,6 +90,60 @@ static int cfg_int(const char *json, const char *key, int dflt) {
     return atoi(s + 1);
 }
 
+// the position after `"key" :` in json, or nullptr.  Like cfg_int it looks for the quoted text anywhere in the string and
+// takes what follows the next ':' without checking that the match is a key: enough for the flat cfg object, no JSON parser.
+static const char *cfg_value(const char *json, const char *key) {
+    if (!json) return nullptr;
+    const std::string pat = std::string("\"") + key + "\"";
+    const char *s = strstr(json, pat.c_str());
+    if (!s) return nullptr;
+    s = strchr(s + pat.size(), ':');
+    return s ? s + 1 : nullptr;
+}
+// A list of decimal integers: `[a, b, ...]` (json = true) or `a,b,...` up to the end of the string.  False on anything else
+// (an entry that is not an integer, a missing bracket or comma).
+static bool parse_int_list(const char *s, bool json, std::vector<long> *out) {
+    auto blank = [&] { while (*s == ' ' || *s == '\t' || *s == '\n' || *s == '\r') s++; };
+    blank();
+    if (json && *s++ != '[') return false;
+    blank();
+    if (json ? *s == ']' : !*s) return true;   // empty
+    for (;;) {
+        blank();
+        char *end = nullptr;
+        const long v = strtol(s, &end, 10);
+        if (end == s) return false;
+        s = end;
+        out->push_back(v);
+        blank();
+        if (json ? *s == ']' : !*s) return true;
+        if (*s++ != ',') return false;
+    }
+}
+// The device list of a handle: the cfg key "devices", else the environment variable DVT_DEVICES, else the key "device".
+static int cfg_devices(const char *json, int ndev, std::vector<int> *out) {
+    std::vector<long> list;
+    const char *from = nullptr;
+    const char *env = getenv("DVT_DEVICES");
+    if (const char *v = cfg_value(json, "devices")) {
+        from = "\"devices\"";
+        if (cfg_value(json, "device")) return fail(nullptr, DVT_ERR_INPUT, "give \"device\" or \"devices\", not both");
+        if (!parse_int_list(v, true, &list)) return fail(nullptr, DVT_ERR_INPUT, "\"devices\" must be a list of integers");
+    } else if (env && *env) {
+        from = "DVT_DEVICES";
+        if (!parse_int_list(env, false, &list)) return fail(nullptr, DVT_ERR_INPUT, "DVT_DEVICES must be a comma-separated list of integers");
+    } else {
+        from = "\"device\"";
+        list.push_back(cfg_int(json, "device", 0));
+    }
+    if (list.empty() || list.size() > (size_t)MAX_MEMBERS) return fail(nullptr, DVT_ERR_INPUT, "%s must name 1..%d devices (got %zu)", from, MAX_MEMBERS, list.size());
+    for (long d : list) {
+        if (d < 0 || d >= ndev) return fail(nullptr, DVT_ERR_INPUT, "%s: device %ld out of range (%d present)", from, d, ndev);
+        out->push_back((int)d);
+    }
+    return DVT_OK;
+}
+
 const MachineDesc *machine_by_name(const char *name) {
     if (!name) return nullptr;
     if (!strcmp(name, "toy")) return machine_toy();
@@ -81,6 +152,15 @@ const MachineDesc *machine_by_name(const char *name) {
 }
 
 void pk_release(dvt_prover *p, dvt_pk *pk) {
+    // (a key is freed on the handle that made it, include/dvt_prover.h; on another one the copies it cannot reach are skipped)
+    for (size_t m = pk->peers.size(); m > 0; m--) {
+        if (!pk->peers[m - 1] || m >= n_members(p)) continue;
+        (void)select_member(p, m);
+        dvt_pk *peer = pk->peers[m - 1];
+        pk->peers[m - 1] = nullptr;
+        pk_release(member(p, m), peer);
+    }
+    (void)hipSetDevice(p->eng.device);
     p->eng.free_key(&pk->key);
     if (pk->d_instrs) (void)hipFree(pk->d_instrs);
     if (pk->d_prog_row) (void)hipFree(pk->d_prog_row);
@@ -152,7 +232,7 @@ int verify_words(const uint8_t *proof, size_t len, int len_code, char **reason,
 
 extern "C" {
 
-uint32_t dvt_abi_version(void) { return 3; }
+uint32_t dvt_abi_version(void) { return 4; }
 
 int dvt_prover_create(const char *cfg_json, dvt_prover **out) {
     if (!out) return fail(nullptr, DVT_ERR_INPUT, "out == NULL");
@@ -162,13 +242,16 @@ int dvt_prover_create(const char *cfg_json, dvt_prover **out) {
     if (e != hipSuccess || ndev == 0)
         return fail(nullptr, DVT_ERR_DEVICE, "no HIP device (%s); this library has no CPU fallback",
                     e != hipSuccess ? hipGetErrorString(e) : "device count 0");
-    int dev = cfg_int(cfg_json, "device", 0);
-    if (dev < 0 || dev >= ndev) return fail(nullptr, DVT_ERR_INPUT, "device %d out of range (%d present)", dev, ndev);
-    hipDeviceProp_t prop;
+    std::vector<int> devs;
+    if (int rc = cfg_devices(cfg_json, ndev, &devs)) return rc;
+    for (int d : devs) {
+        hipDeviceProp_t prop;
+        HIP_TRY(nullptr, hipGetDeviceProperties(&prop, d));
+        if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+            return fail(nullptr, DVT_ERR_DEVICE, "device %d is %s; this library is built for gfx950 only", d, prop.gcnArchName);
+    }
+    const int dev = devs[0];
     HIP_TRY(nullptr, hipSetDevice(dev));
-    HIP_TRY(nullptr, hipGetDeviceProperties(&prop, dev));
-    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return fail(nullptr, DVT_ERR_DEVICE, "device %d is %s; this library is built for gfx950 only", dev, prop.gcnArchName);
     std::unique_ptr<dvt_prover> p(new dvt_prover());   // (freed on the early returns)
     p->eng.device = dev;
     p->cfg.num_queries = (uint32_t)cfg_int(cfg_json, "fri_queries", 100);
@@ -181,8 +264,9 @@ int dvt_prover_create(const char *cfg_json, dvt_prover **out) {
     if (p->eng.parts_parallel_log < -1 || p->eng.parts_parallel_log > (int)PARTS_PARALLEL_LOG)
         return fail(nullptr, DVT_ERR_INPUT, "parts_parallel_log must be -1..%u", PARTS_PARALLEL_LOG);
     {
-        // phase-2 lanes: the config key, else DVT_LANES (same-process A/B measurements), else 2; profile mode times stages
-        // with events on one stream and keeps one lane
+        // phase-2 lanes (of every member): the config key, else DVT_LANES (same-process A/B measurements), else 2, which
+        // measured best with one member and with two members on one device (profiles/README.md, round 5); profile mode
+        // times stages with events on one stream and keeps one lane
         const char *env = getenv("DVT_LANES");
         const int dflt = env && *env ? atoi(env) : 2;
         p->lanes = cfg_int(cfg_json, "lanes", dflt);
@@ -194,22 +278,43 @@ int dvt_prover_create(const char *cfg_json, dvt_prover **out) {
         return fail(nullptr, DVT_ERR_INPUT, "fri_queries must be 1..1024 and pow_bits <= 30");
     e = p->eng.init(dev);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&p->copy_stream, hipStreamNonBlocking);
+    // the further members: the same settings on their own devices
+    for (size_t m = 1; m < devs.size() && e == hipSuccess; m++) {
+        std::unique_ptr<dvt_prover> q(new dvt_prover());
+        q->owner = p.get();
+        q->cfg = p->cfg; q->log_shard = p->log_shard; q->keep_phase1 = p->keep_phase1; q->lanes = p->lanes;
+        q->eng.device = devs[m];
+        q->eng.profile = p->eng.profile;
+        q->eng.parts_parallel_log = p->eng.parts_parallel_log;
+        dvt_prover *mem = q.get();
+        p->peers.push_back(std::move(q));   // (the destroy below takes care of a half-made member)
+        e = mem->eng.init(devs[m]);
+        if (e == hipSuccess) e = hipStreamCreateWithFlags(&mem->copy_stream, hipStreamNonBlocking);
+    }
+    for (size_t a = 0; a < devs.size(); a++)
+        for (size_t b = 0; b < devs.size(); b++)
+            if (a != b && devs[a] == devs[b]) member(p.get(), a)->shares_device = true;
     if (e != hipSuccess) {
         fail(nullptr, DVT_ERR_DEVICE, "handle setup: %s", hipGetErrorString(e));
         dvt_prover_destroy(p.release());
         return DVT_ERR_DEVICE;
     }
+    (void)hipSetDevice(dev);
     *out = p.release();
     return DVT_OK;
 }
 
 void dvt_prover_destroy(dvt_prover *p) {
     if (!p) return;
-    (void)hipSetDevice(p->eng.device);
-    {
+    if (!p->owner) {
         std::lock_guard<std::mutex> lk(p->mu);
-        (void)pipe_drain(p);
+        pipe_drain_all(p);
     }
+    while (!p->peers.empty()) {   // in reverse, each with its device current
+        dvt_prover_destroy(p->peers.back().release());
+        p->peers.pop_back();
+    }
+    (void)hipSetDevice(p->eng.device);
     if (p->copy_stream) { (void)hipStreamSynchronize(p->copy_stream); (void)hipStreamDestroy(p->copy_stream); }
     for (auto b : p->pinned) (void)hipHostFree(b);
     if (p->aux_pinned) (void)hipHostFree(p->aux_pinned);
@@ -226,8 +331,16 @@ void *dvt_stream(dvt_prover *p) { return p ? (void *)p->eng.stream : nullptr; }
 int dvt_sync(dvt_prover *p) {
     if (!p) return DVT_ERR_INPUT;
     Guard g(p); if (g.rc) return g.rc;
-    HIP_TRY(p, hipStreamSynchronize(p->eng.stream));
+    for (size_t m = n_members(p); m-- > 0;) {   // (the guard has drained the lanes; member 0 last, its device stays current)
+        if (int rc = select_member(p, m)) return rc;
+        HIP_TRY(p, hipStreamSynchronize(member(p, m)->eng.stream));
+    }
     return DVT_OK;
+}
+
+uint32_t dvt_prover_device_count(const dvt_prover *p) { return p ? (uint32_t)n_members(p) : 0; }
+int dvt_prover_device(const dvt_prover *p, uint32_t m) {
+    return p && m < n_members(p) ? member(const_cast<dvt_prover *>(p), m)->eng.device : -1;
 }
 
 int dvt_dev_to_internal(dvt_prover *p, uint32_t *d, size_t n) {

@@ -15,6 +15,7 @@
 #include "rv32.h"
 
 constexpr int MAX_LANES = 3;
+constexpr int MAX_MEMBERS = 8;   // devices of one handle ("devices")
 
 // what dvt_rv32_prove_shard is about to collect from a running phase-2 pipeline
 struct PipeClaim {
@@ -76,6 +77,13 @@ struct dvt_prover {
     // process to drop that mapping - measured as a 20-30 ms stall of the GPU right before phase 1 of a single-shard proof.
     uint8_t *aux_pinned = nullptr;
     size_t aux_pinned_bytes = 0;
+    // Device members ("devices": [d0, d1, ...]).  The handle itself is member 0; each further member is a handle of its own
+    // device - lane-0 engine, lanes, copy stream, staging, phase-2 pipeline - with the settings of member 0.  Only member 0 is
+    // ever given to a caller: a further member's mutex is unused, and its err is scratch of the API thread (see lift()).
+    // Empty on a one-device handle, whose code path is the one-device path.
+    std::vector<std::unique_ptr<dvt_prover>> peers;
+    dvt_prover *owner = nullptr;      // of a further member: the handle it belongs to
+    bool shares_device = false;       // another member of the handle proves on the same physical device
     std::string err;
     std::mutex mu;
 };
@@ -87,10 +95,16 @@ struct dvt_pk {
     dvt::rv32::HostPrep prep;
     dvt::rv32::Instr *d_instrs = nullptr;   // device copy of prog.instrs (K0)
     uint32_t *d_prog_row = nullptr;    // instruction index -> program-table row
+    // the key on the further members' devices (device buffers and vk only; prog and prep live here), in member order
+    std::vector<dvt_pk *> peers;
 };
 
 namespace dvt {   // (the helpers the two units share stay out of the library's global namespace)
 inline Engine &lane_engine(dvt_prover *p, int k) { return k == 0 ? p->eng : *p->more[k - 1]; }
+// device members of a handle: member 0 is the handle itself
+inline size_t n_members(const dvt_prover *p) { return 1 + p->peers.size(); }
+inline dvt_prover *member(dvt_prover *p, size_t m) { return m == 0 ? p : p->peers[m - 1].get(); }
+inline const dvt_pk *member_key(const dvt_pk *pk, size_t m) { return m == 0 ? pk : pk->peers[m - 1]; }
 
 // ---- errors: every message of the ABI layer goes through one formatter into one string
 int fail(std::string &err, int code, const char *fmt, ...) __attribute__((format(printf, 3, 4)));
@@ -104,18 +118,30 @@ inline int engine_fail(std::string &err, const Engine &e) { return fail(err, DVT
         if (e_ != hipSuccess) return fail(to, DVT_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
-// Stops the pipeline (running shards finish, nothing new starts; unclaimed results are discarded) and waits for every lane's
-// stream.  With first_err != nullptr: the error of the lowest failed slot, if any.  Caller holds p->mu.
+// Stops the pipeline of one member (running shards finish, nothing new starts; unclaimed results are discarded) and waits
+// for every lane's stream.  With first_err != nullptr: the error of the lowest failed slot, if any.  Caller holds the
+// handle's mutex.
 int pipe_drain(dvt_prover *p, std::string *first_err = nullptr);
+// the same on every member of the handle (the API thread is left on member 0's device)
+void pipe_drain_all(dvt_prover *p);
+// The API thread turns to member m: its device becomes the calling thread's.
+int select_member(dvt_prover *p, size_t m);
+// the code of a call made on a member, its message moved to the handle (a further member's err is only scratch)
+inline int lift(dvt_prover *p, dvt_prover *mem, int rc) {
+    if (rc && mem != p) p->err = mem->err;
+    return rc;
+}
 
-// Built first by every entry point that works on a handle: holds p->mu for the whole call, drains the phase-2 pipeline and
-// selects the handle's device (rc: DVT_ERR_DEVICE when that fails).  With a claim (dvt_rv32_prove_shard only) a pipeline
-// that holds the claimed shard keeps running, and `slot` is that shard's slot.
+// Built first by every entry point that works on a handle: holds p->mu for the whole call, drains the phase-2 pipelines of
+// every member and selects member 0's device (rc: DVT_ERR_DEVICE when that fails).  With a claim (dvt_rv32_prove_shard
+// only, on member `claim_member`) pipelines that hold the claimed shard keep running, and `slot` is that shard's slot.
 struct Guard {
+    dvt_prover *p;
     std::lock_guard<std::mutex> lk;
     long slot = -1;
     int rc;
-    explicit Guard(dvt_prover *p, const PipeClaim *claim = nullptr);
+    explicit Guard(dvt_prover *p, const PipeClaim *claim = nullptr, size_t claim_member = 0);
+    ~Guard() { if (!p->peers.empty()) (void)hipSetDevice(p->eng.device); }   // (a call may have turned to another member)
 };
 
 // A lane's view of the prover for K0 and phase 2: its engine, and the error string it reports to (p->err for lane 0 on the

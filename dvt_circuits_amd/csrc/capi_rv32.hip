@@ -87,13 +87,37 @@ struct dvt_job {
         uint32_t log_cpu = 0;
     } work[MAX_LANES];
     size_t byte_words = 0, prog_words = 0;
-    double t_exec_wait = 0;   // seconds the GPU thread spent waiting for the executor inside prepare
+    double t_exec_wait = 0;   // seconds the GPU thread spent waiting for the executor inside prepare (several members: the longest wait)
+    // On a handle with several device members the k-th held shard lives on member k mod G: parts[m] is the job of member m
+    // (first + m stride, then G stride apart), and this job holds no shard itself, only what describes the execution.
+    std::vector<dvt_job *> parts;
+    dvt_job *part(size_t m) { return parts.empty() ? this : parts[m]; }
+    size_t held() const {
+        size_t n = shards.size();
+        for (auto q : parts) n += q->shards.size();
+        return n;
+    }
+    // the job that holds the shard at pos, and its member; nullptr when this job does not hold it
+    dvt_job *part_at(size_t pos, size_t *m) {
+        *m = 0;
+        if (parts.empty()) return at(pos) ? this : nullptr;
+        if (pos < first || (pos - first) % stride) return nullptr;
+        *m = (pos - first) / stride % parts.size();
+        return parts[*m]->at(pos) ? parts[*m] : nullptr;
+    }
     ShardJob *at(size_t pos) { return pos >= first && (pos - first) % stride == 0 && (pos - first) / stride < shards.size() ? &shards[(pos - first) / stride] : nullptr; }
 };
 
 // (no phase-2 pipeline runs: the phase-1 buffers go back to lane 0's pool only after every lane is done)
+// Every buffer returns to the pool of the member (and lane) it came from.
 static void job_release(dvt_prover *p, dvt_job *j) {
     if (!j) return;
+    for (size_t m = j->parts.size(); m-- > 0;) {
+        if (m >= n_members(p)) { delete j->parts[m]; continue; }   // (not the handle that made the job, include/dvt_prover.h: its buffers cannot be reached)
+        (void)select_member(p, m);
+        job_release(member(p, m), j->parts[m]);
+    }
+    if (!j->parts.empty()) (void)select_member(p, 0);
     DevPool &pool = p->eng.pool;
     for (auto &s : j->shards) {
         pool.free(s.d_recs);
@@ -142,7 +166,15 @@ static int shard_traces(const Lane &c, const dvt_pk *pk, dvt_job *j, ShardJob &s
     return DVT_OK;
 }
 
-// phase 1 of a shard (lane 0): K0 + K1..K3 of the main traces -> header
+// Two members of one handle on one physical device read the same free bytes: the first phase 1 of a shard, which asks
+// how much is free and then allocates what it keeps (inside commit_main_root), takes turns between them.  A shard that is
+// committed again has its buffers and does not wait; nor do one-device handles and members alone on their device.
+static std::mutex &device_turn(int dev) {
+    static std::mutex mu[64];
+    return mu[dev & 63];
+}
+
+// phase 1 of a shard (lane 0 of its member): K0 + K1..K3 of the main traces -> header
 static int shard_commit(const Lane &c, const dvt_pk *pk, dvt_job *j, ShardJob &s) {
     dvt_prover *p = c.p;
     std::vector<ChipTrace> traces;
@@ -152,15 +184,27 @@ static int shard_commit(const Lane &c, const dvt_pk *pk, dvt_job *j, ShardJob &s
         if (time_stages) fprintf(stderr, "[commit] %s at %.2f ms (pool misses so far %zu)\n", what, ms_since(t0), c.eng.pool.misses);
     };
     // keep the phase-1 results in HBM while they fit (about 3 GB per 2^21-cycle shard); otherwise phase 2 recomputes
+    std::unique_lock<std::mutex> turn;
+    if (p->shares_device && p->keep_phase1 && !s.cache.tree) turn = std::unique_lock<std::mutex>(device_turn(c.eng.device));
     size_t free_b = 0, total_b = 0;
     if (p->keep_phase1 && !s.cache.tree) { (void)hipMemGetInfo(&free_b, &total_b); free_b += c.eng.pool.cached_bytes; }   // (only the first commit of a shard asks)
     lap("memory asked");
     // the further lanes' phase-2 arenas are not there yet on the first job: leave room for them (lane 0's arena is the measure
     // of one), so that the kept caches do not take what the second lane's working set then cannot get
+    // (and for the lanes of the members that share this device, whose phase 1 waits for its turn meanwhile)
     size_t lane_room = 0;
-    for (int k = 1; k < p->lanes; k++) {
-        const size_t have = p->more[k - 1] ? p->more[k - 1]->arena.cap : 0;
-        if (c.eng.arena.cap > have) lane_room += c.eng.arena.cap - have;
+    auto room_of = [&](dvt_prover *q) {
+        for (int k = 0; k < q->lanes; k++) {
+            if (q == p && k == 0) continue;
+            const size_t have = k == 0 ? q->eng.arena.cap : q->more[k - 1] ? q->more[k - 1]->arena.cap : 0;
+            if (c.eng.arena.cap > have) lane_room += c.eng.arena.cap - have;
+        }
+    };
+    room_of(p);
+    if (turn.owns_lock()) {
+        dvt_prover *top = p->owner ? p->owner : p;
+        for (size_t m = 0; m < n_members(top); m++)
+            if (member(top, m) != p && member(top, m)->eng.device == c.eng.device) room_of(member(top, m));
     }
     MainCache *keep = p->keep_phase1 && (s.cache.tree || free_b > ((size_t)24 << 30) + lane_room) ? &s.cache : nullptr;
     if (keep && !s.d_cpu) {
@@ -341,7 +385,7 @@ struct Executor {
     bool take(size_t pos, ReadyShard *r, double *waited) {
         std::unique_lock<std::mutex> lk(mu);
         const auto t0 = Clock::now();
-        cv.wait(lk, [&] { return ready.count(pos) || (fast_done && pos >= fast.n_total) || (fast_done && !fast.error.empty()); });
+        cv.wait(lk, [&] { return ready.count(pos) || (fast_done && pos >= fast.n_total) || (fast_done && !fast.error.empty()) || abort; });
         *waited += std::chrono::duration<double>(Clock::now() - t0).count();
         auto it = ready.find(pos);
         if (it == ready.end()) return false;
@@ -352,6 +396,12 @@ struct Executor {
     void give_back(rv32::CycleRec *b) {
         std::lock_guard<std::mutex> lk(mu);
         free_bufs.push_back(b);
+        cv.notify_all();
+    }
+    // a member's phase 1 failed: the threads stop, and the other members' take() returns false for what is not ready
+    void cancel() {
+        std::lock_guard<std::mutex> lk(mu);
+        abort = true;
         cv.notify_all();
     }
     // stops and joins the threads: what the fast pass found is final
@@ -519,16 +569,55 @@ static int prepare_verdict(std::string &err, const FastPass &f, int rc) {
     return DVT_OK;
 }
 
+// Phase 1 on a handle with several members: the k-th shard the job holds goes to member k mod G.  Every member runs the
+// upload + phase-1 loop for its shards on a thread of its own (its device, copy stream, staging and lane-0 engine), all fed by
+// the one executor.  The threads report into strings of their own, never into p->err; the error is that of the lowest
+// failed position.  Every thread is joined and every member's streams are idle on return.
+static int commit_on_members(dvt_prover *p, const dvt_pk *pk, dvt_job *j, Executor &ex, bool time_stages, Clock::time_point t_begin) {
+    const size_t G = n_members(p);
+    struct Run { int rc = DVT_OK; std::string err; };
+    std::vector<Run> runs(G);
+    for (size_t m = 0; m < G; m++) {
+        dvt_job *q = new dvt_job();
+        q->first = j->first + m * j->stride; q->stride = j->stride * G;
+        q->byte_words = j->byte_words; q->prog_words = j->prog_words;
+        j->parts.push_back(q);
+    }
+    std::vector<std::thread> threads;
+    for (size_t m = 0; m < G; m++) threads.emplace_back([&, m] {
+        Run &r = runs[m];
+        dvt_prover *mem = member(p, m);
+        const hipError_t e = hipSetDevice(mem->eng.device);
+        r.rc = e != hipSuccess ? fail(r.err, DVT_ERR_DEVICE, "hipSetDevice(%d): %s", mem->eng.device, hipGetErrorString(e))
+                               : commit_overlapped(Lane{mem, 0, mem->eng, r.err}, member_key(pk, m), j->parts[m], ex, time_stages, t_begin);
+        if (r.rc) ex.cancel();
+    });
+    for (auto &t : threads) t.join();
+    int rc = DVT_OK;
+    size_t at = ~(size_t)0;
+    for (size_t m = G; m-- > 0;) {
+        dvt_prover *mem = member(p, m);
+        if (select_member(p, m) == DVT_OK) { (void)hipStreamSynchronize(mem->copy_stream); (void)hipStreamSynchronize(mem->eng.stream); }
+        j->t_exec_wait = std::max(j->t_exec_wait, j->parts[m]->t_exec_wait);
+        const size_t pos = j->parts[m]->first + j->parts[m]->shards.size() * j->parts[m]->stride;   // about where it stopped
+        if (runs[m].rc && pos <= at) { at = pos; rc = runs[m].rc; p->err = runs[m].err; }
+    }
+    return rc;
+}
+
 static int job_prepare(dvt_prover *p, const dvt_pk *pk, const dvt_buf *stdin_bufs, size_t nbuf, size_t first, size_t stride, dvt_job **out,
                        dvt_report *report) {
     if (stride == 0 || first >= stride) return fail(p, DVT_ERR_INPUT, "bad shard partition %zu / %zu", first, stride);
+    const size_t G = n_members(p);
+    if (pk->peers.size() + 1 != G) return fail(p, DVT_ERR_INPUT, "the proving key holds %zu device copies, this handle has %zu devices", pk->peers.size() + 1, G);
     unsigned hw = std::thread::hardware_concurrency();
     const unsigned n_workers = p->exec_threads ? p->exec_threads : std::max(1u, std::min(6u, hw > 3 ? hw - 2 : 1u));
-    // pinned staging: one buffer per worker + two in flight on the GPU side
-    const size_t want_bufs = n_workers + 2;
+    // pinned staging: one buffer per worker + two in flight on the GPU side of every member.  Any worker's buffer may go to
+    // any member, so with several members the buffers are pinned for every device (portable).
+    const size_t want_bufs = n_workers + 2 * G;
     while (p->pinned.size() < want_bufs) {
         rv32::CycleRec *b = nullptr;
-        HIP_TRY(p, hipHostMalloc(&b, sizeof(rv32::CycleRec) << p->log_shard));
+        HIP_TRY(p, hipHostMalloc(&b, sizeof(rv32::CycleRec) << p->log_shard, G > 1 ? hipHostMallocPortable : hipHostMallocDefault));
         p->pinned.push_back(b);
     }
     const bool time_stages = getenv("DVT_TIME_PREPARE") != nullptr;   // (stderr: where the host side of a prepare goes)
@@ -539,7 +628,7 @@ static int job_prepare(dvt_prover *p, const dvt_pk *pk, const dvt_buf *stdin_buf
     j->first = first; j->stride = stride;
     j->byte_words = (size_t)rv32::N_BYTE_OPS * 65536;
     j->prog_words = (size_t)1 << pk->prep.log_n[RV32_CHIP_PROGRAM];
-    int rc = commit_overlapped(lane0(p), pk, j, ex, time_stages, t_begin);
+    int rc = G == 1 ? commit_overlapped(lane0(p), pk, j, ex, time_stages, t_begin) : commit_on_members(p, pk, j, ex, time_stages, t_begin);
     FastPass &f = ex.finish();
     if (time_stages) fprintf(stderr, "[prepare] %.2f ms: threads joined\n", ms_since(t_begin));
     if (report) {
@@ -606,13 +695,15 @@ static void pipe_worker(dvt_prover *p, Phase2Pipe *pp, PermChallenges gc, int k)
 
 // Starts the pipeline over the job's shards with a valid header, in job order from shard index k0 (which must be one of
 // them).  Returns DVT_OK with p->pipe set; DVT_OK without a pipeline when there is nothing to run ahead (one lane, or
-// fewer than two such shards).  Caller holds p->mu; no pipeline runs.
-static int pipe_start(dvt_prover *p, const dvt_pk *pk, dvt_job *j, size_t k0, const PermChallenges &gc) {
-    if (p->lanes < 2 || k0 >= j->shards.size() || !j->shards[k0].header_valid) return DVT_OK;
+// fewer than two such shards).  p is one member, pk its copy of the key and j its part of the job; `always` (a handle with
+// several members, which run at the same time) starts a pipeline for a single lane or a single shard too.  Caller holds the
+// handle's mutex and has selected the member; no pipeline runs on it.
+static int pipe_start(dvt_prover *p, const dvt_pk *pk, dvt_job *j, size_t k0, const PermChallenges &gc, bool always) {
+    if ((p->lanes < 2 && !always) || k0 >= j->shards.size() || !j->shards[k0].header_valid) return DVT_OK;
     std::vector<size_t> order;
     for (size_t k = k0; k < j->shards.size(); k++)
         if (j->shards[k].header_valid) order.push_back(k);
-    if (order.size() < 2) return DVT_OK;
+    if (order.size() < (always ? 1u : 2u)) return DVT_OK;
     int rc = ensure_lanes(p);
     if (rc) return rc;
     HIP_TRY(p, hipStreamSynchronize(p->eng.stream));   // phase 1 (lane 0) is complete before another lane reads its buffers
@@ -656,28 +747,41 @@ static int pipe_claim(dvt_prover *p, size_t slot, std::vector<uint32_t> *words) 
     return fail(p, rc ? rc : DVT_ERR_DEVICE, "%s", rc ? why.c_str() : "phase-2 pipeline stopped");
 }
 
-// both phases on one GPU; the job must hold every shard of the execution.  Leaves no pipeline running.
+// both phases on the handle's devices; the job must hold every shard of the execution.  Leaves no pipeline running.
+// Shard i is on member i mod G; the challenges are computed once, then phase 2 runs on every member's lanes at the same time.
 static int job_prove(dvt_prover *p, const dvt_pk *pk, dvt_job *j, uint8_t **proof, size_t *proof_len) {
-    const size_t n = j->shards.size();
+    const size_t n = j->held(), G = n_members(p);
     if (n != j->n_total) return fail(p, DVT_ERR_INPUT, "this job holds %zu of the execution's %zu shards: prove them shard by shard", n, j->n_total);
-    const Lane c = lane0(p);
+    if (pk->peers.size() + 1 != G || (G > 1 && j->parts.size() != G)) return fail(p, DVT_ERR_INPUT, "proving key or job of a handle with other devices");
+    auto shard = [&](size_t i) -> ShardJob & { return j->part(i % G)->shards[i / G]; };
     std::vector<uint32_t> headers(n * HEADER_WORDS);
     for (size_t i = 0; i < n; i++) {
-        if (!j->shards[i].header_valid) {
-            int rc = shard_commit(c, pk, j, j->shards[i]);
+        if (!shard(i).header_valid) {
+            dvt_prover *mem = member(p, i % G);
+            int rc = G > 1 ? select_member(p, i % G) : DVT_OK;
+            if (!rc) rc = lift(p, mem, shard_commit(lane0(mem), member_key(pk, i % G), j->part(i % G), shard(i)));
             if (rc) return rc;
         }
-        memcpy(headers.data() + i * HEADER_WORDS, j->shards[i].header, sizeof(uint32_t) * HEADER_WORDS);
+        memcpy(headers.data() + i * HEADER_WORDS, shard(i).header, sizeof(uint32_t) * HEADER_WORDS);
     }
     PermChallenges gc = global_challenges(pk->key.vk, headers.data(), n);
     std::vector<std::vector<uint32_t>> shards(n);
-    int rc = pipe_start(p, pk, j, 0, gc);
-    if (rc) return rc;
-    for (size_t i = 0; i < n; i++) {   // (every shard is in the pipeline when one runs: its last claim ends it)
-        rc = p->pipe ? pipe_claim(p, i, &shards[i]) : shard_prove(c, pk, j, j->shards[i], gc, &shards[i]);
-        if (rc) return rc;
+    int rc = DVT_OK;
+    for (size_t m = 0; m < G && !rc; m++) {
+        if (G > 1) rc = select_member(p, m);
+        if (!rc) rc = lift(p, member(p, m), pipe_start(member(p, m), member_key(pk, m), j->part(m), 0, gc, G > 1));
     }
-    (void)hipStreamSynchronize(p->eng.stream);
+    for (size_t i = 0; i < n && !rc; i++) {   // (every shard of a member is in its pipeline when one runs: its last claim ends it)
+        dvt_prover *mem = member(p, i % G);
+        if (G > 1) rc = select_member(p, i % G);
+        if (!rc) rc = lift(p, mem, mem->pipe ? pipe_claim(mem, i / G, &shards[i]) : shard_prove(lane0(mem), member_key(pk, i % G), j->part(i % G), shard(i), gc, &shards[i]));
+    }
+    if (G > 1) pipe_drain_all(p);   // (on an error the other members still run)
+    for (size_t m = G; m-- > 0;) {
+        if (G > 1 && select_member(p, m)) continue;
+        (void)hipStreamSynchronize(member(p, m)->eng.stream);
+    }
+    if (rc) return rc;
     if (!proof) return DVT_OK;  // timing runs may discard the bytes
     *proof = copy_out(write_core_proof({(uint32_t)j->exit_code, j->public_values, std::move(shards)}), proof_len);
     if (!*proof) return fail(p, DVT_ERR_DEVICE, "out of host memory");
@@ -767,8 +871,30 @@ static std::vector<uint32_t> trace_blob(const rv32::HostTraces &T, const rv32::H
     return w;
 }
 
+// the device half of dvt_setup on one member (its device is current): the preprocessed commitment and the program tables
+static int setup_on(dvt_prover *mem, const rv32::Program &prog, const rv32::HostPrep &prep, dvt_pk *dst) {
+    std::vector<ChipRef> refs;
+    std::vector<std::vector<uint32_t>> host;
+    for (int c : {RV32_CHIP_PROGRAM, RV32_CHIP_BYTE, RV32_CHIP_MEM_IMAGE}) {
+        refs.push_back({c, prep.log_n[c]});
+        host.push_back(prep.prep[c]);
+    }
+    if (!mem->eng.setup(machine_rv32(), refs, host, &dst->key)) return engine_fail(mem->err, mem->eng);
+    dst->key.vk.extra = {prog.entry};
+    std::vector<uint32_t> rowmap = rv32::program_row_map(prog);
+    size_t ib = prog.instrs.size() * sizeof(rv32::Instr);
+    if (hipMalloc(&dst->d_instrs, ib) != hipSuccess || hipMalloc(&dst->d_prog_row, rowmap.size() * 4) != hipSuccess ||
+        hipMemcpy(dst->d_instrs, prog.instrs.data(), ib, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dst->d_prog_row, rowmap.data(), rowmap.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
+        return fail(mem, DVT_ERR_DEVICE, "uploading the program table failed");
+    return DVT_OK;
+}
+
 extern "C" {
 
+// On a handle with several members the setup runs on every member, from the one decoded program: it needs no peer access
+// between the devices (and none between two members on one device), and a member whose commitment differed would be caught
+// here instead of in a proof that does not verify.
 int dvt_setup(dvt_prover *p, const uint8_t *elf, size_t elf_len, dvt_pk **pk_out, uint8_t **vk, size_t *vk_len) {
     if (!p || !elf || !pk_out) return fail(p, DVT_ERR_INPUT, "null argument");
     Guard g(p); if (g.rc) return g.rc;
@@ -777,21 +903,18 @@ int dvt_setup(dvt_prover *p, const uint8_t *elf, size_t elf_len, dvt_pk **pk_out
     if (!rv32::load_elf(elf, elf_len, &pk->prog, &err)) return setup_finish(p, pk, fail(p, DVT_ERR_INPUT, "ELF: %s", err.c_str()), pk_out, vk, vk_len);
     rv32::build_prep(pk->prog, &pk->prep);
     pk->is_rv32 = true;
-    std::vector<ChipRef> refs;
-    std::vector<std::vector<uint32_t>> host;
-    for (int c : {RV32_CHIP_PROGRAM, RV32_CHIP_BYTE, RV32_CHIP_MEM_IMAGE}) {
-        refs.push_back({c, pk->prep.log_n[c]});
-        host.push_back(pk->prep.prep[c]);
+    int rc = setup_on(p, pk->prog, pk->prep, pk);
+    for (size_t m = 1; m < n_members(p) && !rc; m++) {
+        dvt_pk *q = new dvt_pk();
+        q->is_rv32 = true;
+        pk->peers.push_back(q);
+        rc = select_member(p, m);
+        if (!rc) rc = lift(p, member(p, m), setup_on(member(p, m), pk->prog, pk->prep, q));
+        if (!rc && vk_words(q->key.vk) != vk_words(pk->key.vk))
+            rc = fail(p, DVT_ERR_DEVICE, "member %zu (device %d) built a verifying key that differs from member 0's", m, member(p, m)->eng.device);
     }
-    if (!p->eng.setup(machine_rv32(), refs, host, &pk->key)) return setup_finish(p, pk, engine_fail(p->err, p->eng), pk_out, vk, vk_len);
-    pk->key.vk.extra = {pk->prog.entry};
-    std::vector<uint32_t> rowmap = rv32::program_row_map(pk->prog);
-    size_t ib = pk->prog.instrs.size() * sizeof(rv32::Instr);
-    if (hipMalloc(&pk->d_instrs, ib) != hipSuccess || hipMalloc(&pk->d_prog_row, rowmap.size() * 4) != hipSuccess ||
-        hipMemcpy(pk->d_instrs, pk->prog.instrs.data(), ib, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(pk->d_prog_row, rowmap.data(), rowmap.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-        return setup_finish(p, pk, fail(p, DVT_ERR_DEVICE, "uploading the program table failed"), pk_out, vk, vk_len);
-    return setup_finish(p, pk, DVT_OK, pk_out, vk, vk_len);
+    if (n_members(p) > 1 && select_member(p, 0) && !rc) rc = DVT_ERR_DEVICE;
+    return setup_finish(p, pk, rc, pk_out, vk, vk_len);
 }
 
 int dvt_execute_io(const uint8_t *elf, size_t elf_len, const dvt_buf *stdin_bufs, size_t nbuf, uint64_t max_cycles,
@@ -852,15 +975,24 @@ void dvt_job_free(dvt_prover *p, dvt_job *job) {
     job_release(p, job);
 }
 size_t dvt_rv32_job_shards(const dvt_job *job) { return job ? job->n_total : 0; }
+int dvt_rv32_job_shard_member(const dvt_job *job, size_t shard) {
+    size_t m = 0;
+    return job && const_cast<dvt_job *>(job)->part_at(shard, &m) ? (int)m : -1;
+}
 double dvt_rv32_job_exec_wait_seconds(const dvt_job *job) { return job ? job->t_exec_wait : 0.0; }
 
 int dvt_rv32_commit_shard(dvt_prover *p, const dvt_pk *pk, dvt_job *job, size_t shard, uint32_t *header) {
     if (!p || !pk || !job || !header) return fail(p, DVT_ERR_INPUT, "bad argument");
-    ShardJob *s = job->at(shard);
-    if (!s) return fail(p, DVT_ERR_INPUT, "shard %zu is not held by this job", shard);
+    size_t m = 0;
+    dvt_job *part = job->part_at(shard, &m);
+    if (!part) return fail(p, DVT_ERR_INPUT, "shard %zu is not held by this job", shard);
+    if (m >= n_members(p) || pk->peers.size() + 1 != n_members(p)) return fail(p, DVT_ERR_INPUT, "proving key or job of a handle with other devices");
+    ShardJob *s = part->at(shard);
     Guard g(p); if (g.rc) return g.rc;
     if (!s->header_valid) {   // (the prepare pipeline already ran phase 1; a second proof of the same job runs it again)
-        int rc = shard_commit(lane0(p), pk, job, *s);
+        dvt_prover *mem = member(p, m);
+        int rc = m ? select_member(p, m) : DVT_OK;
+        if (!rc) rc = lift(p, mem, shard_commit(lane0(mem), member_key(pk, m), part, *s));
         if (rc) return rc;
     }
     memcpy(header, s->header, sizeof(uint32_t) * HEADER_WORDS);
@@ -879,27 +1011,42 @@ int dvt_rv32_challenges(const uint8_t *vk, size_t vk_len, const uint32_t *header
 int dvt_rv32_prove_shard(dvt_prover *p, const dvt_pk *pk, dvt_job *job, size_t shard, const uint32_t challenges[8], uint8_t **proof,
                          size_t *proof_len) {
     if (!p || !pk || !job || !challenges || (proof && !proof_len)) return fail(p, DVT_ERR_INPUT, "bad argument");
-    ShardJob *s = job->at(shard);
-    if (!s) return fail(p, DVT_ERR_INPUT, "shard %zu is not held by this job", shard);
+    size_t m = 0;
+    dvt_job *part = job->part_at(shard, &m);
+    if (!part) return fail(p, DVT_ERR_INPUT, "shard %zu is not held by this job", shard);
+    const size_t G = n_members(p);
+    if (m >= G || pk->peers.size() + 1 != G || (G > 1 && job->parts.size() != G)) return fail(p, DVT_ERR_INPUT, "proving key or job of a handle with other devices");
+    ShardJob *s = part->at(shard);
     PermChallenges gc;
     for (int k = 0; k < 4; k++) {
         if (challenges[k] >= P || challenges[4 + k] >= P) return fail(p, DVT_ERR_INPUT, "challenge not canonical");
         gc.alpha.c[k] = Fp::from_canonical(challenges[k]);
         gc.beta.c[k] = Fp::from_canonical(challenges[4 + k]);
     }
-    // phase 2 runs ahead on the prover lanes: the first call of a job starts the pipeline, later calls with the same
-    // challenges collect from it; anything else drains it (the guard) and takes the one-lane path
-    const size_t k = (size_t)(s - job->shards.data());
-    const PipeClaim claim{job, pk, challenges, k};
-    Guard g(p, &claim); if (g.rc) return g.rc;
+    // phase 2 runs ahead on the prover lanes of every member: the first call of a job starts the pipelines, later calls with
+    // the same challenges collect from them; anything else drains them (the guard) and takes the one-lane path
+    const size_t k = (size_t)(s - part->shards.data());
+    const PipeClaim claim{part, member_key(pk, m), challenges, k};
+    Guard g(p, &claim, m); if (g.rc) return g.rc;
+    dvt_prover *mem = member(p, m);
     long slot = g.slot;
-    if (!p->pipe) {
-        int rc = pipe_start(p, pk, job, k, gc);
-        if (rc) return rc;
-        if (p->pipe) slot = 0;
+    int rc = DVT_OK;
+    if (slot < 0 && (G == 1 || s->header_valid)) {   // (a shard whose phase-1 result was consumed is proven alone: no member runs ahead)
+        for (size_t i = 0; i < G && !rc; i++) {      // the claimed shard's member first
+            const size_t mm = (m + i) % G;
+            dvt_job *q = job->part(mm);
+            // its own part from the claimed shard; the others from their first shard after it
+            const size_t k0 = mm == m ? k : q->first > shard ? 0 : (shard - q->first) / q->stride + 1;
+            if (G > 1) rc = select_member(p, mm);
+            if (!rc) rc = lift(p, member(p, mm), pipe_start(member(p, mm), member_key(pk, mm), q, k0, gc, G > 1));
+        }
+        if (rc) { pipe_drain_all(p); return rc; }
+        if (mem->pipe) slot = 0;
     }
+    if (G > 1) rc = select_member(p, m);
     std::vector<uint32_t> words;
-    int rc = slot >= 0 ? pipe_claim(p, (size_t)slot, &words) : shard_prove(lane0(p), pk, job, *s, gc, &words);
+    if (!rc) rc = lift(p, mem, slot >= 0 ? pipe_claim(mem, (size_t)slot, &words) : shard_prove(lane0(mem), member_key(pk, m), part, *s, gc, &words));
+    if (rc && G > 1) pipe_drain_all(p);
     if (rc || !proof) return rc;
     *proof = copy_out(words, proof_len);
     return *proof ? DVT_OK : fail(p, DVT_ERR_DEVICE, "out of host memory");
@@ -977,13 +1124,17 @@ int dvt_rv32_debug_traces(const uint8_t *elf, size_t elf_len, const dvt_buf *std
 // test hook: run K0 on shard `shard` of a prepared job and return the device-generated main traces (canonical),
 // same blob layout as dvt_rv32_debug_traces but without preprocessed columns (prep_width = 0)
 int dvt_rv32_debug_device_traces(dvt_prover *p, const dvt_pk *pk, dvt_job *j, size_t shard, uint32_t **blob, size_t *blob_words) {
-    if (!p || !pk || !j || !blob || !blob_words || !j->at(shard)) return fail(p, DVT_ERR_INPUT, "bad argument");
+    size_t mi = 0;
+    dvt_job *part = p && pk && j && blob && blob_words ? j->part_at(shard, &mi) : nullptr;
+    if (!part || mi >= n_members(p) || pk->peers.size() + 1 != n_members(p)) return fail(p, DVT_ERR_INPUT, "bad argument");
     Guard g(p); if (g.rc) return g.rc;
     std::vector<ChipTrace> traces;
-    ShardJob &sj = *j->at(shard);
-    int rc = shard_traces(lane0(p), pk, j, sj, &traces, false);
+    ShardJob &sj = *part->at(shard);
+    dvt_prover *mem = member(p, mi);
+    int rc = mi ? select_member(p, mi) : DVT_OK;
+    if (!rc) rc = lift(p, mem, shard_traces(lane0(mem), member_key(pk, mi), part, sj, &traces, false));
     if (rc) return rc;
-    HIP_TRY(p, hipStreamSynchronize(p->eng.stream));
+    HIP_TRY(p, hipStreamSynchronize(mem->eng.stream));
     const MachineDesc *m = machine_rv32();
     rv32::HostTraces T;
     for (int c = 0; c < rv32::N_CHIPS; c++) T.present[c] = false;

@@ -1,6 +1,6 @@
 // dvt_prover_host — the reference's CLI verbs (src/main.rs:58-106) over the C ABI.
 //
-//   dvt_prover_host prove   --type T -i INPUT.json [-o PROOF] [--elf GUEST.elf]
+//   dvt_prover_host prove   --type T -i INPUT.json [-o PROOF] [--elf GUEST.elf] [--devices D0,D1,...]
 //   dvt_prover_host execute --type T -i INPUT.json [--show-report] [--elf GUEST.elf]
 //   dvt_prover_host verify  --type T -i PROOF [--elf GUEST.elf]
 //
@@ -11,6 +11,8 @@
 // success (:476), any error is printed and the process exits with code 1 (:421-427) — which is what the
 // reference's 92 test vectors observe (script/run.sh:82-89).  `verify` has stock client.verify semantics
 // (the reference's own verify sub-command re-executes the guest instead).
+// --devices (prove only) spreads the shards of the execution over those GPUs (an index may repeat): the "devices" key of
+// dvt_prover_create.
 // get-schema / validate-schema / node are product UI outside the accelerated path and are not provided.
 #include <cstdio>
 #include <cstdlib>
@@ -34,9 +36,9 @@ static int die(const std::string &m) {
 }
 
 int main(int argc, char **argv) {
-    if (argc < 2) return die("usage: dvt_prover_host prove|execute|verify --type T -i FILE [-o FILE] [--show-report] [--elf FILE]");
+    if (argc < 2) return die("usage: dvt_prover_host prove|execute|verify --type T -i FILE [-o FILE] [--show-report] [--elf FILE] [--devices D0,D1,...]");
     const std::string verb = argv[1];
-    std::string type, input, output, elf_path, schema_path;
+    std::string type, input, output, elf_path, schema_path, devices;
     bool show_report = false, auth = false;
     for (int i = 2; i < argc; i++) {
         std::string a = argv[i], inline_val;
@@ -50,6 +52,7 @@ int main(int argc, char **argv) {
         else if (a == "-i" || a == "--input-file") input = next();
         else if (a == "-o" || a == "--output-file-path") output = next();
         else if (a == "--elf") elf_path = next();
+        else if (a == "--devices") devices = next();
         else if (a == "--show-report") show_report = true;
         else if (a == "--auth-commitment") auth = true;  // the reference selects this at build time (cargo feature)
         else if (a == "--json-schema-file") schema_path = next();
@@ -115,7 +118,8 @@ int main(int argc, char **argv) {
     }
 
     dvt_prover *p = nullptr;
-    if (dvt_prover_create(nullptr, &p)) return die(dvt_last_error(nullptr));
+    const std::string cfg = "{\"devices\": [" + devices + "]}";   // (the library checks the list)
+    if (dvt_prover_create(devices.empty() ? nullptr : cfg.c_str(), &p)) return die(dvt_last_error(nullptr));
     dvt_pk *pk = nullptr;
     if (dvt_setup(p, elf.data(), elf.size(), &pk, nullptr, nullptr)) return die(dvt_last_error(p));
     uint8_t *proof = nullptr;

@@ -25,7 +25,9 @@
  *   - "device field array": uint32_t words in HBM holding BabyBear elements in
  *     the library's internal (Montgomery) representation, COLUMN-MAJOR
  *     ([width][height], element (r,c) at c*height + r), natural row order.
- *   - all device work of a handle runs on the handle's own HIP stream (dvt_stream).
+ *   - all device work of a handle runs on the handle's own HIP streams (dvt_stream is the first of them).
+ *   - a handle may own several devices ("devices"): the shards of one execution are then proven on all of them inside the
+ *     same calls; see dvt_prover_create and the shard-level calls below.
  */
 #ifndef DVT_PROVER_H
 #define DVT_PROVER_H
@@ -56,13 +58,47 @@ typedef struct dvt_pk dvt_pk;
  * "lanes" (1..3, default 2; without the key the environment variable DVT_LANES sets the default; anything else is
  * DVT_ERR_INPUT): prover lanes that run phase 2 of different shards of one job at the same time, each with its own HIP
  * stream, device arena and buffer cache.  The further lanes are created on the first job that holds at least two shards;
- * "profile":1 forces one lane.  The proof bytes do not depend on it. */
+ * "profile":1 forces one lane.  The proof bytes do not depend on it.
+ * "devices": [d0, d1, ...] (1..8 HIP device indices, each a gfx950 device) instead of "device": the handle owns one device
+ * MEMBER per entry, and shard i of an execution is proven on member i mod G (exactly: the k-th shard a job holds on member
+ * k mod G).  An index may repeat: [0, 0] is two members on one GPU, each with its own streams, arenas and copy of the
+ * proving key.  "devices": [d] is "device": d.  Both keys together, an empty list, more than 8 entries, an index that is
+ * negative or not below the device count, or an entry that is not an integer: DVT_ERR_INPUT.  Without the key "devices"
+ * the environment variable DVT_DEVICES (comma-separated indices, the same checks) is the list when it is set, and "device"
+ * is then ignored.  "lanes" counts per member; its default is 2 for every G (measured on [0, 0], profiles/README.md
+ * "Round 5": two members of two lanes each take 889 ms per 32-shard call, of one lane each 980 ms; one device with two
+ * lanes 915 ms).
+ * Proof bytes, verifying key and container do not depend on the device list.  With G > 1:
+ *   dvt_setup            builds the proving key on every member (the setup runs once per member from the one decoded
+ *                        program: no peer access between devices is needed) and fails with DVT_ERR_DEVICE if a member's
+ *                        verifying key differs from member 0's; dvt_pk_free frees every copy
+ *   prepare / prove_core / prove_job
+ *                        ONE executor (one fast pass, one pool of trace threads) per call feeds all members; every member
+ *                        uploads and runs phase 1 of its shards on a host thread of its own; the headers meet in host memory,
+ *                        the challenges are computed once, phase 2 runs on every member's lanes at the same time
+ *   commit_shard / prove_shard
+ *                        go to the member that holds the shard; the first prove_shard of a job starts the run-ahead
+ *                        pipeline on EVERY member (its own part from the shard asked for, the others from their first shard
+ *                        after it), under the contract described at prove_shard below.  An abandoned job wastes at most
+ *                        (sum of the members' lanes - 1) shard proofs.
+ *   stage- and machine-level calls, dvt_dev_*, dvt_stream, dvt_last_*
+ *                        run on member 0; dvt_sync also waits for the other members' streams
+ * Two members on one physical device take turns in the first phase 1 of a shard when "keep_phase1" is on (they would
+ * otherwise count the same free HBM twice when deciding what to keep).  A second dvt_rv32_prove_job of the same job runs
+ * phase 1 of all its shards again one after the other on the calling thread, member by member: only prepare runs the
+ * members' phase 1 at the same time.  A proving key and a job are freed on the handle that made them: dvt_pk_free /
+ * dvt_job_free on a handle with fewer members cannot reach the other members' device buffers and leave them allocated.
+ * On return from a call the calling thread's current device is member 0's. */
 int dvt_prover_create(const char *cfg_json, dvt_prover **out);
+/* device members of the handle (1 unless "devices" / DVT_DEVICES named more), and the HIP device index of a member
+ * (-1 when member >= the count) */
+uint32_t dvt_prover_device_count(const dvt_prover *p);
+int dvt_prover_device(const dvt_prover *p, uint32_t member);
 void dvt_prover_destroy(dvt_prover *p);
 /* last error text of this handle (or of the failed create when p == NULL) */
 const char *dvt_last_error(const dvt_prover *p);
 void dvt_free(void *ptr);
-/* ABI version of this header */
+/* ABI version of this header (4: "devices", dvt_prover_device_count, dvt_prover_device, dvt_rv32_job_shard_member) */
 uint32_t dvt_abi_version(void);
 /* the handle's hipStream_t (for event timing by the caller) */
 void *dvt_stream(dvt_prover *p);
@@ -209,8 +245,9 @@ int dvt_setup(dvt_prover *p, const uint8_t *elf, size_t elf_len, dvt_pk **pk, ui
  * 0x02 WRITE(fd, ptr, len), 0x10 COMMIT(index, word) - the eight words of SHA-256(public-value bytes),
  * which the proof binds -, 0x1A COMMIT_DEFERRED_PROOFS (no-op), 0xF0 HINT_LEN, 0xF1 HINT_READ(ptr, len).
  * Precompiles (SP1 syscall codes with byte 1 = 1, proven by their own chips): 0x00_30_01_05 SHA_EXTEND(w) and
- * 0x00_01_01_06 SHA_COMPRESS(w, state), the two calls of SP1's patched `sha2` crate.  The BLS12-381 / secp256k1
- * accelerators are not implemented: such a call traps ("unknown syscall"), no proof is produced. */
+ * 0x00_01_01_06 SHA_COMPRESS(w, state), the two calls of SP1's patched `sha2` crate; the BLS12-381 accelerators (Fp and
+ * Fp2 add / sub / mul, affine G1 add and double), secp256k1 affine add and double, and the 256-bit multiply UINT256_MUL,
+ * each proven by a chip of its own.  Any other precompile code traps ("unknown syscall"): no proof is produced. */
 int dvt_execute(const uint8_t *elf, size_t elf_len, const dvt_buf *stdin_bufs, size_t nbuf, uint64_t max_cycles,
                 uint8_t **public_values, size_t *pv_len, dvt_report *report, char **err_text);
 /* the same, also handing back what the guest wrote to the other file descriptors (SP1 forwards fd 1 / 2 to the
@@ -252,12 +289,16 @@ int dvt_rv32_prepare_part(dvt_prover *p, const dvt_pk *pk, const dvt_buf *stdin_
                           size_t stride, dvt_job **job, dvt_report *report);
 /* words per shard header (13) */
 uint32_t dvt_rv32_header_words(void);
-/* seconds the GPU-side thread of the last prepare spent waiting for the host executor (0 = fully hidden) */
+/* seconds the GPU-side thread of the last prepare spent waiting for the host executor (0 = fully hidden); on a handle
+ * with several members, of the member thread that waited longest */
 double dvt_rv32_job_exec_wait_seconds(const dvt_job *job);
 int dvt_rv32_prove_job(dvt_prover *p, const dvt_pk *pk, dvt_job *job, uint8_t **proof, size_t *proof_len);
 void dvt_job_free(dvt_prover *p, dvt_job *job);
 /* shards of the whole execution (a prepare_part job holds only its share of them) */
 size_t dvt_rv32_job_shards(const dvt_job *job);
+/* the device member that holds shard `shard` (global position in the execution): 0 on a one-device handle; -1 when this
+ * job does not hold the shard */
+int dvt_rv32_job_shard_member(const dvt_job *job, size_t shard);
 int dvt_rv32_commit_shard(dvt_prover *p, const dvt_pk *pk, dvt_job *job, size_t shard, uint32_t *header);
 int dvt_rv32_challenges(const uint8_t *vk, size_t vk_len, const uint32_t *headers, size_t n_shards, uint32_t out[8]);
 int dvt_rv32_prove_shard(dvt_prover *p, const dvt_pk *pk, dvt_job *job, size_t shard, const uint32_t challenges[8],
