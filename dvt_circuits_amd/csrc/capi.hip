@@ -272,6 +272,13 @@ int dvt_prover_create(const char *cfg_json, dvt_prover **out) {
         p->lanes = cfg_int(cfg_json, "lanes", dflt);
         if (p->lanes < 1 || p->lanes > MAX_LANES) return fail(nullptr, DVT_ERR_INPUT, "lanes must be 1..%d (got %d)", MAX_LANES, p->lanes);
         if (p->eng.profile) p->lanes = 1;
+        // phase-1 lanes: the config key, else DVT_PHASE1_LANES (capped at the handle's lanes, so that one setting serves
+        // handles of any lane count in an A/B run), else PHASE1_LANES_DEFAULT
+        const char *env1 = getenv("DVT_PHASE1_LANES");
+        const int dflt1 = std::min(p->lanes, env1 && *env1 ? atoi(env1) : PHASE1_LANES_DEFAULT);
+        p->phase1_lanes = p->eng.profile ? 1 : cfg_int(cfg_json, "phase1_lanes", dflt1);
+        if (p->phase1_lanes < 1 || p->phase1_lanes > p->lanes)
+            return fail(nullptr, DVT_ERR_INPUT, "phase1_lanes must be 1..lanes = 1..%d (got %d)", p->lanes, p->phase1_lanes);
     }
     if (p->log_shard < 4 || p->log_shard > 22) return fail(nullptr, DVT_ERR_INPUT, "log_shard_size must be 4..22");
     if (p->cfg.num_queries == 0 || p->cfg.num_queries > 1024 || p->cfg.pow_bits > 30)
@@ -282,7 +289,7 @@ int dvt_prover_create(const char *cfg_json, dvt_prover **out) {
     for (size_t m = 1; m < devs.size() && e == hipSuccess; m++) {
         std::unique_ptr<dvt_prover> q(new dvt_prover());
         q->owner = p.get();
-        q->cfg = p->cfg; q->log_shard = p->log_shard; q->keep_phase1 = p->keep_phase1; q->lanes = p->lanes;
+        q->cfg = p->cfg; q->log_shard = p->log_shard; q->keep_phase1 = p->keep_phase1; q->lanes = p->lanes; q->phase1_lanes = p->phase1_lanes;
         q->eng.device = devs[m];
         q->eng.profile = p->eng.profile;
         q->eng.parts_parallel_log = p->eng.parts_parallel_log;

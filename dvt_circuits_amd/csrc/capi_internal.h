@@ -15,6 +15,9 @@
 #include "rv32.h"
 
 constexpr int MAX_LANES = 3;
+// Lanes that commit (phase 1) unless the handle's config says otherwise; capped at the handle's lanes, so every lane commits:
+// two lanes beat one by 2.2-3.8 % per call in every A/B pair (profiles/README.md, round 6).
+constexpr int PHASE1_LANES_DEFAULT = MAX_LANES;
 constexpr int MAX_MEMBERS = 8;   // devices of one handle ("devices")
 
 // what dvt_rv32_prove_shard is about to collect from a running phase-2 pipeline
@@ -59,10 +62,12 @@ struct Phase2Pipe {
 };
 
 struct dvt_prover {
-    dvt::Engine eng;                  // lane 0: phase 1, the stage entry points and (with one lane) phase 2
-    // Further prover lanes (phase 2 only): own stream, ring, arena, pool and tables each, sharing the proving key's read-only
-    // device buffers.  Created on the first job that holds at least two shards.
+    dvt::Engine eng;                  // lane 0: the stage entry points, phase 1 and phase 2 of the shards it takes
+    // Further prover lanes: own stream, ring, arena, pool and tables each, sharing the proving key's read-only device
+    // buffers.  Lane k is created when phase 1 has a k-th shard waiting and no lane free for it (k < phase1_lanes), else on
+    // the first job that has at least two shards to prove in phase 2.  A job of one shard never creates one.
     int lanes = 2;
+    int phase1_lanes = 1;             // lanes that also commit (phase 1) inside a prepare, 1..lanes ("phase1_lanes")
     std::unique_ptr<dvt::Engine> more[MAX_LANES - 1];
     std::unique_ptr<Phase2Pipe> pipe;   // the phase-2 pipeline of the current job, if one runs (see Phase2Pipe)
     dvt::StarkConfig cfg;
@@ -70,7 +75,8 @@ struct dvt_prover {
     uint64_t max_cycles = 1ull << 36;
     bool keep_phase1 = true;          // keep K0 output, main LDEs and tree of phase 1 in HBM for phase 2 ("keep_phase1": 0 recomputes)
     uint32_t exec_threads = 0;        // trace-mode executor threads of the prove pipeline ("exec_threads", 0 = from the host's core count)
-    hipStream_t copy_stream = nullptr;            // record uploads overlap the previous shard's kernels
+    // record uploads overlap the lanes' kernels; with several phase-1 lanes the auxiliary uploads and their K0 launches too
+    hipStream_t copy_stream = nullptr;
     std::vector<dvt::rv32::CycleRec *> pinned;    // pinned staging buffers of 2^log_shard records each, reused across calls
     // Pinned staging of everything else a shard uploads (auxiliary traces, precompile calls).  Handing the runtime PAGEABLE
     // memory makes it pin the pages on the fly; when the vectors are freed afterwards the driver quiesces every queue of the

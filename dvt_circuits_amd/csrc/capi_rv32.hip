@@ -71,6 +71,7 @@ struct ShardJob {
     // job's working buffers are used and phase 2 runs K0 again
     uint32_t *d_cpu = nullptr, *d_byte = nullptr, *d_prog = nullptr;
     bool traces_valid = false;
+    int lane = 0;             // the lane that first committed the shard: cache and kept K0 output are from its pool
     uint32_t header[HEADER_WORDS] = {};
     bool header_valid = false;   // phase 1 ran (inside the prepare pipeline, or by commit_shard) and no phase 2 has consumed it
 };
@@ -108,8 +109,10 @@ struct dvt_job {
     ShardJob *at(size_t pos) { return pos >= first && (pos - first) % stride == 0 && (pos - first) / stride < shards.size() ? &shards[(pos - first) / stride] : nullptr; }
 };
 
-// (no phase-2 pipeline runs: the phase-1 buffers go back to lane 0's pool only after every lane is done)
-// Every buffer returns to the pool of the member (and lane) it came from.
+// (no phase-1 worker and no phase-2 pipeline runs: buffers go back to the pools only after every lane is done)
+// Every buffer returns to the pool of the member and lane it came from: what a shard uploaded to lane 0's, what phase 1 kept
+// (K0 output; LDEs and tree through the cache) to the pool of the lane that committed the shard, the working buffers to
+// their lane's.
 static void job_release(dvt_prover *p, dvt_job *j) {
     if (!j) return;
     for (size_t m = j->parts.size(); m-- > 0;) {
@@ -122,7 +125,10 @@ static void job_release(dvt_prover *p, dvt_job *j) {
     for (auto &s : j->shards) {
         pool.free(s.d_recs);
         for (auto &d : s.d_aux) pool.free(d);
-        for (uint32_t *d : {s.d_cpu, s.d_byte, s.d_prog}) pool.free(d);
+        if (s.d_cpu || s.d_byte || s.d_prog) {
+            DevPool &kept = lane_engine(p, s.lane).pool;
+            for (uint32_t *d : {s.d_cpu, s.d_byte, s.d_prog}) kept.free(d);
+        }
         s.cache.release();
     }
     for (int k = 0; k < MAX_LANES; k++) {
@@ -166,16 +172,21 @@ static int shard_traces(const Lane &c, const dvt_pk *pk, dvt_job *j, ShardJob &s
     return DVT_OK;
 }
 
-// Two members of one handle on one physical device read the same free bytes: the first phase 1 of a shard, which asks
-// how much is free and then allocates what it keeps (inside commit_main_root), takes turns between them.  A shard that is
-// committed again has its buffers and does not wait; nor do one-device handles and members alone on their device.
+// Committers on one physical device (the phase-1 lanes of a member, the members of a handle that share the device) read the
+// same free bytes: the first phase 1 of a shard, which asks how much is free and then allocates what it keeps, takes
+// turns between them.  The turn covers the question and every allocation of the commit and ends before the commit's first
+// LDE kernel is launched (commit_main_root), so the kernels of two committers overlap.  While a member commits on several
+// lanes, every use of its pools is made under the turn, the feeder's uploads into lane 0's pool included: that is what
+// keeps a pool single-threaded.  A shard that is committed again outside a prepare has its buffers and does not wait; nor
+// does a one-lane member alone on its device.
 static std::mutex &device_turn(int dev) {
     static std::mutex mu[64];
     return mu[dev & 63];
 }
 
-// phase 1 of a shard (lane 0 of its member): K0 + K1..K3 of the main traces -> header
-static int shard_commit(const Lane &c, const dvt_pk *pk, dvt_job *j, ShardJob &s) {
+// phase 1 of a shard: K0 + K1..K3 of the main traces -> header.  `concurrent`: other threads of this member commit or upload
+// meanwhile (the phase-1 lanes of a prepare)
+static int shard_commit(const Lane &c, const dvt_pk *pk, dvt_job *j, ShardJob &s, bool concurrent = false) {
     dvt_prover *p = c.p;
     std::vector<ChipTrace> traces;
     const bool time_stages = getenv("DVT_TIME_PREPARE") != nullptr;
@@ -185,19 +196,21 @@ static int shard_commit(const Lane &c, const dvt_pk *pk, dvt_job *j, ShardJob &s
     };
     // keep the phase-1 results in HBM while they fit (about 3 GB per 2^21-cycle shard); otherwise phase 2 recomputes
     std::unique_lock<std::mutex> turn;
-    if (p->shares_device && p->keep_phase1 && !s.cache.tree) turn = std::unique_lock<std::mutex>(device_turn(c.eng.device));
+    if (concurrent || (p->shares_device && p->keep_phase1 && !s.cache.tree)) turn = std::unique_lock<std::mutex>(device_turn(c.eng.device));
     size_t free_b = 0, total_b = 0;
     if (p->keep_phase1 && !s.cache.tree) { (void)hipMemGetInfo(&free_b, &total_b); free_b += c.eng.pool.cached_bytes; }   // (only the first commit of a shard asks)
     lap("memory asked");
-    // the further lanes' phase-2 arenas are not there yet on the first job: leave room for them (lane 0's arena is the measure
-    // of one), so that the kept caches do not take what the second lane's working set then cannot get
+    // the further lanes' arenas are not there yet on the first job: leave room for them (the largest arena of this member's
+    // lanes is the measure of one), so that the kept caches do not take what another lane's working set then cannot get
     // (and for the lanes of the members that share this device, whose phase 1 waits for its turn meanwhile)
-    size_t lane_room = 0;
+    size_t lane_room = 0, one_arena = p->eng.arena.cap;
+    for (auto &e : p->more)
+        if (e) one_arena = std::max(one_arena, e->arena.cap);
     auto room_of = [&](dvt_prover *q) {
         for (int k = 0; k < q->lanes; k++) {
-            if (q == p && k == 0) continue;
+            if (q == p && k == c.k) continue;
             const size_t have = k == 0 ? q->eng.arena.cap : q->more[k - 1] ? q->more[k - 1]->arena.cap : 0;
-            if (c.eng.arena.cap > have) lane_room += c.eng.arena.cap - have;
+            if (one_arena > have) lane_room += one_arena - have;
         }
     };
     room_of(p);
@@ -209,6 +222,7 @@ static int shard_commit(const Lane &c, const dvt_pk *pk, dvt_job *j, ShardJob &s
     MainCache *keep = p->keep_phase1 && (s.cache.tree || free_b > ((size_t)24 << 30) + lane_room) ? &s.cache : nullptr;
     if (keep && !s.d_cpu) {
         DevPool &pool = c.eng.pool;
+        s.lane = c.k;
         bool ok = pool.alloc(&s.d_cpu, ((size_t)RV32_CPU_MAIN_W << s.log_n[RV32_CHIP_CPU]) * 4) == hipSuccess && pool.alloc(&s.d_byte, j->byte_words * 4) == hipSuccess &&
                   pool.alloc(&s.d_prog, j->prog_words * 4) == hipSuccess;
         if (!ok) {  // not fatal: fall back to the shared working buffers
@@ -221,7 +235,7 @@ static int shard_commit(const Lane &c, const dvt_pk *pk, dvt_job *j, ShardJob &s
     if (rc) return rc;
     lap("K0 launched");
     Digest root;
-    if (!c.eng.commit_main_root(pk->key, traces, &root, keep)) return engine_fail(c.err, c.eng);
+    if (!c.eng.commit_main_root(pk->key, traces, &root, keep, &turn)) return engine_fail(c.err, c.eng);
     lap("main root");
     for (int k = 0; k < 8; k++) s.header[k] = root.d[k].canonical();
     for (uint32_t k = 0; k < N_PUB; k++) s.header[8 + k] = s.pubs[k].canonical();
@@ -230,7 +244,7 @@ static int shard_commit(const Lane &c, const dvt_pk *pk, dvt_job *j, ShardJob &s
 }
 
 // phase 2 of a shard: K0..K9 with the common challenges -> shard proof words
-// (on any lane: the shard's phase-1 buffers came from lane 0's pool and are only read here)
+// (on any lane: the shard's phase-1 buffers came from the pool of the lane that committed it and are only read here)
 static int shard_prove(const Lane &c, const dvt_pk *pk, dvt_job *j, ShardJob &s, const PermChallenges &gc, std::vector<uint32_t> *words) {
     std::vector<ChipTrace> traces;
     int rc = shard_traces(c, pk, j, s, &traces, s.cache.valid);
@@ -427,30 +441,41 @@ bool events_of(const ReadyShard &r, int c, const void **src, size_t *bytes) {
 }
 }  // namespace
 
-// upload of one ready shard into a new shard of the job: records on the copy stream (pinned source, overlaps the compute
-// stream; `ev` is recorded after them), the small auxiliary traces on the compute stream
-static int upload_shard(const Lane &lane, ReadyShard &r, dvt_job *j, hipEvent_t ev) {
+// Upload of one ready shard into the shard s of the job: records on the copy stream (pinned source, overlaps the compute
+// streams; `ev` is recorded after them), the small auxiliary traces and the K0 launches of the precompile chips on `aux`.
+// With one phase-1 lane `aux` is the lane's compute stream.  The feeder of several phase-1 lanes passes the copy stream,
+// so that the wait at the end (the staging buffer is reused by the next shard, the error words are read) is for this upload
+// alone and no committing lane's stream is drained; it allocates from lane 0's pool under the device's turn (device_turn).
+static int upload_shard(const Lane &lane, ReadyShard &r, ShardJob &s, hipEvent_t ev, hipStream_t aux, bool feeder) {
     dvt_prover *p = lane.p;
     Engine &e = lane.eng;
     const MachineDesc *m = machine_rv32();
-    j->shards.emplace_back();
-    ShardJob &s = j->shards.back();
     s.index = r.meta.index; s.n_recs = r.meta.n_recs; s.next_pc = r.meta.next_pc;
     for (int c = 0; c < m->n_chips; c++) { s.log_n[c] = r.aux.log_n[c]; s.present[c] = r.aux.present[c]; }
-    HIP_TRY(lane.err, e.pool.alloc(&s.d_recs, s.n_recs * sizeof(rv32::CycleRec)));
-    HIP_TRY(lane.err, hipMemcpyAsync(s.d_recs, r.buf, s.n_recs * sizeof(rv32::CycleRec), hipMemcpyHostToDevice, p->copy_stream));
-    HIP_TRY(lane.err, hipEventRecord(ev, p->copy_stream));
     uint32_t *d_calls[rv32::N_CHIPS] = {};   // per precompile chip: [error word, padding to 16 bytes, the calls]
     size_t stage_bytes = 0;
-    for (int c = 0; c < m->n_chips; c++) {
-        if (c == RV32_CHIP_CPU || !s.present[c]) continue;
-        const void *src = nullptr;
-        size_t bytes = 0;
-        if (!events_of(r, c, &src, &bytes)) bytes = r.aux.main[c].size() * 4;
-        stage_bytes += (bytes + 255) & ~(size_t)255;
+    {
+        std::unique_lock<std::mutex> turn;
+        if (feeder) turn = std::unique_lock<std::mutex>(device_turn(e.device));
+        HIP_TRY(lane.err, e.pool.alloc(&s.d_recs, s.n_recs * sizeof(rv32::CycleRec)));
+        for (int c = 0; c < m->n_chips; c++) {
+            if (c == RV32_CHIP_CPU || !s.present[c]) continue;
+            const void *src = nullptr;
+            size_t bytes = 0;
+            if (events_of(r, c, &src, &bytes)) {
+                HIP_TRY(lane.err, e.pool.alloc(&s.d_aux[c], ((size_t)m->chips[c].main_w << s.log_n[c]) * 4));
+                HIP_TRY(lane.err, e.pool.alloc(&d_calls[c], 16 + bytes));
+            } else {
+                bytes = r.aux.main[c].size() * 4;
+                HIP_TRY(lane.err, e.pool.alloc(&s.d_aux[c], bytes));
+            }
+            stage_bytes += (bytes + 255) & ~(size_t)255;
+        }
     }
+    HIP_TRY(lane.err, hipMemcpyAsync(s.d_recs, r.buf, s.n_recs * sizeof(rv32::CycleRec), hipMemcpyHostToDevice, p->copy_stream));
+    HIP_TRY(lane.err, hipEventRecord(ev, p->copy_stream));
     if (stage_bytes > p->aux_pinned_bytes) {
-        HIP_TRY(lane.err, hipStreamSynchronize(e.stream));
+        HIP_TRY(lane.err, hipStreamSynchronize(aux));
         if (p->aux_pinned) HIP_TRY(lane.err, hipHostFree(p->aux_pinned));
         p->aux_pinned = nullptr; p->aux_pinned_bytes = 0;
         HIP_TRY(lane.err, hipHostMalloc(&p->aux_pinned, stage_bytes + stage_bytes / 4));
@@ -470,49 +495,193 @@ static int upload_shard(const Lane &lane, ReadyShard &r, dvt_job *j, hipEvent_t 
         size_t bytes = 0;
         if (events_of(r, c, &src, &bytes)) {   // K0 of this chip on the GPU (after the byte counts are in): [error word, padding to 16 bytes, the events]
             const size_t words = (size_t)m->chips[c].main_w << s.log_n[c];
-            HIP_TRY(lane.err, e.pool.alloc(&s.d_aux[c], words * 4));
-            HIP_TRY(lane.err, hipMemsetAsync(s.d_aux[c], 0, words * 4, e.stream));
-            HIP_TRY(lane.err, e.pool.alloc(&d_calls[c], 16 + bytes));
-            HIP_TRY(lane.err, hipMemsetAsync(d_calls[c], 0, 16, e.stream));
-            HIP_TRY(lane.err, hipMemcpyAsync(d_calls[c] + 4, staged(src, bytes), bytes, hipMemcpyHostToDevice, e.stream));
+            HIP_TRY(lane.err, hipMemsetAsync(s.d_aux[c], 0, words * 4, aux));
+            HIP_TRY(lane.err, hipMemsetAsync(d_calls[c], 0, 16, aux));
+            HIP_TRY(lane.err, hipMemcpyAsync(d_calls[c] + 4, staged(src, bytes), bytes, hipMemcpyHostToDevice, aux));
             n_events[c] = c == RV32_CHIP_SHIFT ? r.big.shifts.size() : c == RV32_CHIP_MEM_INIT ? r.big.mem_rows->size() : r.big.ev[c].size();
             continue;
         }
         size_t words = r.aux.main[c].size();
-        HIP_TRY(lane.err, e.pool.alloc(&s.d_aux[c], words * 4));
-        HIP_TRY(lane.err, hipMemcpyAsync(s.d_aux[c], staged(r.aux.main[c].data(), words * 4), words * 4, hipMemcpyHostToDevice, e.stream));
+        HIP_TRY(lane.err, hipMemcpyAsync(s.d_aux[c], staged(r.aux.main[c].data(), words * 4), words * 4, hipMemcpyHostToDevice, aux));
         // byte / program multiplicities stay plain integers until K0 has added the cpu rows' lookups
-        if (c != RV32_CHIP_BYTE && c != RV32_CHIP_PROGRAM) HIP_TRY(lane.err, launch_to_internal(e.stream, s.d_aux[c], words));
+        if (c != RV32_CHIP_BYTE && c != RV32_CHIP_PROGRAM) HIP_TRY(lane.err, launch_to_internal(aux, s.d_aux[c], words));
     }
     for (int c = 0; c < m->n_chips; c++) {
         if (!d_calls[c]) continue;
         const size_t words = (size_t)m->chips[c].main_w << s.log_n[c];
         if (c == RV32_CHIP_SHIFT) {   // (these two write Montgomery words themselves)
-            HIP_TRY(lane.err, rv32::launch_k0_shift_rows(e.stream, reinterpret_cast<const rv32::AluEvent *>(d_calls[c] + 4), n_events[c], s.d_aux[c], s.log_n[c], s.d_aux[RV32_CHIP_BYTE]));
+            HIP_TRY(lane.err, rv32::launch_k0_shift_rows(aux, reinterpret_cast<const rv32::AluEvent *>(d_calls[c] + 4), n_events[c], s.d_aux[c], s.log_n[c], s.d_aux[RV32_CHIP_BYTE]));
         } else if (c == RV32_CHIP_MEM_INIT) {
-            HIP_TRY(lane.err, rv32::launch_k0_mem_init_rows(e.stream, reinterpret_cast<const rv32::MemInitRow *>(d_calls[c] + 4), n_events[c], s.d_aux[c], s.log_n[c], s.d_aux[RV32_CHIP_BYTE]));
+            HIP_TRY(lane.err, rv32::launch_k0_mem_init_rows(aux, reinterpret_cast<const rv32::MemInitRow *>(d_calls[c] + 4), n_events[c], s.d_aux[c], s.log_n[c], s.d_aux[RV32_CHIP_BYTE]));
         } else {
-            HIP_TRY(lane.err, rv32::launch_k0_bigop_rows(e.stream, c, reinterpret_cast<const rv32::BigOpEvent *>(d_calls[c] + 4), (uint32_t)n_events[c], s.index,
+            HIP_TRY(lane.err, rv32::launch_k0_bigop_rows(aux, c, reinterpret_cast<const rv32::BigOpEvent *>(d_calls[c] + 4), (uint32_t)n_events[c], s.index,
                                                        s.d_aux[c], s.log_n[c], s.d_aux[RV32_CHIP_BYTE], d_calls[c]));
-            HIP_TRY(lane.err, launch_to_internal(e.stream, s.d_aux[c], words));
+            HIP_TRY(lane.err, launch_to_internal(aux, s.d_aux[c], words));
         }
     }
-    HIP_TRY(lane.err, hipStreamSynchronize(e.stream));   // (the staging buffer is reused by the next shard; the error words below)
+    HIP_TRY(lane.err, hipStreamSynchronize(aux));   // (the staging buffer is reused by the next shard; the error words below)
+    int rc = DVT_OK;
     for (int c = 0; c < m->n_chips; c++) {
         if (!d_calls[c]) continue;
         uint32_t row_err = 0;
-        const hipError_t he = hipMemcpy(&row_err, d_calls[c], 4, hipMemcpyDeviceToHost);
-        e.pool.free(d_calls[c]);
-        HIP_TRY(lane.err, he);
-        if (row_err) return fail(lane.err, DVT_ERR_DEVICE, "K0 of chip %s: %s", m->chips[c].name, rv32::bigop_row_error_text(row_err));
+        const hipError_t he = rc ? hipSuccess : hipMemcpy(&row_err, d_calls[c], 4, hipMemcpyDeviceToHost);
+        {
+            std::unique_lock<std::mutex> turn;
+            if (feeder) turn = std::unique_lock<std::mutex>(device_turn(e.device));
+            e.pool.free(d_calls[c]);
+        }
+        if (rc) continue;
+        if (he != hipSuccess) rc = fail(lane.err, DVT_ERR_DEVICE, "reading the K0 error word: %s", hipGetErrorString(he));
+        else if (row_err) rc = fail(lane.err, DVT_ERR_DEVICE, "K0 of chip %s: %s", m->chips[c].name, rv32::bigop_row_error_text(row_err));
     }
+    if (rc) return rc;
     for (auto x : r.aux.pubs) s.pubs.push_back(Fp::from_canonical(x));
     return DVT_OK;
 }
 
+// lane k of a member (k >= 1), made when it is first needed
+static int ensure_lane(dvt_prover *p, int k, std::string &err) {
+    if (p->more[k - 1]) return DVT_OK;
+    std::unique_ptr<Engine> e(new Engine());
+    e->profile = false;
+    e->parts_parallel_log = p->eng.parts_parallel_log;
+    const hipError_t r = e->init(p->eng.device);
+    if (r != hipSuccess) {
+        e->shutdown();
+        return fail(err, DVT_ERR_DEVICE, "prover lane %d: %s", k, hipGetErrorString(r));
+    }
+    p->more[k - 1] = std::move(e);
+    return DVT_OK;
+}
+
+// ------------------------------------------------------------------ phase 1 on several lanes ("phase1_lanes" > 1)
+// The calling thread is the feeder: it takes the shards from the executor in execution order, uploads each (upload_shard on
+// the copy stream) and queues it.  Up to phase1_lanes workers, one per lane and each on a thread of its own, take the next
+// queued shard and run shard_commit on their lane's engine, so the LDE of one shard runs under the leaf hashing of another.
+// Lane k's worker (and, for k >= 1, its engine) is started when a shard is queued and no started worker is free: a job of
+// one shard starts lane 0 only.  The feeder uploads the next shard once the queue is empty, so a member has at most
+// phase1_lanes shards in commit and one uploaded or in upload: that many pinned record buffers are out of the executor's
+// hands (job_prepare).  A buffer goes back when the commit that read it is done.
+namespace {
+struct Phase1Lanes {
+    struct Item { ShardJob *s; size_t pos; rv32::CycleRec *buf; };
+    struct Worker {   // (workers report here, never into p->err)
+        std::thread th;
+        int rc = DVT_OK;
+        size_t at = 0;   // the position of the shard that failed
+        std::string err;
+    };
+    std::mutex mu;
+    std::condition_variable cv;
+    std::deque<Item> queue;   // uploaded, waiting for a lane
+    int idle = 0;             // started workers that wait for a shard
+    bool closed = false, failed = false;
+    Worker w[MAX_LANES];
+    int n = 0;                // started workers (written by the feeder only)
+};
+}  // namespace
+
+static void phase1_worker(dvt_prover *p, const dvt_pk *pk, dvt_job *j, Executor &ex, Phase1Lanes *q, int k) {
+    Phase1Lanes::Worker &me = q->w[k];
+    const Lane c{p, k, lane_engine(p, k), me.err};
+    const hipError_t dev = hipSetDevice(p->eng.device);
+    for (;;) {
+        Phase1Lanes::Item it;
+        {
+            std::unique_lock<std::mutex> lk(q->mu);
+            q->idle++;
+            q->cv.wait(lk, [&] { return q->failed || q->closed || !q->queue.empty(); });
+            q->idle--;
+            if (q->failed || q->queue.empty()) return;
+            it = q->queue.front();
+            q->queue.pop_front();
+            q->cv.notify_all();   // (the feeder uploads the next shard)
+        }
+        const int rc = dev != hipSuccess ? fail(me.err, DVT_ERR_DEVICE, "hipSetDevice: %s", hipGetErrorString(dev)) : shard_commit(c, pk, j, *it.s, true);
+        ex.give_back(it.buf);
+        if (rc) {
+            ex.cancel();
+            std::lock_guard<std::mutex> lk(q->mu);
+            me.rc = rc;
+            me.at = it.pos;
+            q->failed = true;   // the other lanes stop at their next shard boundary, the feeder after its upload
+            q->cv.notify_all();
+            return;
+        }
+    }
+}
+
+static int commit_on_lanes(const Lane &c, const dvt_pk *pk, dvt_job *j, Executor &ex, bool time_stages, Clock::time_point t_begin) {
+    dvt_prover *p = c.p;
+    Phase1Lanes q;
+    std::deque<ShardJob> built;   // (the workers hold references: j->shards takes the shards, in execution order, at the end)
+    int rc = DVT_OK;
+    size_t rc_at = ~(size_t)0;
+    hipEvent_t ev = nullptr;
+    (void)hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+    for (size_t pos = j->first;; pos += j->stride) {
+        {
+            std::unique_lock<std::mutex> lk(q.mu);
+            q.cv.wait(lk, [&] { return q.failed || q.queue.empty(); });
+            if (q.failed) break;
+        }
+        ReadyShard r;
+        if (!ex.take(pos, &r, &j->t_exec_wait)) break;
+        rc_at = pos;
+        if (!r.err.empty()) {
+            rc = r.unsupported ? fail(c.err, DVT_ERR_UNSUPPORTED, "no chip for an instruction of the guest (%s)", r.err.c_str())
+                               : fail(c.err, DVT_ERR_GUEST, "guest trapped: %s", r.err.c_str());
+            ex.give_back(r.buf);
+            break;
+        }
+        if (time_stages) fprintf(stderr, "[prepare] %.2f ms: shard at position %zu ready\n", ms_since(t_begin), pos);
+        built.emplace_back();
+        rc = upload_shard(c, r, built.back(), ev, p->copy_stream, true);
+        if (time_stages) fprintf(stderr, "[prepare] %.2f ms: uploaded\n", ms_since(t_begin));
+        if (rc) { ex.give_back(r.buf); break; }
+        bool start;
+        {
+            std::lock_guard<std::mutex> lk(q.mu);
+            q.queue.push_back({&built.back(), pos, r.buf});
+            start = q.idle == 0 && q.n < p->phase1_lanes;
+            q.cv.notify_all();
+        }
+        if (!start) continue;
+        if (q.n > 0) {   // (an engine allocates, and the committers read p->more: under the turn)
+            std::lock_guard<std::mutex> turn(device_turn(p->eng.device));
+            rc = ensure_lane(p, q.n, c.err);
+        }
+        if (rc) break;
+        q.w[q.n].th = std::thread(phase1_worker, p, pk, j, std::ref(ex), &q, q.n);
+        q.n++;
+    }
+    if (rc) ex.cancel();
+    {
+        std::lock_guard<std::mutex> lk(q.mu);
+        if (rc) q.failed = true;
+        q.closed = true;
+        q.cv.notify_all();
+    }
+    for (int k = 0; k < q.n; k++) q.w[k].th.join();
+    for (auto &it : q.queue) ex.give_back(it.buf);   // (left behind by a failure)
+    (void)hipStreamSynchronize(p->copy_stream);
+    for (int k = 0; k < q.n; k++) (void)hipStreamSynchronize(lane_engine(p, k).stream);
+    (void)hipEventDestroy(ev);
+    for (auto &s : built) j->shards.push_back(std::move(s));
+    for (int k = 0; k < q.n; k++)   // the error of the lowest failed position
+        if (q.w[k].rc && (!rc || q.w[k].at < rc_at)) {
+            rc_at = q.w[k].at;
+            rc = fail(c.err, q.w[k].rc, "%s", q.w[k].err.c_str());
+        }
+    if (time_stages) fprintf(stderr, "[prepare] %.2f ms: phase 1 of the last shard done (%d lanes)\n", ms_since(t_begin), q.n);
+    return rc;
+}
+
 // Phase 1 of the job's shards in execution order, as the executor hands them over: the records of shard i+1 come in on the
-// copy stream while the GPU runs phase 1 of shard i.  Every pinned buffer goes back to the executor.
+// copy stream while the GPU runs phase 1 of shard i.  Every pinned buffer goes back to the executor.  (One phase-1 lane: one
+// compute stream, the calling thread uploads and commits in turn.)
 static int commit_overlapped(const Lane &c, const dvt_pk *pk, dvt_job *j, Executor &ex, bool time_stages, Clock::time_point t_begin) {
+    if (c.p->phase1_lanes > 1) return commit_on_lanes(c, pk, j, ex, time_stages, t_begin);
     int rc = DVT_OK;
     hipEvent_t ev = nullptr;
     (void)hipEventCreateWithFlags(&ev, hipEventDisableTiming);
@@ -528,7 +697,10 @@ static int commit_overlapped(const Lane &c, const dvt_pk *pk, dvt_job *j, Execut
             break;
         }
         if (time_stages && got) fprintf(stderr, "[prepare] %.2f ms: shard at position %zu ready\n", ms_since(t_begin), pos);
-        if (got) rc = upload_shard(c, r, j, ev);
+        if (got) {
+            j->shards.emplace_back();
+            rc = upload_shard(c, r, j->shards.back(), ev, c.eng.stream, false);
+        }
         if (time_stages && got) fprintf(stderr, "[prepare] %.2f ms: uploaded\n", ms_since(t_begin));
         // phase 1 of the previous shard runs while the copy engine brings this one in
         if (rc == DVT_OK && have_prev) {
@@ -570,7 +742,7 @@ static int prepare_verdict(std::string &err, const FastPass &f, int rc) {
 }
 
 // Phase 1 on a handle with several members: the k-th shard the job holds goes to member k mod G.  Every member runs the
-// upload + phase-1 loop for its shards on a thread of its own (its device, copy stream, staging and lane-0 engine), all fed by
+// upload + phase-1 loop for its shards on a thread of its own (its device, copy stream, staging and lanes), all fed by
 // the one executor.  The threads report into strings of their own, never into p->err; the error is that of the lowest
 // failed position.  Every thread is joined and every member's streams are idle on return.
 static int commit_on_members(dvt_prover *p, const dvt_pk *pk, dvt_job *j, Executor &ex, bool time_stages, Clock::time_point t_begin) {
@@ -597,7 +769,11 @@ static int commit_on_members(dvt_prover *p, const dvt_pk *pk, dvt_job *j, Execut
     size_t at = ~(size_t)0;
     for (size_t m = G; m-- > 0;) {
         dvt_prover *mem = member(p, m);
-        if (select_member(p, m) == DVT_OK) { (void)hipStreamSynchronize(mem->copy_stream); (void)hipStreamSynchronize(mem->eng.stream); }
+        if (select_member(p, m) == DVT_OK) {
+            (void)hipStreamSynchronize(mem->copy_stream);
+            for (int k = 0; k < mem->lanes; k++)
+                if (k == 0 || mem->more[k - 1]) (void)hipStreamSynchronize(lane_engine(mem, k).stream);
+        }
         j->t_exec_wait = std::max(j->t_exec_wait, j->parts[m]->t_exec_wait);
         const size_t pos = j->parts[m]->first + j->parts[m]->shards.size() * j->parts[m]->stride;   // about where it stopped
         if (runs[m].rc && pos <= at) { at = pos; rc = runs[m].rc; p->err = runs[m].err; }
@@ -612,9 +788,10 @@ static int job_prepare(dvt_prover *p, const dvt_pk *pk, const dvt_buf *stdin_buf
     if (pk->peers.size() + 1 != G) return fail(p, DVT_ERR_INPUT, "the proving key holds %zu device copies, this handle has %zu devices", pk->peers.size() + 1, G);
     unsigned hw = std::thread::hardware_concurrency();
     const unsigned n_workers = p->exec_threads ? p->exec_threads : std::max(1u, std::min(6u, hw > 3 ? hw - 2 : 1u));
-    // pinned staging: one buffer per worker + two in flight on the GPU side of every member.  Any worker's buffer may go to
-    // any member, so with several members the buffers are pinned for every device (portable).
-    const size_t want_bufs = n_workers + 2 * G;
+    // pinned staging: one buffer per worker + two in flight on the GPU side of every member (one in upload, one in commit) and
+    // one more for each further lane that commits.  Any worker's buffer may go to any member, so with several members the
+    // buffers are pinned for every device (portable).
+    const size_t want_bufs = n_workers + (2 + (size_t)(p->phase1_lanes - 1)) * G;
     while (p->pinned.size() < want_bufs) {
         rv32::CycleRec *b = nullptr;
         HIP_TRY(p, hipHostMalloc(&b, sizeof(rv32::CycleRec) << p->log_shard, G > 1 ? hipHostMallocPortable : hipHostMallocDefault));
@@ -648,20 +825,10 @@ static int job_prepare(dvt_prover *p, const dvt_pk *pk, const dvt_buf *stdin_buf
 }
 
 // ------------------------------------------------------------------ the phase-2 pipeline (Phase2Pipe)
-// the further lanes' engines, made on the first job that has at least two shards to prove
+// the further lanes' engines that phase 1 has not made, on the first job that has at least two shards to prove
 static int ensure_lanes(dvt_prover *p) {
-    for (int k = 1; k < p->lanes; k++) {
-        if (p->more[k - 1]) continue;
-        std::unique_ptr<Engine> e(new Engine());
-        e->profile = false;
-        e->parts_parallel_log = p->eng.parts_parallel_log;
-        const hipError_t r = e->init(p->eng.device);
-        if (r != hipSuccess) {
-            e->shutdown();
-            return fail(p, DVT_ERR_DEVICE, "prover lane %d: %s", k, hipGetErrorString(r));
-        }
-        p->more[k - 1] = std::move(e);
-    }
+    for (int k = 1; k < p->lanes; k++)
+        if (int rc = ensure_lane(p, k, p->err)) return rc;
     return DVT_OK;
 }
 
@@ -706,7 +873,8 @@ static int pipe_start(dvt_prover *p, const dvt_pk *pk, dvt_job *j, size_t k0, co
     if (order.size() < (always ? 1u : 2u)) return DVT_OK;
     int rc = ensure_lanes(p);
     if (rc) return rc;
-    HIP_TRY(p, hipStreamSynchronize(p->eng.stream));   // phase 1 (lane 0) is complete before another lane reads its buffers
+    for (int k = 0; k < p->lanes; k++)   // phase 1 (on whichever lanes committed) is complete before another lane reads its buffers
+        if (k == 0 || p->more[k - 1]) HIP_TRY(p, hipStreamSynchronize(lane_engine(p, k).stream));
     std::unique_ptr<Phase2Pipe> pp(new Phase2Pipe());
     pp->job = j;
     pp->pk = pk;

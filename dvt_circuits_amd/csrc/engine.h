@@ -7,6 +7,7 @@
 // structure, see DESIGN.md "Protocol".
 #pragma once
 #include <map>
+#include <mutex>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -72,7 +73,8 @@ struct Arena {
 // Size-keyed cache of freed device buffers.  The per-shard buffers of a prove (cycle records, cpu trace, main-trace LDEs,
 // Merkle tree: ~3 GB per 2^21-cycle shard) have the same sizes shard after shard and call after call; hipMalloc / hipFree
 // of them cost ~80 ms per shard (measured: 3.85 s instead of 1.3 s per 32-shard prove), a cached buffer costs nothing.
-// Not thread-safe: callers hold the prover's mutex.
+// Not thread-safe: one thread at a time (the API thread under the prover's mutex; while phase 1 runs on several lanes, a lane's
+// worker or the feeder under the device's admission lock).
 struct DevPool {
     std::multimap<size_t, void *> cached;
     std::unordered_map<void *, size_t> live;
@@ -194,8 +196,11 @@ class Engine {
                      const StarkConfig &cfg, ShardProof *out, const PermChallenges *global = nullptr,
                      const MainCache *cached = nullptr);
     // phase 1 of a multi-shard proof: K1-K3 of the main traces only -> main_root; with keep != nullptr the
-    // LDEs and the tree stay in HBM (hipMalloc'ed into *keep) for prove_shard(..., cached = keep)
-    bool commit_main_root(const ProvingKey &pk, const std::vector<ChipTrace> &traces, Digest *root, MainCache *keep = nullptr);
+    // LDEs and the tree stay in HBM (from this engine's pool, into *keep) for prove_shard(..., cached = keep).  `admitted`: a
+    // lock the caller holds over "how much is free?" and the allocations that follow; it is released once every buffer of
+    // the commit is allocated, before the first kernel is launched.
+    bool commit_main_root(const ProvingKey &pk, const std::vector<ChipTrace> &traces, Digest *root, MainCache *keep = nullptr,
+                          std::unique_lock<std::mutex> *admitted = nullptr);
 
     // ---- host side of the K4 running sum, K6, K7 and the K9 grind: prove_shard and the stage entry points (capi.hip) both
     // go through these.  Device words are in Montgomery form.

@@ -401,7 +401,8 @@ struct EventTimer {
 };
 }  // namespace
 
-bool Engine::commit_main_root(const ProvingKey &pk, const std::vector<ChipTrace> &traces, Digest *root, MainCache *keep) {
+bool Engine::commit_main_root(const ProvingKey &pk, const std::vector<ChipTrace> &traces, Digest *root, MainCache *keep,
+                              std::unique_lock<std::mutex> *admitted) {
     times = StageTimes();
     EventTimer t_all(stream, profile);
     HIPCHK(hipSetDevice(device));
@@ -435,9 +436,12 @@ bool Engine::commit_main_root(const ProvingKey &pk, const std::vector<ChipTrace>
         if (!reuse) { keep->release(); keep->lde_words = want; keep->pool = &pool; }
         keep->valid = false;
     }
-    size_t ti = 0;
     lap("cache decided");
-    for (auto &t : traces) {
+    // every buffer first, then the launches: whoever serialises the admission of shards (`admitted`) waits for the
+    // allocations only, not for the kernels
+    std::vector<uint32_t *> ldes;
+    for (size_t ti = 0; ti < traces.size(); ti++) {
+        const ChipTrace &t = traces[ti];
         const ChipDesc &d = m->chips[t.chip_id];
         uint32_t *lde = nullptr;
         if (keep && reuse) {
@@ -449,21 +453,8 @@ bool Engine::commit_main_root(const ProvingKey &pk, const std::vector<ChipTrace>
             lde = arena.alloc<uint32_t>(((size_t)d.main_w << t.log_n) * 2);
         }
         if (!lde) return fail("commit: device arena exhausted");
-        if (time_stages && ti == 0) lap("first buffer");
-        {
-            EventTimer t_lde(stream, profile);
-            HIPCHK(launch_coset_lde(stream, tabs, const_cast<uint32_t *>(t.d_main), d_scratch, lde, d.main_w, t.log_n, 0));
-            if (profile) {
-                times.lde_ms += t_lde.stop();
-                times.lde_alg_bytes += 12.0 * d.main_w * (double)((size_t)1 << t.log_n);
-                times.lde_calls++;
-            }
-        }
-        mats.push_back({lde, (uint32_t)d.main_w, t.log_n + 1});
-        ti++;
-        if (time_stages) lap(d.name);
+        ldes.push_back(lde);
     }
-    lap("LDEs launched");
     const uint32_t hmax = max_log_n + 1;
     uint32_t *tree = nullptr;
     if (keep && reuse) {
@@ -476,6 +467,25 @@ bool Engine::commit_main_root(const ProvingKey &pk, const std::vector<ChipTrace>
         tree = arena.alloc<uint32_t>((((size_t)2 << hmax) - 1) * 8);
     }
     if (!tree) return fail("commit: device arena exhausted");
+    lap("buffers");
+    if (admitted && admitted->owns_lock()) admitted->unlock();
+    for (size_t ti = 0; ti < traces.size(); ti++) {
+        const ChipTrace &t = traces[ti];
+        const ChipDesc &d = m->chips[t.chip_id];
+        uint32_t *lde = ldes[ti];
+        {
+            EventTimer t_lde(stream, profile);
+            HIPCHK(launch_coset_lde(stream, tabs, const_cast<uint32_t *>(t.d_main), d_scratch, lde, d.main_w, t.log_n, 0));
+            if (profile) {
+                times.lde_ms += t_lde.stop();
+                times.lde_alg_bytes += 12.0 * d.main_w * (double)((size_t)1 << t.log_n);
+                times.lde_calls++;
+            }
+        }
+        mats.push_back({lde, (uint32_t)d.main_w, t.log_n + 1});
+        if (time_stages) lap(d.name);
+    }
+    lap("LDEs launched");
     {
         EventTimer t_mk(stream, profile);
         if (!commit_tree(mats, tree)) return false;

@@ -59,6 +59,12 @@ typedef struct dvt_pk dvt_pk;
  * DVT_ERR_INPUT): prover lanes that run phase 2 of different shards of one job at the same time, each with its own HIP
  * stream, device arena and buffer cache.  The further lanes are created on the first job that holds at least two shards;
  * "profile":1 forces one lane.  The proof bytes do not depend on it.
+ * "phase1_lanes" (1..lanes, default lanes; without the key the environment variable DVT_PHASE1_LANES sets the
+ * default, capped at "lanes"; a key outside 1..lanes is DVT_ERR_INPUT): how many of the lanes also run phase 1 (K0 and the
+ * main commitment) of different shards at the same time inside prepare / prove_core.  1 is one compute stream that
+ * uploads and commits shard after shard.  With more, a feeder uploads the shards in execution order on the copy stream and
+ * each committing lane takes the next uploaded shard; lane k is created when a k-th shard waits and no lane is free, so
+ * a job of one shard creates none.  Headers, shard order and proof bytes do not depend on it.  "profile":1 forces 1.
  * "devices": [d0, d1, ...] (1..8 HIP device indices, each a gfx950 device) instead of "device": the handle owns one device
  * MEMBER per entry, and shard i of an execution is proven on member i mod G (exactly: the k-th shard a job holds on member
  * k mod G).  An index may repeat: [0, 0] is two members on one GPU, each with its own streams, arenas and copy of the
@@ -83,8 +89,9 @@ typedef struct dvt_pk dvt_pk;
  *                        (sum of the members' lanes - 1) shard proofs.
  *   stage- and machine-level calls, dvt_dev_*, dvt_stream, dvt_last_*
  *                        run on member 0; dvt_sync also waits for the other members' streams
- * Two members on one physical device take turns in the first phase 1 of a shard when "keep_phase1" is on (they would
- * otherwise count the same free HBM twice when deciding what to keep).  A second dvt_rv32_prove_job of the same job runs
+ * Two members on one physical device (and the phase-1 lanes of one member) take turns in the admission of a shard's first
+ * phase 1: asking how much HBM is free and allocating what the commit keeps, so that no two count the same free bytes.
+ * The turn ends before the commit's kernels are launched, which therefore overlap.  A second dvt_rv32_prove_job of the same job runs
  * phase 1 of all its shards again one after the other on the calling thread, member by member: only prepare runs the
  * members' phase 1 at the same time.  A proving key and a job are freed on the handle that made them: dvt_pk_free /
  * dvt_job_free on a handle with fewer members cannot reach the other members' device buffers and leave them allocated.

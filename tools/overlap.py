@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
 """Busy, idle and cross-queue overlap of one timed call in a rocprofv3 --kernel-trace run:
-    python tools/overlap.py DIR [--per-call K] [--call I]
+    python tools/overlap.py DIR [--per-call K] [--call I] [--phase 1|2]
 tools/gaps.py sums kernel durations on the assumption of one stream; with several prover lanes kernels of different queues
 run at the same time.  A call is delimited by k0_cpu_rows launches (phase 1 runs K0 once per shard: K launches per call,
 default 32, the bench's 32-shard execution); --call picks the call (default -2: the last complete one).  Prints the union
-of busy intervals, the idle time, the time with kernels of at least two queues running, and the per-queue sums."""
+of busy intervals, the idle time, the time with kernels of at least two queues running, and the per-queue sums.  --phase
+cuts the call at its last phase-1 kernel, the one before the first LogUp kernel (perm_*) of the call: 1 is the part up to
+it (phase 1 of every shard), 2 the rest."""
 import argparse
 import csv
 import glob
@@ -29,6 +31,12 @@ def window(rows, per_call, call):
         raise SystemExit("no complete call of %d k0_cpu_rows launches in the trace" % per_call)
     i = call % (len(starts) - 1)
     return rows[starts[i]:starts[i + 1]]
+
+
+def phase(win, which):
+    """the part of a call's kernels before (1) or from (2) its first perm_* kernel"""
+    cut = next((i for i, r in enumerate(win) if "perm_" in r[3]), len(win))
+    return win[:cut] if which == 1 else win[cut:]
 
 
 def analyse(win):
@@ -60,8 +68,11 @@ def main():
     ap.add_argument("dir")
     ap.add_argument("--per-call", type=int, default=32)
     ap.add_argument("--call", type=int, default=-2)
+    ap.add_argument("--phase", type=int, choices=(0, 1, 2), default=0, help="1 / 2: that phase of the call only")
     a = ap.parse_args()
     win = window(load(a.dir), a.per_call, a.call)
+    if a.phase:
+        win = phase(win, a.phase)
     wall, busy, multi, per_q = analyse(win)
     print("kernels %d  wall %.2f ms  busy (union) %.2f ms  idle %.2f ms  >=2 queues busy %.2f ms" %
           (len(win), wall / 1e6, busy / 1e6, (wall - busy) / 1e6, multi / 1e6))
