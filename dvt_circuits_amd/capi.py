@@ -110,6 +110,8 @@ def load():
     lib.dvt_rv32_job_shards.restype = sz
     lib.dvt_rv32_job_shard_member.argtypes = [vp, sz]
     lib.dvt_rv32_job_shard_member.restype = C.c_int
+    lib.dvt_rv32_job_shard_device_rows.argtypes = [vp, sz]
+    lib.dvt_rv32_job_shard_device_rows.restype = u32
     lib.dvt_rv32_commit_shard.argtypes = [vp, vp, vp, sz, u32p]
     lib.dvt_rv32_challenges.argtypes = [C.c_char_p, sz, u32p, sz, u32p]
     lib.dvt_rv32_prove_shard.argtypes = [vp, vp, vp, sz, u32p, C.POINTER(u8p), C.POINTER(sz)]
@@ -491,6 +493,11 @@ class Prover:
     def job_shard_member(self, job, shard):
         """the device member that holds a shard (global position), -1 when the job does not hold it"""
         return int(self.lib.dvt_rv32_job_shard_member(job, shard))
+
+    def job_shard_device_rows(self, job, shard):
+        """bit c set: the rows of chip c of that shard (global position) were built on the GPU from events; 0 when the
+        job does not hold the shard"""
+        return int(self.lib.dvt_rv32_job_shard_device_rows(job, shard))
 
     def commit_shard(self, pk, job, shard):
         h = np.zeros(HEADER_WORDS, np.uint32)

@@ -232,7 +232,7 @@ int verify_words(const uint8_t *proof, size_t len, int len_code, char **reason,
 
 extern "C" {
 
-uint32_t dvt_abi_version(void) { return 4; }
+uint32_t dvt_abi_version(void) { return 5; }
 
 int dvt_prover_create(const char *cfg_json, dvt_prover **out) {
     if (!out) return fail(nullptr, DVT_ERR_INPUT, "out == NULL");

@@ -65,6 +65,7 @@ struct ShardJob {
     uint32_t log_n[rv32::N_CHIPS] = {};
     bool present[rv32::N_CHIPS] = {};
     uint32_t *d_aux[rv32::N_CHIPS] = {};  // main traces except cpu
+    uint32_t device_rows = 1u << RV32_CHIP_CPU;   // bit c: the rows of chip c were (and on every K0 are) built on the GPU from events
     std::vector<Fp> pubs;
     MainCache cache;  // phase-1 LDEs + tree of the main traces, consumed by phase 2
     // K0 output of this shard kept from phase 1 to phase 2 (with the cache, while HBM allows); otherwise the
@@ -433,10 +434,18 @@ struct Executor {
 
 // what a chip of a ready shard uploads: its calls / events when K0 of the chip runs on the GPU (true), else the rows the
 // executor thread built (false)
-bool events_of(const ReadyShard &r, int c, const void **src, size_t *bytes) {
-    if (!r.big.ev[c].empty()) { *src = r.big.ev[c].data(); *bytes = r.big.ev[c].size() * sizeof(rv32::BigOpEvent); return true; }
-    if (c == RV32_CHIP_SHIFT && !r.big.shifts.empty()) { *src = r.big.shifts.data(); *bytes = r.big.shifts.size() * sizeof(rv32::AluEvent); return true; }
-    if (c == RV32_CHIP_MEM_INIT && r.big.mem_rows && !r.big.mem_rows->empty()) { *src = r.big.mem_rows->data(); *bytes = r.big.mem_rows->size() * sizeof(rv32::MemInitRow); return true; }
+bool events_of(const ReadyShard &r, int c, const void **src, size_t *bytes, size_t *count = nullptr) {
+    auto is = [&](const void *data, size_t n, size_t each) {
+        *src = data; *bytes = n * each;
+        if (count) *count = n;
+        return true;
+    };
+    if (!r.big.ev[c].empty()) return is(r.big.ev[c].data(), r.big.ev[c].size(), sizeof(rv32::BigOpEvent));
+    if (c == RV32_CHIP_SHIFT && !r.big.shifts.empty()) return is(r.big.shifts.data(), r.big.shifts.size(), sizeof(rv32::AluEvent));
+    if (c == RV32_CHIP_MULDIV && !r.big.muldivs.empty()) return is(r.big.muldivs.data(), r.big.muldivs.size(), sizeof(rv32::AluEvent));
+    if (c == RV32_CHIP_SHA_EXTEND && !r.big.sha_ext.empty()) return is(r.big.sha_ext.data(), r.big.sha_ext.size(), sizeof(rv32::ShaExtEvent));
+    if (c == RV32_CHIP_SHA_COMPRESS && !r.big.sha_cmp.empty()) return is(r.big.sha_cmp.data(), r.big.sha_cmp.size(), sizeof(rv32::ShaCmpEvent));
+    if (c == RV32_CHIP_MEM_INIT && r.big.mem_rows && !r.big.mem_rows->empty()) return is(r.big.mem_rows->data(), r.big.mem_rows->size(), sizeof(rv32::MemInitRow));
     return false;
 }
 }  // namespace
@@ -493,12 +502,11 @@ static int upload_shard(const Lane &lane, ReadyShard &r, ShardJob &s, hipEvent_t
         if (c == RV32_CHIP_CPU || !s.present[c]) continue;
         const void *src = nullptr;
         size_t bytes = 0;
-        if (events_of(r, c, &src, &bytes)) {   // K0 of this chip on the GPU (after the byte counts are in): [error word, padding to 16 bytes, the events]
+        if (events_of(r, c, &src, &bytes, &n_events[c])) {   // K0 of this chip on the GPU (after the byte counts are in): [error word, padding to 16 bytes, the events]
             const size_t words = (size_t)m->chips[c].main_w << s.log_n[c];
             HIP_TRY(lane.err, hipMemsetAsync(s.d_aux[c], 0, words * 4, aux));
             HIP_TRY(lane.err, hipMemsetAsync(d_calls[c], 0, 16, aux));
             HIP_TRY(lane.err, hipMemcpyAsync(d_calls[c] + 4, staged(src, bytes), bytes, hipMemcpyHostToDevice, aux));
-            n_events[c] = c == RV32_CHIP_SHIFT ? r.big.shifts.size() : c == RV32_CHIP_MEM_INIT ? r.big.mem_rows->size() : r.big.ev[c].size();
             continue;
         }
         size_t words = r.aux.main[c].size();
@@ -509,10 +517,18 @@ static int upload_shard(const Lane &lane, ReadyShard &r, ShardJob &s, hipEvent_t
     for (int c = 0; c < m->n_chips; c++) {
         if (!d_calls[c]) continue;
         const size_t words = (size_t)m->chips[c].main_w << s.log_n[c];
-        if (c == RV32_CHIP_SHIFT) {   // (these two write Montgomery words themselves)
-            HIP_TRY(lane.err, rv32::launch_k0_shift_rows(aux, reinterpret_cast<const rv32::AluEvent *>(d_calls[c] + 4), n_events[c], s.d_aux[c], s.log_n[c], s.d_aux[RV32_CHIP_BYTE]));
+        s.device_rows |= 1u << c;
+        uint32_t *byte = s.d_aux[RV32_CHIP_BYTE];
+        if (c == RV32_CHIP_SHIFT) {   // (these five write Montgomery words themselves)
+            HIP_TRY(lane.err, rv32::launch_k0_shift_rows(aux, reinterpret_cast<const rv32::AluEvent *>(d_calls[c] + 4), n_events[c], s.d_aux[c], s.log_n[c], byte));
         } else if (c == RV32_CHIP_MEM_INIT) {
-            HIP_TRY(lane.err, rv32::launch_k0_mem_init_rows(aux, reinterpret_cast<const rv32::MemInitRow *>(d_calls[c] + 4), n_events[c], s.d_aux[c], s.log_n[c], s.d_aux[RV32_CHIP_BYTE]));
+            HIP_TRY(lane.err, rv32::launch_k0_mem_init_rows(aux, reinterpret_cast<const rv32::MemInitRow *>(d_calls[c] + 4), n_events[c], s.d_aux[c], s.log_n[c], byte));
+        } else if (c == RV32_CHIP_MULDIV) {
+            HIP_TRY(lane.err, rv32::launch_k0_muldiv_rows(aux, reinterpret_cast<const rv32::AluEvent *>(d_calls[c] + 4), n_events[c], s.d_aux[c], s.log_n[c], byte));
+        } else if (c == RV32_CHIP_SHA_EXTEND) {
+            HIP_TRY(lane.err, rv32::launch_k0_sha_extend_rows(aux, reinterpret_cast<const rv32::ShaExtEvent *>(d_calls[c] + 4), n_events[c], s.index, s.d_aux[c], s.log_n[c], byte));
+        } else if (c == RV32_CHIP_SHA_COMPRESS) {
+            HIP_TRY(lane.err, rv32::launch_k0_sha_compress_rows(aux, reinterpret_cast<const rv32::ShaCmpEvent *>(d_calls[c] + 4), n_events[c], s.index, s.d_aux[c], s.log_n[c], byte));
         } else {
             HIP_TRY(lane.err, rv32::launch_k0_bigop_rows(aux, c, reinterpret_cast<const rv32::BigOpEvent *>(d_calls[c] + 4), (uint32_t)n_events[c], s.index,
                                                        s.d_aux[c], s.log_n[c], s.d_aux[RV32_CHIP_BYTE], d_calls[c]));
@@ -1146,6 +1162,11 @@ size_t dvt_rv32_job_shards(const dvt_job *job) { return job ? job->n_total : 0; 
 int dvt_rv32_job_shard_member(const dvt_job *job, size_t shard) {
     size_t m = 0;
     return job && const_cast<dvt_job *>(job)->part_at(shard, &m) ? (int)m : -1;
+}
+uint32_t dvt_rv32_job_shard_device_rows(const dvt_job *job, size_t shard) {
+    size_t m = 0;
+    dvt_job *part = job ? const_cast<dvt_job *>(job)->part_at(shard, &m) : nullptr;
+    return part ? part->at(shard)->device_rows : 0;
 }
 double dvt_rv32_job_exec_wait_seconds(const dvt_job *job) { return job ? job->t_exec_wait : 0.0; }
 

@@ -378,6 +378,226 @@ DVT_HD void fill_mem_init_row(const MemInitRow *rows, size_t r, Sink &s) {
     }
 }
 
+// the SHA-256 round constants (the guest machine's SHA_COMPRESS and the rows of the sha_compress chip, host and device)
+#if defined(__HIP_DEVICE_COMPILE__)
+static __constant__ const uint32_t SHA256_K[64] = {
+#else
+static const uint32_t SHA256_K[64] = {
+#endif
+    0x428a2f98, 0x71374491, 0xb5c0fbcf, 0xe9b5dba5, 0x3956c25b, 0x59f111f1, 0x923f82a4, 0xab1c5ed5, 0xd807aa98, 0x12835b01, 0x243185be,
+    0x550c7dc3, 0x72be5d74, 0x80deb1fe, 0x9bdc06a7, 0xc19bf174, 0xe49b69c1, 0xefbe4786, 0x0fc19dc6, 0x240ca1cc, 0x2de92c6f, 0x4a7484aa,
+    0x5cb0a9dc, 0x76f988da, 0x983e5152, 0xa831c66d, 0xb00327c8, 0xbf597fc7, 0xc6e00bf3, 0xd5a79147, 0x06ca6351, 0x14292967, 0x27b70a85,
+    0x2e1b2138, 0x4d2c6dfc, 0x53380d13, 0x650a7354, 0x766a0abb, 0x81c2c92e, 0x92722c85, 0xa2bfe8a1, 0xa81a664b, 0xc24b8b70, 0xc76c51a3,
+    0xd192e819, 0xd6990624, 0xf40e3585, 0x106aa070, 0x19a4c116, 0x1e376c08, 0x2748774c, 0x34b0bcb5, 0x391c0cb3, 0x4ed8aa4a, 0x5b9cca4f,
+    0x682e6ff3, 0x748f82ee, 0x78a5636f, 0x84c87814, 0x8cc70208, 0x90befffa, 0xa4506ceb, 0xbef9a3f7, 0xc67178f2};
+
+// ---- rows of the muldiv and SHA precompile chips (K0; the same Sink, plus fence(accumulator): see fill_cpu_row) -------------
+// one MULH / MULHSU / DIV / DIVU / REM / REMU instruction; witness as tools/airgen/rv32.py:build_muldiv lays it out.
+// Every value put is a byte, a bit, a carry or a 16-bit limb (dl_0 / dl_1 index the u16 table), or an inverse in canonical
+// form: all below p, so no reduction is needed before a sink converts it.
+template <class Sink>
+DVT_HD void fill_muldiv_row(const AluEvent &e, Sink &s) {
+    auto B = [](uint32_t w, int i) -> uint32_t { return (w >> (8 * i)) & 0xffu; };
+    const bool is_mul = e.op == ALU_MULH || e.op == ALU_MULHSU, is_sdr = e.op == ALU_DIV || e.op == ALU_REM;
+    const bool is_dr = !is_mul;
+    s.put(RV32_MULDIV_is_real, 1);
+    s.put(e.op == ALU_MULH ? RV32_MULDIV_is_mulh : e.op == ALU_MULHSU ? RV32_MULDIV_is_mulhsu : e.op == ALU_DIV ? RV32_MULDIV_is_div :
+          e.op == ALU_DIVU ? RV32_MULDIV_is_divu : e.op == ALU_REM ? RV32_MULDIV_is_rem : RV32_MULDIV_is_remu, 1);
+    // quotient / remainder (divisions), X = b (multiplications)
+    uint32_t q = e.b, r = 0;
+    const bool c0 = is_dr && e.c == 0, ovf = is_sdr && e.b == 0x80000000u && e.c == 0xffffffffu;
+    if (is_dr) {
+        if (c0) { q = 0xffffffffu; r = e.b; }
+        else if (ovf) { q = e.b; r = 0; }
+        else if (is_sdr) { q = (uint32_t)((int32_t)e.b / (int32_t)e.c); r = (uint32_t)((int32_t)e.b % (int32_t)e.c); }
+        else { q = e.b / e.c; r = e.b % e.c; }
+    }
+    const uint32_t mx = q >> 31, my = e.c >> 31, mr = r >> 31, mb = e.b >> 31;
+    const uint32_t sx = mx & (uint32_t)(is_mul || is_sdr), sy = my & (uint32_t)(e.op == ALU_MULH || is_sdr);
+    const uint32_t sr = mr & (uint32_t)is_sdr, sb = mb & (uint32_t)is_sdr;
+    for (int i = 0; i < 4; i++) {
+        s.put(RV32_MULDIV_a_0 + i, B(e.a, i)); s.put(RV32_MULDIV_b_0 + i, B(e.b, i)); s.put(RV32_MULDIV_c_0 + i, B(e.c, i));
+        s.put(RV32_MULDIV_q_0 + i, B(q, i)); s.put(RV32_MULDIV_r_0 + i, B(r, i));
+    }
+    s.put(RV32_MULDIV_mx, mx); s.put(RV32_MULDIV_my, my); s.put(RV32_MULDIV_mr, mr); s.put(RV32_MULDIV_mb, mb);
+    s.put(RV32_MULDIV_sx, sx); s.put(RV32_MULDIV_sy, sy); s.put(RV32_MULDIV_sr, sr); s.put(RV32_MULDIV_sb, sb);
+    s.byte(B_MSB - 1, B(q, 3) << 8); s.byte(B_MSB - 1, B(e.c, 3) << 8);
+    s.byte(B_MSB - 1, B(r, 3) << 8); s.byte(B_MSB - 1, B(e.b, 3) << 8);
+    // unsigned product bytes and carries (the carry chain of fill_cpu_row's MUL family: fenced for the same reason)
+    uint32_t prod[8], carry = 0;
+    for (int k = 0; k < 8; k++) {
+        uint32_t t = carry;
+        for (int i = 0; i < 4; i++) if (k - i >= 0 && k - i < 4) t += B(q, i) * B(e.c, k - i);
+        s.fence(t);
+        prod[k] = t & 0xff; carry = t >> 8;
+        s.put(RV32_MULDIV_prod_0 + k, prod[k]); s.put(RV32_MULDIV_mcy_0 + k, carry);
+        s.byte(B_U16 - 1, carry);
+    }
+    for (int k = 0; k < 4; k++) s.byte(B_RANGE - 1, (prod[2 * k] << 8) | prod[2 * k + 1]);
+    // high word of the signed product with borrows 0..2
+    uint32_t h[4], bin = 0;
+    for (int i = 0; i < 4; i++) {
+        int32_t t = (int32_t)prod[4 + i] - (int32_t)(sx * B(e.c, i)) - (int32_t)(sy * B(q, i)) - (int32_t)bin;
+        uint32_t bo = 0;
+        while (t < 0) { t += 256; bo++; }
+        h[i] = (uint32_t)t; bin = bo;
+        s.fence(bin);
+        s.put(RV32_MULDIV_h_0 + i, h[i]); s.put(RV32_MULDIV_bw_0 + i, bo);
+    }
+    s.byte(B_RANGE - 1, (h[0] << 8) | h[1]); s.byte(B_RANGE - 1, (h[2] << 8) | h[3]);
+    s.byte(B_RANGE - 1, (B(q, 0) << 8) | B(q, 1)); s.byte(B_RANGE - 1, (B(q, 2) << 8) | B(q, 3));
+    s.byte(B_RANGE - 1, (B(r, 0) << 8) | B(r, 1)); s.byte(B_RANGE - 1, (B(r, 2) << 8) | B(r, 3));
+    uint32_t dl0 = 0, dl1 = 0;
+    if (is_dr) {
+        s.put(RV32_MULDIV_is_c0, c0); s.put(RV32_MULDIV_is_ovf, ovf);
+        const uint32_t csum = B(e.c, 0) + B(e.c, 1) + B(e.c, 2) + B(e.c, 3);
+        if (csum) s.put(RV32_MULDIV_cinv, inv(Fp::from_canonical(csum)).canonical());
+        if (!ovf) {  // 64-bit sum P + R' = B' in 16-bit limbs
+            const uint32_t Pl[4] = {prod[0] | (prod[1] << 8), prod[2] | (prod[3] << 8), h[0] | (h[1] << 8), h[2] | (h[3] << 8)};
+            const uint32_t Rl[4] = {r & 0xffff, r >> 16, 65535 * sr, 65535 * sr};
+            uint32_t cy = 0;
+            for (int k = 0; k < 4; k++) {
+                cy = (Pl[k] + Rl[k] + cy) >> 16;
+                s.fence(cy);
+                s.put(RV32_MULDIV_dcy_0 + k, cy);
+            }
+        }
+        if (!c0) {  // |c| - |r| - 1 in two limbs, low-limb carry e0 = ea + 2 eb - 1
+            const int64_t sc_ = 1 - 2 * (int64_t)sy, sr_ = 1 - 2 * (int64_t)sr;
+            const int64_t t0 = sc_ * (e.c & 0xffff) - sr_ * (r & 0xffff) - 1;
+            int64_t e0 = 0;
+            while (t0 + 65536 * e0 < 0) e0++;
+            while (t0 + 65536 * e0 > 65535) e0--;
+            dl0 = (uint32_t)(t0 + 65536 * e0);
+            dl1 = (uint32_t)(sc_ * (e.c >> 16) - sr_ * (r >> 16) + 65536 * ((int64_t)sy - (int64_t)sr) - e0);
+            s.put(RV32_MULDIV_ea, (uint32_t)((e0 + 1) & 1)); s.put(RV32_MULDIV_eb, (uint32_t)((e0 + 1) >> 1));
+        } else {
+            s.put(RV32_MULDIV_ea, 1);  // e0 = 0 (unconstrained here; any boolean pair is fine)
+        }
+    } else {
+        s.put(RV32_MULDIV_ea, 1);
+    }
+    s.put(RV32_MULDIV_dl_0, dl0); s.put(RV32_MULDIV_dl_1, dl1);
+    s.byte(B_U16 - 1, dl0); s.byte(B_U16 - 1, dl1);
+}
+// row j (0..63) of a SHA_EXTEND call of shard `shard`: rows 0..15 load w[j], rows 16..63 write it
+template <class Sink>
+DVT_HD void fill_sha_extend_row(const ShaExtEvent &ev, uint32_t j, uint32_t shard, Sink &s) {
+    auto put_word = [&](int col0, uint32_t v) { for (int i = 0; i < 4; i++) s.put(col0 + i, (v >> (8 * i)) & 0xff); };
+    s.put(RV32_SHA_EXTEND_is_real, 1);
+    s.put(RV32_SHA_EXTEND_is_first, j == 0); s.put(RV32_SHA_EXTEND_is_last, j == 63);
+    s.put(RV32_SHA_EXTEND_is_load, j < 16); s.put(RV32_SHA_EXTEND_is_e, j == 15);
+    s.put(RV32_SHA_EXTEND_j, j);
+    if (j != 63) s.put(RV32_SHA_EXTEND_j_inv, inv(Fp::from_canonical(j) - Fp::from_canonical(63)).canonical());
+    s.put(RV32_SHA_EXTEND_clk, ev.clk);
+    put_word(RV32_SHA_EXTEND_p_0, ev.ptr);
+    // window: W[k] = w[j - 16 + k] (zero before the array's start)
+    for (uint32_t k = 0; k < 16; k++) put_word(RV32_SHA_EXTEND_w0_0 + 4 * k, j + k >= 16 ? ev.w[j + k - 16] : 0u);
+    const uint32_t x = j + 1 >= 16 ? ev.w[j + 1 - 16] : 0u, y = j + 14 >= 16 ? ev.w[j + 14 - 16] : 0u;
+    for (int k = 0; k < 32; k++) { s.put(RV32_SHA_EXTEND_xb_0 + k, (x >> k) & 1); s.put(RV32_SHA_EXTEND_yb_0 + k, (y >> k) & 1); }
+    const uint32_t s0 = ((x >> 7) | (x << 25)) ^ ((x >> 18) | (x << 14)) ^ (x >> 3);
+    const uint32_t s1 = ((y >> 17) | (y << 15)) ^ ((y >> 19) | (y << 13)) ^ (y >> 10);
+    s.put(RV32_SHA_EXTEND_s0_0, s0 & 0xffff); s.put(RV32_SHA_EXTEND_s0_1, s0 >> 16);
+    s.put(RV32_SHA_EXTEND_s1_0, s1 & 0xffff); s.put(RV32_SHA_EXTEND_s1_1, s1 >> 16);
+    const uint32_t nw = ev.w[j];
+    put_word(RV32_SHA_EXTEND_nw_0, nw);
+    put_word(RV32_SHA_EXTEND_old_0, ev.old[j]);
+    if (j >= 16) {
+        const uint32_t w0 = ev.w[j - 16], w9 = ev.w[j - 7];
+        const uint32_t lo = (w0 & 0xffff) + (s0 & 0xffff) + (w9 & 0xffff) + (s1 & 0xffff);
+        const uint32_t c_lo = lo >> 16;
+        const uint32_t hi = (w0 >> 16) + (s0 >> 16) + (w9 >> 16) + (s1 >> 16) + c_lo;
+        const uint32_t c_hi = hi >> 16;
+        s.put(RV32_SHA_EXTEND_cy_0, c_lo & 1); s.put(RV32_SHA_EXTEND_cy_1, c_lo >> 1);
+        s.put(RV32_SHA_EXTEND_cy_2, c_hi & 1); s.put(RV32_SHA_EXTEND_cy_3, c_hi >> 1);
+        s.byte(B_RANGE - 1, ((nw & 0xff) << 8) | ((nw >> 8) & 0xff));
+        s.byte(B_RANGE - 1, (((nw >> 16) & 0xff) << 8) | (nw >> 24));
+    }
+    // the access: previous (shard, clk) of the word, gap to (shard, clk + 2)
+    const uint32_t psh = ev.prev_sh[j], pts = ev.prev_ts[j];
+    const uint32_t d = psh == shard ? ev.clk + 2 - pts - 1 : shard - psh - 1;
+    s.put(RV32_SHA_EXTEND_m_sh, psh); s.put(RV32_SHA_EXTEND_m_ts, pts); s.put(RV32_SHA_EXTEND_m_same, psh == shard);
+    s.put(RV32_SHA_EXTEND_m_lo, d & 0xffff); s.put(RV32_SHA_EXTEND_m_hi, d >> 16);
+    s.byte(B_U16 - 1, d & 0xffff);
+    s.byte(B_RANGE - 1, (d >> 16) << 8);
+    if (j == 0) s.byte(B_ADDR - 1, ((ev.ptr & 0xff) << 8) | (ev.ptr >> 24));
+}
+// The 80 rows of a SHA_COMPRESS call: rows 0..7 read the state words h[7]..h[0] into the working variables, rows 8..71 are the
+// 64 rounds, rows 72..79 add the variables back into h[7]..h[0].  v = the working variables a..h at the START of a row.
+DVT_HD uint32_t sha_rotr(uint32_t x, int n) { return (x >> n) | (x << (32 - n)); }
+// v at the start of row j -> v at the start of row j + 1
+DVT_HD void sha_compress_next(const ShaCmpEvent &ev, uint32_t j, uint32_t v[8]) {
+    const uint32_t g = j >> 3, o = j & 7;
+    uint32_t a = 0, e = v[3];
+    if (g == 0) a = ev.hs[7 - o];
+    else if (g <= 8) {
+        const uint32_t i = 8 * (g - 1) + o;
+        const uint32_t t1 = v[7] + (sha_rotr(v[4], 6) ^ sha_rotr(v[4], 11) ^ sha_rotr(v[4], 25)) + ((v[4] & v[5]) ^ (~v[4] & v[6])) + SHA256_K[i] + ev.w[i];
+        a = t1 + (sha_rotr(v[0], 2) ^ sha_rotr(v[0], 13) ^ sha_rotr(v[0], 22)) + ((v[0] & v[1]) ^ (v[0] & v[2]) ^ (v[1] & v[2]));
+        e = v[3] + t1;
+    }
+    for (int k = 7; k > 0; k--) v[k] = v[k - 1];
+    v[0] = a; v[4] = e;
+}
+// v at the start of row j of the call: the recurrence from row 0 (at most 79 steps of integer work)
+DVT_HD void sha_compress_vars_at(const ShaCmpEvent &ev, uint32_t j, uint32_t v[8]) {
+    for (int k = 0; k < 8; k++) v[k] = 0;
+    for (uint32_t t = 0; t < j; t++) sha_compress_next(ev, t, v);
+}
+template <class Sink>
+DVT_HD void fill_sha_compress_row(const ShaCmpEvent &ev, uint32_t j, const uint32_t v[8], uint32_t shard, Sink &s) {
+    const uint32_t g = j >> 3, o = j & 7;
+    auto put_word = [&](int col0, uint32_t x) { for (int i = 0; i < 4; i++) s.put(col0 + i, (x >> (8 * i)) & 0xff); };
+    auto put_bits = [&](int col0, uint32_t x) { for (int k = 0; k < 32; k++) s.put(col0 + k, (x >> k) & 1); };
+    s.put(RV32_SHA_COMPRESS_is_real, 1); s.put(RV32_SHA_COMPRESS_is_first, j == 0); s.put(RV32_SHA_COMPRESS_is_last, j == 79);
+    s.put(RV32_SHA_COMPRESS_oc_0 + o, 1); s.put(RV32_SHA_COMPRESS_gr_0 + g, 1);
+    s.put(RV32_SHA_COMPRESS_clk, ev.clk);
+    put_word(RV32_SHA_COMPRESS_wp_0, ev.w_ptr); put_word(RV32_SHA_COMPRESS_hp_0, ev.h_ptr);
+    put_bits(RV32_SHA_COMPRESS_ab_0, v[0]); put_bits(RV32_SHA_COMPRESS_bb_0, v[1]); put_bits(RV32_SHA_COMPRESS_cb_0, v[2]);
+    put_bits(RV32_SHA_COMPRESS_eb_0, v[4]); put_bits(RV32_SHA_COMPRESS_fb_0, v[5]); put_bits(RV32_SHA_COMPRESS_gb_0, v[6]);
+    s.put(RV32_SHA_COMPRESS_d_0, v[3] & 0xffff); s.put(RV32_SHA_COMPRESS_d_1, v[3] >> 16);
+    s.put(RV32_SHA_COMPRESS_h_0, v[7] & 0xffff); s.put(RV32_SHA_COMPRESS_h_1, v[7] >> 16);
+    const uint32_t S1 = sha_rotr(v[4], 6) ^ sha_rotr(v[4], 11) ^ sha_rotr(v[4], 25), S0 = sha_rotr(v[0], 2) ^ sha_rotr(v[0], 13) ^ sha_rotr(v[0], 22);
+    const uint32_t mj = (v[0] & v[1]) ^ (v[0] & v[2]) ^ (v[1] & v[2]), chv = (v[4] & v[5]) ^ (~v[4] & v[6]);
+    s.put(RV32_SHA_COMPRESS_s1_0, S1 & 0xffff); s.put(RV32_SHA_COMPRESS_s1_1, S1 >> 16);
+    s.put(RV32_SHA_COMPRESS_s0_0, S0 & 0xffff); s.put(RV32_SHA_COMPRESS_s0_1, S0 >> 16);
+    s.put(RV32_SHA_COMPRESS_mj_0, mj & 0xffff); s.put(RV32_SHA_COMPRESS_mj_1, mj >> 16);
+    // the access of this row
+    uint32_t addr, before, after, psh, pts, ts = ev.clk + 2;
+    if (g == 0) { addr = ev.h_ptr + 4 * (7 - o); before = after = ev.hs[7 - o]; psh = ev.h_sh[7 - o]; pts = ev.h_ts[7 - o]; }
+    else if (g <= 8) { const uint32_t i = 8 * (g - 1) + o; addr = ev.w_ptr + 4 * i; before = after = ev.w[i]; psh = ev.w_sh[i]; pts = ev.w_ts[i]; }
+    else { addr = ev.h_ptr + 4 * (7 - o); before = ev.hs[7 - o]; after = before + v[7]; psh = (uint16_t)shard; pts = ev.clk + 2; ts = ev.clk + 3; }
+    s.put(RV32_SHA_COMPRESS_maddr, addr);   // (below ADDR_LIMIT + 256 < p)
+    put_word(RV32_SHA_COMPRESS_mv_0, after); put_word(RV32_SHA_COMPRESS_mo_0, before);
+    const uint32_t dgap = psh == shard ? ts - pts - 1 : shard - psh - 1;
+    s.put(RV32_SHA_COMPRESS_m_sh, psh); s.put(RV32_SHA_COMPRESS_m_ts, pts); s.put(RV32_SHA_COMPRESS_m_same, psh == shard);
+    s.put(RV32_SHA_COMPRESS_m_lo, dgap & 0xffff); s.put(RV32_SHA_COMPRESS_m_hi, dgap >> 16);
+    s.byte(B_U16 - 1, dgap & 0xffff);
+    s.byte(B_RANGE - 1, (dgap >> 16) << 8);
+    if (j == 0) {
+        s.byte(B_ADDR - 1, ((ev.w_ptr & 0xff) << 8) | (ev.w_ptr >> 24));
+        s.byte(B_ADDR - 1, ((ev.h_ptr & 0xff) << 8) | (ev.h_ptr >> 24));
+    }
+    if (g >= 1 && g <= 8) {
+        const uint32_t i = 8 * (g - 1) + o, K = SHA256_K[i], wv = ev.w[i];
+        // e' = d + T1, a' = T1 + T2 in 16-bit halves: the carries are witnesses
+        const uint32_t lo_t = (v[7] & 0xffff) + (S1 & 0xffff) + (chv & 0xffff) + (K & 0xffff) + (wv & 0xffff);
+        const uint32_t hi_t = (v[7] >> 16) + (S1 >> 16) + (chv >> 16) + (K >> 16) + (wv >> 16);
+        const uint32_t e_lo = lo_t + (v[3] & 0xffff), ce_lo = e_lo >> 16, e_hi = hi_t + (v[3] >> 16) + ce_lo, ce_hi = e_hi >> 16;
+        const uint32_t a_lo = lo_t + (S0 & 0xffff) + (mj & 0xffff), ca_lo = a_lo >> 16;
+        const uint32_t a_hi = hi_t + (S0 >> 16) + (mj >> 16) + ca_lo, ca_hi = a_hi >> 16;
+        for (int k = 0; k < 3; k++) {
+            s.put(RV32_SHA_COMPRESS_ce_0 + k, (ce_lo >> k) & 1); s.put(RV32_SHA_COMPRESS_ce_0 + 3 + k, (ce_hi >> k) & 1);
+            s.put(RV32_SHA_COMPRESS_ca_0 + k, (ca_lo >> k) & 1); s.put(RV32_SHA_COMPRESS_ca_0 + 3 + k, (ca_hi >> k) & 1);
+        }
+    } else if (g == 9) {
+        const uint32_t lo = (before & 0xffff) + (v[7] & 0xffff), hi2 = (before >> 16) + (v[7] >> 16) + (lo >> 16);
+        s.put(RV32_SHA_COMPRESS_cf_0, lo >> 16); s.put(RV32_SHA_COMPRESS_cf_1, hi2 >> 16);
+        s.byte(B_RANGE - 1, ((after & 0xff) << 8) | ((after >> 8) & 0xff));
+        s.byte(B_RANGE - 1, (((after >> 16) & 0xff) << 8) | (after >> 24));
+    }
+}
+
 // ---- trace generation (K0) ---------------------------------------------------
 // Sink interface used by fill_cpu_row:  put(col, canonical value);  byte(op_index, table_row);  prog(idx)
 // next_pc: pc of the next retired instruction (the shard's next_pc public value after its last row).
@@ -591,8 +811,8 @@ struct HostPrep {
     std::vector<uint32_t> prep[N_CHIPS];
 };
 void build_prep(const Program &prog, HostPrep *out);
-// Everything of a shard except the cpu trace and the lookups the cpu rows make: shift / muldiv rows, in the last
-// shard (mem_rows != nullptr) the mem_init rows, the byte-table multiplicities those cause, zeroed program / mem_image
+// Everything of a shard except the cpu trace and the lookups the cpu rows make: shift / muldiv / SHA precompile rows, in the
+// last shard (mem_rows != nullptr) the mem_init rows, the byte-table multiplicities those cause, zeroed program / mem_image
 // columns, public values.  The device path (K0) adds the cpu chip and its lookup counts on top.
 struct ShardMeta {
     uint32_t index, start_pc, next_pc;
@@ -606,9 +826,16 @@ struct BigOpBatches {
     // on the GPU too (launch_k0_shift_rows / launch_k0_mem_init_rows)
     std::vector<AluEvent> shifts;
     const std::vector<MemInitRow> *mem_rows = nullptr;
+    // and the muldiv instructions and the SHA precompile calls (launch_k0_muldiv_rows / launch_k0_sha_extend_rows /
+    // launch_k0_sha_compress_rows)
+    std::vector<AluEvent> muldivs;
+    std::vector<ShaExtEvent> sha_ext;
+    std::vector<ShaCmpEvent> sha_cmp;
 };
-// device_rows != nullptr (the product path): the field / curve precompile chips get their shape only (present, log_n) and
-// their calls are handed back in *device_rows; nullptr (CPU-only debug / test entry points): their rows are built here
+// device_rows != nullptr (the product path): every chip whose K0 runs on the GPU (shift, muldiv, sha_extend, sha_compress,
+// mem_init, the field / curve precompile chips) gets its shape only (present, log_n), its events are handed back in
+// *device_rows and the byte-table lookups of its rows are NOT counted here; nullptr (CPU-only debug / test entry points):
+// the rows are built here, by the same fill_*_row templates
 bool build_aux_host(const ShardMeta &meta, const std::vector<AluEvent> &alu, const std::vector<ShaExtEvent> &sha_ext,
                     const std::vector<ShaCmpEvent> &sha_cmp, const std::vector<BigOpEvent> &big, const std::vector<MemInitRow> *mem_rows, int exit_code,
                     const HostPrep &prep, HostTraces *out, std::string *err, BigOpBatches *device_rows = nullptr);
@@ -633,6 +860,11 @@ const char *bigop_row_error_text(uint32_t code);
 // byte-table lookups added to d_byte_mult (plain counts) through the same workgroup LDS cache as K0 of the cpu chip
 hipError_t launch_k0_shift_rows(hipStream_t st, const AluEvent *d_ev, size_t n_ev, uint32_t *d_main, uint32_t log_n, uint32_t *d_byte_mult);
 hipError_t launch_k0_mem_init_rows(hipStream_t st, const MemInitRow *d_rows, size_t n_rows, uint32_t *d_main, uint32_t log_n, uint32_t *d_byte_mult);
+// K0 of the muldiv chip (row i from event i) and of the SHA precompile chips (64 / 80 rows per call of shard `shard`, n_calls
+// calls): same conventions
+hipError_t launch_k0_muldiv_rows(hipStream_t st, const AluEvent *d_ev, size_t n_ev, uint32_t *d_main, uint32_t log_n, uint32_t *d_byte_mult);
+hipError_t launch_k0_sha_extend_rows(hipStream_t st, const ShaExtEvent *d_ev, size_t n_calls, uint32_t shard, uint32_t *d_main, uint32_t log_n, uint32_t *d_byte_mult);
+hipError_t launch_k0_sha_compress_rows(hipStream_t st, const ShaCmpEvent *d_ev, size_t n_calls, uint32_t shard, uint32_t *d_main, uint32_t log_n, uint32_t *d_byte_mult);
 #endif
 
 }  // namespace rv32

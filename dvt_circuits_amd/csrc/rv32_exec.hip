@@ -9,13 +9,6 @@
 
 namespace dvt {
 namespace rv32 {
-static const uint32_t SHA256_K[64] = {
-    0x428a2f98, 0x71374491, 0xb5c0fbcf, 0xe9b5dba5, 0x3956c25b, 0x59f111f1, 0x923f82a4, 0xab1c5ed5, 0xd807aa98, 0x12835b01, 0x243185be,
-    0x550c7dc3, 0x72be5d74, 0x80deb1fe, 0x9bdc06a7, 0xc19bf174, 0xe49b69c1, 0xefbe4786, 0x0fc19dc6, 0x240ca1cc, 0x2de92c6f, 0x4a7484aa,
-    0x5cb0a9dc, 0x76f988da, 0x983e5152, 0xa831c66d, 0xb00327c8, 0xbf597fc7, 0xc6e00bf3, 0xd5a79147, 0x06ca6351, 0x14292967, 0x27b70a85,
-    0x2e1b2138, 0x4d2c6dfc, 0x53380d13, 0x650a7354, 0x766a0abb, 0x81c2c92e, 0x92722c85, 0xa2bfe8a1, 0xa81a664b, 0xc24b8b70, 0xc76c51a3,
-    0xd192e819, 0xd6990624, 0xf40e3585, 0x106aa070, 0x19a4c116, 0x1e376c08, 0x2748774c, 0x34b0bcb5, 0x391c0cb3, 0x4ed8aa4a, 0x5b9cca4f,
-    0x682e6ff3, 0x748f82ee, 0x78a5636f, 0x84c87814, 0x8cc70208, 0x90befffa, 0xa4506ceb, 0xbef9a3f7, 0xc67178f2};
 
 
 // ------------------------------------------------------------------ decode
@@ -752,7 +745,6 @@ bool build_aux_host(const ShardMeta &S, const std::vector<AluEvent> &alu, const 
         t_aux = now;
     };
     std::vector<uint32_t> byte_mult((size_t)N_BYTE_OPS * 65536, 0);
-    HostSink sink{nullptr, 0, 0, byte_mult.data(), nullptr};
     T.present[RV32_CHIP_MEM_INIT] = last;
     T.log_n[RV32_CHIP_MEM_INIT] = 0;
     if (last) {
@@ -794,96 +786,23 @@ bool build_aux_host(const ShardMeta &S, const std::vector<AluEvent> &alu, const 
         }
     }
     lap_aux("shift rows");
-    // muldiv chip: one row per MULH/MULHSU/DIV/DIVU/REM/REMU of this shard (absent when there is none);
-    // witness as tools/airgen/rv32.py:build_muldiv lays it out
+    // muldiv chip: one row per MULH/MULHSU/DIV/DIVU/REM/REMU of this shard (absent when there is none)
     T.present[RV32_CHIP_MULDIV] = !muldivs.empty();
     T.log_n[RV32_CHIP_MULDIV] = 0;
     if (!muldivs.empty()) {
         const uint32_t ls = ceil_log2(muldivs.size());
         const size_t ns = (size_t)1 << ls;
         T.log_n[RV32_CHIP_MULDIV] = ls;
-        auto &H = T.main[RV32_CHIP_MULDIV];
-        H.assign((size_t)RV32_MULDIV_MAIN_W * ns, 0);
-        for (size_t row = 0; row < muldivs.size(); row++) {
-            const AluEvent &e = muldivs[row];
-            auto put = [&](int col, uint32_t v) { H[(size_t)col * ns + row] = v % P; };
-            auto B = [](uint32_t w, int i) -> uint32_t { return (w >> (8 * i)) & 0xffu; };
-            const bool is_mul = e.op == ALU_MULH || e.op == ALU_MULHSU, is_sdr = e.op == ALU_DIV || e.op == ALU_REM;
-            const bool is_dr = !is_mul;
-            static const int flag_col[10] = {0, 0, 0, 0, RV32_MULDIV_is_mulh, RV32_MULDIV_is_mulhsu, RV32_MULDIV_is_div, RV32_MULDIV_is_divu,
-                                             RV32_MULDIV_is_rem, RV32_MULDIV_is_remu};
-            put(RV32_MULDIV_is_real, 1);
-            put(flag_col[e.op], 1);
-            // quotient / remainder (divisions), X = b (multiplications)
-            uint32_t q = e.b, r = 0;
-            const bool c0 = is_dr && e.c == 0, ovf = is_sdr && e.b == 0x80000000u && e.c == 0xffffffffu;
-            if (is_dr) {
-                if (c0) { q = 0xffffffffu; r = e.b; }
-                else if (ovf) { q = e.b; r = 0; }
-                else if (is_sdr) { q = (uint32_t)((int32_t)e.b / (int32_t)e.c); r = (uint32_t)((int32_t)e.b % (int32_t)e.c); }
-                else { q = e.b / e.c; r = e.b % e.c; }
+        if (device_rows) {
+            device_rows->muldivs = std::move(muldivs);   // K0 of this chip runs on the GPU (launch_k0_muldiv_rows)
+        } else {
+            auto &H = T.main[RV32_CHIP_MULDIV];
+            H.assign((size_t)RV32_MULDIV_MAIN_W * ns, 0);
+            HostSink hs{H.data(), ns, 0, byte_mult.data(), nullptr};
+            for (size_t r = 0; r < muldivs.size(); r++) {
+                hs.row = r;
+                fill_muldiv_row(muldivs[r], hs);
             }
-            const uint32_t mx = q >> 31, my = e.c >> 31, mr = r >> 31, mb = e.b >> 31;
-            const uint32_t sx = mx & (uint32_t)(is_mul || is_sdr), sy = my & (uint32_t)(e.op == ALU_MULH || is_sdr);
-            const uint32_t sr = mr & (uint32_t)is_sdr, sb = mb & (uint32_t)is_sdr;
-            for (int i = 0; i < 4; i++) {
-                put(RV32_MULDIV_a_0 + i, B(e.a, i)); put(RV32_MULDIV_b_0 + i, B(e.b, i)); put(RV32_MULDIV_c_0 + i, B(e.c, i));
-                put(RV32_MULDIV_q_0 + i, B(q, i)); put(RV32_MULDIV_r_0 + i, B(r, i));
-            }
-            put(RV32_MULDIV_mx, mx); put(RV32_MULDIV_my, my); put(RV32_MULDIV_mr, mr); put(RV32_MULDIV_mb, mb);
-            put(RV32_MULDIV_sx, sx); put(RV32_MULDIV_sy, sy); put(RV32_MULDIV_sr, sr); put(RV32_MULDIV_sb, sb);
-            sink.byte(B_MSB - 1, B(q, 3) << 8); sink.byte(B_MSB - 1, B(e.c, 3) << 8);
-            sink.byte(B_MSB - 1, B(r, 3) << 8); sink.byte(B_MSB - 1, B(e.b, 3) << 8);
-            // unsigned product bytes and carries
-            uint32_t prod[8], carry = 0;
-            for (int k = 0; k < 8; k++) {
-                uint32_t t = carry;
-                for (int i = 0; i < 4; i++) if (k - i >= 0 && k - i < 4) t += B(q, i) * B(e.c, k - i);
-                prod[k] = t & 0xff; carry = t >> 8;
-                put(RV32_MULDIV_prod_0 + k, prod[k]); put(RV32_MULDIV_mcy_0 + k, carry);
-                sink.byte(B_U16 - 1, carry);
-            }
-            for (int k = 0; k < 4; k++) sink.byte(B_RANGE - 1, (prod[2 * k] << 8) | prod[2 * k + 1]);
-            // high word of the signed product with borrows 0..2
-            uint32_t h[4], bin = 0;
-            for (int i = 0; i < 4; i++) {
-                int32_t t = (int32_t)prod[4 + i] - (int32_t)(sx * B(e.c, i)) - (int32_t)(sy * B(q, i)) - (int32_t)bin;
-                uint32_t bo = 0;
-                while (t < 0) { t += 256; bo++; }
-                h[i] = (uint32_t)t; bin = bo;
-                put(RV32_MULDIV_h_0 + i, h[i]); put(RV32_MULDIV_bw_0 + i, bo);
-            }
-            sink.byte(B_RANGE - 1, (h[0] << 8) | h[1]); sink.byte(B_RANGE - 1, (h[2] << 8) | h[3]);
-            sink.byte(B_RANGE - 1, (B(q, 0) << 8) | B(q, 1)); sink.byte(B_RANGE - 1, (B(q, 2) << 8) | B(q, 3));
-            sink.byte(B_RANGE - 1, (B(r, 0) << 8) | B(r, 1)); sink.byte(B_RANGE - 1, (B(r, 2) << 8) | B(r, 3));
-            uint32_t dl0 = 0, dl1 = 0;
-            if (is_dr) {
-                put(RV32_MULDIV_is_c0, c0); put(RV32_MULDIV_is_ovf, ovf);
-                const uint32_t csum = B(e.c, 0) + B(e.c, 1) + B(e.c, 2) + B(e.c, 3);
-                if (csum) put(RV32_MULDIV_cinv, inv(Fp::from_canonical(csum)).canonical());
-                if (!ovf) {  // 64-bit sum P + R' = B' in 16-bit limbs
-                    const uint32_t Pl[4] = {prod[0] | (prod[1] << 8), prod[2] | (prod[3] << 8), h[0] | (h[1] << 8), h[2] | (h[3] << 8)};
-                    const uint32_t Rl[4] = {r & 0xffff, r >> 16, 65535 * sr, 65535 * sr};
-                    uint32_t cy = 0;
-                    for (int k = 0; k < 4; k++) { cy = (Pl[k] + Rl[k] + cy) >> 16; put(RV32_MULDIV_dcy_0 + k, cy); }
-                }
-                if (!c0) {  // |c| - |r| - 1 in two limbs, low-limb carry e0 = ea + 2 eb - 1
-                    const int64_t sc_ = 1 - 2 * (int64_t)sy, sr_ = 1 - 2 * (int64_t)sr;
-                    const int64_t t0 = sc_ * (e.c & 0xffff) - sr_ * (r & 0xffff) - 1;
-                    int64_t e0 = 0;
-                    while (t0 + 65536 * e0 < 0) e0++;
-                    while (t0 + 65536 * e0 > 65535) e0--;
-                    dl0 = (uint32_t)(t0 + 65536 * e0);
-                    dl1 = (uint32_t)(sc_ * (e.c >> 16) - sr_ * (r >> 16) + 65536 * ((int64_t)sy - (int64_t)sr) - e0);
-                    put(RV32_MULDIV_ea, (uint32_t)((e0 + 1) & 1)); put(RV32_MULDIV_eb, (uint32_t)((e0 + 1) >> 1));
-                } else {
-                    put(RV32_MULDIV_ea, 1);  // e0 = 0 (unconstrained here; any boolean pair is fine)
-                }
-            } else {
-                put(RV32_MULDIV_ea, 1);
-            }
-            put(RV32_MULDIV_dl_0, dl0); put(RV32_MULDIV_dl_1, dl1);
-            sink.byte(B_U16 - 1, dl0); sink.byte(B_U16 - 1, dl1);
         }
     }
     lap_aux("muldiv rows");
@@ -894,52 +813,17 @@ bool build_aux_host(const ShardMeta &S, const std::vector<AluEvent> &alu, const 
         const uint32_t lx = ceil_log2(sha_ext.size() * 64);
         const size_t nx = (size_t)1 << lx;
         T.log_n[RV32_CHIP_SHA_EXTEND] = lx;
-        auto &H = T.main[RV32_CHIP_SHA_EXTEND];
-        H.assign((size_t)RV32_SHA_EXTEND_MAIN_W * nx, 0);
-        for (size_t e = 0; e < sha_ext.size(); e++) {
-            const ShaExtEvent &ev = sha_ext[e];
-            for (uint32_t j = 0; j < 64; j++) {
-                const size_t row = e * 64 + j;
-                auto put = [&](int col, uint32_t v) { H[(size_t)col * nx + row] = v; };
-                auto put_word = [&](int col0, uint32_t v) { for (int i = 0; i < 4; i++) put(col0 + i, (v >> (8 * i)) & 0xff); };
-                put(RV32_SHA_EXTEND_is_real, 1);
-                put(RV32_SHA_EXTEND_is_first, j == 0); put(RV32_SHA_EXTEND_is_last, j == 63);
-                put(RV32_SHA_EXTEND_is_load, j < 16); put(RV32_SHA_EXTEND_is_e, j == 15);
-                put(RV32_SHA_EXTEND_j, j);
-                if (j != 63) put(RV32_SHA_EXTEND_j_inv, inv(Fp::from_canonical(j) - Fp::from_canonical(63)).canonical());
-                put(RV32_SHA_EXTEND_clk, ev.clk);
-                put_word(RV32_SHA_EXTEND_p_0, ev.ptr);
-                // window: W[k] = w[j - 16 + k] (zero before the array's start)
-                for (uint32_t k = 0; k < 16; k++) put_word(RV32_SHA_EXTEND_w0_0 + 4 * k, j + k >= 16 ? ev.w[j + k - 16] : 0u);
-                const uint32_t x = j + 1 >= 16 ? ev.w[j + 1 - 16] : 0u, y = j + 14 >= 16 ? ev.w[j + 14 - 16] : 0u;
-                for (int k = 0; k < 32; k++) { put(RV32_SHA_EXTEND_xb_0 + k, (x >> k) & 1); put(RV32_SHA_EXTEND_yb_0 + k, (y >> k) & 1); }
-                const uint32_t s0 = ((x >> 7) | (x << 25)) ^ ((x >> 18) | (x << 14)) ^ (x >> 3);
-                const uint32_t s1 = ((y >> 17) | (y << 15)) ^ ((y >> 19) | (y << 13)) ^ (y >> 10);
-                put(RV32_SHA_EXTEND_s0_0, s0 & 0xffff); put(RV32_SHA_EXTEND_s0_1, s0 >> 16);
-                put(RV32_SHA_EXTEND_s1_0, s1 & 0xffff); put(RV32_SHA_EXTEND_s1_1, s1 >> 16);
-                const uint32_t nw = ev.w[j];
-                put_word(RV32_SHA_EXTEND_nw_0, nw);
-                put_word(RV32_SHA_EXTEND_old_0, ev.old[j]);
-                if (j >= 16) {
-                    const uint32_t w0 = ev.w[j - 16], w9 = ev.w[j - 7];
-                    const uint32_t lo = (w0 & 0xffff) + (s0 & 0xffff) + (w9 & 0xffff) + (s1 & 0xffff);
-                    const uint32_t c_lo = lo >> 16;
-                    const uint32_t hi = (w0 >> 16) + (s0 >> 16) + (w9 >> 16) + (s1 >> 16) + c_lo;
-                    const uint32_t c_hi = hi >> 16;
-                    put(RV32_SHA_EXTEND_cy_0, c_lo & 1); put(RV32_SHA_EXTEND_cy_1, c_lo >> 1);
-                    put(RV32_SHA_EXTEND_cy_2, c_hi & 1); put(RV32_SHA_EXTEND_cy_3, c_hi >> 1);
-                    sink.byte(B_RANGE - 1, ((nw & 0xff) << 8) | ((nw >> 8) & 0xff));
-                    sink.byte(B_RANGE - 1, (((nw >> 16) & 0xff) << 8) | (nw >> 24));
+        if (device_rows) {
+            device_rows->sha_ext = sha_ext;              // K0 of this chip runs on the GPU (launch_k0_sha_extend_rows)
+        } else {
+            auto &H = T.main[RV32_CHIP_SHA_EXTEND];
+            H.assign((size_t)RV32_SHA_EXTEND_MAIN_W * nx, 0);
+            HostSink hs{H.data(), nx, 0, byte_mult.data(), nullptr};
+            for (size_t e = 0; e < sha_ext.size(); e++)
+                for (uint32_t j = 0; j < 64; j++) {
+                    hs.row = e * 64 + j;
+                    fill_sha_extend_row(sha_ext[e], j, S.index, hs);
                 }
-                // the access: previous (shard, clk) of the word, gap to (shard, clk + 2)
-                const uint32_t psh = ev.prev_sh[j], pts = ev.prev_ts[j];
-                const uint32_t d = psh == S.index ? ev.clk + 2 - pts - 1 : S.index - psh - 1;
-                put(RV32_SHA_EXTEND_m_sh, psh); put(RV32_SHA_EXTEND_m_ts, pts); put(RV32_SHA_EXTEND_m_same, psh == S.index);
-                put(RV32_SHA_EXTEND_m_lo, d & 0xffff); put(RV32_SHA_EXTEND_m_hi, d >> 16);
-                sink.byte(B_U16 - 1, d & 0xffff);
-                sink.byte(B_RANGE - 1, (d >> 16) << 8);
-                if (j == 0) sink.byte(B_ADDR - 1, ((ev.ptr & 0xff) << 8) | (ev.ptr >> 24));
-            }
         }
     }
     // sha_compress chip: 80 rows per SHA_COMPRESS call
@@ -949,73 +833,19 @@ bool build_aux_host(const ShardMeta &S, const std::vector<AluEvent> &alu, const 
         const uint32_t lx = ceil_log2(sha_cmp.size() * 80);
         const size_t nx = (size_t)1 << lx;
         T.log_n[RV32_CHIP_SHA_COMPRESS] = lx;
-        auto &H = T.main[RV32_CHIP_SHA_COMPRESS];
-        H.assign((size_t)RV32_SHA_COMPRESS_MAIN_W * nx, 0);
-        auto rotr = [](uint32_t x, int n) { return (x >> n) | (x << (32 - n)); };
-        for (size_t e = 0; e < sha_cmp.size(); e++) {
-            const ShaCmpEvent &ev = sha_cmp[e];
-            uint32_t v[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // working variables a..h at the START of the row
-            for (uint32_t j = 0; j < 80; j++) {
-                const size_t row = e * 80 + j;
-                const uint32_t g = j >> 3, o = j & 7;
-                auto put = [&](int col, uint32_t x) { H[(size_t)col * nx + row] = x; };
-                auto put_word = [&](int col0, uint32_t x) { for (int i = 0; i < 4; i++) put(col0 + i, (x >> (8 * i)) & 0xff); };
-                auto put_bits = [&](int col0, uint32_t x) { for (int k = 0; k < 32; k++) put(col0 + k, (x >> k) & 1); };
-                put(RV32_SHA_COMPRESS_is_real, 1); put(RV32_SHA_COMPRESS_is_first, j == 0); put(RV32_SHA_COMPRESS_is_last, j == 79);
-                put(RV32_SHA_COMPRESS_oc_0 + o, 1); put(RV32_SHA_COMPRESS_gr_0 + g, 1);
-                put(RV32_SHA_COMPRESS_clk, ev.clk);
-                put_word(RV32_SHA_COMPRESS_wp_0, ev.w_ptr); put_word(RV32_SHA_COMPRESS_hp_0, ev.h_ptr);
-                put_bits(RV32_SHA_COMPRESS_ab_0, v[0]); put_bits(RV32_SHA_COMPRESS_bb_0, v[1]); put_bits(RV32_SHA_COMPRESS_cb_0, v[2]);
-                put_bits(RV32_SHA_COMPRESS_eb_0, v[4]); put_bits(RV32_SHA_COMPRESS_fb_0, v[5]); put_bits(RV32_SHA_COMPRESS_gb_0, v[6]);
-                put(RV32_SHA_COMPRESS_d_0, v[3] & 0xffff); put(RV32_SHA_COMPRESS_d_1, v[3] >> 16);
-                put(RV32_SHA_COMPRESS_h_0, v[7] & 0xffff); put(RV32_SHA_COMPRESS_h_1, v[7] >> 16);
-                const uint32_t S1 = rotr(v[4], 6) ^ rotr(v[4], 11) ^ rotr(v[4], 25), S0 = rotr(v[0], 2) ^ rotr(v[0], 13) ^ rotr(v[0], 22);
-                const uint32_t mj = (v[0] & v[1]) ^ (v[0] & v[2]) ^ (v[1] & v[2]), chv = (v[4] & v[5]) ^ (~v[4] & v[6]);
-                put(RV32_SHA_COMPRESS_s1_0, S1 & 0xffff); put(RV32_SHA_COMPRESS_s1_1, S1 >> 16);
-                put(RV32_SHA_COMPRESS_s0_0, S0 & 0xffff); put(RV32_SHA_COMPRESS_s0_1, S0 >> 16);
-                put(RV32_SHA_COMPRESS_mj_0, mj & 0xffff); put(RV32_SHA_COMPRESS_mj_1, mj >> 16);
-                // the access of this row
-                uint32_t addr, before, after, psh, pts, ts = ev.clk + 2;
-                if (g == 0) { addr = ev.h_ptr + 4 * (7 - o); before = after = ev.hs[7 - o]; psh = ev.h_sh[7 - o]; pts = ev.h_ts[7 - o]; }
-                else if (g <= 8) { const uint32_t i = 8 * (g - 1) + o; addr = ev.w_ptr + 4 * i; before = after = ev.w[i]; psh = ev.w_sh[i]; pts = ev.w_ts[i]; }
-                else { addr = ev.h_ptr + 4 * (7 - o); before = ev.hs[7 - o]; after = before + v[7]; psh = (uint16_t)S.index; pts = ev.clk + 2; ts = ev.clk + 3; }
-                put(RV32_SHA_COMPRESS_maddr, addr);
-                put_word(RV32_SHA_COMPRESS_mv_0, after); put_word(RV32_SHA_COMPRESS_mo_0, before);
-                const uint32_t dgap = psh == S.index ? ts - pts - 1 : S.index - psh - 1;
-                put(RV32_SHA_COMPRESS_m_sh, psh); put(RV32_SHA_COMPRESS_m_ts, pts); put(RV32_SHA_COMPRESS_m_same, psh == S.index);
-                put(RV32_SHA_COMPRESS_m_lo, dgap & 0xffff); put(RV32_SHA_COMPRESS_m_hi, dgap >> 16);
-                sink.byte(B_U16 - 1, dgap & 0xffff);
-                sink.byte(B_RANGE - 1, (dgap >> 16) << 8);
-                if (j == 0) {
-                    sink.byte(B_ADDR - 1, ((ev.w_ptr & 0xff) << 8) | (ev.w_ptr >> 24));
-                    sink.byte(B_ADDR - 1, ((ev.h_ptr & 0xff) << 8) | (ev.h_ptr >> 24));
+        if (device_rows) {
+            device_rows->sha_cmp = sha_cmp;              // K0 of this chip runs on the GPU (launch_k0_sha_compress_rows)
+        } else {
+            auto &H = T.main[RV32_CHIP_SHA_COMPRESS];
+            H.assign((size_t)RV32_SHA_COMPRESS_MAIN_W * nx, 0);
+            HostSink hs{H.data(), nx, 0, byte_mult.data(), nullptr};
+            for (size_t e = 0; e < sha_cmp.size(); e++) {
+                uint32_t v[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // working variables a..h at the START of the row
+                for (uint32_t j = 0; j < 80; j++) {
+                    hs.row = e * 80 + j;
+                    fill_sha_compress_row(sha_cmp[e], j, v, S.index, hs);
+                    sha_compress_next(sha_cmp[e], j, v);
                 }
-                // next row's variables
-                uint32_t nv[8];
-                for (int k = 7; k > 0; k--) nv[k] = v[k - 1];
-                nv[0] = 0;
-                if (g == 0) nv[0] = before;
-                else if (g <= 8) {
-                    const uint32_t i = 8 * (g - 1) + o, K = SHA256_K[i], wv = ev.w[i];
-                    // e' = d + T1, a' = T1 + T2 in 16-bit halves: the carries are witnesses
-                    const uint32_t lo_t = (v[7] & 0xffff) + (S1 & 0xffff) + (chv & 0xffff) + (K & 0xffff) + (wv & 0xffff);
-                    const uint32_t hi_t = (v[7] >> 16) + (S1 >> 16) + (chv >> 16) + (K >> 16) + (wv >> 16);
-                    const uint32_t e_lo = lo_t + (v[3] & 0xffff), ce_lo = e_lo >> 16, e_hi = hi_t + (v[3] >> 16) + ce_lo, ce_hi = e_hi >> 16;
-                    const uint32_t a_lo = lo_t + (S0 & 0xffff) + (mj & 0xffff), ca_lo = a_lo >> 16;
-                    const uint32_t a_hi = hi_t + (S0 >> 16) + (mj >> 16) + ca_lo, ca_hi = a_hi >> 16;
-                    for (int k = 0; k < 3; k++) {
-                        put(RV32_SHA_COMPRESS_ce_0 + k, (ce_lo >> k) & 1); put(RV32_SHA_COMPRESS_ce_0 + 3 + k, (ce_hi >> k) & 1);
-                        put(RV32_SHA_COMPRESS_ca_0 + k, (ca_lo >> k) & 1); put(RV32_SHA_COMPRESS_ca_0 + 3 + k, (ca_hi >> k) & 1);
-                    }
-                    nv[4] = (e_lo & 0xffff) | (e_hi << 16);
-                    nv[0] = (a_lo & 0xffff) | (a_hi << 16);
-                } else {
-                    const uint32_t lo = (before & 0xffff) + (v[7] & 0xffff), hi2 = (before >> 16) + (v[7] >> 16) + (lo >> 16);
-                    put(RV32_SHA_COMPRESS_cf_0, lo >> 16); put(RV32_SHA_COMPRESS_cf_1, hi2 >> 16);
-                    sink.byte(B_RANGE - 1, ((after & 0xff) << 8) | ((after >> 8) & 0xff));
-                    sink.byte(B_RANGE - 1, (((after >> 16) & 0xff) << 8) | (after >> 24));
-                }
-                for (int k = 0; k < 8; k++) v[k] = nv[k];
             }
         }
     }

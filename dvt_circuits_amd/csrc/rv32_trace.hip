@@ -90,11 +90,19 @@ __global__ void __launch_bounds__(256) k0_cpu_rows_kernel(const CycleRec *recs, 
         if (keys[s] != K0_EMPTY && counts[s]) sink.global_add(keys[s], counts[s]);
 }
 
-// K0 of the shift (WHICH = 0: one AluEvent per row) and mem_init (WHICH = 1: one MemInitRow per row) chips: the same sink as the
-// cpu chip's K0 (Montgomery words straight into the column-major trace, lookups through the workgroup's LDS cache).  The
-// host used to build these rows and upload them: 168 MB of mem_init table for the largest legal input against 26 MB of rows.
+// K0 of the chips outside the cpu chip whose rows come from compact events: the same sink as the cpu chip's K0 (Montgomery
+// words straight into the column-major trace, lookups through the workgroup's LDS cache), one thread per trace row.
+//   K0_SHIFT / K0_MULDIV   row r <- AluEvent r
+//   K0_MEM_INIT            row r <- MemInitRow r (and r - 1)
+//   K0_SHA_EXTEND          row r <- call r / 64, j = r % 64: the 64 lanes of a wave read one event (broadcast loads)
+//   K0_SHA_COMPRESS        row r <- call r / 80, j = r % 80.  The working variables at the start of row j are a recurrence over
+//                          the call's earlier rows; each thread recomputes it (at most 71 rounds of integer work against 260
+//                          column stores), which keeps one thread per row and with it the coalesced stores
+// The host used to build these rows and upload them: 168 MB of mem_init table for the largest legal input against 26 MB of
+// rows, 83 KB of sha_compress table per call against an event of 732 B.
+enum K0Aux { K0_SHIFT, K0_MEM_INIT, K0_MULDIV, K0_SHA_EXTEND, K0_SHA_COMPRESS };
 template <int WHICH>
-__global__ void __launch_bounds__(256) k0_aux_rows_kernel(const void *events, size_t n_ev, uint32_t *main, uint32_t log_n, uint32_t *byte_mult) {
+__global__ void __launch_bounds__(256) k0_aux_rows_kernel(const void *events, size_t n_rows, uint32_t shard, uint32_t *main, uint32_t log_n, uint32_t *byte_mult) {
     __shared__ uint32_t keys[K0_SLOTS], counts[K0_SLOTS];
     for (uint32_t s = threadIdx.x; s < K0_SLOTS; s += blockDim.x) { keys[s] = K0_EMPTY; counts[s] = 0; }
     __syncthreads();
@@ -102,27 +110,47 @@ __global__ void __launch_bounds__(256) k0_aux_rows_kernel(const void *events, si
     const size_t base = (size_t)blockIdx.x * K0_ROWS_PER_BLOCK;
     for (uint32_t k = 0; k < K0_ROWS_PER_BLOCK / 256; k++) {
         const size_t r = base + (size_t)k * 256 + threadIdx.x;
-        if (r < n_ev) {
+        if (r < n_rows) {
             sink.row = r;
-            if constexpr (WHICH == 0) fill_shift_row(static_cast<const AluEvent *>(events)[r], sink);
-            else fill_mem_init_row(static_cast<const MemInitRow *>(events), r, sink);
+            if constexpr (WHICH == K0_SHIFT) fill_shift_row(static_cast<const AluEvent *>(events)[r], sink);
+            else if constexpr (WHICH == K0_MEM_INIT) fill_mem_init_row(static_cast<const MemInitRow *>(events), r, sink);
+            else if constexpr (WHICH == K0_MULDIV) fill_muldiv_row(static_cast<const AluEvent *>(events)[r], sink);
+            else if constexpr (WHICH == K0_SHA_EXTEND) fill_sha_extend_row(static_cast<const ShaExtEvent *>(events)[r / 64], (uint32_t)(r % 64), shard, sink);
+            else {
+                const ShaCmpEvent &ev = static_cast<const ShaCmpEvent *>(events)[r / 80];
+                const uint32_t j = (uint32_t)(r % 80);
+                uint32_t v[8];
+                sha_compress_vars_at(ev, j, v);
+                fill_sha_compress_row(ev, j, v, shard, sink);
+            }
         }
     }
     __syncthreads();
     for (uint32_t s = threadIdx.x; s < K0_SLOTS; s += blockDim.x)
         if (keys[s] != K0_EMPTY && counts[s]) sink.global_add(keys[s], counts[s]);
 }
-hipError_t launch_k0_shift_rows(hipStream_t st, const AluEvent *d_ev, size_t n_ev, uint32_t *d_main, uint32_t log_n, uint32_t *d_byte_mult) {
-    if (!n_ev) return hipSuccess;
-    if (((size_t)1 << log_n) < n_ev) return hipErrorInvalidValue;
-    k0_aux_rows_kernel<0><<<(unsigned)((n_ev + K0_ROWS_PER_BLOCK - 1) / K0_ROWS_PER_BLOCK), 256, 0, st>>>(d_ev, n_ev, d_main, log_n, d_byte_mult);
-    return hipGetLastError();
-}
-hipError_t launch_k0_mem_init_rows(hipStream_t st, const MemInitRow *d_rows, size_t n_rows, uint32_t *d_main, uint32_t log_n, uint32_t *d_byte_mult) {
+// n_rows rows of the zeroed matrix d_main [W][2^log_n]
+template <int WHICH>
+static hipError_t launch_k0_aux_rows(hipStream_t st, const void *d_ev, size_t n_rows, uint32_t shard, uint32_t *d_main, uint32_t log_n, uint32_t *d_byte_mult) {
     if (!n_rows) return hipSuccess;
     if (((size_t)1 << log_n) < n_rows) return hipErrorInvalidValue;
-    k0_aux_rows_kernel<1><<<(unsigned)((n_rows + K0_ROWS_PER_BLOCK - 1) / K0_ROWS_PER_BLOCK), 256, 0, st>>>(d_rows, n_rows, d_main, log_n, d_byte_mult);
+    k0_aux_rows_kernel<WHICH><<<(unsigned)((n_rows + K0_ROWS_PER_BLOCK - 1) / K0_ROWS_PER_BLOCK), 256, 0, st>>>(d_ev, n_rows, shard, d_main, log_n, d_byte_mult);
     return hipGetLastError();
+}
+hipError_t launch_k0_shift_rows(hipStream_t st, const AluEvent *d_ev, size_t n_ev, uint32_t *d_main, uint32_t log_n, uint32_t *d_byte_mult) {
+    return launch_k0_aux_rows<K0_SHIFT>(st, d_ev, n_ev, 0, d_main, log_n, d_byte_mult);
+}
+hipError_t launch_k0_mem_init_rows(hipStream_t st, const MemInitRow *d_rows, size_t n_rows, uint32_t *d_main, uint32_t log_n, uint32_t *d_byte_mult) {
+    return launch_k0_aux_rows<K0_MEM_INIT>(st, d_rows, n_rows, 0, d_main, log_n, d_byte_mult);
+}
+hipError_t launch_k0_muldiv_rows(hipStream_t st, const AluEvent *d_ev, size_t n_ev, uint32_t *d_main, uint32_t log_n, uint32_t *d_byte_mult) {
+    return launch_k0_aux_rows<K0_MULDIV>(st, d_ev, n_ev, 0, d_main, log_n, d_byte_mult);
+}
+hipError_t launch_k0_sha_extend_rows(hipStream_t st, const ShaExtEvent *d_ev, size_t n_calls, uint32_t shard, uint32_t *d_main, uint32_t log_n, uint32_t *d_byte_mult) {
+    return launch_k0_aux_rows<K0_SHA_EXTEND>(st, d_ev, n_calls * 64, shard, d_main, log_n, d_byte_mult);
+}
+hipError_t launch_k0_sha_compress_rows(hipStream_t st, const ShaCmpEvent *d_ev, size_t n_calls, uint32_t shard, uint32_t *d_main, uint32_t log_n, uint32_t *d_byte_mult) {
+    return launch_k0_aux_rows<K0_SHA_COMPRESS>(st, d_ev, n_calls * 80, shard, d_main, log_n, d_byte_mult);
 }
 
 hipError_t launch_k0_cpu_rows(hipStream_t st, const CycleRec *d_recs, size_t n_recs, uint32_t shard, uint32_t shard_next_pc, const Instr *d_instrs,

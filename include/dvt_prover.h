@@ -105,7 +105,8 @@ void dvt_prover_destroy(dvt_prover *p);
 /* last error text of this handle (or of the failed create when p == NULL) */
 const char *dvt_last_error(const dvt_prover *p);
 void dvt_free(void *ptr);
-/* ABI version of this header (4: "devices", dvt_prover_device_count, dvt_prover_device, dvt_rv32_job_shard_member) */
+/* ABI version of this header (4: "devices", dvt_prover_device_count, dvt_prover_device, dvt_rv32_job_shard_member;
+ * 5: dvt_rv32_job_shard_device_rows) */
 uint32_t dvt_abi_version(void);
 /* the handle's hipStream_t (for event timing by the caller) */
 void *dvt_stream(dvt_prover *p);
@@ -275,7 +276,9 @@ int dvt_prove_core(dvt_prover *p, const dvt_pk *pk, const dvt_buf *stdin_bufs, s
  *   prepare        the executor pipeline: one sequential fast pass of the guest cuts the execution into
  *                  shards; the shards this job owns (prepare: all; prepare_part: first, first + stride, ...)
  *                  are re-executed in trace mode on host threads, uploaded (compact 48-byte per-cycle
- *                  records) and taken through phase 1 on the GPU as they arrive
+ *                  records; the events of the shift, muldiv, SHA and field / curve precompile chips and the rows of
+ *                  the mem_init table, from which the GPU builds those chips' trace rows: the host builds no trace
+ *                  row) and taken through phase 1 on the GPU as they arrive
  *   commit_shard   header of shard i (global position in the execution); phase 1 = K0 + K1..K3 of the
  *                  main traces runs here only if the pipeline's result has been consumed by an earlier proof
  *   challenges     host-only: the common challenges from ALL headers (in shard order)
@@ -306,6 +309,10 @@ size_t dvt_rv32_job_shards(const dvt_job *job);
 /* the device member that holds shard `shard` (global position in the execution): 0 on a one-device handle; -1 when this
  * job does not hold the shard */
 int dvt_rv32_job_shard_member(const dvt_job *job, size_t shard);
+/* bit mask over the chip ids of the rv32 machine (2 cpu, 4 mem_init, 5 shift, 6 muldiv, 7 sha_extend, 8 sha_compress,
+ * 9..13 the field / curve precompile chips): bit c is set when the trace rows of chip c of shard `shard` (global position)
+ * were built on the GPU from uploaded events, not uploaded as a table.  0 for a shard this job does not hold. */
+uint32_t dvt_rv32_job_shard_device_rows(const dvt_job *job, size_t shard);
 int dvt_rv32_commit_shard(dvt_prover *p, const dvt_pk *pk, dvt_job *job, size_t shard, uint32_t *header);
 int dvt_rv32_challenges(const uint8_t *vk, size_t vk_len, const uint32_t *headers, size_t n_shards, uint32_t out[8]);
 int dvt_rv32_prove_shard(dvt_prover *p, const dvt_pk *pk, dvt_job *job, size_t shard, const uint32_t challenges[8],
