@@ -84,6 +84,11 @@ def load():
     lib.dvt_stage_pow_grind.argtypes = [vp, u32p, u32, u32, u32p]
     lib.dvt_stage_perm.argtypes = [vp, C.c_char_p, u32, vp, vp, u32, u32p, u32p, u32p, u32, vp, u32p]
     lib.dvt_stage_quotient.argtypes = [vp, C.c_char_p, u32, vp, vp, vp, u32, u32p, u32p, u32p, u32p, u32p, u32, u32, vp]
+    lib.dvt_stage_check_constraints.argtypes = [vp, C.c_char_p, u32, vp, vp, u32, u32p, u32p, u32p, C.POINTER(CheckResult)]
+    lib.dvt_stage_bus_sums.argtypes = [vp, C.c_char_p, u32, vp, vp, u32, u32p, u32p, u32p, u32p]
+    lib.dvt_rv32_check_job.argtypes = [vp, vp, vp, C.POINTER(CheckFinding), sz, C.POINTER(CheckSummary)]
+    lib.dvt_rv32_job_shard_chips.argtypes = [vp, sz]
+    lib.dvt_rv32_job_shard_chips.restype = u32
     lib.dvt_machine_setup.argtypes = [vp, C.c_char_p, C.POINTER(HostTrace), sz, C.POINTER(vp), C.POINTER(u8p), C.POINTER(sz)]
     lib.dvt_pk_free.argtypes = [vp, vp]
     lib.dvt_pk_free.restype = None
@@ -120,6 +125,22 @@ def load():
     lib.dvt_stdin_from_json.argtypes = [C.c_char_p, C.c_char_p, sz, C.c_int, C.POINTER(u8p), C.POINTER(sz), C.POINTER(C.c_char_p)]
     _lib = lib
     return lib
+
+
+class CheckResult(C.Structure):
+    _fields_ = [("violations", C.c_uint64), ("first_row", C.c_uint32), ("first_constraint", C.c_int32)]
+
+
+class CheckFinding(C.Structure):
+    _fields_ = [("shard", C.c_uint32), ("chip", C.c_uint32), ("log_n", C.c_uint32), ("r", CheckResult)]
+
+
+class CheckSummary(C.Structure):
+    _fields_ = [("violations", C.c_uint64), ("n_findings", C.c_uint32), ("bus_checked", C.c_uint32), ("unbalanced_buses", C.c_uint32),
+                ("ms", C.c_float)]
+
+
+CHECK_BUSES = 8   # DVT_CHECK_BUSES
 
 
 class Buf(C.Structure):
@@ -420,6 +441,30 @@ class Prover:
                                                pv, u4(perm_alpha), u4(beta), u4(alpha), u4(cum), PATHS[path], SELECTORS[selectors],
                                                t_out.data_ptr()))
 
+    def stage_check_constraints(self, machine, chip, t_main, t_prep, log_n, pubs, xi, n_constraints=None):
+        """Trace-row check of one chip: device matrices in Montgomery form (t_prep None when the width is 0), xi = 4
+        canonical words.  Returns (dict(violations, first_row, first_constraint), counts); counts is a uint32 array of
+        n_constraints words (rows violating each unit), or None when n_constraints is None."""
+        pv = (C.c_uint32 * max(len(pubs), 1))(*[int(x) for x in pubs])
+        x4 = (C.c_uint32 * 4)(*[int(x) for x in xi])
+        counts = np.zeros(max(n_constraints, 1), np.uint32) if n_constraints is not None else None
+        r = CheckResult()
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        self.check(self.lib.dvt_stage_check_constraints(self.h, machine.encode(), chip, ptr(t_main), ptr(t_prep), log_n, pv, x4,
+                                                        counts.ctypes.data_as(u32p) if counts is not None else None, C.byref(r)))
+        return (dict(violations=int(r.violations), first_row=int(r.first_row), first_constraint=int(r.first_constraint)),
+                counts[:n_constraints] if counts is not None else None)
+
+    def stage_bus_sums(self, machine, chip, t_main, t_prep, log_n, pubs, perm_alpha, beta):
+        """The chip's signed LogUp terms summed over the rows, per bus: a [CHECK_BUSES][4] array of canonical words."""
+        u4 = lambda v: (C.c_uint32 * 4)(*[int(x) for x in v])
+        pv = (C.c_uint32 * max(len(pubs), 1))(*[int(x) for x in pubs])
+        out = np.zeros((CHECK_BUSES, 4), np.uint32)
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        self.check(self.lib.dvt_stage_bus_sums(self.h, machine.encode(), chip, ptr(t_main), ptr(t_prep), log_n, pv, u4(perm_alpha), u4(beta),
+                                               out.ctypes.data_as(u32p)))
+        return out
+
     # ---- machine level
     def machine_setup(self, machine: str, prep):
         arr, keep = _traces(prep)
@@ -477,6 +522,26 @@ class Prover:
         b = C.string_at(out, n.value)
         self.lib.dvt_free(C.cast(out, C.c_void_p))
         return b
+
+    def check_job(self, pk, job, cap=256):
+        """Trace rows of a prepared job against the AIR, on the GPU (dvt_rv32_check_job).  Returns (summary, findings):
+        summary = dict(ok, violations, n_findings, bus_checked, unbalanced_buses, ms, error), findings = list of
+        dict(shard, chip, log_n, violations, first_row, first_constraint), at most cap of them.  A job with violations or
+        unbalanced buses is reported (ok False, error = the library's message), not raised; other failures raise."""
+        arr = (CheckFinding * max(cap, 1))()
+        s = CheckSummary()
+        rc = self.lib.dvt_rv32_check_job(self.h, pk, job, arr, cap, C.byref(s))
+        if rc not in (DVT_OK, DVT_ERR_REJECTED):
+            self.check(rc)
+        summary = dict(ok=rc == DVT_OK, violations=int(s.violations), n_findings=int(s.n_findings), bus_checked=int(s.bus_checked),
+                       unbalanced_buses=int(s.unbalanced_buses), ms=float(s.ms), error=self.lib.dvt_last_error(self.h).decode() if rc else "")
+        found = [dict(shard=int(f.shard), chip=int(f.chip), log_n=int(f.log_n), violations=int(f.r.violations), first_row=int(f.r.first_row),
+                      first_constraint=int(f.r.first_constraint)) for f in arr[:min(int(s.n_findings), cap)]]
+        return summary, found
+
+    def job_shard_chips(self, job, shard):
+        """bit c set: shard `shard` (global position) has a table of chip c; 0 when the job does not hold the shard"""
+        return int(self.lib.dvt_rv32_job_shard_chips(job, shard))
 
     def debug_device_traces(self, pk, job, shard=0):
         """K0 on the device for one shard, traces downloaded (canonical): (chips, pubs)"""

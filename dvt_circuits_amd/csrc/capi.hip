@@ -228,11 +228,69 @@ int verify_words(const uint8_t *proof, size_t len, int len_code, char **reason,
     } catch (const std::exception &e) { why = e.what(); }
     return rc ? reject(reason, rc, why) : DVT_OK;
 }
+
+int check_tables(const Lane &c, const MachineDesc *m, const std::vector<CheckTable> &tabs, const std::vector<uint32_t> &pub_mont,
+                 const CheckChallenges &ch, bool constraints, bool buses, std::vector<CheckTableOut> *out) {
+    Engine &e = c.eng;
+    constexpr size_t BW = 4 * DVT_CHECK_BUSES;
+    // result words: one 64-bit key per table, then per table its counts and its bus sums
+    std::vector<size_t> at(tabs.size());
+    size_t words = 2 * tabs.size();
+    for (size_t i = 0; i < tabs.size(); i++) {
+        if (!tabs[i].d->launch_check || !tabs[i].d->launch_bus) return fail(c.err, DVT_ERR_UNSUPPORTED, "chip %s has no trace-row check", tabs[i].d->name);
+        at[i] = words;
+        words += (size_t)tabs[i].d->n_constraints + BW;
+    }
+    out->assign(tabs.size(), CheckTableOut{});
+    for (auto &o : *out) {
+        o.r = dvt_check_result{0, 0, -1};
+        for (auto &b : o.bus) b = Fp4::zero();
+    }
+    if (tabs.empty()) return DVT_OK;
+    StageBuf res{e.pool}, partial{e.pool};
+    HIP_TRY(c.err, e.pool.alloc_bytes(&res.ptr, words * 4));
+    if (buses) HIP_TRY(c.err, e.pool.alloc_bytes(&partial.ptr, BUS_PARTIAL_WORDS * 4));
+    uint32_t *d_res = static_cast<uint32_t *>(res.ptr);
+    HIP_TRY(c.err, hipMemsetAsync(d_res, 0xff, 8 * tabs.size(), e.stream));
+    HIP_TRY(c.err, hipMemsetAsync(d_res + 2 * tabs.size(), 0, (words - 2 * tabs.size()) * 4, e.stream));
+    int n_beta, n_alpha;
+    challenge_power_counts(m, &n_beta, &n_alpha);
+    const Fp4 *d_xi = nullptr, *d_beta = nullptr;
+    const double *d_xi_f64 = nullptr, *d_beta_f64 = nullptr;
+    const uint32_t *d_pub = static_cast<const uint32_t *>(e.upload_vec(pub_mont));
+    if (!d_pub || (constraints && !e.upload_powers(ch.xi, (size_t)n_alpha, true, &d_xi, &d_xi_f64)) ||
+        (buses && !e.upload_powers(ch.beta, (size_t)n_beta, false, &d_beta, &d_beta_f64)))
+        return engine_fail(c.err, e);
+    for (size_t i = 0; i < tabs.size(); i++) {
+        const CheckTable &t = tabs[i];
+        if (constraints) {
+            const CheckArgs ca{t.main, t.prep, d_pub, d_xi, d_xi_f64, t.log_n, d_res + at[i], reinterpret_cast<unsigned long long *>(d_res) + i};
+            HIP_TRY(c.err, t.d->launch_check(e.stream, ca));
+        }
+        if (buses) {
+            const BusArgs ba{t.main, t.prep, d_pub, d_beta_f64, ch.perm_alpha, t.log_n, static_cast<uint32_t *>(partial.ptr), d_res + at[i] + t.d->n_constraints};
+            HIP_TRY(c.err, t.d->launch_bus(e.stream, ba));
+        }
+    }
+    std::vector<uint32_t> h(words);
+    if (!e.download(h.data(), d_res, words * 4)) return engine_fail(c.err, e);
+    for (size_t i = 0; i < tabs.size(); i++) {
+        CheckTableOut &o = (*out)[i];
+        const uint32_t *cw = h.data() + at[i];
+        o.counts.assign(cw, cw + tabs[i].d->n_constraints);
+        for (uint32_t x : o.counts) o.r.violations += x;
+        const uint64_t key = (uint64_t)h[2 * i] | ((uint64_t)h[2 * i + 1] << 32);
+        if (key != CHECK_NO_KEY) { o.r.first_row = (uint32_t)(key >> 32); o.r.first_constraint = (int32_t)(uint32_t)key; }
+        for (uint32_t b = 0; b < DVT_CHECK_BUSES; b++)
+            for (int k = 0; k < 4; k++) o.bus[b].c[k] = Fp::raw(cw[tabs[i].d->n_constraints + 4 * b + k]);
+    }
+    return DVT_OK;
+}
 }  // namespace dvt
 
 extern "C" {
 
-uint32_t dvt_abi_version(void) { return 5; }
+uint32_t dvt_abi_version(void) { return 6; }
 
 int dvt_prover_create(const char *cfg_json, dvt_prover **out) {
     if (!out) return fail(nullptr, DVT_ERR_INPUT, "out == NULL");
@@ -421,13 +479,6 @@ int dvt_stage_fri_fold(dvt_prover *p, const uint32_t *d_v, uint32_t *d_out, cons
     return DVT_OK;
 }
 
-// device scratch of a stage entry point from the handle's buffer cache, given back at scope exit (stream-ordered: the next
-// user of a cached buffer runs on the same stream)
-struct StageBuf {
-    DevPool &pool;
-    void *ptr = nullptr;
-    ~StageBuf() { pool.free(ptr); }
-};
 static bool overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
     const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
     return x < y + b_bytes && y < x + a_bytes;
@@ -637,6 +688,42 @@ int dvt_stage_quotient(dvt_prover *p, const char *machine, uint32_t chip, const 
         !e.quotient_chip(d, in, d.perm_ext_w ? d_perm_lde : nullptr, cs, d_alpha, d_alpha_f64, selectors == DVT_SELECTORS_TABLE, d_parts,
                          d_out))
         return engine_fail(p->err, e);
+    return DVT_OK;
+}
+
+// ---- the trace-row checks of one chip (check.cuh)
+int dvt_stage_check_constraints(dvt_prover *p, const char *machine, uint32_t chip, const uint32_t *d_main, const uint32_t *d_prep,
+                                uint32_t log_n, const uint32_t *pub, const uint32_t xi[4], uint32_t *counts, dvt_check_result *out) {
+    if (!p) return DVT_ERR_INPUT;
+    if (!xi || !out) return fail(p, DVT_ERR_INPUT, "null argument");
+    ChipStageArgs a;
+    CheckChallenges ch;
+    if (!ext_from_canonical(xi, &ch.xi)) return fail(p, DVT_ERR_INPUT, "xi not canonical");
+    // (the checks of machine, chip, log_n and pub that K4 / K5 make; xi stands in for the two challenges this call has not)
+    if (int rc = chip_stage_args(p, machine, chip, log_n, pub, xi, xi, DVT_PATH_DEFAULT, &a)) return rc;
+    if (!d_main || (a.d->prep_w && !d_prep)) return fail(p, DVT_ERR_INPUT, "null matrix");
+    ch.perm_alpha = ch.beta = Fp4::zero();
+    Guard g(p); if (g.rc) return g.rc;
+    std::vector<CheckTableOut> res;
+    if (int rc = check_tables(lane0(p), machine_by_name(machine), {{a.d, d_main, a.d->prep_w ? d_prep : nullptr, log_n}}, a.pub, ch, true, false, &res)) return rc;
+    if (counts) memcpy(counts, res[0].counts.data(), res[0].counts.size() * 4);
+    *out = res[0].r;
+    return DVT_OK;
+}
+
+int dvt_stage_bus_sums(dvt_prover *p, const char *machine, uint32_t chip, const uint32_t *d_main, const uint32_t *d_prep, uint32_t log_n,
+                       const uint32_t *pub, const uint32_t perm_alpha[4], const uint32_t beta[4], uint32_t out[DVT_CHECK_BUSES][4]) {
+    if (!p) return DVT_ERR_INPUT;
+    if (!out) return fail(p, DVT_ERR_INPUT, "null argument");
+    ChipStageArgs a;
+    if (int rc = chip_stage_args(p, machine, chip, log_n, pub, perm_alpha, beta, DVT_PATH_DEFAULT, &a)) return rc;
+    if (!d_main || (a.d->prep_w && !d_prep)) return fail(p, DVT_ERR_INPUT, "null matrix");
+    const CheckChallenges ch{Fp4::zero(), a.perm_alpha, a.beta};
+    Guard g(p); if (g.rc) return g.rc;
+    std::vector<CheckTableOut> res;
+    if (int rc = check_tables(lane0(p), machine_by_name(machine), {{a.d, d_main, a.d->prep_w ? d_prep : nullptr, log_n}}, a.pub, ch, false, true, &res)) return rc;
+    for (uint32_t b = 0; b < DVT_CHECK_BUSES; b++)
+        for (int k = 0; k < 4; k++) out[b][k] = res[0].bus[b].c[k].canonical();
     return DVT_OK;
 }
 

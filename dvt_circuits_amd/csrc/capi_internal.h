@@ -161,6 +161,34 @@ struct Lane {
 };
 inline Lane lane0(dvt_prover *p) { return {p, 0, p->eng, p->err}; }
 
+// device scratch of an entry point from a lane's buffer cache, given back at scope exit (stream-ordered: the next user of a
+// cached buffer runs on the same stream)
+struct StageBuf {
+    DevPool &pool;
+    void *ptr = nullptr;
+    ~StageBuf() { pool.free(ptr); }
+};
+
+// ---- the trace-row checks (check.cuh) of a list of chip tables that share their public values, on one lane:
+// dvt_stage_check_constraints, dvt_stage_bus_sums and dvt_rv32_check_job go through this.  One download, which
+// synchronises the lane's stream, for the whole list.
+struct CheckTable {
+    const ChipDesc *d;
+    const uint32_t *main, *prep;   // device, Montgomery, column-major (prep may be null when the chip has no such column)
+    uint32_t log_n;
+};
+struct CheckChallenges {
+    Fp4 xi;                 // where the closed-form big-integer identities are evaluated
+    Fp4 perm_alpha, beta;   // of the LogUp terms
+};
+struct CheckTableOut {
+    dvt_check_result r;
+    std::vector<uint32_t> counts;    // [n_constraints] rows violating each unit (with want_counts)
+    Fp4 bus[DVT_CHECK_BUSES];        // the table's signed LogUp terms summed over its rows, by bus id
+};
+int check_tables(const Lane &c, const MachineDesc *m, const std::vector<CheckTable> &tabs, const std::vector<uint32_t> &pub_mont,
+                 const CheckChallenges &ch, bool constraints, bool buses, std::vector<CheckTableOut> *out);
+
 // a library-allocated copy of w (release with dvt_free); *len = its bytes
 inline uint8_t *copy_out(const std::vector<uint32_t> &w, size_t *len) {
     uint8_t *b = (uint8_t *)malloc(w.size() * 4 + 1);

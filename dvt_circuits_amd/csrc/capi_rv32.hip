@@ -972,6 +972,26 @@ static int job_prove(dvt_prover *p, const dvt_pk *pk, dvt_job *j, uint8_t **proo
     return DVT_OK;
 }
 
+// The receiving side of the COMMIT rows' sys-bus tuples, from the claimed public-value bytes: an SP1 guest commits
+// the eight words of SHA-256(public-value bytes) with COMMIT(k, word k); the cpu chip sends
+// (t0 bytes = 0x10 0 0 0, a0 bytes = k 0 0 0, a1 bytes = the bytes of digest word k, 0, 0), tuple k contributes
+// 1 / (alpha + bus + beta 0x10 + beta^5 k + beta^9 b0 + ... + beta^12 b3).  What the LogUp sums of all chips and shards
+// must add up to (the verifier), and the sys bus alone (the job check).
+static Fp4 commit_digest_term(const PermChallenges &gc, const std::vector<uint8_t> &public_values) {
+    uint8_t dg[32];
+    sha256(public_values.data(), public_values.size(), dg);
+    Fp4 bp[13];
+    bp[1] = gc.beta;
+    for (int k = 2; k < 13; k++) bp[k] = bp[k - 1] * gc.beta;
+    Fp4 expect = Fp4::zero();
+    for (uint32_t k = 0; k < 8; k++) {
+        Fp4 d = gc.alpha + Fp::from_canonical(PV_BUS) + bp[1] * Fp::from_canonical(rv32::SYS_COMMIT) + bp[5] * Fp::from_canonical(k);
+        for (int b = 0; b < 4; b++) d += bp[9 + b] * Fp::from_canonical(dg[4 * k + b]);
+        expect += inv(d);
+    }
+    return expect;
+}
+
 // The rv32 checks of a parsed container: shard chaining through the public values, the chip set of every shard, each
 // shard's proof under the common challenges, and the COMMIT-digest balance.  "" or why the proof is rejected.
 static std::string verify_core(const VerifyingKey &key, const CoreProof &cp, const StarkConfig &cfg) {
@@ -1018,23 +1038,96 @@ static std::string verify_core(const VerifyingKey &key, const CoreProof &cp, con
         if (!why.empty()) return "shard " + std::to_string(i + 1) + ": " + why;
         total += t;
     }
-    // The receiving side of the COMMIT rows' sys-bus tuples is supplied here, from the claimed bytes: an SP1 guest commits
-    // the eight words of SHA-256(public-value bytes) with COMMIT(k, word k); the cpu chip sends
-    // (t0 bytes = 0x10 0 0 0, a0 bytes = k 0 0 0, a1 bytes = the bytes of digest word k, 0, 0), tuple k contributes
-    // 1 / (alpha + bus + beta 0x10 + beta^5 k + beta^9 b0 + ... + beta^12 b3).
-    uint8_t dg[32];
-    sha256(cp.public_values.data(), cp.public_values.size(), dg);
-    Fp4 bp[13];
-    bp[1] = gc.beta;
-    for (int k = 2; k < 13; k++) bp[k] = bp[k - 1] * gc.beta;
-    Fp4 expect = Fp4::zero();
-    for (uint32_t k = 0; k < 8; k++) {
-        Fp4 d = gc.alpha + Fp::from_canonical(PV_BUS) + bp[1] * Fp::from_canonical(rv32::SYS_COMMIT) + bp[5] * Fp::from_canonical(k);
-        for (int b = 0; b < 4; b++) d += bp[9 + b] * Fp::from_canonical(dg[4 * k + b]);
-        expect += inv(d);
-    }
+    const Fp4 expect = commit_digest_term(gc, cp.public_values);
     if (total != expect) return "LogUp cumulative sums do not cancel across the shards (memory bus or public-values digest)";
     return "";
+}
+
+// ------------------------------------------------------------------ the job check (dvt_rv32_check_job)
+// The point of the closed-form identities and the LogUp challenges of a check: a transcript over a domain tag, the key, the
+// job's public-value bytes and its shard count.  Not the headers: the check needs no phase 1 (and is no soundness boundary).
+static CheckChallenges check_challenges(const VerifyingKey &vk, const dvt_job *j) {
+    Challenger g;
+    for (const char *t = "dvt-check-rows-1"; *t; t++) g.observe_u32((uint8_t)*t);
+    g.observe(vk.prep_root);
+    g.observe_u32((uint32_t)vk.extra.size());
+    for (auto x : vk.extra) g.observe_u32(x);
+    g.observe_u32((uint32_t)j->public_values.size());
+    for (auto b : j->public_values) g.observe_u32(b);
+    g.observe_u32((uint32_t)j->n_total);
+    CheckChallenges c;
+    c.xi = g.sample_ext();
+    c.perm_alpha = g.sample_ext();
+    c.beta = g.sample_ext();
+    return c;
+}
+
+// the tables of one shard on the member that holds it (its device is current): findings and the shard's per-bus sums
+static int shard_check(dvt_prover *mem, const dvt_pk *key, dvt_job *part, ShardJob &s, size_t pos, const CheckChallenges &ch,
+                       std::vector<dvt_check_finding> *findings, Fp4 bus[DVT_CHECK_BUSES]) {
+    const MachineDesc *m = machine_rv32();
+    std::vector<ChipTrace> traces;
+    const bool kept = s.traces_valid;
+    const int rc = shard_traces(lane0(mem), key, part, s, &traces, true);
+    s.traces_valid = kept;   // (K0 into a kept buffer whose content had been consumed: the job stays as it was found)
+    if (rc) return rc;
+    std::vector<CheckTable> tabs;
+    for (auto &t : traces) {
+        const ChipDesc &d = m->chips[t.chip_id];
+        const uint32_t *prep = nullptr;
+        for (auto &pr : key->key.prep)
+            if (pr.chip_id == t.chip_id && pr.log_n == t.log_n) prep = pr.d_trace;
+        if (d.prep_w && !prep) return fail(mem, DVT_ERR_INPUT, "chip %s of shard %zu has no preprocessed trace of its height in the proving key", d.name, pos);
+        tabs.push_back({&d, t.d_main, prep, t.log_n});
+    }
+    std::vector<uint32_t> pub;
+    for (auto x : s.pubs) pub.push_back(x.v);
+    std::vector<CheckTableOut> res;
+    if (int rc2 = check_tables(lane0(mem), m, tabs, pub, ch, true, true, &res)) return rc2;
+    for (size_t i = 0; i < tabs.size(); i++) {
+        if (res[i].r.violations) findings->push_back({(uint32_t)pos, (uint32_t)traces[i].chip_id, tabs[i].log_n, res[i].r});
+        for (uint32_t b = 0; b < DVT_CHECK_BUSES; b++) bus[b] += res[i].bus[b];
+    }
+    return DVT_OK;
+}
+
+static int job_check(dvt_prover *p, const dvt_pk *pk, dvt_job *j, dvt_check_finding *findings, size_t cap, dvt_check_summary *summary) {
+    const size_t G = n_members(p);
+    if (pk->peers.size() + 1 != G || (G > 1 && j->parts.size() != G) || (G == 1 && !j->parts.empty()))
+        return fail(p, DVT_ERR_INPUT, "proving key or job of a handle with other devices");
+    const auto t0 = Clock::now();
+    const CheckChallenges ch = check_challenges(pk->key.vk, j);
+    std::vector<dvt_check_finding> all;
+    Fp4 bus[DVT_CHECK_BUSES];
+    for (auto &b : bus) b = Fp4::zero();
+    int rc = DVT_OK;
+    for (size_t m = 0; m < G && !rc; m++) {
+        dvt_prover *mem = member(p, m);
+        dvt_job *part = j->part(m);
+        if (G > 1) rc = select_member(p, m);
+        for (size_t k = 0; k < part->shards.size() && !rc; k++)
+            rc = lift(p, mem, shard_check(mem, member_key(pk, m), part, part->shards[k], part->first + k * part->stride, ch, &all, bus));
+    }
+    if (G > 1 && select_member(p, 0) && !rc) rc = DVT_ERR_DEVICE;
+    if (rc) return rc;
+    std::sort(all.begin(), all.end(), [](const dvt_check_finding &a, const dvt_check_finding &b) { return a.shard != b.shard ? a.shard < b.shard : a.chip < b.chip; });
+    *summary = dvt_check_summary{};
+    for (auto &f : all) summary->violations += f.r.violations;
+    summary->n_findings = (uint32_t)all.size();
+    for (size_t i = 0; i < all.size() && i < cap; i++) findings[i] = all[i];
+    if (j->held() == j->n_total) {
+        summary->bus_checked = 1;
+        const Fp4 sys = commit_digest_term(PermChallenges{ch.perm_alpha, ch.beta}, j->public_values);
+        for (uint32_t b = 0; b < DVT_CHECK_BUSES; b++)
+            if (bus[b] != (b == PV_BUS ? sys : Fp4::zero())) summary->unbalanced_buses |= 1u << b;
+    }
+    summary->ms = (float)ms_since(t0);
+    if (!all.empty())
+        return fail(p, DVT_ERR_REJECTED, "shard %u, chip %s: row %u violates constraint %d (%llu violations in %u chip tables)", all[0].shard,
+                    machine_rv32()->chips[all[0].chip].name, all[0].r.first_row, all[0].r.first_constraint, (unsigned long long)summary->violations,
+                    summary->n_findings);
+    if (summary->unbalanced_buses) return fail(p, DVT_ERR_REJECTED, "the LogUp sums of the job do not balance (bus mask 0x%x)", summary->unbalanced_buses);
+    return DVT_OK;
 }
 
 static std::vector<uint32_t> trace_blob(const rv32::HostTraces &T, const rv32::HostPrep *prep) {
@@ -1168,7 +1261,21 @@ uint32_t dvt_rv32_job_shard_device_rows(const dvt_job *job, size_t shard) {
     dvt_job *part = job ? const_cast<dvt_job *>(job)->part_at(shard, &m) : nullptr;
     return part ? part->at(shard)->device_rows : 0;
 }
+uint32_t dvt_rv32_job_shard_chips(const dvt_job *job, size_t shard) {
+    size_t m = 0;
+    dvt_job *part = job ? const_cast<dvt_job *>(job)->part_at(shard, &m) : nullptr;
+    uint32_t mask = 0;
+    for (int c = 0; part && c < rv32::N_CHIPS; c++) mask |= (uint32_t)part->at(shard)->present[c] << c;
+    return mask;
+}
 double dvt_rv32_job_exec_wait_seconds(const dvt_job *job) { return job ? job->t_exec_wait : 0.0; }
+
+int dvt_rv32_check_job(dvt_prover *p, const dvt_pk *pk, dvt_job *job, dvt_check_finding *findings, size_t cap, dvt_check_summary *summary) {
+    if (!p || !pk || !job || !summary || (cap && !findings)) return fail(p, DVT_ERR_INPUT, "null argument");
+    if (!pk->is_rv32) return fail(p, DVT_ERR_INPUT, "proving key was not made by dvt_setup");
+    Guard g(p); if (g.rc) return g.rc;
+    return job_check(p, pk, job, findings, cap, summary);
+}
 
 int dvt_rv32_commit_shard(dvt_prover *p, const dvt_pk *pk, dvt_job *job, size_t shard, uint32_t *header) {
     if (!p || !pk || !job || !header) return fail(p, DVT_ERR_INPUT, "bad argument");

@@ -3,6 +3,7 @@
 //   dvt_prover_host prove   --type T -i INPUT.json [-o PROOF] [--elf GUEST.elf] [--devices D0,D1,...]
 //   dvt_prover_host execute --type T -i INPUT.json [--show-report] [--elf GUEST.elf]
 //   dvt_prover_host verify  --type T -i PROOF [--elf GUEST.elf]
+//   dvt_prover_host check   --type T -i INPUT.json [--elf GUEST.elf] [--devices D0,D1,...]
 //
 // T = bad-share | finalization | bad-partial-key | bad-encrypted-share (clap names of CircuitType, :36-42).
 // The reference embeds the four guest ELFs at build time (include_elf!, :115-118); they cannot be built in
@@ -13,6 +14,9 @@
 // (the reference's own verify sub-command re-executes the guest instead).
 // --devices (prove only) spreads the shards of the execution over those GPUs (an index may repeat): the "devices" key of
 // dvt_prover_create.
+// check (no counterpart in the reference; SP1's debug_constraints) prepares the job as prove does and checks its trace rows
+// against the AIR on the GPU (dvt_rv32_check_job) instead of proving: "clean: N shards, M chip tables, T ms" and exit code 0,
+// or one line per finding and per unbalanced bus and exit code 1.
 // get-schema / validate-schema / node are product UI outside the accelerated path and are not provided.
 #include <cstdio>
 #include <cstdlib>
@@ -36,7 +40,7 @@ static int die(const std::string &m) {
 }
 
 int main(int argc, char **argv) {
-    if (argc < 2) return die("usage: dvt_prover_host prove|execute|verify --type T -i FILE [-o FILE] [--show-report] [--elf FILE] [--devices D0,D1,...]");
+    if (argc < 2) return die("usage: dvt_prover_host prove|execute|verify|check --type T -i FILE [-o FILE] [--show-report] [--elf FILE] [--devices D0,D1,...]");
     const std::string verb = argv[1];
     std::string type, input, output, elf_path, schema_path, devices;
     bool show_report = false, auth = false;
@@ -58,7 +62,7 @@ int main(int argc, char **argv) {
         else if (a == "--json-schema-file") schema_path = next();
         else return die("unknown argument " + a);
     }
-    if (verb != "prove" && verb != "execute" && verb != "verify") return die("unknown sub-command " + verb);
+    if (verb != "prove" && verb != "execute" && verb != "verify" && verb != "check") return die("unknown sub-command " + verb);
     if (type.empty() || input.empty()) return die("--type and --input-file are required");
     if (elf_path.empty()) {
         const char *dir = getenv("DVT_ELF_DIR");
@@ -122,6 +126,29 @@ int main(int argc, char **argv) {
     if (dvt_prover_create(devices.empty() ? nullptr : cfg.c_str(), &p)) return die(dvt_last_error(nullptr));
     dvt_pk *pk = nullptr;
     if (dvt_setup(p, elf.data(), elf.size(), &pk, nullptr, nullptr)) return die(dvt_last_error(p));
+    if (verb == "check") {
+        dvt_job *job = nullptr;
+        dvt_report rep{};
+        if (dvt_rv32_prepare(p, pk, &buf, 1, &job, &rep)) return die(std::string("Preparing the job failed: ") + dvt_last_error(p));
+        std::vector<dvt_check_finding> found(256);
+        dvt_check_summary sum{};
+        const int rc = dvt_rv32_check_job(p, pk, job, found.data(), found.size(), &sum);
+        if (rc && rc != DVT_ERR_REJECTED) return die(std::string("Check failed: ") + dvt_last_error(p));
+        const size_t shards = dvt_rv32_job_shards(job);
+        size_t tables = 0;
+        for (size_t i = 0; i < shards; i++) tables += (size_t)__builtin_popcount(dvt_rv32_job_shard_chips(job, i));
+        if (rc == DVT_OK) printf("clean: %zu shards, %zu chip tables, %.2f ms\n", shards, tables, sum.ms);
+        for (size_t i = 0; i < sum.n_findings && i < found.size(); i++)
+            printf("shard %u chip %u (2^%u rows): %llu violations, first at row %u, constraint %d\n", found[i].shard, found[i].chip, found[i].log_n,
+                   (unsigned long long)found[i].r.violations, found[i].r.first_row, found[i].r.first_constraint);
+        if (sum.n_findings > found.size()) printf("... and %zu more chip tables with violations\n", sum.n_findings - found.size());
+        for (uint32_t b = 0; b < DVT_CHECK_BUSES; b++)
+            if (sum.unbalanced_buses >> b & 1) printf("bus %u: the LogUp sums over all chips and shards do not balance\n", b);
+        dvt_job_free(p, job);
+        dvt_pk_free(p, pk);
+        dvt_prover_destroy(p);
+        return rc ? 1 : 0;
+    }
     uint8_t *proof = nullptr;
     size_t proof_len = 0;
     dvt_report rep{};

@@ -2,6 +2,7 @@
 // verifier see it: widths, LogUp shape, and per-chip entry points instantiated
 // from the generated Air structs (gen/air_<machine>.inc).
 #pragma once
+#include "check.cuh"
 #include "stark.cuh"
 
 namespace dvt {
@@ -40,6 +41,10 @@ struct ChipDesc {
     hipError_t (*launch_perm)(hipStream_t, const PermArgs &);
     hipError_t (*launch_quotient)(hipStream_t, const QuotientArgs &);
     Fp4 (*verify_eval)(const VerifierAccess &, const VerifierPoint &);
+    // the trace-row checks (check.cuh): constraints on the trace rows, per-bus LogUp sums.  The rv32 chips get theirs from
+    // translation units of their own (check_rv32.hip, check_rv32_wide.hip).
+    hipError_t (*launch_check)(hipStream_t, const CheckArgs &) = nullptr;
+    hipError_t (*launch_bus)(hipStream_t, const BusArgs &) = nullptr;
 };
 
 struct MachineDesc {
@@ -113,6 +118,12 @@ constexpr ChipDesc make_chip_desc() {
     return ChipDesc{Air::NAME, Air::MAIN_W, Air::PREP_W, Air::N_PUB, Air::N_CONSTRAINTS, Air::N_INTERACTIONS,
                     Air::MAX_ARITY, PermShape<Air>::EXT_W, PermShape<Air>::N_FOLDED,
                     perm_parts_parallel<Air>(), quot_parts_parallel<Air>(), &launch_perm_t<Air>, &launch_quotient_t<Air>, &verify_eval_t<Air>};
+}
+template <class Air>
+ChipDesc with_check_fns(ChipDesc d) {
+    d.launch_check = &launch_check_t<Air>;
+    d.launch_bus = &launch_bus_t<Air>;
+    return d;
 }
 #endif
 

@@ -16,11 +16,16 @@
 // field / curve precompile chips with their part-parallel kernels in machine_rv32_wide.hip): one unit took seven minutes.
 namespace dvt {
 ChipDesc rv32_wide_chip_desc(int chip);   // machine_rv32_wide.hip
+// the trace-row checks of the chips (check.cuh), in two further units: check_rv32.hip, check_rv32_wide.hip
+void rv32_check_fns(int chip, ChipDesc *d);
+void rv32_wide_check_fns(int chip, ChipDesc *d);
 namespace {
 template <int I, class A>
 ChipDesc chip_desc_here() {
-    if constexpr (I < RV32_FIRST_WIDE_CHIP) return make_chip_desc<A>();
-    else return rv32_wide_chip_desc(I);
+    ChipDesc d;
+    if constexpr (I < RV32_FIRST_WIDE_CHIP) { d = make_chip_desc<A>(); rv32_check_fns(I, &d); }
+    else { d = rv32_wide_chip_desc(I); rv32_wide_check_fns(I, &d); }
+    return d;
 }
 }  // namespace
 #define DVT_X(i, A) chip_desc_here<i, A>(),

@@ -106,7 +106,8 @@ void dvt_prover_destroy(dvt_prover *p);
 const char *dvt_last_error(const dvt_prover *p);
 void dvt_free(void *ptr);
 /* ABI version of this header (4: "devices", dvt_prover_device_count, dvt_prover_device, dvt_rv32_job_shard_member;
- * 5: dvt_rv32_job_shard_device_rows) */
+ * 5: dvt_rv32_job_shard_device_rows; 6: dvt_stage_check_constraints, dvt_stage_bus_sums, dvt_rv32_check_job,
+ * dvt_rv32_job_shard_chips) */
 uint32_t dvt_abi_version(void);
 /* the handle's hipStream_t (for event timing by the caller) */
 void *dvt_stream(dvt_prover *p);
@@ -195,6 +196,35 @@ int dvt_stage_quotient(dvt_prover *p, const char *machine, uint32_t chip, const 
                        const uint32_t *d_perm_lde, uint32_t log_n, const uint32_t *pub, const uint32_t perm_alpha[4],
                        const uint32_t beta[4], const uint32_t alpha[4], const uint32_t cum[4], uint32_t path, uint32_t selectors,
                        uint32_t *d_out);
+
+/* Trace-row checks of one chip (SP1 users know the first as debug_constraints): do the rows of a trace satisfy the chip's
+ * AIR, and what do its LogUp terms add up to on each bus?  Both read the matrices dvt_stage_perm reads (d_main
+ * [main_w][2^log_n], d_prep [prep_w][2^log_n] or NULL when prep_w = 0; Montgomery words, column-major; the row after the
+ * last is row 0), evaluate the same generated AIR source as K4 / K5, and synchronise the stream.  log_n <= 22; a chip index
+ * out of range or a NULL d_main is DVT_ERR_INPUT.
+ * A constraint is checked on the rows where it is active (all rows, row 0, row n-1, every row but the last).  What is
+ * counted is a UNIT: a plain constraint under its index, or a whole big-integer identity (its K coefficient constraints)
+ * under the index of the FIRST of them: the library holds such an identity only in closed form, C(x) + (x - 256) W(x),
+ * and evaluates it at the point xi of F_p^4 the caller supplies (4 canonical words).  A row with a wrong coefficient is
+ * missed with probability at most K / p^4 over xi; the indices first + 1 .. first + K - 1 never fire.
+ * counts (host array of the chip's n_constraints words, or NULL): rows that violate each unit.  out->violations: their
+ * sum; out->first_row / first_constraint: the lowest violating row and the lowest violated unit of that row
+ * (first_constraint = -1, first_row = 0 without a violation).  A chip without constraints returns zeros. */
+#define DVT_CHECK_BUSES 8u
+typedef struct {
+    uint64_t violations;
+    uint32_t first_row;
+    int32_t first_constraint; /* -1: none */
+} dvt_check_result;
+int dvt_stage_check_constraints(dvt_prover *p, const char *machine, uint32_t chip, const uint32_t *d_main, const uint32_t *d_prep,
+                                uint32_t log_n, const uint32_t *pub, const uint32_t xi[4], uint32_t *counts, dvt_check_result *out);
+/* out[bus][4], canonical: the sum over the rows of the chip's signed LogUp terms +-mult / (perm_alpha + bus + sum_k
+ * beta^(k+1) v_k) on each bus (bus ids of the machine; rv32 has 6).  The sum over the buses is the cumulative sum
+ * dvt_stage_perm returns.  Field addition is exact: the result does not depend on the launch shape.  A chip without
+ * interactions returns zeros. */
+int dvt_stage_bus_sums(dvt_prover *p, const char *machine, uint32_t chip, const uint32_t *d_main, const uint32_t *d_prep,
+                       uint32_t log_n, const uint32_t *pub, const uint32_t perm_alpha[4], const uint32_t beta[4],
+                       uint32_t out[DVT_CHECK_BUSES][4]);
 
 /* ------------------------------------------------- machine-level entry points
  * A "machine" is a fixed list of chips (AIRs) compiled into the library:
@@ -313,12 +343,44 @@ int dvt_rv32_job_shard_member(const dvt_job *job, size_t shard);
  * 9..13 the field / curve precompile chips): bit c is set when the trace rows of chip c of shard `shard` (global position)
  * were built on the GPU from uploaded events, not uploaded as a table.  0 for a shard this job does not hold. */
 uint32_t dvt_rv32_job_shard_device_rows(const dvt_job *job, size_t shard);
+/* bit mask over the chip ids: the chip tables shard `shard` (global position) consists of.  0 for a shard this job does
+ * not hold. */
+uint32_t dvt_rv32_job_shard_chips(const dvt_job *job, size_t shard);
 int dvt_rv32_commit_shard(dvt_prover *p, const dvt_pk *pk, dvt_job *job, size_t shard, uint32_t *header);
 int dvt_rv32_challenges(const uint8_t *vk, size_t vk_len, const uint32_t *headers, size_t n_shards, uint32_t out[8]);
 int dvt_rv32_prove_shard(dvt_prover *p, const dvt_pk *pk, dvt_job *job, size_t shard, const uint32_t challenges[8],
                          uint8_t **proof, size_t *proof_len);
 int dvt_rv32_assemble(const dvt_job *job, const uint8_t *const *shard_proofs, const size_t *lens, size_t n_shards,
                       uint8_t **proof, size_t *proof_len);
+/* Check the trace rows of a prepared job against the AIR on the GPU, before (or instead of) proving: a wrong row otherwise
+ * shows up only as a proof that dvt_verify rejects.  For every shard the job holds, on the device member that holds it:
+ * the traces phase 1 kept in HBM are reused when they are valid, else K0 runs into the working buffers; every chip table
+ * is checked (dvt_stage_check_constraints) against its preprocessed trace from the proving key; the per-bus LogUp sums
+ * (dvt_stage_bus_sums) are accumulated.  The job is left as it was found (headers, phase-1 results and kept traces stay
+ * valid or invalid as they were): a dvt_rv32_prove_job after the check returns the bytes it would have returned without.
+ * Like every call on the handle it stops a running prove_shard pipeline first.
+ * The point xi and the LogUp challenges are drawn from a transcript over a domain tag, the verifying key, the job's
+ * public-value bytes and its shard count - NOT from the shard headers: the check works at any point of a job's life and
+ * needs no phase 1.  They do not depend on the rows, so this is a diagnostic for honest-but-buggy rows (a K0 or guest-
+ * restatement bug), not a soundness boundary: rows chosen after the challenges could pass it.
+ * Bus balance is evaluated only when the job holds every shard of the execution (otherwise bus_checked = 0): the sums over
+ * all chips and shards must vanish on every bus except the sys bus, which must equal the verifier's term for the
+ * COMMITted public-value digest.
+ * findings: one entry per (shard, chip) with violations, ordered by shard (global position), then chip; at most cap are
+ * written, summary->n_findings counts all.  summary->ms: wall-clock milliseconds of the call after the entry guard.
+ * Returns DVT_OK for a clean job; DVT_ERR_REJECTED when anything is violated or unbalanced, and dvt_last_error then names
+ * the first finding (shard, chip name, row, constraint index) or the unbalanced buses. */
+typedef struct {
+    uint32_t shard, chip, log_n;
+    dvt_check_result r;
+} dvt_check_finding;
+typedef struct {
+    uint64_t violations;
+    uint32_t n_findings, bus_checked, unbalanced_buses; /* bit b = bus b */
+    float ms;
+} dvt_check_summary;
+int dvt_rv32_check_job(dvt_prover *p, const dvt_pk *pk, dvt_job *job, dvt_check_finding *findings, size_t cap,
+                       dvt_check_summary *summary);
 /* test hook: run K0 on one shard of a prepared job and return the device-generated main traces
  * (canonical); blob layout as dvt_rv32_debug_traces with prep_width = 0. */
 int dvt_rv32_debug_device_traces(dvt_prover *p, const dvt_pk *pk, dvt_job *job, size_t shard, uint32_t **blob,
