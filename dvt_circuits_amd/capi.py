@@ -26,6 +26,11 @@ class HostTrace(C.Structure):
     _fields_ = [("chip_id", C.c_uint32), ("log_n", C.c_uint32), ("data", u32p)]
 
 
+class PathChain(C.Structure):
+    _fields_ = [("start", C.POINTER(C.c_uint32)), ("depth", C.c_uint32), ("leaf", C.c_uint32), ("siblings", C.POINTER(C.c_uint32)),
+                ("inject", C.POINTER(C.c_uint32)), ("inject_at", C.POINTER(C.c_uint8)), ("root", C.POINTER(C.c_uint32))]
+
+
 class DvtError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"dvt error {code}: {msg}")
@@ -94,6 +99,11 @@ def load():
     lib.dvt_pk_free.restype = None
     lib.dvt_machine_prove.argtypes = [vp, vp, C.POINTER(HostTrace), sz, u32p, sz, C.POINTER(u8p), C.POINTER(sz)]
     lib.dvt_machine_verify.argtypes = [C.c_char_p, sz, C.c_char_p, sz, u32, u32, C.POINTER(C.c_char_p)]
+    lib.dvt_prover_machine_verify.argtypes = [vp, C.c_char_p, sz, C.c_char_p, sz, u32, u32, C.POINTER(C.c_char_p)]
+    lib.dvt_prover_verify.argtypes = [vp, C.c_char_p, sz, C.c_char_p, sz, u32, u32, C.POINTER(C.c_int32), C.POINTER(u8p), C.POINTER(sz), C.POINTER(C.c_char_p)]
+    lib.dvt_prover_verify_times.argtypes = [vp, C.POINTER(C.c_double)]
+    lib.dvt_stage_sponge_rows.argtypes = [vp, u32p, u32p, sz, u32p]
+    lib.dvt_stage_verify_paths.argtypes = [vp, C.POINTER(PathChain), sz, u8p]
     lib.dvt_last_stage_ms.argtypes = [vp, C.POINTER(C.c_float)]
     lib.dvt_setup.argtypes = [vp, C.c_char_p, sz, C.POINTER(vp), C.POINTER(u8p), C.POINTER(sz)]
     lib.dvt_execute.argtypes = [C.c_char_p, sz, C.POINTER(Buf), sz, C.c_uint64, C.POINTER(u8p), C.POINTER(sz), C.POINTER(Report), C.POINTER(C.c_char_p)]
@@ -466,6 +476,72 @@ class Prover:
         return out
 
     # ---- machine level
+    def verify(self, vk: bytes, proof: bytes, fri_queries=100, pow_bits=16):
+        """capi.verify with the query part on this handle's GPU.  Returns (ok, exit_code, public_values, reason); a device
+        failure raises."""
+        lib = self.lib
+        ec, pv, n, why = C.c_int32(), u8p(), C.c_size_t(), C.c_char_p()
+        rc = lib.dvt_prover_verify(self.h, vk, len(vk), proof, len(proof), fri_queries, pow_bits, C.byref(ec), C.byref(pv), C.byref(n), C.byref(why))
+        out = C.string_at(pv, n.value) if pv else b""
+        if pv:
+            lib.dvt_free(C.cast(pv, C.c_void_p))
+        reason = _take_str(lib, why)
+        if rc == DVT_ERR_DEVICE:
+            self.check(rc)
+        return rc == DVT_OK, ec.value, out, reason
+
+    def machine_verify(self, vk: bytes, proof: bytes, fri_queries=100, pow_bits=16):
+        """capi.machine_verify with the query part on this handle's GPU.  Returns (ok, reason); a device failure raises."""
+        reason = C.c_char_p()
+        rc = self.lib.dvt_prover_machine_verify(self.h, vk, len(vk), proof, len(proof), fri_queries, pow_bits, C.byref(reason))
+        why = reason.value.decode() if reason.value else ""
+        if reason.value:
+            self.lib.dvt_free(C.cast(reason, C.c_void_p))
+        if rc == DVT_ERR_DEVICE:
+            self.check(rc)
+        return rc == DVT_OK, why
+
+    def verify_times(self):
+        """The last verify / machine_verify of this handle: milliseconds of the host part, flattening, uploads, kernels,
+        downloads and waiting, then permutations, launches and chunks."""
+        out = (C.c_double * 9)()
+        self.check(self.lib.dvt_prover_verify_times(self.h, out))
+        keys = ("host_ms", "flatten_ms", "upload_ms", "kernels_ms", "download_ms", "wait_ms", "permutations", "launches", "chunks")
+        return dict(zip(keys, [float(x) for x in out]))
+
+    def stage_sponge_rows(self, vectors):
+        """Digests [n][8] (canonical) of n canonical word vectors: the sponge kernel of the device verifier."""
+        lens = np.array([len(v) for v in vectors], np.uint32)
+        words = np.ascontiguousarray(np.concatenate([np.asarray(v, np.uint32) for v in vectors]) if len(vectors) else np.zeros(0, np.uint32))
+        out = np.zeros((len(vectors), 8), np.uint32)
+        self.check(self.lib.dvt_stage_sponge_rows(self.h, words.ctypes.data_as(u32p), lens.ctypes.data_as(u32p), len(vectors), out.ctypes.data_as(u32p)))
+        return out
+
+    def stage_verify_paths(self, chains):
+        """chains: dicts with start [8], depth, leaf, siblings [depth][8], root [8] and optionally inject [depth][8] with
+        inject_at [depth] (canonical words).  Returns the ok-bytes: the path kernel of the device verifier."""
+        arr = (PathChain * len(chains))()
+        keep = []
+
+        def ptr(a, dt, ct):
+            a = np.ascontiguousarray(np.asarray(a, dt).reshape(-1))
+            if a.size == 0:
+                a = np.zeros(1, dt)
+            keep.append(a)
+            return a.ctypes.data_as(C.POINTER(ct))
+
+        for i, c in enumerate(chains):
+            arr[i].start = ptr(c["start"], np.uint32, C.c_uint32)
+            arr[i].depth, arr[i].leaf = int(c["depth"]), int(c["leaf"])
+            arr[i].siblings = ptr(c["siblings"], np.uint32, C.c_uint32)
+            arr[i].root = ptr(c["root"], np.uint32, C.c_uint32)
+            if c.get("inject") is not None:
+                arr[i].inject = ptr(c["inject"], np.uint32, C.c_uint32)
+                arr[i].inject_at = ptr(c["inject_at"], np.uint8, C.c_uint8)
+        ok = np.zeros(len(chains), np.uint8)
+        self.check(self.lib.dvt_stage_verify_paths(self.h, arr, len(chains), ok.ctypes.data_as(u8p)))
+        return ok
+
     def machine_setup(self, machine: str, prep):
         arr, keep = _traces(prep)
         pk, vk, n = C.c_void_p(), u8p(), C.c_size_t()

@@ -5,7 +5,10 @@
 #include <cstdarg>
 #include <cstdio>
 
+#include <chrono>
+
 #include "capi_internal.h"
+#include "verify_query.h"
 
 using namespace dvt;
 
@@ -290,7 +293,7 @@ int check_tables(const Lane &c, const MachineDesc *m, const std::vector<CheckTab
 
 extern "C" {
 
-uint32_t dvt_abi_version(void) { return 6; }
+uint32_t dvt_abi_version(void) { return 7; }
 
 int dvt_prover_create(const char *cfg_json, dvt_prover **out) {
     if (!out) return fail(nullptr, DVT_ERR_INPUT, "out == NULL");
@@ -383,6 +386,7 @@ void dvt_prover_destroy(dvt_prover *p) {
     if (p->copy_stream) { (void)hipStreamSynchronize(p->copy_stream); (void)hipStreamDestroy(p->copy_stream); }
     for (auto b : p->pinned) (void)hipHostFree(b);
     if (p->aux_pinned) (void)hipHostFree(p->aux_pinned);
+    vq::stage_free(p->vq_stage);
     for (auto &e : p->more)
         if (e) e->shutdown();
     p->eng.shutdown();
@@ -814,6 +818,67 @@ int dvt_machine_verify(const uint8_t *vk, size_t vk_len, const uint8_t *proof, s
         else why = verify_shard(key, sp, StarkConfig{fri_queries, pow_bits});
         return why.empty() ? DVT_OK : DVT_ERR_REJECTED;
     });
+}
+
+int dvt_prover_machine_verify(dvt_prover *p, const uint8_t *vk, size_t vk_len, const uint8_t *proof, size_t proof_len,
+                              uint32_t fri_queries, uint32_t pow_bits, char **reason) {
+    if (reason) *reason = nullptr;
+    if (!p) return DVT_ERR_INPUT;
+    if (!vk || !proof) return reject(reason, DVT_ERR_INPUT, "null argument");
+    VerifyingKey key;
+    if (!vk_parse(vk, vk_len, &key)) return reject(reason, DVT_ERR_INPUT, "malformed verifying key");
+    Guard g(p); if (g.rc) return g.rc;
+    int dev_rc = DVT_OK;
+    const int rc = verify_words(proof, proof_len, DVT_ERR_INPUT, reason, [&](WordReader &r, std::string &why) {
+        const auto t0 = std::chrono::steady_clock::now();
+        const uint32_t *w0 = r.p;
+        const ShardProof sp = read_shard_proof(r);
+        if (r.p != r.end) why = "trailing bytes after proof";
+        else {
+            ShardQueryCtx ctx;
+            why = verify_shard_host(key, sp, StarkConfig{fri_queries, pow_bits}, nullptr, nullptr, &ctx);
+            if (why.empty()) {
+                DeviceQueries dq(p);
+                dq.add(ctx, w0, (size_t)(r.end - w0));
+                dq.finish(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+                if ((dev_rc = dq.rc)) return DVT_OK;
+                why = dq.why(0);
+            }
+        }
+        return why.empty() ? DVT_OK : DVT_ERR_REJECTED;
+    });
+    return dev_rc ? dev_rc : rc;
+}
+
+int dvt_prover_verify_times(dvt_prover *p, double out[9]) {
+    if (!p || !out) return DVT_ERR_INPUT;
+    std::lock_guard<std::mutex> lk(p->mu);
+    for (int i = 0; i < 9; i++) out[i] = p->vq_times[i];
+    return DVT_OK;
+}
+
+int dvt_stage_sponge_rows(dvt_prover *p, const uint32_t *words, const uint32_t *lens, size_t n, uint32_t *digests) {
+    if (!p) return DVT_ERR_INPUT;
+    if (!n) return DVT_OK;
+    if (!lens || !digests) return fail(p, DVT_ERR_INPUT, "null argument");
+    size_t total = 0;
+    for (size_t i = 0; i < n; i++) {
+        if (lens[i] > (1u << 24)) return fail(p, DVT_ERR_INPUT, "vector %zu is longer than 2^24 words", i);
+        total += lens[i];
+    }
+    if ((total && !words) || total + 8 * n >= ((size_t)1 << 31)) return fail(p, DVT_ERR_INPUT, "null or too many words");
+    Guard g(p); if (g.rc) return g.rc;
+    return vq::stage_sponge_rows(lane0(p), words, lens, n, digests);
+}
+
+int dvt_stage_verify_paths(dvt_prover *p, const dvt_path_chain *chains, size_t n, uint8_t *ok) {
+    if (!p) return DVT_ERR_INPUT;
+    if (!n) return DVT_OK;
+    if (!chains || !ok || n > (1u << 24)) return fail(p, DVT_ERR_INPUT, "null argument or too many chains");
+    for (size_t i = 0; i < n; i++)
+        if (!chains[i].start || !chains[i].root) return fail(p, DVT_ERR_INPUT, "chain %zu: null digest", i);
+    Guard g(p); if (g.rc) return g.rc;
+    return vq::stage_verify_paths(lane0(p), chains, n, ok);
 }
 
 int dvt_last_kernel_stats(dvt_prover *p, double out[9]) {

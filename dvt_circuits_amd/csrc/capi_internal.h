@@ -14,6 +14,7 @@
 #include "engine.h"
 #include "rv32.h"
 
+namespace dvt { namespace vq { struct Stage; void stage_free(Stage *); } }
 constexpr int MAX_LANES = 3;
 // Lanes that commit (phase 1) unless the handle's config says otherwise; capped at the handle's lanes, so every lane commits:
 // two lanes beat one by 2.2-3.8 % per call in every A/B pair (profiles/README.md, round 6).
@@ -90,6 +91,9 @@ struct dvt_prover {
     std::vector<std::unique_ptr<dvt_prover>> peers;
     dvt_prover *owner = nullptr;      // of a further member: the handle it belongs to
     bool shares_device = false;       // another member of the handle proves on the same physical device
+    // the device verifier's pinned staging and events (verify_query.hip), made by the first dvt_prover_verify; its last times
+    dvt::vq::Stage *vq_stage = nullptr;
+    double vq_times[9] = {};
     std::string err;
     std::mutex mu;
 };
@@ -214,4 +218,17 @@ inline int reject(char **reason, int code, const std::string &why) {
 // inside a try-block: a malformed proof throws, and its message is the reason.
 int verify_words(const uint8_t *proof, size_t len, int len_code, char **reason,
                  const std::function<int(WordReader &, std::string &)> &check);
+// The query part of the shards of one verify call on lane 0 of the handle (verify_query.hip), behind an interface the two
+// verify entry points share: add() after a shard's host part has passed, finish() once, then why() per shard.  A device
+// failure is kept in rc (its text in p->err) and makes every later call a no-op.
+struct DeviceQueries {
+    explicit DeviceQueries(dvt_prover *p);
+    ~DeviceQueries();
+    void add(const ShardQueryCtx &ctx, const uint32_t *words, size_t nwords);
+    void finish(double host_ms);
+    std::string why(size_t shard) const;
+    int rc = 0;
+    dvt_prover *p;
+    void *batch;
+};
 }  // namespace dvt

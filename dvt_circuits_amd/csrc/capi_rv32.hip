@@ -994,7 +994,10 @@ static Fp4 commit_digest_term(const PermChallenges &gc, const std::vector<uint8_
 
 // The rv32 checks of a parsed container: shard chaining through the public values, the chip set of every shard, each
 // shard's proof under the common challenges, and the COMMIT-digest balance.  "" or why the proof is rejected.
-static std::string verify_core(const VerifyingKey &key, const CoreProof &cp, const StarkConfig &cfg) {
+// With dev != nullptr the query part of the shards runs on the device: the host part of every shard in order up to the first
+// that fails it, then the first failure in the host's order (the queries of an earlier shard come before that host failure).
+static std::string verify_core(const VerifyingKey &key, const CoreProof &cp, const StarkConfig &cfg, DeviceQueries *dev = nullptr) {
+    const auto t0 = Clock::now();
     const size_t nshards = cp.shards.size();
     std::vector<ShardProof> sps(nshards);
     for (size_t i = 0; i < nshards; i++) {
@@ -1032,7 +1035,26 @@ static std::string verify_core(const VerifyingKey &key, const CoreProof &cp, con
     }
     PermChallenges gc = global_challenges(key, headers.data(), nshards);
     Fp4 total = Fp4::zero();
-    for (size_t i = 0; i < nshards; i++) {
+    if (dev) {
+        std::string host_why;
+        size_t added = 0;
+        for (; added < nshards && !dev->rc; added++) {
+            Fp4 t;
+            ShardQueryCtx ctx;
+            host_why = verify_shard_host(key, sps[added], cfg, &gc, &t, &ctx);
+            if (!host_why.empty()) break;
+            total += t;
+            dev->add(ctx, cp.shards[added].data(), cp.shards[added].size());
+        }
+        dev->finish(std::chrono::duration<double, std::milli>(Clock::now() - t0).count());
+        if (dev->rc) return "";
+        for (size_t i = 0; i < added; i++) {
+            const std::string why = dev->why(i);
+            if (!why.empty()) return "shard " + std::to_string(i + 1) + ": " + why;
+        }
+        if (!host_why.empty()) return "shard " + std::to_string(added + 1) + ": " + host_why;
+    }
+    for (size_t i = 0; !dev && i < nshards; i++) {
         Fp4 t;
         std::string why = verify_shard(key, sps[i], cfg, &gc, &t);
         if (!why.empty()) return "shard " + std::to_string(i + 1) + ": " + why;
@@ -1393,6 +1415,33 @@ int dvt_verify(const uint8_t *vk, size_t vk_len, const uint8_t *proof, size_t pr
         if (public_values) *public_values = dup_bytes(cp.public_values, pv_len);
         return DVT_OK;
     });
+}
+
+int dvt_prover_verify(dvt_prover *p, const uint8_t *vk, size_t vk_len, const uint8_t *proof, size_t proof_len, uint32_t fri_queries,
+                      uint32_t pow_bits, int32_t *exit_code, uint8_t **public_values, size_t *pv_len, char **reason) {
+    if (reason) *reason = nullptr;
+    if (public_values) *public_values = nullptr;
+    if (!p) return DVT_ERR_INPUT;
+    if (!vk || !proof) return reject(reason, DVT_ERR_INPUT, "null argument");
+    VerifyingKey key;
+    if (!vk_parse(vk, vk_len, &key) || key.machine != machine_rv32() || key.extra.size() != 1) return reject(reason, DVT_ERR_INPUT, "malformed verifying key");
+    Guard g(p); if (g.rc) return g.rc;
+    int dev_rc = DVT_OK;
+    const int rc = verify_words(proof, proof_len, DVT_ERR_REJECTED, reason, [&](WordReader &r, std::string &why) {
+        if (fri_queries == 0 || fri_queries > 1024 || pow_bits > 30) {
+            why = "fri_queries must be 1..1024 and pow_bits <= 30";
+            return DVT_ERR_INPUT;
+        }
+        const CoreProof cp = read_core_proof(r);
+        DeviceQueries dq(p);
+        why = verify_core(key, cp, StarkConfig{fri_queries, pow_bits}, &dq);
+        if ((dev_rc = dq.rc)) return DVT_OK;
+        if (!why.empty()) return DVT_ERR_REJECTED;
+        if (exit_code) *exit_code = (int32_t)cp.exit_code;
+        if (public_values) *public_values = dup_bytes(cp.public_values, pv_len);
+        return DVT_OK;
+    });
+    return dev_rc ? dev_rc : rc;
 }
 
 int dvt_rv32_debug_traces(const uint8_t *elf, size_t elf_len, const dvt_buf *stdin_bufs, size_t nbuf, uint32_t log_shard, uint32_t shard,

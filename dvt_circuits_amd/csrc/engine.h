@@ -54,6 +54,32 @@ struct PermChallenges {
 std::string verify_shard(const VerifyingKey &vk, const ShardProof &proof, const StarkConfig &cfg,
                          const PermChallenges *global = nullptr, Fp4 *cumsum_total = nullptr);
 
+// The two parts of verify_shard.  The host part (shape checks, transcript, constraint check at zeta, FRI challenges, PoW,
+// query indices) leaves what the query part needs in a ShardQueryCtx, which refers to the key and the proof it was made
+// from; the query part is verify_query_host per query (dvt_verify) or the device path (verify_query.hip).
+struct TreeShape {
+    std::vector<std::pair<uint32_t, uint32_t>> mats;  // (width, log_h) in tree order
+    uint32_t log_h = 0;
+};
+struct ShardQueryCtx {
+    const VerifyingKey *vk = nullptr;
+    const ShardProof *pf = nullptr;
+    uint32_t hmax = 0;
+    Fp4 zeta;
+    std::vector<Fp4> fold_betas, apow;               // per FRI layer; alpha_fri^0 .. alpha_fri^max_cols
+    TreeShape shapes[4];
+    const Digest *roots[4] = {};
+    std::vector<std::vector<ColRef>> cols_by_h;      // [h] for h = 1 .. hmax
+    std::vector<uint32_t> n_two_by_h;
+    std::vector<uint32_t> idx;                       // the query indices (hmax bits each)
+};
+std::string verify_shard_host(const VerifyingKey &vk, const ShardProof &proof, const StarkConfig &cfg, const PermChallenges *global,
+                              Fp4 *cumsum_total, ShardQueryCtx *ctx);
+// "" or the first failure of query qi in step order (tree 0..3, layer count, each layer's opening, final value)
+std::string verify_query_host(const ShardQueryCtx &ctx, uint32_t qi);
+// whether query qi's section passes every shape check (row counts and widths, path lengths, layer count, empty trees)
+bool query_shape_ok(const ShardQueryCtx &ctx, uint32_t qi);
+
 #if defined(__HIPCC__)
 struct Arena {
     char *base = nullptr;

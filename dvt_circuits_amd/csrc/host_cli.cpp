@@ -40,9 +40,9 @@ static int die(const std::string &m) {
 }
 
 int main(int argc, char **argv) {
-    if (argc < 2) return die("usage: dvt_prover_host prove|execute|verify|check --type T -i FILE [-o FILE] [--show-report] [--elf FILE] [--devices D0,D1,...]");
+    if (argc < 2) return die("usage: dvt_prover_host prove|execute|verify|check --type T -i FILE [-o FILE] [--show-report] [--elf FILE] [--devices D0,D1,...] [--device D]");
     const std::string verb = argv[1];
-    std::string type, input, output, elf_path, schema_path, devices;
+    std::string type, input, output, elf_path, schema_path, devices, verify_device;
     bool show_report = false, auth = false;
     for (int i = 2; i < argc; i++) {
         std::string a = argv[i], inline_val;
@@ -57,6 +57,7 @@ int main(int argc, char **argv) {
         else if (a == "-o" || a == "--output-file-path") output = next();
         else if (a == "--elf") elf_path = next();
         else if (a == "--devices") devices = next();
+        else if (a == "--device") verify_device = next();   // verify: the query part on that GPU (dvt_prover_verify)
         else if (a == "--show-report") show_report = true;
         else if (a == "--auth-commitment") auth = true;  // the reference selects this at build time (cargo feature)
         else if (a == "--json-schema-file") schema_path = next();
@@ -92,14 +93,17 @@ int main(int argc, char **argv) {
 
     if (verb == "verify") {
         dvt_prover *p = nullptr;
-        if (dvt_prover_create(nullptr, &p)) return die(dvt_last_error(nullptr));
+        const std::string vcfg = "{\"device\": " + std::to_string(atoi(verify_device.c_str())) + "}";
+        if (dvt_prover_create(verify_device.empty() ? nullptr : vcfg.c_str(), &p)) return die(dvt_last_error(nullptr));
         dvt_pk *pk = nullptr;
         uint8_t *vk = nullptr;
         size_t vk_len = 0;
         if (dvt_setup(p, elf.data(), elf.size(), &pk, &vk, &vk_len)) return die(dvt_last_error(p));
         char *why = nullptr;
         int32_t ec = 0;
-        int rc = dvt_verify(vk, vk_len, in.data(), in.size(), 100, 16, &ec, nullptr, nullptr, &why);
+        int rc = verify_device.empty() ? dvt_verify(vk, vk_len, in.data(), in.size(), 100, 16, &ec, nullptr, nullptr, &why)
+                                       : dvt_prover_verify(p, vk, vk_len, in.data(), in.size(), 100, 16, &ec, nullptr, nullptr, &why);
+        if (rc == DVT_ERR_DEVICE) return die(dvt_last_error(p));
         if (rc) return die(std::string("Verification failed: ") + (why ? why : "?"));
         printf("Proof verified (guest exit code %d)\n", ec);
         return 0;

@@ -16,11 +16,6 @@ Digest hash_rows(const std::vector<const std::vector<Fp> *> &rows) {
     return sp.finish();
 }
 
-struct TreeShape {
-    std::vector<std::pair<uint32_t, uint32_t>> mats;  // (width, log_h) in tree order
-    uint32_t log_h = 0;
-};
-
 bool verify_tree_opening(const TreeShape &shape, const TreeOpening &op, uint32_t idx, const Digest &root) {
     if (op.rows.size() != shape.mats.size() || op.path.size() != shape.log_h) return false;
     for (size_t i = 0; i < shape.mats.size(); i++)
@@ -67,8 +62,9 @@ Fp4 ext_from_flat(const Fp4 *p) {  // sum_k x^k * p[k]
 
 }  // namespace
 
-std::string verify_shard(const VerifyingKey &vk, const ShardProof &pf, const StarkConfig &cfg, const PermChallenges *global,
-                         Fp4 *cumsum_total) {
+// ---- the host part: everything up to the query indices
+std::string verify_shard_host(const VerifyingKey &vk, const ShardProof &pf, const StarkConfig &cfg, const PermChallenges *global,
+                              Fp4 *cumsum_total, ShardQueryCtx *ctx) {
     const MachineDesc *m = vk.machine;
     if (!m) return "no machine";
     if (pf.chips.empty()) return "no chips";
@@ -173,7 +169,8 @@ std::string verify_shard(const VerifyingKey &vk, const ShardProof &pf, const Sta
 
     // ---- FRI
     Fp4 alpha_fri = ch.sample_ext();
-    std::vector<Fp4> fold_betas;
+    std::vector<Fp4> &fold_betas = ctx->fold_betas;
+    fold_betas.clear();
     for (auto &r : pf.fri_roots) {
         ch.observe(r);
         fold_betas.push_back(ch.sample_ext());
@@ -181,7 +178,8 @@ std::string verify_shard(const VerifyingKey &vk, const ShardProof &pf, const Sta
     ch.observe(pf.final_poly);
     if (!ch.check_witness(cfg.pow_bits, pf.pow_witness)) return "proof-of-work witness rejected";
 
-    TreeShape shapes[4];
+    TreeShape *shapes = ctx->shapes;
+    for (int t = 0; t < 4; t++) shapes[t] = TreeShape{};
     for (auto &r : refs) {
         const ChipDesc &d = m->chips[r.chip_id];
         if (d.prep_w) shapes[0].mats.push_back({(uint32_t)d.prep_w, r.log_n + 1});
@@ -189,24 +187,46 @@ std::string verify_shard(const VerifyingKey &vk, const ShardProof &pf, const Sta
         if (d.perm_ext_w) shapes[2].mats.push_back({(uint32_t)(4 * d.perm_ext_w), r.log_n + 1});
         shapes[3].mats.push_back({8u, r.log_n + 1});
     }
-    for (auto &sh : shapes)
-        for (auto &mt : sh.mats) sh.log_h = std::max(sh.log_h, mt.second);
-    const Digest *roots[4] = {&vk.prep_root, &pf.main_root, &pf.perm_root, &pf.quot_root};
+    for (int t = 0; t < 4; t++)
+        for (auto &mt : shapes[t].mats) shapes[t].log_h = std::max(shapes[t].log_h, mt.second);
+    ctx->vk = &vk;
+    ctx->pf = &pf;
+    ctx->hmax = hmax;
+    ctx->zeta = zeta;
+    ctx->roots[0] = &vk.prep_root; ctx->roots[1] = &pf.main_root; ctx->roots[2] = &pf.perm_root; ctx->roots[3] = &pf.quot_root;
 
-    std::vector<std::vector<ColRef>> cols_by_h(hmax + 1);
-    std::vector<uint32_t> n_two_by_h(hmax + 1, 0);
+    std::vector<std::vector<ColRef>> &cols_by_h = ctx->cols_by_h;
+    std::vector<uint32_t> &n_two_by_h = ctx->n_two_by_h;
+    cols_by_h.assign(hmax + 1, {});
+    n_two_by_h.assign(hmax + 1, 0);
     size_t max_cols = 1;
     for (uint32_t h = 1; h <= hmax; h++) {
         cols_by_h[h] = fri_columns(m, refs, h, &n_two_by_h[h]);
         max_cols = std::max(max_cols, cols_by_h[h].size());
     }
-    std::vector<Fp4> apow(max_cols + 1);
-    { Fp4 x = Fp4::one(); for (auto &a : apow) { a = x; x = x * alpha_fri; } }
-    const Fp inv2 = inv(Fp::two());
+    ctx->apow.assign(max_cols + 1, Fp4::zero());
+    { Fp4 x = Fp4::one(); for (auto &a : ctx->apow) { a = x; x = x * alpha_fri; } }
+    // the query indices depend on nothing a query opens: all of them are drawn here
+    ctx->idx.resize(cfg.num_queries);
+    for (auto &i : ctx->idx) i = ch.sample_bits(hmax);
+    return "";
+}
 
-    for (uint32_t qi = 0; qi < cfg.num_queries; qi++) {
+// ---- the query part on the host: query qi of the shard whose host part left ctx
+std::string verify_query_host(const ShardQueryCtx &ctx, uint32_t qi) {
+    const ShardProof &pf = *ctx.pf;
+    const TreeShape *shapes = ctx.shapes;
+    const Digest *const *roots = ctx.roots;
+    const std::vector<std::vector<ColRef>> &cols_by_h = ctx.cols_by_h;
+    const std::vector<uint32_t> &n_two_by_h = ctx.n_two_by_h;
+    const std::vector<Fp4> &apow = ctx.apow, &fold_betas = ctx.fold_betas;
+    const uint32_t hmax = ctx.hmax;
+    const Fp4 zeta = ctx.zeta;
+    const Fp g = Fp::from_canonical(COSET_SHIFT);
+    const Fp inv2 = inv(Fp::two());
+    {
         const QueryProof &q = pf.queries[qi];
-        const uint32_t idx = ch.sample_bits(hmax);
+        const uint32_t idx = ctx.idx[qi];
         for (int t = 0; t < 4; t++) {
             if (shapes[t].mats.empty()) {
                 if (!q.trees[t].rows.empty() || !q.trees[t].path.empty()) return "unexpected opening for an empty tree";
@@ -252,6 +272,34 @@ std::string verify_shard(const VerifyingKey &vk, const ShardProof &pf, const Sta
         if (e != pf.final_poly) return "FRI final value mismatch";
     }
     return "";
+}
+
+std::string verify_shard(const VerifyingKey &vk, const ShardProof &pf, const StarkConfig &cfg, const PermChallenges *global,
+                         Fp4 *cumsum_total) {
+    ShardQueryCtx ctx;
+    std::string why = verify_shard_host(vk, pf, cfg, global, cumsum_total, &ctx);
+    for (uint32_t qi = 0; why.empty() && qi < cfg.num_queries; qi++) why = verify_query_host(ctx, qi);
+    return why;
+}
+
+// every shape check of query qi's section (what verify_query_host refuses before or while it hashes)
+bool query_shape_ok(const ShardQueryCtx &ctx, uint32_t qi) {
+    const QueryProof &q = ctx.pf->queries[qi];
+    for (int t = 0; t < 4; t++) {
+        const TreeShape &sh = ctx.shapes[t];
+        const TreeOpening &op = q.trees[t];
+        if (sh.mats.empty()) {
+            if (!op.rows.empty() || !op.path.empty()) return false;
+            continue;
+        }
+        if (op.rows.size() != sh.mats.size() || op.path.size() != sh.log_h) return false;
+        for (size_t i = 0; i < sh.mats.size(); i++)
+            if (op.rows[i].size() != sh.mats[i].first) return false;
+    }
+    if (q.layers.size() != ctx.hmax - 1) return false;
+    for (uint32_t k = 0; k + 1 < ctx.hmax; k++)
+        if (q.layers[k].path.size() != ctx.hmax - k - 1) return false;
+    return true;
 }
 
 }  // namespace dvt

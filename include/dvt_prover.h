@@ -107,7 +107,8 @@ const char *dvt_last_error(const dvt_prover *p);
 void dvt_free(void *ptr);
 /* ABI version of this header (4: "devices", dvt_prover_device_count, dvt_prover_device, dvt_rv32_job_shard_member;
  * 5: dvt_rv32_job_shard_device_rows; 6: dvt_stage_check_constraints, dvt_stage_bus_sums, dvt_rv32_check_job,
- * dvt_rv32_job_shard_chips) */
+ * dvt_rv32_job_shard_chips; 7: dvt_prover_verify, dvt_prover_machine_verify, dvt_stage_sponge_rows,
+ * dvt_stage_verify_paths, dvt_prover_verify_times) */
 uint32_t dvt_abi_version(void);
 /* the handle's hipStream_t (for event timing by the caller) */
 void *dvt_stream(dvt_prover *p);
@@ -226,6 +227,26 @@ int dvt_stage_bus_sums(dvt_prover *p, const char *machine, uint32_t chip, const 
                        uint32_t log_n, const uint32_t *pub, const uint32_t perm_alpha[4], const uint32_t beta[4],
                        uint32_t out[DVT_CHECK_BUSES][4]);
 
+/* The two hashing kernels of the device verifier (dvt_prover_verify), driven at chosen shapes without a proof.  Both
+ * take and return HOST arrays of canonical words (a word >= p is DVT_ERR_INPUT) and are synchronous.
+ * dvt_stage_sponge_rows: n word vectors, concatenated in `words`, of lens[i] words each -> digests [n][8]: the sponge of
+ * every vector (rate 8, overwrite mode, the ragged last block keeps the state words it does not overwrite). */
+int dvt_stage_sponge_rows(dvt_prover *p, const uint32_t *words, const uint32_t *lens, size_t n, uint32_t *digests);
+/* dvt_stage_verify_paths: n Merkle chains -> ok[n] (1: the chain ends in its root).  A chain starts from `start` at leaf
+ * `leaf` (taken modulo 2^depth) of a tree of 2^depth leaves, natural-order pairing (the node on the left while the index
+ * is below half the level's width); siblings [depth][8] from the leaf level upwards; with inject != NULL, after the level
+ * l at which inject_at[l] != 0 the node is compressed once more with inject[l] ([depth][8]: the row digest of the shorter
+ * matrices that join there).  depth = 0 compares `start` with `root`. */
+typedef struct {
+    const uint32_t *start;    /* [8] */
+    uint32_t depth, leaf;
+    const uint32_t *siblings; /* [depth][8] */
+    const uint32_t *inject;   /* [depth][8] or NULL */
+    const uint8_t *inject_at; /* [depth], with inject */
+    const uint32_t *root;     /* [8] */
+} dvt_path_chain;
+int dvt_stage_verify_paths(dvt_prover *p, const dvt_path_chain *chains, size_t n, uint8_t *ok);
+
 /* ------------------------------------------------- machine-level entry points
  * A "machine" is a fixed list of chips (AIRs) compiled into the library:
  * "toy" (engine unit tests) and "rv32" (the RISC-V core machine).  Traces are
@@ -245,6 +266,11 @@ int dvt_machine_prove(dvt_prover *p, const dvt_pk *pk, const dvt_host_trace *mai
 /* host-only; DVT_ERR_REJECTED + reason in *reason (release with dvt_free) when the proof is bad */
 int dvt_machine_verify(const uint8_t *vk, size_t vk_len, const uint8_t *proof, size_t proof_len,
                        uint32_t fri_queries, uint32_t pow_bits, char **reason);
+/* dvt_machine_verify with the query part (every sponge, Merkle path, reduced opening and fold of every query) on the
+ * handle's GPU (member 0, lane 0): same arguments, same return codes, same *reason text for EVERY input.  p == NULL is
+ * DVT_ERR_INPUT; a HIP failure is DVT_ERR_DEVICE with the text in dvt_last_error (there is no fallback to the host path). */
+int dvt_prover_machine_verify(dvt_prover *p, const uint8_t *vk, size_t vk_len, const uint8_t *proof, size_t proof_len,
+                              uint32_t fri_queries, uint32_t pow_bits, char **reason);
 /* per-stage milliseconds of the last dvt_machine_prove on this handle (needs "profile":1):
  * out[0..5] = commit_main, permutation, quotient, openings, fri, total */
 int dvt_last_stage_ms(dvt_prover *p, float out[6]);
@@ -392,6 +418,20 @@ int dvt_rv32_debug_device_traces(dvt_prover *p, const dvt_pk *pk, dvt_job *job, 
  * (1..1024 queries, at most 30 bits; anything else is DVT_ERR_INPUT). */
 int dvt_verify(const uint8_t *vk, size_t vk_len, const uint8_t *proof, size_t proof_len, uint32_t fri_queries,
                uint32_t pow_bits, int32_t *exit_code, uint8_t **public_values, size_t *pv_len, char **reason);
+/* dvt_verify on the handle's GPU (member 0, lane 0): same arguments, same return codes, same *reason text, same
+ * exit_code / public_values as dvt_verify for EVERY input.  The host runs, per shard, the shape checks, the transcript,
+ * the constraint check at zeta, the FRI challenges and the proof-of-work check; the query part of all shards that pass
+ * runs on the device, a staging-size chunk of shards at a time, and the first failure in dvt_verify's order (shard,
+ * host part before queries, query, step) is reported.  p == NULL is DVT_ERR_INPUT; a HIP failure is DVT_ERR_DEVICE
+ * with the text in dvt_last_error (there is no fallback to the host path). */
+int dvt_prover_verify(dvt_prover *p, const uint8_t *vk, size_t vk_len, const uint8_t *proof, size_t proof_len,
+                      uint32_t fri_queries, uint32_t pow_bits, int32_t *exit_code, uint8_t **public_values,
+                      size_t *pv_len, char **reason);
+/* measurement hook: the last dvt_prover_verify / dvt_prover_machine_verify of this handle in milliseconds.  out[0] = the
+ * host part (parse, transcript, zeta check), out[1] = flattening into pinned staging, out[2] = uploads, out[3] = kernels,
+ * out[4] = downloads (2..4: HIP events, summed over the chunks), out[5] = host time spent waiting for the device,
+ * out[6] = Poseidon2 permutations, out[7] = kernel launches, out[8] = chunks. */
+int dvt_prover_verify_times(dvt_prover *p, double out[9]);
 /* measurement hook, host only: guest cycles per second of the executor alone; trace = 0: fast mode (the sequential
  * pass of the prove pipeline), 1: trace mode (48-byte record per cycle).  0.0 when the guest does not halt. */
 double dvt_debug_exec_rate(const uint8_t *elf, size_t elf_len, const dvt_buf *stdin_bufs, size_t nbuf, uint32_t log_shard,
