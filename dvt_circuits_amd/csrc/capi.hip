@@ -448,8 +448,11 @@ int dvt_stage_merkle_commit(dvt_prover *p, const dvt_dev_matrix *mats, size_t n,
     Guard g(p); if (g.rc) return g.rc;
     std::vector<Engine::DevMat> dm;
     for (size_t i = 0; i < n; i++) {
-        if (mats[i].log_height > 30) return fail(p, DVT_ERR_INPUT, "log_height too large");
-        if (mats[i].width && !mats[i].d_data) return fail(p, DVT_ERR_INPUT, "null matrix data");
+        if (mats[i].log_height >= MERKLE_MAX_SEGMENTS)
+            return fail(p, DVT_ERR_INPUT, "tree too tall: matrix %zu has log_height %u, at most %u", i, mats[i].log_height, MERKLE_MAX_SEGMENTS - 1);
+        // (commit_tree skips a matrix without columns, where the tree's definition hashes the empty row)
+        if (!mats[i].width) return fail(p, DVT_ERR_INPUT, "matrix %zu has width 0", i);
+        if (!mats[i].d_data) return fail(p, DVT_ERR_INPUT, "null matrix data");
         dm.push_back({mats[i].d_data, mats[i].width, mats[i].log_height});
     }
     if (!p->eng.commit_tree(dm, d_digests)) return engine_fail(p->err, p->eng);

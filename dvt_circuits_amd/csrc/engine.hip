@@ -169,7 +169,7 @@ bool Engine::commit_tree(const std::vector<DevMat> &mats, uint32_t *d_digests) {
         for (auto &m : mats)
             if (m.log_h == lh)
                 for (uint32_t c = 0; c < m.width; c++) ptrs.push_back((uint64_t)(uintptr_t)(m.ptr + ((size_t)c << lh)));
-        if (ptrs.empty()) continue;
+        if (ptrs.empty()) continue;   // (also a height whose matrices all have width 0: no caller builds one, the stage entry refuses it)
         auto d_cols = reinterpret_cast<const uint32_t *const *>(upload(ptrs.data(), ptrs.size() * 8));
         if (!d_cols) return false;
         uint32_t *out = d_digests;

@@ -127,7 +127,9 @@ int dvt_dev_from_internal(dvt_prover *p, uint32_t *d_words, size_t n);
  * evaluations on shift*H', |H'| = 2|H|.  shift_mode: 0 = the generator 31 (trace
  * commitments), 1 = 1, 2 = w_{2N}^-1 (the two quotient chunks).  d_scratch
  * ([width][2^log_n]) holds the intermediate of the first pass when log_n > 12;
- * pass NULL to run that pass in place, which clobbers d_in.  log_n <= 22. */
+ * pass NULL to run that pass in place, which clobbers d_in.  With d_scratch given,
+ * d_in is left as it was; what d_scratch holds afterwards is unspecified at every
+ * log_n (at log_n <= 12 it is not needed and may be NULL).  log_n <= 22. */
 int dvt_stage_coset_lde(dvt_prover *p, uint32_t *d_in, uint32_t *d_scratch, uint32_t *d_out,
                         uint32_t width, uint32_t log_n, uint32_t shift_mode);
 
@@ -139,7 +141,10 @@ typedef struct {
 } dvt_dev_matrix;
 /* words the digest buffer must hold: (2*H - 1) * 8, H = tallest height */
 size_t dvt_merkle_digest_words(const dvt_dev_matrix *mats, size_t n);
-/* d_digests: layer 0 (H digests of 8 words) first, then H/2, ..., the root last */
+/* d_digests: layer 0 (H digests of 8 words) first, then H/2, ..., the root last.
+ * DVT_ERR_INPUT (text in dvt_last_error, nothing launched, the handle stays usable)
+ * for a matrix of width 0 - the prover builds none, and the tree's definition would
+ * hash an empty row there - and for a log_height above 23 ("tree too tall"). */
 int dvt_stage_merkle_commit(dvt_prover *p, const dvt_dev_matrix *mats, size_t n, uint32_t *d_digests);
 /* raw permutation on n states of 16 words each (device array [n][16]); test hook */
 int dvt_stage_poseidon2_permute(dvt_prover *p, uint32_t *d_states, size_t n);

@@ -154,8 +154,9 @@ def test_merkle_commit_edge_shapes(gpu, oracle, shapes):
 
 def test_merkle_full_size_root_of_subtrees(gpu, oracle):
     """2^20 rows x 24 columns: the GPU root must equal the oracle's compression
-    of the GPU's own level-10 digests (checksum of checksums), and 64 sampled
-    leaves must equal the oracle's sponge of those rows."""
+    of the GPU's own level-10 digests (checksum of checksums), 64 sampled
+    leaves must equal the oracle's sponge of those rows, and 64 sampled nodes of
+    each level between must equal the oracle's compression of their children."""
     import torch
 
     rng = np.random.default_rng(9)
@@ -171,6 +172,16 @@ def test_merkle_full_size_root_of_subtrees(gpu, oracle):
     layers = host(dg).reshape(-1, 8)
     for r in rng.integers(0, 1 << lh, 64):
         assert (layers[r] == oracle.hash_slice(m[:, r])).all()
+    # levels 19 to 11 (merkle_level_kernel<false> down to 2^14 nodes, then the coop kernel): 64 sampled nodes of each
+    # against the oracle's compression of the GPU's own children i and i + len in the layer above
+    above = 0
+    for lvl_log in range(lh - 1, 10, -1):
+        ln = 1 << lvl_log
+        cur_off = above + 2 * ln
+        for i in (int(x) for x in rng.integers(0, ln, 64)):
+            want = oracle.compress(layers[above + i], layers[above + i + ln])
+            assert (layers[cur_off + i] == want).all(), f"layer of 2^{lvl_log} nodes, node {i}: {layers[cur_off + i].tolist()} != {want.tolist()}"
+        above = cur_off
     off = sum((1 << lh) >> k for k in range(10))
     lvl = layers[off : off + (1 << (lh - 10))]
     cur = [x for x in lvl]
