@@ -2,6 +2,7 @@
 // the stage entry points and the machine-level ones (the rv32 boundary is capi_rv32.hip).  There is no CPU fallback
 // anywhere in this layer: without a HIP device every entry point that computes returns DVT_ERR_DEVICE.  (dvt_machine_verify
 // is host-only by nature.)
+#include <algorithm>
 #include <cstdarg>
 #include <cstdio>
 
@@ -37,9 +38,16 @@ int fail(dvt_prover *p, int code, const char *fmt, ...) {
     return code;
 }
 
-int pipe_drain(dvt_prover *p, std::string *first_err) {
-    if (!p->pipe) return DVT_OK;
-    Phase2Pipe &pp = *p->pipe;
+hipError_t sync_lanes(Member &mem) {
+    hipError_t first = hipStreamSynchronize(mem.eng.stream);
+    for (auto &e : mem.more)
+        if (e) { const hipError_t r = hipStreamSynchronize(e->stream); if (first == hipSuccess) first = r; }
+    return first;
+}
+
+int pipe_drain(Member &mem, std::string *first_err) {
+    if (!mem.pipe) return DVT_OK;
+    Phase2Pipe &pp = *mem.pipe;
     {
         std::lock_guard<std::mutex> lk(pp.mu);
         pp.stop = true;
@@ -53,30 +61,28 @@ int pipe_drain(dvt_prover *p, std::string *first_err) {
             if (first_err) *first_err = s.err;
             break;
         }
-    for (int k = 0; k < p->lanes; k++)
-        if (k == 0 || p->more[k - 1]) (void)hipStreamSynchronize(lane_engine(p, k).stream);
-    p->pipe.reset();
+    (void)sync_lanes(mem);
+    mem.pipe.reset();
     return rc;
 }
 
 void pipe_drain_all(dvt_prover *p) {
     for (size_t m = n_members(p); m-- > 0;) {
-        dvt_prover *mem = member(p, m);
-        if (!mem->pipe) continue;
-        if (m) (void)hipSetDevice(mem->eng.device);   // (the streams a drain waits for are that device's)
+        Member &mem = member(p, m);
+        if (!mem.pipe) continue;
+        if (m) (void)hipSetDevice(mem.eng.device);   // (the streams a drain waits for are that device's)
         (void)pipe_drain(mem);
-        if (m) (void)hipSetDevice(p->eng.device);
+        if (m) (void)hipSetDevice(eng0(p).device);
     }
 }
 
 int select_member(dvt_prover *p, size_t m) {
-    const hipError_t e = hipSetDevice(member(p, m)->eng.device);
-    return e == hipSuccess ? DVT_OK : fail(p, DVT_ERR_DEVICE, "hipSetDevice(%d): %s", member(p, m)->eng.device, hipGetErrorString(e));
+    const hipError_t e = hipSetDevice(member(p, m).eng.device);
+    return e == hipSuccess ? DVT_OK : fail(p, DVT_ERR_DEVICE, "hipSetDevice(%d): %s", member(p, m).eng.device, hipGetErrorString(e));
 }
 
 Guard::Guard(dvt_prover *p, const PipeClaim *claim, size_t claim_member) : p(p), lk(p->mu) {
-    dvt_prover *mem = member(p, claim_member);
-    if (claim && mem->pipe) slot = mem->pipe->slot_of(*claim);
+    if (claim && member(p, claim_member).pipe) slot = member(p, claim_member).pipe->slot_of(*claim);
     if (slot < 0) pipe_drain_all(p);
     rc = select_member(p, 0);
 }
@@ -156,21 +162,17 @@ const MachineDesc *machine_by_name(const char *name) {
 
 void pk_release(dvt_prover *p, dvt_pk *pk) {
     // (a key is freed on the handle that made it, include/dvt_prover.h; on another one the copies it cannot reach are skipped)
-    for (size_t m = pk->peers.size(); m > 0; m--) {
-        if (!pk->peers[m - 1] || m >= n_members(p)) continue;
-        (void)select_member(p, m);
-        dvt_pk *peer = pk->peers[m - 1];
-        pk->peers[m - 1] = nullptr;
-        pk_release(member(p, m), peer);
+    for (size_t m = std::min(pk->dev.size(), n_members(p)); m-- > 0;) {   // in reverse: member 0's device stays current
+        DeviceKey &k = pk->dev[m];
+        (void)hipSetDevice(member(p, m).eng.device);
+        member(p, m).eng.free_key(&k.key);
+        if (k.d_instrs) (void)hipFree(k.d_instrs);
+        if (k.d_prog_row) (void)hipFree(k.d_prog_row);
     }
-    (void)hipSetDevice(p->eng.device);
-    p->eng.free_key(&pk->key);
-    if (pk->d_instrs) (void)hipFree(pk->d_instrs);
-    if (pk->d_prog_row) (void)hipFree(pk->d_prog_row);
     delete pk;
 }
 int setup_finish(dvt_prover *p, dvt_pk *pk, int rc, dvt_pk **pk_out, uint8_t **vk, size_t *vk_len) {
-    if (!rc && vk && vk_len && !(*vk = copy_out(vk_words(pk->key.vk), vk_len))) rc = fail(p, DVT_ERR_DEVICE, "out of host memory");
+    if (!rc && vk && vk_len && !(*vk = copy_out(vk_words(pk->dev[0].key.vk), vk_len))) rc = fail(p, DVT_ERR_DEVICE, "out of host memory");
     if (rc) pk_release(p, pk);
     else *pk_out = pk;
     return rc;
@@ -311,18 +313,15 @@ int dvt_prover_create(const char *cfg_json, dvt_prover **out) {
         if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
             return fail(nullptr, DVT_ERR_DEVICE, "device %d is %s; this library is built for gfx950 only", d, prop.gcnArchName);
     }
-    const int dev = devs[0];
-    HIP_TRY(nullptr, hipSetDevice(dev));
     std::unique_ptr<dvt_prover> p(new dvt_prover());   // (freed on the early returns)
-    p->eng.device = dev;
     p->cfg.num_queries = (uint32_t)cfg_int(cfg_json, "fri_queries", 100);
     p->cfg.pow_bits = (uint32_t)cfg_int(cfg_json, "pow_bits", 16);
-    p->eng.profile = cfg_int(cfg_json, "profile", 0) != 0;
+    const bool profile = cfg_int(cfg_json, "profile", 0) != 0;
     p->log_shard = (uint32_t)cfg_int(cfg_json, "log_shard_size", 21);
     p->keep_phase1 = cfg_int(cfg_json, "keep_phase1", 1) != 0;
     p->exec_threads = (uint32_t)std::max(0, cfg_int(cfg_json, "exec_threads", 0));
-    p->eng.parts_parallel_log = cfg_int(cfg_json, "parts_parallel_log", (int)PARTS_PARALLEL_LOG);
-    if (p->eng.parts_parallel_log < -1 || p->eng.parts_parallel_log > (int)PARTS_PARALLEL_LOG)
+    const int parts_parallel_log = cfg_int(cfg_json, "parts_parallel_log", (int)PARTS_PARALLEL_LOG);
+    if (parts_parallel_log < -1 || parts_parallel_log > (int)PARTS_PARALLEL_LOG)
         return fail(nullptr, DVT_ERR_INPUT, "parts_parallel_log must be -1..%u", PARTS_PARALLEL_LOG);
     {
         // phase-2 lanes (of every member): the config key, else DVT_LANES (same-process A/B measurements), else 2, which
@@ -330,98 +329,93 @@ int dvt_prover_create(const char *cfg_json, dvt_prover **out) {
         // times stages with events on one stream and keeps one lane
         const char *env = getenv("DVT_LANES");
         const int dflt = env && *env ? atoi(env) : 2;
-        p->lanes = cfg_int(cfg_json, "lanes", dflt);
-        if (p->lanes < 1 || p->lanes > MAX_LANES) return fail(nullptr, DVT_ERR_INPUT, "lanes must be 1..%d (got %d)", MAX_LANES, p->lanes);
-        if (p->eng.profile) p->lanes = 1;
+        const int lanes = cfg_int(cfg_json, "lanes", dflt);
+        if (lanes < 1 || lanes > MAX_LANES) return fail(nullptr, DVT_ERR_INPUT, "lanes must be 1..%d (got %d)", MAX_LANES, lanes);
+        p->lanes = profile ? 1 : lanes;
         // phase-1 lanes: the config key, else DVT_PHASE1_LANES (capped at the handle's lanes, so that one setting serves
         // handles of any lane count in an A/B run), else PHASE1_LANES_DEFAULT
         const char *env1 = getenv("DVT_PHASE1_LANES");
         const int dflt1 = std::min(p->lanes, env1 && *env1 ? atoi(env1) : PHASE1_LANES_DEFAULT);
-        p->phase1_lanes = p->eng.profile ? 1 : cfg_int(cfg_json, "phase1_lanes", dflt1);
+        p->phase1_lanes = profile ? 1 : cfg_int(cfg_json, "phase1_lanes", dflt1);
         if (p->phase1_lanes < 1 || p->phase1_lanes > p->lanes)
             return fail(nullptr, DVT_ERR_INPUT, "phase1_lanes must be 1..lanes = 1..%d (got %d)", p->lanes, p->phase1_lanes);
     }
     if (p->log_shard < 4 || p->log_shard > 22) return fail(nullptr, DVT_ERR_INPUT, "log_shard_size must be 4..22");
     if (p->cfg.num_queries == 0 || p->cfg.num_queries > 1024 || p->cfg.pow_bits > 30)
         return fail(nullptr, DVT_ERR_INPUT, "fri_queries must be 1..1024 and pow_bits <= 30");
-    e = p->eng.init(dev);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&p->copy_stream, hipStreamNonBlocking);
-    // the further members: the same settings on their own devices
-    for (size_t m = 1; m < devs.size() && e == hipSuccess; m++) {
-        std::unique_ptr<dvt_prover> q(new dvt_prover());
-        q->owner = p.get();
-        q->cfg = p->cfg; q->log_shard = p->log_shard; q->keep_phase1 = p->keep_phase1; q->lanes = p->lanes; q->phase1_lanes = p->phase1_lanes;
-        q->eng.device = devs[m];
-        q->eng.profile = p->eng.profile;
-        q->eng.parts_parallel_log = p->eng.parts_parallel_log;
-        dvt_prover *mem = q.get();
-        p->peers.push_back(std::move(q));   // (the destroy below takes care of a half-made member)
-        e = mem->eng.init(devs[m]);
-        if (e == hipSuccess) e = hipStreamCreateWithFlags(&mem->copy_stream, hipStreamNonBlocking);
+    HIP_TRY(nullptr, hipSetDevice(devs[0]));
+    for (size_t m = 0; m < devs.size() && e == hipSuccess; m++) {
+        p->members.emplace_back(new Member());   // (the destroy below takes care of a half-made member)
+        Member &mem = *p->members.back();
+        mem.index = m;
+        mem.eng.device = devs[m];
+        mem.eng.profile = profile;
+        mem.eng.parts_parallel_log = parts_parallel_log;
+        mem.shares_device = std::count(devs.begin(), devs.end(), devs[m]) > 1;
+        e = mem.eng.init(devs[m]);
+        if (e == hipSuccess) e = hipStreamCreateWithFlags(&mem.copy_stream, hipStreamNonBlocking);
     }
-    for (size_t a = 0; a < devs.size(); a++)
-        for (size_t b = 0; b < devs.size(); b++)
-            if (a != b && devs[a] == devs[b]) member(p.get(), a)->shares_device = true;
     if (e != hipSuccess) {
         fail(nullptr, DVT_ERR_DEVICE, "handle setup: %s", hipGetErrorString(e));
         dvt_prover_destroy(p.release());
         return DVT_ERR_DEVICE;
     }
-    (void)hipSetDevice(dev);
+    (void)hipSetDevice(devs[0]);
     *out = p.release();
     return DVT_OK;
 }
 
 void dvt_prover_destroy(dvt_prover *p) {
     if (!p) return;
-    if (!p->owner) {
+    {
         std::lock_guard<std::mutex> lk(p->mu);
         pipe_drain_all(p);
     }
-    while (!p->peers.empty()) {   // in reverse, each with its device current
-        dvt_prover_destroy(p->peers.back().release());
-        p->peers.pop_back();
+    for (size_t m = n_members(p); m-- > 0;) {   // in reverse, each with its device current
+        Member &mem = member(p, m);
+        (void)hipSetDevice(mem.eng.device);
+        if (mem.copy_stream) { (void)hipStreamSynchronize(mem.copy_stream); (void)hipStreamDestroy(mem.copy_stream); }
+        if (mem.aux_pinned) (void)hipHostFree(mem.aux_pinned);
+        if (m == 0) {   // (what the handle keeps, before the engine of the device it was made on goes)
+            for (auto b : p->pinned) (void)hipHostFree(b);
+            vq::stage_free(p->vq_stage);
+        }
+        for (auto &e : mem.more)
+            if (e) e->shutdown();
+        mem.eng.shutdown();
     }
-    (void)hipSetDevice(p->eng.device);
-    if (p->copy_stream) { (void)hipStreamSynchronize(p->copy_stream); (void)hipStreamDestroy(p->copy_stream); }
-    for (auto b : p->pinned) (void)hipHostFree(b);
-    if (p->aux_pinned) (void)hipHostFree(p->aux_pinned);
-    vq::stage_free(p->vq_stage);
-    for (auto &e : p->more)
-        if (e) e->shutdown();
-    p->eng.shutdown();
     delete p;
 }
 
 const char *dvt_last_error(const dvt_prover *p) { return p ? p->err.c_str() : g_create_err.c_str(); }
 void dvt_free(void *ptr) { free(ptr); }
-void *dvt_stream(dvt_prover *p) { return p ? (void *)p->eng.stream : nullptr; }
+void *dvt_stream(dvt_prover *p) { return p ? (void *)eng0(p).stream : nullptr; }
 
 int dvt_sync(dvt_prover *p) {
     if (!p) return DVT_ERR_INPUT;
     Guard g(p); if (g.rc) return g.rc;
     for (size_t m = n_members(p); m-- > 0;) {   // (the guard has drained the lanes; member 0 last, its device stays current)
         if (int rc = select_member(p, m)) return rc;
-        HIP_TRY(p, hipStreamSynchronize(member(p, m)->eng.stream));
+        HIP_TRY(p, hipStreamSynchronize(member(p, m).eng.stream));
     }
     return DVT_OK;
 }
 
 uint32_t dvt_prover_device_count(const dvt_prover *p) { return p ? (uint32_t)n_members(p) : 0; }
 int dvt_prover_device(const dvt_prover *p, uint32_t m) {
-    return p && m < n_members(p) ? member(const_cast<dvt_prover *>(p), m)->eng.device : -1;
+    return p && m < n_members(p) ? p->members[m]->eng.device : -1;
 }
 
 int dvt_dev_to_internal(dvt_prover *p, uint32_t *d, size_t n) {
     if (!p || (!d && n)) return fail(p, DVT_ERR_INPUT, "null argument");
     Guard g(p); if (g.rc) return g.rc;
-    HIP_TRY(p, launch_to_internal(p->eng.stream, d, n));
+    HIP_TRY(p, launch_to_internal(eng0(p).stream, d, n));
     return DVT_OK;
 }
 int dvt_dev_from_internal(dvt_prover *p, uint32_t *d, size_t n) {
     if (!p || (!d && n)) return fail(p, DVT_ERR_INPUT, "null argument");
     Guard g(p); if (g.rc) return g.rc;
-    HIP_TRY(p, launch_from_internal(p->eng.stream, d, n));
+    HIP_TRY(p, launch_from_internal(eng0(p).stream, d, n));
     return DVT_OK;
 }
 
@@ -432,7 +426,7 @@ int dvt_stage_coset_lde(dvt_prover *p, uint32_t *d_in, uint32_t *d_scratch, uint
     if (log_n > 22) return fail(p, DVT_ERR_INPUT, "log_n %u > 22", log_n);
     if (shift_mode > 2) return fail(p, DVT_ERR_INPUT, "shift_mode %u", shift_mode);
     Guard g(p); if (g.rc) return g.rc;
-    HIP_TRY(p, launch_coset_lde(p->eng.stream, p->eng.tabs, d_in, d_scratch, d_out, width, log_n, shift_mode));
+    HIP_TRY(p, launch_coset_lde(eng0(p).stream, eng0(p).tabs, d_in, d_scratch, d_out, width, log_n, shift_mode));
     return DVT_OK;
 }
 
@@ -455,14 +449,14 @@ int dvt_stage_merkle_commit(dvt_prover *p, const dvt_dev_matrix *mats, size_t n,
         if (!mats[i].d_data) return fail(p, DVT_ERR_INPUT, "null matrix data");
         dm.push_back({mats[i].d_data, mats[i].width, mats[i].log_height});
     }
-    if (!p->eng.commit_tree(dm, d_digests)) return engine_fail(p->err, p->eng);
+    if (!eng0(p).commit_tree(dm, d_digests)) return engine_fail(p->err, eng0(p));
     return DVT_OK;
 }
 
 int dvt_stage_poseidon2_permute(dvt_prover *p, uint32_t *d_states, size_t n) {
     if (!p || (!d_states && n)) return fail(p, DVT_ERR_INPUT, "null argument");
     Guard g(p); if (g.rc) return g.rc;
-    HIP_TRY(p, launch_poseidon2_permute(p->eng.stream, d_states, n));
+    HIP_TRY(p, launch_poseidon2_permute(eng0(p).stream, d_states, n));
     return DVT_OK;
 }
 
@@ -481,7 +475,7 @@ int dvt_stage_fri_fold(dvt_prover *p, const uint32_t *d_v, uint32_t *d_out, cons
     Fp4 b;
     if (!ext_from_canonical(beta, &b)) return fail(p, DVT_ERR_INPUT, "beta not canonical");
     Guard g(p); if (g.rc) return g.rc;
-    HIP_TRY(p, launch_fri_fold(p->eng.stream, p->eng.tabs, reinterpret_cast<const Fp4 *>(d_v), reinterpret_cast<Fp4 *>(d_out),
+    HIP_TRY(p, launch_fri_fold(eng0(p).stream, eng0(p).tabs, reinterpret_cast<const Fp4 *>(d_v), reinterpret_cast<Fp4 *>(d_out),
                                reinterpret_cast<const Fp4 *>(d_ro), b, log_m));
     return DVT_OK;
 }
@@ -499,13 +493,13 @@ int dvt_stage_logup_running_sum(dvt_prover *p, uint32_t *d_totals, uint32_t *d_p
     const size_t n = (size_t)1 << log_n;
     if (overlap(d_totals, d_phi, 16 * n)) return fail(p, DVT_ERR_INPUT, "totals and phi overlap");
     Guard g(p); if (g.rc) return g.rc;
-    StageBuf scratch{p->eng.pool}, d_cum{p->eng.pool};
-    HIP_TRY(p, p->eng.pool.alloc_bytes(&scratch.ptr, prefix_sum_scratch_words(4, n) * 4));
-    HIP_TRY(p, p->eng.pool.alloc_bytes(&d_cum.ptr, 16));
+    StageBuf scratch{eng0(p).pool}, d_cum{eng0(p).pool};
+    HIP_TRY(p, eng0(p).pool.alloc_bytes(&scratch.ptr, prefix_sum_scratch_words(4, n) * 4));
+    HIP_TRY(p, eng0(p).pool.alloc_bytes(&d_cum.ptr, 16));
     uint32_t w[4];
-    if (!p->eng.logup_running_sum(d_totals, static_cast<uint32_t *>(scratch.ptr), d_phi, log_n, static_cast<uint32_t *>(d_cum.ptr)) ||
-        !p->eng.download(w, d_cum.ptr, sizeof w))
-        return engine_fail(p->err, p->eng);
+    if (!eng0(p).logup_running_sum(d_totals, static_cast<uint32_t *>(scratch.ptr), d_phi, log_n, static_cast<uint32_t *>(d_cum.ptr)) ||
+        !eng0(p).download(w, d_cum.ptr, sizeof w))
+        return engine_fail(p->err, eng0(p));
     for (int k = 0; k < 4; k++) cum[k] = Fp::raw(w[k]).canonical();
     return DVT_OK;
 }
@@ -526,7 +520,7 @@ int dvt_stage_open(dvt_prover *p, const dvt_dev_matrix *mats, size_t n, const ui
     const uint32_t width = (uint32_t)ptrs.size();
     if (!width) return DVT_OK;
     Guard g(p); if (g.rc) return g.rc;
-    Engine &e = p->eng;
+    Engine &e = eng0(p);
     StageBuf w{e.pool}, partial{e.pool}, res{e.pool};
     HIP_TRY(p, e.pool.alloc_bytes(&w.ptr, sizeof(Fp4) << log_n));
     HIP_TRY(p, e.pool.alloc_bytes(&partial.ptr, sizeof(Fp4) * open_row_blocks(log_n) * width * 2));
@@ -562,7 +556,7 @@ int dvt_stage_reduced_opening(dvt_prover *p, const uint32_t *const *cols, uint32
             return fail(p, DVT_ERR_INPUT, "opened value of column %u not canonical", c);
     }
     Guard g(p); if (g.rc) return g.rc;
-    Engine &e = p->eng;
+    Engine &e = eng0(p);
     std::vector<Fp4> apow;
     std::vector<double> apow_d;
     fri_alpha_powers(al, n_all, &apow, &apow_d);
@@ -583,9 +577,9 @@ int dvt_stage_pow_grind(dvt_prover *p, const uint32_t state[16], uint32_t pos, u
         st16[k] = Fp::from_canonical(state[k]).v;
     }
     Guard g(p); if (g.rc) return g.rc;
-    StageBuf found{p->eng.pool};
-    HIP_TRY(p, p->eng.pool.alloc_bytes(&found.ptr, 4));
-    if (!p->eng.pow_grind(st16, pos, bits, static_cast<uint32_t *>(found.ptr), witness)) return engine_fail(p->err, p->eng);
+    StageBuf found{eng0(p).pool};
+    HIP_TRY(p, eng0(p).pool.alloc_bytes(&found.ptr, 4));
+    if (!eng0(p).pow_grind(st16, pos, bits, static_cast<uint32_t *>(found.ptr), witness)) return engine_fail(p->err, eng0(p));
     return DVT_OK;
 }
 
@@ -622,9 +616,9 @@ static int chip_stage_parts(dvt_prover *p, uint32_t path, bool has_parts, uint32
                             uint32_t **d_parts) {
     *d_parts = nullptr;
     if (path == DVT_PATH_PARTS && !has_parts) return fail(p, DVT_ERR_INPUT, "this chip has no part-parallel launch");
-    const bool parts = path == DVT_PATH_PARTS || (path == DVT_PATH_DEFAULT && (int)log_n <= p->eng.parts_parallel_log);
+    const bool parts = path == DVT_PATH_PARTS || (path == DVT_PATH_DEFAULT && (int)log_n <= eng0(p).parts_parallel_log);
     if (!parts || !has_parts) return DVT_OK;
-    HIP_TRY(p, p->eng.pool.alloc_bytes(&buf->ptr, (size_t)PARTS_MAX * words_per_row * 4 << log_n));
+    HIP_TRY(p, eng0(p).pool.alloc_bytes(&buf->ptr, (size_t)PARTS_MAX * words_per_row * 4 << log_n));
     *d_parts = static_cast<uint32_t *>(buf->ptr);
     return DVT_OK;
 }
@@ -641,7 +635,7 @@ int dvt_stage_perm(dvt_prover *p, const char *machine, uint32_t chip, const uint
     if (d.perm_ext_w && (overlap(d_perm, perm_bytes, d_main, 4 * d.main_w * n) || (d.prep_w && overlap(d_perm, perm_bytes, d_prep, 4 * d.prep_w * n))))
         return fail(p, DVT_ERR_INPUT, "perm overlaps main or prep");
     Guard g(p); if (g.rc) return g.rc;
-    Engine &e = p->eng;
+    Engine &e = eng0(p);
     StageBuf parts{e.pool}, totals{e.pool}, scan{e.pool}, d_cum{e.pool};
     uint32_t *d_parts;
     if (int rc = chip_stage_parts(p, path, d.perm_parts, log_n, 4, &parts, &d_parts)) return rc;
@@ -682,7 +676,7 @@ int dvt_stage_quotient(dvt_prover *p, const char *machine, uint32_t chip, const 
         (d.perm_ext_w && overlap(d_out, out_bytes, d_perm_lde, 16 * d.perm_ext_w * m)))
         return fail(p, DVT_ERR_INPUT, "out overlaps an input");
     Guard g(p); if (g.rc) return g.rc;
-    Engine &e = p->eng;
+    Engine &e = eng0(p);
     StageBuf parts{e.pool};
     uint32_t *d_parts;
     if (int rc = chip_stage_parts(p, path, d.quot_parts, log_n, 8, &parts, &d_parts)) return rc;
@@ -759,7 +753,8 @@ int dvt_machine_setup(dvt_prover *p, const char *machine, const dvt_host_trace *
             if (!have) return fail(p, DVT_ERR_INPUT, "chip %s needs a preprocessed trace", m->chips[c].name);
         }
     dvt_pk *pk = new dvt_pk();
-    const int rc = p->eng.setup(m, refs, host, &pk->key) ? DVT_OK : engine_fail(p->err, p->eng);
+    pk->dev.emplace_back();
+    const int rc = eng0(p).setup(m, refs, host, &pk->dev[0].key) ? DVT_OK : engine_fail(p->err, eng0(p));
     return setup_finish(p, pk, rc, pk_out, vk, vk_len);
 }
 
@@ -773,7 +768,7 @@ int dvt_machine_prove(dvt_prover *p, const dvt_pk *pk, const dvt_host_trace *mai
                       uint8_t **proof, size_t *proof_len) {
     if (!p || !pk || !main || !nmain || !proof || !proof_len || (npub && !pubs)) return fail(p, DVT_ERR_INPUT, "null argument");
     Guard g(p); if (g.rc) return g.rc;
-    const MachineDesc *m = pk->key.vk.machine;
+    const MachineDesc *m = pk->dev[0].key.vk.machine;
     std::vector<uint32_t *> dev(nmain, nullptr);
     std::vector<ChipTrace> traces;
     int rc = DVT_OK;
@@ -785,7 +780,7 @@ int dvt_machine_prove(dvt_prover *p, const dvt_pk *pk, const dvt_host_trace *mai
             if (main[i].data[k] >= P) { rc = fail(p, DVT_ERR_INPUT, "main trace %zu holds a non-canonical value", i); break; }
         if (rc) break;
         if (hipMalloc(&dev[i], words * 4) != hipSuccess || hipMemcpy(dev[i], main[i].data, words * 4, hipMemcpyHostToDevice) != hipSuccess ||
-            launch_to_internal(p->eng.stream, dev[i], words) != hipSuccess) {
+            launch_to_internal(eng0(p).stream, dev[i], words) != hipSuccess) {
             rc = fail(p, DVT_ERR_DEVICE, "uploading main trace %zu failed", i);
             break;
         }
@@ -798,10 +793,10 @@ int dvt_machine_prove(dvt_prover *p, const dvt_pk *pk, const dvt_host_trace *mai
         pv[i] = Fp::from_canonical(pubs[i]);
     }
     ShardProof sp;
-    bool ok = p->eng.prove_shard(pk->key, traces, pv, p->cfg, &sp);
-    (void)hipStreamSynchronize(p->eng.stream);
+    bool ok = eng0(p).prove_shard(pk->dev[0].key, traces, pv, p->cfg, &sp);
+    (void)hipStreamSynchronize(eng0(p).stream);
     cleanup();
-    if (!ok) return engine_fail(p->err, p->eng);
+    if (!ok) return engine_fail(p->err, eng0(p));
     WordWriter w;
     write_shard_proof(w, sp);
     *proof = copy_out(w.w, proof_len);
@@ -886,7 +881,7 @@ int dvt_stage_verify_paths(dvt_prover *p, const dvt_path_chain *chains, size_t n
 
 int dvt_last_kernel_stats(dvt_prover *p, double out[9]) {
     if (!p || !out) return DVT_ERR_INPUT;
-    const StageTimes &t = p->eng.times;
+    const StageTimes &t = eng0(p).times;
     out[0] = t.lde_ms; out[1] = t.lde_alg_bytes; out[2] = t.lde_calls; out[3] = t.merkle_ms; out[4] = t.merkle_perms;
     out[5] = t.cells_m; out[6] = t.cells_p; out[7] = t.cells_q; out[8] = t.cells_pre;
     return DVT_OK;
@@ -894,7 +889,7 @@ int dvt_last_kernel_stats(dvt_prover *p, double out[9]) {
 
 int dvt_last_stage_ms(dvt_prover *p, float out[6]) {
     if (!p || !out) return DVT_ERR_INPUT;
-    const StageTimes &t = p->eng.times;
+    const StageTimes &t = eng0(p).times;
     out[0] = t.commit_main; out[1] = t.perm; out[2] = t.quotient; out[3] = t.open; out[4] = t.fri; out[5] = t.total;
     return DVT_OK;
 }

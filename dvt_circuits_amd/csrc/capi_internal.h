@@ -21,21 +21,22 @@ constexpr int MAX_LANES = 3;
 constexpr int PHASE1_LANES_DEFAULT = MAX_LANES;
 constexpr int MAX_MEMBERS = 8;   // devices of one handle ("devices")
 
+struct DeviceKey;
 // what dvt_rv32_prove_shard is about to collect from a running phase-2 pipeline
 struct PipeClaim {
     const dvt_job *job;
-    const dvt_pk *pk;
+    const DeviceKey *pk;
     const uint32_t *ch;   // the challenges, canonical
-    size_t shard;         // index into the job's shards
+    size_t shard;         // index into the shards of the member's part of the job
 };
 
-// Phase 2 of a job's shards, run ahead of the caller on the prover lanes: one worker thread per lane takes the next shard in
-// job order (that shard then stays on that lane), at most `lanes` shards past the last one the caller asked for.  Worker
-// threads never touch p->err: each slot keeps its own result.  Everything here is guarded by mu; the API thread holds the
-// prover's mutex while it creates, claims from or drains the pipeline.
+// Phase 2 of the shards a member holds of a job, run ahead of the caller on the member's prover lanes: one worker thread per
+// lane takes the next shard in job order (that shard then stays on that lane), at most `lanes` shards past the last one the
+// caller asked for.  Worker threads never touch p->err: each slot keeps its own result.  Everything here is guarded by mu;
+// the API thread holds the prover's mutex while it creates, claims from or drains the pipeline.
 struct Phase2Pipe {
     struct Slot {
-        size_t shard = 0;               // index into the job's shards
+        size_t shard = 0;               // index into the shards of the member's part
         int state = 0;                  // 0 waiting, 1 running, 2 done
         bool claimed = false;
         int rc = 0;
@@ -43,7 +44,7 @@ struct Phase2Pipe {
         std::vector<uint32_t> words;
     };
     dvt_job *job = nullptr;
-    const dvt_pk *pk = nullptr;
+    const DeviceKey *pk = nullptr;
     uint32_t ch[8] = {};                // the challenges, canonical
     std::vector<Slot> slots;            // in proving order
     size_t next = 0;                    // the next slot a worker starts
@@ -62,59 +63,62 @@ struct Phase2Pipe {
     }
 };
 
-struct dvt_prover {
-    dvt::Engine eng;                  // lane 0: the stage entry points, phase 1 and phase 2 of the shards it takes
+// What one device of a handle ("devices": [d0, d1, ...]) owns.  Settings are the handle's.
+struct Member {
+    size_t index = 0;                 // position in the handle
+    dvt::Engine eng;                  // lane 0: phase 1 and phase 2 of the shards it takes; on member 0 also the stage entry points
     // Further prover lanes: own stream, ring, arena, pool and tables each, sharing the proving key's read-only device
     // buffers.  Lane k is created when phase 1 has a k-th shard waiting and no lane free for it (k < phase1_lanes), else on
     // the first job that has at least two shards to prove in phase 2.  A job of one shard never creates one.
-    int lanes = 2;
-    int phase1_lanes = 1;             // lanes that also commit (phase 1) inside a prepare, 1..lanes ("phase1_lanes")
     std::unique_ptr<dvt::Engine> more[MAX_LANES - 1];
     std::unique_ptr<Phase2Pipe> pipe;   // the phase-2 pipeline of the current job, if one runs (see Phase2Pipe)
+    // record uploads overlap the lanes' kernels; with several phase-1 lanes the auxiliary uploads and their K0 launches too
+    hipStream_t copy_stream = nullptr;
+    // Pinned staging of everything a shard uploads besides its records (auxiliary traces, precompile calls).  Handing the
+    // runtime PAGEABLE memory makes it pin the pages on the fly; when the vectors are freed afterwards the driver quiesces
+    // every queue of the process to drop that mapping - measured as a 20-30 ms stall of the GPU right before phase 1 of a
+    // single-shard proof.
+    uint8_t *aux_pinned = nullptr;
+    size_t aux_pinned_bytes = 0;
+    bool shares_device = false;       // another member of the handle proves on the same physical device
+};
+
+struct dvt_prover {
+    std::vector<std::unique_ptr<Member>> members;   // one per device, never empty; a one-device handle runs the one-device path
+    int lanes = 2;                    // prover lanes of every member ("lanes")
+    int phase1_lanes = 1;             // lanes that also commit (phase 1) inside a prepare, 1..lanes ("phase1_lanes")
     dvt::StarkConfig cfg;
     uint32_t log_shard = 21;          // cycles per shard = 2^log_shard (SP1's default shard size)
     uint64_t max_cycles = 1ull << 36;
     bool keep_phase1 = true;          // keep K0 output, main LDEs and tree of phase 1 in HBM for phase 2 ("keep_phase1": 0 recomputes)
     uint32_t exec_threads = 0;        // trace-mode executor threads of the prove pipeline ("exec_threads", 0 = from the host's core count)
-    // record uploads overlap the lanes' kernels; with several phase-1 lanes the auxiliary uploads and their K0 launches too
-    hipStream_t copy_stream = nullptr;
     std::vector<dvt::rv32::CycleRec *> pinned;    // pinned staging buffers of 2^log_shard records each, reused across calls
-    // Pinned staging of everything else a shard uploads (auxiliary traces, precompile calls).  Handing the runtime PAGEABLE
-    // memory makes it pin the pages on the fly; when the vectors are freed afterwards the driver quiesces every queue of the
-    // process to drop that mapping - measured as a 20-30 ms stall of the GPU right before phase 1 of a single-shard proof.
-    uint8_t *aux_pinned = nullptr;
-    size_t aux_pinned_bytes = 0;
-    // Device members ("devices": [d0, d1, ...]).  The handle itself is member 0; each further member is a handle of its own
-    // device - lane-0 engine, lanes, copy stream, staging, phase-2 pipeline - with the settings of member 0.  Only member 0 is
-    // ever given to a caller: a further member's mutex is unused, and its err is scratch of the API thread (see lift()).
-    // Empty on a one-device handle, whose code path is the one-device path.
-    std::vector<std::unique_ptr<dvt_prover>> peers;
-    dvt_prover *owner = nullptr;      // of a further member: the handle it belongs to
-    bool shares_device = false;       // another member of the handle proves on the same physical device
-    // the device verifier's pinned staging and events (verify_query.hip), made by the first dvt_prover_verify; its last times
+    // the device verifier's pinned staging and events (verify_query.hip, on member 0), made by the first dvt_prover_verify; its last times
     dvt::vq::Stage *vq_stage = nullptr;
     double vq_times[9] = {};
     std::string err;
     std::mutex mu;
 };
 
-struct dvt_pk {
+// a proving key on one member's device
+struct DeviceKey {
     dvt::ProvingKey key;
+    dvt::rv32::Instr *d_instrs = nullptr;   // device copy of prog.instrs (K0)
+    uint32_t *d_prog_row = nullptr;    // instruction index -> program-table row
+};
+struct dvt_pk {
     bool is_rv32 = false;
     dvt::rv32::Program prog;
     dvt::rv32::HostPrep prep;
-    dvt::rv32::Instr *d_instrs = nullptr;   // device copy of prog.instrs (K0)
-    uint32_t *d_prog_row = nullptr;    // instruction index -> program-table row
-    // the key on the further members' devices (device buffers and vk only; prog and prep live here), in member order
-    std::vector<dvt_pk *> peers;
+    std::vector<DeviceKey> dev;   // in member order; a machine-level key (dvt_machine_setup) has member 0's only
 };
 
 namespace dvt {   // (the helpers the two units share stay out of the library's global namespace)
-inline Engine &lane_engine(dvt_prover *p, int k) { return k == 0 ? p->eng : *p->more[k - 1]; }
-// device members of a handle: member 0 is the handle itself
-inline size_t n_members(const dvt_prover *p) { return 1 + p->peers.size(); }
-inline dvt_prover *member(dvt_prover *p, size_t m) { return m == 0 ? p : p->peers[m - 1].get(); }
-inline const dvt_pk *member_key(const dvt_pk *pk, size_t m) { return m == 0 ? pk : pk->peers[m - 1]; }
+inline size_t n_members(const dvt_prover *p) { return p->members.size(); }
+inline Member &member(dvt_prover *p, size_t m) { return *p->members[m]; }
+inline Engine &lane_engine(Member &mem, int k) { return k == 0 ? mem.eng : *mem.more[k - 1]; }
+inline Engine &eng0(dvt_prover *p) { return p->members[0]->eng; }   // lane 0 of member 0: the stage and machine-level entry points
+inline const DeviceKey &member_key(const dvt_pk *pk, size_t m) { return pk->dev[m]; }
 
 // ---- errors: every message of the ABI layer goes through one formatter into one string
 int fail(std::string &err, int code, const char *fmt, ...) __attribute__((format(printf, 3, 4)));
@@ -128,19 +132,18 @@ inline int engine_fail(std::string &err, const Engine &e) { return fail(err, DVT
         if (e_ != hipSuccess) return fail(to, DVT_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
+// every lane's stream of a member is idle (its device is current); the first error
+hipError_t sync_lanes(Member &mem);
 // Stops the pipeline of one member (running shards finish, nothing new starts; unclaimed results are discarded) and waits
 // for every lane's stream.  With first_err != nullptr: the error of the lowest failed slot, if any.  Caller holds the
 // handle's mutex.
-int pipe_drain(dvt_prover *p, std::string *first_err = nullptr);
+int pipe_drain(Member &mem, std::string *first_err = nullptr);
 // the same on every member of the handle (the API thread is left on member 0's device)
 void pipe_drain_all(dvt_prover *p);
 // The API thread turns to member m: its device becomes the calling thread's.
 int select_member(dvt_prover *p, size_t m);
-// the code of a call made on a member, its message moved to the handle (a further member's err is only scratch)
-inline int lift(dvt_prover *p, dvt_prover *mem, int rc) {
-    if (rc && mem != p) p->err = mem->err;
-    return rc;
-}
+// the same before it touches a member; on a one-device handle the entry guard has done it
+inline int turn_to(dvt_prover *p, size_t m) { return n_members(p) > 1 ? select_member(p, m) : DVT_OK; }
 
 // Built first by every entry point that works on a handle: holds p->mu for the whole call, drains the phase-2 pipelines of
 // every member and selects member 0's device (rc: DVT_ERR_DEVICE when that fails).  With a claim (dvt_rv32_prove_shard
@@ -151,19 +154,20 @@ struct Guard {
     long slot = -1;
     int rc;
     explicit Guard(dvt_prover *p, const PipeClaim *claim = nullptr, size_t claim_member = 0);
-    ~Guard() { if (!p->peers.empty()) (void)hipSetDevice(p->eng.device); }   // (a call may have turned to another member)
+    ~Guard() { if (n_members(p) > 1) (void)hipSetDevice(eng0(p).device); }   // (a call may have turned to another member)
 };
 
-// A lane's view of the prover for K0 and phase 2: its engine, and the error string it reports to (p->err for lane 0 on the
-// API thread; a pipeline worker's own string, which its slot keeps: worker threads never write p->err).  Passed as
+// A lane's view of the prover for K0 and both phases: the handle (settings), the member, its engine, and the error string
+// it reports to (p->err on the API thread; a worker thread's own string: worker threads never write p->err).  Passed as
 // `const Lane &`: what it refers to stays writable.
 struct Lane {
     dvt_prover *p;
+    Member &mem;
     int k;
     Engine &eng;
     std::string &err;
 };
-inline Lane lane0(dvt_prover *p) { return {p, 0, p->eng, p->err}; }
+inline Lane lane0(dvt_prover *p, size_t m = 0) { return {p, member(p, m), 0, member(p, m).eng, p->err}; }
 
 // device scratch of an entry point from a lane's buffer cache, given back at scope exit (stream-ordered: the next user of a
 // cached buffer runs on the same stream)
@@ -218,7 +222,7 @@ inline int reject(char **reason, int code, const std::string &why) {
 // inside a try-block: a malformed proof throws, and its message is the reason.
 int verify_words(const uint8_t *proof, size_t len, int len_code, char **reason,
                  const std::function<int(WordReader &, std::string &)> &check);
-// The query part of the shards of one verify call on lane 0 of the handle (verify_query.hip), behind an interface the two
+// The query part of the shards of one verify call on lane 0 of member 0 (verify_query.hip), behind an interface the two
 // verify entry points share: add() after a shard's host part has passed, finish() once, then why() per shard.  A device
 // failure is kept in rc (its text in p->err) and makes every later call a no-op.
 struct DeviceQueries {

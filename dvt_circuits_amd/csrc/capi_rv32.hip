@@ -76,76 +76,80 @@ struct ShardJob {
     uint32_t header[HEADER_WORDS] = {};
     bool header_valid = false;   // phase 1 ran (inside the prepare pipeline, or by commit_shard) and no phase 2 has consumed it
 };
-// one prepared execution: cut into shards by the executor; the shards this job owns (first, first + stride, ...) are
-// resident in HBM, ready for K0..K9
-struct dvt_job {
-    int exit_code = -1;
-    uint64_t cycles = 0;
-    std::vector<uint8_t> public_values;
-    size_t n_total = 0, first = 0, stride = 1;   // shards of the execution / which of them this job holds
+// the shards of a job that one member of the handle holds (first, first + stride, ... of the execution), resident in that
+// member's HBM, ready for K0..K9
+struct JobPart {
+    size_t first = 0, stride = 1;
     std::vector<ShardJob> shards;
     struct Work {   // K0 working buffers of one lane (largest shard seen), from that lane's pool
         uint32_t *d_cpu = nullptr, *d_byte = nullptr, *d_prog = nullptr;
         uint32_t log_cpu = 0;
     } work[MAX_LANES];
-    size_t byte_words = 0, prog_words = 0;
-    double t_exec_wait = 0;   // seconds the GPU thread spent waiting for the executor inside prepare (several members: the longest wait)
-    // On a handle with several device members the k-th held shard lives on member k mod G: parts[m] is the job of member m
-    // (first + m stride, then G stride apart), and this job holds no shard itself, only what describes the execution.
-    std::vector<dvt_job *> parts;
-    dvt_job *part(size_t m) { return parts.empty() ? this : parts[m]; }
-    size_t held() const {
-        size_t n = shards.size();
-        for (auto q : parts) n += q->shards.size();
-        return n;
-    }
-    // the job that holds the shard at pos, and its member; nullptr when this job does not hold it
-    dvt_job *part_at(size_t pos, size_t *m) {
-        *m = 0;
-        if (parts.empty()) return at(pos) ? this : nullptr;
-        if (pos < first || (pos - first) % stride) return nullptr;
-        *m = (pos - first) / stride % parts.size();
-        return parts[*m]->at(pos) ? parts[*m] : nullptr;
-    }
+    double t_exec_wait = 0;   // seconds the member's GPU thread spent waiting for the executor inside prepare
     ShardJob *at(size_t pos) { return pos >= first && (pos - first) % stride == 0 && (pos - first) / stride < shards.size() ? &shards[(pos - first) / stride] : nullptr; }
 };
+// One prepared execution, cut into shards by the executor.  Of the shards this job holds (first, first + stride, ...) the
+// k-th lives on member k mod G of the handle that prepared it: parts[m] is member m's (first + m stride, then G stride apart).
+struct dvt_job {
+    int exit_code = -1;
+    uint64_t cycles = 0;
+    std::vector<uint8_t> public_values;
+    size_t n_total = 0, first = 0, stride = 1;   // shards of the execution / which of them this job holds
+    size_t byte_words = 0, prog_words = 0;
+    double t_exec_wait = 0;   // the longest executor wait of a member
+    std::vector<JobPart> parts;   // one per member
+    size_t held() const {
+        size_t n = 0;
+        for (auto &q : parts) n += q.shards.size();
+        return n;
+    }
+    // the shard at pos and the member that holds it; nullptr when this job does not hold it
+    ShardJob *at(size_t pos, size_t *m) {
+        if (pos < first || (pos - first) % stride) return nullptr;
+        *m = (pos - first) / stride % parts.size();
+        return parts[*m].at(pos);
+    }
+};
+
+// The one wrong-handle check of the entry points that take a key and/or a job (either may be null): both were made by a
+// handle with as many members as this one, so member m finds its DeviceKey and its JobPart.
+static int same_members(dvt_prover *p, const dvt_pk *pk, const dvt_job *j) {
+    const size_t G = n_members(p);
+    if ((pk && pk->dev.size() != G) || (j && j->parts.size() != G)) return fail(p, DVT_ERR_INPUT, "proving key or job of a handle with other devices");
+    return DVT_OK;
+}
 
 // (no phase-1 worker and no phase-2 pipeline runs: buffers go back to the pools only after every lane is done)
 // Every buffer returns to the pool of the member and lane it came from: what a shard uploaded to lane 0's, what phase 1 kept
 // (K0 output; LDEs and tree through the cache) to the pool of the lane that committed the shard, the working buffers to
-// their lane's.
+// their lane's.  On a handle with fewer members than the one that made the job (include/dvt_prover.h) the other members'
+// buffers cannot be reached and stay allocated.
 static void job_release(dvt_prover *p, dvt_job *j) {
     if (!j) return;
-    for (size_t m = j->parts.size(); m-- > 0;) {
-        if (m >= n_members(p)) { delete j->parts[m]; continue; }   // (not the handle that made the job, include/dvt_prover.h: its buffers cannot be reached)
-        (void)select_member(p, m);
-        job_release(member(p, m), j->parts[m]);
-    }
-    if (!j->parts.empty()) (void)select_member(p, 0);
-    DevPool &pool = p->eng.pool;
-    for (auto &s : j->shards) {
-        pool.free(s.d_recs);
-        for (auto &d : s.d_aux) pool.free(d);
-        if (s.d_cpu || s.d_byte || s.d_prog) {
-            DevPool &kept = lane_engine(p, s.lane).pool;
-            for (uint32_t *d : {s.d_cpu, s.d_byte, s.d_prog}) kept.free(d);
+    for (size_t m = std::min(j->parts.size(), n_members(p)); m-- > 0;) {
+        (void)turn_to(p, m);
+        Member &mem = member(p, m);
+        for (auto &s : j->parts[m].shards) {
+            mem.eng.pool.free(s.d_recs);
+            for (auto &d : s.d_aux) mem.eng.pool.free(d);
+            if (s.d_cpu || s.d_byte || s.d_prog)
+                for (uint32_t *d : {s.d_cpu, s.d_byte, s.d_prog}) lane_engine(mem, s.lane).pool.free(d);
+            s.cache.release();
         }
-        s.cache.release();
-    }
-    for (int k = 0; k < MAX_LANES; k++) {
-        auto &w = j->work[k];
-        if (!w.d_cpu && !w.d_byte && !w.d_prog) continue;
-        DevPool &lp = lane_engine(p, k).pool;
-        for (uint32_t *d : {w.d_cpu, w.d_byte, w.d_prog}) lp.free(d);
+        for (int k = 0; k < MAX_LANES; k++) {
+            auto &w = j->parts[m].work[k];
+            if (w.d_cpu || w.d_byte || w.d_prog)
+                for (uint32_t *d : {w.d_cpu, w.d_byte, w.d_prog}) lane_engine(mem, k).pool.free(d);
+        }
     }
     delete j;
 }
 
 // K0 of a shard (into the shard's own buffers when it has them, else the job's working buffers); fills the chip
 // trace list of that shard.  `reuse`: phase 2 takes the traces phase 1 left behind instead of generating them again.
-static int shard_traces(const Lane &c, const dvt_pk *pk, dvt_job *j, ShardJob &s, std::vector<ChipTrace> *traces, bool reuse) {
+static int shard_traces(const Lane &c, const DeviceKey &key, dvt_job *j, ShardJob &s, std::vector<ChipTrace> *traces, bool reuse) {
     hipStream_t st = c.eng.stream;
-    dvt_job::Work &w = j->work[c.k];
+    JobPart::Work &w = j->parts[c.mem.index].work[c.k];
     const MachineDesc *m = machine_rv32();
     if (!s.d_cpu && (!w.d_cpu || w.log_cpu < s.log_n[RV32_CHIP_CPU])) {   // working buffers, sized for the largest shard seen
         HIP_TRY(c.err, hipStreamSynchronize(st));
@@ -159,7 +163,7 @@ static int shard_traces(const Lane &c, const dvt_pk *pk, dvt_job *j, ShardJob &s
     if (!(reuse && s.d_cpu && s.traces_valid)) {
         bool ok = hipMemcpyAsync(byte, s.d_aux[RV32_CHIP_BYTE], j->byte_words * 4, hipMemcpyDeviceToDevice, st) == hipSuccess &&
                   hipMemcpyAsync(prog, s.d_aux[RV32_CHIP_PROGRAM], j->prog_words * 4, hipMemcpyDeviceToDevice, st) == hipSuccess &&
-                  rv32::launch_k0_cpu_rows(st, s.d_recs, s.n_recs, s.index, s.next_pc, pk->d_instrs, pk->d_prog_row, cpu, s.log_n[RV32_CHIP_CPU], byte, prog) == hipSuccess &&
+                  rv32::launch_k0_cpu_rows(st, s.d_recs, s.n_recs, s.index, s.next_pc, key.d_instrs, key.d_prog_row, cpu, s.log_n[RV32_CHIP_CPU], byte, prog) == hipSuccess &&
                   launch_to_internal(st, byte, j->byte_words) == hipSuccess && launch_to_internal(st, prog, j->prog_words) == hipSuccess;
         if (!ok) return fail(c.err, DVT_ERR_DEVICE, "trace generation (K0) failed: %s", hipGetErrorString(hipGetLastError()));
         s.traces_valid = s.d_cpu != nullptr;
@@ -187,8 +191,9 @@ static std::mutex &device_turn(int dev) {
 
 // phase 1 of a shard: K0 + K1..K3 of the main traces -> header.  `concurrent`: other threads of this member commit or upload
 // meanwhile (the phase-1 lanes of a prepare)
-static int shard_commit(const Lane &c, const dvt_pk *pk, dvt_job *j, ShardJob &s, bool concurrent = false) {
+static int shard_commit(const Lane &c, const DeviceKey &key, dvt_job *j, ShardJob &s, bool concurrent = false) {
     dvt_prover *p = c.p;
+    Member &mem = c.mem;
     std::vector<ChipTrace> traces;
     const bool time_stages = getenv("DVT_TIME_PREPARE") != nullptr;
     const auto t0 = Clock::now();
@@ -197,29 +202,27 @@ static int shard_commit(const Lane &c, const dvt_pk *pk, dvt_job *j, ShardJob &s
     };
     // keep the phase-1 results in HBM while they fit (about 3 GB per 2^21-cycle shard); otherwise phase 2 recomputes
     std::unique_lock<std::mutex> turn;
-    if (concurrent || (p->shares_device && p->keep_phase1 && !s.cache.tree)) turn = std::unique_lock<std::mutex>(device_turn(c.eng.device));
+    if (concurrent || (mem.shares_device && p->keep_phase1 && !s.cache.tree)) turn = std::unique_lock<std::mutex>(device_turn(c.eng.device));
     size_t free_b = 0, total_b = 0;
     if (p->keep_phase1 && !s.cache.tree) { (void)hipMemGetInfo(&free_b, &total_b); free_b += c.eng.pool.cached_bytes; }   // (only the first commit of a shard asks)
     lap("memory asked");
     // the further lanes' arenas are not there yet on the first job: leave room for them (the largest arena of this member's
     // lanes is the measure of one), so that the kept caches do not take what another lane's working set then cannot get
     // (and for the lanes of the members that share this device, whose phase 1 waits for its turn meanwhile)
-    size_t lane_room = 0, one_arena = p->eng.arena.cap;
-    for (auto &e : p->more)
+    size_t lane_room = 0, one_arena = mem.eng.arena.cap;
+    for (auto &e : mem.more)
         if (e) one_arena = std::max(one_arena, e->arena.cap);
-    auto room_of = [&](dvt_prover *q) {
-        for (int k = 0; k < q->lanes; k++) {
-            if (q == p && k == c.k) continue;
-            const size_t have = k == 0 ? q->eng.arena.cap : q->more[k - 1] ? q->more[k - 1]->arena.cap : 0;
+    auto room_of = [&](const Member &q) {
+        for (int k = 0; k < p->lanes; k++) {
+            if (&q == &mem && k == c.k) continue;
+            const size_t have = k == 0 ? q.eng.arena.cap : q.more[k - 1] ? q.more[k - 1]->arena.cap : 0;
             if (one_arena > have) lane_room += one_arena - have;
         }
     };
-    room_of(p);
-    if (turn.owns_lock()) {
-        dvt_prover *top = p->owner ? p->owner : p;
-        for (size_t m = 0; m < n_members(top); m++)
-            if (member(top, m) != p && member(top, m)->eng.device == c.eng.device) room_of(member(top, m));
-    }
+    room_of(mem);
+    if (turn.owns_lock())
+        for (auto &q : p->members)
+            if (q.get() != &mem && q->eng.device == c.eng.device) room_of(*q);
     MainCache *keep = p->keep_phase1 && (s.cache.tree || free_b > ((size_t)24 << 30) + lane_room) ? &s.cache : nullptr;
     if (keep && !s.d_cpu) {
         DevPool &pool = c.eng.pool;
@@ -232,11 +235,11 @@ static int shard_commit(const Lane &c, const dvt_pk *pk, dvt_job *j, ShardJob &s
         }
     }
     lap("trace buffers");
-    int rc = shard_traces(c, pk, j, s, &traces, false);
+    int rc = shard_traces(c, key, j, s, &traces, false);
     if (rc) return rc;
     lap("K0 launched");
     Digest root;
-    if (!c.eng.commit_main_root(pk->key, traces, &root, keep, &turn)) return engine_fail(c.err, c.eng);
+    if (!c.eng.commit_main_root(key.key, traces, &root, keep, &turn)) return engine_fail(c.err, c.eng);
     lap("main root");
     for (int k = 0; k < 8; k++) s.header[k] = root.d[k].canonical();
     for (uint32_t k = 0; k < N_PUB; k++) s.header[8 + k] = s.pubs[k].canonical();
@@ -246,12 +249,12 @@ static int shard_commit(const Lane &c, const dvt_pk *pk, dvt_job *j, ShardJob &s
 
 // phase 2 of a shard: K0..K9 with the common challenges -> shard proof words
 // (on any lane: the shard's phase-1 buffers came from the pool of the lane that committed it and are only read here)
-static int shard_prove(const Lane &c, const dvt_pk *pk, dvt_job *j, ShardJob &s, const PermChallenges &gc, std::vector<uint32_t> *words) {
+static int shard_prove(const Lane &c, const DeviceKey &key, dvt_job *j, ShardJob &s, const PermChallenges &gc, std::vector<uint32_t> *words) {
     std::vector<ChipTrace> traces;
-    int rc = shard_traces(c, pk, j, s, &traces, s.cache.valid);
+    int rc = shard_traces(c, key, j, s, &traces, s.cache.valid);
     if (rc) return rc;
     ShardProof sp;
-    bool ok = c.eng.prove_shard(pk->key, traces, s.pubs, c.p->cfg, &sp, &gc, &s.cache);
+    bool ok = c.eng.prove_shard(key.key, traces, s.pubs, c.p->cfg, &sp, &gc, &s.cache);
     (void)hipStreamSynchronize(c.eng.stream);
     s.cache.valid = false;  // the buffers stay for the next commit of this shard (released with the job)
     s.traces_valid = false;
@@ -456,7 +459,7 @@ bool events_of(const ReadyShard &r, int c, const void **src, size_t *bytes, size
 // so that the wait at the end (the staging buffer is reused by the next shard, the error words are read) is for this upload
 // alone and no committing lane's stream is drained; it allocates from lane 0's pool under the device's turn (device_turn).
 static int upload_shard(const Lane &lane, ReadyShard &r, ShardJob &s, hipEvent_t ev, hipStream_t aux, bool feeder) {
-    dvt_prover *p = lane.p;
+    Member &mem = lane.mem;
     Engine &e = lane.eng;
     const MachineDesc *m = machine_rv32();
     s.index = r.meta.index; s.n_recs = r.meta.n_recs; s.next_pc = r.meta.next_pc;
@@ -481,18 +484,18 @@ static int upload_shard(const Lane &lane, ReadyShard &r, ShardJob &s, hipEvent_t
             stage_bytes += (bytes + 255) & ~(size_t)255;
         }
     }
-    HIP_TRY(lane.err, hipMemcpyAsync(s.d_recs, r.buf, s.n_recs * sizeof(rv32::CycleRec), hipMemcpyHostToDevice, p->copy_stream));
-    HIP_TRY(lane.err, hipEventRecord(ev, p->copy_stream));
-    if (stage_bytes > p->aux_pinned_bytes) {
+    HIP_TRY(lane.err, hipMemcpyAsync(s.d_recs, r.buf, s.n_recs * sizeof(rv32::CycleRec), hipMemcpyHostToDevice, mem.copy_stream));
+    HIP_TRY(lane.err, hipEventRecord(ev, mem.copy_stream));
+    if (stage_bytes > mem.aux_pinned_bytes) {
         HIP_TRY(lane.err, hipStreamSynchronize(aux));
-        if (p->aux_pinned) HIP_TRY(lane.err, hipHostFree(p->aux_pinned));
-        p->aux_pinned = nullptr; p->aux_pinned_bytes = 0;
-        HIP_TRY(lane.err, hipHostMalloc(&p->aux_pinned, stage_bytes + stage_bytes / 4));
-        p->aux_pinned_bytes = stage_bytes + stage_bytes / 4;
+        if (mem.aux_pinned) HIP_TRY(lane.err, hipHostFree(mem.aux_pinned));
+        mem.aux_pinned = nullptr; mem.aux_pinned_bytes = 0;
+        HIP_TRY(lane.err, hipHostMalloc(&mem.aux_pinned, stage_bytes + stage_bytes / 4));
+        mem.aux_pinned_bytes = stage_bytes + stage_bytes / 4;
     }
     size_t stage_at = 0;
     auto staged = [&](const void *src, size_t bytes) -> const void * {
-        uint8_t *dst = p->aux_pinned + stage_at;
+        uint8_t *dst = mem.aux_pinned + stage_at;
         memcpy(dst, src, bytes);
         stage_at += (bytes + 255) & ~(size_t)255;
         return dst;
@@ -556,17 +559,17 @@ static int upload_shard(const Lane &lane, ReadyShard &r, ShardJob &s, hipEvent_t
 }
 
 // lane k of a member (k >= 1), made when it is first needed
-static int ensure_lane(dvt_prover *p, int k, std::string &err) {
-    if (p->more[k - 1]) return DVT_OK;
+static int ensure_lane(Member &mem, int k, std::string &err) {
+    if (mem.more[k - 1]) return DVT_OK;
     std::unique_ptr<Engine> e(new Engine());
     e->profile = false;
-    e->parts_parallel_log = p->eng.parts_parallel_log;
-    const hipError_t r = e->init(p->eng.device);
+    e->parts_parallel_log = mem.eng.parts_parallel_log;
+    const hipError_t r = e->init(mem.eng.device);
     if (r != hipSuccess) {
         e->shutdown();
         return fail(err, DVT_ERR_DEVICE, "prover lane %d: %s", k, hipGetErrorString(r));
     }
-    p->more[k - 1] = std::move(e);
+    mem.more[k - 1] = std::move(e);
     return DVT_OK;
 }
 
@@ -597,10 +600,10 @@ struct Phase1Lanes {
 };
 }  // namespace
 
-static void phase1_worker(dvt_prover *p, const dvt_pk *pk, dvt_job *j, Executor &ex, Phase1Lanes *q, int k) {
+static void phase1_worker(const Lane &feeder, const DeviceKey &key, dvt_job *j, Executor &ex, Phase1Lanes *q, int k) {
     Phase1Lanes::Worker &me = q->w[k];
-    const Lane c{p, k, lane_engine(p, k), me.err};
-    const hipError_t dev = hipSetDevice(p->eng.device);
+    const Lane c{feeder.p, feeder.mem, k, lane_engine(feeder.mem, k), me.err};
+    const hipError_t dev = hipSetDevice(c.mem.eng.device);
     for (;;) {
         Phase1Lanes::Item it;
         {
@@ -613,7 +616,7 @@ static void phase1_worker(dvt_prover *p, const dvt_pk *pk, dvt_job *j, Executor 
             q->queue.pop_front();
             q->cv.notify_all();   // (the feeder uploads the next shard)
         }
-        const int rc = dev != hipSuccess ? fail(me.err, DVT_ERR_DEVICE, "hipSetDevice: %s", hipGetErrorString(dev)) : shard_commit(c, pk, j, *it.s, true);
+        const int rc = dev != hipSuccess ? fail(me.err, DVT_ERR_DEVICE, "hipSetDevice: %s", hipGetErrorString(dev)) : shard_commit(c, key, j, *it.s, true);
         ex.give_back(it.buf);
         if (rc) {
             ex.cancel();
@@ -627,22 +630,23 @@ static void phase1_worker(dvt_prover *p, const dvt_pk *pk, dvt_job *j, Executor 
     }
 }
 
-static int commit_on_lanes(const Lane &c, const dvt_pk *pk, dvt_job *j, Executor &ex, bool time_stages, Clock::time_point t_begin) {
-    dvt_prover *p = c.p;
+static int commit_on_lanes(const Lane &c, const DeviceKey &key, dvt_job *j, Executor &ex, bool time_stages, Clock::time_point t_begin) {
+    Member &mem = c.mem;
+    JobPart &part = j->parts[mem.index];
     Phase1Lanes q;
-    std::deque<ShardJob> built;   // (the workers hold references: j->shards takes the shards, in execution order, at the end)
+    std::deque<ShardJob> built;   // (the workers hold references: the part takes the shards, in execution order, at the end)
     int rc = DVT_OK;
     size_t rc_at = ~(size_t)0;
     hipEvent_t ev = nullptr;
     (void)hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-    for (size_t pos = j->first;; pos += j->stride) {
+    for (size_t pos = part.first;; pos += part.stride) {
         {
             std::unique_lock<std::mutex> lk(q.mu);
             q.cv.wait(lk, [&] { return q.failed || q.queue.empty(); });
             if (q.failed) break;
         }
         ReadyShard r;
-        if (!ex.take(pos, &r, &j->t_exec_wait)) break;
+        if (!ex.take(pos, &r, &part.t_exec_wait)) break;
         rc_at = pos;
         if (!r.err.empty()) {
             rc = r.unsupported ? fail(c.err, DVT_ERR_UNSUPPORTED, "no chip for an instruction of the guest (%s)", r.err.c_str())
@@ -652,23 +656,23 @@ static int commit_on_lanes(const Lane &c, const dvt_pk *pk, dvt_job *j, Executor
         }
         if (time_stages) fprintf(stderr, "[prepare] %.2f ms: shard at position %zu ready\n", ms_since(t_begin), pos);
         built.emplace_back();
-        rc = upload_shard(c, r, built.back(), ev, p->copy_stream, true);
+        rc = upload_shard(c, r, built.back(), ev, mem.copy_stream, true);
         if (time_stages) fprintf(stderr, "[prepare] %.2f ms: uploaded\n", ms_since(t_begin));
         if (rc) { ex.give_back(r.buf); break; }
         bool start;
         {
             std::lock_guard<std::mutex> lk(q.mu);
             q.queue.push_back({&built.back(), pos, r.buf});
-            start = q.idle == 0 && q.n < p->phase1_lanes;
+            start = q.idle == 0 && q.n < c.p->phase1_lanes;
             q.cv.notify_all();
         }
         if (!start) continue;
-        if (q.n > 0) {   // (an engine allocates, and the committers read p->more: under the turn)
-            std::lock_guard<std::mutex> turn(device_turn(p->eng.device));
-            rc = ensure_lane(p, q.n, c.err);
+        if (q.n > 0) {   // (an engine allocates, and the committers read the member's lanes: under the turn)
+            std::lock_guard<std::mutex> turn(device_turn(mem.eng.device));
+            rc = ensure_lane(mem, q.n, c.err);
         }
         if (rc) break;
-        q.w[q.n].th = std::thread(phase1_worker, p, pk, j, std::ref(ex), &q, q.n);
+        q.w[q.n].th = std::thread([&, k = q.n] { phase1_worker(c, key, j, ex, &q, k); });
         q.n++;
     }
     if (rc) ex.cancel();
@@ -680,10 +684,10 @@ static int commit_on_lanes(const Lane &c, const dvt_pk *pk, dvt_job *j, Executor
     }
     for (int k = 0; k < q.n; k++) q.w[k].th.join();
     for (auto &it : q.queue) ex.give_back(it.buf);   // (left behind by a failure)
-    (void)hipStreamSynchronize(p->copy_stream);
-    for (int k = 0; k < q.n; k++) (void)hipStreamSynchronize(lane_engine(p, k).stream);
+    (void)hipStreamSynchronize(mem.copy_stream);
+    for (int k = 0; k < q.n; k++) (void)hipStreamSynchronize(lane_engine(mem, k).stream);
     (void)hipEventDestroy(ev);
-    for (auto &s : built) j->shards.push_back(std::move(s));
+    for (auto &s : built) part.shards.push_back(std::move(s));
     for (int k = 0; k < q.n; k++)   // the error of the lowest failed position
         if (q.w[k].rc && (!rc || q.w[k].at < rc_at)) {
             rc_at = q.w[k].at;
@@ -696,16 +700,17 @@ static int commit_on_lanes(const Lane &c, const dvt_pk *pk, dvt_job *j, Executor
 // Phase 1 of the job's shards in execution order, as the executor hands them over: the records of shard i+1 come in on the
 // copy stream while the GPU runs phase 1 of shard i.  Every pinned buffer goes back to the executor.  (One phase-1 lane: one
 // compute stream, the calling thread uploads and commits in turn.)
-static int commit_overlapped(const Lane &c, const dvt_pk *pk, dvt_job *j, Executor &ex, bool time_stages, Clock::time_point t_begin) {
-    if (c.p->phase1_lanes > 1) return commit_on_lanes(c, pk, j, ex, time_stages, t_begin);
+static int commit_overlapped(const Lane &c, const DeviceKey &key, dvt_job *j, Executor &ex, bool time_stages, Clock::time_point t_begin) {
+    if (c.p->phase1_lanes > 1) return commit_on_lanes(c, key, j, ex, time_stages, t_begin);
+    JobPart &part = j->parts[c.mem.index];
     int rc = DVT_OK;
     hipEvent_t ev = nullptr;
     (void)hipEventCreateWithFlags(&ev, hipEventDisableTiming);
     bool have_prev = false;
     rv32::CycleRec *prev_buf = nullptr;
-    for (size_t pos = j->first; rc == DVT_OK; pos += j->stride) {
+    for (size_t pos = part.first; rc == DVT_OK; pos += part.stride) {
         ReadyShard r;
-        const bool got = ex.take(pos, &r, &j->t_exec_wait);
+        const bool got = ex.take(pos, &r, &part.t_exec_wait);
         if (got && !r.err.empty()) {
             rc = r.unsupported ? fail(c.err, DVT_ERR_UNSUPPORTED, "no chip for an instruction of the guest (%s)", r.err.c_str())
                                : fail(c.err, DVT_ERR_GUEST, "guest trapped: %s", r.err.c_str());
@@ -714,14 +719,14 @@ static int commit_overlapped(const Lane &c, const dvt_pk *pk, dvt_job *j, Execut
         }
         if (time_stages && got) fprintf(stderr, "[prepare] %.2f ms: shard at position %zu ready\n", ms_since(t_begin), pos);
         if (got) {
-            j->shards.emplace_back();
-            rc = upload_shard(c, r, j->shards.back(), ev, c.eng.stream, false);
+            part.shards.emplace_back();
+            rc = upload_shard(c, r, part.shards.back(), ev, c.eng.stream, false);
         }
         if (time_stages && got) fprintf(stderr, "[prepare] %.2f ms: uploaded\n", ms_since(t_begin));
         // phase 1 of the previous shard runs while the copy engine brings this one in
         if (rc == DVT_OK && have_prev) {
-            ShardJob &ps = j->shards[j->shards.size() - (got ? 2 : 1)];
-            rc = shard_commit(c, pk, j, ps);
+            ShardJob &ps = part.shards[part.shards.size() - (got ? 2 : 1)];
+            rc = shard_commit(c, key, j, ps);
             ex.give_back(prev_buf);
         }
         if (!got) { have_prev = false; break; }
@@ -734,7 +739,7 @@ static int commit_overlapped(const Lane &c, const dvt_pk *pk, dvt_job *j, Execut
         prev_buf = r.buf;
     }
     if (rc == DVT_OK && have_prev) {
-        rc = shard_commit(c, pk, j, j->shards.back());
+        rc = shard_commit(c, key, j, part.shards.back());
         ex.give_back(prev_buf);
     }
     if (time_stages) fprintf(stderr, "[prepare] %.2f ms: phase 1 of the last shard done\n", ms_since(t_begin));
@@ -757,41 +762,33 @@ static int prepare_verdict(std::string &err, const FastPass &f, int rc) {
     return DVT_OK;
 }
 
-// Phase 1 on a handle with several members: the k-th shard the job holds goes to member k mod G.  Every member runs the
-// upload + phase-1 loop for its shards on a thread of its own (its device, copy stream, staging and lanes), all fed by
-// the one executor.  The threads report into strings of their own, never into p->err; the error is that of the lowest
-// failed position.  Every thread is joined and every member's streams are idle on return.
+// Phase 1 on a handle with several members: every member runs the upload + phase-1 loop for its part of the job on a thread
+// of its own (its device, copy stream, staging and lanes), all fed by the one executor.  The threads report into strings of
+// their own, never into p->err; the error is that of the lowest failed position.  Every thread is joined and every member's
+// streams are idle on return.
 static int commit_on_members(dvt_prover *p, const dvt_pk *pk, dvt_job *j, Executor &ex, bool time_stages, Clock::time_point t_begin) {
     const size_t G = n_members(p);
     struct Run { int rc = DVT_OK; std::string err; };
     std::vector<Run> runs(G);
-    for (size_t m = 0; m < G; m++) {
-        dvt_job *q = new dvt_job();
-        q->first = j->first + m * j->stride; q->stride = j->stride * G;
-        q->byte_words = j->byte_words; q->prog_words = j->prog_words;
-        j->parts.push_back(q);
-    }
     std::vector<std::thread> threads;
     for (size_t m = 0; m < G; m++) threads.emplace_back([&, m] {
         Run &r = runs[m];
-        dvt_prover *mem = member(p, m);
-        const hipError_t e = hipSetDevice(mem->eng.device);
-        r.rc = e != hipSuccess ? fail(r.err, DVT_ERR_DEVICE, "hipSetDevice(%d): %s", mem->eng.device, hipGetErrorString(e))
-                               : commit_overlapped(Lane{mem, 0, mem->eng, r.err}, member_key(pk, m), j->parts[m], ex, time_stages, t_begin);
+        Member &mem = member(p, m);
+        const hipError_t e = hipSetDevice(mem.eng.device);
+        r.rc = e != hipSuccess ? fail(r.err, DVT_ERR_DEVICE, "hipSetDevice(%d): %s", mem.eng.device, hipGetErrorString(e))
+                               : commit_overlapped(Lane{p, mem, 0, mem.eng, r.err}, member_key(pk, m), j, ex, time_stages, t_begin);
         if (r.rc) ex.cancel();
     });
     for (auto &t : threads) t.join();
     int rc = DVT_OK;
     size_t at = ~(size_t)0;
     for (size_t m = G; m-- > 0;) {
-        dvt_prover *mem = member(p, m);
         if (select_member(p, m) == DVT_OK) {
-            (void)hipStreamSynchronize(mem->copy_stream);
-            for (int k = 0; k < mem->lanes; k++)
-                if (k == 0 || mem->more[k - 1]) (void)hipStreamSynchronize(lane_engine(mem, k).stream);
+            (void)hipStreamSynchronize(member(p, m).copy_stream);
+            (void)sync_lanes(member(p, m));
         }
-        j->t_exec_wait = std::max(j->t_exec_wait, j->parts[m]->t_exec_wait);
-        const size_t pos = j->parts[m]->first + j->parts[m]->shards.size() * j->parts[m]->stride;   // about where it stopped
+        const JobPart &q = j->parts[m];
+        const size_t pos = q.first + q.shards.size() * q.stride;   // about where it stopped
         if (runs[m].rc && pos <= at) { at = pos; rc = runs[m].rc; p->err = runs[m].err; }
     }
     return rc;
@@ -801,7 +798,7 @@ static int job_prepare(dvt_prover *p, const dvt_pk *pk, const dvt_buf *stdin_buf
                        dvt_report *report) {
     if (stride == 0 || first >= stride) return fail(p, DVT_ERR_INPUT, "bad shard partition %zu / %zu", first, stride);
     const size_t G = n_members(p);
-    if (pk->peers.size() + 1 != G) return fail(p, DVT_ERR_INPUT, "the proving key holds %zu device copies, this handle has %zu devices", pk->peers.size() + 1, G);
+    if (int rc = same_members(p, pk, nullptr)) return rc;
     unsigned hw = std::thread::hardware_concurrency();
     const unsigned n_workers = p->exec_threads ? p->exec_threads : std::max(1u, std::min(6u, hw > 3 ? hw - 2 : 1u));
     // pinned staging: one buffer per worker + two in flight on the GPU side of every member (one in upload, one in commit) and
@@ -821,7 +818,11 @@ static int job_prepare(dvt_prover *p, const dvt_pk *pk, const dvt_buf *stdin_buf
     j->first = first; j->stride = stride;
     j->byte_words = (size_t)rv32::N_BYTE_OPS * 65536;
     j->prog_words = (size_t)1 << pk->prep.log_n[RV32_CHIP_PROGRAM];
-    int rc = G == 1 ? commit_overlapped(lane0(p), pk, j, ex, time_stages, t_begin) : commit_on_members(p, pk, j, ex, time_stages, t_begin);
+    j->parts.resize(G);
+    for (size_t m = 0; m < G; m++) { j->parts[m].first = first + m * stride; j->parts[m].stride = stride * G; }
+    // (one member: phase 1 runs on the calling thread)
+    int rc = G == 1 ? commit_overlapped(lane0(p), member_key(pk, 0), j, ex, time_stages, t_begin) : commit_on_members(p, pk, j, ex, time_stages, t_begin);
+    for (auto &q : j->parts) j->t_exec_wait = std::max(j->t_exec_wait, q.t_exec_wait);
     FastPass &f = ex.finish();
     if (time_stages) fprintf(stderr, "[prepare] %.2f ms: threads joined\n", ms_since(t_begin));
     if (report) {
@@ -842,16 +843,16 @@ static int job_prepare(dvt_prover *p, const dvt_pk *pk, const dvt_buf *stdin_buf
 
 // ------------------------------------------------------------------ the phase-2 pipeline (Phase2Pipe)
 // the further lanes' engines that phase 1 has not made, on the first job that has at least two shards to prove
-static int ensure_lanes(dvt_prover *p) {
+static int ensure_lanes(dvt_prover *p, Member &mem) {
     for (int k = 1; k < p->lanes; k++)
-        if (int rc = ensure_lane(p, k, p->err)) return rc;
+        if (int rc = ensure_lane(mem, k, p->err)) return rc;
     return DVT_OK;
 }
 
-static void pipe_worker(dvt_prover *p, Phase2Pipe *pp, PermChallenges gc, int k) {
+static void pipe_worker(dvt_prover *p, Member *mem, Phase2Pipe *pp, PermChallenges gc, int k) {
     std::string err;
-    const Lane c{p, k, lane_engine(p, k), err};
-    const hipError_t dev = hipSetDevice(p->eng.device);
+    const Lane c{p, *mem, k, lane_engine(*mem, k), err};
+    const hipError_t dev = hipSetDevice(mem->eng.device);
     for (;;) {
         size_t i;
         {
@@ -864,7 +865,7 @@ static void pipe_worker(dvt_prover *p, Phase2Pipe *pp, PermChallenges gc, int k)
         std::vector<uint32_t> words;
         err.clear();
         const int rc = dev != hipSuccess ? fail(err, DVT_ERR_DEVICE, "hipSetDevice: %s", hipGetErrorString(dev))
-                                         : shard_prove(c, pp->pk, pp->job, pp->job->shards[pp->slots[i].shard], gc, &words);
+                                         : shard_prove(c, *pp->pk, pp->job, pp->job->parts[mem->index].shards[pp->slots[i].shard], gc, &words);
         std::lock_guard<std::mutex> lk(pp->mu);
         Phase2Pipe::Slot &s = pp->slots[i];
         s.rc = rc;
@@ -876,38 +877,38 @@ static void pipe_worker(dvt_prover *p, Phase2Pipe *pp, PermChallenges gc, int k)
     }
 }
 
-// Starts the pipeline over the job's shards with a valid header, in job order from shard index k0 (which must be one of
-// them).  Returns DVT_OK with p->pipe set; DVT_OK without a pipeline when there is nothing to run ahead (one lane, or
-// fewer than two such shards).  p is one member, pk its copy of the key and j its part of the job; `always` (a handle with
-// several members, which run at the same time) starts a pipeline for a single lane or a single shard too.  Caller holds the
-// handle's mutex and has selected the member; no pipeline runs on it.
-static int pipe_start(dvt_prover *p, const dvt_pk *pk, dvt_job *j, size_t k0, const PermChallenges &gc, bool always) {
-    if ((p->lanes < 2 && !always) || k0 >= j->shards.size() || !j->shards[k0].header_valid) return DVT_OK;
+// Starts the pipeline of a member over the shards of its part of the job that have a valid header, in job order from shard
+// index k0 of the part (which must be one of them).  Returns DVT_OK with mem.pipe set; DVT_OK without a pipeline when there
+// is nothing to run ahead (one lane, or fewer than two such shards).  `always` (a handle with several members, which run at
+// the same time) starts a pipeline for a single lane or a single shard too.  Caller holds the handle's mutex and has
+// selected the member; no pipeline runs on it.
+static int pipe_start(dvt_prover *p, Member &mem, const DeviceKey &key, dvt_job *j, size_t k0, const PermChallenges &gc, bool always) {
+    const std::vector<ShardJob> &shards = j->parts[mem.index].shards;
+    if ((p->lanes < 2 && !always) || k0 >= shards.size() || !shards[k0].header_valid) return DVT_OK;
     std::vector<size_t> order;
-    for (size_t k = k0; k < j->shards.size(); k++)
-        if (j->shards[k].header_valid) order.push_back(k);
+    for (size_t k = k0; k < shards.size(); k++)
+        if (shards[k].header_valid) order.push_back(k);
     if (order.size() < (always ? 1u : 2u)) return DVT_OK;
-    int rc = ensure_lanes(p);
+    int rc = ensure_lanes(p, mem);
     if (rc) return rc;
-    for (int k = 0; k < p->lanes; k++)   // phase 1 (on whichever lanes committed) is complete before another lane reads its buffers
-        if (k == 0 || p->more[k - 1]) HIP_TRY(p, hipStreamSynchronize(lane_engine(p, k).stream));
+    HIP_TRY(p, sync_lanes(mem));   // phase 1 (on whichever lanes committed) is complete before another lane reads its buffers
     std::unique_ptr<Phase2Pipe> pp(new Phase2Pipe());
     pp->job = j;
-    pp->pk = pk;
+    pp->pk = &key;
     for (int k = 0; k < 4; k++) { pp->ch[k] = gc.alpha.c[k].canonical(); pp->ch[4 + k] = gc.beta.c[k].canonical(); }
     pp->slots.resize(order.size());
     for (size_t i = 0; i < order.size(); i++) pp->slots[i].shard = order[i];
     pp->limit = (size_t)p->lanes;   // (the caller claims slot 0 next)
     const int n_workers = (int)std::min<size_t>((size_t)p->lanes, order.size());
-    for (int k = 0; k < n_workers; k++) pp->workers.emplace_back(pipe_worker, p, pp.get(), gc, k);
-    p->pipe = std::move(pp);
+    for (int k = 0; k < n_workers; k++) pp->workers.emplace_back(pipe_worker, p, &mem, pp.get(), gc, k);
+    mem.pipe = std::move(pp);
     return DVT_OK;
 }
 
 // Waits for a slot's words.  Taking the last unclaimed slot ends the pipeline (nothing is left to run ahead).  On a failure
 // the pipeline is drained and the error of the lowest failed shard is reported.
-static int pipe_claim(dvt_prover *p, size_t slot, std::vector<uint32_t> *words) {
-    Phase2Pipe &pp = *p->pipe;
+static int pipe_claim(dvt_prover *p, Member &mem, size_t slot, std::vector<uint32_t> *words) {
+    Phase2Pipe &pp = *mem.pipe;
     bool ok, last;
     {
         std::unique_lock<std::mutex> lk(pp.mu);
@@ -923,11 +924,11 @@ static int pipe_claim(dvt_prover *p, size_t slot, std::vector<uint32_t> *words) 
         last = std::all_of(pp.slots.begin(), pp.slots.end(), [](const Phase2Pipe::Slot &x) { return x.claimed; });
     }
     if (ok) {
-        if (last) (void)pipe_drain(p);
+        if (last) (void)pipe_drain(mem);
         return DVT_OK;
     }
     std::string why;
-    const int rc = pipe_drain(p, &why);
+    const int rc = pipe_drain(mem, &why);
     return fail(p, rc ? rc : DVT_ERR_DEVICE, "%s", rc ? why.c_str() : "phase-2 pipeline stopped");
 }
 
@@ -936,35 +937,32 @@ static int pipe_claim(dvt_prover *p, size_t slot, std::vector<uint32_t> *words) 
 static int job_prove(dvt_prover *p, const dvt_pk *pk, dvt_job *j, uint8_t **proof, size_t *proof_len) {
     const size_t n = j->held(), G = n_members(p);
     if (n != j->n_total) return fail(p, DVT_ERR_INPUT, "this job holds %zu of the execution's %zu shards: prove them shard by shard", n, j->n_total);
-    if (pk->peers.size() + 1 != G || (G > 1 && j->parts.size() != G)) return fail(p, DVT_ERR_INPUT, "proving key or job of a handle with other devices");
-    auto shard = [&](size_t i) -> ShardJob & { return j->part(i % G)->shards[i / G]; };
+    if (int rc = same_members(p, pk, j)) return rc;
+    auto shard = [&](size_t i) -> ShardJob & { return j->parts[i % G].shards[i / G]; };
     std::vector<uint32_t> headers(n * HEADER_WORDS);
     for (size_t i = 0; i < n; i++) {
         if (!shard(i).header_valid) {
-            dvt_prover *mem = member(p, i % G);
-            int rc = G > 1 ? select_member(p, i % G) : DVT_OK;
-            if (!rc) rc = lift(p, mem, shard_commit(lane0(mem), member_key(pk, i % G), j->part(i % G), shard(i)));
+            int rc = turn_to(p, i % G);
+            if (!rc) rc = shard_commit(lane0(p, i % G), member_key(pk, i % G), j, shard(i));
             if (rc) return rc;
         }
         memcpy(headers.data() + i * HEADER_WORDS, shard(i).header, sizeof(uint32_t) * HEADER_WORDS);
     }
-    PermChallenges gc = global_challenges(pk->key.vk, headers.data(), n);
+    PermChallenges gc = global_challenges(pk->dev[0].key.vk, headers.data(), n);
     std::vector<std::vector<uint32_t>> shards(n);
     int rc = DVT_OK;
     for (size_t m = 0; m < G && !rc; m++) {
-        if (G > 1) rc = select_member(p, m);
-        if (!rc) rc = lift(p, member(p, m), pipe_start(member(p, m), member_key(pk, m), j->part(m), 0, gc, G > 1));
+        rc = turn_to(p, m);
+        if (!rc) rc = pipe_start(p, member(p, m), member_key(pk, m), j, 0, gc, G > 1);
     }
     for (size_t i = 0; i < n && !rc; i++) {   // (every shard of a member is in its pipeline when one runs: its last claim ends it)
-        dvt_prover *mem = member(p, i % G);
-        if (G > 1) rc = select_member(p, i % G);
-        if (!rc) rc = lift(p, mem, mem->pipe ? pipe_claim(mem, i / G, &shards[i]) : shard_prove(lane0(mem), member_key(pk, i % G), j->part(i % G), shard(i), gc, &shards[i]));
+        Member &mem = member(p, i % G);
+        rc = turn_to(p, i % G);
+        if (!rc) rc = mem.pipe ? pipe_claim(p, mem, i / G, &shards[i]) : shard_prove(lane0(p, i % G), member_key(pk, i % G), j, shard(i), gc, &shards[i]);
     }
     if (G > 1) pipe_drain_all(p);   // (on an error the other members still run)
-    for (size_t m = G; m-- > 0;) {
-        if (G > 1 && select_member(p, m)) continue;
-        (void)hipStreamSynchronize(member(p, m)->eng.stream);
-    }
+    for (size_t m = G; m-- > 0;)   // member 0 last: its device stays current
+        if (!turn_to(p, m)) (void)hipStreamSynchronize(member(p, m).eng.stream);
     if (rc) return rc;
     if (!proof) return DVT_OK;  // timing runs may discard the bytes
     *proof = copy_out(write_core_proof({(uint32_t)j->exit_code, j->public_values, std::move(shards)}), proof_len);
@@ -1084,28 +1082,28 @@ static CheckChallenges check_challenges(const VerifyingKey &vk, const dvt_job *j
     return c;
 }
 
-// the tables of one shard on the member that holds it (its device is current): findings and the shard's per-bus sums
-static int shard_check(dvt_prover *mem, const dvt_pk *key, dvt_job *part, ShardJob &s, size_t pos, const CheckChallenges &ch,
+// the tables of one shard on lane 0 of the member that holds it (its device is current): findings and the shard's per-bus sums
+static int shard_check(const Lane &c, const DeviceKey &key, dvt_job *j, ShardJob &s, size_t pos, const CheckChallenges &ch,
                        std::vector<dvt_check_finding> *findings, Fp4 bus[DVT_CHECK_BUSES]) {
     const MachineDesc *m = machine_rv32();
     std::vector<ChipTrace> traces;
     const bool kept = s.traces_valid;
-    const int rc = shard_traces(lane0(mem), key, part, s, &traces, true);
+    const int rc = shard_traces(c, key, j, s, &traces, true);
     s.traces_valid = kept;   // (K0 into a kept buffer whose content had been consumed: the job stays as it was found)
     if (rc) return rc;
     std::vector<CheckTable> tabs;
     for (auto &t : traces) {
         const ChipDesc &d = m->chips[t.chip_id];
         const uint32_t *prep = nullptr;
-        for (auto &pr : key->key.prep)
+        for (auto &pr : key.key.prep)
             if (pr.chip_id == t.chip_id && pr.log_n == t.log_n) prep = pr.d_trace;
-        if (d.prep_w && !prep) return fail(mem, DVT_ERR_INPUT, "chip %s of shard %zu has no preprocessed trace of its height in the proving key", d.name, pos);
+        if (d.prep_w && !prep) return fail(c.err, DVT_ERR_INPUT, "chip %s of shard %zu has no preprocessed trace of its height in the proving key", d.name, pos);
         tabs.push_back({&d, t.d_main, prep, t.log_n});
     }
     std::vector<uint32_t> pub;
     for (auto x : s.pubs) pub.push_back(x.v);
     std::vector<CheckTableOut> res;
-    if (int rc2 = check_tables(lane0(mem), m, tabs, pub, ch, true, true, &res)) return rc2;
+    if (int rc2 = check_tables(c, m, tabs, pub, ch, true, true, &res)) return rc2;
     for (size_t i = 0; i < tabs.size(); i++) {
         if (res[i].r.violations) findings->push_back({(uint32_t)pos, (uint32_t)traces[i].chip_id, tabs[i].log_n, res[i].r});
         for (uint32_t b = 0; b < DVT_CHECK_BUSES; b++) bus[b] += res[i].bus[b];
@@ -1115,22 +1113,20 @@ static int shard_check(dvt_prover *mem, const dvt_pk *key, dvt_job *part, ShardJ
 
 static int job_check(dvt_prover *p, const dvt_pk *pk, dvt_job *j, dvt_check_finding *findings, size_t cap, dvt_check_summary *summary) {
     const size_t G = n_members(p);
-    if (pk->peers.size() + 1 != G || (G > 1 && j->parts.size() != G) || (G == 1 && !j->parts.empty()))
-        return fail(p, DVT_ERR_INPUT, "proving key or job of a handle with other devices");
+    if (int rc = same_members(p, pk, j)) return rc;
     const auto t0 = Clock::now();
-    const CheckChallenges ch = check_challenges(pk->key.vk, j);
+    const CheckChallenges ch = check_challenges(pk->dev[0].key.vk, j);
     std::vector<dvt_check_finding> all;
     Fp4 bus[DVT_CHECK_BUSES];
     for (auto &b : bus) b = Fp4::zero();
     int rc = DVT_OK;
     for (size_t m = 0; m < G && !rc; m++) {
-        dvt_prover *mem = member(p, m);
-        dvt_job *part = j->part(m);
-        if (G > 1) rc = select_member(p, m);
-        for (size_t k = 0; k < part->shards.size() && !rc; k++)
-            rc = lift(p, mem, shard_check(mem, member_key(pk, m), part, part->shards[k], part->first + k * part->stride, ch, &all, bus));
+        JobPart &part = j->parts[m];
+        rc = turn_to(p, m);
+        for (size_t k = 0; k < part.shards.size() && !rc; k++)
+            rc = shard_check(lane0(p, m), member_key(pk, m), j, part.shards[k], part.first + k * part.stride, ch, &all, bus);
     }
-    if (G > 1 && select_member(p, 0) && !rc) rc = DVT_ERR_DEVICE;
+    if (turn_to(p, 0) && !rc) rc = DVT_ERR_DEVICE;
     if (rc) return rc;
     std::sort(all.begin(), all.end(), [](const dvt_check_finding &a, const dvt_check_finding &b) { return a.shard != b.shard ? a.shard < b.shard : a.chip < b.chip; });
     *summary = dvt_check_summary{};
@@ -1171,21 +1167,21 @@ static std::vector<uint32_t> trace_blob(const rv32::HostTraces &T, const rv32::H
 }
 
 // the device half of dvt_setup on one member (its device is current): the preprocessed commitment and the program tables
-static int setup_on(dvt_prover *mem, const rv32::Program &prog, const rv32::HostPrep &prep, dvt_pk *dst) {
+static int setup_on(const Lane &c, const rv32::Program &prog, const rv32::HostPrep &prep, DeviceKey *dst) {
     std::vector<ChipRef> refs;
     std::vector<std::vector<uint32_t>> host;
     for (int c : {RV32_CHIP_PROGRAM, RV32_CHIP_BYTE, RV32_CHIP_MEM_IMAGE}) {
         refs.push_back({c, prep.log_n[c]});
         host.push_back(prep.prep[c]);
     }
-    if (!mem->eng.setup(machine_rv32(), refs, host, &dst->key)) return engine_fail(mem->err, mem->eng);
+    if (!c.eng.setup(machine_rv32(), refs, host, &dst->key)) return engine_fail(c.err, c.eng);
     dst->key.vk.extra = {prog.entry};
     std::vector<uint32_t> rowmap = rv32::program_row_map(prog);
     size_t ib = prog.instrs.size() * sizeof(rv32::Instr);
     if (hipMalloc(&dst->d_instrs, ib) != hipSuccess || hipMalloc(&dst->d_prog_row, rowmap.size() * 4) != hipSuccess ||
         hipMemcpy(dst->d_instrs, prog.instrs.data(), ib, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(dst->d_prog_row, rowmap.data(), rowmap.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-        return fail(mem, DVT_ERR_DEVICE, "uploading the program table failed");
+        return fail(c.err, DVT_ERR_DEVICE, "uploading the program table failed");
     return DVT_OK;
 }
 
@@ -1202,17 +1198,16 @@ int dvt_setup(dvt_prover *p, const uint8_t *elf, size_t elf_len, dvt_pk **pk_out
     if (!rv32::load_elf(elf, elf_len, &pk->prog, &err)) return setup_finish(p, pk, fail(p, DVT_ERR_INPUT, "ELF: %s", err.c_str()), pk_out, vk, vk_len);
     rv32::build_prep(pk->prog, &pk->prep);
     pk->is_rv32 = true;
-    int rc = setup_on(p, pk->prog, pk->prep, pk);
-    for (size_t m = 1; m < n_members(p) && !rc; m++) {
-        dvt_pk *q = new dvt_pk();
-        q->is_rv32 = true;
-        pk->peers.push_back(q);
-        rc = select_member(p, m);
-        if (!rc) rc = lift(p, member(p, m), setup_on(member(p, m), pk->prog, pk->prep, q));
-        if (!rc && vk_words(q->key.vk) != vk_words(pk->key.vk))
-            rc = fail(p, DVT_ERR_DEVICE, "member %zu (device %d) built a verifying key that differs from member 0's", m, member(p, m)->eng.device);
+    pk->dev.reserve(n_members(p));
+    int rc = DVT_OK;
+    for (size_t m = 0; m < n_members(p) && !rc; m++) {
+        pk->dev.emplace_back();   // (setup_finish releases a half-built one)
+        rc = turn_to(p, m);
+        if (!rc) rc = setup_on(lane0(p, m), pk->prog, pk->prep, &pk->dev[m]);
+        if (!rc && vk_words(pk->dev[m].key.vk) != vk_words(pk->dev[0].key.vk))
+            rc = fail(p, DVT_ERR_DEVICE, "member %zu (device %d) built a verifying key that differs from member 0's", m, member(p, m).eng.device);
     }
-    if (n_members(p) > 1 && select_member(p, 0) && !rc) rc = DVT_ERR_DEVICE;
+    if (turn_to(p, 0) && !rc) rc = DVT_ERR_DEVICE;
     return setup_finish(p, pk, rc, pk_out, vk, vk_len);
 }
 
@@ -1276,18 +1271,18 @@ void dvt_job_free(dvt_prover *p, dvt_job *job) {
 size_t dvt_rv32_job_shards(const dvt_job *job) { return job ? job->n_total : 0; }
 int dvt_rv32_job_shard_member(const dvt_job *job, size_t shard) {
     size_t m = 0;
-    return job && const_cast<dvt_job *>(job)->part_at(shard, &m) ? (int)m : -1;
+    return job && const_cast<dvt_job *>(job)->at(shard, &m) ? (int)m : -1;
 }
 uint32_t dvt_rv32_job_shard_device_rows(const dvt_job *job, size_t shard) {
     size_t m = 0;
-    dvt_job *part = job ? const_cast<dvt_job *>(job)->part_at(shard, &m) : nullptr;
-    return part ? part->at(shard)->device_rows : 0;
+    const ShardJob *s = job ? const_cast<dvt_job *>(job)->at(shard, &m) : nullptr;
+    return s ? s->device_rows : 0;
 }
 uint32_t dvt_rv32_job_shard_chips(const dvt_job *job, size_t shard) {
     size_t m = 0;
-    dvt_job *part = job ? const_cast<dvt_job *>(job)->part_at(shard, &m) : nullptr;
+    const ShardJob *s = job ? const_cast<dvt_job *>(job)->at(shard, &m) : nullptr;
     uint32_t mask = 0;
-    for (int c = 0; part && c < rv32::N_CHIPS; c++) mask |= (uint32_t)part->at(shard)->present[c] << c;
+    for (int c = 0; s && c < rv32::N_CHIPS; c++) mask |= (uint32_t)s->present[c] << c;
     return mask;
 }
 double dvt_rv32_job_exec_wait_seconds(const dvt_job *job) { return job ? job->t_exec_wait : 0.0; }
@@ -1301,16 +1296,14 @@ int dvt_rv32_check_job(dvt_prover *p, const dvt_pk *pk, dvt_job *job, dvt_check_
 
 int dvt_rv32_commit_shard(dvt_prover *p, const dvt_pk *pk, dvt_job *job, size_t shard, uint32_t *header) {
     if (!p || !pk || !job || !header) return fail(p, DVT_ERR_INPUT, "bad argument");
+    if (int rc = same_members(p, pk, job)) return rc;
     size_t m = 0;
-    dvt_job *part = job->part_at(shard, &m);
-    if (!part) return fail(p, DVT_ERR_INPUT, "shard %zu is not held by this job", shard);
-    if (m >= n_members(p) || pk->peers.size() + 1 != n_members(p)) return fail(p, DVT_ERR_INPUT, "proving key or job of a handle with other devices");
-    ShardJob *s = part->at(shard);
+    ShardJob *s = job->at(shard, &m);
+    if (!s) return fail(p, DVT_ERR_INPUT, "shard %zu is not held by this job", shard);
     Guard g(p); if (g.rc) return g.rc;
     if (!s->header_valid) {   // (the prepare pipeline already ran phase 1; a second proof of the same job runs it again)
-        dvt_prover *mem = member(p, m);
-        int rc = m ? select_member(p, m) : DVT_OK;
-        if (!rc) rc = lift(p, mem, shard_commit(lane0(mem), member_key(pk, m), part, *s));
+        int rc = turn_to(p, m);
+        if (!rc) rc = shard_commit(lane0(p, m), member_key(pk, m), job, *s);
         if (rc) return rc;
     }
     memcpy(header, s->header, sizeof(uint32_t) * HEADER_WORDS);
@@ -1329,12 +1322,11 @@ int dvt_rv32_challenges(const uint8_t *vk, size_t vk_len, const uint32_t *header
 int dvt_rv32_prove_shard(dvt_prover *p, const dvt_pk *pk, dvt_job *job, size_t shard, const uint32_t challenges[8], uint8_t **proof,
                          size_t *proof_len) {
     if (!p || !pk || !job || !challenges || (proof && !proof_len)) return fail(p, DVT_ERR_INPUT, "bad argument");
+    if (int rc = same_members(p, pk, job)) return rc;
     size_t m = 0;
-    dvt_job *part = job->part_at(shard, &m);
-    if (!part) return fail(p, DVT_ERR_INPUT, "shard %zu is not held by this job", shard);
+    ShardJob *s = job->at(shard, &m);
+    if (!s) return fail(p, DVT_ERR_INPUT, "shard %zu is not held by this job", shard);
     const size_t G = n_members(p);
-    if (m >= G || pk->peers.size() + 1 != G || (G > 1 && job->parts.size() != G)) return fail(p, DVT_ERR_INPUT, "proving key or job of a handle with other devices");
-    ShardJob *s = part->at(shard);
     PermChallenges gc;
     for (int k = 0; k < 4; k++) {
         if (challenges[k] >= P || challenges[4 + k] >= P) return fail(p, DVT_ERR_INPUT, "challenge not canonical");
@@ -1343,27 +1335,27 @@ int dvt_rv32_prove_shard(dvt_prover *p, const dvt_pk *pk, dvt_job *job, size_t s
     }
     // phase 2 runs ahead on the prover lanes of every member: the first call of a job starts the pipelines, later calls with
     // the same challenges collect from them; anything else drains them (the guard) and takes the one-lane path
-    const size_t k = (size_t)(s - part->shards.data());
-    const PipeClaim claim{part, member_key(pk, m), challenges, k};
+    const size_t k = (size_t)(s - job->parts[m].shards.data());
+    const PipeClaim claim{job, &member_key(pk, m), challenges, k};
     Guard g(p, &claim, m); if (g.rc) return g.rc;
-    dvt_prover *mem = member(p, m);
+    Member &mem = member(p, m);
     long slot = g.slot;
     int rc = DVT_OK;
     if (slot < 0 && (G == 1 || s->header_valid)) {   // (a shard whose phase-1 result was consumed is proven alone: no member runs ahead)
         for (size_t i = 0; i < G && !rc; i++) {      // the claimed shard's member first
             const size_t mm = (m + i) % G;
-            dvt_job *q = job->part(mm);
+            const JobPart &q = job->parts[mm];
             // its own part from the claimed shard; the others from their first shard after it
-            const size_t k0 = mm == m ? k : q->first > shard ? 0 : (shard - q->first) / q->stride + 1;
-            if (G > 1) rc = select_member(p, mm);
-            if (!rc) rc = lift(p, member(p, mm), pipe_start(member(p, mm), member_key(pk, mm), q, k0, gc, G > 1));
+            const size_t k0 = mm == m ? k : q.first > shard ? 0 : (shard - q.first) / q.stride + 1;
+            rc = turn_to(p, mm);
+            if (!rc) rc = pipe_start(p, member(p, mm), member_key(pk, mm), job, k0, gc, G > 1);
         }
         if (rc) { pipe_drain_all(p); return rc; }
-        if (mem->pipe) slot = 0;
+        if (mem.pipe) slot = 0;
     }
-    if (G > 1) rc = select_member(p, m);
+    rc = turn_to(p, m);
     std::vector<uint32_t> words;
-    if (!rc) rc = lift(p, mem, slot >= 0 ? pipe_claim(mem, (size_t)slot, &words) : shard_prove(lane0(mem), member_key(pk, m), part, *s, gc, &words));
+    if (!rc) rc = slot >= 0 ? pipe_claim(p, mem, (size_t)slot, &words) : shard_prove(lane0(p, m), member_key(pk, m), job, *s, gc, &words);
     if (rc && G > 1) pipe_drain_all(p);
     if (rc || !proof) return rc;
     *proof = copy_out(words, proof_len);
@@ -1469,17 +1461,18 @@ int dvt_rv32_debug_traces(const uint8_t *elf, size_t elf_len, const dvt_buf *std
 // test hook: run K0 on shard `shard` of a prepared job and return the device-generated main traces (canonical),
 // same blob layout as dvt_rv32_debug_traces but without preprocessed columns (prep_width = 0)
 int dvt_rv32_debug_device_traces(dvt_prover *p, const dvt_pk *pk, dvt_job *j, size_t shard, uint32_t **blob, size_t *blob_words) {
+    if (!p || !pk || !j || !blob || !blob_words) return fail(p, DVT_ERR_INPUT, "bad argument");
+    if (int rc = same_members(p, pk, j)) return rc;
     size_t mi = 0;
-    dvt_job *part = p && pk && j && blob && blob_words ? j->part_at(shard, &mi) : nullptr;
-    if (!part || mi >= n_members(p) || pk->peers.size() + 1 != n_members(p)) return fail(p, DVT_ERR_INPUT, "bad argument");
+    ShardJob *held = j->at(shard, &mi);
+    if (!held) return fail(p, DVT_ERR_INPUT, "bad argument");
     Guard g(p); if (g.rc) return g.rc;
     std::vector<ChipTrace> traces;
-    ShardJob &sj = *part->at(shard);
-    dvt_prover *mem = member(p, mi);
-    int rc = mi ? select_member(p, mi) : DVT_OK;
-    if (!rc) rc = lift(p, mem, shard_traces(lane0(mem), member_key(pk, mi), part, sj, &traces, false));
+    ShardJob &sj = *held;
+    int rc = turn_to(p, mi);
+    if (!rc) rc = shard_traces(lane0(p, mi), member_key(pk, mi), j, sj, &traces, false);
     if (rc) return rc;
-    HIP_TRY(p, hipStreamSynchronize(mem->eng.stream));
+    HIP_TRY(p, hipStreamSynchronize(member(p, mi).eng.stream));
     const MachineDesc *m = machine_rv32();
     rv32::HostTraces T;
     for (int c = 0; c < rv32::N_CHIPS; c++) T.present[c] = false;

@@ -378,6 +378,34 @@ def test_a_two_member_handle_next_to_a_default_handle(gpu):
     assert got == [[want] * 3, [want] * 3]
 
 
+def test_key_or_job_of_a_handle_with_other_devices_is_refused(gpu):
+    """a job prepared on [0, 0] given to a one-device handle (with that handle's own key), and the one-device key given to
+    the [0, 0] handle with its job: every entry point that takes a key and a job answers DVT_ERR_INPUT; the [0, 0] handle
+    then proves its job to the one-device bytes"""
+    from dvt_circuits_amd import capi
+
+    elf, _ = guests.bignum(1, limbs=12)
+    p1 = _single(10)
+    pk1, vk = p1.setup(elf)
+    want, _ = p1.prove_core(pk1, ())
+    p2 = _multi((0, 0), 10)
+    pk2, vk2 = p2.setup(elf)
+    assert vk2 == vk
+    job, _ = p2.prepare(pk2, ())
+    ch = np.arange(1, 9, dtype=np.uint32)
+    for p in (p1, p2):                       # the key is p1's both times, the job p2's
+        for call in (lambda: p.prove_job(pk1, job), lambda: p.check_job(pk1, job), lambda: p.commit_shard(pk1, job, 0),
+                     lambda: p.prove_shard(pk1, job, 0, ch), lambda: p.debug_device_traces(pk1, job, 0)):
+            with pytest.raises(capi.DvtError) as e:
+                call()
+            assert e.value.code == capi.DVT_ERR_INPUT and "other devices" in e.value.msg
+    assert p2.prove_job(pk2, job) == want
+    p2.job_free(job)
+    for p, pk in ((p1, pk1), (p2, pk2)):
+        p.pk_free(pk)
+        p.close()
+
+
 def test_cli_prove_on_two_members_then_verify(tmp_path):
     """`dvt_prover_host prove --devices 0,0` writes the proof the one-device CLI writes, and `verify` accepts it; a bad list is
     the library's DVT_ERR_INPUT, exit code 1"""
