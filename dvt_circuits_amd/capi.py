@@ -92,6 +92,16 @@ def load():
     lib.dvt_stage_check_constraints.argtypes = [vp, C.c_char_p, u32, vp, vp, u32, u32p, u32p, u32p, C.POINTER(CheckResult)]
     lib.dvt_stage_bus_sums.argtypes = [vp, C.c_char_p, u32, vp, vp, u32, u32p, u32p, u32p, u32p]
     lib.dvt_rv32_check_job.argtypes = [vp, vp, vp, C.POINTER(CheckFinding), sz, C.POINTER(CheckSummary)]
+    lib.dvt_stage_bus_ledger_new.argtypes = [vp, C.c_char_p, u32, u32, C.c_uint64, C.POINTER(vp)]
+    lib.dvt_stage_bus_ledger_add.argtypes = [vp, vp, u32, vp, vp, u32, u32p, u32]
+    lib.dvt_stage_bus_ledger_collect.argtypes = [vp, vp, u32, vp, vp, u32, u32p, u32]
+    lib.dvt_stage_bus_ledger_add_tuple.argtypes = [vp, vp, u32, u32p, u32, C.c_int32, u32, u32]
+    lib.dvt_stage_bus_ledger_close.argtypes = [vp, vp, u32p]
+    lib.dvt_stage_bus_ledger_result.argtypes = [vp, vp, C.POINTER(BusTuple), sz, C.POINTER(sz), u32p]
+    lib.dvt_stage_bus_ledger_free.argtypes = [vp, vp]
+    lib.dvt_rv32_job_bus_tuples.argtypes = [vp, vp, vp, C.POINTER(BusTuple), sz, C.POINTER(sz), u32p]
+    lib.dvt_debug_ledger_key.argtypes = [C.c_uint64, u32, u32, u32p]
+    lib.dvt_debug_ledger_key.restype = C.c_uint64
     lib.dvt_rv32_job_shard_chips.argtypes = [vp, sz]
     lib.dvt_rv32_job_shard_chips.restype = u32
     lib.dvt_machine_setup.argtypes = [vp, C.c_char_p, C.POINTER(HostTrace), sz, C.POINTER(vp), C.POINTER(u8p), C.POINTER(sz)]
@@ -151,6 +161,72 @@ class CheckSummary(C.Structure):
 
 
 CHECK_BUSES = 8   # DVT_CHECK_BUSES
+LEDGER_MAX_ARITY = 40   # DVT_LEDGER_MAX_ARITY
+HOST_CHIP = 0xffffffff  # first_chip of a tuple whose lowest occurrence the caller added
+
+
+class BusTuple(C.Structure):
+    """dvt_bus_tuple: a tuple of a LogUp bus whose signed multiplicities do not cancel"""
+    _fields_ = [("bus", C.c_uint32), ("arity", C.c_uint32), ("net", C.c_uint32), ("n_send", C.c_uint32), ("n_recv", C.c_uint32),
+                ("first_tag", C.c_uint32), ("first_chip", C.c_uint32), ("first_row", C.c_uint32), ("first_interaction", C.c_uint32),
+                ("values", C.c_uint32 * LEDGER_MAX_ARITY)]
+
+    def as_dict(self):
+        d = {k: int(getattr(self, k)) for k, _ in self._fields_[:9]}
+        d["values"] = [int(x) for x in self.values[:min(self.arity, LEDGER_MAX_ARITY)]]
+        return d
+
+
+def _bus_tuples(arr, n):
+    """the first n records of a BusTuple array as dicts (through numpy: a ledger may return hundreds of thousands)"""
+    if not n:
+        return []
+    names = [k for k, _ in BusTuple._fields_[:9]]
+    rows = np.frombuffer(arr, np.uint32).reshape(-1, 9 + LEDGER_MAX_ARITY)[:n].tolist()
+    return [dict(zip(names, r[:9]), values=r[9:9 + min(r[1], LEDGER_MAX_ARITY)]) for r in rows]
+
+
+class BusLedger:
+    """The stage-level bus ledger (dvt_stage_bus_ledger_*): add / add_tuple every table and tuple, close(), and when it
+    reports dirty buckets collect / add_tuple the same again, then result().  Matrices as Prover.stage_bus_sums takes them."""
+
+    def __init__(self, prover, machine, log_buckets=20, cap_slots=1 << 16, seed=1):
+        self.p, self.machine = prover, machine
+        h = C.c_void_p()
+        prover.check(prover.lib.dvt_stage_bus_ledger_new(prover.h, machine.encode(), log_buckets, cap_slots, seed, C.byref(h)))
+        self.h = h
+
+    def _rows(self, fn, chip, t_main, t_prep, log_n, pubs, tag):
+        pv = (C.c_uint32 * max(len(pubs), 1))(*[int(x) for x in pubs])
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        self.p.check(fn(self.p.h, self.h, chip, ptr(t_main), ptr(t_prep), log_n, pv, tag))
+
+    def add(self, chip, t_main, t_prep, log_n, pubs, tag=0):
+        self._rows(self.p.lib.dvt_stage_bus_ledger_add, chip, t_main, t_prep, log_n, pubs, tag)
+
+    def collect(self, chip, t_main, t_prep, log_n, pubs, tag=0):
+        self._rows(self.p.lib.dvt_stage_bus_ledger_collect, chip, t_main, t_prep, log_n, pubs, tag)
+
+    def add_tuple(self, bus, values, sign, mult, tag=0):
+        v = (C.c_uint32 * max(len(values), 1))(*[int(x) for x in values])
+        self.p.check(self.p.lib.dvt_stage_bus_ledger_add_tuple(self.p.h, self.h, bus, v, len(values), sign, mult, tag))
+
+    def close(self):
+        n = C.c_uint32()
+        self.p.check(self.p.lib.dvt_stage_bus_ledger_close(self.p.h, self.h, C.byref(n)))
+        return int(n.value)
+
+    def result(self, cap=1 << 16):
+        """(tuples as dicts sorted by (bus, values), truncated)"""
+        arr = (BusTuple * max(cap, 1))()
+        n, trunc = C.c_size_t(), C.c_uint32()
+        self.p.check(self.p.lib.dvt_stage_bus_ledger_result(self.p.h, self.h, arr, cap, C.byref(n), C.byref(trunc)))
+        return _bus_tuples(arr, n.value), bool(trunc.value)
+
+    def free(self):
+        if self.h:
+            self.p.check(self.p.lib.dvt_stage_bus_ledger_free(self.p.h, self.h))
+            self.h = None
 
 
 class Buf(C.Structure):
@@ -614,6 +690,18 @@ class Prover:
         found = [dict(shard=int(f.shard), chip=int(f.chip), log_n=int(f.log_n), violations=int(f.r.violations), first_row=int(f.r.first_row),
                       first_constraint=int(f.r.first_constraint)) for f in arr[:min(int(s.n_findings), cap)]]
         return summary, found
+
+    def bus_ledger(self, machine, log_buckets=20, cap_slots=1 << 16, seed=1):
+        """a BusLedger on this handle: which tuples of the LogUp buses do not cancel over the tables it is given"""
+        return BusLedger(self, machine, log_buckets, cap_slots, seed)
+
+    def job_bus_tuples(self, pk, job, cap=4096):
+        """The unmatched LogUp tuples of a prepared job (dvt_rv32_job_bus_tuples): (tuples, truncated); a tuple is a dict(bus,
+        arity, net, n_send, n_recv, first_tag = shard position, first_chip, first_row, first_interaction, values)."""
+        arr = (BusTuple * max(cap, 1))()
+        n, trunc = C.c_size_t(), C.c_uint32()
+        self.check(self.lib.dvt_rv32_job_bus_tuples(self.h, pk, job, arr, cap, C.byref(n), C.byref(trunc)))
+        return _bus_tuples(arr, n.value), bool(trunc.value)
 
     def job_shard_chips(self, job, shard):
         """bit c set: shard `shard` (global position) has a table of chip c; 0 when the job does not hold the shard"""

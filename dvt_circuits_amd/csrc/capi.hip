@@ -9,6 +9,7 @@
 #include <chrono>
 
 #include "capi_internal.h"
+#include "ledger_key.h"
 #include "verify_query.h"
 
 using namespace dvt;
@@ -295,7 +296,7 @@ int check_tables(const Lane &c, const MachineDesc *m, const std::vector<CheckTab
 
 extern "C" {
 
-uint32_t dvt_abi_version(void) { return 7; }
+uint32_t dvt_abi_version(void) { return 8; }
 
 int dvt_prover_create(const char *cfg_json, dvt_prover **out) {
     if (!out) return fail(nullptr, DVT_ERR_INPUT, "out == NULL");
@@ -726,6 +727,101 @@ int dvt_stage_bus_sums(dvt_prover *p, const char *machine, uint32_t chip, const 
     for (uint32_t b = 0; b < DVT_CHECK_BUSES; b++)
         for (int k = 0; k < 4; k++) out[b][k] = res[0].bus[b].c[k].canonical();
     return DVT_OK;
+}
+
+// ---- the bus ledger of chip tables (ledger.cuh), on lane 0 of member 0
+static int ledger_stage_rows(dvt_prover *p, dvt_bus_ledger *l, uint32_t chip, const uint32_t *d_main, const uint32_t *d_prep, uint32_t log_n,
+                             const uint32_t *pub, uint32_t tag, bool collect) {
+    if (!p) return DVT_ERR_INPUT;
+    if (!l) return fail(p, DVT_ERR_INPUT, "null ledger");
+    if (l->closed != collect) return fail(p, DVT_ERR_INPUT, collect ? "collect before close" : "add after close");
+    static const uint32_t zero[4] = {0, 0, 0, 0};   // (the checks of chip, log_n and pub that K4 / K5 make; no challenge here)
+    ChipStageArgs a;
+    if (int rc = chip_stage_args(p, l->m->name, chip, log_n, pub, zero, zero, DVT_PATH_DEFAULT, &a)) return rc;
+    if (tag >= (1u << 16)) return fail(p, DVT_ERR_INPUT, "tag %u >= 2^16", tag);
+    if (!d_main || (a.d->prep_w && !d_prep)) return fail(p, DVT_ERR_INPUT, "null matrix");
+    if (collect && !l->n_dirty) return DVT_OK;
+    Guard g(p); if (g.rc) return g.rc;
+    const Lane c = lane0(p);
+    const uint32_t *d_pub = static_cast<const uint32_t *>(c.eng.upload_vec(a.pub));
+    if (!d_pub) return engine_fail(p->err, c.eng);
+    if (int rc = ledger_rows(c, l->dev, *a.d, chip, d_main, a.d->prep_w ? d_prep : nullptr, log_n, d_pub, tag, collect)) return rc;
+    HIP_TRY(p, hipStreamSynchronize(c.eng.stream));
+    return DVT_OK;
+}
+
+int dvt_stage_bus_ledger_new(dvt_prover *p, const char *machine, uint32_t log_buckets, uint32_t cap_slots, uint64_t seed, dvt_bus_ledger **ledger) {
+    if (!p) return DVT_ERR_INPUT;
+    if (!ledger) return fail(p, DVT_ERR_INPUT, "null argument");
+    *ledger = nullptr;
+    const MachineDesc *m = machine_by_name(machine);
+    if (!m) return fail(p, DVT_ERR_INPUT, "unknown machine '%s'", machine ? machine : "(null)");
+    Guard g(p); if (g.rc) return g.rc;
+    std::unique_ptr<dvt_bus_ledger> l(new dvt_bus_ledger());
+    l->m = m;
+    if (int rc = ledger_init(lane0(p), &l->dev, log_buckets, cap_slots, seed)) return rc;
+    HIP_TRY(p, hipStreamSynchronize(eng0(p).stream));
+    *ledger = l.release();
+    return DVT_OK;
+}
+
+int dvt_stage_bus_ledger_add(dvt_prover *p, dvt_bus_ledger *ledger, uint32_t chip, const uint32_t *d_main, const uint32_t *d_prep,
+                             uint32_t log_n, const uint32_t *pub, uint32_t tag) {
+    return ledger_stage_rows(p, ledger, chip, d_main, d_prep, log_n, pub, tag, false);
+}
+
+int dvt_stage_bus_ledger_collect(dvt_prover *p, dvt_bus_ledger *ledger, uint32_t chip, const uint32_t *d_main, const uint32_t *d_prep,
+                                 uint32_t log_n, const uint32_t *pub, uint32_t tag) {
+    return ledger_stage_rows(p, ledger, chip, d_main, d_prep, log_n, pub, tag, true);
+}
+
+int dvt_stage_bus_ledger_add_tuple(dvt_prover *p, dvt_bus_ledger *ledger, uint32_t bus, const uint32_t *values, uint32_t arity, int32_t sign,
+                                   uint32_t mult, uint32_t tag) {
+    if (!p) return DVT_ERR_INPUT;
+    if (!ledger || (arity && !values)) return fail(p, DVT_ERR_INPUT, "null argument");
+    if (ledger->closed && !ledger->n_dirty) return DVT_OK;
+    Guard g(p); if (g.rc) return g.rc;
+    if (int rc = ledger_tuple(lane0(p), ledger->dev, bus, values, arity, sign, mult, tag, ledger->closed)) return rc;
+    HIP_TRY(p, hipStreamSynchronize(eng0(p).stream));
+    return DVT_OK;
+}
+
+int dvt_stage_bus_ledger_close(dvt_prover *p, dvt_bus_ledger *ledger, uint32_t *n_dirty) {
+    if (!p) return DVT_ERR_INPUT;
+    if (!ledger || !n_dirty) return fail(p, DVT_ERR_INPUT, "null argument");
+    if (ledger->closed) return fail(p, DVT_ERR_INPUT, "the ledger is closed already");
+    Guard g(p); if (g.rc) return g.rc;
+    if (int rc = ledger_close(lane0(p), ledger->dev, &ledger->n_dirty)) return rc;
+    ledger->closed = true;
+    *n_dirty = ledger->n_dirty;
+    return DVT_OK;
+}
+
+int dvt_stage_bus_ledger_result(dvt_prover *p, dvt_bus_ledger *ledger, dvt_bus_tuple *out, size_t cap, size_t *n_tuples, uint32_t *truncated) {
+    if (!p) return DVT_ERR_INPUT;
+    if (!ledger || !n_tuples || !truncated || (cap && !out)) return fail(p, DVT_ERR_INPUT, "null argument");
+    if (!ledger->closed) return fail(p, DVT_ERR_INPUT, "result before close");
+    Guard g(p); if (g.rc) return g.rc;
+    std::vector<dvt_bus_tuple> all;
+    bool overflow = false;
+    if (int rc = ledger_records(lane0(p), ledger->dev, &all, &overflow)) return rc;
+    ledger_finish(&all);
+    ledger_copy_out(all, overflow, out, cap, n_tuples, truncated);
+    return DVT_OK;
+}
+
+int dvt_stage_bus_ledger_free(dvt_prover *p, dvt_bus_ledger *ledger) {
+    if (!p) return DVT_ERR_INPUT;
+    if (!ledger) return fail(p, DVT_ERR_INPUT, "null ledger");
+    Guard g(p); if (g.rc) return g.rc;
+    (void)hipStreamSynchronize(eng0(p).stream);
+    ledger_release(&ledger->dev);
+    delete ledger;
+    return DVT_OK;
+}
+
+uint64_t dvt_debug_ledger_key(uint64_t seed, uint32_t bus, uint32_t arity, const uint32_t *values) {
+    return values || !arity ? ledger_key(seed, bus, arity, values) : 0;
 }
 
 // ------------------------------------------------------------------ machine level

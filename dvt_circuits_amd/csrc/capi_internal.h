@@ -197,6 +197,41 @@ struct CheckTableOut {
 int check_tables(const Lane &c, const MachineDesc *m, const std::vector<CheckTable> &tabs, const std::vector<uint32_t> &pub_mont,
                  const CheckChallenges &ch, bool constraints, bool buses, std::vector<CheckTableOut> *out);
 
+// ---- the bus ledger (ledger.cuh) on one lane: dvt_stage_bus_ledger_* and dvt_rv32_job_bus_tuples go through this
+// (ledger.hip).  Buffers come from the lane's pool and go back in ledger_release.
+struct LedgerDev {
+    uint32_t log_buckets = 0, cap_slots = 0;
+    uint64_t seed = 0;
+    DevPool *pool = nullptr;
+    unsigned long long *d_tally = nullptr;   // [2^log_buckets][3]
+    uint32_t *d_dirty = nullptr;             // [2^log_buckets / 32]
+    uint32_t *d_flags = nullptr;             // dirty buckets, overflow
+    void *d_slots = nullptr;                 // [cap_slots] records, made by the first COLLECT launch
+};
+int ledger_init(const Lane &c, LedgerDev *l, uint32_t log_buckets, uint32_t cap_slots, uint64_t seed);
+void ledger_release(LedgerDev *l);
+// one pass (mode: LEDGER_TALLY = 0, LEDGER_COLLECT = 1) over a chip table; d_pub: device, Montgomery
+int ledger_rows(const Lane &c, LedgerDev &l, const ChipDesc &d, uint32_t chip, const uint32_t *main, const uint32_t *prep, uint32_t log_n,
+                const uint32_t *d_pub, uint32_t tag, uint32_t mode);
+// a tuple the host adds (canonical values), keyed on the host
+int ledger_tuple(const Lane &c, LedgerDev &l, uint32_t bus, const uint32_t *values, uint32_t arity, int sign, uint32_t mult, uint32_t tag, uint32_t mode);
+int ledger_close(const Lane &c, LedgerDev &l, uint32_t *n_dirty);   // the bitmap on the device from the ledger's own tallies
+// several ledgers of one shape and seed: their tallies to the host, the bitmap of the sum back to each
+int ledger_tallies(const Lane &c, LedgerDev &l, std::vector<uint64_t> *out);
+uint32_t ledger_dirty_of(const std::vector<uint64_t> &tallies, std::vector<uint32_t> *bitmap);
+int ledger_set_dirty(const Lane &c, LedgerDev &l, const std::vector<uint32_t> &bitmap);
+// appends the used records (balanced ones included); sets *overflow when an occurrence was dropped
+int ledger_records(const Lane &c, LedgerDev &l, std::vector<dvt_bus_tuple> *out, bool *overflow);
+// records of one tuple added up, the balanced ones dropped, the rest sorted by (bus, values)
+void ledger_finish(std::vector<dvt_bus_tuple> *tuples);
+// the caller's share of a finished list
+inline void ledger_copy_out(const std::vector<dvt_bus_tuple> &all, bool overflow, dvt_bus_tuple *out, size_t cap, size_t *n_tuples, uint32_t *truncated) {
+    const size_t n = std::min(all.size(), out ? cap : 0);
+    for (size_t i = 0; i < n; i++) out[i] = all[i];
+    *n_tuples = n;
+    if (truncated) *truncated = overflow || n < all.size();
+}
+
 // a library-allocated copy of w (release with dvt_free); *len = its bytes
 inline uint8_t *copy_out(const std::vector<uint32_t> &w, size_t *len) {
     uint8_t *b = (uint8_t *)malloc(w.size() * 4 + 1);
@@ -236,3 +271,11 @@ struct DeviceQueries {
     void *batch;
 };
 }  // namespace dvt
+
+// a bus ledger of the stage entry points (dvt_stage_bus_ledger_*): on lane 0 of member 0
+struct dvt_bus_ledger {
+    dvt::LedgerDev dev;
+    const dvt::MachineDesc *m = nullptr;
+    bool closed = false;       // TALLY is over: add is refused, collect and result are allowed
+    uint32_t n_dirty = 0;      // what close found
+};

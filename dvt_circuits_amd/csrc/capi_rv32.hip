@@ -1148,6 +1148,114 @@ static int job_check(dvt_prover *p, const dvt_pk *pk, dvt_job *j, dvt_check_find
     return DVT_OK;
 }
 
+// ------------------------------------------------------------------ the job's bus ledger (dvt_rv32_job_bus_tuples)
+// one pass (LEDGER_TALLY = 0 or LEDGER_COLLECT = 1, ledger.cuh) over the tables of one shard on lane 0 of the member that holds
+// it (its device is current), into that member's ledger; the job stays as found, as in shard_check
+static int shard_ledger(const Lane &c, const DeviceKey &key, dvt_job *j, ShardJob &s, size_t pos, LedgerDev &l, uint32_t mode) {
+    const MachineDesc *m = machine_rv32();
+    std::vector<ChipTrace> traces;
+    const bool kept = s.traces_valid;
+    const int rc = shard_traces(c, key, j, s, &traces, true);
+    s.traces_valid = kept;
+    if (rc) return rc;
+    std::vector<uint32_t> pub;
+    for (auto x : s.pubs) pub.push_back(x.v);
+    const uint32_t *d_pub = c.eng.upload_vec(pub);
+    if (!d_pub) return engine_fail(c.err, c.eng);
+    for (auto &t : traces) {
+        const ChipDesc &d = m->chips[t.chip_id];
+        const uint32_t *prep = nullptr;
+        for (auto &pr : key.key.prep)
+            if (pr.chip_id == t.chip_id && pr.log_n == t.log_n) prep = pr.d_trace;
+        if (d.prep_w && !prep) return fail(c.err, DVT_ERR_INPUT, "chip %s of shard %zu has no preprocessed trace of its height in the proving key", d.name, pos);
+        if (int rc2 = ledger_rows(c, l, d, (uint32_t)t.chip_id, t.d_main, prep, t.log_n, d_pub, (uint32_t)pos, mode)) return rc2;
+    }
+    HIP_TRY(c.err, hipStreamSynchronize(c.eng.stream));   // (the next shard's K0 may write the working buffers these launches read)
+    return DVT_OK;
+}
+
+// one pass over every held shard, and the verifier's side of the eight COMMIT tuples (what commit_digest_term stands for:
+// receives of (0x10 0 0 0, k 0 0 0, the bytes of digest word k, 0, 0) on the sys bus) into member 0's ledger
+static int job_ledger_pass(dvt_prover *p, const dvt_pk *pk, dvt_job *j, std::vector<LedgerDev> &ledgers, uint32_t mode) {
+    for (size_t m = 0; m < ledgers.size(); m++) {
+        JobPart &part = j->parts[m];
+        if (int rc = turn_to(p, m)) return rc;
+        for (size_t k = 0; k < part.shards.size(); k++)
+            if (int rc = shard_ledger(lane0(p, m), member_key(pk, m), j, part.shards[k], part.first + k * part.stride, ledgers[m], mode)) return rc;
+    }
+    if (int rc = turn_to(p, 0)) return rc;
+    uint8_t dg[32];
+    sha256(j->public_values.data(), j->public_values.size(), dg);
+    for (uint32_t k = 0; k < 8; k++) {
+        const uint32_t v[14] = {rv32::SYS_COMMIT, 0, 0, 0, k, 0, 0, 0, dg[4 * k], dg[4 * k + 1], dg[4 * k + 2], dg[4 * k + 3], 0, 0};
+        if (int rc = ledger_tuple(lane0(p), ledgers[0], PV_BUS, v, 14, -1, 1, 0, mode)) return rc;
+    }
+    HIP_TRY(p, hipStreamSynchronize(eng0(p).stream));
+    return DVT_OK;
+}
+
+static int job_ledger_run(dvt_prover *p, const dvt_pk *pk, dvt_job *j, std::vector<LedgerDev> &ledgers, uint64_t seed, std::vector<dvt_bus_tuple> *all,
+                          bool *overflow) {
+    constexpr uint32_t LOG_BUCKETS = 20, CAP_SLOTS = 1u << 16;
+    const size_t G = ledgers.size();
+    for (size_t m = 0; m < G; m++) {
+        if (int rc = turn_to(p, m)) return rc;
+        if (int rc = ledger_init(lane0(p, m), &ledgers[m], LOG_BUCKETS, CAP_SLOTS, seed)) return rc;
+    }
+    if (int rc = job_ledger_pass(p, pk, j, ledgers, 0)) return rc;
+    uint32_t n_dirty = 0;
+    if (G == 1) {
+        if (int rc = ledger_close(lane0(p), ledgers[0], &n_dirty)) return rc;
+    } else {   // the members' tallies added mod p on the host; the one bitmap back to every member
+        std::vector<uint64_t> sum, one;
+        for (size_t m = 0; m < G; m++) {
+            if (int rc = turn_to(p, m)) return rc;
+            if (int rc = ledger_tallies(lane0(p, m), ledgers[m], m ? &one : &sum)) return rc;
+            for (size_t i = 0; m && i < sum.size(); i++) sum[i] = (sum[i] + one[i]) % P;
+        }
+        std::vector<uint32_t> bitmap;
+        n_dirty = ledger_dirty_of(sum, &bitmap);
+        for (size_t m = 0; n_dirty && m < G; m++) {
+            if (int rc = turn_to(p, m)) return rc;
+            if (int rc = ledger_set_dirty(lane0(p, m), ledgers[m], bitmap)) return rc;
+        }
+    }
+    all->clear();
+    *overflow = false;
+    if (!n_dirty) return DVT_OK;
+    if (int rc = job_ledger_pass(p, pk, j, ledgers, 1)) return rc;
+    for (size_t m = 0; m < G; m++) {
+        if (int rc = turn_to(p, m)) return rc;
+        if (int rc = ledger_records(lane0(p, m), ledgers[m], all, overflow)) return rc;
+    }
+    ledger_finish(all);
+    return DVT_OK;
+}
+
+static int job_bus_tuples(dvt_prover *p, const dvt_pk *pk, dvt_job *j, dvt_bus_tuple *out, size_t cap, size_t *n_tuples, uint32_t *truncated) {
+    if (int rc = same_members(p, pk, j)) return rc;
+    if (j->n_total > (1u << 16)) return fail(p, DVT_ERR_INPUT, "a job of %zu shards: the ledger tags at most 2^16", (size_t)j->n_total);
+    const CheckChallenges ch = check_challenges(pk->dev[0].key.vk, j);
+    uint64_t seed = (uint64_t)ch.xi.c[0].v | ((uint64_t)ch.xi.c[1].v << 32);
+    std::vector<dvt_bus_tuple> all;
+    bool overflow = false;
+    int rc = DVT_OK;
+    for (int attempt = 0; attempt < 2 && !rc; attempt++) {   // records overflowed: once more with another seed
+        std::vector<LedgerDev> ledgers(n_members(p));
+        rc = job_ledger_run(p, pk, j, ledgers, seed, &all, &overflow);
+        for (size_t m = ledgers.size(); m-- > 0;) {   // member 0 last: its device stays current
+            if (turn_to(p, m)) continue;
+            (void)hipStreamSynchronize(member(p, m).eng.stream);
+            ledger_release(&ledgers[m]);
+        }
+        if (!overflow) break;
+        seed = seed * 0x9e3779b97f4a7c15ull + 1;
+    }
+    if (rc) return rc;
+    ledger_copy_out(all, overflow, out, cap, n_tuples, truncated);
+    return DVT_OK;
+}
+
 static std::vector<uint32_t> trace_blob(const rv32::HostTraces &T, const rv32::HostPrep *prep) {
     const MachineDesc *m = machine_rv32();
     std::vector<uint32_t> w;
@@ -1286,6 +1394,14 @@ uint32_t dvt_rv32_job_shard_chips(const dvt_job *job, size_t shard) {
     return mask;
 }
 double dvt_rv32_job_exec_wait_seconds(const dvt_job *job) { return job ? job->t_exec_wait : 0.0; }
+
+int dvt_rv32_job_bus_tuples(dvt_prover *p, const dvt_pk *pk, dvt_job *job, dvt_bus_tuple *out, size_t cap, size_t *n_tuples, uint32_t *truncated) {
+    if (!p) return DVT_ERR_INPUT;
+    if (!pk || !job || !n_tuples || !truncated || (cap && !out)) return fail(p, DVT_ERR_INPUT, "null argument");
+    if (!pk->is_rv32) return fail(p, DVT_ERR_INPUT, "not an rv32 proving key");
+    Guard g(p); if (g.rc) return g.rc;
+    return job_bus_tuples(p, pk, job, out, cap, n_tuples, truncated);
+}
 
 int dvt_rv32_check_job(dvt_prover *p, const dvt_pk *pk, dvt_job *job, dvt_check_finding *findings, size_t cap, dvt_check_summary *summary) {
     if (!p || !pk || !job || !summary || (cap && !findings)) return fail(p, DVT_ERR_INPUT, "null argument");

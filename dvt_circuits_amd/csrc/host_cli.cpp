@@ -16,7 +16,8 @@
 // dvt_prover_create.
 // check (no counterpart in the reference; SP1's debug_constraints) prepares the job as prove does and checks its trace rows
 // against the AIR on the GPU (dvt_rv32_check_job) instead of proving: "clean: N shards, M chip tables, T ms" and exit code 0,
-// or one line per finding and per unbalanced bus and exit code 1.
+// or one line per finding and per unbalanced bus and exit code 1; after the bus lines, the tuples that do not cancel
+// (dvt_rv32_job_bus_tuples): at most 32 lines, then "... and N more".
 // get-schema / validate-schema / node are product UI outside the accelerated path and are not provided.
 #include <cstdio>
 #include <cstdlib>
@@ -37,6 +38,18 @@ static bool read_file(const std::string &path, std::vector<uint8_t> *out) {
 static int die(const std::string &m) {
     fprintf(stderr, "Error: %s\n", m.c_str());
     return 1;
+}
+// bus and chip ids of the rv32 machine (tools/airgen/rv32.py)
+static const char *const BUS_NAMES[] = {"?", "program", "byte", "mem", "image", "sys", "alu"};
+static const char *const CHIP_NAMES[] = {"program", "byte", "cpu", "mem_image", "mem_init", "shift", "muldiv", "sha_extend", "sha_compress",
+                                         "fp_op", "fp2_op", "bls_g1", "secp_k1", "u256_mul"};
+static void print_bus_tuple(const dvt_bus_tuple &t) {
+    printf("bus %s: (", t.bus < sizeof BUS_NAMES / sizeof *BUS_NAMES ? BUS_NAMES[t.bus] : "?");
+    for (uint32_t k = 0; k < t.arity && k < DVT_LEDGER_MAX_ARITY; k++) printf(k ? " %u" : "%u", t.values[k]);
+    printf(") net %u, sends %u, receives %u, first at ", t.net, t.n_send, t.n_recv);
+    if (t.first_chip == 0xffffffffu) printf("the verifier's side\n");
+    else printf("shard %u chip %s row %u interaction %u\n", t.first_tag, t.first_chip < sizeof CHIP_NAMES / sizeof *CHIP_NAMES ? CHIP_NAMES[t.first_chip] : "?",
+                t.first_row, t.first_interaction);
 }
 
 int main(int argc, char **argv) {
@@ -148,6 +161,14 @@ int main(int argc, char **argv) {
         if (sum.n_findings > found.size()) printf("... and %zu more chip tables with violations\n", sum.n_findings - found.size());
         for (uint32_t b = 0; b < DVT_CHECK_BUSES; b++)
             if (sum.unbalanced_buses >> b & 1) printf("bus %u: the LogUp sums over all chips and shards do not balance\n", b);
+        if (sum.unbalanced_buses) {   // the tuples behind the mask (the bus ledger)
+            std::vector<dvt_bus_tuple> tuples(4096);
+            size_t n = 0;
+            uint32_t truncated = 0;
+            if (dvt_rv32_job_bus_tuples(p, pk, job, tuples.data(), tuples.size(), &n, &truncated)) return die(std::string("Check failed: ") + dvt_last_error(p));
+            for (size_t i = 0; i < n && i < 32; i++) print_bus_tuple(tuples[i]);
+            if (n > 32) printf("... and %zu more%s\n", n - 32, truncated ? " (at least: the ledger was truncated)" : "");
+        }
         dvt_job_free(p, job);
         dvt_pk_free(p, pk);
         dvt_prover_destroy(p);

@@ -32,6 +32,8 @@ struct VerifierPoint {
     Fp4 perm_alpha, cum_over_n, sel_first, sel_last, sel_trans;
 };
 
+struct LedgerArgs;   // ledger.cuh
+
 struct ChipDesc {
     const char *name;
     int main_w, prep_w, n_pub, n_constraints, n_interactions, max_arity;
@@ -45,6 +47,9 @@ struct ChipDesc {
     // translation units of their own (check_rv32.hip, check_rv32_wide.hip).
     hipError_t (*launch_check)(hipStream_t, const CheckArgs &) = nullptr;
     hipError_t (*launch_bus)(hipStream_t, const BusArgs &) = nullptr;
+    // the bus ledger's pass over the chip's interactions (ledger.cuh), from further units: ledger_toy.hip, ledger_rv32.hip,
+    // ledger_rv32_wide.hip
+    hipError_t (*launch_ledger)(hipStream_t, const LedgerArgs &) = nullptr;
 };
 
 struct MachineDesc {

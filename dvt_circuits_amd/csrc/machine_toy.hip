@@ -3,7 +3,16 @@
 #include "gen/air_toy.inc"
 
 namespace dvt {
-#define DVT_X(i, A) with_check_fns<A>(make_chip_desc<A>()),
+void toy_ledger_fns(int chip, ChipDesc *d);   // ledger_toy.hip
+namespace {
+template <int I, class A>
+ChipDesc chip_desc_here() {
+    ChipDesc d = with_check_fns<A>(make_chip_desc<A>());
+    toy_ledger_fns(I, &d);
+    return d;
+}
+}  // namespace
+#define DVT_X(i, A) chip_desc_here<i, A>(),
 static const ChipDesc toy_chips[] = {DVT_AIR_TOY_CHIPS(DVT_X)};
 #undef DVT_X
 static const MachineDesc toy_machine = {"toy", air_toy::N_CHIPS, toy_chips};

@@ -108,7 +108,7 @@ void dvt_free(void *ptr);
 /* ABI version of this header (4: "devices", dvt_prover_device_count, dvt_prover_device, dvt_rv32_job_shard_member;
  * 5: dvt_rv32_job_shard_device_rows; 6: dvt_stage_check_constraints, dvt_stage_bus_sums, dvt_rv32_check_job,
  * dvt_rv32_job_shard_chips; 7: dvt_prover_verify, dvt_prover_machine_verify, dvt_stage_sponge_rows,
- * dvt_stage_verify_paths, dvt_prover_verify_times) */
+ * dvt_stage_verify_paths, dvt_prover_verify_times; 8: dvt_stage_bus_ledger_*, dvt_rv32_job_bus_tuples) */
 uint32_t dvt_abi_version(void);
 /* the handle's hipStream_t (for event timing by the caller) */
 void *dvt_stream(dvt_prover *p);
@@ -231,6 +231,46 @@ int dvt_stage_check_constraints(dvt_prover *p, const char *machine, uint32_t chi
 int dvt_stage_bus_sums(dvt_prover *p, const char *machine, uint32_t chip, const uint32_t *d_main, const uint32_t *d_prep,
                        uint32_t log_n, const uint32_t *pub, const uint32_t perm_alpha[4], const uint32_t beta[4],
                        uint32_t out[DVT_CHECK_BUSES][4]);
+
+/* The bus ledger: WHICH tuples of the LogUp buses do not cancel (dvt_stage_bus_sums only says which bus).  A tuple is
+ * (bus, arity, canonical values); an occurrence is one interaction of one row with a non-zero multiplicity, or a tuple the
+ * caller adds.  Two passes over the same chip tables:
+ *   new -> add / add_tuple (TALLY: every occurrence adds its signed multiplicity, weighted three ways, to the bucket its
+ *   64-bit key selects; a balanced tuple adds up to 0 mod p) -> close (n_dirty: buckets with a non-zero sum; 0 means every
+ *   bus balances, and nothing more is needed) -> collect / add_tuple over the SAME tables and tuples (COLLECT: the
+ *   occurrences of the dirty buckets go into a table of cap_slots records, one per tuple) -> result -> free.
+ * The matrices are those of dvt_stage_bus_sums (device, internal representation, column-major); pub: the chip's public
+ * values, canonical.  tag (< 2^16) is the caller's label of a table, e.g. a shard position; it comes back in first_tag.
+ * Every call runs on device 0 of the handle and synchronises.  Wrong order (collect before close, add after it), a NULL, a
+ * chip out of range, log_n > 22, an arity above DVT_LEDGER_MAX_ARITY or a tag >= 2^16 is DVT_ERR_INPUT; a HIP failure is
+ * DVT_ERR_DEVICE.  log_buckets: 10..24; seed: any (it keys the tuples: a retry after truncation takes another).
+ * result: the tuples whose net multiplicity is not 0, sorted by (bus, values); at most cap are written.  *truncated is set
+ * when the record table overflowed (64 probes found no free record: that occurrence was dropped) or cap is too small; the
+ * tuples that are returned are exact all the same: a tuple that owns a record saw all of its occurrences.
+ * A diagnostic, not a soundness boundary: an unmatched tuple goes unseen only when the three sums of its bucket cancel
+ * against other unmatched tuples (about 2^-60); the seed does not depend on the rows. */
+#define DVT_LEDGER_MAX_ARITY 40u /* rv32's widest tuple has 38 values */
+typedef struct {
+    uint32_t bus, arity, net; /* net: sum of the signed multiplicities mod p, canonical, never 0 */
+    uint32_t n_send, n_recv;  /* occurrences with a non-zero multiplicity, saturating */
+    uint32_t first_tag, first_chip, first_row, first_interaction; /* lowest occurrence; chip 0xffffffff: added by the caller */
+    uint32_t values[DVT_LEDGER_MAX_ARITY]; /* canonical */
+} dvt_bus_tuple;
+typedef struct dvt_bus_ledger dvt_bus_ledger;
+int dvt_stage_bus_ledger_new(dvt_prover *p, const char *machine, uint32_t log_buckets, uint32_t cap_slots, uint64_t seed,
+                             dvt_bus_ledger **ledger);
+int dvt_stage_bus_ledger_add(dvt_prover *p, dvt_bus_ledger *ledger, uint32_t chip, const uint32_t *d_main, const uint32_t *d_prep,
+                             uint32_t log_n, const uint32_t *pub, uint32_t tag);
+/* a term of the caller's (sign > 0: a send of multiplicity mult, else a receive); before close it tallies, after it collects */
+int dvt_stage_bus_ledger_add_tuple(dvt_prover *p, dvt_bus_ledger *ledger, uint32_t bus, const uint32_t *values, uint32_t arity,
+                                   int32_t sign, uint32_t mult, uint32_t tag);
+int dvt_stage_bus_ledger_close(dvt_prover *p, dvt_bus_ledger *ledger, uint32_t *n_dirty);
+/* a no-op when close found no dirty bucket */
+int dvt_stage_bus_ledger_collect(dvt_prover *p, dvt_bus_ledger *ledger, uint32_t chip, const uint32_t *d_main, const uint32_t *d_prep,
+                                 uint32_t log_n, const uint32_t *pub, uint32_t tag);
+int dvt_stage_bus_ledger_result(dvt_prover *p, dvt_bus_ledger *ledger, dvt_bus_tuple *out, size_t cap, size_t *n_tuples,
+                                uint32_t *truncated);
+int dvt_stage_bus_ledger_free(dvt_prover *p, dvt_bus_ledger *ledger);
 
 /* The two hashing kernels of the device verifier (dvt_prover_verify), driven at chosen shapes without a proof.  Both
  * take and return HOST arrays of canonical words (a word >= p is DVT_ERR_INPUT) and are synchronous.
@@ -412,6 +452,16 @@ typedef struct {
 } dvt_check_summary;
 int dvt_rv32_check_job(dvt_prover *p, const dvt_pk *pk, dvt_job *job, dvt_check_finding *findings, size_t cap,
                        dvt_check_summary *summary);
+/* The unmatched LogUp tuples of a job (the bus ledger, dvt_stage_bus_ledger_*): what dvt_rv32_check_job's bus mask stands
+ * for.  The traces of every shard the job holds are taken as dvt_rv32_check_job takes them, on the device that holds the
+ * shard, and the job is left as found; first_tag is the shard's position, first_chip 0xffffffff one of the eight verifier-
+ * side COMMIT tuples, which are always added.  With several devices each tallies into a ledger of its own; the host adds
+ * the tallies, hands the dirty buckets back and merges the records by exact tuple.  On a job that holds only part of the
+ * execution the result is what does not cancel among the held shards.  An honest whole job returns no tuple after the
+ * TALLY pass alone.  2^20 buckets, 2^16 records, the seed from the check's transcript; when the records overflow the call
+ * runs once more with another seed, and *truncated is set if that overflows too (or cap is too small). */
+int dvt_rv32_job_bus_tuples(dvt_prover *p, const dvt_pk *pk, dvt_job *job, dvt_bus_tuple *out, size_t cap, size_t *n_tuples,
+                            uint32_t *truncated);
 /* test hook: run K0 on one shard of a prepared job and return the device-generated main traces
  * (canonical); blob layout as dvt_rv32_debug_traces with prep_width = 0. */
 int dvt_rv32_debug_device_traces(dvt_prover *p, const dvt_pk *pk, dvt_job *job, size_t shard, uint32_t **blob,
@@ -444,6 +494,8 @@ double dvt_debug_exec_rate(const uint8_t *elf, size_t elf_len, const dvt_buf *st
 /* test hook, host only: FP64 formulation of Poseidon2 (csrc/poseidon2_f64.cuh, what the hashing kernels run)
  * against the integer permutation on n states; returns the number of differing words (0 = identical) */
 uint64_t dvt_debug_p2_f64_selfcheck(uint32_t n, uint32_t seed);
+/* test hook, host only: the bus ledger's key of a tuple (csrc/ledger_key.h: the function the kernels key the rows with) */
+uint64_t dvt_debug_ledger_key(uint64_t seed, uint32_t bus, uint32_t arity, const uint32_t *values);
 
 /* Host side of the reference's prove()/execute() above the prover call: the typed JSON input of
  * `--type` (bad-share | finalization | bad-partial-key | bad-encrypted-share; crates/dkg/src/types.rs:26-203)
