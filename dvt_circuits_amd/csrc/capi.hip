@@ -324,6 +324,9 @@ int dvt_prover_create(const char *cfg_json, dvt_prover **out) {
     const int parts_parallel_log = cfg_int(cfg_json, "parts_parallel_log", (int)PARTS_PARALLEL_LOG);
     if (parts_parallel_log < -1 || parts_parallel_log > (int)PARTS_PARALLEL_LOG)
         return fail(nullptr, DVT_ERR_INPUT, "parts_parallel_log must be -1..%u", PARTS_PARALLEL_LOG);
+    const int verify_chunk_words = cfg_int(cfg_json, "verify_chunk_words", (int)vq::CHUNK_WORDS);
+    if (verify_chunk_words <= 0) return fail(nullptr, DVT_ERR_INPUT, "verify_chunk_words must be positive");
+    p->vq_chunk_words = (size_t)verify_chunk_words;
     {
         // phase-2 lanes (of every member): the config key, else DVT_LANES (same-process A/B measurements), else 2, which
         // measured best with one member and with two members on one device (profiles/README.md, round 5); profile mode

@@ -603,7 +603,7 @@ void stage_free(Stage *s) { delete s; }
 
 DeviceQueries::DeviceQueries(dvt_prover *p) : p(p), batch(nullptr) {
     if (!p->vq_stage) p->vq_stage = new vq::Stage();
-    batch = new vq::Batch(lane0(p), *p->vq_stage);
+    batch = new vq::Batch(lane0(p), *p->vq_stage, p->vq_chunk_words);
 }
 DeviceQueries::~DeviceQueries() { delete static_cast<vq::Batch *>(batch); }
 void DeviceQueries::add(const ShardQueryCtx &ctx, const uint32_t *words, size_t nwords) {

@@ -55,6 +55,9 @@ typedef struct dvt_pk dvt_pk;
  * instead of keeping them in HBM (about 3 GB per 2^21-cycle shard) between the two phases.  parts_parallel_log: tables of
  * at most 2^parts_parallel_log rows compute their LogUp rows (K4) and quotient (K5) one constraint group per thread, taller
  * ones one row per thread; -1 = never, at most 15 (DVT_ERR_INPUT above).  The proof bytes do not depend on it.
+ * "verify_chunk_words" (default 4194304; 0 or less is DVT_ERR_INPUT): proof words per chunk of dvt_prover_verify's device
+ * part.  Shards are gathered into a chunk until the next one would not fit; a single shard larger than the chunk goes
+ * alone.  Answers do not depend on it (a test knob, like parts_parallel_log: small proofs reach the multi-chunk path).
  * "lanes" (1..3, default 2; without the key the environment variable DVT_LANES sets the default; anything else is
  * DVT_ERR_INPUT): prover lanes that run phase 2 of different shards of one job at the same time, each with its own HIP
  * stream, device arena and buffer cache.  The further lanes are created on the first job that holds at least two shards;

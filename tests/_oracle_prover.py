@@ -167,9 +167,11 @@ def prep_root_of(chips):
 STAGE_SECONDS = {}     # wall time of the stages of the LAST prove_shard call (bench.py prints them beside the GPU's stage_ms)
 
 
-def prove_shard(machine, chips, pubs, num_queries, pow_bits, perm_challenges=None, prep_chips=None):
+def prove_shard(machine, chips, pubs, num_queries, pow_bits, perm_challenges=None, prep_chips=None, cheat=None):
     """chips: list of dict(chip_id, main [w][N], prep [w][N]) sorted by chip id (every chip of the shard).
-    Returns the shard proof bytes and the preprocessed root (8 ints)."""
+    Returns the shard proof bytes and the preprocessed root (8 ints).
+    cheat: None, or a tests/_forger.py Forgery whose hooks deviate from the protocol at one place each (a dishonest prover:
+    every step after a deviation is the honest one on the altered data).  The honest path only tests it for None."""
     import time
 
     t_mark = [time.perf_counter()]
@@ -213,7 +215,7 @@ def prove_shard(machine, chips, pubs, num_queries, pow_bits, perm_challenges=Non
     # 1. main
     for c in cs:
         c["main_lde"] = orc.coset_lde(c["main"], 1, G)
-    main_layers, main_root = commit([c["main_lde"] for c in cs])
+    main_layers, main_root = commit([c["main_lde"] for c in cs] if cheat is None else cheat.committed("main", cs, cs))
     ch.observe(main_root)
     ch.observe([npub])
     ch.observe(pubs[:npub])
@@ -233,7 +235,9 @@ def prove_shard(machine, chips, pubs, num_queries, pow_bits, perm_challenges=Non
         perm, cum = air.perm_trace(c["id"], c["main"], c["prep"] if c["prep"] is not None else np.zeros((1, c["n"]), np.uint32), pubs, perm_alpha, beta)
         c["perm"], c["cumsum"] = perm, cum.tolist()
         c["perm_lde"] = orc.coset_lde(perm, 1, G)
-    perm_layers, perm_root = commit([c["perm_lde"] for c in perm_cs]) if perm_cs else (None, [0] * 8)
+    if cheat is not None:
+        cheat.cumsums(cs)
+    perm_layers, perm_root = commit([c["perm_lde"] for c in perm_cs] if cheat is None else cheat.committed("perm", perm_cs, cs)) if perm_cs else (None, [0] * 8)
     perm_log_h = max([c["log_n"] + 1 for c in perm_cs], default=0)
     ch.observe(perm_root)
     for c in cs:
@@ -251,7 +255,7 @@ def prove_shard(machine, chips, pubs, num_queries, pow_bits, perm_challenges=Non
         c["quot"] = out
         w2inv = pow(two_adic(c["log_n"] + 1), P - 2, P)
         c["quot_lde"] = np.concatenate([orc.coset_lde(out[:4], 1, 1), orc.coset_lde(out[4:], 1, w2inv)])
-    quot_layers, quot_root = commit([c["quot_lde"] for c in cs])
+    quot_layers, quot_root = commit([c["quot_lde"] for c in cs] if cheat is None else cheat.committed("quot", cs, cs))
     ch.observe(quot_root)
     lap("quotient")
     # 4. openings
@@ -271,6 +275,8 @@ def prove_shard(machine, chips, pubs, num_queries, pow_bits, perm_challenges=Non
             c["open"][name + "_n"] = evals(m, c["log_n"], 1, zn) if m is not None else []
         s1 = G * two_adic(c["log_n"] + 1) % P
         c["open"]["quot"] = evals(c["quot"][:4], c["log_n"], G, zeta) + evals(c["quot"][4:], c["log_n"], s1, zeta)
+    if cheat is not None:
+        cheat.openings(cs)      # claimed values; from here on c["*_lde"] are the committed matrices
     for c in cs:
         for k in ("prep_l", "prep_n", "main_l", "main_n", "perm_l", "perm_n", "quot"):
             ch.observe_values(c["open"][k])
@@ -305,6 +311,8 @@ def prove_shard(machine, chips, pubs, num_queries, pow_bits, perm_challenges=Non
     fri_layers, fri_roots, fri_vecs = [], [], []
     for lm in range(hmax, 1, -1):
         half = 1 << (lm - 1)
+        if cheat is not None:
+            cur = cheat.layer(len(fri_vecs), cur)
         mat = np.ascontiguousarray(np.concatenate([cur[:half].T, cur[half:].T]))  # [8][half]
         layers, root = commit([mat])
         fri_layers.append(layers)
@@ -316,16 +324,23 @@ def prove_shard(machine, chips, pubs, num_queries, pow_bits, perm_challenges=Non
         r = ro.get(lm - 1)
         lib.orc_fri_fold(_p(np.ascontiguousarray(cur)), lm, _p(_a(fb)), _p(np.ascontiguousarray(r)) if r is not None else None, _p(nxt))
         cur = nxt
-    assert cur.shape[0] == 2 and (cur[0] == cur[1]).all(), "oracle: FRI final polynomial is not constant"
-    final_poly = cur[0].tolist()
+    if cheat is None:
+        assert cur.shape[0] == 2 and (cur[0] == cur[1]).all(), "oracle: FRI final polynomial is not constant"
+        final_poly = cur[0].tolist()
+    else:
+        final_poly = cheat.final(cur)
     ch.observe(final_poly)
     # 7. proof of work: smallest witness
     base = list(ch.state)
     base[: len(ch.inp)] = ch.inp
     w = int(lib.orc_pow_grind(_p(np.array(base, np.uint32)), len(ch.inp), pow_bits))     # smallest witness (C + OpenMP)
+    if cheat is not None:
+        w = cheat.witness(ch, w, pow_bits)
     ch.observe([w])
-    assert ch.sample_bits(pow_bits) == 0
+    assert ch.sample_bits(pow_bits) == 0 or (cheat is not None and not cheat.witness_valid)
     idx = [ch.sample_bits(hmax) for _ in range(num_queries)]
+    if cheat is not None:
+        cheat.done(air, cs, idx)
     # 8. serialise
     W = Writer()
     W.u32(0x31505644)
