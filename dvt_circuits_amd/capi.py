@@ -101,9 +101,16 @@ def load():
     lib.dvt_stage_bus_ledger_free.argtypes = [vp, vp]
     lib.dvt_rv32_job_bus_tuples.argtypes = [vp, vp, vp, C.POINTER(BusTuple), sz, C.POINTER(sz), u32p]
     lib.dvt_debug_ledger_key.argtypes = [C.c_uint64, u32, u32, u32p]
+    u64 = C.c_uint64
+    lib.dvt_stage_hunt_cells.argtypes = [vp, C.c_char_p, u32, vp, vp, u32, u32p, u64, u32p, u32, u32, u32, u64, u32p, u8p]
+    lib.dvt_stage_hunt_pairs.argtypes = [vp, C.c_char_p, u32, vp, vp, u32, u32p, u64, u32p, u32, u32p, u32, u32, u32, u32, u64,
+                                         C.POINTER(Escape), sz, C.POINTER(u64), C.POINTER(u64)]
+    lib.dvt_rv32_hunt_shard.argtypes = [vp, vp, vp, sz, u32, u64, u32p, u32, u32, u32p, u32, u32, u32, u32, u64, u32p, u8p,
+                                        C.POINTER(Escape), sz, C.POINTER(u64), C.POINTER(u64)]
     lib.dvt_debug_ledger_key.restype = C.c_uint64
     lib.dvt_rv32_job_shard_chips.argtypes = [vp, sz]
     lib.dvt_rv32_job_shard_chips.restype = u32
+    lib.dvt_rv32_job_shard_chip_shape.argtypes = [vp, sz, u32, u32p, u32p]
     lib.dvt_machine_setup.argtypes = [vp, C.c_char_p, C.POINTER(HostTrace), sz, C.POINTER(vp), C.POINTER(u8p), C.POINTER(sz)]
     lib.dvt_pk_free.argtypes = [vp, vp]
     lib.dvt_pk_free.restype = None
@@ -184,6 +191,23 @@ def _bus_tuples(arr, n):
     names = [k for k, _ in BusTuple._fields_[:9]]
     rows = np.frombuffer(arr, np.uint32).reshape(-1, 9 + LEDGER_MAX_ARITY)[:n].tolist()
     return [dict(zip(names, r[:9]), values=r[9:9 + min(r[1], LEDGER_MAX_ARITY)]) for r in rows]
+
+
+HUNT_MAX_DELTAS = 8   # DVT_HUNT_MAX_DELTAS
+
+
+class Escape(C.Structure):
+    """dvt_escape: a pair of changes that nothing rejects although one of them alone is rejected"""
+    _fields_ = [("row", C.c_uint32), ("n_cells", C.c_uint32), ("col", C.c_uint32 * 2), ("row_off", C.c_uint32 * 2),
+                ("delta", C.c_uint32 * 2), ("alone", C.c_uint32)]
+
+
+def _escapes(arr, n):
+    """the first n records of an Escape array as dicts"""
+    if not n:
+        return []
+    rows = np.frombuffer(arr, np.uint32).reshape(-1, 9)[:n].tolist()
+    return [dict(row=r[0], n_cells=r[1], col=r[2:4], row_off=r[4:6], delta=r[6:8], alone=r[8]) for r in rows]
 
 
 class BusLedger:
@@ -551,6 +575,62 @@ class Prover:
                                                out.ctypes.data_as(u32p)))
         return out
 
+    def _hunt_cells(self, call, main_w, deltas, row_count, want_map):
+        dl = np.ascontiguousarray(deltas, dtype=np.uint32)
+        counts = np.zeros((main_w, max(dl.size, 1)), np.uint32)
+        fmap = np.zeros((max(dl.size, 1), main_w, max(row_count, 1)), np.uint8) if want_map else None
+        self.check(call(dl.ctypes.data_as(u32p), dl.size, counts.ctypes.data_as(u32p), fmap.ctypes.data_as(u8p) if want_map else None))
+        return counts[:, :dl.size], (fmap[:dl.size, :, :row_count] if want_map else None)
+
+    def _hunt_pairs(self, call, deltas, cols, cap):
+        dl = np.ascontiguousarray(deltas, dtype=np.uint32)
+        cl = np.ascontiguousarray(cols, dtype=np.uint32) if cols is not None else None
+        arr = (Escape * max(cap, 1))()
+        n_rep, n_tried = C.c_uint64(), C.c_uint64()
+        self.check(call(dl.ctypes.data_as(u32p), dl.size, cl.ctypes.data_as(u32p) if cl is not None else None, cl.size if cl is not None else 0,
+                        arr, cap, C.byref(n_rep), C.byref(n_tried)))
+        return dict(reported=_escapes(arr, min(int(n_rep.value), cap)), n_reported=int(n_rep.value), n_tried=int(n_tried.value))
+
+    def stage_hunt_cells(self, machine, chip, t_main, t_prep, log_n, pubs, main_w, deltas, row_first=0, row_count=None, seed=1,
+                         max_evals=0, want_map=True):
+        """Single-cell forgeries of one chip table (dvt_stage_hunt_cells; matrices as stage_check_constraints takes them).
+        Returns (free_counts [main_w][n_deltas], free_map [n_deltas][main_w][row_count] of 0 / 1 or None): where the change
+        of a cell by a delta escapes every constraint and the LogUp multiset.  A table that is not honest raises
+        DvtError(DVT_ERR_REJECTED)."""
+        pv = (C.c_uint32 * max(len(pubs), 1))(*[int(x) for x in pubs])
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        rc = (1 << log_n) - row_first if row_count is None else row_count
+        call = lambda dl, nd, counts, fmap: self.lib.dvt_stage_hunt_cells(self.h, machine.encode(), chip, ptr(t_main), ptr(t_prep), log_n, pv, seed,
+                                                                         dl, nd, row_first, rc, max_evals, counts, fmap)
+        return self._hunt_cells(call, main_w, deltas, rc, want_map)
+
+    def stage_hunt_pairs(self, machine, chip, t_main, t_prep, log_n, pubs, deltas, cols=None, adjacent=False, row_first=0, row_count=None,
+                         seed=1, max_evals=0, cap=4096):
+        """Two-cell forgeries of one chip table (dvt_stage_hunt_pairs).  Returns dict(reported, n_reported, n_tried): reported
+        = at most cap dicts(row, n_cells, col, row_off, delta, alone) sorted by (row, col, delta): pairs that escape although
+        one of their changes alone is caught."""
+        pv = (C.c_uint32 * max(len(pubs), 1))(*[int(x) for x in pubs])
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        rc = (1 << log_n) - row_first if row_count is None else row_count
+        call = lambda dl, nd, cl, nc, arr, cp, a, b: self.lib.dvt_stage_hunt_pairs(self.h, machine.encode(), chip, ptr(t_main), ptr(t_prep), log_n, pv,
+                                                                                  seed, dl, nd, cl, nc, int(adjacent), row_first, rc, max_evals,
+                                                                                  arr, cp, a, b)
+        return self._hunt_pairs(call, deltas, cols, cap)
+
+    def hunt_shard(self, pk, job, shard, chip, deltas, pairs=False, cols=None, adjacent=False, row_first=0, row_count=None,
+                   seed=1, max_evals=0, cap=4096, want_map=True):
+        """The same two hunts on chip `chip` of a shard of a prepared job (dvt_rv32_hunt_shard): what stage_hunt_cells
+        (pairs False) or stage_hunt_pairs (pairs True) returns."""
+        main_w, log_n = self.job_shard_chip_shape(job, shard, chip)
+        rc = (1 << log_n) - row_first if row_count is None else row_count
+        if pairs:
+            call = lambda dl, nd, cl, nc, arr, cp, a, b: self.lib.dvt_rv32_hunt_shard(self.h, pk, job, shard, chip, seed, dl, nd, 1, cl, nc, int(adjacent),
+                                                                                     row_first, rc, max_evals, None, None, arr, cp, a, b)
+            return self._hunt_pairs(call, deltas, cols, cap)
+        call = lambda dl, nd, counts, fmap: self.lib.dvt_rv32_hunt_shard(self.h, pk, job, shard, chip, seed, dl, nd, 0, None, 0, 0, row_first, rc,
+                                                                        max_evals, counts, fmap, None, 0, None, None)
+        return self._hunt_cells(call, main_w, deltas, rc, want_map)
+
     # ---- machine level
     def verify(self, vk: bytes, proof: bytes, fri_queries=100, pow_bits=16):
         """capi.verify with the query part on this handle's GPU.  Returns (ok, exit_code, public_values, reason); a device
@@ -706,6 +786,15 @@ class Prover:
     def job_shard_chips(self, job, shard):
         """bit c set: shard `shard` (global position) has a table of chip c; 0 when the job does not hold the shard"""
         return int(self.lib.dvt_rv32_job_shard_chips(job, shard))
+
+    def job_shard_chip_shape(self, job, shard, chip):
+        """(main_w, log_n) of the main trace of chip `chip` of that shard (global position); DvtError(DVT_ERR_INPUT) when the job
+        does not hold the shard or the shard has no table of the chip"""
+        w, h = C.c_uint32(), C.c_uint32()
+        rc = self.lib.dvt_rv32_job_shard_chip_shape(job, shard, chip, C.byref(w), C.byref(h))
+        if rc:
+            raise DvtError(rc, f"shard {shard} of this job has no table of chip {chip}")
+        return int(w.value), int(h.value)
 
     def debug_device_traces(self, pk, job, shard=0):
         """K0 on the device for one shard, traces downloaded (canonical): (chips, pubs)"""

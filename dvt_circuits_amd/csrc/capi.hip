@@ -296,7 +296,7 @@ int check_tables(const Lane &c, const MachineDesc *m, const std::vector<CheckTab
 
 extern "C" {
 
-uint32_t dvt_abi_version(void) { return 8; }
+uint32_t dvt_abi_version(void) { return 9; }
 
 int dvt_prover_create(const char *cfg_json, dvt_prover **out) {
     if (!out) return fail(nullptr, DVT_ERR_INPUT, "out == NULL");
@@ -821,6 +821,37 @@ int dvt_stage_bus_ledger_free(dvt_prover *p, dvt_bus_ledger *ledger) {
     ledger_release(&ledger->dev);
     delete ledger;
     return DVT_OK;
+}
+
+// ---- the forgery hunt of one chip table (hunt.cuh), on lane 0 of member 0
+static int hunt_stage(dvt_prover *p, const char *machine, uint32_t chip, const uint32_t *d_main, const uint32_t *d_prep, uint32_t log_n,
+                      const uint32_t *pub, const HuntRequest &rq) {
+    if (!p) return DVT_ERR_INPUT;
+    static const uint32_t zero[4] = {0, 0, 0, 0};   // (the checks of machine, chip, log_n and pub that K4 / K5 make; no challenge here)
+    ChipStageArgs a;
+    if (int rc = chip_stage_args(p, machine, chip, log_n, pub, zero, zero, DVT_PATH_DEFAULT, &a)) return rc;
+    if (!d_main || (a.d->prep_w && !d_prep)) return fail(p, DVT_ERR_INPUT, "null matrix");
+    HuntPlan plan;
+    if (int rc = hunt_plan(p->err, *a.d, log_n, rq, &plan)) return rc;
+    Guard g(p); if (g.rc) return g.rc;
+    return hunt_table(lane0(p), machine_by_name(machine), {a.d, d_main, a.d->prep_w ? d_prep : nullptr, log_n}, a.pub, rq, plan);
+}
+
+int dvt_stage_hunt_cells(dvt_prover *p, const char *machine, uint32_t chip, const uint32_t *d_main, const uint32_t *d_prep,
+                         uint32_t log_n, const uint32_t *pub, uint64_t seed, const uint32_t *deltas, uint32_t n_deltas,
+                         uint32_t row_first, uint32_t row_count, uint64_t max_evals, uint32_t *free_counts, uint8_t *free_map) {
+    HuntRequest rq = hunt_request(seed, deltas, n_deltas, row_first, row_count, max_evals);
+    hunt_want_cells(&rq, free_counts, free_map);
+    return hunt_stage(p, machine, chip, d_main, d_prep, log_n, pub, rq);
+}
+
+int dvt_stage_hunt_pairs(dvt_prover *p, const char *machine, uint32_t chip, const uint32_t *d_main, const uint32_t *d_prep,
+                         uint32_t log_n, const uint32_t *pub, uint64_t seed, const uint32_t *deltas, uint32_t n_deltas,
+                         const uint32_t *cols, uint32_t n_cols, uint32_t adjacent, uint32_t row_first, uint32_t row_count,
+                         uint64_t max_evals, dvt_escape *out, size_t cap, uint64_t *n_reported, uint64_t *n_tried) {
+    HuntRequest rq = hunt_request(seed, deltas, n_deltas, row_first, row_count, max_evals);
+    hunt_want_pairs(&rq, cols, n_cols, adjacent, out, cap, n_reported, n_tried);
+    return hunt_stage(p, machine, chip, d_main, d_prep, log_n, pub, rq);
 }
 
 uint64_t dvt_debug_ledger_key(uint64_t seed, uint32_t bus, uint32_t arity, const uint32_t *values) {

@@ -233,6 +233,57 @@ inline void ledger_copy_out(const std::vector<dvt_bus_tuple> &all, bool overflow
     if (truncated) *truncated = overflow || n < all.size();
 }
 
+// ---- the forgery hunt (hunt.cuh) of one chip table on one lane: dvt_stage_hunt_cells, dvt_stage_hunt_pairs and
+// dvt_rv32_hunt_shard go through this (hunt.hip).  Synchronises the lane's stream.
+// One evaluation = one row evaluated for one candidate; a lane slot = one lane of a workgroup for one touched row, live or not
+// (256 x touched rows per candidate and row block).  The rates per chip are measured in profiles/README.md ("Forgery hunt"):
+// a launch is cut at 2^24 lane slots, which is a few milliseconds on the chips whose tables fill their workgroups and a
+// fraction of a second on the slowest precompile chip; a call without a max_evals of its own stops at 2^33 evaluations, which
+// admits the cpu chip's adjacent hunt over all 8192 rows of the smallest guest (8.2 10^9, under 3 s).
+constexpr uint64_t HUNT_LAUNCH_EVALS = 1ull << 24, HUNT_DEFAULT_MAX_EVALS = 1ull << 33;
+constexpr uint64_t HUNT_MAX_RECORDS = 1ull << 22;   // records a call brings back at most (include/dvt_prover.h)
+struct HuntRequest {   // (filled member by member: see hunt_request)
+    uint64_t seed = 0;
+    const uint32_t *deltas = nullptr;   // canonical, 1 <= delta < p
+    uint32_t n_deltas = 0;
+    uint32_t row_first = 0, row_count = 0;
+    uint64_t max_evals = 0;             // 0: HUNT_DEFAULT_MAX_EVALS
+    uint32_t pairs = 0;                 // 0: single cells -> free_counts, free_map; 1: pairs -> out, n_reported, n_tried
+    uint32_t *free_counts = nullptr;    // [main_w][n_deltas]
+    uint8_t *free_map = nullptr;        // [n_deltas][main_w][row_count] or nullptr
+    const uint32_t *cols = nullptr;     // pairs: the columns both cells are taken from (nullptr: every main column)
+    uint32_t n_cols = 0, adjacent = 0;
+    dvt_escape *out = nullptr;
+    size_t cap = 0;
+    uint64_t *n_reported = nullptr, *n_tried = nullptr;
+};
+// what every hunt has
+inline HuntRequest hunt_request(uint64_t seed, const uint32_t *deltas, uint32_t n_deltas, uint32_t row_first, uint32_t row_count, uint64_t max_evals) {
+    HuntRequest rq;
+    rq.seed = seed; rq.deltas = deltas; rq.n_deltas = n_deltas;
+    rq.row_first = row_first; rq.row_count = row_count; rq.max_evals = max_evals;
+    return rq;
+}
+inline void hunt_want_cells(HuntRequest *rq, uint32_t *free_counts, uint8_t *free_map) {
+    rq->pairs = 0; rq->free_counts = free_counts; rq->free_map = free_map;
+}
+inline void hunt_want_pairs(HuntRequest *rq, const uint32_t *cols, uint32_t n_cols, uint32_t adjacent, dvt_escape *out, size_t cap, uint64_t *n_reported,
+                            uint64_t *n_tried) {
+    rq->pairs = 1; rq->cols = cols; rq->n_cols = n_cols; rq->adjacent = adjacent;
+    rq->out = out; rq->cap = cap; rq->n_reported = n_reported; rq->n_tried = n_tried;
+}
+// what a checked request comes to: made once per call by hunt_plan, read by hunt_table
+struct HuntPlan {
+    std::vector<uint32_t> cols;    // the columns the cells are taken from, sorted, each once
+    std::vector<uint32_t> pairs;   // positions in cols, k0 | k1 << 16
+    uint32_t map_rows = 0;         // window indices of the single-cell map
+    uint64_t cell_evals = 0, pair_evals = 0;
+};
+// the DVT_ERR_INPUT / DVT_ERR_UNSUPPORTED cases of a request (nothing is launched), and its plan
+int hunt_plan(std::string &err, const ChipDesc &d, uint32_t log_n, const HuntRequest &rq, HuntPlan *out);
+int hunt_table(const Lane &c, const MachineDesc *m, const CheckTable &t, const std::vector<uint32_t> &pub_mont, const HuntRequest &rq,
+               const HuntPlan &plan);
+
 // a library-allocated copy of w (release with dvt_free); *len = its bytes
 inline uint8_t *copy_out(const std::vector<uint32_t> &w, size_t *len) {
     uint8_t *b = (uint8_t *)malloc(w.size() * 4 + 1);

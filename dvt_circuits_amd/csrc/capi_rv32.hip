@@ -1410,6 +1410,59 @@ int dvt_rv32_check_job(dvt_prover *p, const dvt_pk *pk, dvt_job *job, dvt_check_
     return job_check(p, pk, job, findings, cap, summary);
 }
 
+int dvt_rv32_job_shard_chip_shape(const dvt_job *job, size_t shard, uint32_t chip, uint32_t *main_w, uint32_t *log_n) {
+    size_t m = 0;
+    const ShardJob *s = job ? const_cast<dvt_job *>(job)->at(shard, &m) : nullptr;
+    if (!s || chip >= (uint32_t)rv32::N_CHIPS || !s->present[chip] || !main_w || !log_n) return DVT_ERR_INPUT;
+    *main_w = (uint32_t)machine_rv32()->chips[chip].main_w;
+    *log_n = s->log_n[chip];
+    return DVT_OK;
+}
+
+// The forgery hunt (hunt.cuh) of one chip table of a shard, on lane 0 of the member that holds it; the job stays as found, as
+// in shard_check.
+int dvt_rv32_hunt_shard(dvt_prover *p, const dvt_pk *pk, dvt_job *job, size_t shard, uint32_t chip, uint64_t seed, const uint32_t *deltas,
+                        uint32_t n_deltas, uint32_t pairs, const uint32_t *cols, uint32_t n_cols, uint32_t adjacent, uint32_t row_first,
+                        uint32_t row_count, uint64_t max_evals, uint32_t *free_counts, uint8_t *free_map, dvt_escape *out, size_t cap,
+                        uint64_t *n_reported, uint64_t *n_tried) {
+    if (!p || !pk || !job) return fail(p, DVT_ERR_INPUT, "null argument");
+    if (!pk->is_rv32) return fail(p, DVT_ERR_INPUT, "proving key was not made by dvt_setup");
+    if (pairs > 1) return fail(p, DVT_ERR_INPUT, "pairs %u", pairs);
+    if (int rc = same_members(p, pk, job)) return rc;
+    const MachineDesc *m = machine_rv32();
+    if (chip >= (uint32_t)m->n_chips) return fail(p, DVT_ERR_INPUT, "chip %u out of range (%d chips)", chip, m->n_chips);
+    size_t mi = 0;
+    ShardJob *s = job->at(shard, &mi);
+    if (!s) return fail(p, DVT_ERR_INPUT, "shard %zu is not held by this job", shard);
+    if (!s->present[chip]) return fail(p, DVT_ERR_INPUT, "shard %zu has no table of chip %s", shard, m->chips[chip].name);
+    HuntRequest rq = hunt_request(seed, deltas, n_deltas, row_first, row_count, max_evals);
+    if (pairs) hunt_want_pairs(&rq, cols, n_cols, adjacent, out, cap, n_reported, n_tried);
+    else hunt_want_cells(&rq, free_counts, free_map);
+    HuntPlan plan;
+    if (int rc = hunt_plan(p->err, m->chips[chip], s->log_n[chip], rq, &plan)) return rc;
+    Guard g(p); if (g.rc) return g.rc;
+    if (int rc = turn_to(p, mi)) return rc;
+    const Lane c = lane0(p, mi);
+    const DeviceKey &key = member_key(pk, mi);
+    std::vector<ChipTrace> traces;
+    const bool kept = s->traces_valid;
+    const int rc = shard_traces(c, key, job, *s, &traces, true);
+    s->traces_valid = kept;
+    if (rc) return rc;
+    for (auto &t : traces) {
+        if (t.chip_id != (int)chip) continue;
+        const ChipDesc &d = m->chips[chip];
+        const uint32_t *prep = nullptr;
+        for (auto &pr : key.key.prep)
+            if (pr.chip_id == t.chip_id && pr.log_n == t.log_n) prep = pr.d_trace;
+        if (d.prep_w && !prep) return fail(p, DVT_ERR_INPUT, "chip %s of shard %zu has no preprocessed trace of its height in the proving key", d.name, shard);
+        std::vector<uint32_t> pub;
+        for (auto x : s->pubs) pub.push_back(x.v);
+        return hunt_table(c, m, {&d, t.d_main, prep, t.log_n}, pub, rq, plan);
+    }
+    return fail(p, DVT_ERR_INPUT, "shard %zu has no table of chip %s", shard, m->chips[chip].name);
+}
+
 int dvt_rv32_commit_shard(dvt_prover *p, const dvt_pk *pk, dvt_job *job, size_t shard, uint32_t *header) {
     if (!p || !pk || !job || !header) return fail(p, DVT_ERR_INPUT, "bad argument");
     if (int rc = same_members(p, pk, job)) return rc;

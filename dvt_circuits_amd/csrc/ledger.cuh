@@ -107,9 +107,8 @@ __device__ __forceinline__ void ledger_apply(const LedgerArgs &a, uint64_t key, 
 static __device__ __noinline__ void ledger_row_occurrence(const LedgerArgs &a, uint32_t row, uint32_t j, uint32_t bus, bool send, Fp mult,
                                                           const Fp *vals, uint32_t nv) {
     if (nv > LEDGER_MAX_ARITY || j >= LEDGER_MAX_INTERACTIONS) { atomicOr(a.flags + 1, 1u); return; }
-    uint64_t h = ledger_mix(a.seed ^ 0x6a09e667f3bcc908ull);   // ledger_key without the canonical copy of the values
-    h = ledger_mix(h ^ (((uint64_t)bus << 32) | nv));
-    for (uint32_t k = 0; k < nv; k++) h = ledger_mix(h ^ vals[k].canonical());
+    uint64_t h = ledger_key_begin(a.seed, bus, nv);   // ledger_key without the canonical copy of the values
+    for (uint32_t k = 0; k < nv; k++) h = ledger_key_value(h, vals[k].canonical());
     const uint32_t m = (send ? mult : -mult).canonical();
     ledger_apply(a, h, bus, nv, m, send, ledger_occurrence(a.tag, a.chip, row, j), [&](uint32_t *dst) {
         for (uint32_t k = 0; k < nv; k++) dst[k] = vals[k].canonical();

@@ -16,10 +16,14 @@ DVT_HD uint64_t ledger_mix(uint64_t x) {
 }
 // key(seed, bus, arity, canonical values).  Every step is a bijection of the running word after a XOR with one input, so the
 // key depends on the seed, the bus, the arity and every value.
+// (in steps, for a caller that has the values one at a time: ledger_key_begin, then ledger_key_value for each canonical value)
+DVT_HD uint64_t ledger_key_begin(uint64_t seed, uint32_t bus, uint32_t arity) {
+    return ledger_mix(ledger_mix(seed ^ 0x6a09e667f3bcc908ull) ^ (((uint64_t)bus << 32) | arity));
+}
+DVT_HD uint64_t ledger_key_value(uint64_t h, uint32_t canonical) { return ledger_mix(h ^ canonical); }
 DVT_HD uint64_t ledger_key(uint64_t seed, uint32_t bus, uint32_t arity, const uint32_t *values) {
-    uint64_t h = ledger_mix(seed ^ 0x6a09e667f3bcc908ull);
-    h = ledger_mix(h ^ (((uint64_t)bus << 32) | arity));
-    for (uint32_t k = 0; k < arity; k++) h = ledger_mix(h ^ values[k]);
+    uint64_t h = ledger_key_begin(seed, bus, arity);
+    for (uint32_t k = 0; k < arity; k++) h = ledger_key_value(h, values[k]);
     return h;
 }
 // the two weights of a key, in [1, p)

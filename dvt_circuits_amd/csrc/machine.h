@@ -33,6 +33,7 @@ struct VerifierPoint {
 };
 
 struct LedgerArgs;   // ledger.cuh
+struct HuntArgs;     // hunt.cuh
 
 struct ChipDesc {
     const char *name;
@@ -50,6 +51,9 @@ struct ChipDesc {
     // the bus ledger's pass over the chip's interactions (ledger.cuh), from further units: ledger_toy.hip, ledger_rv32.hip,
     // ledger_rv32_wide.hip
     hipError_t (*launch_ledger)(hipStream_t, const LedgerArgs &) = nullptr;
+    // the forgery hunt over the chip's constraints and interactions (hunt.cuh), likewise: hunt_toy.hip, hunt_rv32.hip,
+    // hunt_rv32_wide.hip.  (row blocks, candidates) is the grid.
+    hipError_t (*launch_hunt)(hipStream_t, const HuntArgs &, unsigned row_blocks, unsigned n_candidates) = nullptr;
 };
 
 struct MachineDesc {

@@ -111,7 +111,8 @@ void dvt_free(void *ptr);
 /* ABI version of this header (4: "devices", dvt_prover_device_count, dvt_prover_device, dvt_rv32_job_shard_member;
  * 5: dvt_rv32_job_shard_device_rows; 6: dvt_stage_check_constraints, dvt_stage_bus_sums, dvt_rv32_check_job,
  * dvt_rv32_job_shard_chips; 7: dvt_prover_verify, dvt_prover_machine_verify, dvt_stage_sponge_rows,
- * dvt_stage_verify_paths, dvt_prover_verify_times; 8: dvt_stage_bus_ledger_*, dvt_rv32_job_bus_tuples) */
+ * dvt_stage_verify_paths, dvt_prover_verify_times; 8: dvt_stage_bus_ledger_*, dvt_rv32_job_bus_tuples;
+ * 9: dvt_stage_hunt_cells, dvt_stage_hunt_pairs, dvt_rv32_hunt_shard, dvt_rv32_job_shard_chip_shape) */
 uint32_t dvt_abi_version(void);
 /* the handle's hipStream_t (for event timing by the caller) */
 void *dvt_stream(dvt_prover *p);
@@ -275,6 +276,56 @@ int dvt_stage_bus_ledger_result(dvt_prover *p, dvt_bus_ledger *ledger, dvt_bus_t
                                 uint32_t *truncated);
 int dvt_stage_bus_ledger_free(dvt_prover *p, dvt_bus_ledger *ledger);
 
+/* The forgery hunt: which one- and two-cell changes of a chip's main trace does NOTHING reject?  The matrices are those of
+ * dvt_stage_check_constraints (device, Montgomery words, column-major); only main cells are changed, and the trace itself
+ * is only read (the kernels evaluate the generated AIR through a view that overrides the changed cells).
+ *   change     (col, row, delta), 1 <= delta < p canonical: the cell becomes value + delta mod p.
+ *   forgery    one change, or two changes at different cells: a same-row pair has both cells in base row r, col[0] < col[1];
+ *              an adjacent pair has the first cell in row r and the second in row (r + 1) mod n, any two columns.  A candidate
+ *              whose two changes fall on one cell (n = 1 only) is skipped.
+ *   touched    the set of rows {row - 1, row} mod n over the changed cells (the AIR reads rotations 0 and 1 only).
+ *   caught     (a) a unit of the chip (dvt_stage_check_constraints: units, `when`, identities at xi) is violated on a touched
+ *              row where it is active, or (b) the touched rows' signed multiset of (bus, values) over their interactions with
+ *              non-zero multiplicity differs from the honest table's.  (b) is decided through a keyed fingerprint per row:
+ *              a changed multiset is taken for unchanged with probability about 2^-60 over the key (one changed tuple: never),
+ *              multiplicities compared mod p.  An escape of the exact multiset is never called caught.
+ *   escape     not caught.  A single change that escapes makes its cell FREE for that delta on that row (cells the row's
+ *              instruction family does not read are free, and that is expected).
+ *   reported   a pair that escapes although at least one of its changes is caught on its own.  Pairs of two free cells are
+ *              dropped without being evaluated.
+ * seed: xi and the fingerprint key come from a transcript over a domain tag and seed; the answers for honest tables do not
+ * depend on it apart from the stated miss probability.  Precondition: the honest table violates nothing; the call runs the
+ * constraint check first and returns DVT_ERR_REJECTED, reporting nothing, when it does.
+ * max_evals (0: the default, 2^33): an evaluation is one row evaluated for one candidate; a call whose candidates x touched
+ * rows (for pairs: before the free x free rule, plus the single-cell pass of the listed columns) exceed it is DVT_ERR_INPUT
+ * before anything is launched.  The work is split into launches of at most 2^24 lane slots (256 per candidate and touched row).
+ * Every call runs on lane 0 of device 0 of the handle (dvt_rv32_hunt_shard: of the device that holds the shard) and
+ * synchronises.  DVT_ERR_INPUT: a NULL handle, d_main or output, a chip out of range, log_n > 22, n_deltas 0 or above
+ * DVT_HUNT_MAX_DELTAS, a delta of 0 or >= p, a column >= main_w, a window that is empty or not inside the table, adjacent
+ * > 1, a shard the job does not hold.  DVT_ERR_UNSUPPORTED: a chip without the hunt.  DVT_ERR_DEVICE: a HIP failure (text in
+ * dvt_last_error).  Outputs are written only by a call that returns DVT_OK. */
+#define DVT_HUNT_MAX_DELTAS 8u
+typedef struct {
+    uint32_t row, n_cells;                 /* base row; 2 for a pair */
+    uint32_t col[2], row_off[2], delta[2]; /* row_off 0 | 1; delta canonical */
+    uint32_t alone;                        /* bit i: change i is caught on its own */
+} dvt_escape;                              /* 36 bytes */
+/* single cells of rows [row_first, row_first + row_count) (inside the table, no wrap of the window):
+ * free_counts [main_w][n_deltas] = rows of the window where the change escapes;
+ * free_map (host, may be NULL) [n_deltas][main_w][row_count] bytes 0 / 1 */
+int dvt_stage_hunt_cells(dvt_prover *p, const char *machine, uint32_t chip, const uint32_t *d_main, const uint32_t *d_prep,
+                         uint32_t log_n, const uint32_t *pub, uint64_t seed, const uint32_t *deltas, uint32_t n_deltas,
+                         uint32_t row_first, uint32_t row_count, uint64_t max_evals, uint32_t *free_counts, uint8_t *free_map);
+/* pairs with base row in the window; adjacent = 0: both cells in the base row, 1: the second in the next row;
+ * cols (host, n_cols entries in any order, repeats count once; or NULL = every main column): the columns both cells are
+ * taken from.  out: at most min(cap, 2^22) records, sorted by (row, col[0], col[1], delta[0], delta[1]); when fewer come
+ * back than were reported, which ones is unspecified, and each is a true report.  *n_reported counts all; *n_tried =
+ * pairs evaluated */
+int dvt_stage_hunt_pairs(dvt_prover *p, const char *machine, uint32_t chip, const uint32_t *d_main, const uint32_t *d_prep,
+                         uint32_t log_n, const uint32_t *pub, uint64_t seed, const uint32_t *deltas, uint32_t n_deltas,
+                         const uint32_t *cols, uint32_t n_cols, uint32_t adjacent, uint32_t row_first, uint32_t row_count,
+                         uint64_t max_evals, dvt_escape *out, size_t cap, uint64_t *n_reported, uint64_t *n_tried);
+
 /* The two hashing kernels of the device verifier (dvt_prover_verify), driven at chosen shapes without a proof.  Both
  * take and return HOST arrays of canonical words (a word >= p is DVT_ERR_INPUT) and are synchronous.
  * dvt_stage_sponge_rows: n word vectors, concatenated in `words`, of lens[i] words each -> digests [n][8]: the sponge of
@@ -420,6 +471,9 @@ uint32_t dvt_rv32_job_shard_device_rows(const dvt_job *job, size_t shard);
 /* bit mask over the chip ids: the chip tables shard `shard` (global position) consists of.  0 for a shard this job does
  * not hold. */
 uint32_t dvt_rv32_job_shard_chips(const dvt_job *job, size_t shard);
+/* width and height (log2 of the rows) of the main trace of chip `chip` of that shard; DVT_ERR_INPUT when the job does not hold
+ * the shard, the shard has no table of that chip, or a pointer is NULL.  Host-only. */
+int dvt_rv32_job_shard_chip_shape(const dvt_job *job, size_t shard, uint32_t chip, uint32_t *main_w, uint32_t *log_n);
 int dvt_rv32_commit_shard(dvt_prover *p, const dvt_pk *pk, dvt_job *job, size_t shard, uint32_t *header);
 int dvt_rv32_challenges(const uint8_t *vk, size_t vk_len, const uint32_t *headers, size_t n_shards, uint32_t out[8]);
 int dvt_rv32_prove_shard(dvt_prover *p, const dvt_pk *pk, dvt_job *job, size_t shard, const uint32_t challenges[8],
@@ -455,6 +509,15 @@ typedef struct {
 } dvt_check_summary;
 int dvt_rv32_check_job(dvt_prover *p, const dvt_pk *pk, dvt_job *job, dvt_check_finding *findings, size_t cap,
                        dvt_check_summary *summary);
+/* The same two hunts (dvt_stage_hunt_cells with pairs = 0: free_counts, free_map; dvt_stage_hunt_pairs with pairs = 1: cols,
+ * n_cols, adjacent, out, cap, n_reported, n_tried; the other group is ignored) on chip `chip` of shard `shard` of a prepared
+ * job.  The traces are taken as dvt_rv32_check_job takes them, the preprocessed trace comes from the proving key, and the job
+ * is left as found: dvt_rv32_prove_job afterwards returns the bytes it would have returned without the hunt.  A shard the
+ * job does not hold, or one without a table of that chip, is DVT_ERR_INPUT. */
+int dvt_rv32_hunt_shard(dvt_prover *p, const dvt_pk *pk, dvt_job *job, size_t shard, uint32_t chip, uint64_t seed,
+                        const uint32_t *deltas, uint32_t n_deltas, uint32_t pairs, const uint32_t *cols, uint32_t n_cols,
+                        uint32_t adjacent, uint32_t row_first, uint32_t row_count, uint64_t max_evals, uint32_t *free_counts,
+                        uint8_t *free_map, dvt_escape *out, size_t cap, uint64_t *n_reported, uint64_t *n_tried);
 /* The unmatched LogUp tuples of a job (the bus ledger, dvt_stage_bus_ledger_*): what dvt_rv32_check_job's bus mask stands
  * for.  The traces of every shard the job holds are taken as dvt_rv32_check_job takes them, on the device that holds the
  * shard, and the job is left as found; first_tag is the shard's position, first_chip 0xffffffff one of the eight verifier-
