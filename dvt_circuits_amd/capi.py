@@ -108,6 +108,14 @@ def load():
     lib.dvt_rv32_hunt_shard.argtypes = [vp, vp, vp, sz, u32, u64, u32p, u32, u32, u32p, u32, u32, u32, u32, u64, u32p, u8p,
                                         C.POINTER(Escape), sz, C.POINTER(u64), C.POINTER(u64)]
     lib.dvt_debug_ledger_key.restype = C.c_uint64
+    lib.dvt_stage_hunt_join_new.argtypes = [vp, C.c_char_p, u64, u32p, u32, sz, sz, u32, C.POINTER(vp)]
+    lib.dvt_stage_hunt_join_supply.argtypes = [vp, vp, u32, vp, vp, u32, u32p]
+    lib.dvt_stage_hunt_join_add.argtypes = [vp, vp, u32, u32, vp, vp, u32, u32p, u32, u32, u32p, u32, u64]
+    lib.dvt_stage_hunt_join_match.argtypes = [vp, vp, C.POINTER(JoinSummary)]
+    lib.dvt_stage_hunt_join_result.argtypes = [vp, vp, C.POINTER(JoinCell), sz, C.POINTER(sz), C.POINTER(JoinCell), sz, C.POINTER(sz)]
+    lib.dvt_stage_hunt_join_free.argtypes = [vp, vp]
+    lib.dvt_rv32_hunt_join_job.argtypes = [vp, vp, vp, C.POINTER(JoinWindow), sz, u32p, u32, u64, u32p, u32, u32p, u32p, u64, sz, sz, u32,
+                                           C.POINTER(JoinSummary), C.POINTER(JoinCell), sz, C.POINTER(sz), C.POINTER(JoinCell), sz, C.POINTER(sz)]
     lib.dvt_rv32_job_shard_chips.argtypes = [vp, sz]
     lib.dvt_rv32_job_shard_chips.restype = u32
     lib.dvt_rv32_job_shard_chip_shape.argtypes = [vp, sz, u32, u32p, u32p]
@@ -208,6 +216,50 @@ def _escapes(arr, n):
         return []
     rows = np.frombuffer(arr, np.uint32).reshape(-1, 9)[:n].tolist()
     return [dict(row=r[0], n_cells=r[1], col=r[2:4], row_off=r[4:6], delta=r[6:8], alone=r[8]) for r in rows]
+
+
+JOIN_TRUNC_RECORDS, JOIN_TRUNC_ABSORBED, JOIN_TRUNC_PROBES, JOIN_TRUNC_OUTPUT = 1, 2, 4, 8   # DVT_JOIN_TRUNC_*
+JOIN_NO_GROUP = 0xffffffff
+
+
+class JoinCell(C.Structure):
+    """dvt_join_cell: one changed cell of a group of the join hunt, or an absorbed cell (group JOIN_NO_GROUP)"""
+    _fields_ = [("group", C.c_uint32), ("side", C.c_uint32), ("tag", C.c_uint32), ("chip", C.c_uint32), ("col", C.c_uint32),
+                ("row", C.c_uint32), ("delta", C.c_uint32)]
+
+
+class JoinSummary(C.Structure):
+    """dvt_join_summary"""
+    _fields_ = [("candidates", C.c_uint64), ("open_emitted", C.c_uint64), ("open_stored", C.c_uint64), ("absorbed_emitted", C.c_uint64),
+                ("absorbed_stored", C.c_uint64), ("matched", C.c_uint64), ("groups", C.c_uint64), ("pairs", C.c_uint64),
+                ("truncated", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class JoinWindow(C.Structure):
+    """dvt_join_window: rows of one chip table of one shard of a job (row_count 0: to the end of the table)"""
+    _fields_ = [("shard", C.c_uint32), ("chip", C.c_uint32), ("row_first", C.c_uint32), ("row_count", C.c_uint32)]
+
+
+def _join_result(sm, cells, n_cells, cap_cells, soaked, n_soaked, cap_soaked):
+    """what Prover.hunt_join and Prover.hunt_join_job return"""
+    summary = {k: int(getattr(sm, k)) for k, _ in JoinSummary._fields_ if k != "reserved"}
+    if n_cells > cap_cells:
+        summary["truncated"] |= JOIN_TRUNC_OUTPUT
+    groups = []
+    for c in _join_cells(cells, min(n_cells, cap_cells)):
+        while len(groups) <= c["group"]:
+            groups.append([[], []])
+        groups[c["group"]][c["side"]].append({k: c[k] for k in ("tag", "chip", "col", "row", "delta")})
+    absorbed = [{k: c[k] for k in ("tag", "chip", "col", "row", "delta")} for c in _join_cells(soaked, min(n_soaked, cap_soaked))]
+    return dict(summary=summary, groups=groups, absorbed=absorbed)
+
+
+def _join_cells(arr, n):
+    """the first n records of a JoinCell array as dicts"""
+    if not n:
+        return []
+    names = [k for k, _ in JoinCell._fields_]
+    return [dict(zip(names, r)) for r in np.frombuffer(arr, np.uint32).reshape(-1, 7)[:n].tolist()]
 
 
 class BusLedger:
@@ -616,6 +668,63 @@ class Prover:
                                                                                   seed, dl, nd, cl, nc, int(adjacent), row_first, rc, max_evals,
                                                                                   arr, cp, a, b)
         return self._hunt_pairs(call, deltas, cols, cap)
+
+    def hunt_join(self, machine, windows, deltas, supply=(), seed=1, max_evals=0, cap_records=1 << 16, cap_absorbed=1 << 16, log_slots=0,
+                  cap_cells=1 << 16):
+        """The join hunt over windows of several chip tables (dvt_stage_hunt_join_*): two-cell forgeries whose halves lie in
+        different tables or in distant rows, and single cells that a supply table absorbs.  windows: dicts(tag, chip, main,
+        prep, log_n, pubs[, row_first, row_count, cols]); supply: dicts(chip, main, prep, log_n, pubs); matrices as
+        stage_check_constraints takes them.  Returns dict(summary, groups, absorbed): summary = the fields of
+        dvt_join_summary, with DVT_JOIN_TRUNC_OUTPUT also set when more cells exist than cap_cells; groups = a list of
+        [side 0, side 1], each a list of dicts(tag, chip, col, row, delta) in the result's order; absorbed = such dicts."""
+        dl = np.ascontiguousarray(deltas, dtype=np.uint32)
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        pubv = lambda pubs: (C.c_uint32 * max(len(pubs), 1))(*[int(x) for x in pubs])
+        h = C.c_void_p()
+        self.check(self.lib.dvt_stage_hunt_join_new(self.h, machine.encode(), seed, dl.ctypes.data_as(u32p), dl.size, cap_records, cap_absorbed,
+                                                    log_slots, C.byref(h)))
+        try:
+            # (the library keeps the supply matrices' device pointers until the first add: `supply` holds the tensors until then)
+            supply = list(supply)
+            for s in supply:
+                self.check(self.lib.dvt_stage_hunt_join_supply(self.h, h, s["chip"], ptr(s["main"]), ptr(s.get("prep")), s["log_n"], pubv(s["pubs"])))
+            for w in windows:
+                first = w.get("row_first", 0)
+                count = w.get("row_count")
+                count = (1 << w["log_n"]) - first if count is None else count
+                cl = np.ascontiguousarray(w["cols"], dtype=np.uint32) if w.get("cols") is not None else None
+                self.check(self.lib.dvt_stage_hunt_join_add(self.h, h, w["tag"], w["chip"], ptr(w["main"]), ptr(w.get("prep")), w["log_n"],
+                                                            pubv(w["pubs"]), first, count, cl.ctypes.data_as(u32p) if cl is not None else None,
+                                                            cl.size if cl is not None else 0, max_evals))
+            sm = JoinSummary()
+            self.check(self.lib.dvt_stage_hunt_join_match(self.h, h, C.byref(sm)))
+            cells, soaked = (JoinCell * max(cap_cells, 1))(), (JoinCell * max(cap_absorbed, 1))()
+            n_cells, n_soaked = C.c_size_t(), C.c_size_t()
+            self.check(self.lib.dvt_stage_hunt_join_result(self.h, h, cells, cap_cells, C.byref(n_cells), soaked, cap_absorbed, C.byref(n_soaked)))
+        finally:
+            self.lib.dvt_stage_hunt_join_free(self.h, h)
+        return _join_result(sm, cells, n_cells.value, cap_cells, soaked, n_soaked.value, cap_absorbed)
+
+    def hunt_join_job(self, pk, job, windows, deltas, supply_chips=(0, 1, 3), cols=None, seed=1, max_evals=0, cap_records=1 << 16,
+                      cap_absorbed=1 << 16, log_slots=0, cap_cells=1 << 16):
+        """The join hunt over windows of a prepared job's tables (dvt_rv32_hunt_join_job).  windows: tuples (shard, chip[,
+        row_first[, row_count]]), row_count 0 / missing = to the end of the table; the tag of a cell is its shard.
+        supply_chips: the supply tables, taken from the first window's shard (default program, byte, mem_image).  cols: None, or
+        one list of columns (or None = all) per window.  Returns what hunt_join returns.  Windows on shards of several device
+        members raise DvtError(DVT_ERR_UNSUPPORTED).  The job is left as found."""
+        dl = np.ascontiguousarray(deltas, dtype=np.uint32)
+        ws = (JoinWindow * max(len(windows), 1))(*[JoinWindow(*(tuple(w) + (0, 0))[:4]) for w in windows])
+        sc = np.ascontiguousarray(list(supply_chips), dtype=np.uint32)
+        counts = np.ascontiguousarray([len(c) if c is not None else 0 for c in cols], dtype=np.uint32) if cols is not None else None
+        flat = np.ascontiguousarray([x for c in cols if c is not None for x in c] + [0], dtype=np.uint32) if cols is not None else None
+        sm = JoinSummary()
+        cells, soaked = (JoinCell * max(cap_cells, 1))(), (JoinCell * max(cap_absorbed, 1))()
+        n_cells, n_soaked = C.c_size_t(), C.c_size_t()
+        self.check(self.lib.dvt_rv32_hunt_join_job(self.h, pk, job, ws, len(windows), sc.ctypes.data_as(u32p) if sc.size else None, sc.size, seed,
+                                                   dl.ctypes.data_as(u32p), dl.size, flat.ctypes.data_as(u32p) if flat is not None else None,
+                                                   counts.ctypes.data_as(u32p) if counts is not None else None, max_evals, cap_records, cap_absorbed,
+                                                   log_slots, C.byref(sm), cells, cap_cells, C.byref(n_cells), soaked, cap_absorbed, C.byref(n_soaked)))
+        return _join_result(sm, cells, n_cells.value, cap_cells, soaked, n_soaked.value, cap_absorbed)
 
     def hunt_shard(self, pk, job, shard, chip, deltas, pairs=False, cols=None, adjacent=False, row_first=0, row_count=None,
                    seed=1, max_evals=0, cap=4096, want_map=True):

@@ -296,7 +296,7 @@ int check_tables(const Lane &c, const MachineDesc *m, const std::vector<CheckTab
 
 extern "C" {
 
-uint32_t dvt_abi_version(void) { return 9; }
+uint32_t dvt_abi_version(void) { return 10; }
 
 int dvt_prover_create(const char *cfg_json, dvt_prover **out) {
     if (!out) return fail(nullptr, DVT_ERR_INPUT, "out == NULL");
@@ -852,6 +852,85 @@ int dvt_stage_hunt_pairs(dvt_prover *p, const char *machine, uint32_t chip, cons
     HuntRequest rq = hunt_request(seed, deltas, n_deltas, row_first, row_count, max_evals);
     hunt_want_pairs(&rq, cols, n_cols, adjacent, out, cap, n_reported, n_tried);
     return hunt_stage(p, machine, chip, d_main, d_prep, log_n, pub, rq);
+}
+
+// ---- the join hunt over windows of several chip tables (hunt_join.cuh), on lane 0 of member 0
+int dvt_stage_hunt_join_new(dvt_prover *p, const char *machine, uint64_t seed, const uint32_t *deltas, uint32_t n_deltas, size_t cap_records,
+                            size_t cap_absorbed, uint32_t log_slots, dvt_hunt_join **join) {
+    if (!p) return DVT_ERR_INPUT;
+    if (!join) return fail(p, DVT_ERR_INPUT, "null argument");
+    *join = nullptr;
+    const MachineDesc *m = machine_by_name(machine);
+    if (!m) return fail(p, DVT_ERR_INPUT, "unknown machine '%s'", machine ? machine : "(null)");
+    Guard g(p); if (g.rc) return g.rc;
+    std::unique_ptr<dvt_hunt_join> j(new dvt_hunt_join());
+    if (int rc = join_init(lane0(p), &j->dev, m, seed, deltas, n_deltas, cap_records, cap_absorbed, log_slots)) {
+        join_release(&j->dev);
+        return rc;
+    }
+    HIP_TRY(p, hipStreamSynchronize(eng0(p).stream));
+    *join = j.release();
+    return DVT_OK;
+}
+
+int dvt_stage_hunt_join_supply(dvt_prover *p, dvt_hunt_join *join, uint32_t chip, const uint32_t *d_main, const uint32_t *d_prep, uint32_t log_n,
+                               const uint32_t *pub) {
+    if (!p) return DVT_ERR_INPUT;
+    if (!join) return fail(p, DVT_ERR_INPUT, "null join");
+    static const uint32_t zero[4] = {0, 0, 0, 0};   // (the checks of chip, log_n and pub that K4 / K5 make; no challenge here)
+    ChipStageArgs a;
+    if (int rc = chip_stage_args(p, join->dev.m->name, chip, log_n, pub, zero, zero, DVT_PATH_DEFAULT, &a)) return rc;
+    if (!d_main || (a.d->prep_w && !d_prep)) return fail(p, DVT_ERR_INPUT, "null matrix");
+    Guard g(p); if (g.rc) return g.rc;
+    return join_supply(p->err, join->dev, {a.d, d_main, a.d->prep_w ? d_prep : nullptr, log_n}, a.pub);
+}
+
+int dvt_stage_hunt_join_add(dvt_prover *p, dvt_hunt_join *join, uint32_t tag, uint32_t chip, const uint32_t *d_main, const uint32_t *d_prep,
+                            uint32_t log_n, const uint32_t *pub, uint32_t row_first, uint32_t row_count, const uint32_t *cols, uint32_t n_cols,
+                            uint64_t max_evals) {
+    if (!p) return DVT_ERR_INPUT;
+    if (!join) return fail(p, DVT_ERR_INPUT, "null join");
+    static const uint32_t zero[4] = {0, 0, 0, 0};
+    ChipStageArgs a;
+    if (int rc = chip_stage_args(p, join->dev.m->name, chip, log_n, pub, zero, zero, DVT_PATH_DEFAULT, &a)) return rc;
+    if (!d_main || (a.d->prep_w && !d_prep)) return fail(p, DVT_ERR_INPUT, "null matrix");
+    std::vector<uint32_t> cl;
+    if (int rc = join_check_add(p->err, join->dev, tag, chip, *a.d, log_n, row_first, row_count, cols, n_cols, max_evals, &cl)) return rc;
+    Guard g(p); if (g.rc) return g.rc;
+    return join_add(lane0(p), join->dev, tag, chip, {a.d, d_main, a.d->prep_w ? d_prep : nullptr, log_n}, a.pub, row_first, row_count, cl);
+}
+
+int dvt_stage_hunt_join_match(dvt_prover *p, dvt_hunt_join *join, dvt_join_summary *summary) {
+    if (!p) return DVT_ERR_INPUT;
+    if (!join || !summary) return fail(p, DVT_ERR_INPUT, "null argument");
+    Guard g(p); if (g.rc) return g.rc;
+    if (int rc = join_match(lane0(p), join->dev)) return rc;
+    *summary = join->dev.summary;
+    return DVT_OK;
+}
+
+int dvt_stage_hunt_join_result(dvt_prover *p, dvt_hunt_join *join, dvt_join_cell *cells, size_t cap_cells, size_t *n_cells, dvt_join_cell *absorbed,
+                               size_t cap_absorbed, size_t *n_absorbed) {
+    if (!p) return DVT_ERR_INPUT;
+    if (!join || !n_cells || !n_absorbed || (cap_cells && !cells) || (cap_absorbed && !absorbed)) return fail(p, DVT_ERR_INPUT, "null argument");
+    Guard g(p); if (g.rc) return g.rc;
+    if (!join->dev.matched) return fail(p, DVT_ERR_INPUT, "result before match");
+    const JoinDev &j = join->dev;
+    std::copy_n(j.cells.begin(), std::min(cap_cells, j.cells.size()), cells);
+    std::copy_n(j.absorbed.begin(), std::min(cap_absorbed, j.absorbed.size()), absorbed);
+    *n_cells = j.cells.size();
+    *n_absorbed = j.absorbed.size();
+    return DVT_OK;
+}
+
+int dvt_stage_hunt_join_free(dvt_prover *p, dvt_hunt_join *join) {
+    if (!p) return DVT_ERR_INPUT;
+    if (!join) return fail(p, DVT_ERR_INPUT, "null join");
+    Guard g(p); if (g.rc) return g.rc;
+    (void)hipStreamSynchronize(eng0(p).stream);
+    join_release(&join->dev);
+    delete join;
+    return DVT_OK;
 }
 
 uint64_t dvt_debug_ledger_key(uint64_t seed, uint32_t bus, uint32_t arity, const uint32_t *values) {

@@ -284,6 +284,49 @@ int hunt_plan(std::string &err, const ChipDesc &d, uint32_t log_n, const HuntReq
 int hunt_table(const Lane &c, const MachineDesc *m, const CheckTable &t, const std::vector<uint32_t> &pub_mont, const HuntRequest &rq,
                const HuntPlan &plan);
 
+// ---- the join hunt (hunt_join.cuh) over windows of several tables on one lane: dvt_stage_hunt_join_* go through this
+// (hunt_join.hip).  Buffers come from the lane's pool and go back in join_release.  The bounds of a launch and of a call are
+// the hunt's (HUNT_LAUNCH_EVALS, HUNT_DEFAULT_MAX_EVALS, HUNT_MAX_RECORDS).
+struct JoinSupplyRef {   // a supply table, kept until the first window is added: the set is sized and built then
+    const ChipDesc *d;
+    const uint32_t *main, *prep;
+    uint32_t log_n;
+    std::vector<uint32_t> pub_mont;
+};
+struct JoinInstance {    // a hunted (tag, chip) and its windows [first, first + count)
+    uint32_t tag, chip, log_n;
+    std::vector<std::pair<uint32_t, uint32_t>> windows;
+};
+struct JoinDev {
+    const MachineDesc *m = nullptr;
+    uint64_t seed = 0;
+    uint32_t n_deltas = 0, deltas[DVT_HUNT_MAX_DELTAS] = {};   // canonical
+    size_t cap_open = 0, cap_absorbed = 0;
+    uint32_t log_slots = 0;
+    DevPool *pool = nullptr;
+    void *d_open = nullptr, *d_absorbed = nullptr, *d_counters = nullptr, *d_flags = nullptr, *d_supply = nullptr;
+    uint32_t supply_mask = 0;
+    std::vector<JoinSupplyRef> supply;
+    std::vector<JoinInstance> instances;
+    bool sealed = false;    // a window was added: no further supply table
+    bool matched = false;
+    bool broken = false;    // a window failed after its first launch: its records are in the arrays, add and match are refused
+    dvt_join_summary summary = {};
+    std::vector<dvt_join_cell> cells, absorbed;   // what match found, in the result's order
+};
+// the DVT_ERR_INPUT cases of new (nothing is allocated), then the buffers
+int join_check_new(std::string &err, uint32_t n_deltas, const uint32_t *deltas, size_t cap_records, size_t cap_absorbed, uint32_t log_slots);
+int join_init(const Lane &c, JoinDev *j, const MachineDesc *m, uint64_t seed, const uint32_t *deltas, uint32_t n_deltas, size_t cap_records,
+              size_t cap_absorbed, uint32_t log_slots);
+void join_release(JoinDev *j);
+int join_supply(std::string &err, JoinDev &j, const CheckTable &t, const std::vector<uint32_t> &pub_mont);
+// the DVT_ERR_INPUT / DVT_ERR_UNSUPPORTED cases of a window (nothing is launched); *cols_out: its columns, sorted, each once
+int join_check_add(std::string &err, const JoinDev &j, uint32_t tag, uint32_t chip, const ChipDesc &d, uint32_t log_n, uint32_t row_first,
+                   uint32_t row_count, const uint32_t *cols, uint32_t n_cols, uint64_t max_evals, std::vector<uint32_t> *cols_out);
+int join_add(const Lane &c, JoinDev &j, uint32_t tag, uint32_t chip, const CheckTable &t, const std::vector<uint32_t> &pub_mont, uint32_t row_first,
+             uint32_t row_count, const std::vector<uint32_t> &cols);
+int join_match(const Lane &c, JoinDev &j);
+
 // a library-allocated copy of w (release with dvt_free); *len = its bytes
 inline uint8_t *copy_out(const std::vector<uint32_t> &w, size_t *len) {
     uint8_t *b = (uint8_t *)malloc(w.size() * 4 + 1);
@@ -324,6 +367,10 @@ struct DeviceQueries {
 };
 }  // namespace dvt
 
+// a join hunt of the stage entry points (dvt_stage_hunt_join_*): on lane 0 of member 0
+struct dvt_hunt_join {
+    dvt::JoinDev dev;
+};
 // a bus ledger of the stage entry points (dvt_stage_bus_ledger_*): on lane 0 of member 0
 struct dvt_bus_ledger {
     dvt::LedgerDev dev;

@@ -1463,6 +1463,105 @@ int dvt_rv32_hunt_shard(dvt_prover *p, const dvt_pk *pk, dvt_job *job, size_t sh
     return fail(p, DVT_ERR_INPUT, "shard %zu has no table of chip %s", shard, m->chips[chip].name);
 }
 
+// The join hunt (hunt_join.cuh) over windows of the job's tables, on lane 0 of the one member that holds their shards; the
+// job stays as found, as in shard_check.  Shard after shard: the next shard's K0 may write the working buffers the launches
+// of the last one read, and every join_add synchronises.
+int dvt_rv32_hunt_join_job(dvt_prover *p, const dvt_pk *pk, dvt_job *job, const dvt_join_window *windows, size_t n_windows,
+                           const uint32_t *supply_chips, uint32_t n_supply, uint64_t seed, const uint32_t *deltas, uint32_t n_deltas,
+                           const uint32_t *cols, const uint32_t *cols_count, uint64_t max_evals, size_t cap_records, size_t cap_absorbed,
+                           uint32_t log_slots, dvt_join_summary *summary, dvt_join_cell *cells, size_t cap_cells, size_t *n_cells,
+                           dvt_join_cell *absorbed, size_t cap_absorbed_out, size_t *n_absorbed) {
+    if (!p || !pk || !job) return fail(p, DVT_ERR_INPUT, "null argument");
+    if (!windows || !n_windows || (n_supply && !supply_chips) || !summary || !n_cells || !n_absorbed || (cap_cells && !cells) ||
+        (cap_absorbed_out && !absorbed) || (cols_count && !cols))
+        return fail(p, DVT_ERR_INPUT, "null argument");
+    if (!pk->is_rv32) return fail(p, DVT_ERR_INPUT, "proving key was not made by dvt_setup");
+    if (int rc = same_members(p, pk, job)) return rc;
+    if (int rc = join_check_new(p->err, n_deltas, deltas, cap_records, cap_absorbed, log_slots)) return rc;
+    const MachineDesc *m = machine_rv32();
+    size_t mi = 0;
+    std::vector<uint32_t> order;   // the shards in the order of their first window
+    for (size_t w = 0; w < n_windows; w++) {
+        size_t at = 0;
+        ShardJob *s = job->at(windows[w].shard, &at);
+        if (!s) return fail(p, DVT_ERR_INPUT, "shard %u is not held by this job", windows[w].shard);
+        if (windows[w].chip >= (uint32_t)m->n_chips) return fail(p, DVT_ERR_INPUT, "chip %u out of range (%d chips)", windows[w].chip, m->n_chips);
+        if (!s->present[windows[w].chip]) return fail(p, DVT_ERR_INPUT, "shard %u has no table of chip %s", windows[w].shard, m->chips[windows[w].chip].name);
+        if (w && at != mi)
+            return fail(p, DVT_ERR_UNSUPPORTED, "windows on shards of members %zu and %zu: a join runs on one device", mi, at);
+        mi = at;
+        if (std::find(order.begin(), order.end(), windows[w].shard) == order.end()) order.push_back(windows[w].shard);
+    }
+    for (uint32_t k = 0; k < n_supply; k++)
+        if (supply_chips[k] >= (uint32_t)m->n_chips) return fail(p, DVT_ERR_INPUT, "supply chip %u out of range", supply_chips[k]);
+    Guard g(p); if (g.rc) return g.rc;
+    if (int rc = turn_to(p, mi)) return rc;
+    const Lane c = lane0(p, mi);
+    const DeviceKey &key = member_key(pk, mi);
+    struct Held {   // the join's buffers go back however the call ends
+        JoinDev dev;
+        hipStream_t st;
+        ~Held() { (void)hipStreamSynchronize(st); join_release(&dev); }
+    } held{{}, c.eng.stream};
+    JoinDev &j = held.dev;
+    if (int rc = join_init(c, &j, m, seed, deltas, n_deltas, cap_records, cap_absorbed, log_slots)) return rc;
+    auto prep_of = [&](const ChipTrace &t) -> const uint32_t * {
+        for (auto &pr : key.key.prep)
+            if (pr.chip_id == t.chip_id && pr.log_n == t.log_n) return pr.d_trace;
+        return nullptr;
+    };
+    for (size_t o = 0; o < order.size(); o++) {
+        size_t at = 0;
+        ShardJob *s = job->at(order[o], &at);
+        std::vector<ChipTrace> traces;
+        const bool kept = s->traces_valid;
+        const int rc = shard_traces(c, key, job, *s, &traces, true);
+        s->traces_valid = kept;
+        if (rc) return rc;
+        std::vector<uint32_t> pub;
+        for (auto x : s->pubs) pub.push_back(x.v);
+        auto table_of = [&](uint32_t chip, CheckTable *out) -> int {
+            for (auto &t : traces) {
+                if (t.chip_id != (int)chip) continue;
+                const ChipDesc &d = m->chips[chip];
+                const uint32_t *prep = prep_of(t);
+                if (d.prep_w && !prep) return fail(p, DVT_ERR_INPUT, "chip %s of shard %u has no preprocessed trace of its height in the proving key", d.name, order[o]);
+                *out = {&d, t.d_main, prep, t.log_n};
+                return DVT_OK;
+            }
+            return fail(p, DVT_ERR_INPUT, "shard %u has no table of chip %s", order[o], m->chips[chip].name);
+        };
+        for (uint32_t k = 0; o == 0 && k < n_supply; k++) {
+            CheckTable t;
+            if (int rc2 = table_of(supply_chips[k], &t)) return rc2;
+            if (int rc2 = join_supply(p->err, j, t, pub)) return rc2;
+        }
+        size_t col_at = 0;
+        for (size_t w = 0; w < n_windows; w++) {
+            const uint32_t nc = cols_count ? cols_count[w] : 0;
+            const uint32_t *cl = nc ? cols + col_at : nullptr;
+            col_at += nc;
+            if (windows[w].shard != order[o]) continue;
+            CheckTable t;
+            if (int rc2 = table_of(windows[w].chip, &t)) return rc2;
+            const uint64_t n = (uint64_t)1 << t.log_n;
+            const uint32_t first = windows[w].row_first;
+            const uint32_t count = windows[w].row_count ? windows[w].row_count : (uint32_t)(first < n ? n - first : 0);
+            std::vector<uint32_t> use;
+            if (int rc2 = join_check_add(p->err, j, order[o], windows[w].chip, *t.d, t.log_n, first, count, cl, nc, max_evals, &use)) return rc2;
+            if (int rc2 = join_add(c, j, order[o], windows[w].chip, t, pub, first, count, use)) return rc2;
+        }
+        HIP_TRY(p, hipStreamSynchronize(c.eng.stream));
+    }
+    if (int rc = join_match(c, j)) return rc;
+    std::copy_n(j.cells.begin(), std::min(cap_cells, j.cells.size()), cells);
+    std::copy_n(j.absorbed.begin(), std::min(cap_absorbed_out, j.absorbed.size()), absorbed);
+    *n_cells = j.cells.size();
+    *n_absorbed = j.absorbed.size();
+    *summary = j.summary;
+    return DVT_OK;
+}
+
 int dvt_rv32_commit_shard(dvt_prover *p, const dvt_pk *pk, dvt_job *job, size_t shard, uint32_t *header) {
     if (!p || !pk || !job || !header) return fail(p, DVT_ERR_INPUT, "bad argument");
     if (int rc = same_members(p, pk, job)) return rc;

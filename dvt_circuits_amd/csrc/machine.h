@@ -34,6 +34,7 @@ struct VerifierPoint {
 
 struct LedgerArgs;   // ledger.cuh
 struct HuntArgs;     // hunt.cuh
+struct JoinArgs;     // hunt_join.cuh
 
 struct ChipDesc {
     const char *name;
@@ -54,6 +55,11 @@ struct ChipDesc {
     // the forgery hunt over the chip's constraints and interactions (hunt.cuh), likewise: hunt_toy.hip, hunt_rv32.hip,
     // hunt_rv32_wide.hip.  (row blocks, candidates) is the grid.
     hipError_t (*launch_hunt)(hipStream_t, const HuntArgs &, unsigned row_blocks, unsigned n_candidates) = nullptr;
+    // the join hunt (hunt_join.cuh), from units of its own again: hunt_join_toy.hip, hunt_join_rv32.hip, hunt_join_rv32_wide.hip.
+    // launch_join: the honest fingerprints and EMIT, grid as launch_hunt.  launch_supply: the keys of every interaction of
+    // every row into the supply set; only the chips that may serve as supply tables have it.
+    hipError_t (*launch_join)(hipStream_t, const JoinArgs &, unsigned row_blocks, unsigned n_candidates) = nullptr;
+    hipError_t (*launch_supply)(hipStream_t, const JoinArgs &) = nullptr;
 };
 
 struct MachineDesc {

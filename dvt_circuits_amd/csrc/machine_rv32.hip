@@ -24,12 +24,14 @@ void rv32_ledger_fns(int chip, ChipDesc *d);
 void rv32_wide_ledger_fns(int chip, ChipDesc *d);
 void rv32_hunt_fns(int chip, ChipDesc *d);        // hunt_rv32.hip
 void rv32_wide_hunt_fns(int chip, ChipDesc *d);   // hunt_rv32_wide.hip
+void rv32_join_fns(int chip, ChipDesc *d);        // hunt_join_rv32.hip
+void rv32_wide_join_fns(int chip, ChipDesc *d);   // hunt_join_rv32_wide.hip
 namespace {
 template <int I, class A>
 ChipDesc chip_desc_here() {
     ChipDesc d;
-    if constexpr (I < RV32_FIRST_WIDE_CHIP) { d = make_chip_desc<A>(); rv32_check_fns(I, &d); rv32_ledger_fns(I, &d); rv32_hunt_fns(I, &d); }
-    else { d = rv32_wide_chip_desc(I); rv32_wide_check_fns(I, &d); rv32_wide_ledger_fns(I, &d); rv32_wide_hunt_fns(I, &d); }
+    if constexpr (I < RV32_FIRST_WIDE_CHIP) { d = make_chip_desc<A>(); rv32_check_fns(I, &d); rv32_ledger_fns(I, &d); rv32_hunt_fns(I, &d); rv32_join_fns(I, &d); }
+    else { d = rv32_wide_chip_desc(I); rv32_wide_check_fns(I, &d); rv32_wide_ledger_fns(I, &d); rv32_wide_hunt_fns(I, &d); rv32_wide_join_fns(I, &d); }
     return d;
 }
 }  // namespace

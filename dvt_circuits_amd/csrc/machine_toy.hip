@@ -5,12 +5,14 @@
 namespace dvt {
 void toy_ledger_fns(int chip, ChipDesc *d);   // ledger_toy.hip
 void toy_hunt_fns(int chip, ChipDesc *d);     // hunt_toy.hip
+void toy_join_fns(int chip, ChipDesc *d);     // hunt_join_toy.hip
 namespace {
 template <int I, class A>
 ChipDesc chip_desc_here() {
     ChipDesc d = with_check_fns<A>(make_chip_desc<A>());
     toy_ledger_fns(I, &d);
     toy_hunt_fns(I, &d);
+    toy_join_fns(I, &d);
     return d;
 }
 }  // namespace

@@ -112,7 +112,8 @@ void dvt_free(void *ptr);
  * 5: dvt_rv32_job_shard_device_rows; 6: dvt_stage_check_constraints, dvt_stage_bus_sums, dvt_rv32_check_job,
  * dvt_rv32_job_shard_chips; 7: dvt_prover_verify, dvt_prover_machine_verify, dvt_stage_sponge_rows,
  * dvt_stage_verify_paths, dvt_prover_verify_times; 8: dvt_stage_bus_ledger_*, dvt_rv32_job_bus_tuples;
- * 9: dvt_stage_hunt_cells, dvt_stage_hunt_pairs, dvt_rv32_hunt_shard, dvt_rv32_job_shard_chip_shape) */
+ * 9: dvt_stage_hunt_cells, dvt_stage_hunt_pairs, dvt_rv32_hunt_shard, dvt_rv32_job_shard_chip_shape;
+ * 10: dvt_stage_hunt_join_*, dvt_rv32_hunt_join_job) */
 uint32_t dvt_abi_version(void);
 /* the handle's hipStream_t (for event timing by the caller) */
 void *dvt_stream(dvt_prover *p);
@@ -326,6 +327,77 @@ int dvt_stage_hunt_pairs(dvt_prover *p, const char *machine, uint32_t chip, cons
                          const uint32_t *cols, uint32_t n_cols, uint32_t adjacent, uint32_t row_first, uint32_t row_count,
                          uint64_t max_evals, dvt_escape *out, size_t cap, uint64_t *n_reported, uint64_t *n_tried);
 
+/* The join hunt: two-cell forgeries ACROSS tables and distant rows, and single cells that a lookup table absorbs.  The hunts
+ * above stop at the edge of one table and at a distance of one row, and call a change caught as soon as the multiset of its
+ * touched rows differs from the honest one.  The join keeps that difference and looks for the other half.
+ *   window     (tag, chip, matrices, log_n, pub, row_first, row_count, optional columns): rows of one table instance.  tag
+ *              (< 2^16) names the instance, e.g. a shard position.  The same (tag, chip) may be added more than once only with
+ *              disjoint windows and the same log_n.
+ *   candidate  (window, col, row, delta), delta from the call's list; touched rows {row - 1, row} mod n as above.
+ *   supply     a table whose receive interactions carry preprocessed values under a bare multiplicity column (rv32 program,
+ *              byte, mem_image; toy range8).  Its tuples are the values of its interactions on EVERY row, whatever the
+ *              multiplicity holds: a forger re-counts that column.  Supply tables are not hunted (every change of their
+ *              multiplicity cells is absorbed by definition).  WHETHER A CHIP MAY SERVE AS ONE IS THE CALLER'S STATEMENT: the
+ *              call only refuses the chips that have no supply launch (DVT_ERR_UNSUPPORTED).
+ *   difference D = (multiset of the touched rows under the change) - (honest multiset of those rows), after removing from
+ *              both every tuple a supply table holds; D_all is the same over all tuples.  The device works with the
+ *              fingerprint of the hunts above (three sums mod p), one key for the whole call, computed over all tuples and
+ *              over the unsupplied ones; a tuple counts as supplied when its 64-bit key is in the supply set.
+ *   outcome    caught by a constraint: nothing is kept.  free (D_all = 0): the business of dvt_stage_hunt_cells, nothing is
+ *              kept.  ABSORBED (D_all != 0, D = 0): a one-cell finding.  OPEN (D != 0): a record is kept.
+ *   group      a value D with the open records whose difference is D on one side and those whose difference is -D on the
+ *              other; both sides non-empty.  Its pairs are the combinations of one cell of each side, EXCEPT those whose two
+ *              cells lie in the same (tag, chip) at circular row distance <= 1: there the touched rows overlap, the
+ *              differences do not add, and the pair belongs to dvt_stage_hunt_pairs.  A group that keeps no pair is dropped.
+ *              For every pair that remains the touched rows are disjoint or lie in different tables, so constraints and
+ *              multisets add: the pair escapes the whole machine, up to the fingerprint's miss probability stated above.
+ * NOT LOOKED AT, and no soundness claim follows from an empty answer: three or more cells; a pair in which one half is caught
+ * by a constraint and repaired by the other; permutation and quotient columns.
+ * Order: new -> supply* -> add+ -> match -> result -> free.  A supply after the first add, overlapping windows of one (tag,
+ * chip) and a tag >= 2^16 are DVT_ERR_INPUT, with everything the hunts above refuse.  The supply tables' matrices must stay
+ * valid until the first add returns (the set is built then: its capacity is a power of two of at least four times the number
+ * of keys; a key that finds no slot in 64 probes fails the call with DVT_ERR_INPUT "supply set too small").  add runs the
+ * precondition on the window's table (DVT_ERR_REJECTED) and refuses more than max_evals evaluations (0: 2^33) before
+ * anything is launched.  cap_records / cap_absorbed: records kept on the device (0: 2^22); the totals keep counting past
+ * them.  log_slots (0: twice the stored records, rounded up to a power of two; else 6..26): the slots of the join's table;
+ * a record that finds none in 64 probes is left out and sets DVT_JOIN_TRUNC_PROBES.  Whatever is truncated, every group
+ * that comes back is a subset of a true group.  After an add that fails with DVT_ERR_DEVICE the join takes no further add or
+ * match: free it.  Every call runs on lane 0 of device 0 of the handle and synchronises. */
+#define DVT_JOIN_TRUNC_RECORDS 1u  /* more open records than cap_records */
+#define DVT_JOIN_TRUNC_ABSORBED 2u /* more absorbed cells than cap_absorbed */
+#define DVT_JOIN_TRUNC_PROBES 4u   /* a record found no slot of the join's table */
+#define DVT_JOIN_TRUNC_OUTPUT 8u   /* more matched records than the device's output array holds */
+#define DVT_JOIN_NO_GROUP 0xffffffffu
+typedef struct {
+    uint32_t group, side;                 /* group index, side 0 | 1; an absorbed cell: DVT_JOIN_NO_GROUP, 0 */
+    uint32_t tag, chip, col, row, delta;  /* delta canonical */
+} dvt_join_cell;                          /* 28 bytes */
+typedef struct {
+    uint64_t candidates;                      /* (window, col, row, delta) evaluated */
+    uint64_t open_emitted, open_stored;       /* open records: all, and those below cap_records */
+    uint64_t absorbed_emitted, absorbed_stored;
+    uint64_t matched;                         /* records whose slot has both sides */
+    uint64_t groups, pairs;                   /* after the exclusion rule */
+    uint32_t truncated, reserved;             /* DVT_JOIN_TRUNC_* */
+} dvt_join_summary;                           /* 72 bytes */
+typedef struct dvt_hunt_join dvt_hunt_join;
+int dvt_stage_hunt_join_new(dvt_prover *p, const char *machine, uint64_t seed, const uint32_t *deltas, uint32_t n_deltas,
+                            size_t cap_records, size_t cap_absorbed, uint32_t log_slots, dvt_hunt_join **join);
+int dvt_stage_hunt_join_supply(dvt_prover *p, dvt_hunt_join *join, uint32_t chip, const uint32_t *d_main, const uint32_t *d_prep,
+                               uint32_t log_n, const uint32_t *pub);
+/* cols (host, n_cols entries in any order, repeats count once; or NULL = every main column) */
+int dvt_stage_hunt_join_add(dvt_prover *p, dvt_hunt_join *join, uint32_t tag, uint32_t chip, const uint32_t *d_main,
+                            const uint32_t *d_prep, uint32_t log_n, const uint32_t *pub, uint32_t row_first, uint32_t row_count,
+                            const uint32_t *cols, uint32_t n_cols, uint64_t max_evals);
+/* once, after the last add */
+int dvt_stage_hunt_join_match(dvt_prover *p, dvt_hunt_join *join, dvt_join_summary *summary);
+/* cells: the groups' cells, groups sorted by the lowest (tag, chip, row, col, delta) of their side 0, which is the side that
+ * holds the group's lowest cell; inside a group side 0 first, each side in that order.  absorbed: sorted likewise.
+ * *n_cells / *n_absorbed: ALL there are; min(cap, all) are written, so a count above its cap says the list is cut. */
+int dvt_stage_hunt_join_result(dvt_prover *p, dvt_hunt_join *join, dvt_join_cell *cells, size_t cap_cells, size_t *n_cells,
+                               dvt_join_cell *absorbed, size_t cap_absorbed, size_t *n_absorbed);
+int dvt_stage_hunt_join_free(dvt_prover *p, dvt_hunt_join *join);
+
 /* The two hashing kernels of the device verifier (dvt_prover_verify), driven at chosen shapes without a proof.  Both
  * take and return HOST arrays of canonical words (a word >= p is DVT_ERR_INPUT) and are synchronous.
  * dvt_stage_sponge_rows: n word vectors, concatenated in `words`, of lens[i] words each -> digests [n][8]: the sponge of
@@ -518,6 +590,24 @@ int dvt_rv32_hunt_shard(dvt_prover *p, const dvt_pk *pk, dvt_job *job, size_t sh
                         const uint32_t *deltas, uint32_t n_deltas, uint32_t pairs, const uint32_t *cols, uint32_t n_cols,
                         uint32_t adjacent, uint32_t row_first, uint32_t row_count, uint64_t max_evals, uint32_t *free_counts,
                         uint8_t *free_map, dvt_escape *out, size_t cap, uint64_t *n_reported, uint64_t *n_tried);
+/* The join hunt (dvt_stage_hunt_join_*) over windows of a prepared job's tables.  A window is (shard, chip, row_first,
+ * row_count), row_count 0 = from row_first to the end of the table; its tag is the shard index.  Traces are taken as
+ * dvt_rv32_hunt_shard takes them, one shard after the other in the order of their first window; the supply tables are the
+ * tables of supply_chips (n_supply may be 0) in the FIRST window's shard.  cols_count (or NULL = every main column of every
+ * window) gives each window's number of listed columns, 0 = every column, and cols holds the lists one after the other.
+ * Outputs as dvt_stage_hunt_join_match and dvt_stage_hunt_join_result give them, written only by a call that returns DVT_OK.
+ * The job is left as found: dvt_rv32_prove_job afterwards returns the bytes it would have returned without the hunt.
+ * All windows must lie on shards held by ONE member of the handle, else DVT_ERR_UNSUPPORTED: the join's supply set, record
+ * arrays and table live on one lane of one device, and joining across devices is out of scope.  DVT_ERR_INPUT: what the
+ * stage calls refuse, no window, a shard the job does not hold, a chip the shard has no table of. */
+typedef struct {
+    uint32_t shard, chip, row_first, row_count;
+} dvt_join_window;
+int dvt_rv32_hunt_join_job(dvt_prover *p, const dvt_pk *pk, dvt_job *job, const dvt_join_window *windows, size_t n_windows,
+                           const uint32_t *supply_chips, uint32_t n_supply, uint64_t seed, const uint32_t *deltas, uint32_t n_deltas,
+                           const uint32_t *cols, const uint32_t *cols_count, uint64_t max_evals, size_t cap_records,
+                           size_t cap_absorbed, uint32_t log_slots, dvt_join_summary *summary, dvt_join_cell *cells, size_t cap_cells,
+                           size_t *n_cells, dvt_join_cell *absorbed, size_t cap_absorbed_out, size_t *n_absorbed);
 /* The unmatched LogUp tuples of a job (the bus ledger, dvt_stage_bus_ledger_*): what dvt_rv32_check_job's bus mask stands
  * for.  The traces of every shard the job holds are taken as dvt_rv32_check_job takes them, on the device that holds the
  * shard, and the job is left as found; first_tag is the shard's position, first_chip 0xffffffff one of the eight verifier-
