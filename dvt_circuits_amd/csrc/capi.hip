@@ -1,7 +1,7 @@
 // C-ABI layer (include/dvt_prover.h) over the gfx950 engine: the handle and its config, the entry guard and the error path,
-// the stage entry points and the machine-level ones (the rv32 boundary is capi_rv32.hip).  There is no CPU fallback
-// anywhere in this layer: without a HIP device every entry point that computes returns DVT_ERR_DEVICE.  (dvt_machine_verify
-// is host-only by nature.)
+// the stage entry points of the prover's kernels and the machine-level ones (the rv32 boundary is capi_rv32.hip, the
+// inspectors of trace rows capi_inspect.hip).  There is no CPU fallback anywhere in this layer: without a HIP device every
+// entry point that computes returns DVT_ERR_DEVICE.  (dvt_machine_verify is host-only by nature.)
 #include <algorithm>
 #include <cstdarg>
 #include <cstdio>
@@ -9,7 +9,6 @@
 #include <chrono>
 
 #include "capi_internal.h"
-#include "ledger_key.h"
 #include "verify_query.h"
 
 using namespace dvt;
@@ -235,61 +234,35 @@ int verify_words(const uint8_t *proof, size_t len, int len_code, char **reason,
     return rc ? reject(reason, rc, why) : DVT_OK;
 }
 
-int check_tables(const Lane &c, const MachineDesc *m, const std::vector<CheckTable> &tabs, const std::vector<uint32_t> &pub_mont,
-                 const CheckChallenges &ch, bool constraints, bool buses, std::vector<CheckTableOut> *out) {
-    Engine &e = c.eng;
-    constexpr size_t BW = 4 * DVT_CHECK_BUSES;
-    // result words: one 64-bit key per table, then per table its counts and its bus sums
-    std::vector<size_t> at(tabs.size());
-    size_t words = 2 * tabs.size();
-    for (size_t i = 0; i < tabs.size(); i++) {
-        if (!tabs[i].d->launch_check || !tabs[i].d->launch_bus) return fail(c.err, DVT_ERR_UNSUPPORTED, "chip %s has no trace-row check", tabs[i].d->name);
-        at[i] = words;
-        words += (size_t)tabs[i].d->n_constraints + BW;
+
+// ---- K4 / K5 of one chip: the argument checks both entries share (ChipStageArgs, capi_internal.h)
+int chip_stage_args(dvt_prover *p, const char *machine, uint32_t chip, uint32_t log_n, const uint32_t *pub, const uint32_t perm_alpha[4],
+                    const uint32_t beta[4], uint32_t path, ChipStageArgs *out) {
+    const MachineDesc *m = machine_by_name(machine);
+    if (!m) return fail(p, DVT_ERR_INPUT, "unknown machine '%s'", machine ? machine : "(null)");
+    if (chip >= (uint32_t)m->n_chips) return fail(p, DVT_ERR_INPUT, "chip %u out of range (%d chips)", chip, m->n_chips);
+    out->m = m;
+    out->d = &m->chips[chip];
+    challenge_power_counts(m, &out->n_beta, &out->n_alpha);
+    if (log_n > 22) return fail(p, DVT_ERR_INPUT, "log_n %u > 22", log_n);
+    if (path > DVT_PATH_PARTS) return fail(p, DVT_ERR_INPUT, "path %u", path);
+    if (path == DVT_PATH_PARTS && log_n > PARTS_PARALLEL_LOG)
+        return fail(p, DVT_ERR_INPUT, "the part-parallel launches take at most 2^%u rows", PARTS_PARALLEL_LOG);
+    if (!perm_alpha || !beta || (out->d->n_pub && !pub)) return fail(p, DVT_ERR_INPUT, "null argument");
+    if (!ext_from_canonical(perm_alpha, &out->perm_alpha) || !ext_from_canonical(beta, &out->beta))
+        return fail(p, DVT_ERR_INPUT, "perm_alpha or beta not canonical");
+    out->pub.assign(std::max(out->d->n_pub, 1), 0);
+    for (int k = 0; k < out->d->n_pub; k++) {
+        if (pub[k] >= P) return fail(p, DVT_ERR_INPUT, "public value %d not canonical", k);
+        out->pub[k] = Fp::from_canonical(pub[k]).v;
     }
-    out->assign(tabs.size(), CheckTableOut{});
-    for (auto &o : *out) {
-        o.r = dvt_check_result{0, 0, -1};
-        for (auto &b : o.bus) b = Fp4::zero();
-    }
-    if (tabs.empty()) return DVT_OK;
-    StageBuf res{e.pool}, partial{e.pool};
-    HIP_TRY(c.err, e.pool.alloc_bytes(&res.ptr, words * 4));
-    if (buses) HIP_TRY(c.err, e.pool.alloc_bytes(&partial.ptr, BUS_PARTIAL_WORDS * 4));
-    uint32_t *d_res = static_cast<uint32_t *>(res.ptr);
-    HIP_TRY(c.err, hipMemsetAsync(d_res, 0xff, 8 * tabs.size(), e.stream));
-    HIP_TRY(c.err, hipMemsetAsync(d_res + 2 * tabs.size(), 0, (words - 2 * tabs.size()) * 4, e.stream));
-    int n_beta, n_alpha;
-    challenge_power_counts(m, &n_beta, &n_alpha);
-    const Fp4 *d_xi = nullptr, *d_beta = nullptr;
-    const double *d_xi_f64 = nullptr, *d_beta_f64 = nullptr;
-    const uint32_t *d_pub = static_cast<const uint32_t *>(e.upload_vec(pub_mont));
-    if (!d_pub || (constraints && !e.upload_powers(ch.xi, (size_t)n_alpha, true, &d_xi, &d_xi_f64)) ||
-        (buses && !e.upload_powers(ch.beta, (size_t)n_beta, false, &d_beta, &d_beta_f64)))
-        return engine_fail(c.err, e);
-    for (size_t i = 0; i < tabs.size(); i++) {
-        const CheckTable &t = tabs[i];
-        if (constraints) {
-            const CheckArgs ca{t.main, t.prep, d_pub, d_xi, d_xi_f64, t.log_n, d_res + at[i], reinterpret_cast<unsigned long long *>(d_res) + i};
-            HIP_TRY(c.err, t.d->launch_check(e.stream, ca));
-        }
-        if (buses) {
-            const BusArgs ba{t.main, t.prep, d_pub, d_beta_f64, ch.perm_alpha, t.log_n, static_cast<uint32_t *>(partial.ptr), d_res + at[i] + t.d->n_constraints};
-            HIP_TRY(c.err, t.d->launch_bus(e.stream, ba));
-        }
-    }
-    std::vector<uint32_t> h(words);
-    if (!e.download(h.data(), d_res, words * 4)) return engine_fail(c.err, e);
-    for (size_t i = 0; i < tabs.size(); i++) {
-        CheckTableOut &o = (*out)[i];
-        const uint32_t *cw = h.data() + at[i];
-        o.counts.assign(cw, cw + tabs[i].d->n_constraints);
-        for (uint32_t x : o.counts) o.r.violations += x;
-        const uint64_t key = (uint64_t)h[2 * i] | ((uint64_t)h[2 * i + 1] << 32);
-        if (key != CHECK_NO_KEY) { o.r.first_row = (uint32_t)(key >> 32); o.r.first_constraint = (int32_t)(uint32_t)key; }
-        for (uint32_t b = 0; b < DVT_CHECK_BUSES; b++)
-            for (int k = 0; k < 4; k++) o.bus[b].c[k] = Fp::raw(cw[tabs[i].d->n_constraints + 4 * b + k]);
-    }
+    return DVT_OK;
+}
+int stage_table(dvt_prover *p, const char *machine, uint32_t chip, const uint32_t *d_main, const uint32_t *d_prep, uint32_t log_n,
+                const uint32_t *pub, ChipStageArgs *out, const uint32_t *perm_alpha, const uint32_t *beta) {
+    if (int rc = chip_stage_args(p, machine, chip, log_n, pub, perm_alpha, beta, DVT_PATH_DEFAULT, out)) return rc;
+    if (!d_main || (out->d->prep_w && !d_prep)) return fail(p, DVT_ERR_INPUT, "null matrix");
+    out->t = {out->d, d_main, out->d->prep_w ? d_prep : nullptr, log_n};
     return DVT_OK;
 }
 }  // namespace dvt
@@ -464,14 +437,6 @@ int dvt_stage_poseidon2_permute(dvt_prover *p, uint32_t *d_states, size_t n) {
     return DVT_OK;
 }
 
-static bool ext_from_canonical(const uint32_t w[4], Fp4 *out) {
-    for (int k = 0; k < 4; k++) {
-        if (w[k] >= P) return false;
-        out->c[k] = Fp::from_canonical(w[k]);
-    }
-    return true;
-}
-
 int dvt_stage_fri_fold(dvt_prover *p, const uint32_t *d_v, uint32_t *d_out, const uint32_t *d_ro, const uint32_t beta[4],
                        uint32_t log_m) {
     if (!p || !d_v || !d_out || !beta) return fail(p, DVT_ERR_INPUT, "null argument");
@@ -587,34 +552,6 @@ int dvt_stage_pow_grind(dvt_prover *p, const uint32_t state[16], uint32_t pos, u
     return DVT_OK;
 }
 
-// ---- K4 / K5 of one chip: the argument checks both entries share
-struct ChipStageArgs {
-    const ChipDesc *d = nullptr;
-    std::vector<uint32_t> pub;   // Montgomery words, at least one
-    Fp4 perm_alpha, beta;
-    int n_beta = 0, n_alpha = 0;   // challenge powers the machine's kernels read
-};
-static int chip_stage_args(dvt_prover *p, const char *machine, uint32_t chip, uint32_t log_n, const uint32_t *pub,
-                           const uint32_t perm_alpha[4], const uint32_t beta[4], uint32_t path, ChipStageArgs *out) {
-    const MachineDesc *m = machine_by_name(machine);
-    if (!m) return fail(p, DVT_ERR_INPUT, "unknown machine '%s'", machine ? machine : "(null)");
-    if (chip >= (uint32_t)m->n_chips) return fail(p, DVT_ERR_INPUT, "chip %u out of range (%d chips)", chip, m->n_chips);
-    out->d = &m->chips[chip];
-    challenge_power_counts(m, &out->n_beta, &out->n_alpha);
-    if (log_n > 22) return fail(p, DVT_ERR_INPUT, "log_n %u > 22", log_n);
-    if (path > DVT_PATH_PARTS) return fail(p, DVT_ERR_INPUT, "path %u", path);
-    if (path == DVT_PATH_PARTS && log_n > PARTS_PARALLEL_LOG)
-        return fail(p, DVT_ERR_INPUT, "the part-parallel launches take at most 2^%u rows", PARTS_PARALLEL_LOG);
-    if (!perm_alpha || !beta || (out->d->n_pub && !pub)) return fail(p, DVT_ERR_INPUT, "null argument");
-    if (!ext_from_canonical(perm_alpha, &out->perm_alpha) || !ext_from_canonical(beta, &out->beta))
-        return fail(p, DVT_ERR_INPUT, "perm_alpha or beta not canonical");
-    out->pub.assign(std::max(out->d->n_pub, 1), 0);
-    for (int k = 0; k < out->d->n_pub; k++) {
-        if (pub[k] >= P) return fail(p, DVT_ERR_INPUT, "public value %d not canonical", k);
-        out->pub[k] = Fp::from_canonical(pub[k]).v;
-    }
-    return DVT_OK;
-}
 // the part-parallel scratch of a K4 / K5 call, or nullptr (the per-row / per-part launches); words per row of the scratch
 static int chip_stage_parts(dvt_prover *p, uint32_t path, bool has_parts, uint32_t log_n, size_t words_per_row, StageBuf *buf,
                             uint32_t **d_parts) {
@@ -694,247 +631,6 @@ int dvt_stage_quotient(dvt_prover *p, const char *machine, uint32_t chip, const 
                          d_out))
         return engine_fail(p->err, e);
     return DVT_OK;
-}
-
-// ---- the trace-row checks of one chip (check.cuh)
-int dvt_stage_check_constraints(dvt_prover *p, const char *machine, uint32_t chip, const uint32_t *d_main, const uint32_t *d_prep,
-                                uint32_t log_n, const uint32_t *pub, const uint32_t xi[4], uint32_t *counts, dvt_check_result *out) {
-    if (!p) return DVT_ERR_INPUT;
-    if (!xi || !out) return fail(p, DVT_ERR_INPUT, "null argument");
-    ChipStageArgs a;
-    CheckChallenges ch;
-    if (!ext_from_canonical(xi, &ch.xi)) return fail(p, DVT_ERR_INPUT, "xi not canonical");
-    // (the checks of machine, chip, log_n and pub that K4 / K5 make; xi stands in for the two challenges this call has not)
-    if (int rc = chip_stage_args(p, machine, chip, log_n, pub, xi, xi, DVT_PATH_DEFAULT, &a)) return rc;
-    if (!d_main || (a.d->prep_w && !d_prep)) return fail(p, DVT_ERR_INPUT, "null matrix");
-    ch.perm_alpha = ch.beta = Fp4::zero();
-    Guard g(p); if (g.rc) return g.rc;
-    std::vector<CheckTableOut> res;
-    if (int rc = check_tables(lane0(p), machine_by_name(machine), {{a.d, d_main, a.d->prep_w ? d_prep : nullptr, log_n}}, a.pub, ch, true, false, &res)) return rc;
-    if (counts) memcpy(counts, res[0].counts.data(), res[0].counts.size() * 4);
-    *out = res[0].r;
-    return DVT_OK;
-}
-
-int dvt_stage_bus_sums(dvt_prover *p, const char *machine, uint32_t chip, const uint32_t *d_main, const uint32_t *d_prep, uint32_t log_n,
-                       const uint32_t *pub, const uint32_t perm_alpha[4], const uint32_t beta[4], uint32_t out[DVT_CHECK_BUSES][4]) {
-    if (!p) return DVT_ERR_INPUT;
-    if (!out) return fail(p, DVT_ERR_INPUT, "null argument");
-    ChipStageArgs a;
-    if (int rc = chip_stage_args(p, machine, chip, log_n, pub, perm_alpha, beta, DVT_PATH_DEFAULT, &a)) return rc;
-    if (!d_main || (a.d->prep_w && !d_prep)) return fail(p, DVT_ERR_INPUT, "null matrix");
-    const CheckChallenges ch{Fp4::zero(), a.perm_alpha, a.beta};
-    Guard g(p); if (g.rc) return g.rc;
-    std::vector<CheckTableOut> res;
-    if (int rc = check_tables(lane0(p), machine_by_name(machine), {{a.d, d_main, a.d->prep_w ? d_prep : nullptr, log_n}}, a.pub, ch, false, true, &res)) return rc;
-    for (uint32_t b = 0; b < DVT_CHECK_BUSES; b++)
-        for (int k = 0; k < 4; k++) out[b][k] = res[0].bus[b].c[k].canonical();
-    return DVT_OK;
-}
-
-// ---- the bus ledger of chip tables (ledger.cuh), on lane 0 of member 0
-static int ledger_stage_rows(dvt_prover *p, dvt_bus_ledger *l, uint32_t chip, const uint32_t *d_main, const uint32_t *d_prep, uint32_t log_n,
-                             const uint32_t *pub, uint32_t tag, bool collect) {
-    if (!p) return DVT_ERR_INPUT;
-    if (!l) return fail(p, DVT_ERR_INPUT, "null ledger");
-    if (l->closed != collect) return fail(p, DVT_ERR_INPUT, collect ? "collect before close" : "add after close");
-    static const uint32_t zero[4] = {0, 0, 0, 0};   // (the checks of chip, log_n and pub that K4 / K5 make; no challenge here)
-    ChipStageArgs a;
-    if (int rc = chip_stage_args(p, l->m->name, chip, log_n, pub, zero, zero, DVT_PATH_DEFAULT, &a)) return rc;
-    if (tag >= (1u << 16)) return fail(p, DVT_ERR_INPUT, "tag %u >= 2^16", tag);
-    if (!d_main || (a.d->prep_w && !d_prep)) return fail(p, DVT_ERR_INPUT, "null matrix");
-    if (collect && !l->n_dirty) return DVT_OK;
-    Guard g(p); if (g.rc) return g.rc;
-    const Lane c = lane0(p);
-    const uint32_t *d_pub = static_cast<const uint32_t *>(c.eng.upload_vec(a.pub));
-    if (!d_pub) return engine_fail(p->err, c.eng);
-    if (int rc = ledger_rows(c, l->dev, *a.d, chip, d_main, a.d->prep_w ? d_prep : nullptr, log_n, d_pub, tag, collect)) return rc;
-    HIP_TRY(p, hipStreamSynchronize(c.eng.stream));
-    return DVT_OK;
-}
-
-int dvt_stage_bus_ledger_new(dvt_prover *p, const char *machine, uint32_t log_buckets, uint32_t cap_slots, uint64_t seed, dvt_bus_ledger **ledger) {
-    if (!p) return DVT_ERR_INPUT;
-    if (!ledger) return fail(p, DVT_ERR_INPUT, "null argument");
-    *ledger = nullptr;
-    const MachineDesc *m = machine_by_name(machine);
-    if (!m) return fail(p, DVT_ERR_INPUT, "unknown machine '%s'", machine ? machine : "(null)");
-    Guard g(p); if (g.rc) return g.rc;
-    std::unique_ptr<dvt_bus_ledger> l(new dvt_bus_ledger());
-    l->m = m;
-    if (int rc = ledger_init(lane0(p), &l->dev, log_buckets, cap_slots, seed)) return rc;
-    HIP_TRY(p, hipStreamSynchronize(eng0(p).stream));
-    *ledger = l.release();
-    return DVT_OK;
-}
-
-int dvt_stage_bus_ledger_add(dvt_prover *p, dvt_bus_ledger *ledger, uint32_t chip, const uint32_t *d_main, const uint32_t *d_prep,
-                             uint32_t log_n, const uint32_t *pub, uint32_t tag) {
-    return ledger_stage_rows(p, ledger, chip, d_main, d_prep, log_n, pub, tag, false);
-}
-
-int dvt_stage_bus_ledger_collect(dvt_prover *p, dvt_bus_ledger *ledger, uint32_t chip, const uint32_t *d_main, const uint32_t *d_prep,
-                                 uint32_t log_n, const uint32_t *pub, uint32_t tag) {
-    return ledger_stage_rows(p, ledger, chip, d_main, d_prep, log_n, pub, tag, true);
-}
-
-int dvt_stage_bus_ledger_add_tuple(dvt_prover *p, dvt_bus_ledger *ledger, uint32_t bus, const uint32_t *values, uint32_t arity, int32_t sign,
-                                   uint32_t mult, uint32_t tag) {
-    if (!p) return DVT_ERR_INPUT;
-    if (!ledger || (arity && !values)) return fail(p, DVT_ERR_INPUT, "null argument");
-    if (ledger->closed && !ledger->n_dirty) return DVT_OK;
-    Guard g(p); if (g.rc) return g.rc;
-    if (int rc = ledger_tuple(lane0(p), ledger->dev, bus, values, arity, sign, mult, tag, ledger->closed)) return rc;
-    HIP_TRY(p, hipStreamSynchronize(eng0(p).stream));
-    return DVT_OK;
-}
-
-int dvt_stage_bus_ledger_close(dvt_prover *p, dvt_bus_ledger *ledger, uint32_t *n_dirty) {
-    if (!p) return DVT_ERR_INPUT;
-    if (!ledger || !n_dirty) return fail(p, DVT_ERR_INPUT, "null argument");
-    if (ledger->closed) return fail(p, DVT_ERR_INPUT, "the ledger is closed already");
-    Guard g(p); if (g.rc) return g.rc;
-    if (int rc = ledger_close(lane0(p), ledger->dev, &ledger->n_dirty)) return rc;
-    ledger->closed = true;
-    *n_dirty = ledger->n_dirty;
-    return DVT_OK;
-}
-
-int dvt_stage_bus_ledger_result(dvt_prover *p, dvt_bus_ledger *ledger, dvt_bus_tuple *out, size_t cap, size_t *n_tuples, uint32_t *truncated) {
-    if (!p) return DVT_ERR_INPUT;
-    if (!ledger || !n_tuples || !truncated || (cap && !out)) return fail(p, DVT_ERR_INPUT, "null argument");
-    if (!ledger->closed) return fail(p, DVT_ERR_INPUT, "result before close");
-    Guard g(p); if (g.rc) return g.rc;
-    std::vector<dvt_bus_tuple> all;
-    bool overflow = false;
-    if (int rc = ledger_records(lane0(p), ledger->dev, &all, &overflow)) return rc;
-    ledger_finish(&all);
-    ledger_copy_out(all, overflow, out, cap, n_tuples, truncated);
-    return DVT_OK;
-}
-
-int dvt_stage_bus_ledger_free(dvt_prover *p, dvt_bus_ledger *ledger) {
-    if (!p) return DVT_ERR_INPUT;
-    if (!ledger) return fail(p, DVT_ERR_INPUT, "null ledger");
-    Guard g(p); if (g.rc) return g.rc;
-    (void)hipStreamSynchronize(eng0(p).stream);
-    ledger_release(&ledger->dev);
-    delete ledger;
-    return DVT_OK;
-}
-
-// ---- the forgery hunt of one chip table (hunt.cuh), on lane 0 of member 0
-static int hunt_stage(dvt_prover *p, const char *machine, uint32_t chip, const uint32_t *d_main, const uint32_t *d_prep, uint32_t log_n,
-                      const uint32_t *pub, const HuntRequest &rq) {
-    if (!p) return DVT_ERR_INPUT;
-    static const uint32_t zero[4] = {0, 0, 0, 0};   // (the checks of machine, chip, log_n and pub that K4 / K5 make; no challenge here)
-    ChipStageArgs a;
-    if (int rc = chip_stage_args(p, machine, chip, log_n, pub, zero, zero, DVT_PATH_DEFAULT, &a)) return rc;
-    if (!d_main || (a.d->prep_w && !d_prep)) return fail(p, DVT_ERR_INPUT, "null matrix");
-    HuntPlan plan;
-    if (int rc = hunt_plan(p->err, *a.d, log_n, rq, &plan)) return rc;
-    Guard g(p); if (g.rc) return g.rc;
-    return hunt_table(lane0(p), machine_by_name(machine), {a.d, d_main, a.d->prep_w ? d_prep : nullptr, log_n}, a.pub, rq, plan);
-}
-
-int dvt_stage_hunt_cells(dvt_prover *p, const char *machine, uint32_t chip, const uint32_t *d_main, const uint32_t *d_prep,
-                         uint32_t log_n, const uint32_t *pub, uint64_t seed, const uint32_t *deltas, uint32_t n_deltas,
-                         uint32_t row_first, uint32_t row_count, uint64_t max_evals, uint32_t *free_counts, uint8_t *free_map) {
-    HuntRequest rq = hunt_request(seed, deltas, n_deltas, row_first, row_count, max_evals);
-    hunt_want_cells(&rq, free_counts, free_map);
-    return hunt_stage(p, machine, chip, d_main, d_prep, log_n, pub, rq);
-}
-
-int dvt_stage_hunt_pairs(dvt_prover *p, const char *machine, uint32_t chip, const uint32_t *d_main, const uint32_t *d_prep,
-                         uint32_t log_n, const uint32_t *pub, uint64_t seed, const uint32_t *deltas, uint32_t n_deltas,
-                         const uint32_t *cols, uint32_t n_cols, uint32_t adjacent, uint32_t row_first, uint32_t row_count,
-                         uint64_t max_evals, dvt_escape *out, size_t cap, uint64_t *n_reported, uint64_t *n_tried) {
-    HuntRequest rq = hunt_request(seed, deltas, n_deltas, row_first, row_count, max_evals);
-    hunt_want_pairs(&rq, cols, n_cols, adjacent, out, cap, n_reported, n_tried);
-    return hunt_stage(p, machine, chip, d_main, d_prep, log_n, pub, rq);
-}
-
-// ---- the join hunt over windows of several chip tables (hunt_join.cuh), on lane 0 of member 0
-int dvt_stage_hunt_join_new(dvt_prover *p, const char *machine, uint64_t seed, const uint32_t *deltas, uint32_t n_deltas, size_t cap_records,
-                            size_t cap_absorbed, uint32_t log_slots, dvt_hunt_join **join) {
-    if (!p) return DVT_ERR_INPUT;
-    if (!join) return fail(p, DVT_ERR_INPUT, "null argument");
-    *join = nullptr;
-    const MachineDesc *m = machine_by_name(machine);
-    if (!m) return fail(p, DVT_ERR_INPUT, "unknown machine '%s'", machine ? machine : "(null)");
-    Guard g(p); if (g.rc) return g.rc;
-    std::unique_ptr<dvt_hunt_join> j(new dvt_hunt_join());
-    if (int rc = join_init(lane0(p), &j->dev, m, seed, deltas, n_deltas, cap_records, cap_absorbed, log_slots)) {
-        join_release(&j->dev);
-        return rc;
-    }
-    HIP_TRY(p, hipStreamSynchronize(eng0(p).stream));
-    *join = j.release();
-    return DVT_OK;
-}
-
-int dvt_stage_hunt_join_supply(dvt_prover *p, dvt_hunt_join *join, uint32_t chip, const uint32_t *d_main, const uint32_t *d_prep, uint32_t log_n,
-                               const uint32_t *pub) {
-    if (!p) return DVT_ERR_INPUT;
-    if (!join) return fail(p, DVT_ERR_INPUT, "null join");
-    static const uint32_t zero[4] = {0, 0, 0, 0};   // (the checks of chip, log_n and pub that K4 / K5 make; no challenge here)
-    ChipStageArgs a;
-    if (int rc = chip_stage_args(p, join->dev.m->name, chip, log_n, pub, zero, zero, DVT_PATH_DEFAULT, &a)) return rc;
-    if (!d_main || (a.d->prep_w && !d_prep)) return fail(p, DVT_ERR_INPUT, "null matrix");
-    Guard g(p); if (g.rc) return g.rc;
-    return join_supply(p->err, join->dev, {a.d, d_main, a.d->prep_w ? d_prep : nullptr, log_n}, a.pub);
-}
-
-int dvt_stage_hunt_join_add(dvt_prover *p, dvt_hunt_join *join, uint32_t tag, uint32_t chip, const uint32_t *d_main, const uint32_t *d_prep,
-                            uint32_t log_n, const uint32_t *pub, uint32_t row_first, uint32_t row_count, const uint32_t *cols, uint32_t n_cols,
-                            uint64_t max_evals) {
-    if (!p) return DVT_ERR_INPUT;
-    if (!join) return fail(p, DVT_ERR_INPUT, "null join");
-    static const uint32_t zero[4] = {0, 0, 0, 0};
-    ChipStageArgs a;
-    if (int rc = chip_stage_args(p, join->dev.m->name, chip, log_n, pub, zero, zero, DVT_PATH_DEFAULT, &a)) return rc;
-    if (!d_main || (a.d->prep_w && !d_prep)) return fail(p, DVT_ERR_INPUT, "null matrix");
-    std::vector<uint32_t> cl;
-    if (int rc = join_check_add(p->err, join->dev, tag, chip, *a.d, log_n, row_first, row_count, cols, n_cols, max_evals, &cl)) return rc;
-    Guard g(p); if (g.rc) return g.rc;
-    return join_add(lane0(p), join->dev, tag, chip, {a.d, d_main, a.d->prep_w ? d_prep : nullptr, log_n}, a.pub, row_first, row_count, cl);
-}
-
-int dvt_stage_hunt_join_match(dvt_prover *p, dvt_hunt_join *join, dvt_join_summary *summary) {
-    if (!p) return DVT_ERR_INPUT;
-    if (!join || !summary) return fail(p, DVT_ERR_INPUT, "null argument");
-    Guard g(p); if (g.rc) return g.rc;
-    if (int rc = join_match(lane0(p), join->dev)) return rc;
-    *summary = join->dev.summary;
-    return DVT_OK;
-}
-
-int dvt_stage_hunt_join_result(dvt_prover *p, dvt_hunt_join *join, dvt_join_cell *cells, size_t cap_cells, size_t *n_cells, dvt_join_cell *absorbed,
-                               size_t cap_absorbed, size_t *n_absorbed) {
-    if (!p) return DVT_ERR_INPUT;
-    if (!join || !n_cells || !n_absorbed || (cap_cells && !cells) || (cap_absorbed && !absorbed)) return fail(p, DVT_ERR_INPUT, "null argument");
-    Guard g(p); if (g.rc) return g.rc;
-    if (!join->dev.matched) return fail(p, DVT_ERR_INPUT, "result before match");
-    const JoinDev &j = join->dev;
-    std::copy_n(j.cells.begin(), std::min(cap_cells, j.cells.size()), cells);
-    std::copy_n(j.absorbed.begin(), std::min(cap_absorbed, j.absorbed.size()), absorbed);
-    *n_cells = j.cells.size();
-    *n_absorbed = j.absorbed.size();
-    return DVT_OK;
-}
-
-int dvt_stage_hunt_join_free(dvt_prover *p, dvt_hunt_join *join) {
-    if (!p) return DVT_ERR_INPUT;
-    if (!join) return fail(p, DVT_ERR_INPUT, "null join");
-    Guard g(p); if (g.rc) return g.rc;
-    (void)hipStreamSynchronize(eng0(p).stream);
-    join_release(&join->dev);
-    delete join;
-    return DVT_OK;
-}
-
-uint64_t dvt_debug_ledger_key(uint64_t seed, uint32_t bus, uint32_t arity, const uint32_t *values) {
-    return values || !arity ? ledger_key(seed, bus, arity, values) : 0;
 }
 
 // ------------------------------------------------------------------ machine level

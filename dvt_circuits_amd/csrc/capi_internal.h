@@ -1,5 +1,5 @@
-// Private to the C-ABI layer: what capi.hip (the handle, the stage and machine-level entry points) and capi_rv32.hip
-// (the rv32 boundary: setup, the job and its pipelines, prove, assemble, verify) share.
+// Private to the C-ABI layer: what capi.hip (the handle, the stage and machine-level entry points), capi_rv32.hip (the rv32 boundary:
+// setup, the job of capi_job.h and its pipelines, prove, assemble, verify) and capi_inspect.hip (the inspectors of trace rows) share.
 #pragma once
 #include "../../include/dvt_prover.h"
 
@@ -179,8 +179,8 @@ struct StageBuf {
 };
 
 // ---- the trace-row checks (check.cuh) of a list of chip tables that share their public values, on one lane:
-// dvt_stage_check_constraints, dvt_stage_bus_sums and dvt_rv32_check_job go through this.  One download, which
-// synchronises the lane's stream, for the whole list.
+// dvt_stage_check_constraints, dvt_stage_bus_sums and dvt_rv32_check_job go through this (capi_inspect.hip).  One download,
+// which synchronises the lane's stream, for the whole list.
 struct CheckTable {
     const ChipDesc *d;
     const uint32_t *main, *prep;   // device, Montgomery, column-major (prep may be null when the chip has no such column)
@@ -198,6 +198,30 @@ struct CheckTableOut {
 int check_tables(const Lane &c, const MachineDesc *m, const std::vector<CheckTable> &tabs, const std::vector<uint32_t> &pub_mont,
                  const CheckChallenges &ch, bool constraints, bool buses, std::vector<CheckTableOut> *out);
 
+// ---- the arguments of the stage entry points that take one chip table: the checks of machine, chip, log_n, path, pub and the
+// two LogUp challenges that K4 / K5 make (dvt_stage_perm, dvt_stage_quotient), and for the inspectors (capi_inspect.hip) the
+// same checks and then the table's matrices; a call that has no challenges leaves them out
+inline bool ext_from_canonical(const uint32_t w[4], Fp4 *out) {
+    for (int k = 0; k < 4; k++) {
+        if (w[k] >= P) return false;
+        out->c[k] = Fp::from_canonical(w[k]);
+    }
+    return true;
+}
+struct ChipStageArgs {
+    const MachineDesc *m = nullptr;
+    const ChipDesc *d = nullptr;
+    std::vector<uint32_t> pub;   // Montgomery words, at least one (the table's pub_mont)
+    Fp4 perm_alpha, beta;
+    int n_beta = 0, n_alpha = 0;   // challenge powers the machine's kernels read
+    CheckTable t = {};             // (stage_table only)
+};
+int chip_stage_args(dvt_prover *p, const char *machine, uint32_t chip, uint32_t log_n, const uint32_t *pub, const uint32_t perm_alpha[4],
+                    const uint32_t beta[4], uint32_t path, ChipStageArgs *out);
+constexpr uint32_t NO_CHALLENGE[4] = {0, 0, 0, 0};
+int stage_table(dvt_prover *p, const char *machine, uint32_t chip, const uint32_t *d_main, const uint32_t *d_prep, uint32_t log_n,
+                const uint32_t *pub, ChipStageArgs *out, const uint32_t *perm_alpha = NO_CHALLENGE, const uint32_t *beta = NO_CHALLENGE);
+
 // ---- the bus ledger (ledger.cuh) on one lane: dvt_stage_bus_ledger_* and dvt_rv32_job_bus_tuples go through this
 // (ledger.hip).  Buffers come from the lane's pool and go back in ledger_release.
 struct LedgerDev {
@@ -211,9 +235,8 @@ struct LedgerDev {
 };
 int ledger_init(const Lane &c, LedgerDev *l, uint32_t log_buckets, uint32_t cap_slots, uint64_t seed);
 void ledger_release(LedgerDev *l);
-// one pass (mode: LEDGER_TALLY = 0, LEDGER_COLLECT = 1) over a chip table; d_pub: device, Montgomery
-int ledger_rows(const Lane &c, LedgerDev &l, const ChipDesc &d, uint32_t chip, const uint32_t *main, const uint32_t *prep, uint32_t log_n,
-                const uint32_t *d_pub, uint32_t tag, uint32_t mode);
+// one pass (mode: LEDGER_TALLY = 0, LEDGER_COLLECT = 1) over a chip table
+int ledger_rows(const Lane &c, LedgerDev &l, const CheckTable &t, uint32_t chip, const std::vector<uint32_t> &pub_mont, uint32_t tag, uint32_t mode);
 // a tuple the host adds (canonical values), keyed on the host
 int ledger_tuple(const Lane &c, LedgerDev &l, uint32_t bus, const uint32_t *values, uint32_t arity, int sign, uint32_t mult, uint32_t tag, uint32_t mode);
 int ledger_close(const Lane &c, LedgerDev &l, uint32_t *n_dirty);   // the bitmap on the device from the ledger's own tallies

@@ -1,25 +1,18 @@
-// The rv32 boundary of the C ABI (include/dvt_prover.h): setup from an ELF, execute, the job (the prepare pipeline and
-// phase 1, the phase-2 pipeline on the prover lanes), the prove entry points, assemble, verify and the debug hooks.
+// The rv32 boundary of the C ABI (include/dvt_prover.h): setup from an ELF, execute, the job (capi_job.h; the prepare pipeline and phase 1,
+// the phase-2 pipeline on the prover lanes), prove, assemble, verify and the debug hooks.  (A job's inspectors: capi_inspect.hip.)
 #include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <cstdio>
 #include <deque>
 #include <map>
 
-#include "capi_internal.h"
+#include "capi_job.h"
 #include "poseidon2_f64.cuh"
 #include "sha256.h"
 
 using namespace dvt;
 
 namespace {
-constexpr uint32_t N_PUB = rv32::N_PUBLIC;           // start_pc, next_pc, exit_code, shard, is_last
-constexpr uint32_t HEADER_WORDS = 8 + N_PUB;         // per-shard commitment header: main root + public values (canonical)
-constexpr uint32_t PV_BUS = 5;                       // tools/airgen/rv32.py BUSES["sys"]
-using Clock = std::chrono::steady_clock;
-
-double ms_since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
 std::vector<std::vector<uint8_t>> collect_stdin(const dvt_buf *bufs, size_t n) {
     std::vector<std::vector<uint8_t>> v(n);
     for (size_t i = 0; i < n; i++)
@@ -57,63 +50,7 @@ void pv_digest_words(const std::vector<uint8_t> &pv, uint32_t out[8]) {
 }
 }  // namespace
 
-struct ShardJob {
-    uint32_t index = 0;       // shard number (1-based) = position in the execution + 1
-    size_t n_recs = 0;
-    uint32_t next_pc = 0;
-    rv32::CycleRec *d_recs = nullptr;
-    uint32_t log_n[rv32::N_CHIPS] = {};
-    bool present[rv32::N_CHIPS] = {};
-    uint32_t *d_aux[rv32::N_CHIPS] = {};  // main traces except cpu
-    uint32_t device_rows = 1u << RV32_CHIP_CPU;   // bit c: the rows of chip c were (and on every K0 are) built on the GPU from events
-    std::vector<Fp> pubs;
-    MainCache cache;  // phase-1 LDEs + tree of the main traces, consumed by phase 2
-    // K0 output of this shard kept from phase 1 to phase 2 (with the cache, while HBM allows); otherwise the
-    // job's working buffers are used and phase 2 runs K0 again
-    uint32_t *d_cpu = nullptr, *d_byte = nullptr, *d_prog = nullptr;
-    bool traces_valid = false;
-    int lane = 0;             // the lane that first committed the shard: cache and kept K0 output are from its pool
-    uint32_t header[HEADER_WORDS] = {};
-    bool header_valid = false;   // phase 1 ran (inside the prepare pipeline, or by commit_shard) and no phase 2 has consumed it
-};
-// the shards of a job that one member of the handle holds (first, first + stride, ... of the execution), resident in that
-// member's HBM, ready for K0..K9
-struct JobPart {
-    size_t first = 0, stride = 1;
-    std::vector<ShardJob> shards;
-    struct Work {   // K0 working buffers of one lane (largest shard seen), from that lane's pool
-        uint32_t *d_cpu = nullptr, *d_byte = nullptr, *d_prog = nullptr;
-        uint32_t log_cpu = 0;
-    } work[MAX_LANES];
-    double t_exec_wait = 0;   // seconds the member's GPU thread spent waiting for the executor inside prepare
-    ShardJob *at(size_t pos) { return pos >= first && (pos - first) % stride == 0 && (pos - first) / stride < shards.size() ? &shards[(pos - first) / stride] : nullptr; }
-};
-// One prepared execution, cut into shards by the executor.  Of the shards this job holds (first, first + stride, ...) the
-// k-th lives on member k mod G of the handle that prepared it: parts[m] is member m's (first + m stride, then G stride apart).
-struct dvt_job {
-    int exit_code = -1;
-    uint64_t cycles = 0;
-    std::vector<uint8_t> public_values;
-    size_t n_total = 0, first = 0, stride = 1;   // shards of the execution / which of them this job holds
-    size_t byte_words = 0, prog_words = 0;
-    double t_exec_wait = 0;   // the longest executor wait of a member
-    std::vector<JobPart> parts;   // one per member
-    size_t held() const {
-        size_t n = 0;
-        for (auto &q : parts) n += q.shards.size();
-        return n;
-    }
-    // the shard at pos and the member that holds it; nullptr when this job does not hold it
-    ShardJob *at(size_t pos, size_t *m) {
-        if (pos < first || (pos - first) % stride) return nullptr;
-        *m = (pos - first) / stride % parts.size();
-        return parts[*m].at(pos);
-    }
-};
-
-// The one wrong-handle check of the entry points that take a key and/or a job (either may be null): both were made by a
-// handle with as many members as this one, so member m finds its DeviceKey and its JobPart.
-static int same_members(dvt_prover *p, const dvt_pk *pk, const dvt_job *j) {
+int dvt::same_members(dvt_prover *p, const dvt_pk *pk, const dvt_job *j) {
     const size_t G = n_members(p);
     if ((pk && pk->dev.size() != G) || (j && j->parts.size() != G)) return fail(p, DVT_ERR_INPUT, "proving key or job of a handle with other devices");
     return DVT_OK;
@@ -145,9 +82,7 @@ static void job_release(dvt_prover *p, dvt_job *j) {
     delete j;
 }
 
-// K0 of a shard (into the shard's own buffers when it has them, else the job's working buffers); fills the chip
-// trace list of that shard.  `reuse`: phase 2 takes the traces phase 1 left behind instead of generating them again.
-static int shard_traces(const Lane &c, const DeviceKey &key, dvt_job *j, ShardJob &s, std::vector<ChipTrace> *traces, bool reuse) {
+int dvt::shard_traces(const Lane &c, const DeviceKey &key, dvt_job *j, ShardJob &s, std::vector<ChipTrace> *traces, bool reuse) {
     hipStream_t st = c.eng.stream;
     JobPart::Work &w = j->parts[c.mem.index].work[c.k];
     const MachineDesc *m = machine_rv32();
@@ -970,12 +905,7 @@ static int job_prove(dvt_prover *p, const dvt_pk *pk, dvt_job *j, uint8_t **proo
     return DVT_OK;
 }
 
-// The receiving side of the COMMIT rows' sys-bus tuples, from the claimed public-value bytes: an SP1 guest commits
-// the eight words of SHA-256(public-value bytes) with COMMIT(k, word k); the cpu chip sends
-// (t0 bytes = 0x10 0 0 0, a0 bytes = k 0 0 0, a1 bytes = the bytes of digest word k, 0, 0), tuple k contributes
-// 1 / (alpha + bus + beta 0x10 + beta^5 k + beta^9 b0 + ... + beta^12 b3).  What the LogUp sums of all chips and shards
-// must add up to (the verifier), and the sys bus alone (the job check).
-static Fp4 commit_digest_term(const PermChallenges &gc, const std::vector<uint8_t> &public_values) {
+Fp4 dvt::commit_digest_term(const PermChallenges &gc, const std::vector<uint8_t> &public_values) {
     uint8_t dg[32];
     sha256(public_values.data(), public_values.size(), dg);
     Fp4 bp[13];
@@ -1061,199 +991,6 @@ static std::string verify_core(const VerifyingKey &key, const CoreProof &cp, con
     const Fp4 expect = commit_digest_term(gc, cp.public_values);
     if (total != expect) return "LogUp cumulative sums do not cancel across the shards (memory bus or public-values digest)";
     return "";
-}
-
-// ------------------------------------------------------------------ the job check (dvt_rv32_check_job)
-// The point of the closed-form identities and the LogUp challenges of a check: a transcript over a domain tag, the key, the
-// job's public-value bytes and its shard count.  Not the headers: the check needs no phase 1 (and is no soundness boundary).
-static CheckChallenges check_challenges(const VerifyingKey &vk, const dvt_job *j) {
-    Challenger g;
-    for (const char *t = "dvt-check-rows-1"; *t; t++) g.observe_u32((uint8_t)*t);
-    g.observe(vk.prep_root);
-    g.observe_u32((uint32_t)vk.extra.size());
-    for (auto x : vk.extra) g.observe_u32(x);
-    g.observe_u32((uint32_t)j->public_values.size());
-    for (auto b : j->public_values) g.observe_u32(b);
-    g.observe_u32((uint32_t)j->n_total);
-    CheckChallenges c;
-    c.xi = g.sample_ext();
-    c.perm_alpha = g.sample_ext();
-    c.beta = g.sample_ext();
-    return c;
-}
-
-// the tables of one shard on lane 0 of the member that holds it (its device is current): findings and the shard's per-bus sums
-static int shard_check(const Lane &c, const DeviceKey &key, dvt_job *j, ShardJob &s, size_t pos, const CheckChallenges &ch,
-                       std::vector<dvt_check_finding> *findings, Fp4 bus[DVT_CHECK_BUSES]) {
-    const MachineDesc *m = machine_rv32();
-    std::vector<ChipTrace> traces;
-    const bool kept = s.traces_valid;
-    const int rc = shard_traces(c, key, j, s, &traces, true);
-    s.traces_valid = kept;   // (K0 into a kept buffer whose content had been consumed: the job stays as it was found)
-    if (rc) return rc;
-    std::vector<CheckTable> tabs;
-    for (auto &t : traces) {
-        const ChipDesc &d = m->chips[t.chip_id];
-        const uint32_t *prep = nullptr;
-        for (auto &pr : key.key.prep)
-            if (pr.chip_id == t.chip_id && pr.log_n == t.log_n) prep = pr.d_trace;
-        if (d.prep_w && !prep) return fail(c.err, DVT_ERR_INPUT, "chip %s of shard %zu has no preprocessed trace of its height in the proving key", d.name, pos);
-        tabs.push_back({&d, t.d_main, prep, t.log_n});
-    }
-    std::vector<uint32_t> pub;
-    for (auto x : s.pubs) pub.push_back(x.v);
-    std::vector<CheckTableOut> res;
-    if (int rc2 = check_tables(c, m, tabs, pub, ch, true, true, &res)) return rc2;
-    for (size_t i = 0; i < tabs.size(); i++) {
-        if (res[i].r.violations) findings->push_back({(uint32_t)pos, (uint32_t)traces[i].chip_id, tabs[i].log_n, res[i].r});
-        for (uint32_t b = 0; b < DVT_CHECK_BUSES; b++) bus[b] += res[i].bus[b];
-    }
-    return DVT_OK;
-}
-
-static int job_check(dvt_prover *p, const dvt_pk *pk, dvt_job *j, dvt_check_finding *findings, size_t cap, dvt_check_summary *summary) {
-    const size_t G = n_members(p);
-    if (int rc = same_members(p, pk, j)) return rc;
-    const auto t0 = Clock::now();
-    const CheckChallenges ch = check_challenges(pk->dev[0].key.vk, j);
-    std::vector<dvt_check_finding> all;
-    Fp4 bus[DVT_CHECK_BUSES];
-    for (auto &b : bus) b = Fp4::zero();
-    int rc = DVT_OK;
-    for (size_t m = 0; m < G && !rc; m++) {
-        JobPart &part = j->parts[m];
-        rc = turn_to(p, m);
-        for (size_t k = 0; k < part.shards.size() && !rc; k++)
-            rc = shard_check(lane0(p, m), member_key(pk, m), j, part.shards[k], part.first + k * part.stride, ch, &all, bus);
-    }
-    if (turn_to(p, 0) && !rc) rc = DVT_ERR_DEVICE;
-    if (rc) return rc;
-    std::sort(all.begin(), all.end(), [](const dvt_check_finding &a, const dvt_check_finding &b) { return a.shard != b.shard ? a.shard < b.shard : a.chip < b.chip; });
-    *summary = dvt_check_summary{};
-    for (auto &f : all) summary->violations += f.r.violations;
-    summary->n_findings = (uint32_t)all.size();
-    for (size_t i = 0; i < all.size() && i < cap; i++) findings[i] = all[i];
-    if (j->held() == j->n_total) {
-        summary->bus_checked = 1;
-        const Fp4 sys = commit_digest_term(PermChallenges{ch.perm_alpha, ch.beta}, j->public_values);
-        for (uint32_t b = 0; b < DVT_CHECK_BUSES; b++)
-            if (bus[b] != (b == PV_BUS ? sys : Fp4::zero())) summary->unbalanced_buses |= 1u << b;
-    }
-    summary->ms = (float)ms_since(t0);
-    if (!all.empty())
-        return fail(p, DVT_ERR_REJECTED, "shard %u, chip %s: row %u violates constraint %d (%llu violations in %u chip tables)", all[0].shard,
-                    machine_rv32()->chips[all[0].chip].name, all[0].r.first_row, all[0].r.first_constraint, (unsigned long long)summary->violations,
-                    summary->n_findings);
-    if (summary->unbalanced_buses) return fail(p, DVT_ERR_REJECTED, "the LogUp sums of the job do not balance (bus mask 0x%x)", summary->unbalanced_buses);
-    return DVT_OK;
-}
-
-// ------------------------------------------------------------------ the job's bus ledger (dvt_rv32_job_bus_tuples)
-// one pass (LEDGER_TALLY = 0 or LEDGER_COLLECT = 1, ledger.cuh) over the tables of one shard on lane 0 of the member that holds
-// it (its device is current), into that member's ledger; the job stays as found, as in shard_check
-static int shard_ledger(const Lane &c, const DeviceKey &key, dvt_job *j, ShardJob &s, size_t pos, LedgerDev &l, uint32_t mode) {
-    const MachineDesc *m = machine_rv32();
-    std::vector<ChipTrace> traces;
-    const bool kept = s.traces_valid;
-    const int rc = shard_traces(c, key, j, s, &traces, true);
-    s.traces_valid = kept;
-    if (rc) return rc;
-    std::vector<uint32_t> pub;
-    for (auto x : s.pubs) pub.push_back(x.v);
-    const uint32_t *d_pub = c.eng.upload_vec(pub);
-    if (!d_pub) return engine_fail(c.err, c.eng);
-    for (auto &t : traces) {
-        const ChipDesc &d = m->chips[t.chip_id];
-        const uint32_t *prep = nullptr;
-        for (auto &pr : key.key.prep)
-            if (pr.chip_id == t.chip_id && pr.log_n == t.log_n) prep = pr.d_trace;
-        if (d.prep_w && !prep) return fail(c.err, DVT_ERR_INPUT, "chip %s of shard %zu has no preprocessed trace of its height in the proving key", d.name, pos);
-        if (int rc2 = ledger_rows(c, l, d, (uint32_t)t.chip_id, t.d_main, prep, t.log_n, d_pub, (uint32_t)pos, mode)) return rc2;
-    }
-    HIP_TRY(c.err, hipStreamSynchronize(c.eng.stream));   // (the next shard's K0 may write the working buffers these launches read)
-    return DVT_OK;
-}
-
-// one pass over every held shard, and the verifier's side of the eight COMMIT tuples (what commit_digest_term stands for:
-// receives of (0x10 0 0 0, k 0 0 0, the bytes of digest word k, 0, 0) on the sys bus) into member 0's ledger
-static int job_ledger_pass(dvt_prover *p, const dvt_pk *pk, dvt_job *j, std::vector<LedgerDev> &ledgers, uint32_t mode) {
-    for (size_t m = 0; m < ledgers.size(); m++) {
-        JobPart &part = j->parts[m];
-        if (int rc = turn_to(p, m)) return rc;
-        for (size_t k = 0; k < part.shards.size(); k++)
-            if (int rc = shard_ledger(lane0(p, m), member_key(pk, m), j, part.shards[k], part.first + k * part.stride, ledgers[m], mode)) return rc;
-    }
-    if (int rc = turn_to(p, 0)) return rc;
-    uint8_t dg[32];
-    sha256(j->public_values.data(), j->public_values.size(), dg);
-    for (uint32_t k = 0; k < 8; k++) {
-        const uint32_t v[14] = {rv32::SYS_COMMIT, 0, 0, 0, k, 0, 0, 0, dg[4 * k], dg[4 * k + 1], dg[4 * k + 2], dg[4 * k + 3], 0, 0};
-        if (int rc = ledger_tuple(lane0(p), ledgers[0], PV_BUS, v, 14, -1, 1, 0, mode)) return rc;
-    }
-    HIP_TRY(p, hipStreamSynchronize(eng0(p).stream));
-    return DVT_OK;
-}
-
-static int job_ledger_run(dvt_prover *p, const dvt_pk *pk, dvt_job *j, std::vector<LedgerDev> &ledgers, uint64_t seed, std::vector<dvt_bus_tuple> *all,
-                          bool *overflow) {
-    constexpr uint32_t LOG_BUCKETS = 20, CAP_SLOTS = 1u << 16;
-    const size_t G = ledgers.size();
-    for (size_t m = 0; m < G; m++) {
-        if (int rc = turn_to(p, m)) return rc;
-        if (int rc = ledger_init(lane0(p, m), &ledgers[m], LOG_BUCKETS, CAP_SLOTS, seed)) return rc;
-    }
-    if (int rc = job_ledger_pass(p, pk, j, ledgers, 0)) return rc;
-    uint32_t n_dirty = 0;
-    if (G == 1) {
-        if (int rc = ledger_close(lane0(p), ledgers[0], &n_dirty)) return rc;
-    } else {   // the members' tallies added mod p on the host; the one bitmap back to every member
-        std::vector<uint64_t> sum, one;
-        for (size_t m = 0; m < G; m++) {
-            if (int rc = turn_to(p, m)) return rc;
-            if (int rc = ledger_tallies(lane0(p, m), ledgers[m], m ? &one : &sum)) return rc;
-            for (size_t i = 0; m && i < sum.size(); i++) sum[i] = (sum[i] + one[i]) % P;
-        }
-        std::vector<uint32_t> bitmap;
-        n_dirty = ledger_dirty_of(sum, &bitmap);
-        for (size_t m = 0; n_dirty && m < G; m++) {
-            if (int rc = turn_to(p, m)) return rc;
-            if (int rc = ledger_set_dirty(lane0(p, m), ledgers[m], bitmap)) return rc;
-        }
-    }
-    all->clear();
-    *overflow = false;
-    if (!n_dirty) return DVT_OK;
-    if (int rc = job_ledger_pass(p, pk, j, ledgers, 1)) return rc;
-    for (size_t m = 0; m < G; m++) {
-        if (int rc = turn_to(p, m)) return rc;
-        if (int rc = ledger_records(lane0(p, m), ledgers[m], all, overflow)) return rc;
-    }
-    ledger_finish(all);
-    return DVT_OK;
-}
-
-static int job_bus_tuples(dvt_prover *p, const dvt_pk *pk, dvt_job *j, dvt_bus_tuple *out, size_t cap, size_t *n_tuples, uint32_t *truncated) {
-    if (int rc = same_members(p, pk, j)) return rc;
-    if (j->n_total > (1u << 16)) return fail(p, DVT_ERR_INPUT, "a job of %zu shards: the ledger tags at most 2^16", (size_t)j->n_total);
-    const CheckChallenges ch = check_challenges(pk->dev[0].key.vk, j);
-    uint64_t seed = (uint64_t)ch.xi.c[0].v | ((uint64_t)ch.xi.c[1].v << 32);
-    std::vector<dvt_bus_tuple> all;
-    bool overflow = false;
-    int rc = DVT_OK;
-    for (int attempt = 0; attempt < 2 && !rc; attempt++) {   // records overflowed: once more with another seed
-        std::vector<LedgerDev> ledgers(n_members(p));
-        rc = job_ledger_run(p, pk, j, ledgers, seed, &all, &overflow);
-        for (size_t m = ledgers.size(); m-- > 0;) {   // member 0 last: its device stays current
-            if (turn_to(p, m)) continue;
-            (void)hipStreamSynchronize(member(p, m).eng.stream);
-            ledger_release(&ledgers[m]);
-        }
-        if (!overflow) break;
-        seed = seed * 0x9e3779b97f4a7c15ull + 1;
-    }
-    if (rc) return rc;
-    ledger_copy_out(all, overflow, out, cap, n_tuples, truncated);
-    return DVT_OK;
 }
 
 static std::vector<uint32_t> trace_blob(const rv32::HostTraces &T, const rv32::HostPrep *prep) {
@@ -1362,7 +1099,7 @@ int dvt_rv32_prepare(dvt_prover *p, const dvt_pk *pk, const dvt_buf *stdin_bufs,
 int dvt_rv32_prepare_part(dvt_prover *p, const dvt_pk *pk, const dvt_buf *stdin_bufs, size_t nbuf, size_t first, size_t stride, dvt_job **job,
                           dvt_report *report) {
     if (!p || !pk || !job || (nbuf && !stdin_bufs)) return fail(p, DVT_ERR_INPUT, "null argument");
-    if (!pk->is_rv32) return fail(p, DVT_ERR_INPUT, "proving key was not made by dvt_setup");
+    if (int rc = rv32_key(p, pk)) return rc;
     Guard g(p); if (g.rc) return g.rc;
     return job_prepare(p, pk, stdin_bufs, nbuf, first, stride, job, report);
 }
@@ -1394,173 +1131,6 @@ uint32_t dvt_rv32_job_shard_chips(const dvt_job *job, size_t shard) {
     return mask;
 }
 double dvt_rv32_job_exec_wait_seconds(const dvt_job *job) { return job ? job->t_exec_wait : 0.0; }
-
-int dvt_rv32_job_bus_tuples(dvt_prover *p, const dvt_pk *pk, dvt_job *job, dvt_bus_tuple *out, size_t cap, size_t *n_tuples, uint32_t *truncated) {
-    if (!p) return DVT_ERR_INPUT;
-    if (!pk || !job || !n_tuples || !truncated || (cap && !out)) return fail(p, DVT_ERR_INPUT, "null argument");
-    if (!pk->is_rv32) return fail(p, DVT_ERR_INPUT, "not an rv32 proving key");
-    Guard g(p); if (g.rc) return g.rc;
-    return job_bus_tuples(p, pk, job, out, cap, n_tuples, truncated);
-}
-
-int dvt_rv32_check_job(dvt_prover *p, const dvt_pk *pk, dvt_job *job, dvt_check_finding *findings, size_t cap, dvt_check_summary *summary) {
-    if (!p || !pk || !job || !summary || (cap && !findings)) return fail(p, DVT_ERR_INPUT, "null argument");
-    if (!pk->is_rv32) return fail(p, DVT_ERR_INPUT, "proving key was not made by dvt_setup");
-    Guard g(p); if (g.rc) return g.rc;
-    return job_check(p, pk, job, findings, cap, summary);
-}
-
-int dvt_rv32_job_shard_chip_shape(const dvt_job *job, size_t shard, uint32_t chip, uint32_t *main_w, uint32_t *log_n) {
-    size_t m = 0;
-    const ShardJob *s = job ? const_cast<dvt_job *>(job)->at(shard, &m) : nullptr;
-    if (!s || chip >= (uint32_t)rv32::N_CHIPS || !s->present[chip] || !main_w || !log_n) return DVT_ERR_INPUT;
-    *main_w = (uint32_t)machine_rv32()->chips[chip].main_w;
-    *log_n = s->log_n[chip];
-    return DVT_OK;
-}
-
-// The forgery hunt (hunt.cuh) of one chip table of a shard, on lane 0 of the member that holds it; the job stays as found, as
-// in shard_check.
-int dvt_rv32_hunt_shard(dvt_prover *p, const dvt_pk *pk, dvt_job *job, size_t shard, uint32_t chip, uint64_t seed, const uint32_t *deltas,
-                        uint32_t n_deltas, uint32_t pairs, const uint32_t *cols, uint32_t n_cols, uint32_t adjacent, uint32_t row_first,
-                        uint32_t row_count, uint64_t max_evals, uint32_t *free_counts, uint8_t *free_map, dvt_escape *out, size_t cap,
-                        uint64_t *n_reported, uint64_t *n_tried) {
-    if (!p || !pk || !job) return fail(p, DVT_ERR_INPUT, "null argument");
-    if (!pk->is_rv32) return fail(p, DVT_ERR_INPUT, "proving key was not made by dvt_setup");
-    if (pairs > 1) return fail(p, DVT_ERR_INPUT, "pairs %u", pairs);
-    if (int rc = same_members(p, pk, job)) return rc;
-    const MachineDesc *m = machine_rv32();
-    if (chip >= (uint32_t)m->n_chips) return fail(p, DVT_ERR_INPUT, "chip %u out of range (%d chips)", chip, m->n_chips);
-    size_t mi = 0;
-    ShardJob *s = job->at(shard, &mi);
-    if (!s) return fail(p, DVT_ERR_INPUT, "shard %zu is not held by this job", shard);
-    if (!s->present[chip]) return fail(p, DVT_ERR_INPUT, "shard %zu has no table of chip %s", shard, m->chips[chip].name);
-    HuntRequest rq = hunt_request(seed, deltas, n_deltas, row_first, row_count, max_evals);
-    if (pairs) hunt_want_pairs(&rq, cols, n_cols, adjacent, out, cap, n_reported, n_tried);
-    else hunt_want_cells(&rq, free_counts, free_map);
-    HuntPlan plan;
-    if (int rc = hunt_plan(p->err, m->chips[chip], s->log_n[chip], rq, &plan)) return rc;
-    Guard g(p); if (g.rc) return g.rc;
-    if (int rc = turn_to(p, mi)) return rc;
-    const Lane c = lane0(p, mi);
-    const DeviceKey &key = member_key(pk, mi);
-    std::vector<ChipTrace> traces;
-    const bool kept = s->traces_valid;
-    const int rc = shard_traces(c, key, job, *s, &traces, true);
-    s->traces_valid = kept;
-    if (rc) return rc;
-    for (auto &t : traces) {
-        if (t.chip_id != (int)chip) continue;
-        const ChipDesc &d = m->chips[chip];
-        const uint32_t *prep = nullptr;
-        for (auto &pr : key.key.prep)
-            if (pr.chip_id == t.chip_id && pr.log_n == t.log_n) prep = pr.d_trace;
-        if (d.prep_w && !prep) return fail(p, DVT_ERR_INPUT, "chip %s of shard %zu has no preprocessed trace of its height in the proving key", d.name, shard);
-        std::vector<uint32_t> pub;
-        for (auto x : s->pubs) pub.push_back(x.v);
-        return hunt_table(c, m, {&d, t.d_main, prep, t.log_n}, pub, rq, plan);
-    }
-    return fail(p, DVT_ERR_INPUT, "shard %zu has no table of chip %s", shard, m->chips[chip].name);
-}
-
-// The join hunt (hunt_join.cuh) over windows of the job's tables, on lane 0 of the one member that holds their shards; the
-// job stays as found, as in shard_check.  Shard after shard: the next shard's K0 may write the working buffers the launches
-// of the last one read, and every join_add synchronises.
-int dvt_rv32_hunt_join_job(dvt_prover *p, const dvt_pk *pk, dvt_job *job, const dvt_join_window *windows, size_t n_windows,
-                           const uint32_t *supply_chips, uint32_t n_supply, uint64_t seed, const uint32_t *deltas, uint32_t n_deltas,
-                           const uint32_t *cols, const uint32_t *cols_count, uint64_t max_evals, size_t cap_records, size_t cap_absorbed,
-                           uint32_t log_slots, dvt_join_summary *summary, dvt_join_cell *cells, size_t cap_cells, size_t *n_cells,
-                           dvt_join_cell *absorbed, size_t cap_absorbed_out, size_t *n_absorbed) {
-    if (!p || !pk || !job) return fail(p, DVT_ERR_INPUT, "null argument");
-    if (!windows || !n_windows || (n_supply && !supply_chips) || !summary || !n_cells || !n_absorbed || (cap_cells && !cells) ||
-        (cap_absorbed_out && !absorbed) || (cols_count && !cols))
-        return fail(p, DVT_ERR_INPUT, "null argument");
-    if (!pk->is_rv32) return fail(p, DVT_ERR_INPUT, "proving key was not made by dvt_setup");
-    if (int rc = same_members(p, pk, job)) return rc;
-    if (int rc = join_check_new(p->err, n_deltas, deltas, cap_records, cap_absorbed, log_slots)) return rc;
-    const MachineDesc *m = machine_rv32();
-    size_t mi = 0;
-    std::vector<uint32_t> order;   // the shards in the order of their first window
-    for (size_t w = 0; w < n_windows; w++) {
-        size_t at = 0;
-        ShardJob *s = job->at(windows[w].shard, &at);
-        if (!s) return fail(p, DVT_ERR_INPUT, "shard %u is not held by this job", windows[w].shard);
-        if (windows[w].chip >= (uint32_t)m->n_chips) return fail(p, DVT_ERR_INPUT, "chip %u out of range (%d chips)", windows[w].chip, m->n_chips);
-        if (!s->present[windows[w].chip]) return fail(p, DVT_ERR_INPUT, "shard %u has no table of chip %s", windows[w].shard, m->chips[windows[w].chip].name);
-        if (w && at != mi)
-            return fail(p, DVT_ERR_UNSUPPORTED, "windows on shards of members %zu and %zu: a join runs on one device", mi, at);
-        mi = at;
-        if (std::find(order.begin(), order.end(), windows[w].shard) == order.end()) order.push_back(windows[w].shard);
-    }
-    for (uint32_t k = 0; k < n_supply; k++)
-        if (supply_chips[k] >= (uint32_t)m->n_chips) return fail(p, DVT_ERR_INPUT, "supply chip %u out of range", supply_chips[k]);
-    Guard g(p); if (g.rc) return g.rc;
-    if (int rc = turn_to(p, mi)) return rc;
-    const Lane c = lane0(p, mi);
-    const DeviceKey &key = member_key(pk, mi);
-    struct Held {   // the join's buffers go back however the call ends
-        JoinDev dev;
-        hipStream_t st;
-        ~Held() { (void)hipStreamSynchronize(st); join_release(&dev); }
-    } held{{}, c.eng.stream};
-    JoinDev &j = held.dev;
-    if (int rc = join_init(c, &j, m, seed, deltas, n_deltas, cap_records, cap_absorbed, log_slots)) return rc;
-    auto prep_of = [&](const ChipTrace &t) -> const uint32_t * {
-        for (auto &pr : key.key.prep)
-            if (pr.chip_id == t.chip_id && pr.log_n == t.log_n) return pr.d_trace;
-        return nullptr;
-    };
-    for (size_t o = 0; o < order.size(); o++) {
-        size_t at = 0;
-        ShardJob *s = job->at(order[o], &at);
-        std::vector<ChipTrace> traces;
-        const bool kept = s->traces_valid;
-        const int rc = shard_traces(c, key, job, *s, &traces, true);
-        s->traces_valid = kept;
-        if (rc) return rc;
-        std::vector<uint32_t> pub;
-        for (auto x : s->pubs) pub.push_back(x.v);
-        auto table_of = [&](uint32_t chip, CheckTable *out) -> int {
-            for (auto &t : traces) {
-                if (t.chip_id != (int)chip) continue;
-                const ChipDesc &d = m->chips[chip];
-                const uint32_t *prep = prep_of(t);
-                if (d.prep_w && !prep) return fail(p, DVT_ERR_INPUT, "chip %s of shard %u has no preprocessed trace of its height in the proving key", d.name, order[o]);
-                *out = {&d, t.d_main, prep, t.log_n};
-                return DVT_OK;
-            }
-            return fail(p, DVT_ERR_INPUT, "shard %u has no table of chip %s", order[o], m->chips[chip].name);
-        };
-        for (uint32_t k = 0; o == 0 && k < n_supply; k++) {
-            CheckTable t;
-            if (int rc2 = table_of(supply_chips[k], &t)) return rc2;
-            if (int rc2 = join_supply(p->err, j, t, pub)) return rc2;
-        }
-        size_t col_at = 0;
-        for (size_t w = 0; w < n_windows; w++) {
-            const uint32_t nc = cols_count ? cols_count[w] : 0;
-            const uint32_t *cl = nc ? cols + col_at : nullptr;
-            col_at += nc;
-            if (windows[w].shard != order[o]) continue;
-            CheckTable t;
-            if (int rc2 = table_of(windows[w].chip, &t)) return rc2;
-            const uint64_t n = (uint64_t)1 << t.log_n;
-            const uint32_t first = windows[w].row_first;
-            const uint32_t count = windows[w].row_count ? windows[w].row_count : (uint32_t)(first < n ? n - first : 0);
-            std::vector<uint32_t> use;
-            if (int rc2 = join_check_add(p->err, j, order[o], windows[w].chip, *t.d, t.log_n, first, count, cl, nc, max_evals, &use)) return rc2;
-            if (int rc2 = join_add(c, j, order[o], windows[w].chip, t, pub, first, count, use)) return rc2;
-        }
-        HIP_TRY(p, hipStreamSynchronize(c.eng.stream));
-    }
-    if (int rc = join_match(c, j)) return rc;
-    std::copy_n(j.cells.begin(), std::min(cap_cells, j.cells.size()), cells);
-    std::copy_n(j.absorbed.begin(), std::min(cap_absorbed_out, j.absorbed.size()), absorbed);
-    *n_cells = j.cells.size();
-    *n_absorbed = j.absorbed.size();
-    *summary = j.summary;
-    return DVT_OK;
-}
 
 int dvt_rv32_commit_shard(dvt_prover *p, const dvt_pk *pk, dvt_job *job, size_t shard, uint32_t *header) {
     if (!p || !pk || !job || !header) return fail(p, DVT_ERR_INPUT, "bad argument");
@@ -1644,7 +1214,7 @@ int dvt_rv32_assemble(const dvt_job *job, const uint8_t *const *shard_proofs, co
 int dvt_prove_core(dvt_prover *p, const dvt_pk *pk, const dvt_buf *stdin_bufs, size_t nbuf, uint8_t **proof, size_t *proof_len,
                    dvt_report *report) {
     if (!p || !pk || !proof || !proof_len || (nbuf && !stdin_bufs)) return fail(p, DVT_ERR_INPUT, "null argument");
-    if (!pk->is_rv32) return fail(p, DVT_ERR_INPUT, "proving key was not made by dvt_setup");
+    if (int rc = rv32_key(p, pk)) return rc;
     Guard g(p); if (g.rc) return g.rc;
     dvt_job *j = nullptr;
     int rc = job_prepare(p, pk, stdin_bufs, nbuf, 0, 1, &j, report);
@@ -1738,6 +1308,7 @@ int dvt_rv32_debug_device_traces(dvt_prover *p, const dvt_pk *pk, dvt_job *j, si
     std::vector<ChipTrace> traces;
     ShardJob &sj = *held;
     int rc = turn_to(p, mi);
+    // (K0 again, and the shard's flag with it: not through shard_view of capi_inspect.hip, which leaves the job as found)
     if (!rc) rc = shard_traces(lane0(p, mi), member_key(pk, mi), j, sj, &traces, false);
     if (rc) return rc;
     HIP_TRY(p, hipStreamSynchronize(member(p, mi).eng.stream));

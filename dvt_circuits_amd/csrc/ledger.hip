@@ -105,18 +105,20 @@ void ledger_release(LedgerDev *l) {
     *l = LedgerDev{};
 }
 
-int ledger_rows(const Lane &c, LedgerDev &l, const ChipDesc &d, uint32_t chip, const uint32_t *main, const uint32_t *prep, uint32_t log_n,
-                const uint32_t *d_pub, uint32_t tag, uint32_t mode) {
+int ledger_rows(const Lane &c, LedgerDev &l, const CheckTable &t, uint32_t chip, const std::vector<uint32_t> &pub_mont, uint32_t tag, uint32_t mode) {
+    const ChipDesc &d = *t.d;
     if (!d.launch_ledger) return fail(c.err, DVT_ERR_UNSUPPORTED, "chip %s has no ledger pass", d.name);
-    if (log_n > 22 || tag >= (1u << 16) || chip >= LEDGER_HOST_CHIP) return fail(c.err, DVT_ERR_INPUT, "log_n %u, tag %u or chip %u out of range", log_n, tag, chip);
+    if (t.log_n > 22 || tag >= (1u << 16) || chip >= LEDGER_HOST_CHIP) return fail(c.err, DVT_ERR_INPUT, "log_n %u, tag %u or chip %u out of range", t.log_n, tag, chip);
     if (!d.n_interactions) return DVT_OK;
+    const uint32_t *d_pub = c.eng.upload_vec(pub_mont);
+    if (!d_pub) return engine_fail(c.err, c.eng);
     if (mode == LEDGER_COLLECT)
         if (int rc = want_slots(c, l)) return rc;
     LedgerArgs a = args_of(l, mode);
-    a.main = main;
-    a.prep = prep;
+    a.main = t.main;
+    a.prep = t.prep;
     a.pub = d_pub;
-    a.log_n = log_n;
+    a.log_n = t.log_n;
     a.tag = tag;
     a.chip = chip;
     HIP_TRY(c.err, d.launch_ledger(c.eng.stream, a));
