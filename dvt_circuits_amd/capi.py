@@ -2,6 +2,7 @@
 `dvt_circuits_amd/libdvt_prover.so`; raises if it is missing — there is no
 fallback path."""
 import ctypes as C
+import json
 import os
 import subprocess
 
@@ -129,6 +130,11 @@ def load():
     lib.dvt_prover_verify_times.argtypes = [vp, C.POINTER(C.c_double)]
     lib.dvt_stage_sponge_rows.argtypes = [vp, u32p, u32p, sz, u32p]
     lib.dvt_stage_verify_paths.argtypes = [vp, C.POINTER(PathChain), sz, u8p]
+    lib.dvt_stage_multipath_nodes.argtypes = [u32, u32p, sz, u32p, sz, C.POINTER(sz)]
+    lib.dvt_stage_verify_multipath.argtypes = [vp, u32, u32p, u32p, sz, u8p, u32p, u32p, sz, u32p, u8p]
+    for fn in (lib.dvt_proof_compact, lib.dvt_proof_expand):
+        fn.argtypes = [C.c_char_p, sz, C.c_char_p, sz, u32, u32, C.POINTER(u8p), C.POINTER(sz), C.POINTER(C.c_char_p)]
+    lib.dvt_debug_compact_list_sweep.argtypes = [C.c_char_p, sz, C.c_char_p, sz, u32, u32, C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_char_p)]
     lib.dvt_last_stage_ms.argtypes = [vp, C.POINTER(C.c_float)]
     lib.dvt_setup.argtypes = [vp, C.c_char_p, sz, C.POINTER(vp), C.POINTER(u8p), C.POINTER(sz)]
     lib.dvt_execute.argtypes = [C.c_char_p, sz, C.POINTER(Buf), sz, C.c_uint64, C.POINTER(u8p), C.POINTER(sz), C.POINTER(Report), C.POINTER(C.c_char_p)]
@@ -381,6 +387,54 @@ def verify(vk: bytes, proof: bytes, fri_queries=100, pow_bits=16):
     return rc == DVT_OK, ec.value, out, _take_str(lib, why)
 
 
+def _transcode(fn, vk, proof, fri_queries, pow_bits):
+    lib = load()
+    out, n, why = u8p(), C.c_size_t(), C.c_char_p()
+    rc = fn(vk, len(vk), proof, len(proof), fri_queries, pow_bits, C.byref(out), C.byref(n), C.byref(why))
+    reason = _take_str(lib, why)
+    if rc:
+        raise DvtError(rc, reason)
+    b = C.string_at(out, n.value)
+    lib.dvt_free(C.cast(out, C.c_void_p))
+    return b
+
+
+def proof_compact(vk: bytes, proof: bytes, fri_queries=100, pow_bits=16) -> bytes:
+    """Host-only: the proof (a container, or one machine-level shard proof) with every shard in the compact form ("DVP2":
+    shared Merkle paths sent once).  Raises DvtError(DVT_ERR_REJECTED, the verifier's text) when a shard's host part fails."""
+    return _transcode(load().dvt_proof_compact, vk, proof, fri_queries, pow_bits)
+
+
+def proof_expand(vk: bytes, proof: bytes, fri_queries=100, pow_bits=16) -> bytes:
+    """Host-only: the inverse of proof_compact (every shard as "DVP1", the dropped siblings recomputed)."""
+    return _transcode(load().dvt_proof_expand, vk, proof, fri_queries, pow_bits)
+
+
+def compact_list_sweep(vk: bytes, proof: bytes, fri_queries=100, pow_bits=16):
+    """Host-only test hook: every word of every node list of the compact shards of a container that verifies, changed by
+    +1 mod p in turn.  Returns (words changed, changes that were still accepted)."""
+    lib = load()
+    n, acc, why = C.c_uint64(), C.c_uint64(), C.c_char_p()
+    rc = lib.dvt_debug_compact_list_sweep(vk, len(vk), proof, len(proof), fri_queries, pow_bits, C.byref(n), C.byref(acc), C.byref(why))
+    reason = _take_str(lib, why)
+    if rc:
+        raise DvtError(rc, reason)
+    return n.value, acc.value
+
+
+def multipath_nodes(depth: int, indices):
+    """Host-only: the (level, index) pairs a compact proof lists for a tree of 2^depth leaves queried at `indices`, in order."""
+    lib = load()
+    idx = np.ascontiguousarray(indices, dtype=np.uint32)
+    n = C.c_size_t()
+    rc = lib.dvt_stage_multipath_nodes(depth, idx.ctypes.data_as(u32p), idx.size, None, 0, C.byref(n))
+    if rc:
+        raise DvtError(rc, "dvt_stage_multipath_nodes")
+    out = np.zeros((max(n.value, 1), 2), np.uint32)
+    lib.dvt_stage_multipath_nodes(depth, idx.ctypes.data_as(u32p), idx.size, out.ctypes.data_as(u32p), n.value, C.byref(n))
+    return [(int(a), int(b)) for a, b in out[:n.value]]
+
+
 def split_container(proof: bytes):
     """The parts of a core proof ("DVC3" container, csrc/proof.h) -> (exit_code, public value bytes, [shard proof bytes])."""
     w = np.frombuffer(proof, np.uint32)
@@ -470,7 +524,10 @@ def machine_verify(vk: bytes, proof: bytes, fri_queries=100, pow_bits=16):
 class Prover:
     """Owns one dvt_prover handle: one GPU, or with "devices": [d0, d1, ...] in the cfg one device member per entry."""
 
-    def __init__(self, cfg: str = None):
+    def __init__(self, cfg=None):
+        """cfg: the handle's config as a JSON string, or as a dict of its keys."""
+        if isinstance(cfg, dict):
+            cfg = json.dumps(cfg)
         self.lib = load()
         h = C.c_void_p()
         rc = self.lib.dvt_prover_create(cfg.encode() if cfg else None, C.byref(h))
@@ -806,6 +863,29 @@ class Prover:
         ok = np.zeros(len(chains), np.uint8)
         self.check(self.lib.dvt_stage_verify_paths(self.h, arr, len(chains), ok.ctypes.data_as(u8p)))
         return ok
+
+    def verify_multipath(self, depth, leaf_index, leaf_digest, nodes, root, inject=None, inject_at=None):
+        """The tree kernel of the device verifier on one tree: n queries at leaf_index [n] with leaf_digest [n][8], the listed
+        nodes [k][8] in multipath_nodes' order, optionally inject [depth][n][8] with inject_at [depth] (canonical words).
+        Returns ok (bool)."""
+        keep = []
+
+        def ptr(a, dt, ct):
+            a = np.ascontiguousarray(np.asarray(a, dt).reshape(-1))
+            if a.size == 0:
+                a = np.zeros(1, dt)
+            keep.append(a)
+            return a.ctypes.data_as(C.POINTER(ct))
+
+        n = len(leaf_index)
+        nodes = np.asarray(nodes, np.uint32).reshape(-1, 8)
+        ok = np.zeros(1, np.uint8)
+        self.check(self.lib.dvt_stage_verify_multipath(
+            self.h, depth, ptr(leaf_index, np.uint32, C.c_uint32), ptr(leaf_digest, np.uint32, C.c_uint32), n,
+            ptr(inject_at, np.uint8, C.c_uint8) if inject_at is not None else None,
+            ptr(inject, np.uint32, C.c_uint32) if inject is not None else None,
+            ptr(nodes, np.uint32, C.c_uint32), nodes.shape[0], ptr(root, np.uint32, C.c_uint32), ok.ctypes.data_as(u8p)))
+        return bool(ok[0])
 
     def machine_setup(self, machine: str, prep):
         arr, keep = _traces(prep)

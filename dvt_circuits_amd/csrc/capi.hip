@@ -269,7 +269,7 @@ int stage_table(dvt_prover *p, const char *machine, uint32_t chip, const uint32_
 
 extern "C" {
 
-uint32_t dvt_abi_version(void) { return 10; }
+uint32_t dvt_abi_version(void) { return 11; }
 
 int dvt_prover_create(const char *cfg_json, dvt_prover **out) {
     if (!out) return fail(nullptr, DVT_ERR_INPUT, "out == NULL");
@@ -290,6 +290,7 @@ int dvt_prover_create(const char *cfg_json, dvt_prover **out) {
     std::unique_ptr<dvt_prover> p(new dvt_prover());   // (freed on the early returns)
     p->cfg.num_queries = (uint32_t)cfg_int(cfg_json, "fri_queries", 100);
     p->cfg.pow_bits = (uint32_t)cfg_int(cfg_json, "pow_bits", 16);
+    p->cfg.compact_openings = cfg_int(cfg_json, "compact_openings", 0) != 0;
     const bool profile = cfg_int(cfg_json, "profile", 0) != 0;
     p->log_shard = (uint32_t)cfg_int(cfg_json, "log_shard_size", 21);
     p->keep_phase1 = cfg_int(cfg_json, "keep_phase1", 1) != 0;
@@ -782,6 +783,27 @@ int dvt_stage_verify_paths(dvt_prover *p, const dvt_path_chain *chains, size_t n
         if (!chains[i].start || !chains[i].root) return fail(p, DVT_ERR_INPUT, "chain %zu: null digest", i);
     Guard g(p); if (g.rc) return g.rc;
     return vq::stage_verify_paths(lane0(p), chains, n, ok);
+}
+
+int dvt_stage_multipath_nodes(uint32_t depth, const uint32_t *indices, size_t n, uint32_t *out_level_index, size_t cap, size_t *n_out) {
+    if (depth > 30 || (n && !indices) || (cap && !out_level_index) || !n_out) return DVT_ERR_INPUT;
+    const MultipathPlan pl = multipath_plan(depth, indices, n);
+    *n_out = pl.nodes.size();
+    for (size_t i = 0; i < pl.nodes.size() && i < cap; i++) {
+        out_level_index[2 * i] = pl.nodes[i].first;
+        out_level_index[2 * i + 1] = pl.nodes[i].second;
+    }
+    return DVT_OK;
+}
+
+int dvt_stage_verify_multipath(dvt_prover *p, uint32_t depth, const uint32_t *leaf_index, const uint32_t *leaf_digest, size_t n,
+                               const uint8_t *inject_at, const uint32_t *inject, const uint32_t *nodes, size_t n_nodes,
+                               const uint32_t *root, uint8_t *ok) {
+    if (!p) return DVT_ERR_INPUT;
+    if (!n || n > vq::MP_MAX_SLOTS || depth > 30) return fail(p, DVT_ERR_INPUT, "1..%u queries and a depth of at most 30", vq::MP_MAX_SLOTS);
+    if (!leaf_index || !leaf_digest || !root || !ok || (n_nodes && !nodes) || (inject_at && depth && !inject)) return fail(p, DVT_ERR_INPUT, "null argument");
+    Guard g(p); if (g.rc) return g.rc;
+    return vq::stage_verify_multipath(lane0(p), depth, leaf_index, leaf_digest, n, inject_at, inject, nodes, n_nodes, root, ok);
 }
 
 int dvt_last_kernel_stats(dvt_prover *p, double out[9]) {

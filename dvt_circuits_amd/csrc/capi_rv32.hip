@@ -920,6 +920,8 @@ Fp4 dvt::commit_digest_term(const PermChallenges &gc, const std::vector<uint8_t>
     return expect;
 }
 
+static std::string core_shards(const VerifyingKey &key, const CoreProof &cp, std::vector<ShardProof> &sps, PermChallenges *gc_out);
+
 // The rv32 checks of a parsed container: shard chaining through the public values, the chip set of every shard, each
 // shard's proof under the common challenges, and the COMMIT-digest balance.  "" or why the proof is rejected.
 // With dev != nullptr the query part of the shards runs on the device: the host part of every shard in order up to the first
@@ -927,7 +929,48 @@ Fp4 dvt::commit_digest_term(const PermChallenges &gc, const std::vector<uint8_t>
 static std::string verify_core(const VerifyingKey &key, const CoreProof &cp, const StarkConfig &cfg, DeviceQueries *dev = nullptr) {
     const auto t0 = Clock::now();
     const size_t nshards = cp.shards.size();
-    std::vector<ShardProof> sps(nshards);
+    std::vector<ShardProof> sps;
+    PermChallenges gc;
+    {
+        const std::string why = core_shards(key, cp, sps, &gc);
+        if (!why.empty()) return why;
+    }
+    Fp4 total = Fp4::zero();
+    if (dev) {
+        std::string host_why;
+        size_t added = 0;
+        for (; added < nshards && !dev->rc; added++) {
+            Fp4 t;
+            ShardQueryCtx ctx;
+            host_why = verify_shard_host(key, sps[added], cfg, &gc, &t, &ctx);
+            if (!host_why.empty()) break;
+            total += t;
+            dev->add(ctx, cp.shards[added].data(), cp.shards[added].size());
+        }
+        dev->finish(std::chrono::duration<double, std::milli>(Clock::now() - t0).count());
+        if (dev->rc) return "";
+        for (size_t i = 0; i < added; i++) {
+            const std::string why = dev->why(i);
+            if (!why.empty()) return "shard " + std::to_string(i + 1) + ": " + why;
+        }
+        if (!host_why.empty()) return "shard " + std::to_string(added + 1) + ": " + host_why;
+    }
+    for (size_t i = 0; !dev && i < nshards; i++) {
+        Fp4 t;
+        std::string why = verify_shard(key, sps[i], cfg, &gc, &t);
+        if (!why.empty()) return "shard " + std::to_string(i + 1) + ": " + why;
+        total += t;
+    }
+    const Fp4 expect = commit_digest_term(gc, cp.public_values);
+    if (total != expect) return "LogUp cumulative sums do not cancel across the shards (memory bus or public-values digest)";
+    return "";
+}
+
+// the first part of verify_core, which the transcoders share: the shard proofs parsed (either form), their chaining through
+// the public values and their chip sets, and the LogUp challenges common to all shards
+static std::string core_shards(const VerifyingKey &key, const CoreProof &cp, std::vector<ShardProof> &sps, PermChallenges *gc_out) {
+    const size_t nshards = cp.shards.size();
+    sps.resize(nshards);
     for (size_t i = 0; i < nshards; i++) {
         WordReader sr(cp.shards[i].data(), cp.shards[i].size());
         sps[i] = read_shard_proof(sr);
@@ -961,36 +1004,54 @@ static std::string verify_core(const VerifyingKey &key, const CoreProof &cp, con
         for (int k = 0; k < 8; k++) headers[i * HEADER_WORDS + k] = sp.main_root.d[k].canonical();
         for (uint32_t k = 0; k < N_PUB; k++) headers[i * HEADER_WORDS + 8 + k] = pubv[k];
     }
-    PermChallenges gc = global_challenges(key, headers.data(), nshards);
-    Fp4 total = Fp4::zero();
-    if (dev) {
-        std::string host_why;
-        size_t added = 0;
-        for (; added < nshards && !dev->rc; added++) {
+    *gc_out = global_challenges(key, headers.data(), nshards);
+    return "";
+}
+
+// dvt_proof_compact / dvt_proof_expand: every shard of a container (or the one machine-level shard proof) in the wanted form
+static int transcode(const uint8_t *vk, size_t vk_len, const uint8_t *proof, size_t proof_len, uint32_t fri_queries, uint32_t pow_bits,
+                     bool to_compact, uint8_t **out, size_t *out_len, char **reason) {
+    if (reason) *reason = nullptr;
+    if (out) *out = nullptr;
+    if (!vk || !proof || !out || !out_len) return reject(reason, DVT_ERR_INPUT, "null argument");
+    VerifyingKey key;
+    if (!vk_parse(vk, vk_len, &key)) return reject(reason, DVT_ERR_INPUT, "malformed verifying key");
+    return verify_words(proof, proof_len, DVT_ERR_REJECTED, reason, [&](WordReader &r, std::string &why) {
+        if (fri_queries == 0 || fri_queries > 1024 || pow_bits > 30) {
+            why = "fri_queries must be 1..1024 and pow_bits <= 30";
+            return DVT_ERR_INPUT;
+        }
+        const StarkConfig cfg{fri_queries, pow_bits};
+        auto one = [&](const ShardProof &sp, const PermChallenges *gc, std::vector<uint32_t> *words) {
             Fp4 t;
             ShardQueryCtx ctx;
-            host_why = verify_shard_host(key, sps[added], cfg, &gc, &t, &ctx);
-            if (!host_why.empty()) break;
-            total += t;
-            dev->add(ctx, cp.shards[added].data(), cp.shards[added].size());
+            std::string w = verify_shard_host(key, sp, cfg, gc, gc ? &t : nullptr, &ctx);
+            ShardProof other;
+            if (w.empty()) w = to_compact ? compact_shard(ctx, &other) : expand_shard(ctx, &other);
+            if (w.empty()) { WordWriter ww; write_shard_proof(ww, other); words->swap(ww.w); }
+            return w;
+        };
+        std::vector<uint32_t> result;
+        if (r.p < r.end && *r.p == CORE_PROOF_MAGIC) {
+            if (key.machine != machine_rv32() || key.extra.size() != 1) { why = "malformed verifying key"; return DVT_ERR_INPUT; }
+            CoreProof cp = read_core_proof(r);
+            std::vector<ShardProof> sps;
+            PermChallenges gc;
+            why = core_shards(key, cp, sps, &gc);
+            for (size_t i = 0; why.empty() && i < sps.size(); i++) {
+                why = one(sps[i], &gc, &cp.shards[i]);
+                if (!why.empty()) why = "shard " + std::to_string(i + 1) + ": " + why;
+            }
+            if (why.empty()) result = write_core_proof(cp);
+        } else {
+            const ShardProof sp = read_shard_proof(r);
+            if (r.p != r.end) why = "trailing bytes after proof";
+            else why = one(sp, nullptr, &result);
         }
-        dev->finish(std::chrono::duration<double, std::milli>(Clock::now() - t0).count());
-        if (dev->rc) return "";
-        for (size_t i = 0; i < added; i++) {
-            const std::string why = dev->why(i);
-            if (!why.empty()) return "shard " + std::to_string(i + 1) + ": " + why;
-        }
-        if (!host_why.empty()) return "shard " + std::to_string(added + 1) + ": " + host_why;
-    }
-    for (size_t i = 0; !dev && i < nshards; i++) {
-        Fp4 t;
-        std::string why = verify_shard(key, sps[i], cfg, &gc, &t);
-        if (!why.empty()) return "shard " + std::to_string(i + 1) + ": " + why;
-        total += t;
-    }
-    const Fp4 expect = commit_digest_term(gc, cp.public_values);
-    if (total != expect) return "LogUp cumulative sums do not cancel across the shards (memory bus or public-values digest)";
-    return "";
+        if (!why.empty()) return DVT_ERR_REJECTED;
+        if (!(*out = copy_out(result, out_len))) { why = "out of host memory"; return DVT_ERR_DEVICE; }
+        return DVT_OK;
+    });
 }
 
 static std::vector<uint32_t> trace_blob(const rv32::HostTraces &T, const rv32::HostPrep *prep) {
@@ -1245,6 +1306,43 @@ int dvt_verify(const uint8_t *vk, size_t vk_len, const uint8_t *proof, size_t pr
         if (public_values) *public_values = dup_bytes(cp.public_values, pv_len);
         return DVT_OK;
     });
+}
+
+int dvt_debug_compact_list_sweep(const uint8_t *vk, size_t vk_len, const uint8_t *proof, size_t proof_len, uint32_t fri_queries,
+                                 uint32_t pow_bits, uint64_t *n_words, uint64_t *n_accepted, char **reason) {
+    if (reason) *reason = nullptr;
+    if (!vk || !proof || !n_words || !n_accepted) return reject(reason, DVT_ERR_INPUT, "null argument");
+    *n_words = *n_accepted = 0;
+    VerifyingKey key;
+    if (!vk_parse(vk, vk_len, &key) || key.machine != machine_rv32() || key.extra.size() != 1) return reject(reason, DVT_ERR_INPUT, "malformed verifying key");
+    return verify_words(proof, proof_len, DVT_ERR_REJECTED, reason, [&](WordReader &r, std::string &why) {
+        if (fri_queries == 0 || fri_queries > 1024 || pow_bits > 30) {
+            why = "fri_queries must be 1..1024 and pow_bits <= 30";
+            return DVT_ERR_INPUT;
+        }
+        const CoreProof cp = read_core_proof(r);
+        std::vector<ShardProof> sps;
+        PermChallenges gc;
+        why = core_shards(key, cp, sps, &gc);
+        for (size_t i = 0; why.empty() && i < sps.size(); i++) {
+            Fp4 t;
+            ShardQueryCtx ctx;
+            why = verify_shard_host(key, sps[i], StarkConfig{fri_queries, pow_bits}, &gc, &t, &ctx);
+            if (why.empty() && sps[i].compact) why = verify_compact_queries(ctx);   // (the sweep starts from a shard that verifies)
+            if (why.empty() && sps[i].compact) compact_list_sweep(ctx, n_words, n_accepted);
+            if (!why.empty()) why = "shard " + std::to_string(i + 1) + ": " + why;
+        }
+        return why.empty() ? DVT_OK : DVT_ERR_REJECTED;
+    });
+}
+
+int dvt_proof_compact(const uint8_t *vk, size_t vk_len, const uint8_t *proof, size_t proof_len, uint32_t fri_queries, uint32_t pow_bits,
+                      uint8_t **out, size_t *out_len, char **reason) {
+    return transcode(vk, vk_len, proof, proof_len, fri_queries, pow_bits, true, out, out_len, reason);
+}
+int dvt_proof_expand(const uint8_t *vk, size_t vk_len, const uint8_t *proof, size_t proof_len, uint32_t fri_queries, uint32_t pow_bits,
+                     uint8_t **out, size_t *out_len, char **reason) {
+    return transcode(vk, vk_len, proof, proof_len, fri_queries, pow_bits, false, out, out_len, reason);
 }
 
 int dvt_prover_verify(dvt_prover *p, const uint8_t *vk, size_t vk_len, const uint8_t *proof, size_t proof_len, uint32_t fri_queries,

@@ -6,6 +6,7 @@
 // protocol itself is an original restatement of the public multi-table STARK
 // structure, see DESIGN.md "Protocol".
 #pragma once
+#include <array>
 #include <map>
 #include <mutex>
 #include <string>
@@ -21,6 +22,7 @@ namespace dvt {
 struct StarkConfig {
     uint32_t num_queries = 100;
     uint32_t pow_bits = 16;
+    bool compact_openings = false;   // the prover writes the compact form of a shard proof (DVP2, proof.h); verifiers read both
 };
 
 struct ChipRef {
@@ -61,6 +63,18 @@ struct TreeShape {
     std::vector<std::pair<uint32_t, uint32_t>> mats;  // (width, log_h) in tree order
     uint32_t log_h = 0;
 };
+// Who provides what when the queries of a shard walk its trees together (proof.h, MultipathPlan: one plan of hmax levels
+// serves every tree, a tree of d levels from level d on).  first[lh][slot]: the first query whose path passes the slot-th
+// node (ascending index, plan.keys[lh]) of level lh; dups[lh]: (that query, a later query on the same node): where a tree
+// has a digest per query at that level (leaves, rows of shorter matrices), both must carry the same.  listed_at[s]: the
+// listed nodes of level s as (index, position in plan.nodes), ascending.
+struct TreeSources {
+    MultipathPlan plan;
+    std::vector<std::vector<uint32_t>> first;
+    std::vector<std::vector<std::array<uint32_t, 2>>> dups;
+    std::vector<std::vector<std::pair<uint32_t, uint32_t>>> listed_at;
+};
+TreeSources tree_sources(uint32_t depth, const std::vector<uint32_t> &idx);
 struct ShardQueryCtx {
     const VerifyingKey *vk = nullptr;
     const ShardProof *pf = nullptr;
@@ -72,6 +86,7 @@ struct ShardQueryCtx {
     std::vector<std::vector<ColRef>> cols_by_h;      // [h] for h = 1 .. hmax
     std::vector<uint32_t> n_two_by_h;
     std::vector<uint32_t> idx;                       // the query indices (hmax bits each)
+    TreeSources paths;                               // of a compact proof: tree_sources(hmax, idx)
 };
 std::string verify_shard_host(const VerifyingKey &vk, const ShardProof &proof, const StarkConfig &cfg, const PermChallenges *global,
                               Fp4 *cumsum_total, ShardQueryCtx *ctx);
@@ -79,6 +94,22 @@ std::string verify_shard_host(const VerifyingKey &vk, const ShardProof &proof, c
 std::string verify_query_host(const ShardQueryCtx &ctx, uint32_t qi);
 // whether query qi's section passes every shape check (row counts and widths, path lengths, layer count, empty trees)
 bool query_shape_ok(const ShardQueryCtx &ctx, uint32_t qi);
+
+// ---- the compact form of a shard proof (DVP2, proof.h): its query part after verify_shard_host has left ctx.
+// The checks run tree by tree, not query by query, because a tree's queries are verified together: the four input trees
+// (equal digests where queries share a leaf or a row of a shorter matrix, then the walk with the listed nodes), the FRI
+// layers in order, then each query's final value.
+std::string verify_compact_queries(const ShardQueryCtx &ctx);
+// every shape check of a compact shard's query section and node lists (what verify_compact_queries refuses before it hashes)
+bool compact_shape_ok(const ShardQueryCtx &ctx, std::string *why = nullptr);
+// The query part of a compact shard for tests: every word of every node list changed by +1 in turn (the host part, which
+// reads no node list, stands), each time walking the list's tree; counts the words and the changes that were accepted.
+void compact_list_sweep(const ShardQueryCtx &ctx, uint64_t *n_words, uint64_t *n_accepted);
+// The two transcodings, after the host part: *out is ctx.pf's proof in the other form ("" or why not).  compact_shard drops
+// what the rule of multipath_plan drops and hashes nothing; expand_shard recomputes the dropped siblings from the leaves
+// upward.  A proof that is already in the wanted form is copied.
+std::string compact_shard(const ShardQueryCtx &ctx, ShardProof *out);
+std::string expand_shard(const ShardQueryCtx &ctx, ShardProof *out);
 
 #if defined(__HIPCC__)
 struct Arena {

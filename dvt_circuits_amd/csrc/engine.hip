@@ -990,18 +990,36 @@ bool Engine::prove_shard(const ProvingKey &pk, const std::vector<ChipTrace> &tra
     std::vector<Slot> layer_slot(layers.size());
     size_t q_words = 0;
     uint32_t tree_ncols[4] = {0, 0, 0, 0};
+    const bool compact = cfg.compact_openings;
+    std::vector<uint32_t> tree_nodes[4];
+    std::vector<std::vector<uint32_t>> layer_nodes(layers.size());
+    // one plan of hmax levels serves every tree (proof.h): the listed nodes of a tree of h levels, as positions in its digest array
+    const MultipathPlan plan = compact ? multipath_plan(hmax, idx.data(), nq) : MultipathPlan{};
+    auto listed_positions = [&](uint32_t h, std::vector<uint32_t> *at) {
+        for (size_t n = plan.base[h]; n < plan.nodes.size(); n++)
+            at->push_back((uint32_t)(((size_t)2 << h) - ((size_t)2 << plan.nodes[n].first)) + plan.nodes[n].second);
+    };
     for (int t = 0; t < 4; t++) {
         for (auto &tmx : tree_mats[t]) tree_ncols[t] += tmx.width;
         if (tree_mats[t].empty()) continue;
         tree_slot[t].ncols = tree_ncols[t];
         tree_slot[t].rows_at = q_words; q_words += (size_t)nq * tree_ncols[t];
         q_words = (q_words + 3) & ~(size_t)3;
-        tree_slot[t].paths_at = q_words; q_words += (size_t)nq * trees_h[t] * 8 + 8;
+        tree_slot[t].paths_at = q_words;
+        if (compact) {
+            // the listed nodes of the tree instead of a path per query: their positions in its digest array
+            listed_positions(trees_h[t], &tree_nodes[t]);
+            q_words += tree_nodes[t].size() * 8 + 8;
+        } else q_words += (size_t)nq * trees_h[t] * 8 + 8;
     }
     for (size_t l = 0; l < layers.size(); l++) {
         q_words = (q_words + 3) & ~(size_t)3;  // 16-byte aligned: gather_siblings stores uint4
         layer_slot[l].rows_at = q_words; q_words += (size_t)nq * 4;
-        layer_slot[l].paths_at = q_words; q_words += (size_t)nq * (layers[l].log_m - 1) * 8 + 8;
+        layer_slot[l].paths_at = q_words;
+        if (compact) {
+            listed_positions(layers[l].log_m - 1, &layer_nodes[l]);
+            q_words += layer_nodes[l].size() * 8 + 8;
+        } else q_words += (size_t)nq * (layers[l].log_m - 1) * 8 + 8;
     }
     uint32_t *d_q;
     ALLOC(d_q, uint32_t, q_words);
@@ -1018,12 +1036,20 @@ bool Engine::prove_shard(const ProvingKey &pk, const std::vector<ChipTrace> &tra
         const uint32_t *d_lh = upload_vec(lhs);
         if (!d_cols || !d_lh) return false;
         HIPCHK(launch_gather_rows(stream, d_cols, d_lh, tree_ncols[t], d_idx, nq, d_q + tree_slot[t].rows_at));
-        HIPCHK(launch_gather_paths(stream, trees_dev[t], trees_h[t], d_idx, nq, d_q + tree_slot[t].paths_at));
+        if (compact) {
+            const uint32_t *d_at = tree_nodes[t].empty() ? nullptr : upload_vec(tree_nodes[t]);
+            if (!tree_nodes[t].empty() && !d_at) return false;
+            HIPCHK(launch_gather_nodes(stream, trees_dev[t], d_at, (uint32_t)tree_nodes[t].size(), d_q + tree_slot[t].paths_at));
+        } else HIPCHK(launch_gather_paths(stream, trees_dev[t], trees_h[t], d_idx, nq, d_q + tree_slot[t].paths_at));
     }
     for (size_t l = 0; l < layers.size(); l++) {
         auto &L = layers[l];
         HIPCHK(launch_gather_siblings(stream, L.v, L.log_m, d_idx, nq, reinterpret_cast<Fp4 *>(d_q + layer_slot[l].rows_at)));
-        HIPCHK(launch_gather_paths(stream, L.tree, L.log_m - 1, d_idx, nq, d_q + layer_slot[l].paths_at));
+        if (compact) {
+            const uint32_t *d_at = layer_nodes[l].empty() ? nullptr : upload_vec(layer_nodes[l]);
+            if (!layer_nodes[l].empty() && !d_at) return false;
+            HIPCHK(launch_gather_nodes(stream, L.tree, d_at, (uint32_t)layer_nodes[l].size(), d_q + layer_slot[l].paths_at));
+        } else HIPCHK(launch_gather_paths(stream, L.tree, L.log_m - 1, d_idx, nq, d_q + layer_slot[l].paths_at));
     }
     // canonical words on the device, one download, then the query section of the proof straight in wire format
     HIPCHK(launch_from_internal(stream, d_q, q_words));
@@ -1036,7 +1062,7 @@ bool Engine::prove_shard(const ProvingKey &pk, const std::vector<ChipTrace> &tra
         auto put = [&](const uint32_t *src, size_t n) { w.insert(w.end(), src, src + n); };
         for (uint32_t q = 0; q < nq; q++) {
             for (int t = 0; t < 4; t++) {
-                if (tree_mats[t].empty()) { w.push_back(0); w.push_back(0); continue; }   // no rows, empty path
+                if (tree_mats[t].empty()) { w.push_back(0); if (!compact) w.push_back(0); continue; }   // no rows, empty path
                 w.push_back((uint32_t)tree_mats[t].size());
                 const uint32_t *row = hq.data() + tree_slot[t].rows_at + (size_t)q * tree_ncols[t];
                 for (auto &tmx : tree_mats[t]) {
@@ -1044,6 +1070,7 @@ bool Engine::prove_shard(const ProvingKey &pk, const std::vector<ChipTrace> &tra
                     put(row, tmx.width);
                     row += tmx.width;
                 }
+                if (compact) continue;
                 w.push_back(trees_h[t]);
                 put(hq.data() + tree_slot[t].paths_at + (size_t)q * trees_h[t] * 8, (size_t)trees_h[t] * 8);
             }
@@ -1051,8 +1078,20 @@ bool Engine::prove_shard(const ProvingKey &pk, const std::vector<ChipTrace> &tra
             for (size_t li = 0; li < layers.size(); li++) {
                 const uint32_t th = layers[li].log_m - 1;
                 put(hq.data() + layer_slot[li].rows_at + (size_t)q * 4, 4);
+                if (compact) continue;
                 w.push_back(th);
                 put(hq.data() + layer_slot[li].paths_at + (size_t)q * th * 8, (size_t)th * 8);
+            }
+        }
+        if (compact) {   // one node list per tree behind the queries (proof.h)
+            pf.compact = true;
+            for (int t = 0; t < 4; t++) {
+                w.push_back((uint32_t)tree_nodes[t].size());
+                put(hq.data() + tree_slot[t].paths_at, tree_nodes[t].size() * 8);
+            }
+            for (size_t li = 0; li < layers.size(); li++) {
+                w.push_back((uint32_t)layer_nodes[li].size());
+                put(hq.data() + layer_slot[li].paths_at, layer_nodes[li].size() * 8);
             }
         }
     }

@@ -378,6 +378,20 @@ hipError_t launch_gather_paths(hipStream_t st, const uint32_t *d_digests, uint32
     gather_paths_kernel<<<(nq * log_h * 8 + 255) / 256, 256, 0, st>>>(d_digests, log_h, d_idx, nq, d_out);
     return hipGetLastError();
 }
+// out[i] = digests[at[i]]: one thread per digest, two 16-byte loads and stores
+__global__ void gather_nodes_kernel(const uint32_t *digests, const uint32_t *at, uint32_t n, uint32_t *out) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint4 *src = reinterpret_cast<const uint4 *>(digests + (size_t)at[i] * 8);
+    uint4 *dst = reinterpret_cast<uint4 *>(out + (size_t)i * 8);
+    dst[0] = src[0];
+    dst[1] = src[1];
+}
+hipError_t launch_gather_nodes(hipStream_t st, const uint32_t *d_digests, const uint32_t *d_at, uint32_t n, uint32_t *d_out) {
+    if (!n) return hipSuccess;
+    gather_nodes_kernel<<<(n + 255) / 256, 256, 0, st>>>(d_digests, d_at, n, d_out);
+    return hipGetLastError();
+}
 // out[q] = v[(idx[q] mod M) xor M/2]
 __global__ void gather_siblings_kernel(const Fp4 *v, uint32_t log_m, const uint32_t *idx, uint32_t nq, Fp4 *out) {
     uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;

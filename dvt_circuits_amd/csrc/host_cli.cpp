@@ -1,8 +1,10 @@
 // dvt_prover_host — the reference's CLI verbs (src/main.rs:58-106) over the C ABI.
 //
-//   dvt_prover_host prove   --type T -i INPUT.json [-o PROOF] [--elf GUEST.elf] [--devices D0,D1,...]
+//   dvt_prover_host prove   --type T -i INPUT.json [-o PROOF] [--elf GUEST.elf] [--devices D0,D1,...] [--compact]
 //   dvt_prover_host execute --type T -i INPUT.json [--show-report] [--elf GUEST.elf]
 //   dvt_prover_host verify  --type T -i PROOF [--elf GUEST.elf]
+//   dvt_prover_host compact --type T -i PROOF [-o PROOF] [--elf GUEST.elf]     (shared Merkle paths sent once: dvt_proof_compact)
+//   dvt_prover_host expand  --type T -i PROOF [-o PROOF] [--elf GUEST.elf]     (the inverse; verify takes either form)
 //   dvt_prover_host check   --type T -i INPUT.json [--elf GUEST.elf] [--devices D0,D1,...]
 //
 // T = bad-share | finalization | bad-partial-key | bad-encrypted-share (clap names of CircuitType, :36-42).
@@ -53,10 +55,10 @@ static void print_bus_tuple(const dvt_bus_tuple &t) {
 }
 
 int main(int argc, char **argv) {
-    if (argc < 2) return die("usage: dvt_prover_host prove|execute|verify|check --type T -i FILE [-o FILE] [--show-report] [--elf FILE] [--devices D0,D1,...] [--device D]");
+    if (argc < 2) return die("usage: dvt_prover_host prove|execute|verify|check|compact|expand --type T -i FILE [-o FILE] [--show-report] [--compact] [--elf FILE] [--devices D0,D1,...] [--device D]");
     const std::string verb = argv[1];
     std::string type, input, output, elf_path, schema_path, devices, verify_device;
-    bool show_report = false, auth = false;
+    bool show_report = false, auth = false, compact = false;
     for (int i = 2; i < argc; i++) {
         std::string a = argv[i], inline_val;
         bool has_inline = false;
@@ -72,11 +74,13 @@ int main(int argc, char **argv) {
         else if (a == "--devices") devices = next();
         else if (a == "--device") verify_device = next();   // verify: the query part on that GPU (dvt_prover_verify)
         else if (a == "--show-report") show_report = true;
+        else if (a == "--compact") compact = true;       // prove: shard proofs in the compact form ("compact_openings")
         else if (a == "--auth-commitment") auth = true;  // the reference selects this at build time (cargo feature)
         else if (a == "--json-schema-file") schema_path = next();
         else return die("unknown argument " + a);
     }
-    if (verb != "prove" && verb != "execute" && verb != "verify" && verb != "check") return die("unknown sub-command " + verb);
+    const bool transcode = verb == "compact" || verb == "expand";   // -i: a proof; -o: the proof in the other form
+    if (verb != "prove" && verb != "execute" && verb != "verify" && verb != "check" && !transcode) return die("unknown sub-command " + verb);
     if (type.empty() || input.empty()) return die("--type and --input-file are required");
     if (elf_path.empty()) {
         const char *dir = getenv("DVT_ELF_DIR");
@@ -87,7 +91,7 @@ int main(int argc, char **argv) {
     if (!read_file(elf_path, &elf)) return die("cannot read ELF " + elf_path);
     if (!read_file(input, &in)) return die("cannot read " + input);
 
-    if (!schema_path.empty() && verb != "verify") {  // validate_if_needed (src/main.rs:509-541)
+    if (!schema_path.empty() && verb != "verify" && !transcode) {  // validate_if_needed (src/main.rs:509-541)
         std::vector<uint8_t> sch;
         if (!read_file(schema_path, &sch)) return die("Could not read schema file '" + schema_path + "'");
         char *verr = nullptr;
@@ -104,7 +108,7 @@ int main(int argc, char **argv) {
         }
     }
 
-    if (verb == "verify") {
+    if (verb == "verify" || transcode) {
         dvt_prover *p = nullptr;
         const std::string vcfg = "{\"device\": " + std::to_string(atoi(verify_device.c_str())) + "}";
         if (dvt_prover_create(verify_device.empty() ? nullptr : vcfg.c_str(), &p)) return die(dvt_last_error(nullptr));
@@ -113,6 +117,17 @@ int main(int argc, char **argv) {
         size_t vk_len = 0;
         if (dvt_setup(p, elf.data(), elf.size(), &pk, &vk, &vk_len)) return die(dvt_last_error(p));
         char *why = nullptr;
+        if (transcode) {   // either form in, the named form out; verify takes both unchanged
+            uint8_t *out = nullptr;
+            size_t out_len = 0;
+            const int rc = (verb == "compact" ? dvt_proof_compact : dvt_proof_expand)(vk, vk_len, in.data(), in.size(), 100, 16, &out, &out_len, &why);
+            if (rc) return die(std::string("Proof rejected: ") + (why ? why : "?"));
+            const std::string path = output.empty() ? input + (verb == "compact" ? "_compact.bin" : "_plain.bin") : output;
+            std::ofstream f(path, std::ios::binary);
+            if (!f || !f.write((const char *)out, (std::streamsize)out_len)) return die("Saving proof failed: " + path);
+            printf("Proof saved to: %s (%zu -> %zu bytes)\n", path.c_str(), in.size(), out_len);
+            return 0;
+        }
         int32_t ec = 0;
         int rc = verify_device.empty() ? dvt_verify(vk, vk_len, in.data(), in.size(), 100, 16, &ec, nullptr, nullptr, &why)
                                        : dvt_prover_verify(p, vk, vk_len, in.data(), in.size(), 100, 16, &ec, nullptr, nullptr, &why);
@@ -139,8 +154,12 @@ int main(int argc, char **argv) {
     }
 
     dvt_prover *p = nullptr;
-    const std::string cfg = "{\"devices\": [" + devices + "]}";   // (the library checks the list)
-    if (dvt_prover_create(devices.empty() ? nullptr : cfg.c_str(), &p)) return die(dvt_last_error(nullptr));
+    // (the library checks the list; without either option the handle is made as before, from no config at all)
+    std::string cfg;
+    if (!devices.empty()) cfg += "\"devices\": [" + devices + "]";
+    if (compact) cfg += std::string(cfg.empty() ? "" : ", ") + "\"compact_openings\": 1";
+    cfg = "{" + cfg + "}";
+    if (dvt_prover_create(devices.empty() && !compact ? nullptr : cfg.c_str(), &p)) return die(dvt_last_error(nullptr));
     dvt_pk *pk = nullptr;
     if (dvt_setup(p, elf.data(), elf.size(), &pk, nullptr, nullptr)) return die(dvt_last_error(p));
     if (verb == "check") {

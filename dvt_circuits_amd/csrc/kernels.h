@@ -89,6 +89,8 @@ hipError_t launch_gather_rows(hipStream_t st, const uint32_t *const *d_cols, con
                               const uint32_t *d_idx, uint32_t nq, uint32_t *d_out);
 hipError_t launch_gather_paths(hipStream_t st, const uint32_t *d_digests, uint32_t log_h, const uint32_t *d_idx, uint32_t nq,
                                uint32_t *d_out);
+// out[i][8] = digests[at[i]][8]: the listed nodes of a compact proof's tree, `at` being positions in the tree's digest array
+hipError_t launch_gather_nodes(hipStream_t st, const uint32_t *d_digests, const uint32_t *d_at, uint32_t n, uint32_t *d_out);
 hipError_t launch_gather_siblings(hipStream_t st, const Fp4 *d_v, uint32_t log_m, const uint32_t *d_idx, uint32_t nq, Fp4 *d_out);
 hipError_t launch_pow_grind(hipStream_t st, const uint32_t state[16], uint32_t pos, uint32_t bits, uint32_t base, uint32_t count,
                             uint32_t *d_found);

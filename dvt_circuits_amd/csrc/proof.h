@@ -6,8 +6,10 @@
 // element in canonical form, every vector preceded by its length.  DESIGN.md
 // "Proof format" lists the fields in order.
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <stdexcept>
+#include <utility>
 #include <vector>
 
 #include "poseidon2.cuh"
@@ -43,7 +45,74 @@ struct ShardProof {
     // emits for `queries`, including the leading count) instead of building `queries`: one pass over the downloaded
     // gather buffer, no per-query vectors.  Empty = serialise `queries`.
     std::vector<uint32_t> query_words;
+    // The compact form ("DVP2"): no query carries a path; every tree of the shard (trees 0..3, then the FRI layers in
+    // order) carries the nodes its queries cannot compute themselves, once, in the order of multipath_plan.
+    bool compact = false;
+    std::vector<std::vector<Digest>> node_lists;
 };
+
+// ---- shared Merkle paths.  Parents pair (i, i + half): node j of level s-1 has the children j and j + half of level s
+// (level s has 2^s nodes, level `depth` holds the leaves).  K_s is the set of nodes of level s on a path from a queried
+// leaf.  For s = depth .. 1 and n ascending over K_s, the sibling n ^ half is LISTED when it is not in K_s itself: a
+// verifier that knows the leaves of K_depth and the listed nodes computes every node of every K_s, down to the root.
+// Pure index logic: nothing here reads a digest.
+constexpr uint32_t MP_LISTED = 0x80000000u;
+struct MultipathJob {
+    uint32_t l, r;   // the children: a slot of the level below (position in its sorted K_s), or MP_LISTED | k: the k-th listed node
+    uint32_t j;      // the parent's index in level s-1; job i of a level writes slot i of the level above
+};
+struct MultipathPlan {
+    uint32_t depth = 0;
+    std::vector<std::vector<uint32_t>> keys;         // [s] = K_s, ascending, for s = 0 .. depth
+    std::vector<std::vector<MultipathJob>> levels;   // [depth - s] for s = depth .. 1, each ascending in j
+    std::vector<std::pair<uint32_t, uint32_t>> nodes;   // the listed nodes (level, index), in the order of the wire format
+    std::vector<uint32_t> base;                      // [s] = how many listed nodes lie on levels above s (base[depth] = 0)
+    // The plan of the same indices for a tree of only d <= depth levels is this plan from level d on: its leaves are
+    // keys[d], its levels are levels[depth - s] for s = d .. 1, and its listed nodes are nodes[base[d] ..], so that a job's
+    // k-th listed node is the tree's (k - base[d])-th.  All trees of a shard are walked with one plan.
+    size_t listed(uint32_t d) const { return nodes.size() - base[d]; }
+};
+inline MultipathPlan multipath_plan(uint32_t depth, const uint32_t *indices, size_t n) {
+    MultipathPlan pl;
+    pl.depth = depth;
+    std::vector<uint32_t> K(n);
+    for (size_t i = 0; i < n; i++) K[i] = indices[i] & (uint32_t)(((uint64_t)1 << depth) - 1);
+    std::sort(K.begin(), K.end());
+    K.erase(std::unique(K.begin(), K.end()), K.end());
+    pl.keys.resize(depth + 1);
+    pl.base.assign(depth + 1, 0);
+    pl.keys[depth] = K;
+    pl.levels.resize(depth);
+    for (uint32_t s = depth; s >= 1; s--) {
+        const uint32_t half = 1u << (s - 1);
+        const size_t m = std::lower_bound(K.begin(), K.end(), half) - K.begin();   // K[0, m) are left children, K[m, ..) right ones
+        // (both halves ascending: a sibling is present when the other half holds the same offset)
+        std::vector<uint32_t> listed(K.size(), 0);
+        for (size_t i = 0, k = m; i < m || k < K.size();) {
+            const uint32_t a = i < m ? K[i] : 0xffffffffu, b = k < K.size() ? K[k] - half : 0xffffffffu;
+            if (a == b) { i++; k++; }
+            else if (a < b) listed[i++] = MP_LISTED;
+            else listed[k++] = MP_LISTED;
+        }
+        for (size_t i = 0; i < K.size(); i++)      // n ascending over K_s
+            if (listed[i]) {
+                listed[i] = MP_LISTED | (uint32_t)pl.nodes.size();
+                pl.nodes.push_back({s, K[i] ^ half});
+            }
+        std::vector<MultipathJob> &jobs = pl.levels[depth - s];
+        std::vector<uint32_t> &up = pl.keys[s - 1];
+        for (size_t i = 0, k = m; i < m || k < K.size();) {
+            const uint32_t a = i < m ? K[i] : 0xffffffffu, b = k < K.size() ? K[k] - half : 0xffffffffu, j = std::min(a, b);
+            jobs.push_back({a == j ? (uint32_t)i : listed[k], b == j ? (uint32_t)k : listed[i], j});
+            up.push_back(j);
+            if (a == j) i++;
+            if (b == j) k++;
+        }
+        pl.base[s - 1] = (uint32_t)pl.nodes.size();
+        K = up;
+    }
+    return pl;
+}
 
 struct WordWriter {
     std::vector<uint32_t> w;
@@ -69,9 +138,11 @@ struct WordReader {
 };
 
 constexpr uint32_t SHARD_PROOF_MAGIC = 0x31505644u;  // "DVP1"
+constexpr uint32_t SHARD_PROOF_MAGIC_COMPACT = 0x32505644u;  // "DVP2"
+constexpr uint32_t MAX_QUERIES = 1024, MAX_TREE_DEPTH = 22;
 
 inline void write_shard_proof(WordWriter &w, const ShardProof &p) {
-    w.u32(SHARD_PROOF_MAGIC);
+    w.u32(p.compact ? SHARD_PROOF_MAGIC_COMPACT : SHARD_PROOF_MAGIC);
     w.dg(p.main_root); w.dg(p.perm_root); w.dg(p.quot_root);
     w.fps(p.public_values);
     w.u32((uint32_t)p.chips.size());
@@ -90,16 +161,20 @@ inline void write_shard_proof(WordWriter &w, const ShardProof &p) {
         for (int t = 0; t < 4; t++) {
             w.u32((uint32_t)q.trees[t].rows.size());
             for (auto &r : q.trees[t].rows) w.fps(r);
-            w.dgs(q.trees[t].path);
+            if (!p.compact) w.dgs(q.trees[t].path);
         }
         w.u32((uint32_t)q.layers.size());
-        for (auto &l : q.layers) { w.ef(l.sibling); w.dgs(l.path); }
+        for (auto &l : q.layers) { w.ef(l.sibling); if (!p.compact) w.dgs(l.path); }
     }
+    if (p.compact)
+        for (auto &l : p.node_lists) w.dgs(l);
 }
 
 inline ShardProof read_shard_proof(WordReader &r) {
     ShardProof p;
-    if (r.u32() != SHARD_PROOF_MAGIC) throw std::runtime_error("proof: bad magic");
+    const uint32_t magic = r.u32();
+    if (magic != SHARD_PROOF_MAGIC && magic != SHARD_PROOF_MAGIC_COMPACT) throw std::runtime_error("proof: bad magic");
+    p.compact = magic == SHARD_PROOF_MAGIC_COMPACT;
     p.main_root = r.dg(); p.perm_root = r.dg(); p.quot_root = r.dg();
     p.public_values = r.fps(1 << 12);
     uint32_t nc = r.len(64);
@@ -112,18 +187,24 @@ inline ShardProof read_shard_proof(WordReader &r) {
         c.perm_l = r.efs(1 << 12); c.perm_n = r.efs(1 << 12); c.quot = r.efs(8);
     }
     p.fri_roots = r.dgs(); p.final_poly = r.ef(); p.pow_witness = r.fp();
-    uint32_t nq = r.len(1024);
+    uint32_t nq = r.len(MAX_QUERIES);
     p.queries.resize(nq);
     for (auto &q : p.queries) {
         for (int t = 0; t < 4; t++) {
             uint32_t nm = r.len(256);
             q.trees[t].rows.resize(nm);
             for (auto &row : q.trees[t].rows) row = r.fps(1 << 12);
-            q.trees[t].path = r.dgs();
+            if (!p.compact) q.trees[t].path = r.dgs();
         }
         uint32_t nl = r.len(64);
         q.layers.resize(nl);
-        for (auto &l : q.layers) { l.sibling = r.ef(); l.path = r.dgs(); }
+        for (auto &l : q.layers) { l.sibling = r.ef(); if (!p.compact) l.path = r.dgs(); }
+    }
+    if (p.compact) {
+        // one list per tree: the four input trees, then one per FRI root (the verifier checks that number against the
+        // chips' heights).  No tree lists more than one node per query and level.
+        p.node_lists.resize(4 + p.fri_roots.size());
+        for (auto &l : p.node_lists) l = r.dgs(MAX_QUERIES * MAX_TREE_DEPTH);
     }
     return p;
 }

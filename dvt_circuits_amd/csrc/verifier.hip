@@ -209,7 +209,33 @@ std::string verify_shard_host(const VerifyingKey &vk, const ShardProof &pf, cons
     // the query indices depend on nothing a query opens: all of them are drawn here
     ctx->idx.resize(cfg.num_queries);
     for (auto &i : ctx->idx) i = ch.sample_bits(hmax);
+    if (pf.compact) ctx->paths = tree_sources(hmax, ctx->idx);   // one plan for every tree of the shard
     return "";
+}
+
+// the batched quotient of the columns of LDE height h at the point the query opens (the FRI input of that height)
+static Fp4 reduced_opening_at(const ShardQueryCtx &ctx, const QueryProof &q, uint32_t idx, uint32_t h) {
+    const ShardProof &pf = *ctx.pf;
+    const std::vector<Fp4> &apow = ctx.apow;
+    const auto &cols = ctx.cols_by_h[h];
+    const Fp g = Fp::from_canonical(COSET_SHIFT);
+    Fp x = g * pow(two_adic_generator(h), idx & ((1u << h) - 1));
+    Fp4 s_all = Fp4::zero(), s_two = Fp4::zero();
+    for (size_t c = 0; c < cols.size(); c++) {
+        const ColRef &r = cols[c];
+        const ChipOpening &o = pf.chips[r.chip_pos];
+        Fp px = q.trees[r.tree].rows[r.mat][r.col];
+        const std::vector<Fp4> &loc = r.tree == 0 ? o.prep_l : r.tree == 1 ? o.main_l : r.tree == 2 ? o.perm_l : o.quot;
+        s_all += apow[c] * (Fp4::from_base(px) - loc[r.col]);
+        if (r.tree < 3) {
+            const std::vector<Fp4> &nx = r.tree == 0 ? o.prep_n : r.tree == 1 ? o.main_n : o.perm_n;
+            s_two += apow[c] * (Fp4::from_base(px) - nx[r.col]);
+        }
+    }
+    Fp4 zeta_next = ctx.zeta * two_adic_generator(h - 1);
+    Fp4 r = s_all * inv(Fp4::from_base(x) - ctx.zeta);
+    if (ctx.n_two_by_h[h]) r += apow[cols.size()] * (s_two * inv(Fp4::from_base(x) - zeta_next));
+    return r;
 }
 
 // ---- the query part on the host: query qi of the shard whose host part left ctx
@@ -218,11 +244,8 @@ std::string verify_query_host(const ShardQueryCtx &ctx, uint32_t qi) {
     const TreeShape *shapes = ctx.shapes;
     const Digest *const *roots = ctx.roots;
     const std::vector<std::vector<ColRef>> &cols_by_h = ctx.cols_by_h;
-    const std::vector<uint32_t> &n_two_by_h = ctx.n_two_by_h;
-    const std::vector<Fp4> &apow = ctx.apow, &fold_betas = ctx.fold_betas;
+    const std::vector<Fp4> &fold_betas = ctx.fold_betas;
     const uint32_t hmax = ctx.hmax;
-    const Fp4 zeta = ctx.zeta;
-    const Fp g = Fp::from_canonical(COSET_SHIFT);
     const Fp inv2 = inv(Fp::two());
     {
         const QueryProof &q = pf.queries[qi];
@@ -234,26 +257,7 @@ std::string verify_query_host(const ShardQueryCtx &ctx, uint32_t qi) {
             }
             if (!verify_tree_opening(shapes[t], q.trees[t], idx, *roots[t])) return "Merkle opening rejected (input tree)";
         }
-        auto reduced = [&](uint32_t h) {
-            const auto &cols = cols_by_h[h];
-            Fp x = g * pow(two_adic_generator(h), idx & ((1u << h) - 1));
-            Fp4 s_all = Fp4::zero(), s_two = Fp4::zero();
-            for (size_t c = 0; c < cols.size(); c++) {
-                const ColRef &r = cols[c];
-                const ChipOpening &o = pf.chips[r.chip_pos];
-                Fp px = q.trees[r.tree].rows[r.mat][r.col];
-                const std::vector<Fp4> &loc = r.tree == 0 ? o.prep_l : r.tree == 1 ? o.main_l : r.tree == 2 ? o.perm_l : o.quot;
-                s_all += apow[c] * (Fp4::from_base(px) - loc[r.col]);
-                if (r.tree < 3) {
-                    const std::vector<Fp4> &nx = r.tree == 0 ? o.prep_n : r.tree == 1 ? o.main_n : o.perm_n;
-                    s_two += apow[c] * (Fp4::from_base(px) - nx[r.col]);
-                }
-            }
-            Fp4 zeta_next = zeta * two_adic_generator(h - 1);
-            Fp4 r = s_all * inv(Fp4::from_base(x) - zeta);
-            if (n_two_by_h[h]) r += apow[cols.size()] * (s_two * inv(Fp4::from_base(x) - zeta_next));
-            return r;
-        };
+        auto reduced = [&](uint32_t h) { return reduced_opening_at(ctx, q, idx, h); };
         if (q.layers.size() != hmax - 1) return "wrong number of FRI layer openings";
         Fp4 e = reduced(hmax);
         for (uint32_t k = 0; k + 1 < hmax; k++) {
@@ -278,6 +282,7 @@ std::string verify_shard(const VerifyingKey &vk, const ShardProof &pf, const Sta
                          Fp4 *cumsum_total) {
     ShardQueryCtx ctx;
     std::string why = verify_shard_host(vk, pf, cfg, global, cumsum_total, &ctx);
+    if (why.empty() && pf.compact) return verify_compact_queries(ctx);
     for (uint32_t qi = 0; why.empty() && qi < cfg.num_queries; qi++) why = verify_query_host(ctx, qi);
     return why;
 }
@@ -300,6 +305,261 @@ bool query_shape_ok(const ShardQueryCtx &ctx, uint32_t qi) {
     for (uint32_t k = 0; k + 1 < ctx.hmax; k++)
         if (q.layers[k].path.size() != ctx.hmax - k - 1) return false;
     return true;
+}
+
+// ------------------------------------------------------------------------------------------------ the compact form (DVP2)
+
+static uint32_t list_depth(const ShardQueryCtx &ctx, size_t li) { return li < 4 ? ctx.shapes[li].log_h : ctx.hmax - (uint32_t)(li - 4) - 1; }
+
+bool compact_shape_ok(const ShardQueryCtx &ctx, std::string *why) {
+    const ShardProof &pf = *ctx.pf;
+    auto no = [&](const char *t) { if (why) *why = t; return false; };
+    for (auto &q : pf.queries) {
+        for (int t = 0; t < 4; t++) {
+            const TreeShape &sh = ctx.shapes[t];
+            const TreeOpening &op = q.trees[t];
+            if (!op.path.empty()) return no("a compact shard proof carries a path");
+            if (sh.mats.empty()) {
+                if (!op.rows.empty()) return no("unexpected opening for an empty tree");
+                continue;
+            }
+            if (op.rows.size() != sh.mats.size()) return no("Merkle opening rejected (input tree)");
+            for (size_t i = 0; i < sh.mats.size(); i++)
+                if (op.rows[i].size() != sh.mats[i].first) return no("Merkle opening rejected (input tree)");
+        }
+        if (q.layers.size() != ctx.hmax - 1) return no("wrong number of FRI layer openings");
+        for (auto &l : q.layers)
+            if (!l.path.empty()) return no("a compact shard proof carries a path");
+    }
+    if (pf.node_lists.size() != 4 + (size_t)ctx.hmax - 1) return no("wrong number of node lists");
+    for (size_t i = 0; i < pf.node_lists.size(); i++) {
+        const bool empty = i < 4 && ctx.shapes[i].mats.empty();
+        const size_t want = empty ? 0 : ctx.paths.plan.listed(list_depth(ctx, i));
+        if (pf.node_lists[i].size() != want) return no("node list length does not match the query indices");
+    }
+    return true;
+}
+
+TreeSources tree_sources(uint32_t depth, const std::vector<uint32_t> &idx) {
+    TreeSources ts;
+    ts.plan = multipath_plan(depth, idx.data(), idx.size());
+    const uint32_t NOQ = 0xffffffffu;
+    ts.first.resize(depth + 1);
+    ts.dups.resize(depth + 1);
+    ts.listed_at.resize(depth + 1);
+    for (uint32_t lh = 0; lh <= depth; lh++) {
+        const std::vector<uint32_t> &keys = ts.plan.keys[lh];
+        ts.first[lh].assign(keys.size(), NOQ);
+        for (uint32_t q = 0; q < idx.size(); q++) {
+            const uint32_t j = idx[q] & (uint32_t)(((uint64_t)1 << lh) - 1);
+            const size_t slot = std::lower_bound(keys.begin(), keys.end(), j) - keys.begin();
+            uint32_t &f = ts.first[lh][slot];
+            if (f == NOQ) f = q;
+            else ts.dups[lh].push_back({f, q});
+        }
+    }
+    for (size_t n = 0; n < ts.plan.nodes.size(); n++) ts.listed_at[ts.plan.nodes[n].first].push_back({ts.plan.nodes[n].second, (uint32_t)n});
+    for (auto &l : ts.listed_at) std::sort(l.begin(), l.end());
+    return ts;
+}
+
+namespace {
+
+// what the opened values of one query come to before any path: the row digests of each height of each input tree, the
+// leaf of every FRI layer and the value the fold chain ends in
+struct QueryDigests {
+    std::vector<Digest> rows[4];       // [lh] where the tree has matrices of that height
+    std::vector<uint8_t> has[4];
+    std::vector<Digest> layer_leaf;
+    Fp4 final_value;
+};
+QueryDigests query_digests(const ShardQueryCtx &ctx, uint32_t qi) {
+    const ShardProof &pf = *ctx.pf;
+    const QueryProof &q = pf.queries[qi];
+    const uint32_t idx = ctx.idx[qi], hmax = ctx.hmax;
+    QueryDigests d;
+    for (int t = 0; t < 4; t++) {
+        const TreeShape &sh = ctx.shapes[t];
+        if (sh.mats.empty()) continue;
+        d.rows[t].resize(sh.log_h + 1);
+        d.has[t].assign(sh.log_h + 1, 0);
+        for (uint32_t lh = 0; lh <= sh.log_h; lh++) {
+            std::vector<const std::vector<Fp> *> r;
+            for (size_t i = 0; i < sh.mats.size(); i++)
+                if (sh.mats[i].second == lh) r.push_back(&q.trees[t].rows[i]);
+            if (r.empty()) continue;
+            d.has[t][lh] = 1;
+            d.rows[t][lh] = hash_rows(r);
+        }
+    }
+    const Fp inv2 = inv(Fp::two());
+    Fp4 e = reduced_opening_at(ctx, q, idx, hmax);
+    for (uint32_t k = 0; k + 1 < hmax; k++) {
+        const uint32_t lm = hmax - k, half = 1u << (lm - 1);
+        const uint32_t j = idx & ((1u << lm) - 1), jl = j & (half - 1);
+        const Fp4 sib = q.layers[k].sibling;
+        Fp4 a = j < half ? e : sib, b = j < half ? sib : e;
+        Sponge sp;
+        for (int c = 0; c < 4; c++) sp.absorb(a.c[c]);
+        for (int c = 0; c < 4; c++) sp.absorb(b.c[c]);
+        d.layer_leaf.push_back(sp.finish());
+        Fp xinv = inv(pow(two_adic_generator(lm), jl));
+        e = (a + b) * inv2 + ctx.fold_betas[k] * ((a - b) * (inv2 * xinv));
+        if (!ctx.cols_by_h[lm - 1].empty()) e += reduced_opening_at(ctx, q, idx, lm - 1);
+    }
+    d.final_value = e;
+    return d;
+}
+
+// One tree of `depth` levels of a compact shard, walked with the shard's sources: `digest_of(lh, q)` is query q's digest of
+// height lh (nullptr: the tree has none there), `listed` the tree's node list.  False when two queries disagree on a digest
+// they share or the walk does not end in the root.  With levels != nullptr every node on a path is kept:
+// (*levels)[lh][slot of ts.plan.keys[lh]].
+template <class F>
+bool walk_tree(const TreeSources &ts, uint32_t depth, const std::vector<Digest> &listed, const Digest &root, F digest_of,
+               std::vector<std::vector<Digest>> *levels) {
+    const MultipathPlan &pl = ts.plan;
+    const uint32_t base = pl.base[depth];
+    bool agree = true;
+    for (uint32_t lh = 0; lh <= depth; lh++)
+        for (auto &d : ts.dups[lh]) {
+            const Digest *a = digest_of(lh, d[0]);
+            if (a && !(*a == *digest_of(lh, d[1]))) agree = false;
+        }
+    if (!agree && !levels) return false;   // (a caller that wants the nodes gets those of the first query on each)
+    std::vector<Digest> cur(pl.keys[depth].size());
+    for (size_t i = 0; i < cur.size(); i++) cur[i] = *digest_of(depth, ts.first[depth][i]);
+    if (levels) { levels->assign(depth + 1, {}); (*levels)[depth] = cur; }
+    for (uint32_t s = depth; s >= 1; s--) {
+        const auto &jobs = pl.levels[pl.depth - s];
+        std::vector<Digest> up(jobs.size());
+        for (size_t i = 0; i < jobs.size(); i++) {
+            const MultipathJob &jb = jobs[i];
+            const Digest &l = jb.l & MP_LISTED ? listed[(jb.l & ~MP_LISTED) - base] : cur[jb.l];
+            const Digest &r = jb.r & MP_LISTED ? listed[(jb.r & ~MP_LISTED) - base] : cur[jb.r];
+            up[i] = p2_compress(l, r);
+            if (const Digest *inj = digest_of(s - 1, ts.first[s - 1][i])) up[i] = p2_compress(up[i], *inj);
+        }
+        cur.swap(up);
+        if (levels) (*levels)[s - 1] = cur;
+    }
+    return agree && cur.size() == 1 && cur[0] == root;
+}
+
+// the trees of a compact shard in the order of the wire format, each walked by `visit(list index, depth, root, digest_of)`
+template <class V>
+void for_each_tree(const ShardQueryCtx &ctx, const std::vector<QueryDigests> &D, V visit) {
+    for (int t = 0; t < 4; t++) {
+        const TreeShape &sh = ctx.shapes[t];
+        if (sh.mats.empty()) continue;
+        if (!visit((size_t)t, sh.log_h, *ctx.roots[t], [&D, t](uint32_t lh, uint32_t q) { return D[q].has[t][lh] ? &D[q].rows[t][lh] : nullptr; })) return;
+    }
+    for (uint32_t k = 0; k + 1 < ctx.hmax; k++) {
+        const uint32_t depth = ctx.hmax - k - 1;
+        if (!visit((size_t)4 + k, depth, ctx.pf->fri_roots[k], [&D, k, depth](uint32_t lh, uint32_t q) { return lh == depth ? &D[q].layer_leaf[k] : nullptr; })) return;
+    }
+}
+
+}  // namespace
+
+std::string verify_compact_queries(const ShardQueryCtx &ctx) {
+    std::string why;
+    if (!compact_shape_ok(ctx, &why)) return why;
+    const ShardProof &pf = *ctx.pf;
+    std::vector<QueryDigests> D;
+    for (uint32_t qi = 0; qi < pf.queries.size(); qi++) D.push_back(query_digests(ctx, qi));
+    for_each_tree(ctx, D, [&](size_t li, uint32_t depth, const Digest &root, auto digest_of) {
+        if (!walk_tree(ctx.paths, depth, pf.node_lists[li], root, digest_of, nullptr))
+            why = li < 4 ? "Merkle opening rejected (input tree)" : "Merkle opening rejected (FRI layer)";
+        return why.empty();
+    });
+    if (!why.empty()) return why;
+    for (auto &d : D)
+        if (d.final_value != pf.final_poly) return "FRI final value mismatch";
+    return "";
+}
+
+void compact_list_sweep(const ShardQueryCtx &ctx, uint64_t *n_words, uint64_t *n_accepted) {
+    const ShardProof &pf = *ctx.pf;
+    std::vector<QueryDigests> D;
+    for (uint32_t qi = 0; qi < pf.queries.size(); qi++) D.push_back(query_digests(ctx, qi));
+    for_each_tree(ctx, D, [&](size_t li, uint32_t depth, const Digest &root, auto digest_of) {
+        std::vector<Digest> listed = pf.node_lists[li];
+        for (auto &dg : listed)
+            for (int w = 0; w < 8; w++) {
+                const Fp keep = dg.d[w];
+                dg.d[w] = keep + Fp::one();
+                ++*n_words;
+                *n_accepted += walk_tree(ctx.paths, depth, listed, root, digest_of, nullptr);
+                dg.d[w] = keep;
+            }
+        return true;
+    });
+}
+
+std::string compact_shard(const ShardQueryCtx &ctx, ShardProof *out) {
+    const ShardProof &pf = *ctx.pf;
+    *out = pf;
+    if (pf.compact) return "";
+    for (uint32_t qi = 0; qi < pf.queries.size(); qi++)
+        if (!query_shape_ok(ctx, qi)) return verify_query_host(ctx, qi);
+    out->compact = true;
+    out->query_words.clear();
+    out->node_lists.assign(4 + (size_t)ctx.hmax - 1, {});
+    const TreeSources ts = tree_sources(ctx.hmax, ctx.idx);
+    const MultipathPlan &pl = ts.plan;
+    // the listed node (level s, index i) is the sibling at level s of the queries whose path passes i ^ half
+    auto fill = [&](size_t li, uint32_t depth, auto path_of) {
+        for (size_t n = pl.base[depth]; n < pl.nodes.size(); n++) {
+            const uint32_t s = pl.nodes[n].first, me = pl.nodes[n].second ^ (1u << (s - 1));
+            const size_t slot = std::lower_bound(pl.keys[s].begin(), pl.keys[s].end(), me) - pl.keys[s].begin();
+            out->node_lists[li].push_back(path_of(ts.first[s][slot])[depth - s]);
+        }
+    };
+    for (int t = 0; t < 4; t++)
+        if (!ctx.shapes[t].mats.empty()) fill((size_t)t, ctx.shapes[t].log_h, [&](uint32_t q) -> const std::vector<Digest> & { return pf.queries[q].trees[t].path; });
+    for (uint32_t k = 0; k + 1 < ctx.hmax; k++)
+        fill((size_t)4 + k, ctx.hmax - k - 1, [&](uint32_t q) -> const std::vector<Digest> & { return pf.queries[q].layers[k].path; });
+    for (auto &q : out->queries) {
+        for (auto &t : q.trees) t.path.clear();
+        for (auto &l : q.layers) l.path.clear();
+    }
+    return "";
+}
+
+std::string expand_shard(const ShardQueryCtx &ctx, ShardProof *out) {
+    const ShardProof &pf = *ctx.pf;
+    *out = pf;
+    if (!pf.compact) return "";
+    std::string why;
+    if (!compact_shape_ok(ctx, &why)) return why;
+    out->compact = false;
+    out->node_lists.clear();
+    out->query_words.clear();
+    std::vector<QueryDigests> D;
+    for (uint32_t qi = 0; qi < pf.queries.size(); qi++) D.push_back(query_digests(ctx, qi));
+    const TreeSources &ts = ctx.paths;
+    const MultipathPlan &pl = ts.plan;
+    for_each_tree(ctx, D, [&](size_t li, uint32_t depth, const Digest &root, auto digest_of) {
+        std::vector<std::vector<Digest>> levels;
+        (void)walk_tree(ts, depth, pf.node_lists[li], root, digest_of, &levels);
+        // the sibling of a path's node at level s: a node another path computes, or the listed one (both by binary search)
+        for (uint32_t q = 0; q < ctx.idx.size(); q++) {
+            std::vector<Digest> &path = li < 4 ? out->queries[q].trees[li].path : out->queries[q].layers[li - 4].path;
+            path.resize(depth);
+            for (uint32_t s = depth; s >= 1; s--) {
+                const uint32_t half = 1u << (s - 1), sib = (ctx.idx[q] & ((1u << s) - 1)) ^ half;
+                const auto &keys = pl.keys[s];
+                const auto it = std::lower_bound(keys.begin(), keys.end(), sib);
+                if (it != keys.end() && *it == sib) { path[depth - s] = levels[s][it - keys.begin()]; continue; }
+                const auto &at = ts.listed_at[s];
+                const auto ln = std::lower_bound(at.begin(), at.end(), std::make_pair(sib, 0u));
+                path[depth - s] = pf.node_lists[li][ln->second - pl.base[depth]];   // (present: the plan lists what no path computes)
+            }
+        }
+        return true;
+    });
+    return "";
 }
 
 }  // namespace dvt

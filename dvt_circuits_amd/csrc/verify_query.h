@@ -23,6 +23,29 @@ struct Chain {
     uint32_t inj;                  // index into the injection table (`depth` entries: a digest offset or NONE), or NONE
     uint32_t root, status, kind;
 };
+// A tree of a compact shard (DVP2): all its queries walk up together, level by level.  Job i of a level compresses two
+// children (each a slot of the level below, or with its flag in `dst` a digest at a word offset: a listed node), then where
+// shorter matrices join the digest at `inj`, and writes slot `dst & MP_SLOT` of the level above.
+constexpr uint32_t MP_L_WORD = 0x80000000u, MP_R_WORD = 0x40000000u, MP_SLOT = 0xffffu;
+constexpr uint32_t MP_MAX_SLOTS = 1024;               // nodes of one level: at most one per query (the reader's cap)
+struct MpJob { uint32_t l, r, inj, dst; };
+struct MpLevel { uint32_t job0, njobs; };
+struct MpCmp { uint32_t a, b, status; };               // two digests that queries on one node must agree on
+struct Tree {
+    uint32_t leaf0, nleaf;       // word offsets of the leaf digests: leaves[leaf0 ..], ascending leaf index
+    uint32_t level0, nlevels;    // its levels, from the leaves' parents to the root
+    uint32_t cmp0, ncmp;
+    uint32_t root, status;
+};
+struct MpTables {
+    std::vector<Tree> trees;
+    std::vector<MpLevel> levels;
+    std::vector<MpJob> jobs;
+    std::vector<uint32_t> leaves;
+    std::vector<MpCmp> cmps;
+    uint32_t cap = 0;            // most slots of any level of any tree
+    uint64_t perms = 0;
+};
 struct Col { uint32_t px, loc, nx; };   // the opened row word (relative to the query's section), p(zeta), p(zeta w) or NONE
 struct Unit { uint32_t query, h; };
 struct Query { uint32_t shard, idx, base, red0, sib0, leaf0, fin, pad; };
@@ -71,6 +94,13 @@ class Batch {
     struct ShardResult {
         size_t chunk = 0;
         std::vector<QueryResult> queries;
+        // a compact shard: answered on the host (a shape check failed), or the status ranges [first, last] of its trees in
+        // the order of the wire format (the first n_input of them are input trees) and one final-value byte per query
+        bool compact = false, on_device = false;
+        std::string host_why;
+        std::vector<std::pair<uint32_t, uint32_t>> tree_status;
+        uint32_t n_input = 0;
+        std::vector<uint32_t> fin;
     };
     struct Chunk {
         size_t words = 0, nshards = 0, leaf_words = 0, digest_words = 0, nred = 0, nstatus = 0;
@@ -85,6 +115,7 @@ class Batch {
         std::vector<Shard> shards;
         std::vector<Col> cols;
         std::vector<Fp4> ext;
+        MpTables mp;
     };
     struct Flight {
         bool active = false;
@@ -107,9 +138,12 @@ class Batch {
     std::vector<std::vector<uint8_t>> status;   // per chunk, in order
 };
 
-// test hooks (dvt_stage_sponge_rows, dvt_stage_verify_paths)
+// test hooks (dvt_stage_sponge_rows, dvt_stage_verify_paths, dvt_stage_verify_multipath)
 int stage_sponge_rows(const Lane &lane, const uint32_t *words, const uint32_t *lens, size_t n, uint32_t *digests);
 int stage_verify_paths(const Lane &lane, const dvt_path_chain *chains, size_t n, uint8_t *ok);
+int stage_verify_multipath(const Lane &lane, uint32_t depth, const uint32_t *leaf_index, const uint32_t *leaf_digest, size_t n,
+                           const uint8_t *inject_at, const uint32_t *inject, const uint32_t *nodes, size_t n_nodes, const uint32_t *root,
+                           uint8_t *ok);
 
 }  // namespace vq
 }  // namespace dvt

@@ -12,6 +12,9 @@
 //
 // Results.  One status byte per Merkle chain and one per query (the final value), written with plain stores; the host
 // scans them in the host verifier's order (shard, query, tree 0..3, layers in order, final value) and reports the first.
+// A compact shard (DVP2) has no chain: each of its trees is one job of vq_multipath_kernel, with one status byte per tree and
+// one per pair of digests that queries on a common node must agree on, scanned in verify_compact_queries' order (the input
+// trees, the FRI layers, then the final values).
 #include <algorithm>
 #include <chrono>
 
@@ -149,6 +152,97 @@ __global__ void __launch_bounds__(256) vq_path_kernel(const Chain *chains, uint3
     if (live && e == 0) status[c.status] = ((m >> (threadIdx.x & 48)) & 0xffffu) ? 0 : 1;
 }
 
+// (e) one workgroup per tree of a compact shard: all queries of the tree walk up together.  The nodes of the current level
+// and of the one above live in LDS as canonical words ([2][cap][8], cap <= MP_MAX_SLOTS: 64 KB at the reader's 1024
+// queries); one compression per 16-lane row as in the path kernel, rows looping over the level's jobs; one barrier per
+// level, whose trip counts come from the tree's tables and are uniform over the workgroup.  No workgroup waits for another.
+__global__ void __launch_bounds__(256) vq_multipath_kernel(const Tree *trees, const MpLevel *levels, const MpJob *jobs, const uint32_t *leaves,
+                                                           const MpCmp *cmps, uint32_t cap, const uint32_t *W, uint8_t *status) {
+    extern __shared__ uint32_t mp_nodes[];   // [2][cap][8]: at most 64 KB, which a launch may ask for without any function attribute
+    const Tree T = trees[blockIdx.x];
+    const uint32_t tid = threadIdx.x, e = tid & 15, row = tid >> 4;
+    const p2f::CoopConsts k = p2f::coop_consts(e);
+    for (uint32_t i = tid; i < T.ncmp; i += 256) {
+        const MpCmp c = cmps[T.cmp0 + i];
+        bool same = true;
+        for (int w = 0; w < 8; w++) same &= W[c.a + w] == W[c.b + w];
+        status[c.status] = same ? 1 : 0;
+    }
+    uint32_t *cur = mp_nodes, *up = mp_nodes + 8 * (size_t)cap;
+    for (uint32_t i = tid; i < 8 * T.nleaf; i += 256) cur[i] = W[leaves[T.leaf0 + (i >> 3)] + (i & 7)];
+    __syncthreads();
+    for (uint32_t lv = 0; lv < T.nlevels; lv++) {
+        const MpLevel L = levels[T.level0 + lv];
+        for (uint32_t base = 0; base < L.njobs; base += 16) {
+            const bool live = base + row < L.njobs;        // (uniform over the row; a dead row permutes zeros)
+            MpJob jb = {0, 0, NONE, 0};
+            if (live) jb = jobs[L.job0 + base + row];
+            const uint32_t src = e < 8 ? jb.l : jb.r;
+            const bool word = jb.dst & (e < 8 ? MP_L_WORD : MP_R_WORD);
+            double s = live ? p2f::from_canonical(word ? W[src + (e & 7)] : cur[8 * src + (e & 7)]) : 0.0;
+            s = p2f::coop_permute(s, k);
+            if (jb.inj != NONE) {
+                const double hs = p2f::from_canonical(W[jb.inj + (e & 7)]);
+                s = e < 8 ? s : hs;
+                s = p2f::coop_permute(s, k);
+            }
+            if (live && e < 8) up[8 * (jb.dst & MP_SLOT) + e] = p2f::to_canonical(s);
+        }
+        __syncthreads();
+        uint32_t *t = cur; cur = up; up = t;
+    }
+    if (tid == 0) {
+        bool same = T.nleaf != 0;
+        for (int w = 0; w < 8; w++) same &= cur[w] == W[T.root + w];
+        status[T.status] = same ? 1 : 0;
+    }
+}
+
+static_assert(2 * 32 * (size_t)MP_MAX_SLOTS <= 65536 && MP_MAX_SLOTS >= MAX_QUERIES && MP_MAX_SLOTS <= MP_SLOT + 1,
+              "the two levels of a tree fit the dynamic LDS of a plain launch, and a level has at most one node per query");
+
+// One tree of `depth` levels into the tables, from the shard's sources (one plan for all its trees).  digest_at(lh, q): the
+// word offset of query q's digest of height lh, or NONE where the tree has no rows of that height; listed0: the word offset
+// of the tree's first listed node; statuses are numbered from *nstatus on.  Returns the tree's status range [first, last]:
+// its comparisons, then the walk.
+template <class F>
+static std::pair<uint32_t, uint32_t> emit_tree(MpTables &mp, const TreeSources &ts, uint32_t depth, F digest_at, uint32_t listed0, uint32_t root,
+                                               size_t *nstatus) {
+    const MultipathPlan &pl = ts.plan;
+    const uint32_t base = pl.base[depth];
+    Tree T = {};
+    const uint32_t first = (uint32_t)*nstatus;
+    T.cmp0 = (uint32_t)mp.cmps.size();
+    for (uint32_t lh = 0; lh <= depth; lh++) {
+        if (ts.dups[lh].empty() || digest_at(lh, 0) == NONE) continue;   // (a tree has rows of a height for every query or for none)
+        for (auto &d : ts.dups[lh]) mp.cmps.push_back({digest_at(lh, d[0]), digest_at(lh, d[1]), (uint32_t)(*nstatus)++});
+    }
+    T.ncmp = (uint32_t)mp.cmps.size() - T.cmp0;
+    T.leaf0 = (uint32_t)mp.leaves.size();
+    T.nleaf = (uint32_t)pl.keys[depth].size();
+    for (uint32_t i = 0; i < T.nleaf; i++) mp.leaves.push_back(digest_at(depth, ts.first[depth][i]));
+    mp.cap = std::max(mp.cap, T.nleaf);
+    T.level0 = (uint32_t)mp.levels.size();
+    T.nlevels = depth;
+    for (uint32_t s = depth; s >= 1; s--) {
+        const auto &jobs = pl.levels[pl.depth - s];
+        mp.levels.push_back({(uint32_t)mp.jobs.size(), (uint32_t)jobs.size()});
+        const bool joins = digest_at(s - 1, 0) != NONE;
+        for (size_t i = 0; i < jobs.size(); i++) {
+            const MultipathJob &jb = jobs[i];
+            MpJob out = {jb.l, jb.r, joins ? digest_at(s - 1, ts.first[s - 1][i]) : NONE, (uint32_t)i};
+            if (jb.l & MP_LISTED) { out.l = listed0 + 8 * ((jb.l & ~MP_LISTED) - base); out.dst |= MP_L_WORD; }
+            if (jb.r & MP_LISTED) { out.r = listed0 + 8 * ((jb.r & ~MP_LISTED) - base); out.dst |= MP_R_WORD; }
+            mp.jobs.push_back(out);
+        }
+        mp.perms += jobs.size() * (1 + joins);
+    }
+    T.root = root;
+    T.status = (uint32_t)(*nstatus)++;
+    mp.trees.push_back(T);
+    return {first, T.status};
+}
+
 static Consts make_consts() {
     Consts k;
     for (uint32_t h = 0; h < 25; h++) k.gen[h] = two_adic_generator(h).v;
@@ -253,6 +347,7 @@ int Batch::add(const ShardQueryCtx &ctx, const uint32_t *words, size_t nwords, s
             mat_rel[t].push_back((uint32_t)(rel + 1));
             rel += 1 + mt.first;
         }
+        if (pf.compact) continue;   // (no path, not even its length)
         path_rel[t] = (uint32_t)(rel + 1);
         rel += 1 + 8 * (size_t)(ctx.shapes[t].mats.empty() ? 0 : ctx.shapes[t].log_h);
     }
@@ -261,7 +356,7 @@ int Batch::add(const ShardQueryCtx &ctx, const uint32_t *words, size_t nwords, s
     for (uint32_t k = 0; k + 1 < hmax; k++) {
         sib_rel[k] = (uint32_t)rel;
         lpath_rel[k] = (uint32_t)(rel + 5);
-        rel += 4 + 1 + 8 * (size_t)(hmax - k - 1);
+        rel += pf.compact ? 4 : 4 + 1 + 8 * (size_t)(hmax - k - 1);
     }
     const size_t qwords = rel;   // words of a query section that passes the shape checks
     uint32_t nslot = 0;
@@ -286,9 +381,20 @@ int Batch::add(const ShardQueryCtx &ctx, const uint32_t *words, size_t nwords, s
     // ---- the queries
     res.chunk = flushed;
     res.queries.resize(pf.queries.size());
+    res.compact = pf.compact;
+    if (pf.compact && !compact_shape_ok(ctx)) {
+        // nothing of this shard's queries goes to the device: the host names its first failure
+        res.host_why = verify_compact_queries(ctx);
+        times.flatten_ms += ms_since(t0);
+        return DVT_OK;
+    }
+    res.on_device = pf.compact;
+    // a compact shard: where each query's digests will be (relative to the digest area), for the trees below
+    std::vector<std::vector<uint32_t>> row_dig[4];
+    std::vector<std::vector<uint32_t>> leaf_dig(pf.compact ? pf.queries.size() : 0);
     for (uint32_t qi = 0; qi < pf.queries.size(); qi++) {
         QueryResult &qr = res.queries[qi];
-        if (!query_shape_ok(ctx, qi)) {
+        if (!pf.compact && !query_shape_ok(ctx, qi)) {
             // nothing of this query goes to the device: the host names its first failure (a shape, or a hash before it)
             qr.host_why = verify_query_host(ctx, qi);
             qr.on_device = false;
@@ -336,6 +442,7 @@ int Batch::add(const ShardQueryCtx &ctx, const uint32_t *words, size_t nwords, s
                 c.sponges.push_back(jb);
                 c.perms += (jb.total + 7) / 8;
             }
+            if (pf.compact) { row_dig[t].push_back(dig); continue; }
             Chain ch = {dig[sh.log_h], sh.log_h, idx & ((1u << sh.log_h) - 1), qbase + path_rel[t], (uint32_t)c.inj.size(), root_off[t],
                         (uint32_t)c.nstatus++, 1};
             for (uint32_t s = sh.log_h; s >= 1; s--) {
@@ -352,15 +459,35 @@ int Batch::add(const ShardQueryCtx &ctx, const uint32_t *words, size_t nwords, s
             c.segs.push_back({Q.leaf0 + 8 * k, 8 | LEAF_SEG});
             c.digest_words += 8;
             c.sponges.push_back(jb);
+            c.perms += 1;
+            if (pf.compact) { leaf_dig[qi].push_back(jb.out); continue; }
             Chain ch = {jb.out, lm - 1, (idx & ((1u << lm) - 1)) & (half - 1), qbase + lpath_rel[k], NONE, fri_root0 + 8 * k,
                         (uint32_t)c.nstatus++, 0};
             c.chains.push_back(ch);
-            c.perms += 1 + (lm - 1);
+            c.perms += lm - 1;
         }
-        qr.n_layer_chains = hmax - 1;
+        qr.n_layer_chains = pf.compact ? 0 : hmax - 1;
         Q.fin = (uint32_t)c.nstatus++;
+        if (pf.compact) res.fin.push_back(Q.fin);
         c.units0.push_back({(uint32_t)c.queries.size(), nslot});
         c.queries.push_back(Q);
+    }
+    if (pf.compact) {
+        // the node lists follow the queries: a count and its digests per tree, in the order the trees are walked here
+        for (int t = 0; t < 4; t++) {
+            const TreeShape &sh = ctx.shapes[t];
+            const uint32_t listed0 = sbase + (uint32_t)(off + 1);
+            off += 1 + 8 * pf.node_lists[t].size();
+            if (sh.mats.empty()) continue;
+            res.tree_status.push_back(emit_tree(c.mp, ctx.paths, sh.log_h, [&](uint32_t lh, uint32_t q) { return row_dig[t][q][lh]; }, listed0, root_off[t], &c.nstatus));
+            res.n_input++;
+        }
+        for (uint32_t k = 0; k + 1 < hmax; k++) {
+            const uint32_t depth = hmax - k - 1, listed0 = sbase + (uint32_t)(off + 1);
+            off += 1 + 8 * pf.node_lists[4 + k].size();
+            res.tree_status.push_back(emit_tree(c.mp, ctx.paths, depth, [&](uint32_t lh, uint32_t q) { return lh == depth ? leaf_dig[q][k] : NONE; }, listed0,
+                                                fri_root0 + 8 * k, &c.nstatus));
+        }
     }
     times.flatten_ms += ms_since(t0);
     if (off != nwords) return fail(lane.err, DVT_ERR_DEVICE, "internal: the layout walk of a shard proof ended at word %zu of %zu", off, nwords);
@@ -395,7 +522,8 @@ int Batch::flush() {
     std::vector<uint8_t> blob;
     const size_t at_sp = put(blob, c.sponges), at_seg = put(blob, c.segs), at_ch = put(blob, c.chains), at_inj = put(blob, c.inj),
                  at_aux = put(blob, c.aux), at_un = put(blob, units), at_q = put(blob, c.queries), at_sh = put(blob, c.shards),
-                 at_col = put(blob, c.cols), at_ext = put(blob, c.ext);
+                 at_col = put(blob, c.cols), at_ext = put(blob, c.ext), at_tr = put(blob, c.mp.trees), at_lv = put(blob, c.mp.levels),
+                 at_mj = put(blob, c.mp.jobs), at_lf = put(blob, c.mp.leaves), at_cm = put(blob, c.mp.cmps);
     const size_t up_words = (c.words + 3) & ~(size_t)3;
     const size_t tab_bytes = (blob.size() + 15) & ~(size_t)15;
     const size_t leaf0 = up_words + tab_bytes / 4;                 // word offsets of the scratch areas
@@ -418,6 +546,15 @@ int Batch::flush() {
     for (size_t i = 0; i < c.inj.size(); i++)
         if (ij[i] != NONE) ij[i] += (uint32_t)dig0;
     for (size_t i = 0; i < c.queries.size(); i++) qs[i].leaf0 += (uint32_t)leaf0;
+    {   // the trees of compact shards: leaves, joining digests and compared digests are in the digest area
+        MpJob *mj = reinterpret_cast<MpJob *>(tb + at_mj);
+        uint32_t *lf = reinterpret_cast<uint32_t *>(tb + at_lf);
+        MpCmp *cm = reinterpret_cast<MpCmp *>(tb + at_cm);
+        for (size_t i = 0; i < c.mp.jobs.size(); i++)
+            if (mj[i].inj != NONE) mj[i].inj += (uint32_t)dig0;
+        for (size_t i = 0; i < c.mp.leaves.size(); i++) lf[i] += (uint32_t)dig0;
+        for (size_t i = 0; i < c.mp.cmps.size(); i++) { cm[i].a += (uint32_t)dig0; cm[i].b += (uint32_t)dig0; }
+    }
 
     // ---- pinned staging: the words as they are, then the tables; the status bytes come back behind them
     const size_t up_bytes = up_words * 4 + tab_bytes;
@@ -463,12 +600,17 @@ int Batch::flush() {
     if (nq) vq_fold_kernel<<<(nq + 255) / 256, 256, 0, st>>>(d_q, nq, d_sh, reinterpret_cast<const uint32_t *>(T + at_aux), d_ext, d_red, W, consts(), d_status);
     if (ns) vq_sponge_kernel<<<(ns + 15) / 16, 256, 0, st>>>(reinterpret_cast<const Sponge *>(T + at_sp), ns, reinterpret_cast<const Seg *>(T + at_seg), W);
     if (nc) vq_path_kernel<<<(nc + 15) / 16, 256, 0, st>>>(reinterpret_cast<const Chain *>(T + at_ch), nc, reinterpret_cast<const uint32_t *>(T + at_inj), W, d_status);
+    const uint32_t nt = (uint32_t)c.mp.trees.size();
+    if (nt)
+        vq_multipath_kernel<<<nt, 256, 2 * 32 * (size_t)c.mp.cap, st>>>(reinterpret_cast<const Tree *>(T + at_tr), reinterpret_cast<const MpLevel *>(T + at_lv),
+                                                                       reinterpret_cast<const MpJob *>(T + at_mj), reinterpret_cast<const uint32_t *>(T + at_lf),
+                                                                       reinterpret_cast<const MpCmp *>(T + at_cm), c.mp.cap, W, d_status);
     HIP_TRY(lane.err, hipGetLastError());
     HIP_TRY(lane.err, hipEventRecord(slot.ev[2], st));
     if (c.nstatus) HIP_TRY(lane.err, hipMemcpyAsync(f.h_status, d_status, c.nstatus, hipMemcpyDeviceToHost, st));
     HIP_TRY(lane.err, hipEventRecord(slot.ev[3], st));
-    times.perms += c.perms;
-    times.launches += (nu != 0) + (nq != 0) + (ns != 0) + (nc != 0);
+    times.perms += c.perms + c.mp.perms;
+    times.launches += (nu != 0) + (nq != 0) + (ns != 0) + (nc != 0) + (nt != 0);
     times.chunks++;
     flushed++;
     reset_chunk();
@@ -504,6 +646,16 @@ int Batch::finish() {
 
 std::string Batch::why(size_t shard_slot) const {
     const ShardResult &r = results[shard_slot];
+    if (r.compact) {
+        if (!r.on_device) return r.host_why;
+        const uint8_t *s = status[r.chunk].data();
+        for (size_t t = 0; t < r.tree_status.size(); t++)
+            for (uint32_t i = r.tree_status[t].first; i <= r.tree_status[t].second; i++)
+                if (!s[i]) return t < r.n_input ? "Merkle opening rejected (input tree)" : "Merkle opening rejected (FRI layer)";
+        for (uint32_t f : r.fin)
+            if (!s[f]) return "FRI final value mismatch";
+        return "";
+    }
     for (auto &q : r.queries) {
         if (!q.on_device) {
             if (!q.host_why.empty()) return q.host_why;
@@ -594,6 +746,52 @@ int stage_verify_paths(const Lane &lane, const dvt_path_chain *chains, size_t n,
     HIP_TRY(lane.err, hipGetLastError());
     HIP_TRY(lane.err, hipStreamSynchronize(e.stream));
     HIP_TRY(lane.err, hipMemcpy(ok, base + wb + ib + cb, n, hipMemcpyDeviceToHost));
+    return DVT_OK;
+}
+
+int stage_verify_multipath(const Lane &lane, uint32_t depth, const uint32_t *leaf_index, const uint32_t *leaf_digest, size_t n,
+                           const uint8_t *inject_at, const uint32_t *inject, const uint32_t *nodes, size_t n_nodes, const uint32_t *root,
+                           uint8_t *ok) {
+    Engine &e = lane.eng;
+    const TreeSources ts = tree_sources(depth, std::vector<uint32_t>(leaf_index, leaf_index + n));
+    if (ts.plan.nodes.size() != n_nodes)
+        return fail(lane.err, DVT_ERR_INPUT, "%zu listed nodes, the indices ask for %zu", n_nodes, ts.plan.nodes.size());
+    // the word space: leaf digests [n][8], joining digests [depth][n][8], the listed nodes, the root
+    std::vector<uint32_t> w(leaf_digest, leaf_digest + 8 * n);
+    const uint32_t inj0 = (uint32_t)w.size();
+    if (inject_at) w.insert(w.end(), inject, inject + 8 * n * (size_t)depth);
+    const uint32_t listed0 = (uint32_t)w.size();
+    w.insert(w.end(), nodes, nodes + 8 * n_nodes);
+    const uint32_t root0 = (uint32_t)w.size();
+    w.insert(w.end(), root, root + 8);
+    for (size_t i = 0; i < w.size(); i++)
+        if (w[i] >= P) return fail(lane.err, DVT_ERR_INPUT, "a digest word is not canonical");
+    MpTables mp;
+    size_t nstatus = 0;
+    emit_tree(mp, ts, depth, [&](uint32_t lh, uint32_t q) {
+        if (lh == depth) return (uint32_t)(8 * q);
+        return inject_at && inject_at[lh] ? inj0 + 8 * (uint32_t)(lh * n + q) : NONE;
+    }, listed0, root0, &nstatus);
+    std::vector<uint8_t> blob;
+    const size_t at_w = put(blob, w), at_tr = put(blob, mp.trees), at_lv = put(blob, mp.levels), at_mj = put(blob, mp.jobs),
+                 at_lf = put(blob, mp.leaves), at_cm = put(blob, mp.cmps);
+    const size_t at_st = (blob.size() + 15) & ~(size_t)15;
+    StageBuf buf{e.pool};
+    HIP_TRY(lane.err, e.pool.alloc_bytes(&buf.ptr, at_st + nstatus));
+    uint8_t *base = static_cast<uint8_t *>(buf.ptr);
+    HIP_TRY(lane.err, hipStreamSynchronize(e.stream));
+    HIP_TRY(lane.err, hipMemcpy(base, blob.data(), blob.size(), hipMemcpyHostToDevice));
+    HIP_TRY(lane.err, hipMemset(base + at_st, 0, nstatus));
+    vq_multipath_kernel<<<1, 256, 2 * 32 * (size_t)mp.cap, e.stream>>>(reinterpret_cast<const Tree *>(base + at_tr), reinterpret_cast<const MpLevel *>(base + at_lv),
+                                                                     reinterpret_cast<const MpJob *>(base + at_mj), reinterpret_cast<const uint32_t *>(base + at_lf),
+                                                                     reinterpret_cast<const MpCmp *>(base + at_cm), mp.cap, reinterpret_cast<const uint32_t *>(base + at_w),
+                                                                     base + at_st);
+    HIP_TRY(lane.err, hipGetLastError());
+    HIP_TRY(lane.err, hipStreamSynchronize(e.stream));
+    std::vector<uint8_t> st(nstatus);
+    HIP_TRY(lane.err, hipMemcpy(st.data(), base + at_st, nstatus, hipMemcpyDeviceToHost));
+    *ok = 1;
+    for (uint8_t b : st) *ok &= b;
     return DVT_OK;
 }
 

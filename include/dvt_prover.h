@@ -58,6 +58,8 @@ typedef struct dvt_pk dvt_pk;
  * "verify_chunk_words" (default 4194304; 0 or less is DVT_ERR_INPUT): proof words per chunk of dvt_prover_verify's device
  * part.  Shards are gathered into a chunk until the next one would not fit; a single shard larger than the chunk goes
  * alone.  Answers do not depend on it (a test knob, like parts_parallel_log: small proofs reach the multi-chunk path).
+ * "compact_openings" (default 0): 1 makes every prove entry point write its shard proofs in the compact form (see
+ * dvt_proof_compact): the bytes dvt_proof_compact makes of the default proof, without gathering the shared paths.
  * "lanes" (1..3, default 2; without the key the environment variable DVT_LANES sets the default; anything else is
  * DVT_ERR_INPUT): prover lanes that run phase 2 of different shards of one job at the same time, each with its own HIP
  * stream, device arena and buffer cache.  The further lanes are created on the first job that holds at least two shards;
@@ -113,7 +115,8 @@ void dvt_free(void *ptr);
  * dvt_rv32_job_shard_chips; 7: dvt_prover_verify, dvt_prover_machine_verify, dvt_stage_sponge_rows,
  * dvt_stage_verify_paths, dvt_prover_verify_times; 8: dvt_stage_bus_ledger_*, dvt_rv32_job_bus_tuples;
  * 9: dvt_stage_hunt_cells, dvt_stage_hunt_pairs, dvt_rv32_hunt_shard, dvt_rv32_job_shard_chip_shape;
- * 10: dvt_stage_hunt_join_*, dvt_rv32_hunt_join_job) */
+ * 10: dvt_stage_hunt_join_*, dvt_rv32_hunt_join_job; 11: "compact_openings", dvt_proof_compact, dvt_proof_expand,
+ * dvt_stage_multipath_nodes, dvt_stage_verify_multipath, dvt_debug_compact_list_sweep) */
 uint32_t dvt_abi_version(void);
 /* the handle's hipStream_t (for event timing by the caller) */
 void *dvt_stream(dvt_prover *p);
@@ -417,6 +420,20 @@ typedef struct {
     const uint32_t *root;     /* [8] */
 } dvt_path_chain;
 int dvt_stage_verify_paths(dvt_prover *p, const dvt_path_chain *chains, size_t n, uint8_t *ok);
+/* The node rule of the compact proof form (see dvt_proof_compact), host only, pure index logic: the nodes that n queries
+ * at leaves indices[i] mod 2^depth of a tree of 2^depth leaves cannot compute themselves, as (level, index) pairs in
+ * out_level_index [2 * count] in the order of the wire format.  Level s has 2^s nodes, parents pair (i, i + 2^(s-1)).
+ * *n_out = count; at most `cap` pairs are written (out_level_index may be NULL with cap = 0).  depth <= 30. */
+int dvt_stage_multipath_nodes(uint32_t depth, const uint32_t *indices, size_t n, uint32_t *out_level_index, size_t cap, size_t *n_out);
+/* dvt_stage_verify_multipath: the tree kernel of the device verifier on one tree of 2^depth leaves whose n queries
+ * (n <= 1024, depth <= 30) walk up together.  Query i opens leaf leaf_index[i] mod 2^depth with the digest leaf_digest[i];
+ * with inject_at != NULL and inject_at[lh] != 0 (lh < depth) it also carries inject[lh][i], the row digest of the shorter
+ * matrices that join at level lh.  nodes [n_nodes][8]: the listed nodes in dvt_stage_multipath_nodes' order (another count
+ * than that function's is DVT_ERR_INPUT).  *ok = 1 when queries on a common node carry equal digests and the walk ends in
+ * root.  HOST arrays of canonical words, synchronous, as dvt_stage_verify_paths. */
+int dvt_stage_verify_multipath(dvt_prover *p, uint32_t depth, const uint32_t *leaf_index, const uint32_t *leaf_digest, size_t n,
+                               const uint8_t *inject_at, const uint32_t *inject, const uint32_t *nodes, size_t n_nodes,
+                               const uint32_t *root, uint8_t *ok);
 
 /* ------------------------------------------------- machine-level entry points
  * A "machine" is a fixed list of chips (AIRs) compiled into the library:
@@ -638,6 +655,29 @@ int dvt_verify(const uint8_t *vk, size_t vk_len, const uint8_t *proof, size_t pr
 int dvt_prover_verify(dvt_prover *p, const uint8_t *vk, size_t vk_len, const uint8_t *proof, size_t proof_len,
                       uint32_t fri_queries, uint32_t pow_bits, int32_t *exit_code, uint8_t **public_values,
                       size_t *pv_len, char **reason);
+/* The compact form of a proof.  A shard proof ("DVP1") carries one complete Merkle path per query and tree, and the
+ * queries of a shard share most of them; the compact form ("DVP2") carries every query's opened rows and FRI siblings as
+ * before, no path, and per tree (the four input trees, then the FRI layers) ONE list `u32 count, count digests` of the
+ * nodes the queries cannot compute from each other, in the order of dvt_stage_multipath_nodes ("Proof format").
+ * Every verify entry point reads both forms, and a container may mix them; a prover handle writes the compact form with
+ * "compact_openings": 1 in its config (default 0: the bytes of every proof as before).
+ * dvt_proof_compact / dvt_proof_expand turn a container (rv32 key) or a single machine-level shard proof into the other
+ * form.  Host only.  They run the verifier's host part per shard to obtain the query indices (a shard that fails it, or a
+ * malformed proof: DVT_ERR_REJECTED with the verifier's text in *reason) and do not check the openings: compact hashes
+ * nothing, expand recomputes the dropped siblings from the leaves upward.  For a proof P that verifies,
+ * expand(compact(P)) == P byte for byte, and compact(P) equals what the prover writes with "compact_openings": 1.  A
+ * proof that is already in the wanted form comes back unchanged.  *out via dvt_free. */
+int dvt_proof_compact(const uint8_t *vk, size_t vk_len, const uint8_t *proof, size_t proof_len, uint32_t fri_queries,
+                      uint32_t pow_bits, uint8_t **out, size_t *out_len, char **reason);
+int dvt_proof_expand(const uint8_t *vk, size_t vk_len, const uint8_t *proof, size_t proof_len, uint32_t fri_queries,
+                     uint32_t pow_bits, uint8_t **out, size_t *out_len, char **reason);
+/* test hook, host only: every word of every node list of every compact shard of a container changed by +1 mod p, one at a
+ * time, and the query part of that shard's tree verified again.  The host part of a shard reads no node list (the query
+ * indices come from the transcript), so it runs once per shard instead of once per changed word; the container itself
+ * must verify (else DVT_ERR_REJECTED with the text).  *n_words: the words changed; *n_accepted: the changes after which the
+ * tree was still accepted (0 for a sound verifier).  Plain shards are skipped. */
+int dvt_debug_compact_list_sweep(const uint8_t *vk, size_t vk_len, const uint8_t *proof, size_t proof_len, uint32_t fri_queries,
+                                 uint32_t pow_bits, uint64_t *n_words, uint64_t *n_accepted, char **reason);
 /* measurement hook: the last dvt_prover_verify / dvt_prover_machine_verify of this handle in milliseconds.  out[0] = the
  * host part (parse, transcript, zeta check), out[1] = flattening into pinned staging, out[2] = uploads, out[3] = kernels,
  * out[4] = downloads (2..4: HIP events, summed over the chunks), out[5] = host time spent waiting for the device,

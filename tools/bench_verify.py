@@ -1,12 +1,13 @@
 """Host verifier against device verifier on the same proof bytes: capi.verify (one host thread) and Prover.verify (the
 query part on the GPU), in alternating pairs.
 
-  python tools/bench_verify.py [--pairs 3] [--calls 5] [--jobs default,reference,n255]
+  python tools/bench_verify.py [--pairs 3] [--calls 5] [--jobs default,reference,n255] [--compact]
 
 One JSON line per job: the medians per pair, the host call's run-to-run spread, the split of the device call (host part /
 flatten / upload / kernels / download / waiting) and the Poseidon2 permutation count.  The jobs: bench.py's default
 container (32 shards of 2^21 cycles), the reference example (one short, wide shard: tools/bench_reference_guest.py) and
-the --participants 255 --sha-precompiles --curve-precompiles job of bench.py."""
+the --participants 255 --sha-precompiles --curve-precompiles job of bench.py.  With --compact the proof is turned into the
+compact form first (capi.proof_compact; "plain_bytes" is the size it had): the same job in both forms is two runs."""
 import argparse
 import json
 import os
@@ -39,12 +40,17 @@ def make_job(name, prover):
     return vk, proof, rep
 
 
-def measure(name, prover, pairs, calls):
+def measure(name, prover, pairs, calls, compact=False):
     from dvt_circuits_amd import capi
 
     vk, proof, rep = make_job(name, prover)
+    plain_bytes = len(proof)
+    if compact:
+        plain = proof
+        proof = capi.proof_compact(vk, plain)
+        assert capi.verify(vk, proof) == capi.verify(vk, plain) and capi.proof_expand(vk, proof) == plain
     assert prover.verify(vk, proof) == capi.verify(vk, proof) and capi.verify(vk, proof)[0]   # (and warms both paths)
-    out = {"job": name, "shards": len(capi.split_container(proof)[2]), "proof_bytes": len(proof), "cycles": rep["cycles"], "pairs": []}
+    out = {"job": name, "shards": len(capi.split_container(proof)[2]), "proof_bytes": len(proof), "plain_bytes": plain_bytes, "compact": compact, "cycles": rep["cycles"], "pairs": []}
     for _ in range(pairs):
         host, dev, split = [], [], []
         for _ in range(calls):
@@ -71,12 +77,13 @@ def main():
     ap.add_argument("--calls", type=int, default=5)
     ap.add_argument("--jobs", default="default,reference,n255")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--compact", action="store_true")
     args = ap.parse_args()
     from dvt_circuits_amd import capi
 
     for name in args.jobs.split(","):
         prover = capi.Prover('{"device": %d, "fri_queries": 100, "pow_bits": 16}' % args.device)
-        print(json.dumps(measure(name, prover, args.pairs, max(5, args.calls))), flush=True)
+        print(json.dumps(measure(name, prover, args.pairs, max(5, args.calls), args.compact)), flush=True)
         prover.close()
 
 
