@@ -141,6 +141,10 @@ def load():
     lib.dvt_execute_io.argtypes = [C.c_char_p, sz, C.POINTER(Buf), sz, C.c_uint64, C.POINTER(u8p), C.POINTER(sz), C.POINTER(u8p), C.POINTER(sz), C.POINTER(Report), C.POINTER(C.c_char_p)]
     lib.dvt_debug_exec_rate.argtypes = [C.c_char_p, sz, C.POINTER(Buf), sz, u32, C.c_int]
     lib.dvt_debug_exec_rate.restype = C.c_double
+    lib.dvt_debug_p2_f64_selfcheck.argtypes = [u32, u32]
+    lib.dvt_debug_p2_f64_selfcheck.restype = u64
+    lib.dvt_debug_p2_f64_sbox_check.argtypes = [u32, u32, C.POINTER(C.c_double)]
+    lib.dvt_debug_p2_f64_sbox_check.restype = u64
     lib.dvt_prove_core.argtypes = [vp, vp, C.POINTER(Buf), sz, C.POINTER(u8p), C.POINTER(sz), C.POINTER(Report)]
     lib.dvt_verify.argtypes = [C.c_char_p, sz, C.c_char_p, sz, u32, u32, C.POINTER(C.c_int32), C.POINTER(u8p), C.POINTER(sz), C.POINTER(C.c_char_p)]
     lib.dvt_rv32_prepare.argtypes = [vp, vp, C.POINTER(Buf), sz, C.POINTER(vp), C.POINTER(Report)]
@@ -347,6 +351,19 @@ def execute(elf: bytes, stdin=(), max_cycles=0):
 def exec_rate(elf: bytes, stdin=(), log_shard=21, trace=False) -> float:
     """guest cycles / second of the host executor alone (fast or trace mode)"""
     return float(load().dvt_debug_exec_rate(elf, len(elf), _bufs(stdin), len(stdin), log_shard, int(trace)))
+
+
+def p2_f64_selfcheck(n: int, seed: int) -> int:
+    """FP64 Poseidon2 (host evaluation) against the integer permutation on n states: the number of differing words"""
+    return int(load().dvt_debug_p2_f64_selfcheck(n, seed))
+
+
+def p2_f64_sbox_check(n: int, seed: int):
+    """FP64 S-box against x^7 mod p on n random inputs of its input range plus edge values:
+    (mismatches, [max |x2|, max |x3|, max |x4|, max |x7|])"""
+    mx = (C.c_double * 4)()
+    bad = load().dvt_debug_p2_f64_sbox_check(n, seed, mx)
+    return int(bad), [float(v) for v in mx]
 
 
 def execute_io(elf: bytes, stdin=(), max_cycles=0):

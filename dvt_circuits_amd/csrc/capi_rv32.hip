@@ -1473,4 +1473,36 @@ uint64_t dvt_debug_p2_f64_selfcheck(uint32_t n, uint32_t seed) {
     return bad;
 }
 
+// test hook (host only): p2f::sbox against x^7 mod p in integer arithmetic, on n pseudo-random integers of
+// [-SBOX_IN, SBOX_IN] and on the edge families +-(2^e + d) (e = 20..36), m p + d (|m| <= 36) and m (p - 1)/2 + d
+// (|m| <= 72), |d| <= 2000, clamped to the input bound (none is skipped).  Returns the number of inputs whose result is not an integer
+// congruent to x^7; max_abs = the largest |x2|, |x3|, |x4|, |x7| met (the bounds stated at sbox).
+uint64_t dvt_debug_p2_f64_sbox_check(uint32_t n, uint32_t seed, double *max_abs) {
+    uint64_t bad = 0, s = 0x9e3779b97f4a7c15ull ^ seed;
+    double mx[4] = {0, 0, 0, 0};
+    const int64_t lim = (int64_t)p2f::SBOX_IN;
+    auto check = [&](int64_t xi) {
+        xi = xi > lim ? lim : xi < -lim ? -lim : xi;
+        double v[4];
+        v[3] = p2f::sbox_steps((double)xi, v[0], v[1], v[2]);
+        for (int k = 0; k < 4; k++) mx[k] = fmax(mx[k], fabs(v[k]));
+        const uint64_t x = (uint64_t)((xi % (int64_t)P + (int64_t)P) % (int64_t)P);
+        const uint64_t x2 = x * x % P, x3 = x2 * x % P, x4 = x2 * x2 % P, want = x3 * x4 % P;
+        // (an inexact step leaves a non-integer or a value far outside the bound: the cast must stay defined)
+        const bool sane = fabs(v[3]) < 9e15 && v[3] == floor(v[3]);
+        bad += !sane || (uint64_t)(((int64_t)v[3] % (int64_t)P + (int64_t)P) % (int64_t)P) != want;
+    };
+    for (uint32_t t = 0; t < n; t++) {
+        s ^= s << 13; s ^= s >> 7; s ^= s << 17;
+        check((int64_t)(s % (2 * (uint64_t)lim + 1)) - lim);
+    }
+    for (int64_t d = -2000; d <= 2000; d++) {
+        for (int e = 20; e <= 36; e++) { check(((int64_t)1 << e) + d); check(-(((int64_t)1 << e) + d)); }
+        for (int64_t m = -36; m <= 36; m++) check(m * (int64_t)P + d);
+        for (int64_t m = -72; m <= 72; m++) check(m * (((int64_t)P - 1) / 2) + d);
+    }
+    for (int k = 0; k < 4; k++) max_abs[k] = mx[k];
+    return bad;
+}
+
 }  // extern "C"

@@ -13,9 +13,10 @@
 // relation natural-order FRI folding needs) and both child reads are coalesced.
 //
 // ALU-bound (141 S-boxes = 564 modular products per permutation, one permutation per 8 input words), not
-// HBM-bound.  The permutation runs on the FP64 pipe (poseidon2_f64.cuh: exact integers in doubles, 6 full-rate
-// operations per product instead of 3 quarter-rate integer multiplies); states stay in doubles between the
-// permutations of one sponge and are converted from / to the Montgomery words of HBM at the edges.
+// HBM-bound.  The permutation runs on the FP64 pipe (poseidon2_f64.cuh: exact integers in doubles; an S-box is 19
+// full-rate operations - two full products of 5, two partially reduced ones of 3, three quotient factors - instead of
+// 12 quarter-rate integer multiplies); states stay in doubles between the permutations of one sponge and are
+// converted from / to the Montgomery words of HBM at the edges.
 #include <utility>
 
 #include "kernels.h"

@@ -3,8 +3,8 @@
 //
 // Why: v_mul_lo/hi_u32 issue at quarter rate on gfx950 and a Montgomery product needs three of them, which
 // bounds the integer permutation at about 4.5 Gperm/s per GPU (measured, tools/microbench).  v_fma_f64 issues at
-// full rate, a modular product costs six FP64 operations and additions need no reduction at all, which measures
-// 6.5 Gperm/s for the same function.  (No MFMA: nothing here is a contraction.)
+// full rate, a modular product costs three to six FP64 operations and additions need no reduction at all.  (No
+// MFMA: nothing here is a contraction.)
 //
 // How: a field element is an INTEGER carried in a double, congruent mod p to the value, of bounded magnitude
 // ("lazy").  Integers below 2^53 are exact in a double, an FMA rounds once, so every step below is exact integer
@@ -44,8 +44,11 @@ constexpr double MONT_RINV = 943718400.0;     // 2^-32 mod p
 // unit precision (its result lies in [2^52, 2^53)), i.e. to the nearest integer; subtracting the constant is exact.
 // (v_mul_f64 + v_rndne_f64 is the same instruction count and measures the same within 1 %.)  Every quotient estimate
 // below is such a rounded product; an estimate off by one only moves the representative by p, inside the stated bounds.
-// Instruction budget of one permutation (gfx950 ISA of the bare kernel): 4 854 FP64 operations + 117 moves; at four
-// issue cycles per wave64 operation that is 19.9 k cycles per wave, measured 20.5 k: the permutation is issue-bound.
+// Instruction budget of one permutation: 141 S-boxes of 19 operations (sbox below) + 141 round-constant additions
+// + 1 294 operations of the linear layers and reductions = 4 114 FP64 operations in the source.  The gfx950 ISA of the
+// bare kernel's loop (tools/microbench, which reduces the state once more per call) has 4 274 FP64 instructions among
+// 4 989 vector ones (119 of them v_mov_b64); at four issue cycles per wave64 instruction that is 20.0 k cycles per wave,
+// and 8.05 Gperm/s measured is 19.5 k at the nominal 2.4 GHz: the permutation is issue-bound.
 constexpr double MAGIC = 6755399441055744.0;  // 1.5 * 2^52
 DVT_DEV double rnd_prod(double a, double b) { return fma(a, b, MAGIC) - MAGIC; }
 DVT_DEV double mm(double a, double b) {
@@ -63,20 +66,58 @@ DVT_DEV uint32_t fix(double r) { return (uint32_t)(r < 0.0 ? r + PD : r); }
 DVT_DEV uint32_t to_canonical(double x) { return fix(red(x)); }       // |x| < 2^48
 
 // a * b mod p with bp = b / p (rounded) supplied: q = round(a * bp), then a b - q p = (a b - q (p - 1)) - q, where
-// q (p - 1) = 15 q * 2^27 is exact in a double and the FMA result (|r + q| < 2^42) is exact: 5 operations, no error
-// term.  Same bounds as mm.  Worth it where one bp serves several products (the S-box: 23 operations instead of 24).
+// q (p - 1) = 15 q * 2^27 is exact in a double and the FMA result (the integer r + q, |r + q| < 2^50) is exact: 5 operations, no error
+// term.  Needs 15 q < 2^53, which |a b| < 2^80 gives (2^80 / p < 2^53 / 15 because 15 * 2^27 < p).  With
+// bp = RN(b * PINV) the estimate a * bp is a b / p (1 + e), |e| <= PINV_REL, so |r| <= (1/2 + |a b| / p * PINV_REL) p:
+// 0.5004 p for |a b| <= 2^72.2, 0.573 p for |a b| <= 2^79.82.  Worth it where one bp serves several products.
 constexpr double P_MINUS_1 = 2013265920.0;
+// relative error of RN(b * PINV) against b / p: 2^-53 of the product's rounding + 2^-55.08 (the error of PINV itself, a
+// property of this p) and their product: below 2^-52.69
+constexpr double PINV_REL = 1.3718e-16;
 DVT_DEV double mm_pre(double a, double b, double bp) {
     const double q = rnd_prod(a, bp);
     return fma(a, b, -(q * P_MINUS_1)) - q;
 }
 DVT_DEV double from_mont(uint32_t m) { return mm_pre((double)m, MONT_RINV, MONT_RINV / PD); }
 DVT_DEV uint32_t to_mont(double x) { return fix(mm_pre(x, MONT_R, MONT_R / PD)); }      // |x| < 2^48
-DVT_DEV double sbox(double x) {  // |x| < 2^38
+// a * b reduced only to a multiple of 2^K p, in 3 operations, for products whose result feeds one more product and
+// nothing else.  bp = b / p as for mm_pre.  Adding MK = 1.5 * 2^(52+K) rounds the quotient estimate at unit 2^K:
+// qm = MK + q with q a multiple of 2^K, |q - a bp| <= 2^(K-1) (needs |q| < 2^(51+K)).  qm p - MK p = q p is one FMA
+// and exact when q p is representable, i.e. (q / 2^K) p < 2^53; MK p = 3 p 2^(51+K) is (3 p < 2^33).  The last FMA
+// yields the integer a b - q p, below 2^53: exact.
+//   Needs |a b| / p (1 + PINV_REL) + 2^(K-1) <= 2^(53+K) / p, which |a b| <= 2^(52.99+K) gives.
+//   |r| <= (2^(K-1) + |a b| / p * PINV_REL) p  <=  (2^(K-1) + 2^-16) p  under that precondition.
+// (mm_pre cannot take this route: at K = 0 the product q p has up to 80 bits, hence its detour over q (p - 1).)
+template <int K>
+DVT_DEV double mm_c(double a, double b, double bp) {
+    constexpr double MK = 1.5 * (double)(1ull << 52) * (double)(1ull << K);
+    constexpr double MKP = MK * PD;
+    const double qm = fma(a, bp, MK);
+    const double t = fma(qm, PD, -MKP);
+    return fma(a, b, -t);
+}
+
+// x^7 in 19 operations (1 + 5 + 3 + 1 + 3 + 1 + 5): x^3 and x^4 feed only the last product and are reduced partially.
+//   in : |x| <= SBOX_IN = 36 p (2^36.08)
+//   x2 : |x x| <= 1296 p^2 = 2^72.16                          ->  |x2| <= 0.5004 p = 2^29.908        (mm_pre)
+//   x3 : |x2 x| <= 0.5004 * 36 p^2 = 2^65.985 <= 2^65.99      ->  |x3| <= (2^12 + 2^-16) p = 2^42.907  (mm_c<13>)
+//   x4 : |x2 x2| <= 0.2505 p^2 = 2^59.817 <= 2^59.99          ->  |x4| <= (2^6 + 2^-16) p = 2^36.907   (mm_c<7>)
+//   out: |x3 x4| <= (2^18 + 2^-3) p^2 = 2^79.814 < 2^80       ->  |x7| <= SBOX_OUT = 0.573 p (2^30.10) (mm_pre)
+// The granularities are not free: K = 14 for x3 or K = 8 for x4 puts the last product beyond 2^80, K = 12 / K = 6 makes
+// q p of the partial product inexact at these magnitudes.  dvt_debug_p2_f64_sbox_check compares this function with x^7 mod p
+// in integer arithmetic over the whole input range and reports the largest intermediates (tests/test_p2_f64_sbox_host.py).
+constexpr double SBOX_IN = 36.0 * PD;
+constexpr double SBOX_OUT = 0.573 * PD;
+DVT_DEV double sbox_steps(double x, double &x2, double &x3, double &x4) {
     const double xp = x * PINV;
-    const double x2 = mm_pre(x, x, xp), x3 = mm_pre(x2, x, xp);
-    const double x2p = x2 * PINV, x4 = mm_pre(x2, x2, x2p);
+    x2 = mm_pre(x, x, xp);
+    x3 = mm_c<13>(x2, x, xp);
+    x4 = mm_c<7>(x2, x2, x2 * PINV);
     return mm_pre(x3, x4, x4 * PINV);
+}
+DVT_DEV double sbox(double x) {
+    double x2, x3, x4;
+    return sbox_steps(x, x2, x3, x4);
 }
 
 // max |s| = B  ->  <= 35 B
@@ -129,11 +170,17 @@ DVT_DEV void internal_layer(double s[16]) {
     s[15] = sum - s[15];
 }
 
-// in: |s_i| < 2^32 (canonical words, from_mont results or a previous output); out: |s_i| < 0.51 p.
-// Magnitudes: after an S-box layer every entry is below 0.51 p (2^30.03), the external layer multiplies the bound
-// by 35 (2^35.2, the S-box input bound with a round constant added); in the internal rounds s[0] is reduced before
-// each S-box and the other entries every third round: 2^35.2 -> x25 -> 2^39.8 -> 2^44.5 -> reduce, and from a
-// reduced state 2^30 -> 2^34.7 -> 2^39.3 -> 2^44 (< 2^48 as the sums need).
+// in: |s_i| <= p (canonical words, from_mont results or a previous output; NOT any 32-bit word: the first S-box layer
+// needs 35 |s_i| + p/2 <= SBOX_IN); out: |s_i| < 0.51 p (reduced).
+// Magnitudes (round constants are centred, |rc| < p/2):
+//   first layer           35 p + p/2 = 35.5 p                                        <= SBOX_IN
+//   external rounds       an S-box layer leaves SBOX_OUT = 0.573 p, the external layer multiplies by 35: 20.06 p
+//                         (2^35.24); with the round constant 20.6 p                  <= SBOX_IN
+//   internal rounds       s[0] is reduced before each S-box (|red + rc| <= p), the other entries at r = 2, 5, 8, 11:
+//                         20.06 p -> x25 -> 502 p (2^39.9) -> x25 -> 12 540 p (2^44.6) -> reduce; from a reduced
+//                         state (s[0] <= 0.573 p, the others <= p/2) 14.4 p (2^34.8) -> 2^39.4 -> 2^44.1 -> reduce;
+//                         all below 2^48 as red and the sums need.  After r = 12: 2^39.4, then every entry reduced.
+//   last external rounds  |red + rc| <= p for the first, then as above; the final red leaves |s_i| <= p/2 + 2^-8.
 DVT_DEV void permute(double s[16]) {
     external_layer(s);
 #pragma unroll
@@ -199,7 +246,8 @@ __device__ __forceinline__ double coop_external_layer(double x) {
     a = a + dpp_mov<DPP_ROW_ROR + 4>(a);
     return y + a;
 }
-// in: |s| < 2^32; out: |s| < 0.51 p (every lane of the row must be active)
+// in: |s| <= p; out: |s| < 0.51 p (every lane of the row must be active).  The external rounds are those of permute;
+// the internal rounds reduce every entry every round, so each S-box sees |s + rc| <= p.
 __device__ __forceinline__ double coop_permute(double s, const CoopConsts &k) {
     s = coop_external_layer(s);
 #pragma unroll
@@ -214,7 +262,7 @@ __device__ __forceinline__ double coop_permute(double s, const CoopConsts &k) {
         t = t + dpp_mov<DPP_ROW_ROR + 2>(t);
         t = t + dpp_mov<DPP_ROW_ROR + 1>(t);
         // every diagonal entry is a small integer and s is reduced: the fused multiply-add is exact
-        s = red(fma(s, k.diag, t));                      // every entry stays reduced: |sum| <= 16 * 0.51 p
+        s = red(fma(s, k.diag, t));                      // every entry stays reduced: |t| <= 15 p/2 + SBOX_OUT, |s diag| <= 9 p/2
     }
 #pragma unroll
     for (int r = 4; r < 8; r++) s = coop_external_layer(sbox(s + k.rc[r]));

@@ -690,6 +690,10 @@ double dvt_debug_exec_rate(const uint8_t *elf, size_t elf_len, const dvt_buf *st
 /* test hook, host only: FP64 formulation of Poseidon2 (csrc/poseidon2_f64.cuh, what the hashing kernels run)
  * against the integer permutation on n states; returns the number of differing words (0 = identical) */
 uint64_t dvt_debug_p2_f64_selfcheck(uint32_t n, uint32_t seed);
+/* test hook, host only: the S-box of that formulation (x^7 with partially reduced x^3 and x^4) against integer arithmetic
+ * on n pseudo-random inputs over its whole stated input range and on edge values; returns the number of wrong results.
+ * max_abs[4] = the largest |x^2|, |x^3|, |x^4|, |x^7| representatives met, which its exactness conditions bound. */
+uint64_t dvt_debug_p2_f64_sbox_check(uint32_t n, uint32_t seed, double *max_abs);
 /* test hook, host only: the bus ledger's key of a tuple (csrc/ledger_key.h: the function the kernels key the rows with) */
 uint64_t dvt_debug_ledger_key(uint64_t seed, uint32_t bus, uint32_t arity, const uint32_t *values);
 
