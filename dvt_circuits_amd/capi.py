@@ -167,6 +167,9 @@ def load():
     lib.dvt_rv32_prove_shard.argtypes = [vp, vp, vp, sz, u32p, C.POINTER(u8p), C.POINTER(sz)]
     lib.dvt_rv32_assemble.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(sz), sz, C.POINTER(u8p), C.POINTER(sz)]
     lib.dvt_rv32_debug_device_traces.argtypes = [vp, vp, vp, sz, C.POINTER(u32p), C.POINTER(sz)]
+    prof_out = [C.POINTER(u64), sz, C.POINTER(ProfileEdge), sz, C.POINTER(ProfileSyscall), sz, C.POINTER(ProfileOpcode), sz, C.POINTER(ProfileSummary)]
+    lib.dvt_rv32_job_profile.argtypes = [vp, vp, vp, u32] + prof_out
+    lib.dvt_execute_profile.argtypes = [C.c_char_p, sz, C.POINTER(Buf), sz, u64] + prof_out + [C.POINTER(Report), C.POINTER(C.c_char_p)]
     lib.dvt_stdin_from_json.argtypes = [C.c_char_p, C.c_char_p, sz, C.c_int, C.POINTER(u8p), C.POINTER(sz), C.POINTER(C.c_char_p)]
     _lib = lib
     return lib
@@ -346,6 +349,58 @@ def execute(elf: bytes, stdin=(), max_cycles=0):
     if pv:
         lib.dvt_free(C.cast(pv, C.c_void_p))
     return rc, dict(cycles=rep.cycles, exit_code=rep.exit_code, halted=bool(rep.halted), unprovable=bool(rep.unprovable)), out, _take_str(lib, err)
+
+
+class ProfileEdge(C.Structure):
+    _fields_ = [("from_pc", C.c_uint32), ("to_pc", C.c_uint32), ("count", C.c_uint64)]
+
+
+class ProfileSyscall(C.Structure):
+    _fields_ = [("id", C.c_uint32), ("pad", C.c_uint32), ("count", C.c_uint64)]
+
+
+class ProfileOpcode(C.Structure):
+    _fields_ = [("name", C.c_char * 8), ("count", C.c_uint64)]
+
+
+class ProfileSummary(C.Structure):
+    _fields_ = [("cycles", C.c_uint64), ("n_transfers", C.c_uint64), ("dropped_transfers", C.c_uint64), ("text_base", C.c_uint32),
+                ("n_instr", C.c_uint32), ("n_edges", C.c_uint32), ("n_syscalls", C.c_uint32), ("n_opcodes", C.c_uint32),
+                ("shards_tallied", C.c_uint32), ("shards_total", C.c_uint32), ("ms", C.c_float)]
+
+
+def _profile(call):
+    """The execution report through call(pc_count, cap_pc, edges, cap_edges, sys, cap_sys, ops, cap_ops, summary) -> rc: once
+    for the sizes, once for the tables.  Returns (rc, report), report = None when the first call fails without a summary,
+    else dict(summary, pc_count (numpy u64), edges = [(from_pc, to_pc, count)], syscalls = {id: count}, opcodes = {name: count})."""
+    s = ProfileSummary()
+    rc = call(None, 0, None, 0, None, 0, None, 0, C.byref(s))
+    if rc not in (DVT_OK, DVT_ERR_GUEST):
+        return rc, None
+    pc = np.zeros(max(int(s.n_instr), 1), np.uint64)
+    edges, sys_, ops = (ProfileEdge * max(int(s.n_edges), 1))(), (ProfileSyscall * max(int(s.n_syscalls), 1))(), (ProfileOpcode * max(int(s.n_opcodes), 1))()
+    rc = call(pc.ctypes.data_as(C.POINTER(C.c_uint64)), int(s.n_instr), edges, int(s.n_edges), sys_, int(s.n_syscalls), ops, int(s.n_opcodes), C.byref(s))
+    if rc not in (DVT_OK, DVT_ERR_GUEST):
+        return rc, None
+    summary = {name: (float if name == "ms" else int)(getattr(s, name)) for name, _ in ProfileSummary._fields_}
+    return rc, dict(summary=summary, pc_count=pc[:int(s.n_instr)],
+                    edges=[(int(e.from_pc), int(e.to_pc), int(e.count)) for e in edges[:int(s.n_edges)]],
+                    syscalls={int(e.id): int(e.count) for e in sys_[:int(s.n_syscalls)]},
+                    opcodes={e.name.decode(): int(e.count) for e in ops[:int(s.n_opcodes)]})
+
+
+def execute_profile(elf: bytes, stdin=(), max_cycles=0):
+    """Host-only execution report (dvt_execute_profile): the guest in trace mode, tallied shard by shard.  Returns (rc, report
+    dict as execute() gives it, profile dict as Prover.job_profile gives it or None, error text)."""
+    lib = load()
+    rep, err, bufs = Report(), C.c_char_p(), _bufs(stdin)
+
+    def call(*out):
+        if err.value:
+            lib.dvt_free(C.cast(err, C.c_void_p))
+        return lib.dvt_execute_profile(elf, len(elf), bufs, len(stdin), max_cycles, *out, C.byref(rep), C.byref(err))
+    rc, prof = _profile(call)
+    return rc, dict(cycles=rep.cycles, exit_code=rep.exit_code, halted=bool(rep.halted), unprovable=bool(rep.unprovable)), prof, _take_str(lib, err)
 
 
 def exec_rate(elf: bytes, stdin=(), log_shard=21, trace=False) -> float:
@@ -976,6 +1031,15 @@ class Prover:
         found = [dict(shard=int(f.shard), chip=int(f.chip), log_n=int(f.log_n), violations=int(f.r.violations), first_row=int(f.r.first_row),
                       first_constraint=int(f.r.first_constraint)) for f in arr[:min(int(s.n_findings), cap)]]
         return summary, found
+
+    def job_profile(self, pk, job, log_edge_slots=0):
+        """The execution report of a prepared job, tallied on the GPU from the cycle records of the shards it holds
+        (dvt_rv32_job_profile): dict(summary, pc_count (numpy u64, one per instruction of the text), edges = [(from_pc, to_pc,
+        count)] sorted, syscalls = {id: count}, opcodes = {mnemonic: count}).  log_edge_slots bounds the table of the indirect
+        edges (0 = sized from the text); what it cannot hold is counted in summary["dropped_transfers"]."""
+        rc, prof = _profile(lambda *out: self.lib.dvt_rv32_job_profile(self.h, pk, job, log_edge_slots, *out))
+        self.check(rc)
+        return prof
 
     def bus_ledger(self, machine, log_buckets=20, cap_slots=1 << 16, seed=1):
         """a BusLedger on this handle: which tuples of the LogUp buses do not cancel over the tables it is given"""

@@ -1,10 +1,12 @@
 // The inspectors of trace rows of the C ABI (include/dvt_prover.h): row checks, bus ledger, forgery hunt, join hunt.  Each has
 // stage entry points (dvt_stage_*) on a table the caller uploaded (stage_table) and job entry points (dvt_rv32_*) on the
-// tables of a prepared job's held shards (shard_view).
+// tables of a prepared job's held shards (shard_view).  The execution report (profile.h) is the one inspector that reads a
+// job's cycle records instead of its tables.
 #include <algorithm>
 
 #include "capi_job.h"
 #include "ledger_key.h"
+#include "profile.h"
 #include "sha256.h"
 
 using namespace dvt;
@@ -262,7 +264,130 @@ static int job_bus_tuples(dvt_prover *p, const dvt_pk *pk, dvt_job *j, dvt_bus_t
     return DVT_OK;
 }
 
+// ------------------------------------------------------------------ the execution report (dvt_rv32_job_profile)
+// One member's share: its tables from lane 0's pool (counts zeroed, keys all ones), one launch per shard it holds on lane 0's
+// stream, one download (which synchronises), everything added into *t.  The buffer goes back to the pool at scope exit.
+static int member_profile(const Lane &c, const dvt_pk *pk, JobPart &part, uint32_t log_slots, const std::vector<uint32_t> &classes, prof::Tally *t) {
+    if (part.shards.empty()) return DVT_OK;
+    Engine &e = c.eng;
+    const size_t n = classes.size(), S = (size_t)1 << log_slots;
+    // 64-bit words: pc_count, taken, edge counts, syscall counts, counters | edge keys, syscall keys; then the classes
+    const size_t zero_words = 2 * n + S + prof::MAX_SYSCALLS + PROFILE_COUNTERS, key_words = S + prof::MAX_SYSCALLS;
+    StageBuf buf{e.pool};
+    HIP_TRY(c.err, e.pool.alloc_bytes(&buf.ptr, (zero_words + key_words) * 8 + n * 4));
+    unsigned long long *d = static_cast<unsigned long long *>(buf.ptr);
+    ProfileTables tb{};
+    tb.pc_count = d; tb.taken = d + n; tb.edge_counts = d + 2 * n; tb.sys_counts = tb.edge_counts + S; tb.counters = tb.sys_counts + prof::MAX_SYSCALLS;
+    tb.edge_keys = d + zero_words; tb.sys_keys = tb.edge_keys + S;
+    uint32_t *d_classes = reinterpret_cast<uint32_t *>(d + zero_words + key_words);
+    tb.classes = d_classes; tb.n_instr = (uint32_t)n; tb.log_slots = log_slots;
+    HIP_TRY(c.err, hipMemsetAsync(d, 0, zero_words * 8, e.stream));
+    HIP_TRY(c.err, hipMemsetAsync(tb.edge_keys, 0xff, key_words * 8, e.stream));
+    HIP_TRY(c.err, hipMemcpyAsync(d_classes, classes.data(), n * 4, hipMemcpyHostToDevice, e.stream));
+    for (auto &s : part.shards) HIP_TRY(c.err, launch_profile_records(e.stream, s.d_recs, s.n_recs, prof::index_of_pc(pk->prog, s.next_pc), tb));
+    std::vector<unsigned long long> h(zero_words + key_words);
+    if (!e.download(h.data(), d, h.size() * 8)) return engine_fail(c.err, e);
+    const unsigned long long *counters = h.data() + 2 * n + S + prof::MAX_SYSCALLS;
+    if (counters[PROFILE_BAD_RECORDS]) return fail(c.err, DVT_ERR_INPUT, "%llu cycle records name an instruction outside the text", counters[PROFILE_BAD_RECORDS]);
+    if (counters[PROFILE_SYS_OVERFLOW]) return fail(c.err, DVT_ERR_UNSUPPORTED, "more than %u distinct syscall ids", prof::MAX_SYSCALLS);
+    for (size_t i = 0; i < n; i++) {
+        t->pc_count[i] += h[i];
+        if (h[n + i]) t->edges[{(uint32_t)i, classes[i] & prof::TGT_MASK}] += h[n + i];
+    }
+    const unsigned long long *ek = h.data() + zero_words, *ec = h.data() + 2 * n;
+    for (size_t k = 0; k < S; k++)
+        if (ek[k] != ~0ull && ec[k]) t->edges[{(uint32_t)(ek[k] >> 32), (uint32_t)ek[k]}] += ec[k];
+    for (size_t k = 0; k < prof::MAX_SYSCALLS; k++)
+        if (ek[S + k] != ~0ull && ec[S + k]) t->sys[(uint32_t)ek[S + k]] += ec[S + k];
+    t->n_transfers += counters[PROFILE_TRANSFERS];
+    t->dropped += counters[PROFILE_DROPPED];
+    t->shards += (uint32_t)part.shards.size();
+    return DVT_OK;
+}
+
+static int job_profile(dvt_prover *p, const dvt_pk *pk, dvt_job *j, uint32_t log_edge_slots, const prof::Out &out) {
+    if (int rc = same_members(p, pk, j)) return rc;
+    const auto t0 = Clock::now();
+    const std::vector<uint32_t> classes = prof::instr_classes(pk->prog);
+    uint32_t log_slots = log_edge_slots;
+    if (!log_slots)
+        for (log_slots = prof::DEFAULT_MIN_LOG_SLOTS; log_slots < prof::MAX_LOG_SLOTS && ((size_t)1 << log_slots) < 4 * classes.size();) log_slots++;
+    prof::Tally t(pk->prog);
+    int rc = DVT_OK;
+    for (size_t m = 0; m < n_members(p) && !rc; m++) {
+        rc = turn_to(p, m);
+        if (!rc) rc = member_profile(lane0(p, m), pk, j->parts[m], log_slots, classes, &t);
+    }
+    if (turn_to(p, 0) && !rc) rc = DVT_ERR_DEVICE;
+    if (rc) return rc;
+    if (!prof::emit(pk->prog, t, (uint32_t)j->n_total, ms_since(t0), out)) return fail(p, DVT_ERR_UNSUPPORTED, "more than %u distinct syscall ids", prof::MAX_SYSCALLS);
+    return DVT_OK;
+}
+
 extern "C" {
+
+// ---- the execution report (profile.h)
+int dvt_rv32_job_profile(dvt_prover *p, const dvt_pk *pk, dvt_job *job, uint32_t log_edge_slots, uint64_t *pc_count, size_t cap_pc,
+                         dvt_profile_edge *edges, size_t cap_edges, dvt_profile_syscall *sys, size_t cap_sys, dvt_profile_opcode *ops,
+                         size_t cap_ops, dvt_profile_summary *summary) {
+    const prof::Out out{pc_count, cap_pc, edges, cap_edges, sys, cap_sys, ops, cap_ops, summary};
+    if (!p || !pk || !job || !summary || out.null_array()) return fail(p, DVT_ERR_INPUT, "null argument");
+    if (int rc = rv32_key(p, pk)) return rc;
+    if (log_edge_slots && (log_edge_slots < prof::MIN_LOG_SLOTS || log_edge_slots > prof::MAX_LOG_SLOTS))
+        return fail(p, DVT_ERR_INPUT, "log_edge_slots %u (0 or %u..%u)", log_edge_slots, prof::MIN_LOG_SLOTS, prof::MAX_LOG_SLOTS);
+    Guard g(p); if (g.rc) return g.rc;
+    return job_profile(p, pk, job, log_edge_slots, out);
+}
+
+// host-only: the guest in trace mode, one shard's records at a time through the same rule (prof::tally_records)
+int dvt_execute_profile(const uint8_t *elf, size_t elf_len, const dvt_buf *stdin_bufs, size_t nbuf, uint64_t max_cycles, uint64_t *pc_count,
+                        size_t cap_pc, dvt_profile_edge *edges, size_t cap_edges, dvt_profile_syscall *sys, size_t cap_sys,
+                        dvt_profile_opcode *ops, size_t cap_ops, dvt_profile_summary *summary, dvt_report *report, char **err_text) {
+    if (err_text) *err_text = nullptr;
+    const prof::Out out{pc_count, cap_pc, edges, cap_edges, sys, cap_sys, ops, cap_ops, summary};
+    if (!elf || (nbuf && !stdin_bufs) || !summary || out.null_array()) return DVT_ERR_INPUT;
+    const auto t0 = Clock::now();
+    rv32::Program prog;
+    std::string err;
+    if (!rv32::load_elf(elf, elf_len, &prog, &err)) {
+        if (err_text) *err_text = strdup(("ELF: " + err).c_str());
+        return DVT_ERR_INPUT;
+    }
+    constexpr uint32_t LOG_SHARD = 21;
+    std::vector<std::vector<uint8_t>> inputs(nbuf);
+    for (size_t i = 0; i < nbuf; i++)
+        if (stdin_bufs[i].len) inputs[i].assign(stdin_bufs[i].data, stdin_bufs[i].data + stdin_bufs[i].len);
+    rv32::Vm vm(prog, &inputs, LOG_SHARD);
+    vm.trace_unprovable = true;
+    const std::unique_ptr<rv32::CycleRec[]> recs(new rv32::CycleRec[(size_t)1 << LOG_SHARD]);   // (pages a short run never touches cost nothing)
+    rv32::ShardOut so;
+    so.recs = recs.get();
+    prof::Tally t(prog);
+    for (;;) {
+        vm.run_shard(true, &so, max_cycles ? max_cycles : ~0ull);
+        prof::tally_records(prog, so.recs, so.n_recs, prof::index_of_pc(prog, so.next_pc), &t);
+        if (vm.halted || !vm.error.empty() || !vm.next_shard()) break;
+    }
+    if (report) {
+        report->cycles = vm.cycles;
+        report->exit_code = vm.halted ? vm.exit_code : -1;
+        report->halted = vm.halted;
+        report->unprovable = vm.unsupported;
+    }
+    if (!prof::emit(prog, t, t.shards, ms_since(t0), out)) {
+        if (err_text) *err_text = strdup("more than 64 distinct syscall ids");
+        return DVT_ERR_UNSUPPORTED;
+    }
+    if (!vm.error.empty()) {
+        if (err_text) *err_text = strdup(vm.error.c_str());
+        return DVT_ERR_GUEST;
+    }
+    if (vm.exit_code != 0) {
+        if (err_text) *err_text = strdup("guest halted with a non-zero exit code");
+        return DVT_ERR_GUEST;
+    }
+    return DVT_OK;
+}
 
 // ---- the trace-row checks of one chip (check.cuh)
 int dvt_stage_check_constraints(dvt_prover *p, const char *machine, uint32_t chip, const uint32_t *d_main, const uint32_t *d_prep,

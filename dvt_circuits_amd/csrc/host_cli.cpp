@@ -5,7 +5,7 @@
 //   dvt_prover_host verify  --type T -i PROOF [--elf GUEST.elf]
 //   dvt_prover_host compact --type T -i PROOF [-o PROOF] [--elf GUEST.elf]     (shared Merkle paths sent once: dvt_proof_compact)
 //   dvt_prover_host expand  --type T -i PROOF [-o PROOF] [--elf GUEST.elf]     (the inverse; verify takes either form)
-//   dvt_prover_host check   --type T -i INPUT.json [--elf GUEST.elf] [--devices D0,D1,...]
+//   dvt_prover_host check   --type T -i INPUT.json [--show-report] [--elf GUEST.elf] [--devices D0,D1,...]
 //
 // T = bad-share | finalization | bad-partial-key | bad-encrypted-share (clap names of CircuitType, :36-42).
 // The reference embeds the four guest ELFs at build time (include_elf!, :115-118); they cannot be built in
@@ -20,7 +20,12 @@
 // against the AIR on the GPU (dvt_rv32_check_job) instead of proving: "clean: N shards, M chip tables, T ms" and exit code 0,
 // or one line per finding and per unbalanced bus and exit code 1; after the bus lines, the tuples that do not cancel
 // (dvt_rv32_job_bus_tuples): at most 32 lines, then "... and N more".
+// --show-report: after execute's three report lines, and after check's verdict, the execution report (dvt_execute_profile on
+// the host, dvt_rv32_job_profile on the GPU): "opcode counts (N total instructions):" and one "count name" line per RISC-V
+// mnemonic, by count descending, then by name; then "syscall counts (N total syscall instructions):" with the ids of
+// dvt_execute's syscall ABI named and any other in hex.  (The layout is this tool's: SP1's own text is not in the reference.)
 // get-schema / validate-schema / node are product UI outside the accelerated path and are not provided.
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -52,6 +57,35 @@ static void print_bus_tuple(const dvt_bus_tuple &t) {
     if (t.first_chip == 0xffffffffu) printf("the verifier's side\n");
     else printf("shard %u chip %s row %u interaction %u\n", t.first_tag, t.first_chip < sizeof CHIP_NAMES / sizeof *CHIP_NAMES ? CHIP_NAMES[t.first_chip] : "?",
                 t.first_row, t.first_interaction);
+}
+
+// the syscall ids of the guest ABI (dvt_execute in include/dvt_prover.h; csrc/rv32.h)
+static std::string syscall_name(uint32_t id) {
+    static const struct { uint32_t id; const char *name; } NAMES[] = {
+        {0x00, "halt"}, {0x02, "write"}, {0x10, "commit"}, {0x1A, "commit_deferred_proofs"}, {0xF0, "hint_len"}, {0xF1, "hint_read"},
+        {0x00300105, "sha_extend"}, {0x00010106, "sha_compress"}, {0x0001010A, "secp256k1_add"}, {0x0000010B, "secp256k1_double"},
+        {0x0001011D, "uint256_mul"}, {0x0001011E, "bls12381_add"}, {0x0000011F, "bls12381_double"}, {0x00010120, "bls12381_fp_add"},
+        {0x00010121, "bls12381_fp_sub"}, {0x00010122, "bls12381_fp_mul"}, {0x00010123, "bls12381_fp2_add"}, {0x00010124, "bls12381_fp2_sub"},
+        {0x00010125, "bls12381_fp2_mul"}};
+    for (auto &n : NAMES)
+        if (n.id == id) return n.name;
+    char b[16];
+    snprintf(b, sizeof b, "0x%08x", id);
+    return b;
+}
+constexpr size_t REPORT_CAP = 64;   // opcodes (48 mnemonics and "unknown") and syscall ids (the library's bound) of a report
+static void print_report(const dvt_profile_opcode *ops, const dvt_profile_syscall *sys, const dvt_profile_summary &s) {
+    printf("opcode counts (%llu total instructions):\n", (unsigned long long)s.cycles);
+    for (size_t i = 0; i < s.n_opcodes && i < REPORT_CAP; i++) printf("%12llu %s\n", (unsigned long long)ops[i].count, ops[i].name);   // (in the library's order)
+    std::vector<std::pair<std::string, uint64_t>> calls;
+    uint64_t total = 0;
+    for (size_t i = 0; i < s.n_syscalls && i < REPORT_CAP; i++) {
+        calls.emplace_back(syscall_name(sys[i].id), sys[i].count);
+        total += sys[i].count;
+    }
+    std::sort(calls.begin(), calls.end(), [](const auto &a, const auto &b) { return a.second != b.second ? a.second > b.second : a.first < b.first; });
+    printf("syscall counts (%llu total syscall instructions):\n", (unsigned long long)total);
+    for (auto &c : calls) printf("%12llu %s\n", (unsigned long long)c.second, c.first.c_str());
 }
 
 int main(int argc, char **argv) {
@@ -147,9 +181,16 @@ int main(int argc, char **argv) {
     if (verb == "execute") {
         printf("input len: %zu\n", stdin_len - 8);  // the reference prints the CBOR length (src/main.rs:436)
         dvt_report rep{};
-        int rc = dvt_execute(elf.data(), elf.size(), &buf, 1, 0, nullptr, nullptr, &rep, &err);
+        dvt_profile_opcode ops[REPORT_CAP];
+        dvt_profile_syscall sys[REPORT_CAP];
+        dvt_profile_summary sum{};
+        int rc = show_report ? dvt_execute_profile(elf.data(), elf.size(), &buf, 1, 0, nullptr, 0, nullptr, 0, sys, REPORT_CAP, ops, REPORT_CAP, &sum, &rep, &err)
+                             : dvt_execute(elf.data(), elf.size(), &buf, 1, 0, nullptr, nullptr, &rep, &err);
         if (rc) return die(std::string("Verification failed: ") + (err ? err : "?"));
-        if (show_report) printf("Verification report:\ntotal instructions: %llu\nexit code: %d\n", (unsigned long long)rep.cycles, rep.exit_code);
+        if (show_report) {
+            printf("Verification report:\ntotal instructions: %llu\nexit code: %d\n", (unsigned long long)rep.cycles, rep.exit_code);
+            print_report(ops, sys, sum);
+        }
         return 0;
     }
 
@@ -187,6 +228,13 @@ int main(int argc, char **argv) {
             if (dvt_rv32_job_bus_tuples(p, pk, job, tuples.data(), tuples.size(), &n, &truncated)) return die(std::string("Check failed: ") + dvt_last_error(p));
             for (size_t i = 0; i < n && i < 32; i++) print_bus_tuple(tuples[i]);
             if (n > 32) printf("... and %zu more%s\n", n - 32, truncated ? " (at least: the ledger was truncated)" : "");
+        }
+        if (show_report) {
+            dvt_profile_opcode ops[REPORT_CAP];
+            dvt_profile_syscall sys[REPORT_CAP];
+            dvt_profile_summary psum{};
+            if (dvt_rv32_job_profile(p, pk, job, 0, nullptr, 0, nullptr, 0, sys, REPORT_CAP, ops, REPORT_CAP, &psum)) return die(std::string("Report failed: ") + dvt_last_error(p));
+            print_report(ops, sys, psum);
         }
         dvt_job_free(p, job);
         dvt_pk_free(p, pk);

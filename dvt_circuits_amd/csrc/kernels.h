@@ -95,4 +95,21 @@ hipError_t launch_gather_siblings(hipStream_t st, const Fp4 *d_v, uint32_t log_m
 hipError_t launch_pow_grind(hipStream_t st, const uint32_t state[16], uint32_t pos, uint32_t bits, uint32_t base, uint32_t count,
                             uint32_t *d_found);
 
+
+// profile.hip
+// The device tables of the execution report's tally (profile.h) and one pass over the cycle records of a shard into them.
+// counts zeroed and keys all ones by the caller; classes: prof::instr_classes.  The records are only read.
+namespace rv32 { struct CycleRec; }
+enum ProfileCounter { PROFILE_TRANSFERS, PROFILE_DROPPED, PROFILE_SYS_OVERFLOW, PROFILE_BAD_RECORDS, PROFILE_COUNTERS };
+struct ProfileTables {
+    unsigned long long *pc_count, *taken;            // [n_instr]: retired; went to its static target (branches, JAL)
+    unsigned long long *edge_keys, *edge_counts;     // [2^log_slots]: from << 32 | to of every other transfer
+    unsigned long long *sys_keys, *sys_counts;       // [64]: syscall ids
+    unsigned long long *counters;                    // [PROFILE_COUNTERS]
+    const uint32_t *classes;                         // [n_instr]
+    uint32_t n_instr, log_slots;
+};
+// last_succ: the instruction index of the shard's next_pc, or 0xffffffff when that is no instruction of the text
+hipError_t launch_profile_records(hipStream_t st, const rv32::CycleRec *d_recs, size_t n_recs, uint32_t last_succ, const ProfileTables &t);
+
 }  // namespace dvt

@@ -282,6 +282,9 @@ class Vm {
     uint32_t pc, shard = 1, in_shard = 0, log_shard;
     uint64_t cycles = 0;
     bool halted = false, unsupported = false, collect_output = true;
+    // trace mode records an instruction without a chip (FENCE) instead of trapping on it: only for the execution report
+    // (profile.h), whose records are never proven
+    bool trace_unprovable = false;
     int exit_code = -1;
     std::string error, unsupported_what;
     std::vector<uint8_t> public_values, stdout_bytes;

@@ -564,7 +564,10 @@ L_UNSUP: {
     if ((IN.raw & 0x7f) != 0x0f) { why = "illegal instruction"; goto trapped; }
     if (!unsupported) { char bb[64]; snprintf(bb, sizeof bb, "instruction 0x%08x at pc 0x%x", IN.raw, IN.pc); unsupported_what = bb; }
     unsupported = true;
-    if (TRACE) { why = "instruction without a chip in a traced run"; goto trapped; }
+    if (TRACE) {
+        if (!trace_unprovable) { why = "instruction without a chip in a traced run"; goto trapped; }
+        BEGIN(); a = b = c = 0; SEQ();   // (the execution report: a record that only carries its instruction index)
+    }
     done++; clk += 4; ip = ip + 1;
     if (done >= budget) goto out_of_budget;
     goto *handlers[ip->kind];

@@ -116,7 +116,8 @@ void dvt_free(void *ptr);
  * dvt_stage_verify_paths, dvt_prover_verify_times; 8: dvt_stage_bus_ledger_*, dvt_rv32_job_bus_tuples;
  * 9: dvt_stage_hunt_cells, dvt_stage_hunt_pairs, dvt_rv32_hunt_shard, dvt_rv32_job_shard_chip_shape;
  * 10: dvt_stage_hunt_join_*, dvt_rv32_hunt_join_job; 11: "compact_openings", dvt_proof_compact, dvt_proof_expand,
- * dvt_stage_multipath_nodes, dvt_stage_verify_multipath, dvt_debug_compact_list_sweep) */
+ * dvt_stage_multipath_nodes, dvt_stage_verify_multipath, dvt_debug_compact_list_sweep; 12: dvt_rv32_job_profile,
+ * dvt_execute_profile) */
 uint32_t dvt_abi_version(void);
 /* the handle's hipStream_t (for event timing by the caller) */
 void *dvt_stream(dvt_prover *p);
@@ -484,6 +485,8 @@ typedef struct {
     uint32_t halted;
     uint32_t unprovable;  /* retired an instruction without a chip (prove would return DVT_ERR_UNSUPPORTED) */
 } dvt_report;
+/* The rest of SP1's ExecutionReport (counts per opcode and per syscall, and where the cycles go: counts per instruction and
+ * per control transfer) is the execution report below: dvt_execute_profile on the host, dvt_rv32_job_profile on the GPU. */
 /* client.setup(elf) (src/main.rs:462,482): decode the ELF, commit the preprocessed
  * tables (program, byte, memory image) on the GPU. */
 int dvt_setup(dvt_prover *p, const uint8_t *elf, size_t elf_len, dvt_pk **pk, uint8_t **vk, size_t *vk_len);
@@ -635,6 +638,58 @@ int dvt_rv32_hunt_join_job(dvt_prover *p, const dvt_pk *pk, dvt_job *job, const 
  * runs once more with another seed, and *truncated is set if that overflows too (or cap is too small). */
 int dvt_rv32_job_bus_tuples(dvt_prover *p, const dvt_pk *pk, dvt_job *job, dvt_bus_tuple *out, size_t cap, size_t *n_tuples,
                             uint32_t *truncated);
+/* The execution report of a prepared job: what retired how often, tallied on the GPU from the cycle records of the shards the
+ * job holds (one launch per shard on the device that holds it; the records are only read and the job is left as found, so a
+ * dvt_rv32_prove_job afterwards returns the bytes it would have returned without).  On a prepare_part job the report covers
+ * the held shards only (summary->shards_tallied of summary->shards_total).
+ *   pc_count[i]   how often instruction i = (pc - text_base) / 4 of the text retired (instructions without a chip included);
+ *                 n_instr entries, always exact
+ *   edges         a record whose successor (the next record; for the last record of a shard the instruction at the shard's
+ *                 next_pc; none after HALT) is not instruction i + 1 is a transfer; every distinct (from_pc, to_pc) is an edge
+ *                 with its count, sorted by (from_pc, to_pc).  The table of the edges of indirect jumps (JALR) is bounded and
+ *                 insert-only: 2^log_edge_slots slots per device, 3..24, 0 = the smallest power of two of at least
+ *                 4 n_instr and at least 2^10; a transfer whose edge finds no slot in 64 probes adds to dropped_transfers.
+ *                 Always: the counts of all edges + dropped_transfers = n_transfers, and an edge that is returned carries
+ *                 its exact count.  (The taken edges of branches and JAL are static and never dropped.)
+ *   sys           ECALL records by syscall id (t0), sorted by id, always exact; a 65th distinct id is DVT_ERR_UNSUPPORTED
+ *   ops           pc_count summed by the lowercase RISC-V mnemonic of the raw instruction word (lui auipc jal jalr beq bne
+ *                 blt bge bltu bgeu lb lh lw lbu lhu sb sh sw addi slti sltiu xori ori andi slli srli srai add sub sll slt
+ *                 sltu xor srl sra or and mul mulh mulhsu mulhu div divu rem remu ecall fence, else "unknown"), the names
+ *                 with a non-zero count, sorted by count descending, then by name
+ *   summary       cycles = the sum of pc_count (for a whole execution dvt_report.cycles); ms = wall clock of the call after
+ *                 the entry guard
+ * Every array takes at most its cap entries (the first ones of the order above; pc_count its first cap_pc); the summary
+ * counts all, so NULL arrays with caps of 0 ask for the sizes.  DVT_ERR_INPUT: a NULL handle, key, job or summary, a NULL
+ * array with a cap, log_edge_slots outside 0, 3..24, a key or job of a handle with other devices.  DVT_ERR_DEVICE: a HIP
+ * failure.  Like every call on the handle it stops a running prove_shard pipeline first. */
+typedef struct {
+    uint32_t from_pc, to_pc;
+    uint64_t count;
+} dvt_profile_edge;
+typedef struct {
+    uint32_t id, pad;
+    uint64_t count;
+} dvt_profile_syscall;
+typedef struct {
+    char name[8];
+    uint64_t count;
+} dvt_profile_opcode;
+typedef struct {
+    uint64_t cycles, n_transfers, dropped_transfers;
+    uint32_t text_base, n_instr, n_edges, n_syscalls, n_opcodes, shards_tallied, shards_total;
+    float ms;
+} dvt_profile_summary;
+int dvt_rv32_job_profile(dvt_prover *p, const dvt_pk *pk, dvt_job *job, uint32_t log_edge_slots, uint64_t *pc_count, size_t cap_pc,
+                         dvt_profile_edge *edges, size_t cap_edges, dvt_profile_syscall *sys, size_t cap_sys,
+                         dvt_profile_opcode *ops, size_t cap_ops, dvt_profile_summary *summary);
+/* The same report on the host alone (no GPU is touched): the guest runs in trace mode shard by shard (2^21 cycles, at most
+ * one shard's records in memory) and the records go through the same rule in plain C++; nothing is bounded, so
+ * dropped_transfers is 0.  Return codes, *report and *err_text as dvt_execute gives them; the report is filled for whatever
+ * retired, also when the guest fails.  An instruction without a chip (FENCE) is counted under its mnemonic. */
+int dvt_execute_profile(const uint8_t *elf, size_t elf_len, const dvt_buf *stdin_bufs, size_t nbuf, uint64_t max_cycles,
+                        uint64_t *pc_count, size_t cap_pc, dvt_profile_edge *edges, size_t cap_edges, dvt_profile_syscall *sys,
+                        size_t cap_sys, dvt_profile_opcode *ops, size_t cap_ops, dvt_profile_summary *summary, dvt_report *report,
+                        char **err_text);
 /* test hook: run K0 on one shard of a prepared job and return the device-generated main traces
  * (canonical); blob layout as dvt_rv32_debug_traces with prep_width = 0. */
 int dvt_rv32_debug_device_traces(dvt_prover *p, const dvt_pk *pk, dvt_job *job, size_t shard, uint32_t **blob,

@@ -1,0 +1,124 @@
+#!/usr/bin/env python3
+"""Where a guest's cycles go: a flat profile from the execution report (dvt_rv32_job_profile on the GPU, dvt_execute_profile
+with --host).
+
+    python tools/profile_guest.py --guest 'bignum(40)' [--top N] [--json OUT] [--host] [--log-shard L]
+    python tools/profile_guest.py --elf guest.elf [--stdin FILE ...]
+
+The guest is an expression over the functions of tests/guests*.py (its ELF is the value, or the first element of it), or an
+ELF file with its stdin buffers.  The guests are stripped (tools/rvasm.py writes program headers only), so function entries
+come from the report itself: the ELF entry plus the target of every edge whose source is a `jal` / `jalr` that writes ra.
+Every instruction belongs to the nearest entry at or below it.  Prints per function f_<pc> its cycles, its share and its
+calls (the counts of the edges into the entry), then the hottest taken branches, the opcode and the syscall counts; --json
+writes the same with the raw tables."""
+import argparse
+import importlib
+import json
+import os
+import struct
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def guest_elf(expr):
+    scope = {}
+    for mod in ("guests", "guests_bls", "guests_finalization", "guests_share", "guests_profile"):
+        m = importlib.import_module("tests." + mod)
+        scope.update({k: getattr(m, k) for k in dir(m) if not k.startswith("_") and k not in scope})
+    v = eval(expr if "(" in expr else expr + "()", scope)   # noqa: S307 (the caller's own command line)
+    return v if isinstance(v, (bytes, bytearray)) else v[0]
+
+
+def text_words(elf):
+    """(text_base, raw words) of the executable segment"""
+    phoff, = struct.unpack_from("<I", elf, 28)
+    phentsize, phnum = struct.unpack_from("<HH", elf, 42)
+    for k in range(phnum):
+        typ, off, vaddr, _, filesz, _, flags, _ = struct.unpack_from("<8I", elf, phoff + k * phentsize)
+        if typ == 1 and flags & 1:
+            blob = elf[off:off + filesz] + b"\0" * (-filesz % 4)
+            return vaddr, [w for (w,) in struct.iter_unpack("<I", blob)]
+    raise SystemExit("no executable segment")
+
+
+def links_ra(word):
+    """a jal / jalr that writes ra (x1): a call"""
+    return word & 0x7F in (0x6F, 0x67) and (word >> 7) & 31 == 1
+
+
+def flat_profile(elf, prof):
+    """functions = [dict(name, pc, end, cycles, share, calls)] by cycles descending; branches = the taken edges that are no
+    calls and no returns, by count descending"""
+    base, words = text_words(elf)
+    entry, = struct.unpack_from("<I", elf, 24)
+    word_at = lambda pc: words[(pc - base) // 4]
+    calls = {}
+    for a, b, c in prof["edges"]:
+        if links_ra(word_at(a)):
+            calls[b] = calls.get(b, 0) + c
+    entries = sorted(set(calls) | {entry})
+    pc_count, total = prof["pc_count"], max(int(prof["summary"]["cycles"]), 1)
+    funcs = []
+    for k, pc in enumerate(entries):
+        end = entries[k + 1] if k + 1 < len(entries) else base + 4 * len(words)
+        first = base if k == 0 else pc        # (what lies below the lowest entry goes to it)
+        cyc = int(pc_count[(first - base) // 4:(end - base) // 4].sum())
+        funcs.append(dict(name="f_%x" % pc, pc=pc, end=end, cycles=cyc, share=cyc / total, calls=calls.get(pc, 0)))
+    funcs.sort(key=lambda f: (-f["cycles"], f["pc"]))
+    is_ret = lambda w: w & 0x7F == 0x67 and (w >> 7) & 31 == 0
+    branches = sorted(((c, a, b) for a, b, c in prof["edges"] if not links_ra(word_at(a)) and not is_ret(word_at(a))), reverse=True)
+    return funcs, [dict(from_pc=a, to_pc=b, count=c) for c, a, b in branches]
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--guest")
+    ap.add_argument("--elf")
+    ap.add_argument("--stdin", action="append", default=[])
+    ap.add_argument("--top", type=int, default=20)
+    ap.add_argument("--json")
+    ap.add_argument("--host", action="store_true", help="tally on the host (dvt_execute_profile): no GPU is touched")
+    ap.add_argument("--log-shard", type=int, default=21)
+    ap.add_argument("--log-edge-slots", type=int, default=0)
+    args = ap.parse_args()
+    if bool(args.guest) == bool(args.elf):
+        ap.error("one of --guest and --elf")
+    from dvt_circuits_amd import capi
+
+    elf = guest_elf(args.guest) if args.guest else open(args.elf, "rb").read()
+    stdin = [open(f, "rb").read() for f in args.stdin]
+    if args.host:
+        rc, rep, prof, err = capi.execute_profile(elf, stdin)
+        if prof is None:
+            raise SystemExit("execute failed: %s" % err)
+        if rc:
+            print("the guest failed (%s): the profile of what retired" % err)
+    else:
+        p = capi.Prover('{"log_shard_size": %d}' % args.log_shard)
+        pk, _ = p.setup(elf)
+        job, rep = p.prepare(pk, stdin)
+        prof = p.job_profile(pk, job, args.log_edge_slots)
+        p.job_free(job)
+        p.pk_free(pk)
+        p.close()
+    s = prof["summary"]
+    funcs, branches = flat_profile(elf, prof)
+    print("%d cycles, %d instructions in the text, %d transfers over %d edges (%d dropped), %d of %d shards, %.2f ms" %
+          (s["cycles"], s["n_instr"], s["n_transfers"], s["n_edges"], s["dropped_transfers"], s["shards_tallied"], s["shards_total"], s["ms"]))
+    print("%-12s %14s %7s %12s" % ("function", "cycles", "share", "calls"))
+    for f in funcs[:args.top]:
+        print("%-12s %14d %6.2f%% %12d" % (f["name"], f["cycles"], 100 * f["share"], f["calls"]))
+    print("hottest taken branches:")
+    for b in branches[:args.top]:
+        print("  0x%08x -> 0x%08x %14d" % (b["from_pc"], b["to_pc"], b["count"]))
+    print("opcodes: " + ", ".join("%s %d" % kv for kv in sorted(prof["opcodes"].items(), key=lambda kv: (-kv[1], kv[0]))[:args.top]))
+    print("syscalls: " + ", ".join("0x%x %d" % kv for kv in sorted(prof["syscalls"].items())))
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(dict(summary=s, functions=funcs, branches=branches, opcodes=prof["opcodes"], syscalls={"0x%x" % k: v for k, v in prof["syscalls"].items()},
+                           pc_count=[int(x) for x in prof["pc_count"]], edges=prof["edges"]), f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
