@@ -87,8 +87,10 @@ static const char *curve_op(const MontField<N> &F, const uint32_t *p, const uint
     return nullptr;
 }
 
-// x * y mod m for 256-bit numbers (m = 0: mod 2^256): schoolbook product, then one long division (polyrel.h poly_divmnu)
-static void u256_mulmod(const uint32_t *x, const uint32_t *y, const uint32_t *m, uint32_t *r) {
+// x * y mod m for 256-bit numbers (m = 0: mod 2^256): schoolbook product, then one long division (polyrel.h poly_divmnu).
+// The u256_mul chip holds the quotient in 33 bytes (tools/airgen/rv32.py build_u256_mul): a call whose quotient does not fit
+// has no row, so it traps here (-> the reason), as the curve precompiles do on equal abscissae.
+static const char *u256_mulmod(const uint32_t *x, const uint32_t *y, const uint32_t *m, uint32_t *r) {
     uint32_t prod[16] = {0};
     for (int i = 0; i < 8; i++) {
         uint64_t carry = 0;
@@ -101,15 +103,19 @@ static void u256_mulmod(const uint32_t *x, const uint32_t *y, const uint32_t *m,
     }
     int n = 8;
     while (n > 0 && m[n - 1] == 0) n--;
-    if (n == 0) { memcpy(r, prod, 32); return; }
+    if (n == 0) { memcpy(r, prod, 32); return nullptr; }   // (quotient = the high half: below 2^256)
     uint32_t q[16], rem[8] = {0};
     poly_divmnu(q, rem, prod, m, 16, n);
+    bool wide = 16 - n >= 8 && (q[8] >> 8) != 0;           // q has 16 - n + 1 digits; 33 bytes = 8 digits and a byte
+    for (int i = 9; i <= 16 - n; i++) wide = wide || q[i] != 0;
+    if (wide) return "UINT256_MUL with a quotient x * y / m of 2^264 or more (the chip's quotient has 33 bytes)";
     memcpy(r, rem, 32);
+    return nullptr;
 }
 
 const char *bigop_compute(uint32_t code, const uint32_t *a, const uint32_t *b, uint32_t *r, uint32_t *lam) {
     switch (code) {
-    case SYS_UINT256_MUL: u256_mulmod(a, b, b + 8, r); return nullptr;
+    case SYS_UINT256_MUL: return u256_mulmod(a, b, b + 8, r);
     case SYS_BLS12381_FP_ADD: case SYS_BLS12381_FP_SUB: case SYS_BLS12381_FP_MUL:
         field_op<6>(bls(), (int)(code - SYS_BLS12381_FP_ADD), a, b, r);
         return nullptr;
@@ -250,7 +256,9 @@ DVT_HD bool fill_differ(Row &R, int col_z0, int col_a0, int col_b0, int L) {
     return false;
 }
 
-// reasons a row cannot be built (the executor traps on every one of them first: seeing one here is an internal error)
+// reasons a row cannot be built.  The executor traps on every call that has no row before a row is asked for (unreduced or
+// equal curve abscissae, DOUBLE of y = 0, a UINT256_MUL quotient of 2^264 or more: bigop_compute above), and it computes the
+// results the other checks look at, so seeing one of these here is an internal error, not a guest's.
 enum RowError { ROW_OK = 0, ROW_NO_WITNESS, ROW_FP_NOT_REDUCED, ROW_FP2_NOT_REDUCED, ROW_U256_NOT_BELOW, ROW_CURVE_BAD, ROW_N_ERRORS };
 #if !defined(__HIP_DEVICE_COMPILE__)
 const char *const ROW_ERROR_TEXT[ROW_N_ERRORS] = {

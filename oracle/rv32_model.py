@@ -12,6 +12,7 @@ An independent restatement, in plain Python, of the two pieces of the path that 
 Only column NAMES are taken from the AIR description (tools.airgen.rv32.build()); every value is computed here.
 Slow by design (pure Python): use on guests of at most ~10^5 cycles.
 """
+import functools
 import struct
 
 import numpy as np
@@ -55,7 +56,10 @@ def big_op(chip, op, a, b):
     Field operands may be any 384-bit numbers (the result is reduced); curve coordinates must be reduced."""
     if chip == "u256_mul":          # x * y mod m, the modulus behind y in memory; m = 0 stands for 2^256
         m = words_to_int(b[8:]) or 1 << 256
-        return int_to_words(words_to_int(a) * words_to_int(b[:8]) % m, 8), None
+        prod = words_to_int(a) * words_to_int(b[:8])
+        if prod // m >= 1 << 264:       # the chip's quotient has 33 bytes: such a call has no row
+            raise Trap("UINT256_MUL with a quotient x * y / m of 2^264 or more (the chip's quotient has 33 bytes)")
+        return int_to_words(prod % m, 8), None
     if chip in ("fp_op", "fp2_op"):
         f = {"add": lambda x, y: (x + y) % BLS_P, "sub": lambda x, y: (x - y) % BLS_P, "mul": lambda x, y: x * y % BLS_P}[op]
         if chip == "fp_op":
@@ -517,7 +521,9 @@ class Run:
 
 
 # ---------------------------------------------------------------------------------------------- K0: trace matrices
+@functools.lru_cache(maxsize=None)
 def _chips():
+    """the AIR's description (read for column names and carry offsets only: built once per process)"""
     from tools.airgen import rv32
 
     m = rv32.build()

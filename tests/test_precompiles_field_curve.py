@@ -103,6 +103,48 @@ def test_invalid_calls_trap():
     assert rc == capi.DVT_ERR_GUEST and "unknown syscall" in err
 
 
+QUOTIENT_TRAP = "UINT256_MUL with a quotient x * y / m of 2^264 or more"
+
+
+@pytest.mark.parametrize("x,y,m", [(1 << 132, 1 << 132, 1), ((1 << 256) - 1, (1 << 256) - 1, 3), ((1 << 256) - 1, (1 << 256) - 1, 1)])
+def test_u256_mul_quotient_of_34_bytes_traps(x, y, m):
+    """the u256_mul chip's quotient has 33 bytes: a call with floor(x * y / m) >= 2^264 has no row, so it is a guest trap in
+    the executor and in the model (it used to execute and then fail in the row builder as an internal error)"""
+    from tests.guests_bigops import precompile_calls
+
+    elf, _ = precompile_calls([(guests.SYS_UINT256_MUL, guests.words_of(3, 8), guests.words_of(5, 8) + guests.words_of(7, 8)),
+                               (guests.SYS_UINT256_MUL, guests.words_of(x, 8), guests.words_of(y, 8) + guests.words_of(m, 8))])
+    assert x * y // m >= 1 << 264
+    rc, rep, _, err = capi.execute(elf)
+    assert rc == capi.DVT_ERR_GUEST and QUOTIENT_TRAP in err and not rep["halted"], (rc, err)
+    run = rv32_model.Run(elf)
+    assert QUOTIENT_TRAP in run.error and not run.halted
+    with pytest.raises(capi.DvtError) as ei:
+        capi.rv32_debug_traces(elf)
+    assert ei.value.code == capi.DVT_ERR_GUEST and QUOTIENT_TRAP in str(ei.value)
+
+
+def test_u256_mul_quotient_of_33_bytes_of_ff_executes():
+    """x = 2^132 - 1, y = 2^132 + 1, m = 1: quotient 2^264 - 1, the largest the chip holds; host rows == model rows"""
+    from tests.guests_bigops import precompile_calls
+
+    x, y = (1 << 132) - 1, (1 << 132) + 1
+    elf, _ = precompile_calls([(guests.SYS_UINT256_MUL, guests.words_of(x, 8), guests.words_of(y, 8) + guests.words_of(1, 8))])
+    rc, rep, pv, out, err = capi.execute_io(elf)
+    run = rv32_model.Run(elf)
+    assert rc == 0 and rep["halted"] and not rep["unprovable"] and run.error == "" and run.halted, (err, run.error)
+    assert out == run.stdout == bytes(32) and pv == run.public_values
+    host, hpubs, _ = capi.rv32_debug_traces(elf)
+    model, mpubs = rv32_model.traces(run, 0)
+    assert (hpubs == mpubs).all() and [c["chip_id"] for c in host] == [c["chip_id"] for c in model]
+    for h, m_ in zip(host, model):
+        assert (h["main"] == m_["main"]).all() and (h["prep"] == m_["prep"]).all(), h["chip_id"]
+    names = _names("U256_MUL")
+    u = next(c for c in host if c["main"].shape[0] == len(names))
+    q = [int(u["main"][c, 0]) for c, n in sorted(names.items()) if re.match(r"q_\d+$", n)]
+    assert q == [0xff] * 33
+
+
 def _free_cells(air, chips, pubs, extra, chip, names, row):
     main, free = chip["main"], set()
     for c in range(main.shape[0]):

@@ -1063,7 +1063,10 @@ def build_u256_mul():
     """UINT256_MUL (a0 = x: 8 little-endian words; a1 = y: 8 words followed by the 8 words of the modulus m):
     x := x * y mod m, with m = 0 standing for 2^256 (SP1's convention; what the patched bls12_381 crate's scalar field
     arithmetic calls).  x * y - r - q * M = 0 as one big-integer identity with the VARIABLE modulus M = m + is_zero * 2^256;
-    the result is below M."""
+    the result is below M.
+    Restriction: q has L + 1 = 33 byte limbs, so only calls with floor(x * y / M) < 2^264 have a row.  The guest machine
+    traps on the others (the executor and oracle/rv32_model.py big_op: "UINT256_MUL with a quotient ... of 2^264 or more"),
+    e.g. x = y = 2^132 with m = 1; every call with M >= 2^248, the reference's scalar field among them, is inside."""
     L = 32
     ch = Chip("u256_mul")
     shard = ch.pub(PUB_SHARD)
