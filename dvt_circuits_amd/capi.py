@@ -145,6 +145,8 @@ def load():
     lib.dvt_debug_p2_f64_selfcheck.restype = u64
     lib.dvt_debug_p2_f64_sbox_check.argtypes = [u32, u32, C.POINTER(C.c_double)]
     lib.dvt_debug_p2_f64_sbox_check.restype = u64
+    lib.dvt_debug_ntt_group_check.argtypes = [u32, u32] + [C.POINTER(C.c_double)] * 3
+    lib.dvt_debug_ntt_group_check.restype = u64
     lib.dvt_prove_core.argtypes = [vp, vp, C.POINTER(Buf), sz, C.POINTER(u8p), C.POINTER(sz), C.POINTER(Report)]
     lib.dvt_verify.argtypes = [C.c_char_p, sz, C.c_char_p, sz, u32, u32, C.POINTER(C.c_int32), C.POINTER(u8p), C.POINTER(sz), C.POINTER(C.c_char_p)]
     lib.dvt_rv32_prepare.argtypes = [vp, vp, C.POINTER(Buf), sz, C.POINTER(vp), C.POINTER(Report)]
@@ -419,6 +421,15 @@ def p2_f64_sbox_check(n: int, seed: int):
     mx = (C.c_double * 4)()
     bad = load().dvt_debug_p2_f64_sbox_check(n, seed, mx)
     return int(bad), [float(v) for v in mx]
+
+
+def ntt_group_check(n: int, seed: int):
+    """Radix-8 group arithmetic of the K1 passes (csrc/ntt_group.cuh) against integer arithmetic mod p on n random groups
+    plus an edge grid: (mismatching outputs, {"dif" | "dif_unit" | "dit": [max |factor|, |product| of stages 0, 1, 2,
+    max |value before the last reduction|, max |output|]})"""
+    mx = [(C.c_double * 8)() for _ in range(3)]
+    bad = load().dvt_debug_ntt_group_check(n, seed, *mx)
+    return int(bad), {k: [float(v) for v in m] for k, m in zip(("dif", "dif_unit", "dit"), mx)}
 
 
 def execute_io(elf: bytes, stdin=(), max_cycles=0):

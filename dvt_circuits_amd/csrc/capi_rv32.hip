@@ -7,6 +7,7 @@
 #include <map>
 
 #include "capi_job.h"
+#include "ntt_group.cuh"
 #include "poseidon2_f64.cuh"
 #include "sha256.h"
 
@@ -1502,6 +1503,89 @@ uint64_t dvt_debug_p2_f64_sbox_check(uint32_t n, uint32_t seed, double *max_abs)
         for (int64_t m = -72; m <= 72; m++) check(m * (((int64_t)P - 1) / 2) + d);
     }
     for (int k = 0; k < 4; k++) max_abs[k] = mx[k];
+    return bad;
+}
+
+// test hook (host only): ntg::dif_group (with and without UNIT) and ntg::dit_group against three butterfly stages in
+// integer arithmetic mod p.  Inputs: n pseudo-random groups over the whole stated input range with random twiddles, and
+// the grid {0, 1, (p - 1)/2, p - 1, 0.52 p} (clamped to the input bound) x all 256 sign patterns of the eight inputs
+// (whatever pattern maximises |a - b| at a stage is among them) x twiddles +-1, +-(p - 1)/2 chosen per stage (4^3) and
+// eight random sets.  Two columns per call: the second holds the negated inputs.  Returns the number of outputs that are
+// not integers congruent to the reference; max_*[8] = the largest magnitudes met (slots: ntg::NoProbe).
+namespace {
+struct NtgProbe {
+    double *mx;
+    DVT_HD void operator()(int k, double x) const { mx[k] = fmax(mx[k], fabs(x)); }
+};
+inline int64_t ntg_mod(int64_t x) { return (x % (int64_t)P + (int64_t)P) % (int64_t)P; }
+// kind 0: DIF, 1: DIF with unit twiddles at j mod dist = 0, 2: DIT
+uint64_t ntg_check_one(int kind, const int64_t in[8], const int64_t tw[7], double *mx) {
+    double v[8][2], w[7], wp[7];
+    int64_t ref[8], t[7];
+    for (int k = 0; k < 7; k++) t[k] = tw[k];
+    if (kind == 1) t[0] = t[4] = t[6] = 1;
+    for (int k = 0; k < 7; k++) { w[k] = (double)t[k]; wp[k] = w[k] * p2f::PINV; }
+    for (int j = 0; j < 8; j++) { v[j][0] = (double)in[j]; v[j][1] = -(double)in[j]; ref[j] = ntg_mod(in[j]); }
+    if (kind == 0) ntg::dif_group<2, false>(v, w, wp, NtgProbe{mx});
+    else if (kind == 1) ntg::dif_group<2, true>(v, w, wp, NtgProbe{mx});
+    else ntg::dit_group<2>(v, w, wp, NtgProbe{mx});
+    for (int s = 0; s < 3; s++) {
+        const int dist = kind == 2 ? 1 << s : 4 >> s;
+        const int first = kind == 2 ? (s == 0 ? 0 : s == 1 ? 1 : 3) : (s == 0 ? 0 : s == 1 ? 4 : 6);
+        for (int j = 0; j < 8; j++) {
+            if (j & dist) continue;
+            const int64_t wj = ntg_mod(t[first + (j & (dist - 1))]);
+            if (kind == 2) {
+                const int64_t a = ref[j], b = ref[j + dist] * wj % (int64_t)P;
+                ref[j] = (a + b) % (int64_t)P; ref[j + dist] = ntg_mod(a - b);
+            } else {
+                const int64_t a = ref[j], b = ref[j + dist];
+                ref[j] = (a + b) % (int64_t)P; ref[j + dist] = ntg_mod(a - b) * wj % (int64_t)P;
+            }
+        }
+    }
+    uint64_t bad = 0;
+    for (int j = 0; j < 8; j++)
+        for (int c = 0; c < 2; c++) {
+            // (an inexact step leaves a non-integer or a value far outside the bound: the cast must stay defined)
+            const double x = v[j][c];
+            const bool sane = fabs(x) < 9e15 && x == floor(x);
+            bad += !sane || ntg_mod((int64_t)x) != (c ? ntg_mod(-ref[j]) : ref[j]);
+        }
+    return bad;
+}
+}  // namespace
+
+uint64_t dvt_debug_ntt_group_check(uint32_t n, uint32_t seed, double *max_dif, double *max_dif_unit, double *max_dit) {
+    uint64_t bad = 0, s = 0x9e3779b97f4a7c15ull ^ seed;
+    double mx[3][8] = {};
+    const int64_t lim[3] = {(int64_t)ntg::DIF_IN, (int64_t)ntg::DIF_IN, (int64_t)ntg::DIT_IN}, half = ((int64_t)P - 1) / 2;
+    auto next = [&]() { s ^= s << 13; s ^= s >> 7; s ^= s << 17; return s; };
+    auto uniform = [&](int64_t m) { return (int64_t)(next() % (2 * (uint64_t)m + 1)) - m; };
+    int64_t in[8], tw[7];
+    for (uint32_t g = 0; g < n; g++)
+        for (int kind = 0; kind < 3; kind++) {
+            for (int j = 0; j < 8; j++) in[j] = uniform(lim[kind]);
+            for (int k = 0; k < 7; k++) tw[k] = uniform(half);
+            bad += ntg_check_one(kind, in, tw, mx[kind]);
+        }
+    const int64_t mags[5] = {0, 1, half, (int64_t)P - 1, (int64_t)(0.52 * p2f::PD)};
+    const int64_t tws[4] = {1, -1, half, -half};
+    for (int kind = 0; kind < 3; kind++)
+        for (int m = 0; m < 5; m++)
+            for (int signs = 0; signs < 256; signs++) {
+                if (m == 0 && signs) break;
+                const int64_t mag = mags[m] > lim[kind] ? lim[kind] : mags[m];
+                for (int j = 0; j < 8; j++) in[j] = (signs >> j) & 1 ? -mag : mag;
+                for (int c = 0; c < 64 + 8; c++) {
+                    for (int k = 0; k < 7; k++) {
+                        const int stage = kind == 2 ? (k < 1 ? 0 : k < 3 ? 1 : 2) : (k < 4 ? 0 : k < 6 ? 1 : 2);
+                        tw[k] = c < 64 ? tws[(c >> (2 * stage)) & 3] : uniform(half);
+                    }
+                    bad += ntg_check_one(kind, in, tw, mx[kind]);
+                }
+            }
+    for (int k = 0; k < 8; k++) { max_dif[k] = mx[0][k]; max_dif_unit[k] = mx[1][k]; max_dit[k] = mx[2][k]; }
     return bad;
 }
 

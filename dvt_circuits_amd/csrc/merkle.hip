@@ -41,7 +41,7 @@ __device__ __forceinline__ void hash_row(const uint32_t *const *cols, uint32_t n
             if (g + k < ncols) s[k] = p2f::from_mont(w[k]);      // (wave-uniform condition)
 #pragma unroll
         for (int k = 0; k < 8; k++) w[k] = g + 8 + k < ncols ? cols[g + 8 + k][row] : 0u;
-        p2f::permute(s);
+        p2f::permute_in_loop(s);
     }
 }
 
@@ -110,7 +110,7 @@ __global__ void __launch_bounds__(256) merkle_level_kernel(const uint32_t *prev,
 #pragma unroll
             for (int k = 0; k < 8; k++) s[8 + k] = p2f::from_mont(w[k]);
         }
-        p2f::permute(s);
+        if constexpr (INJECT) p2f::permute_in_loop(s); else p2f::permute(s);
     }
     store_digest(out, i, s);
 }

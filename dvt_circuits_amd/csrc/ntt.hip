@@ -30,6 +30,7 @@
 #include <atomic>
 
 #include "kernels.h"
+#include "ntt_group.cuh"
 #include "poseidon2_f64.cuh"
 
 namespace dvt {
@@ -40,6 +41,13 @@ namespace dvt {
 // product), not into the multiplier and not into LDS.  LDS tiles hold 32-bit signed residues in (-p, p); twiddles are
 // CANONICAL residues (the data words are Montgomery words: x~ * w mod p is the Montgomery word of x * w), one
 // conversion per LDS word on the way in, one reduction + conversion on the way out.
+// The two-column passes of lde_block2_kernel (dif_pass2 / dit_pass2) run the radix-8 group of ntt_group.cuh: the products of
+// a group's first two stages feed only the next stage and are reduced to a multiple of 2^K p in 3 operations (p2f::mm_c),
+// the last stage keeps the 5-operation product, and the last DIF pass (one row per group element) skips its 7 of 12
+// products by the twiddle 1: 80 (DIF), 63 (DIF, last pass) and 92 (DIT) FP64 operations per group and column instead of
+// 96 / 96 / 108; bounds and their host check are stated there.  lde_block2_kernel: 1 542 FP64 instructions (1 833 before),
+// -6.2 % time alone on the GPU.  dif3_v4 keeps the full products: with the partial ones ntt_strided_v4_kernel had 909 FP64
+// instructions instead of 1 170 and was NOT faster (+1.6 % / +2.9 %, profiles/README.md round 13): it is not issue-bound.
 using Lw = int32_t;
 __device__ __forceinline__ Lw to_lds(double x) { return (Lw)x; }                    // |x| < 2^31
 __device__ __forceinline__ uint32_t lds_to_word(Lw v) { return v < 0 ? (uint32_t)(v + (Lw)P) : (uint32_t)v; }
@@ -401,6 +409,7 @@ __global__ void __launch_bounds__(1024) lde_block_kernel(const uint32_t *in, uin
 // load / store loops are shared.  64 KB tile + 16 KB twiddles: two workgroups (four columns) per CU.
 template <int R, int L, int S, int TWS>
 __device__ __forceinline__ void dif_pass2(int2 *sm, const Lw *tw, uint32_t tid, uint32_t nt) {
+    static_assert(R == 3, "the two-column passes are radix-8 groups (ntt_group.cuh)");
     constexpr uint32_t G = 1u << R, lh = L - S - R, work = 1u << (L - R);
     for (uint32_t w = tid; w < work; w += nt) {
         const uint32_t r = w & ((1u << lh) - 1);
@@ -412,30 +421,27 @@ __device__ __forceinline__ void dif_pass2(int2 *sm, const Lw *tw, uint32_t tid, 
             const int2 x = sm[base ^ swz(j << lh)];
             v[j][0] = (double)x.x; v[j][1] = (double)x.y;
         }
+        // stage t pairs distance G >> (t + 1); twiddle exponent ((j mod dist) * 2^lh + r) << (S + t).  In the last pass
+        // (lh = 0: r = 0) the exponent of j mod dist = 0 is zero at compile time: no product there (ntg: UNIT)
+        double wv[7], wp[7];
+        uint32_t n = 0;
 #pragma unroll
-        for (uint32_t t = 0; t < (uint32_t)R; t++) {
-            const uint32_t dist = G >> (t + 1);
+        for (uint32_t t = 0; t < 3; t++) {
             const uint32_t twr = swz((r << (S + t)) << TWS);
 #pragma unroll
-            for (uint32_t j = 0; j < G; j++) {
-                if (j & dist) continue;
-                const double wv = (double)tw[twr ^ swz((((j & (dist - 1)) << lh) << (S + t)) << TWS)];
-                const double wp = wv * p2f::PINV;
-#pragma unroll
-                for (int c = 0; c < 2; c++) {
-                    const double a = v[j][c], b = v[j + dist][c];
-                    v[j][c] = a + b;
-                    v[j + dist][c] = p2f::mm_pre(a - b, wv, wp);
-                }
+            for (uint32_t jj = 0; jj < (4u >> t); jj++, n++) {
+                wv[n] = (lh == 0 && jj == 0) ? 1.0 : (double)tw[twr ^ swz(((jj << lh) << (S + t)) << TWS)];
+                wp[n] = wv[n] * p2f::PINV;
             }
         }
+        ntg::dif_group<2, lh == 0>(v, wv, wp);      // every output reduced: |v| <= 0.52 p
 #pragma unroll
-        for (uint32_t j = 0; j < G; j++)
-            sm[base ^ swz(j << lh)] = make_int2(to_lds((j & 1) ? v[j][0] : p2f::red(v[j][0])), to_lds((j & 1) ? v[j][1] : p2f::red(v[j][1])));
+        for (uint32_t j = 0; j < G; j++) sm[base ^ swz(j << lh)] = make_int2(to_lds(v[j][0]), to_lds(v[j][1]));
     }
 }
 template <int R, int L, int S, int TWS>
 __device__ __forceinline__ void dit_pass2(int2 *sm, const Lw *tw, uint32_t tid, uint32_t nt) {
+    static_assert(R == 3, "the two-column passes are radix-8 groups (ntt_group.cuh)");
     constexpr uint32_t G = 1u << R, work = 1u << (L - R), blk_bits = L - R - S;
     for (uint32_t g = tid; g < work; g += nt) {
         const uint32_t r = g & ((1u << S) - 1);
@@ -447,25 +453,21 @@ __device__ __forceinline__ void dit_pass2(int2 *sm, const Lw *tw, uint32_t tid, 
             const int2 x = sm[base ^ swz(j << S)];
             v[j][0] = (double)x.x; v[j][1] = (double)x.y;
         }
+        // stage t pairs distance 2^t; twiddle exponent ((j mod dist) * 2^S + r) << (L - 1 - S - t)
+        double wv[7], wp[7];
+        uint32_t n = 0;
 #pragma unroll
-        for (uint32_t t = 0; t < (uint32_t)R; t++) {
-            const uint32_t dist = 1u << t;
+        for (uint32_t t = 0; t < 3; t++) {
             const uint32_t twr = swz((r << (L - 1 - S - t)) << TWS);
 #pragma unroll
-            for (uint32_t j = 0; j < G; j++) {
-                if (j & dist) continue;
-                const double wv = (double)tw[twr ^ swz((((j & (dist - 1)) << S) << (L - 1 - S - t)) << TWS)];
-                const double wp = wv * p2f::PINV;
-#pragma unroll
-                for (int c = 0; c < 2; c++) {
-                    const double a = v[j][c], b = p2f::mm_pre(v[j + dist][c], wv, wp);   // |v| < 2^33
-                    v[j][c] = a + b;
-                    v[j + dist][c] = a - b;
-                }
+            for (uint32_t jj = 0; jj < (1u << t); jj++, n++) {
+                wv[n] = (double)tw[twr ^ swz(((jj << S) << (L - 1 - S - t)) << TWS)];
+                wp[n] = wv[n] * p2f::PINV;
             }
         }
+        ntg::dit_group<2>(v, wv, wp);               // every output reduced: |v| <= p/2 + 1
 #pragma unroll
-        for (uint32_t j = 0; j < G; j++) sm[base ^ swz(j << S)] = make_int2(to_lds(p2f::red(v[j][0])), to_lds(p2f::red(v[j][1])));
+        for (uint32_t j = 0; j < G; j++) sm[base ^ swz(j << S)] = make_int2(to_lds(v[j][0]), to_lds(v[j][1]));
     }
 }
 template <bool DIF, int L, int FIRST, int COUNT, int TWS>

@@ -49,6 +49,9 @@ constexpr double MONT_RINV = 943718400.0;     // 2^-32 mod p
 // bare kernel's loop (tools/microbench, which reduces the state once more per call) has 4 274 FP64 instructions among
 // 4 989 vector ones (119 of them v_mov_b64); at four issue cycles per wave64 instruction that is 20.0 k cycles per wave,
 // and 8.05 Gperm/s measured is 19.5 k at the nominal 2.4 GHz: the permutation is issue-bound.
+// 210 of those vector instructions are v_readlane_b32: the loop keeps the 141 round constants live across iterations, they
+// do not fit the SGPRs and are parked in VGPR lanes.  permute_in_loop (below) fetches them inside the iteration instead:
+// 4 565 vector instructions, no SGPR spills, 8.77 Gperm/s (profiles/r13_p2_microbench.txt).
 constexpr double MAGIC = 6755399441055744.0;  // 1.5 * 2^52
 DVT_DEV double rnd_prod(double a, double b) { return fma(a, b, MAGIC) - MAGIC; }
 DVT_DEV double mm(double a, double b) {
@@ -181,17 +184,17 @@ DVT_DEV void internal_layer(double s[16]) {
 //                         state (s[0] <= 0.573 p, the others <= p/2) 14.4 p (2^34.8) -> 2^39.4 -> 2^44.1 -> reduce;
 //                         all below 2^48 as red and the sums need.  After r = 12: 2^39.4, then every entry reduced.
 //   last external rounds  |red + rc| <= p for the first, then as above; the final red leaves |s_i| <= p/2 + 2^-8.
-DVT_DEV void permute(double s[16]) {
+DVT_DEV void permute_rc(double s[16], const double *rc_ext, const double *rc_int) {
     external_layer(s);
 #pragma unroll
     for (int r = 0; r < 4; r++) {
 #pragma unroll
-        for (int i = 0; i < 16; i++) s[i] = sbox(s[i] + RC_EXT[16 * r + i]);
+        for (int i = 0; i < 16; i++) s[i] = sbox(s[i] + rc_ext[16 * r + i]);
         external_layer(s);
     }
 #pragma unroll
     for (int r = 0; r < 13; r++) {
-        s[0] = sbox(red(s[0]) + RC_INT[r]);
+        s[0] = sbox(red(s[0]) + rc_int[r]);
         if (r == 2 || r == 5 || r == 8 || r == 11) internal_layer<true>(s); else internal_layer<false>(s);
     }
 #pragma unroll
@@ -199,14 +202,33 @@ DVT_DEV void permute(double s[16]) {
 #pragma unroll
     for (int r = 4; r < 8; r++) {
 #pragma unroll
-        for (int i = 0; i < 16; i++) s[i] = sbox(s[i] + RC_EXT[16 * r + i]);
+        for (int i = 0; i < 16; i++) s[i] = sbox(s[i] + rc_ext[16 * r + i]);
         external_layer(s);
     }
 #pragma unroll
     for (int i = 0; i < 16; i++) s[i] = red(s[i]);
 }
+DVT_DEV void permute(double s[16]) { permute_rc(s, RC_EXT, RC_INT); }
 
 #if defined(__HIPCC__)
+// ---- the same permutation for a kernel that runs it INSIDE a loop (the row sponge, the two passes of an injected level) ----
+// With the tables named directly the compiler hoists all 141 round constants out of the loop, runs out of SGPRs, parks
+// them in VGPR lanes and fetches each one back with a v_readlane_b32 in every iteration (222 SGPR spills, 222 readlanes
+// among the 4 892 vector instructions of the leaf kernel's sponge loop).  Here the tables are addressed through a wave-uniform
+// offset of zero that the compiler cannot see through and must assume changed by every iteration: the constants are
+// fetched inside the iteration with scalar loads (17 s_load_dwordx16, which issue beside the vector instructions) and
+// live in SGPRs only while their round runs.  (Hiding the POINTER instead loses its address space: flat loads.  An LDS
+// table measures the same on the bare permutation, 8.79 against 8.77 Gperm/s, and takes 8 more VGPRs there, 76 against 68:
+// the leaf kernel would pass the 80 of six waves per SIMD.)
+// merkle_leaves_kernel: 76 VGPRs, -5.0 % time alone on the GPU; merkle_level_kernel<true>: 72 VGPRs.
+__device__ __forceinline__ void permute_in_loop(double s[16]) {
+    uint32_t off = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+s"(off));
+#endif
+    permute_rc(s, RC_EXT + off, RC_INT + off);
+}
+
 // ---- the same permutation, one state per 16 LANES (lane e of a DPP row holds state element e) ---------------------
 // A thread that owns a whole state runs ~5 600 FP64 operations back to back: ~9 us however few states there are, which
 // is what the small Merkle levels and every tree top cost per level.  Spread over a DPP row the S-boxes of a round run

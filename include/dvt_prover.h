@@ -749,6 +749,12 @@ uint64_t dvt_debug_p2_f64_selfcheck(uint32_t n, uint32_t seed);
  * on n pseudo-random inputs over its whole stated input range and on edge values; returns the number of wrong results.
  * max_abs[4] = the largest |x^2|, |x^3|, |x^4|, |x^7| representatives met, which its exactness conditions bound. */
 uint64_t dvt_debug_p2_f64_sbox_check(uint32_t n, uint32_t seed, double *max_abs);
+/* test hook, host only: the radix-8 group arithmetic of the K1 register passes (csrc/ntt_group.cuh: stages 0 and 1 reduced
+ * only to a multiple of 2^K p) against integer arithmetic mod p, on n pseudo-random groups and on an edge grid of inputs
+ * and twiddles; returns the number of outputs that are not integers congruent to the reference.  max_dif[8], max_dif_unit[8]
+ * (the variant that skips the products by the twiddle 1) and max_dit[8] = the largest magnitudes met, in the slots that
+ * ntg::NoProbe documents: stage 0/1/2 factor and product, value before the last reduction, output. */
+uint64_t dvt_debug_ntt_group_check(uint32_t n, uint32_t seed, double *max_dif, double *max_dif_unit, double *max_dit);
 /* test hook, host only: the bus ledger's key of a tuple (csrc/ledger_key.h: the function the kernels key the rows with) */
 uint64_t dvt_debug_ledger_key(uint64_t seed, uint32_t bus, uint32_t arity, const uint32_t *values);
 
