@@ -15,6 +15,7 @@ CSRC = os.path.join(HERE, "csrc")
 DVT_OK, DVT_ERR_GUEST, DVT_ERR_INPUT, DVT_ERR_DEVICE, DVT_ERR_UNSUPPORTED, DVT_ERR_REJECTED = 0, 1, 2, 3, 4, 5
 PATHS = {"default": 0, "rows": 1, "parts": 2}             # DVT_PATH_* (K4 / K5 launches)
 SELECTORS = {"table": 0, "kernel": 1}                     # DVT_SELECTORS_*
+DVT_KEEP_NONE, DVT_KEEP_TREE, DVT_KEEP_FULL = 0, 1, 2     # what a committed shard keeps in HBM for phase 2 ("keep_phase1")
 u32p = C.POINTER(C.c_uint32)
 u8p = C.POINTER(C.c_uint8)
 
@@ -164,6 +165,12 @@ def load():
     lib.dvt_rv32_job_shard_member.restype = C.c_int
     lib.dvt_rv32_job_shard_device_rows.argtypes = [vp, sz]
     lib.dvt_rv32_job_shard_device_rows.restype = u32
+    lib.dvt_rv32_job_shard_kept.argtypes = [vp, sz]
+    lib.dvt_rv32_job_shard_kept.restype = C.c_int
+    lib.dvt_rv32_job_shard_kept_bytes.argtypes = [vp, sz]
+    lib.dvt_rv32_job_shard_kept_bytes.restype = C.c_uint64
+    lib.dvt_debug_keep_plan.argtypes = [C.c_int, u64, u64, u64, u64, u64, u64, u64, C.c_int, C.c_int64, u64]
+    lib.dvt_debug_keep_plan.restype = C.c_int
     lib.dvt_rv32_commit_shard.argtypes = [vp, vp, vp, sz, u32p]
     lib.dvt_rv32_challenges.argtypes = [C.c_char_p, sz, u32p, sz, u32p]
     lib.dvt_rv32_prove_shard.argtypes = [vp, vp, vp, sz, u32p, C.POINTER(u8p), C.POINTER(sz)]
@@ -408,6 +415,13 @@ def execute_profile(elf: bytes, stdin=(), max_cycles=0):
 def exec_rate(elf: bytes, stdin=(), log_shard=21, trace=False) -> float:
     """guest cycles / second of the host executor alone (fast or trace mode)"""
     return float(load().dvt_debug_exec_rate(elf, len(elf), _bufs(stdin), len(stdin), log_shard, int(trace)))
+
+
+def keep_plan(mode, free, total, reserve, full, tree, later, remaining=0, count_known=True, full_cap=-1, full_kept=0) -> int:
+    """The admission rule of "keep_phase1" (dvt_debug_keep_plan; host only, no device): the DVT_KEEP_* tier of a shard that
+    keeps `full` bytes in full and `tree` bytes as a tree, with `free` of `total` bytes free, `reserve` to stay free, and
+    `remaining` later shards of at least `later` bytes each still to come"""
+    return int(load().dvt_debug_keep_plan(mode, free, total, reserve, full, tree, later, remaining, int(bool(count_known)), full_cap, full_kept))
 
 
 def p2_f64_selfcheck(n: int, seed: int) -> int:
@@ -1097,6 +1111,15 @@ class Prover:
         """bit c set: the rows of chip c of that shard (global position) were built on the GPU from events; 0 when the
         job does not hold the shard"""
         return int(self.lib.dvt_rv32_job_shard_device_rows(job, shard))
+
+    def job_shard_kept(self, job, shard):
+        """the DVT_KEEP_* tier of that shard (global position) from its last phase 1; -1 when the job does not hold the shard
+        or no phase 1 of it has run"""
+        return int(self.lib.dvt_rv32_job_shard_kept(job, shard))
+
+    def job_shard_kept_bytes(self, job, shard):
+        """the bytes that tier holds in HBM: the tree (TREE), tree + main LDEs + K0 buffers (FULL), 0 otherwise"""
+        return int(self.lib.dvt_rv32_job_shard_kept_bytes(job, shard))
 
     def commit_shard(self, pk, job, shard):
         h = np.zeros(HEADER_WORDS, np.uint32)

@@ -269,7 +269,7 @@ int stage_table(dvt_prover *p, const char *machine, uint32_t chip, const uint32_
 
 extern "C" {
 
-uint32_t dvt_abi_version(void) { return 12; }
+uint32_t dvt_abi_version(void) { return 13; }
 
 int dvt_prover_create(const char *cfg_json, dvt_prover **out) {
     if (!out) return fail(nullptr, DVT_ERR_INPUT, "out == NULL");
@@ -293,7 +293,11 @@ int dvt_prover_create(const char *cfg_json, dvt_prover **out) {
     p->cfg.compact_openings = cfg_int(cfg_json, "compact_openings", 0) != 0;
     const bool profile = cfg_int(cfg_json, "profile", 0) != 0;
     p->log_shard = (uint32_t)cfg_int(cfg_json, "log_shard_size", 21);
-    p->keep_phase1 = cfg_int(cfg_json, "keep_phase1", 1) != 0;
+    {   // (0 and 2 are modes of their own; every other value reads as 1, as it did when the key was a flag)
+        const int keep = cfg_int(cfg_json, "keep_phase1", 1);
+        p->keep_phase1 = keep == 0 || keep == 2 ? keep : 1;
+    }
+    p->keep_full_max = cfg_int(cfg_json, "keep_full_max", -1);
     p->exec_threads = (uint32_t)std::max(0, cfg_int(cfg_json, "exec_threads", 0));
     const int parts_parallel_log = cfg_int(cfg_json, "parts_parallel_log", (int)PARTS_PARALLEL_LOG);
     if (parts_parallel_log < -1 || parts_parallel_log > (int)PARTS_PARALLEL_LOG)

@@ -90,7 +90,10 @@ struct dvt_prover {
     dvt::StarkConfig cfg;
     uint32_t log_shard = 21;          // cycles per shard = 2^log_shard (SP1's default shard size)
     uint64_t max_cycles = 1ull << 36;
-    bool keep_phase1 = true;          // keep K0 output, main LDEs and tree of phase 1 in HBM for phase 2 ("keep_phase1": 0 recomputes)
+    // what phase 1 keeps in HBM for phase 2 ("keep_phase1", keep_plan.h): 0 nothing (phase 2 recomputes), 1 K0 output, main LDEs
+    // and tree while they fit, 2 the same, then the tree alone, then nothing
+    int keep_phase1 = 1;
+    int keep_full_max = -1;           // diagnostic ("keep_full_max"): shards kept in full per physical device and job at most; -1 = no cap
     uint32_t exec_threads = 0;        // trace-mode executor threads of the prove pipeline ("exec_threads", 0 = from the host's core count)
     std::vector<dvt::rv32::CycleRec *> pinned;    // pinned staging buffers of 2^log_shard records each, reused across calls
     // the device verifier's pinned staging and events (verify_query.hip, on member 0), made by the first dvt_prover_verify; its last times

@@ -21,11 +21,12 @@ struct ShardJob {
     uint32_t *d_aux[rv32::N_CHIPS] = {};  // main traces except cpu
     uint32_t device_rows = 1u << RV32_CHIP_CPU;   // bit c: the rows of chip c were (and on every K0 are) built on the GPU from events
     std::vector<Fp> pubs;
-    MainCache cache;  // phase-1 LDEs + tree of the main traces, consumed by phase 2
-    // K0 output of this shard kept from phase 1 to phase 2 (with the cache, while HBM allows); otherwise the
-    // job's working buffers are used and phase 2 runs K0 again
+    MainCache cache;  // phase-1 LDEs + tree of the main traces (or the tree alone), consumed by phase 2
+    // K0 output of this shard kept from phase 1 to phase 2 (with a full cache, while HBM allows); otherwise (tree-only
+    // cache or none) the job's working buffers are used and phase 2 runs K0 again
     uint32_t *d_cpu = nullptr, *d_byte = nullptr, *d_prog = nullptr;
     bool traces_valid = false;
+    int kept = -1;            // the tier of the last phase 1 (KEEP_*, keep_plan.h): what the shard holds in HBM until the job is freed; -1 before
     int lane = 0;             // the lane that first committed the shard: cache and kept K0 output are from its pool
     uint32_t header[HEADER_WORDS] = {};
     bool header_valid = false;   // phase 1 ran (inside the prepare pipeline, or by commit_shard) and no phase 2 has consumed it
@@ -68,6 +69,10 @@ struct dvt_job {
     size_t byte_words = 0, prog_words = 0;
     double t_exec_wait = 0;   // the longest executor wait of a member
     std::vector<dvt::JobPart> parts;   // one per member
+    // Per physical device (index & 63, as the devices' turns): the shards its members have committed in the prepare, and the
+    // shards of this job kept in full on it.  Written at the admission of a shard (shard_commit), under the device's turn
+    // whenever another thread commits on the device.
+    struct DeviceTally { size_t committed = 0, full = 0; } tally[64];
     size_t held() const {
         size_t n = 0;
         for (auto &q : parts) n += q.shards.size();

@@ -12,6 +12,7 @@
 #include "sha256.h"
 
 using namespace dvt;
+static_assert(DVT_KEEP_NONE == KEEP_NONE && DVT_KEEP_TREE == KEEP_TREE && DVT_KEEP_FULL == KEEP_FULL, "the tiers of include/dvt_prover.h");
 
 namespace {
 std::vector<std::vector<uint8_t>> collect_stdin(const dvt_buf *bufs, size_t n) {
@@ -125,9 +126,38 @@ static std::mutex &device_turn(int dev) {
     return mu[dev & 63];
 }
 
+// What the fast pass of a prepare has found so far: the shards of the execution counted as their first cycle is reached, and
+// whether the count is final.  The fast-pass thread advances it; the committers read it at the admission of a shard.
+struct ShardCount {
+    std::atomic<size_t> found{0};
+    std::atomic<bool> final{false};
+};
+
+// the bytes a shard holds in HBM in each tier, and what its upload allocated (keep_plan.h: T, F and L - T)
+static size_t shard_tree_bytes(const ShardJob &s) {
+    uint32_t max_log_n = 0;
+    for (int c = 0; c < rv32::N_CHIPS; c++)
+        if (s.present[c]) max_log_n = std::max(max_log_n, s.log_n[c]);
+    return (((size_t)2 << (max_log_n + 1)) - 1) * 32;
+}
+static size_t shard_k0_bytes(const dvt_job *j, const ShardJob &s) { return (((size_t)RV32_CPU_MAIN_W << s.log_n[RV32_CHIP_CPU]) + j->byte_words + j->prog_words) * 4; }
+static size_t shard_lde_bytes(const ShardJob &s) {
+    size_t n = 0;
+    for (int c = 0; c < rv32::N_CHIPS; c++)
+        if (s.present[c]) n += ((size_t)machine_rv32()->chips[c].main_w << s.log_n[c]) * 8;
+    return n;
+}
+static size_t shard_upload_bytes(const ShardJob &s) {
+    size_t n = s.n_recs * sizeof(rv32::CycleRec);
+    for (int c = 0; c < rv32::N_CHIPS; c++)
+        if (s.present[c] && c != RV32_CHIP_CPU) n += ((size_t)machine_rv32()->chips[c].main_w << s.log_n[c]) * 4;
+    return n;
+}
+
 // phase 1 of a shard: K0 + K1..K3 of the main traces -> header.  `concurrent`: other threads of this member commit or upload
-// meanwhile (the phase-1 lanes of a prepare)
-static int shard_commit(const Lane &c, const DeviceKey &key, dvt_job *j, ShardJob &s, bool concurrent = false) {
+// meanwhile (the phase-1 lanes of a prepare).  `count`: the executor's shard count inside a prepare (what is still to come
+// on this device enters the admission, keep_plan.h); nullptr outside one: nothing is to come and the count is known.
+static int shard_commit(const Lane &c, const DeviceKey &key, dvt_job *j, ShardJob &s, bool concurrent = false, const ShardCount *count = nullptr) {
     dvt_prover *p = c.p;
     Member &mem = c.mem;
     std::vector<ChipTrace> traces;
@@ -136,12 +166,12 @@ static int shard_commit(const Lane &c, const DeviceKey &key, dvt_job *j, ShardJo
     auto lap = [&](const char *what) {
         if (time_stages) fprintf(stderr, "[commit] %s at %.2f ms (pool misses so far %zu)\n", what, ms_since(t0), c.eng.pool.misses);
     };
-    // keep the phase-1 results in HBM while they fit (about 3 GB per 2^21-cycle shard); otherwise phase 2 recomputes
+    // keep the phase-1 results in HBM while they fit (about 3 GB per 2^21-cycle shard); otherwise the tree alone
+    // ("keep_phase1": 2) or nothing, and phase 2 recomputes the rest
     std::unique_lock<std::mutex> turn;
     if (concurrent || (mem.shares_device && p->keep_phase1 && !s.cache.tree)) turn = std::unique_lock<std::mutex>(device_turn(c.eng.device));
     size_t free_b = 0, total_b = 0;
     if (p->keep_phase1 && !s.cache.tree) { (void)hipMemGetInfo(&free_b, &total_b); free_b += c.eng.pool.cached_bytes; }   // (only the first commit of a shard asks)
-    lap("memory asked");
     // the further lanes' arenas are not there yet on the first job: leave room for them (the largest arena of this member's
     // lanes is the measure of one), so that the kept caches do not take what another lane's working set then cannot get
     // (and for the lanes of the members that share this device, whose phase 1 waits for its turn meanwhile)
@@ -159,8 +189,42 @@ static int shard_commit(const Lane &c, const DeviceKey &key, dvt_job *j, ShardJo
     if (turn.owns_lock())
         for (auto &q : p->members)
             if (q.get() != &mem && q->eng.device == c.eng.device) room_of(*q);
-    MainCache *keep = p->keep_phase1 && (s.cache.tree || free_b > ((size_t)24 << 30) + lane_room) ? &s.cache : nullptr;
-    if (keep && !s.d_cpu) {
+    // The tier (keep_plan.h), decided and allocated for under the turn.  The tallies of the device (shards committed in this
+    // prepare, shards kept in full in this job) are shared by the members on it and written under the same turn.
+    dvt_job::DeviceTally &tally = j->tally[c.eng.device & 63];
+    int tier = s.cache.tier();   // (a shard that has a cache keeps its tier: no question asked, as before)
+    if (p->keep_phase1 && !s.cache.tree) {
+        KeepPlanIn in;
+        in.mode = p->keep_phase1;
+        in.free_b = free_b; in.total_b = total_b;
+        in.reserve = ((size_t)24 << 30) + lane_room;
+        in.tree_b = shard_tree_bytes(s);
+        in.full_b = in.tree_b + shard_lde_bytes(s) + shard_k0_bytes(j, s);
+        in.later_b = in.tree_b + shard_upload_bytes(s);
+        if (count) {   // what the fast pass has found so far for the members on this device, less what they have committed
+            in.count_known = count->final.load(std::memory_order_acquire);
+            const size_t found = count->found.load(std::memory_order_acquire);
+            size_t theirs = 0;
+            for (auto &q : p->members) {
+                if (q->eng.device != c.eng.device) continue;
+                const JobPart &part = j->parts[q->index];
+                if (found > part.first) theirs += (found - part.first + part.stride - 1) / part.stride;
+            }
+            in.remaining = theirs > tally.committed + 1 ? theirs - tally.committed - 1 : 0;
+        }
+        in.full_cap = p->keep_full_max;
+        in.full_kept = tally.full;
+        tier = keep_plan(in);
+        if (tier == KEEP_FULL) tally.full++;
+        if (count) tally.committed++;
+    }
+    if (time_stages) {
+        char what[64];
+        snprintf(what, sizeof what, "memory asked (tier %s)", tier == KEEP_FULL ? "FULL" : tier == KEEP_TREE ? "TREE" : "NONE");
+        lap(what);
+    }
+    MainCache *keep = tier != KEEP_NONE ? &s.cache : nullptr;
+    if (tier == KEEP_FULL && !s.d_cpu) {
         DevPool &pool = c.eng.pool;
         s.lane = c.k;
         bool ok = pool.alloc(&s.d_cpu, ((size_t)RV32_CPU_MAIN_W << s.log_n[RV32_CHIP_CPU]) * 4) == hipSuccess && pool.alloc(&s.d_byte, j->byte_words * 4) == hipSuccess &&
@@ -175,11 +239,12 @@ static int shard_commit(const Lane &c, const DeviceKey &key, dvt_job *j, ShardJo
     if (rc) return rc;
     lap("K0 launched");
     Digest root;
-    if (!c.eng.commit_main_root(key.key, traces, &root, keep, &turn)) return engine_fail(c.err, c.eng);
+    if (!c.eng.commit_main_root(key.key, traces, &root, keep, &turn, tier)) return engine_fail(c.err, c.eng);
     lap("main root");
     for (int k = 0; k < 8; k++) s.header[k] = root.d[k].canonical();
     for (uint32_t k = 0; k < N_PUB; k++) s.header[8 + k] = s.pubs[k].canonical();
     s.header_valid = true;
+    s.kept = tier;
     return DVT_OK;
 }
 
@@ -240,6 +305,7 @@ struct Executor {
     std::vector<rv32::CycleRec *> free_bufs;
     std::map<size_t, ReadyShard> ready;
     FastPass fast;
+    ShardCount count;   // the shards the fast pass has reached (the admission of phase 1 reads it)
     rv32::CurveLog curve_log;
     std::vector<std::thread> threads;   // the fast pass, then the workers
 
@@ -253,6 +319,7 @@ struct Executor {
             struct Close { rv32::CurveLog &l; ~Close() { l.closed.store(true, std::memory_order_release); } } close_log{curve_log};
             size_t pos = 0;
             for (;; pos++) {
+                count.found.store(pos + 1, std::memory_order_release);
                 if (pos % stride == first) {
                     rv32::Snapshot snap = vm.snapshot();
                     std::unique_lock<std::mutex> lk(mu);
@@ -266,6 +333,8 @@ struct Executor {
             }
             std::vector<rv32::MemInitRow> rows;
             if (vm.halted) rows = vm.mem_rows();
+            count.found.store(pos + 1, std::memory_order_release);
+            count.final.store(true, std::memory_order_release);
             std::lock_guard<std::mutex> lk(mu);
             fast.n_total = pos + 1;
             fast.mem_rows = std::move(rows);
@@ -552,7 +621,7 @@ static void phase1_worker(const Lane &feeder, const DeviceKey &key, dvt_job *j, 
             q->queue.pop_front();
             q->cv.notify_all();   // (the feeder uploads the next shard)
         }
-        const int rc = dev != hipSuccess ? fail(me.err, DVT_ERR_DEVICE, "hipSetDevice: %s", hipGetErrorString(dev)) : shard_commit(c, key, j, *it.s, true);
+        const int rc = dev != hipSuccess ? fail(me.err, DVT_ERR_DEVICE, "hipSetDevice: %s", hipGetErrorString(dev)) : shard_commit(c, key, j, *it.s, true, &ex.count);
         ex.give_back(it.buf);
         if (rc) {
             ex.cancel();
@@ -662,7 +731,7 @@ static int commit_overlapped(const Lane &c, const DeviceKey &key, dvt_job *j, Ex
         // phase 1 of the previous shard runs while the copy engine brings this one in
         if (rc == DVT_OK && have_prev) {
             ShardJob &ps = part.shards[part.shards.size() - (got ? 2 : 1)];
-            rc = shard_commit(c, key, j, ps);
+            rc = shard_commit(c, key, j, ps, false, &ex.count);
             ex.give_back(prev_buf);
         }
         if (!got) { have_prev = false; break; }
@@ -675,7 +744,7 @@ static int commit_overlapped(const Lane &c, const DeviceKey &key, dvt_job *j, Ex
         prev_buf = r.buf;
     }
     if (rc == DVT_OK && have_prev) {
-        rc = shard_commit(c, key, j, part.shards.back());
+        rc = shard_commit(c, key, j, part.shards.back(), false, &ex.count);
         ex.give_back(prev_buf);
     }
     if (time_stages) fprintf(stderr, "[prepare] %.2f ms: phase 1 of the last shard done\n", ms_since(t_begin));
@@ -1193,6 +1262,21 @@ uint32_t dvt_rv32_job_shard_chips(const dvt_job *job, size_t shard) {
     return mask;
 }
 double dvt_rv32_job_exec_wait_seconds(const dvt_job *job) { return job ? job->t_exec_wait : 0.0; }
+// (read without the handle, like the getters above: between calls on the job, not during one)
+int dvt_rv32_job_shard_kept(const dvt_job *job, size_t shard) {
+    size_t m = 0;
+    const ShardJob *s = job ? const_cast<dvt_job *>(job)->at(shard, &m) : nullptr;
+    return s ? s->kept : -1;
+}
+uint64_t dvt_rv32_job_shard_kept_bytes(const dvt_job *job, size_t shard) {
+    const int tier = dvt_rv32_job_shard_kept(job, shard);
+    if (tier <= DVT_KEEP_NONE) return 0;
+    size_t m = 0;
+    const ShardJob *s = const_cast<dvt_job *>(job)->at(shard, &m);
+    uint64_t n = s->cache.tree_bytes();
+    if (tier == DVT_KEEP_FULL) n += s->cache.lde_bytes() + (s->d_cpu ? shard_k0_bytes(job, *s) : 0);
+    return n;
+}
 
 int dvt_rv32_commit_shard(dvt_prover *p, const dvt_pk *pk, dvt_job *job, size_t shard, uint32_t *header) {
     if (!p || !pk || !job || !header) return fail(p, DVT_ERR_INPUT, "bad argument");
@@ -1427,6 +1511,18 @@ int dvt_rv32_debug_device_traces(dvt_prover *p, const dvt_pk *pk, dvt_job *j, si
     if (!(*blob = reinterpret_cast<uint32_t *>(copy_out(w, blob_words)))) return fail(p, DVT_ERR_DEVICE, "out of host memory");
     *blob_words = w.size();
     return DVT_OK;
+}
+
+// test hook (host only, no device): the admission rule of "keep_phase1" (keep_plan.h) on the caller's figures
+int dvt_debug_keep_plan(int mode, uint64_t free_bytes, uint64_t total_bytes, uint64_t reserve_bytes, uint64_t full_bytes, uint64_t tree_bytes,
+                        uint64_t later_bytes, uint64_t remaining, int count_known, int64_t full_cap, uint64_t full_kept) {
+    KeepPlanIn in;
+    in.mode = mode == 0 || mode == 2 ? mode : 1;   // (as dvt_prover_create reads the key)
+    in.free_b = free_bytes; in.total_b = total_bytes; in.reserve = reserve_bytes;
+    in.full_b = full_bytes; in.tree_b = tree_bytes; in.later_b = later_bytes;
+    in.remaining = remaining; in.count_known = count_known != 0;
+    in.full_cap = full_cap; in.full_kept = full_kept;
+    return keep_plan(in);
 }
 
 // measurement hook (host only): guest cycles per second of the executor alone, fast mode (trace = 0: what the

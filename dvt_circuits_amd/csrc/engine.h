@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "challenger.h"
+#include "keep_plan.h"
 #include "machine.h"
 #include "proof.h"
 
@@ -186,24 +187,36 @@ struct ProvingKey {
     uint32_t prep_log_h = 0;  // log2 of the tallest preprocessed LDE
 };
 
-// Phase-1 results of one shard kept in HBM for phase 2 (main-trace LDEs + their Merkle tree), so that the
-// common-challenge protocol does not pay K1-K3 of the main trace twice.  Owned by the caller.
+// Phase-1 results of one shard kept in HBM for phase 2, so that the common-challenge protocol does not pay K1-K3 of the
+// main trace twice: the main-trace LDEs and their Merkle tree (KEEP_FULL), or the tree alone (KEEP_TREE, tree_only: phase 2
+// pays K1 again and hashes nothing).  Owned by the caller.
 struct MainCache {
     bool valid = false;
+    bool tree_only = false;      // no LDEs are kept: lde and lde_words stay empty
     DevPool *pool = nullptr;     // where lde / tree came from
     std::vector<uint32_t *> lde;  // one per chip trace, in trace order
     std::vector<size_t> lde_words;
     uint32_t *tree = nullptr;
     uint32_t log_h = 0;
     Digest root;
+    int tier() const { return !tree ? KEEP_NONE : tree_only ? KEEP_TREE : KEEP_FULL; }
     // buffers are reused by the next commit of a shard of the same shape (benchmarks prove the same job repeatedly)
-    bool fits(const std::vector<size_t> &words, uint32_t h) const { return tree && log_h == h && lde_words == words; }
+    bool fits(const std::vector<size_t> &words, uint32_t h, bool only_tree) const {
+        return tree && log_h == h && tree_only == only_tree && (only_tree || lde_words == words);
+    }
+    size_t tree_bytes() const { return tree ? (((size_t)2 << log_h) - 1) * 32 : 0; }
+    size_t lde_bytes() const {
+        size_t n = 0;
+        for (auto w : lde_words) n += w * 4;
+        return n;
+    }
     void release() {
         for (auto p : lde) if (p) { if (pool) pool->free(p); else (void)hipFree(p); }
         lde.clear();
         lde_words.clear();
         if (tree) { if (pool) pool->free(tree); else (void)hipFree(tree); }
         tree = nullptr;
+        tree_only = false;
         valid = false;
     }
 };
@@ -253,11 +266,12 @@ class Engine {
                      const StarkConfig &cfg, ShardProof *out, const PermChallenges *global = nullptr,
                      const MainCache *cached = nullptr);
     // phase 1 of a multi-shard proof: K1-K3 of the main traces only -> main_root; with keep != nullptr the
-    // LDEs and the tree stay in HBM (from this engine's pool, into *keep) for prove_shard(..., cached = keep).  `admitted`: a
+    // LDEs and the tree (tier KEEP_FULL) or the tree alone (KEEP_TREE: the LDEs are the arena's) stay in HBM (from this
+    // engine's pool, into *keep) for prove_shard(..., cached = keep).  keep == nullptr is KEEP_NONE.  `admitted`: a
     // lock the caller holds over "how much is free?" and the allocations that follow; it is released once every buffer of
     // the commit is allocated, before the first kernel is launched.
     bool commit_main_root(const ProvingKey &pk, const std::vector<ChipTrace> &traces, Digest *root, MainCache *keep = nullptr,
-                          std::unique_lock<std::mutex> *admitted = nullptr);
+                          std::unique_lock<std::mutex> *admitted = nullptr, int tier = KEEP_FULL);
 
     // ---- host side of the K4 running sum, K6, K7 and the K9 grind: prove_shard and the stage entry points (capi.hip) both
     // go through these.  Device words are in Montgomery form.

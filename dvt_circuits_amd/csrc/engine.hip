@@ -402,8 +402,10 @@ struct EventTimer {
 }  // namespace
 
 bool Engine::commit_main_root(const ProvingKey &pk, const std::vector<ChipTrace> &traces, Digest *root, MainCache *keep,
-                              std::unique_lock<std::mutex> *admitted) {
+                              std::unique_lock<std::mutex> *admitted, int tier) {
     times = StageTimes();
+    if (tier == KEEP_NONE) keep = nullptr;
+    const bool keep_lde = keep && tier == KEEP_FULL;   // (KEEP_TREE: the LDEs live in the arena for the length of this call)
     EventTimer t_all(stream, profile);
     HIPCHK(hipSetDevice(device));
     const MachineDesc *m = pk.vk.machine;
@@ -432,8 +434,13 @@ bool Engine::commit_main_root(const ProvingKey &pk, const std::vector<ChipTrace>
     if (keep) {
         std::vector<size_t> want;
         for (auto &t : traces) want.push_back(((size_t)m->chips[t.chip_id].main_w << t.log_n) * 2);
-        reuse = keep->fits(want, max_log_n + 1);
-        if (!reuse) { keep->release(); keep->lde_words = want; keep->pool = &pool; }
+        reuse = keep->fits(want, max_log_n + 1, !keep_lde);
+        if (!reuse) {
+            keep->release();
+            keep->tree_only = !keep_lde;
+            if (keep_lde) keep->lde_words = want;
+            keep->pool = &pool;
+        }
         keep->valid = false;
     }
     lap("cache decided");
@@ -444,9 +451,9 @@ bool Engine::commit_main_root(const ProvingKey &pk, const std::vector<ChipTrace>
         const ChipTrace &t = traces[ti];
         const ChipDesc &d = m->chips[t.chip_id];
         uint32_t *lde = nullptr;
-        if (keep && reuse) {
+        if (keep_lde && reuse) {
             lde = keep->lde[ti];
-        } else if (keep) {
+        } else if (keep_lde) {
             HIPCHK(pool.alloc(&lde, ((size_t)d.main_w << t.log_n) * 8));
             keep->lde.push_back(lde);
         } else {
@@ -627,8 +634,16 @@ bool Engine::prove_shard(const ProvingKey &pk, const std::vector<ChipTrace> &tra
     uint32_t *d_main_tree;
     uint32_t rootw[8];
     if (cached && cached->valid) {  // phase 1 already did K1-K3 of the main traces and kept the results
-        if (cached->lde.size() != cs.size() || cached->log_h != hmax) return fail("prove: main-trace cache does not match the shard");
-        for (size_t k = 0; k < cs.size(); k++) cs[k].main_lde = cached->lde[k];
+        if ((!cached->tree_only && cached->lde.size() != cs.size()) || cached->log_h != hmax || !cached->tree)
+            return fail("prove: main-trace cache does not match the shard");
+        if (cached->tree_only) {  // the tree alone was kept: K1 of the main traces again (into the arena), no hashing
+            for (auto &s : cs) {
+                ALLOC(s.main_lde, uint32_t, (size_t)s.d->main_w * 2 * s.n);
+                HIPCHK(lde(const_cast<uint32_t *>(s.main), d_scratch, s.main_lde, s.d->main_w, s.log_n, 0));
+            }
+        } else {
+            for (size_t k = 0; k < cs.size(); k++) cs[k].main_lde = cached->lde[k];
+        }
         d_main_tree = cached->tree;
         pf.main_root = cached->root;
     } else {

@@ -89,10 +89,10 @@ static void print_report(const dvt_profile_opcode *ops, const dvt_profile_syscal
 }
 
 int main(int argc, char **argv) {
-    if (argc < 2) return die("usage: dvt_prover_host prove|execute|verify|check|compact|expand --type T -i FILE [-o FILE] [--show-report] [--compact] [--elf FILE] [--devices D0,D1,...] [--device D]");
+    if (argc < 2) return die("usage: dvt_prover_host prove|execute|verify|check|compact|expand --type T -i FILE [-o FILE] [--show-report] [--compact] [--keep-trees] [--elf FILE] [--devices D0,D1,...] [--device D]");
     const std::string verb = argv[1];
     std::string type, input, output, elf_path, schema_path, devices, verify_device;
-    bool show_report = false, auth = false, compact = false;
+    bool show_report = false, auth = false, compact = false, keep_trees = false;
     for (int i = 2; i < argc; i++) {
         std::string a = argv[i], inline_val;
         bool has_inline = false;
@@ -109,6 +109,7 @@ int main(int argc, char **argv) {
         else if (a == "--device") verify_device = next();   // verify: the query part on that GPU (dvt_prover_verify)
         else if (a == "--show-report") show_report = true;
         else if (a == "--compact") compact = true;       // prove: shard proofs in the compact form ("compact_openings")
+        else if (a == "--keep-trees") keep_trees = true;  // prove / check: shards that do not fit in HBM in full keep their main Merkle tree ("keep_phase1": 2)
         else if (a == "--auth-commitment") auth = true;  // the reference selects this at build time (cargo feature)
         else if (a == "--json-schema-file") schema_path = next();
         else return die("unknown argument " + a);
@@ -199,8 +200,10 @@ int main(int argc, char **argv) {
     std::string cfg;
     if (!devices.empty()) cfg += "\"devices\": [" + devices + "]";
     if (compact) cfg += std::string(cfg.empty() ? "" : ", ") + "\"compact_openings\": 1";
+    if (keep_trees) cfg += std::string(cfg.empty() ? "" : ", ") + "\"keep_phase1\": 2";
+    const bool plain = cfg.empty();
     cfg = "{" + cfg + "}";
-    if (dvt_prover_create(devices.empty() && !compact ? nullptr : cfg.c_str(), &p)) return die(dvt_last_error(nullptr));
+    if (dvt_prover_create(plain ? nullptr : cfg.c_str(), &p)) return die(dvt_last_error(nullptr));
     dvt_pk *pk = nullptr;
     if (dvt_setup(p, elf.data(), elf.size(), &pk, nullptr, nullptr)) return die(dvt_last_error(p));
     if (verb == "check") {

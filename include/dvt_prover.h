@@ -51,8 +51,17 @@ typedef struct dvt_pk dvt_pk;
 /* ProverClient::from_env() (src/main.rs:438,461,481).  cfg_json may be NULL or
  * a JSON object: {"device":0,"fri_queries":100,"pow_bits":16,"profile":0,"log_shard_size":21,
  * "keep_phase1":1,"exec_threads":0,"parts_parallel_log":15}.  exec_threads = trace-mode executor threads of the prove pipeline
- * (0 = from the host's core count).  keep_phase1 = 0 makes phase 2 of a shard recompute K0 and the main-trace commitment
- * instead of keeping them in HBM (about 3 GB per 2^21-cycle shard) between the two phases.  parts_parallel_log: tables of
+ * (0 = from the host's core count).  "keep_phase1" is a mode: what a shard keeps in HBM between phase 1 and phase 2 (the
+ * tiers DVT_KEEP_* below).  0: nothing; phase 2 of a shard recomputes K0 and the main-trace commitment.  1 (the default, and
+ * what every value other than 0 and 2 reads as): K0 output, main LDEs and main Merkle tree (about 3 GB per 2^21-cycle
+ * shard) while more than 24 GB plus the room of the lanes not yet created is free, else nothing.  2: the same in full
+ * while that leaves every shard known to come room for its uploads and its tree; then the tree alone (268 MB per
+ * 2^21-cycle shard: phase 2 runs K0 and the main LDEs again and hashes nothing); then nothing.  The rule is
+ * dvt_debug_keep_plan.  Headers, shard proofs and containers are byte for byte the same in every mode and tier: the tier
+ * only decides which launches of the same kernels on the same inputs run once and which twice.
+ * "keep_full_max" (default -1 = no cap; a diagnostic key): at most that many shards per physical device and job are kept in
+ * full, so that jobs far smaller than HBM reach the other tiers of mode 2.  Modes 0 and 1 do not read it.
+ * parts_parallel_log: tables of
  * at most 2^parts_parallel_log rows compute their LogUp rows (K4) and quotient (K5) one constraint group per thread, taller
  * ones one row per thread; -1 = never, at most 15 (DVT_ERR_INPUT above).  The proof bytes do not depend on it.
  * "verify_chunk_words" (default 4194304; 0 or less is DVT_ERR_INPUT): proof words per chunk of dvt_prover_verify's device
@@ -117,7 +126,8 @@ void dvt_free(void *ptr);
  * 9: dvt_stage_hunt_cells, dvt_stage_hunt_pairs, dvt_rv32_hunt_shard, dvt_rv32_job_shard_chip_shape;
  * 10: dvt_stage_hunt_join_*, dvt_rv32_hunt_join_job; 11: "compact_openings", dvt_proof_compact, dvt_proof_expand,
  * dvt_stage_multipath_nodes, dvt_stage_verify_multipath, dvt_debug_compact_list_sweep; 12: dvt_rv32_job_profile,
- * dvt_execute_profile) */
+ * dvt_execute_profile; 13: "keep_phase1": 2, "keep_full_max", DVT_KEEP_*, dvt_rv32_job_shard_kept,
+ * dvt_rv32_job_shard_kept_bytes, dvt_debug_keep_plan) */
 uint32_t dvt_abi_version(void);
 /* the handle's hipStream_t (for event timing by the caller) */
 void *dvt_stream(dvt_prover *p);
@@ -566,6 +576,19 @@ uint32_t dvt_rv32_job_shard_chips(const dvt_job *job, size_t shard);
 /* width and height (log2 of the rows) of the main trace of chip `chip` of that shard; DVT_ERR_INPUT when the job does not hold
  * the shard, the shard has no table of that chip, or a pointer is NULL.  Host-only. */
 int dvt_rv32_job_shard_chip_shape(const dvt_job *job, size_t shard, uint32_t chip, uint32_t *main_w, uint32_t *log_n);
+/* What a committed shard keeps in HBM for phase 2 ("keep_phase1" at dvt_prover_create).  The proof bytes are identical in
+ * every tier. */
+#define DVT_KEEP_NONE 0 /* nothing: phase 2 runs K0, the main LDEs and the main commitment again */
+#define DVT_KEEP_TREE 1 /* the main Merkle tree and its root: phase 2 runs K0 and the main LDEs again, hashes nothing */
+#define DVT_KEEP_FULL 2 /* K0 output, main LDEs and tree: phase 2 starts at the permutation trace */
+/* the tier of shard `shard` (global position) from its last phase 1 (inside prepare, commit_shard or prove_job); a shard
+ * keeps its buffers, and with them its tier, until the job is freed.  -1 when the job does not hold the shard or no
+ * phase 1 of it has run.  Like the getters above it takes no lock: call it between calls on the job. */
+int dvt_rv32_job_shard_kept(const dvt_job *job, size_t shard);
+/* the bytes that tier holds in HBM: the tree, ((2 << hmax) - 1) * 32 with hmax = 1 + the largest log_n of the shard's
+ * chips, for DVT_KEEP_TREE; tree + main LDEs (8 * main_w << log_n per chip) + the K0 buffers for DVT_KEEP_FULL; else 0.
+ * (Sizes asked for: the buffer cache may hand out slightly larger buffers.) */
+uint64_t dvt_rv32_job_shard_kept_bytes(const dvt_job *job, size_t shard);
 int dvt_rv32_commit_shard(dvt_prover *p, const dvt_pk *pk, dvt_job *job, size_t shard, uint32_t *header);
 int dvt_rv32_challenges(const uint8_t *vk, size_t vk_len, const uint32_t *headers, size_t n_shards, uint32_t out[8]);
 int dvt_rv32_prove_shard(dvt_prover *p, const dvt_pk *pk, dvt_job *job, size_t shard, const uint32_t challenges[8],
@@ -738,6 +761,20 @@ int dvt_debug_compact_list_sweep(const uint8_t *vk, size_t vk_len, const uint8_t
  * out[4] = downloads (2..4: HIP events, summed over the chunks), out[5] = host time spent waiting for the device,
  * out[6] = Poseidon2 permutations, out[7] = kernel launches, out[8] = chunks. */
 int dvt_prover_verify_times(dvt_prover *p, double out[9]);
+/* test hook, host only, no device: the admission rule of "keep_phase1" on the caller's figures; returns DVT_KEEP_*.
+ *   mode 0: NONE.   mode 1 (and every value other than 0 and 2): FULL if free > reserve, else NONE.
+ *   mode 2: FULL if free > reserve + (full - tree) + remaining * later, and (count_known or free > floor(3 total / 4)),
+ *           and (full_cap < 0 or full_kept < full_cap); otherwise TREE if free > reserve; otherwise NONE.
+ * free: bytes free on the device, the committing lane's cached buffers included; total: the device's bytes; reserve: 24 GB
+ * plus the room of the lanes not yet created; full, tree: what this shard keeps in each tier; later: what every later
+ * shard takes at least (its tree and what its upload allocates, estimated by this shard's); remaining: the shards the
+ * members on this physical device are known to have still to commit in this prepare, after this one; count_known: the
+ * executor's fast pass has finished, so `remaining` is exact (outside a prepare: remaining 0, known); full_cap
+ * ("keep_full_max") and full_kept: the cap and the count of shards kept in full on the device in this job.  A sum that
+ * leaves 64 bits counts as "does not fit". */
+int dvt_debug_keep_plan(int mode, uint64_t free_bytes, uint64_t total_bytes, uint64_t reserve_bytes, uint64_t full_bytes,
+                        uint64_t tree_bytes, uint64_t later_bytes, uint64_t remaining, int count_known, int64_t full_cap,
+                        uint64_t full_kept);
 /* measurement hook, host only: guest cycles per second of the executor alone; trace = 0: fast mode (the sequential
  * pass of the prove pipeline), 1: trace mode (48-byte record per cycle).  0.0 when the guest does not halt. */
 double dvt_debug_exec_rate(const uint8_t *elf, size_t elf_len, const dvt_buf *stdin_bufs, size_t nbuf, uint32_t log_shard,
