@@ -179,6 +179,10 @@ def load():
     prof_out = [C.POINTER(u64), sz, C.POINTER(ProfileEdge), sz, C.POINTER(ProfileSyscall), sz, C.POINTER(ProfileOpcode), sz, C.POINTER(ProfileSummary)]
     lib.dvt_rv32_job_profile.argtypes = [vp, vp, vp, u32] + prof_out
     lib.dvt_execute_profile.argtypes = [C.c_char_p, sz, C.POINTER(Buf), sz, u64] + prof_out + [C.POINTER(Report), C.POINTER(C.c_char_p)]
+    tree_out = [C.POINTER(CalltreeArc), sz, C.POINTER(CalltreeFunc), sz, C.POINTER(CalltreeSummary)]
+    lib.dvt_rv32_job_calltree.argtypes = [vp, vp, vp, u32] + tree_out
+    lib.dvt_rv32_job_calltree_times.argtypes = [vp, C.POINTER(C.c_double)]
+    lib.dvt_execute_calltree.argtypes = [C.c_char_p, sz, C.POINTER(Buf), sz, u64] + tree_out + [C.POINTER(Report), C.POINTER(C.c_char_p)]
     lib.dvt_stdin_from_json.argtypes = [C.c_char_p, C.c_char_p, sz, C.c_int, C.POINTER(u8p), C.POINTER(sz), C.POINTER(C.c_char_p)]
     _lib = lib
     return lib
@@ -410,6 +414,57 @@ def execute_profile(elf: bytes, stdin=(), max_cycles=0):
         return lib.dvt_execute_profile(elf, len(elf), bufs, len(stdin), max_cycles, *out, C.byref(rep), C.byref(err))
     rc, prof = _profile(call)
     return rc, dict(cycles=rep.cycles, exit_code=rep.exit_code, halted=bool(rep.halted), unprovable=bool(rep.unprovable)), prof, _take_str(lib, err)
+
+
+class CalltreeArc(C.Structure):
+    _fields_ = [("caller_pc", C.c_uint32), ("callee_pc", C.c_uint32), ("calls", C.c_uint64), ("cycles", C.c_uint64)]
+
+
+class CalltreeFunc(C.Structure):
+    _fields_ = [("pc", C.c_uint32), ("pad", C.c_uint32), ("calls", C.c_uint64), ("inclusive", C.c_uint64), ("self", C.c_uint64)]
+
+
+class CalltreeSummary(C.Structure):
+    _fields_ = [("cycles", C.c_uint64), ("n_frames", C.c_uint64), ("dropped_frames", C.c_uint64), ("dropped_cycles", C.c_uint64),
+                ("unmatched_returns", C.c_uint64), ("text_base", C.c_uint32), ("n_instr", C.c_uint32), ("n_arcs", C.c_uint32),
+                ("n_funcs", C.c_uint32), ("max_depth", C.c_uint32), ("open_at_exit", C.c_uint32), ("shards_total", C.c_uint32), ("ms", C.c_float)]
+
+
+NO_FN = 0xffffffff   # caller_pc of the root's arc
+
+
+def _calltree(call):
+    """The call-tree report through call(arcs, cap_arcs, funcs, cap_funcs, summary) -> rc: once for the sizes, once for the
+    tables.  Returns (rc, report), report = None when a call fails without a summary, else dict(summary, arcs = [(caller_pc or
+    None for the root, callee_pc, calls, cycles)], funcs = [(pc, calls, inclusive, self)])."""
+    s = CalltreeSummary()
+    rc = call(None, 0, None, 0, C.byref(s))
+    if rc not in (DVT_OK, DVT_ERR_GUEST):
+        return rc, None
+    n_arcs, n_funcs = int(s.n_arcs), int(s.n_funcs)
+    arcs, funcs = (CalltreeArc * max(n_arcs, 1))(), (CalltreeFunc * max(n_funcs, 1))()
+    rc = call(arcs, n_arcs, funcs, n_funcs, C.byref(s))
+    if rc not in (DVT_OK, DVT_ERR_GUEST):
+        return rc, None
+    summary = {name: (float if name == "ms" else int)(getattr(s, name)) for name, _ in CalltreeSummary._fields_}
+    a = np.frombuffer(arcs, np.dtype([("caller", "<u4"), ("callee", "<u4"), ("calls", "<u8"), ("cycles", "<u8")]))[:min(n_arcs, int(s.n_arcs))].tolist()
+    f = np.frombuffer(funcs, np.dtype([("pc", "<u4"), ("pad", "<u4"), ("calls", "<u8"), ("inclusive", "<u8"), ("self", "<u8")]))[:min(n_funcs, int(s.n_funcs))].tolist()
+    return rc, dict(summary=summary, arcs=[(None if c == NO_FN else c, d, n, cyc) for c, d, n, cyc in a],
+                    funcs=[(pc, n, inc, own) for pc, _, n, inc, own in f])
+
+
+def execute_calltree(elf: bytes, stdin=(), max_cycles=0):
+    """Host-only call-tree report (dvt_execute_calltree): inclusive and self cycles per function and per caller -> callee arc.
+    Returns (rc, report dict as execute() gives it, call-tree dict as Prover.job_calltree gives it or None, error text)."""
+    lib = load()
+    rep, err, bufs = Report(), C.c_char_p(), _bufs(stdin)
+
+    def call(*out):
+        if err.value:
+            lib.dvt_free(C.cast(err, C.c_void_p))
+        return lib.dvt_execute_calltree(elf, len(elf), bufs, len(stdin), max_cycles, *out, C.byref(rep), C.byref(err))
+    rc, tree = _calltree(call)
+    return rc, dict(cycles=rep.cycles, exit_code=rep.exit_code, halted=bool(rep.halted), unprovable=bool(rep.unprovable)), tree, _take_str(lib, err)
 
 
 def exec_rate(elf: bytes, stdin=(), log_shard=21, trace=False) -> float:
@@ -1065,6 +1120,21 @@ class Prover:
         rc, prof = _profile(lambda *out: self.lib.dvt_rv32_job_profile(self.h, pk, job, log_edge_slots, *out))
         self.check(rc)
         return prof
+
+    def job_calltree(self, pk, job, log_arc_slots=0):
+        """The call-tree report of a prepared job that holds every shard of its execution, from its cycle records on the GPU
+        (dvt_rv32_job_calltree): dict(summary, arcs = [(caller_pc or None for the root, callee_pc, calls, cycles)] sorted,
+        funcs = [(pc, calls, inclusive, self)] by self descending).  log_arc_slots bounds the table of the arcs (0 = sized
+        from the text); what it cannot hold is counted in summary["dropped_frames"], and funcs is then empty."""
+        rc, tree = _calltree(lambda *out: self.lib.dvt_rv32_job_calltree(self.h, pk, job, log_arc_slots, *out))
+        self.check(rc)
+        return tree
+
+    def job_calltree_times(self):
+        """milliseconds of the last job_calltree: dict(summary_ms, merge_ms, emit_ms)"""
+        out = (C.c_double * 3)()
+        self.check(self.lib.dvt_rv32_job_calltree_times(self.h, out))
+        return dict(summary_ms=out[0], merge_ms=out[1], emit_ms=out[2])
 
     def bus_ledger(self, machine, log_buckets=20, cap_slots=1 << 16, seed=1):
         """a BusLedger on this handle: which tuples of the LogUp buses do not cancel over the tables it is given"""

@@ -1,9 +1,10 @@
 // The inspectors of trace rows of the C ABI (include/dvt_prover.h): row checks, bus ledger, forgery hunt, join hunt.  Each has
 // stage entry points (dvt_stage_*) on a table the caller uploaded (stage_table) and job entry points (dvt_rv32_*) on the
-// tables of a prepared job's held shards (shard_view).  The execution report (profile.h) is the one inspector that reads a
-// job's cycle records instead of its tables.
+// tables of a prepared job's held shards (shard_view).  The execution report (profile.h) and the call-tree report (calltree.h)
+// are the inspectors that read a job's cycle records instead of its tables.
 #include <algorithm>
 
+#include "calltree.h"
 #include "capi_job.h"
 #include "ledger_key.h"
 #include "profile.h"
@@ -324,28 +325,204 @@ static int job_profile(dvt_prover *p, const dvt_pk *pk, dvt_job *j, uint32_t log
     return DVT_OK;
 }
 
-extern "C" {
+// ------------------------------------------------------------------ the call-tree report (dvt_rv32_job_calltree)
+// Three runs of one kernel body over every span of every shard (calltree.hip), each member on lane 0's stream with buffers
+// from lane 0's pool, and the host between them: summary mode for {u, c} per span; summary mode again, writing the unmatched
+// calls at the offsets the host made of the c's; the merge of the spans in execution order, which keeps the global stack and
+// hands every span the frames it can pop; emit mode.  The frames still open after the last record are closed on the host.
+namespace {
+struct CalltreeMember {
+    StageBuf base, calls, frames;
+    std::vector<size_t> span0;                        // of the member's k-th shard
+    size_t spans = 0, total_calls = 0;
+    std::vector<CalltreeSpanSummary> summaries;
+    std::vector<unsigned long long> calls_at;
+    std::vector<CalltreeCall> h_calls;
+    std::vector<CalltreeSpanIn> span_in;
+    std::vector<CalltreeFrame> h_frames;
+    CalltreeTables tb{};
+    unsigned long long *d_calls_at = nullptr;
+    CalltreeSpanIn *d_span_in = nullptr;
+    explicit CalltreeMember(DevPool &pool) : base{pool}, calls{pool}, frames{pool} {}
+};
+// the members' buffers go back to their pools under their own device's turn
+struct CalltreeRun {
+    dvt_prover *p;
+    std::vector<std::unique_ptr<CalltreeMember>> mem;
+    ~CalltreeRun() {
+        for (size_t m = 0; m < mem.size(); m++) {
+            (void)turn_to(p, m);
+            mem[m].reset();
+        }
+        (void)turn_to(p, 0);
+    }
+};
+}  // namespace
 
-// ---- the execution report (profile.h)
-int dvt_rv32_job_profile(dvt_prover *p, const dvt_pk *pk, dvt_job *job, uint32_t log_edge_slots, uint64_t *pc_count, size_t cap_pc,
-                         dvt_profile_edge *edges, size_t cap_edges, dvt_profile_syscall *sys, size_t cap_sys, dvt_profile_opcode *ops,
-                         size_t cap_ops, dvt_profile_summary *summary) {
-    const prof::Out out{pc_count, cap_pc, edges, cap_edges, sys, cap_sys, ops, cap_ops, summary};
-    if (!p || !pk || !job || !summary || out.null_array()) return fail(p, DVT_ERR_INPUT, "null argument");
-    if (int rc = rv32_key(p, pk)) return rc;
-    if (log_edge_slots && (log_edge_slots < prof::MIN_LOG_SLOTS || log_edge_slots > prof::MAX_LOG_SLOTS))
-        return fail(p, DVT_ERR_INPUT, "log_edge_slots %u (0 or %u..%u)", log_edge_slots, prof::MIN_LOG_SLOTS, prof::MAX_LOG_SLOTS);
-    Guard g(p); if (g.rc) return g.rc;
-    return job_profile(p, pk, job, log_edge_slots, out);
+static int job_calltree(dvt_prover *p, const dvt_pk *pk, dvt_job *j, uint32_t log_arc_slots, const calltree::Out &out) {
+    if (int rc = same_members(p, pk, j)) return rc;
+    if (j->first != 0 || j->stride != 1 || j->held() != j->n_total)
+        return fail(p, DVT_ERR_UNSUPPORTED, "the job holds %zu of the %zu shards of its execution (first %zu, stride %zu): the call stack across a gap is unknown",
+                    j->held(), j->n_total, j->first, j->stride);
+    const auto t0 = Clock::now();
+    calltree::State st(pk->prog);
+    const size_t n = st.classes.size(), G = n_members(p);
+    uint32_t log_slots = log_arc_slots;
+    if (!log_slots)
+        for (log_slots = prof::DEFAULT_MIN_LOG_SLOTS; log_slots < prof::MAX_LOG_SLOTS && ((size_t)1 << log_slots) < 4 * n;) log_slots++;
+    const size_t S = (size_t)1 << log_slots;
+    const uint32_t entry = prof::index_of_pc(pk->prog, pk->prog.entry);
+    if (entry == prof::NO_SUCC) return fail(p, DVT_ERR_INPUT, "the entry 0x%08x is no instruction of the text", pk->prog.entry);
+    auto succ_of = [&](const ShardJob &s) { return prof::index_of_pc(pk->prog, s.next_pc); };
+    CalltreeRun run{p, {}};
+
+    // ---- summary mode: {u, c} of every span
+    for (size_t m = 0; m < G; m++) {
+        if (int rc = turn_to(p, m)) return rc;
+        const Lane c = lane0(p, m);
+        Engine &e = c.eng;
+        run.mem.emplace_back(new CalltreeMember(e.pool));
+        CalltreeMember &cm = *run.mem.back();
+        for (auto &s : j->parts[m].shards) {
+            cm.span0.push_back(cm.spans);
+            cm.spans += (s.n_recs + CALLTREE_SPAN - 1) / CALLTREE_SPAN;
+        }
+        if (!cm.spans) continue;
+        // 64-bit words: counters, arc calls, arc cycles | arc keys | calls_at | span_in (two each) | summaries; then the classes
+        const size_t zero_words = CALLTREE_COUNTERS + 2 * S, words = zero_words + S + 4 * cm.spans;
+        HIP_TRY(c.err, e.pool.alloc_bytes(&cm.base.ptr, words * 8 + n * 4));
+        unsigned long long *d = static_cast<unsigned long long *>(cm.base.ptr);
+        CalltreeTables &tb = cm.tb;
+        tb.counters = d; tb.arc_calls = d + CALLTREE_COUNTERS; tb.arc_cycles = tb.arc_calls + S; tb.arc_keys = d + zero_words;
+        cm.d_calls_at = tb.arc_keys + S;
+        cm.d_span_in = reinterpret_cast<CalltreeSpanIn *>(cm.d_calls_at + cm.spans);
+        tb.summaries = reinterpret_cast<CalltreeSpanSummary *>(cm.d_calls_at + 3 * cm.spans);
+        uint32_t *d_classes = reinterpret_cast<uint32_t *>(d + words);
+        tb.classes = d_classes; tb.n_instr = (uint32_t)n; tb.log_slots = log_slots;
+        HIP_TRY(c.err, hipMemsetAsync(d, 0, zero_words * 8, e.stream));
+        HIP_TRY(c.err, hipMemsetAsync(tb.arc_keys, 0xff, S * 8, e.stream));
+        HIP_TRY(c.err, hipMemcpyAsync(d_classes, st.classes.data(), n * 4, hipMemcpyHostToDevice, e.stream));
+        for (size_t k = 0; k < cm.span0.size(); k++) {
+            const ShardJob &s = j->parts[m].shards[k];
+            HIP_TRY(c.err, launch_calltree_summary(e.stream, s.d_recs, s.n_recs, succ_of(s), cm.span0[k], tb));
+        }
+        cm.summaries.resize(cm.spans);
+        if (!e.download(cm.summaries.data(), tb.summaries, cm.spans * sizeof(CalltreeSpanSummary))) return engine_fail(c.err, e);
+        cm.calls_at.resize(cm.spans);
+        for (size_t i = 0; i < cm.spans; i++) {
+            if (cm.summaries[i].u > CALLTREE_SPAN || cm.summaries[i].c > CALLTREE_SPAN) return fail(p, DVT_ERR_DEVICE, "span summary out of range");
+            cm.calls_at[i] = cm.total_calls;
+            cm.total_calls += cm.summaries[i].c;
+        }
+    }
+    // ---- summary mode again: the unmatched calls of the shards that have any, at those offsets
+    for (size_t m = 0; m < G; m++) {
+        CalltreeMember &cm = *run.mem[m];
+        if (!cm.total_calls) continue;
+        if (int rc = turn_to(p, m)) return rc;
+        const Lane c = lane0(p, m);
+        Engine &e = c.eng;
+        HIP_TRY(c.err, e.pool.alloc_bytes(&cm.calls.ptr, cm.total_calls * sizeof(CalltreeCall)));
+        CalltreeTables tb = cm.tb;
+        tb.calls_at = cm.d_calls_at;
+        tb.calls = static_cast<CalltreeCall *>(cm.calls.ptr);
+        HIP_TRY(c.err, hipMemcpyAsync(cm.d_calls_at, cm.calls_at.data(), cm.spans * 8, hipMemcpyHostToDevice, e.stream));
+        for (size_t k = 0; k < cm.span0.size(); k++) {
+            const ShardJob &s = j->parts[m].shards[k];
+            const size_t end = k + 1 < cm.span0.size() ? cm.span0[k + 1] : cm.spans;
+            size_t n_calls = 0;
+            for (size_t i = cm.span0[k]; i < end; i++) n_calls += cm.summaries[i].c;
+            if (n_calls) HIP_TRY(c.err, launch_calltree_summary(e.stream, s.d_recs, s.n_recs, succ_of(s), cm.span0[k], tb));
+        }
+        cm.h_calls.resize(cm.total_calls);
+        if (!e.download(cm.h_calls.data(), tb.calls, cm.total_calls * sizeof(CalltreeCall))) return engine_fail(c.err, e);
+    }
+    const double ms_summary = ms_since(t0);
+
+    // ---- the merge: the spans in execution order, over all shards in job order, whichever member holds them
+    const auto t1 = Clock::now();
+    std::vector<uint64_t> base_of(j->n_total);   // global position of the shard's first record
+    uint64_t cycles = 0;
+    st.stack.push_back(calltree::Frame{entry, 0});
+    for (size_t pos = 0; pos < j->n_total; pos++) {
+        size_t m = 0;
+        const ShardJob *s = j->at(pos, &m);
+        if (!s) return fail(p, DVT_ERR_UNSUPPORTED, "the job does not hold shard %zu", pos);
+        CalltreeMember &cm = *run.mem[m];
+        const size_t k = (size_t)(s - j->parts[m].shards.data());
+        base_of[pos] = cycles;
+        const size_t n_spans = (s->n_recs + CALLTREE_SPAN - 1) / CALLTREE_SPAN;
+        if (cm.span_in.empty()) cm.span_in.resize(cm.spans);
+        for (size_t i = 0; i < n_spans; i++) {
+            const size_t span = cm.span0[k] + i;
+            const CalltreeSpanSummary sum = cm.summaries[span];
+            const size_t depth = st.stack.size(), n_in = std::min<size_t>((size_t)sum.u + 1, depth), pops = std::min<size_t>(sum.u, depth - 1);
+            cm.span_in[span] = CalltreeSpanIn{cm.h_frames.size(), (uint32_t)n_in, (uint32_t)std::min<size_t>(depth, 0xffffffffu)};
+            for (size_t f = 0; f < n_in; f++) cm.h_frames.push_back(CalltreeFrame{st.stack[depth - 1 - f].open, st.stack[depth - 1 - f].fn, 0});
+            st.stack.resize(depth - pops);
+            const uint64_t span_pos = cycles + i * CALLTREE_SPAN;
+            for (uint32_t q = 0; q < sum.c; q++) {
+                const CalltreeCall &call = cm.h_calls[cm.calls_at[span] + q];
+                st.stack.push_back(calltree::Frame{call.fn, span_pos + call.pos + 1});
+            }
+        }
+        cycles += s->n_recs;
+    }
+    const double ms_merge = ms_since(t1);
+
+    // ---- emit mode
+    const auto t2 = Clock::now();
+    unsigned long long bad = 0;
+    for (size_t m = 0; m < G; m++) {
+        CalltreeMember &cm = *run.mem[m];
+        if (!cm.spans) continue;
+        if (int rc = turn_to(p, m)) return rc;
+        const Lane c = lane0(p, m);
+        Engine &e = c.eng;
+        HIP_TRY(c.err, e.pool.alloc_bytes(&cm.frames.ptr, cm.h_frames.size() * sizeof(CalltreeFrame)));
+        CalltreeTables tb = cm.tb;
+        tb.span_in = cm.d_span_in;
+        tb.frames = static_cast<const CalltreeFrame *>(cm.frames.ptr);
+        HIP_TRY(c.err, hipMemcpyAsync(cm.d_span_in, cm.span_in.data(), cm.spans * sizeof(CalltreeSpanIn), hipMemcpyHostToDevice, e.stream));
+        HIP_TRY(c.err, hipMemcpyAsync(cm.frames.ptr, cm.h_frames.data(), cm.h_frames.size() * sizeof(CalltreeFrame), hipMemcpyHostToDevice, e.stream));
+        for (size_t k = 0; k < cm.span0.size(); k++) {
+            const ShardJob &s = j->parts[m].shards[k];
+            HIP_TRY(c.err, launch_calltree_emit(e.stream, s.d_recs, s.n_recs, succ_of(s), cm.span0[k], base_of[s.index - 1], tb));
+        }
+        std::vector<unsigned long long> h(CALLTREE_COUNTERS + 3 * S);
+        if (!e.download(h.data(), tb.counters, h.size() * 8)) return engine_fail(c.err, e);
+        const unsigned long long *calls = h.data() + CALLTREE_COUNTERS, *cyc = calls + S, *keys = cyc + S;
+        for (size_t q = 0; q < S; q++)
+            if (keys[q] != ~0ull && calls[q]) {
+                calltree::Arc &a = st.arcs[{(uint32_t)(keys[q] >> 32), (uint32_t)keys[q]}];
+                a.calls += calls[q];
+                a.cycles += cyc[q];
+            }
+        st.dropped_frames += h[CALLTREE_DROPPED_FRAMES];
+        st.dropped_cycles += h[CALLTREE_DROPPED_CYCLES];
+        st.unmatched_returns += h[CALLTREE_UNMATCHED];
+        st.max_depth = std::max(st.max_depth, (uint32_t)h[CALLTREE_MAX_DEPTH]);
+        bad += h[CALLTREE_BAD_RECORDS];
+    }
+    if (turn_to(p, 0)) return DVT_ERR_DEVICE;
+    if (bad) return fail(p, DVT_ERR_INPUT, "%llu cycle records name an instruction outside the text", bad);
+    st.cycles = cycles;
+    if (!cycles) st.stack.clear();   // (nothing retired: no root)
+    st.max_depth = std::max(st.max_depth, (uint32_t)st.stack.size());
+    st.finish();
+    p->calltree_ms[0] = ms_summary; p->calltree_ms[1] = ms_merge; p->calltree_ms[2] = ms_since(t2);
+    calltree::emit(pk->prog, st, (uint32_t)j->n_total, ms_since(t0), out);
+    return DVT_OK;
 }
 
-// host-only: the guest in trace mode, one shard's records at a time through the same rule (prof::tally_records)
-int dvt_execute_profile(const uint8_t *elf, size_t elf_len, const dvt_buf *stdin_bufs, size_t nbuf, uint64_t max_cycles, uint64_t *pc_count,
-                        size_t cap_pc, dvt_profile_edge *edges, size_t cap_edges, dvt_profile_syscall *sys, size_t cap_sys,
-                        dvt_profile_opcode *ops, size_t cap_ops, dvt_profile_summary *summary, dvt_report *report, char **err_text) {
-    if (err_text) *err_text = nullptr;
-    const prof::Out out{pc_count, cap_pc, edges, cap_edges, sys, cap_sys, ops, cap_ops, summary};
-    if (!elf || (nbuf && !stdin_bufs) || !summary || out.null_array()) return DVT_ERR_INPUT;
+// The host-only reports (no GPU is touched): the guest in trace mode, where an instruction without a chip is recorded instead
+// of trapping, 2^21 cycles per shard and one shard's records in memory at a time.  begin(prog) once the ELF is loaded;
+// shard(prog, recs, n, last_succ) per shard in execution order; end(prog, ms) after the last, and a text it returns fails the
+// call with DVT_ERR_UNSUPPORTED.  Return codes, *report and *err_text as dvt_execute gives them; end runs for whatever retired,
+// also when the guest fails.
+template <class Begin, class Shard, class End>
+static int execute_traced(const uint8_t *elf, size_t elf_len, const dvt_buf *stdin_bufs, size_t nbuf, uint64_t max_cycles, dvt_report *report,
+                          char **err_text, Begin begin, Shard shard, End end) {
     const auto t0 = Clock::now();
     rv32::Program prog;
     std::string err;
@@ -362,10 +539,10 @@ int dvt_execute_profile(const uint8_t *elf, size_t elf_len, const dvt_buf *stdin
     const std::unique_ptr<rv32::CycleRec[]> recs(new rv32::CycleRec[(size_t)1 << LOG_SHARD]);   // (pages a short run never touches cost nothing)
     rv32::ShardOut so;
     so.recs = recs.get();
-    prof::Tally t(prog);
+    begin(prog);
     for (;;) {
         vm.run_shard(true, &so, max_cycles ? max_cycles : ~0ull);
-        prof::tally_records(prog, so.recs, so.n_recs, prof::index_of_pc(prog, so.next_pc), &t);
+        shard(prog, so.recs, so.n_recs, prof::index_of_pc(prog, so.next_pc));
         if (vm.halted || !vm.error.empty() || !vm.next_shard()) break;
     }
     if (report) {
@@ -374,8 +551,8 @@ int dvt_execute_profile(const uint8_t *elf, size_t elf_len, const dvt_buf *stdin
         report->halted = vm.halted;
         report->unprovable = vm.unsupported;
     }
-    if (!prof::emit(prog, t, t.shards, ms_since(t0), out)) {
-        if (err_text) *err_text = strdup("more than 64 distinct syscall ids");
+    if (const char *why = end(prog, ms_since(t0))) {
+        if (err_text) *err_text = strdup(why);
         return DVT_ERR_UNSUPPORTED;
     }
     if (!vm.error.empty()) {
@@ -387,6 +564,76 @@ int dvt_execute_profile(const uint8_t *elf, size_t elf_len, const dvt_buf *stdin
         return DVT_ERR_GUEST;
     }
     return DVT_OK;
+}
+
+extern "C" {
+
+// ---- the execution report (profile.h)
+int dvt_rv32_job_profile(dvt_prover *p, const dvt_pk *pk, dvt_job *job, uint32_t log_edge_slots, uint64_t *pc_count, size_t cap_pc,
+                         dvt_profile_edge *edges, size_t cap_edges, dvt_profile_syscall *sys, size_t cap_sys, dvt_profile_opcode *ops,
+                         size_t cap_ops, dvt_profile_summary *summary) {
+    const prof::Out out{pc_count, cap_pc, edges, cap_edges, sys, cap_sys, ops, cap_ops, summary};
+    if (!p || !pk || !job || !summary || out.null_array()) return fail(p, DVT_ERR_INPUT, "null argument");
+    if (int rc = rv32_key(p, pk)) return rc;
+    if (log_edge_slots && (log_edge_slots < prof::MIN_LOG_SLOTS || log_edge_slots > prof::MAX_LOG_SLOTS))
+        return fail(p, DVT_ERR_INPUT, "log_edge_slots %u (0 or %u..%u)", log_edge_slots, prof::MIN_LOG_SLOTS, prof::MAX_LOG_SLOTS);
+    Guard g(p); if (g.rc) return g.rc;
+    return job_profile(p, pk, job, log_edge_slots, out);
+}
+
+// host-only: the same rule (prof::tally_records) over execute_traced's shards
+int dvt_execute_profile(const uint8_t *elf, size_t elf_len, const dvt_buf *stdin_bufs, size_t nbuf, uint64_t max_cycles, uint64_t *pc_count,
+                        size_t cap_pc, dvt_profile_edge *edges, size_t cap_edges, dvt_profile_syscall *sys, size_t cap_sys,
+                        dvt_profile_opcode *ops, size_t cap_ops, dvt_profile_summary *summary, dvt_report *report, char **err_text) {
+    if (err_text) *err_text = nullptr;
+    const prof::Out out{pc_count, cap_pc, edges, cap_edges, sys, cap_sys, ops, cap_ops, summary};
+    if (!elf || (nbuf && !stdin_bufs) || !summary || out.null_array()) return DVT_ERR_INPUT;
+    std::unique_ptr<prof::Tally> t;
+    return execute_traced(
+        elf, elf_len, stdin_bufs, nbuf, max_cycles, report, err_text, [&](const rv32::Program &prog) { t.reset(new prof::Tally(prog)); },
+        [&](const rv32::Program &prog, const rv32::CycleRec *recs, size_t n, uint32_t last_succ) { prof::tally_records(prog, recs, n, last_succ, t.get()); },
+        [&](const rv32::Program &prog, double ms) { return prof::emit(prog, *t, t->shards, ms, out) ? nullptr : "more than 64 distinct syscall ids"; });
+}
+
+// ---- the call-tree report (calltree.h)
+int dvt_rv32_job_calltree(dvt_prover *p, const dvt_pk *pk, dvt_job *job, uint32_t log_arc_slots, dvt_calltree_arc *arcs, size_t cap_arcs,
+                          dvt_calltree_func *funcs, size_t cap_funcs, dvt_calltree_summary *summary) {
+    const calltree::Out out{arcs, cap_arcs, funcs, cap_funcs, summary};
+    if (!p || !pk || !job || !summary || out.null_array()) return fail(p, DVT_ERR_INPUT, "null argument");
+    if (int rc = rv32_key(p, pk)) return rc;
+    if (log_arc_slots && (log_arc_slots < prof::MIN_LOG_SLOTS || log_arc_slots > prof::MAX_LOG_SLOTS))
+        return fail(p, DVT_ERR_INPUT, "log_arc_slots %u (0 or %u..%u)", log_arc_slots, prof::MIN_LOG_SLOTS, prof::MAX_LOG_SLOTS);
+    Guard g(p); if (g.rc) return g.rc;
+    return job_calltree(p, pk, job, log_arc_slots, out);
+}
+
+int dvt_rv32_job_calltree_times(dvt_prover *p, double out[3]) {
+    if (!p || !out) return DVT_ERR_INPUT;
+    std::lock_guard<std::mutex> lk(p->mu);
+    for (int i = 0; i < 3; i++) out[i] = p->calltree_ms[i];
+    return DVT_OK;
+}
+
+// host-only: the same rule (calltree::walk_records) over execute_traced's shards
+int dvt_execute_calltree(const uint8_t *elf, size_t elf_len, const dvt_buf *stdin_bufs, size_t nbuf, uint64_t max_cycles, dvt_calltree_arc *arcs,
+                         size_t cap_arcs, dvt_calltree_func *funcs, size_t cap_funcs, dvt_calltree_summary *summary, dvt_report *report,
+                         char **err_text) {
+    if (err_text) *err_text = nullptr;
+    const calltree::Out out{arcs, cap_arcs, funcs, cap_funcs, summary};
+    if (!elf || (nbuf && !stdin_bufs) || !summary || out.null_array()) return DVT_ERR_INPUT;
+    std::unique_ptr<calltree::State> st;
+    uint32_t shards = 0;
+    return execute_traced(
+        elf, elf_len, stdin_bufs, nbuf, max_cycles, report, err_text, [&](const rv32::Program &prog) { st.reset(new calltree::State(prog)); },
+        [&](const rv32::Program &prog, const rv32::CycleRec *recs, size_t n, uint32_t last_succ) {
+            calltree::walk_records(prog, recs, n, last_succ, st->cycles, st.get());
+            shards++;
+        },
+        [&](const rv32::Program &prog, double ms) -> const char * {
+            st->finish();
+            calltree::emit(prog, *st, shards, ms, out);
+            return nullptr;
+        });
 }
 
 // ---- the trace-row checks of one chip (check.cuh)

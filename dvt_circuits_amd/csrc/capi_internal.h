@@ -99,6 +99,7 @@ struct dvt_prover {
     // the device verifier's pinned staging and events (verify_query.hip, on member 0), made by the first dvt_prover_verify; its last times
     dvt::vq::Stage *vq_stage = nullptr;
     double vq_times[9] = {};
+    double calltree_ms[3] = {};       // the last dvt_rv32_job_calltree: summary mode, the host's merge, emit mode (dvt_rv32_job_calltree_times)
     size_t vq_chunk_words = 0;        // proof words per chunk of the device verifier ("verify_chunk_words", default vq::CHUNK_WORDS)
     std::string err;
     std::mutex mu;

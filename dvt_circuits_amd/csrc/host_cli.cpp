@@ -1,11 +1,11 @@
 // dvt_prover_host — the reference's CLI verbs (src/main.rs:58-106) over the C ABI.
 //
 //   dvt_prover_host prove   --type T -i INPUT.json [-o PROOF] [--elf GUEST.elf] [--devices D0,D1,...] [--compact]
-//   dvt_prover_host execute --type T -i INPUT.json [--show-report] [--elf GUEST.elf]
+//   dvt_prover_host execute --type T -i INPUT.json [--show-report] [--show-calls] [--elf GUEST.elf]
 //   dvt_prover_host verify  --type T -i PROOF [--elf GUEST.elf]
 //   dvt_prover_host compact --type T -i PROOF [-o PROOF] [--elf GUEST.elf]     (shared Merkle paths sent once: dvt_proof_compact)
 //   dvt_prover_host expand  --type T -i PROOF [-o PROOF] [--elf GUEST.elf]     (the inverse; verify takes either form)
-//   dvt_prover_host check   --type T -i INPUT.json [--show-report] [--elf GUEST.elf] [--devices D0,D1,...]
+//   dvt_prover_host check   --type T -i INPUT.json [--show-report] [--show-calls] [--elf GUEST.elf] [--devices D0,D1,...]
 //
 // T = bad-share | finalization | bad-partial-key | bad-encrypted-share (clap names of CircuitType, :36-42).
 // The reference embeds the four guest ELFs at build time (include_elf!, :115-118); they cannot be built in
@@ -24,6 +24,8 @@
 // the host, dvt_rv32_job_profile on the GPU): "opcode counts (N total instructions):" and one "count name" line per RISC-V
 // mnemonic, by count descending, then by name; then "syscall counts (N total syscall instructions):" with the ids of
 // dvt_execute's syscall ABI named and any other in hex.  (The layout is this tool's: SP1's own text is not in the reference.)
+// --show-calls: after that (or in its place), the call-tree report (dvt_execute_calltree on the host, dvt_rv32_job_calltree on the
+// GPU): "call tree (N frames, depth D):" and one "inclusive self calls f_<pc>" line per function, by self cycles descending.
 // get-schema / validate-schema / node are product UI outside the accelerated path and are not provided.
 #include <algorithm>
 #include <cstdio>
@@ -88,11 +90,24 @@ static void print_report(const dvt_profile_opcode *ops, const dvt_profile_syscal
     for (auto &c : calls) printf("%12llu %s\n", (unsigned long long)c.second, c.first.c_str());
 }
 
+// both sizes first, then the tables (call: dvt_execute_calltree or dvt_rv32_job_calltree with everything else bound)
+template <class Call> static int print_calls(Call call) {
+    dvt_calltree_summary s{};
+    if (int rc = call(nullptr, 0, nullptr, 0, &s)) return rc;
+    std::vector<dvt_calltree_func> funcs(s.n_funcs);
+    if (int rc = call(nullptr, 0, funcs.data(), funcs.size(), &s)) return rc;
+    printf("call tree (%llu frames, depth %u):\n", (unsigned long long)s.n_frames, s.max_depth);
+    for (size_t i = 0; i < funcs.size() && i < s.n_funcs; i++)
+        printf("%14llu %14llu %12llu f_%x\n", (unsigned long long)funcs[i].inclusive, (unsigned long long)funcs[i].self, (unsigned long long)funcs[i].calls, funcs[i].pc);
+    if (s.dropped_frames) printf("(%llu frames dropped: no function table)\n", (unsigned long long)s.dropped_frames);
+    return 0;
+}
+
 int main(int argc, char **argv) {
-    if (argc < 2) return die("usage: dvt_prover_host prove|execute|verify|check|compact|expand --type T -i FILE [-o FILE] [--show-report] [--compact] [--keep-trees] [--elf FILE] [--devices D0,D1,...] [--device D]");
+    if (argc < 2) return die("usage: dvt_prover_host prove|execute|verify|check|compact|expand --type T -i FILE [-o FILE] [--show-report] [--show-calls] [--compact] [--keep-trees] [--elf FILE] [--devices D0,D1,...] [--device D]");
     const std::string verb = argv[1];
     std::string type, input, output, elf_path, schema_path, devices, verify_device;
-    bool show_report = false, auth = false, compact = false, keep_trees = false;
+    bool show_report = false, show_calls = false, auth = false, compact = false, keep_trees = false;
     for (int i = 2; i < argc; i++) {
         std::string a = argv[i], inline_val;
         bool has_inline = false;
@@ -108,6 +123,7 @@ int main(int argc, char **argv) {
         else if (a == "--devices") devices = next();
         else if (a == "--device") verify_device = next();   // verify: the query part on that GPU (dvt_prover_verify)
         else if (a == "--show-report") show_report = true;
+        else if (a == "--show-calls") show_calls = true;
         else if (a == "--compact") compact = true;       // prove: shard proofs in the compact form ("compact_openings")
         else if (a == "--keep-trees") keep_trees = true;  // prove / check: shards that do not fit in HBM in full keep their main Merkle tree ("keep_phase1": 2)
         else if (a == "--auth-commitment") auth = true;  // the reference selects this at build time (cargo feature)
@@ -192,6 +208,13 @@ int main(int argc, char **argv) {
             printf("Verification report:\ntotal instructions: %llu\nexit code: %d\n", (unsigned long long)rep.cycles, rep.exit_code);
             print_report(ops, sys, sum);
         }
+        if (show_calls) {
+            char *cerr = nullptr;
+            if (print_calls([&](dvt_calltree_arc *arcs, size_t cap_arcs, dvt_calltree_func *funcs, size_t cap_funcs, dvt_calltree_summary *s) {
+                    return dvt_execute_calltree(elf.data(), elf.size(), &buf, 1, 0, arcs, cap_arcs, funcs, cap_funcs, s, nullptr, &cerr);
+                }))
+                return die(std::string("Verification failed: ") + (cerr ? cerr : "?"));
+        }
         return 0;
     }
 
@@ -239,6 +262,11 @@ int main(int argc, char **argv) {
             if (dvt_rv32_job_profile(p, pk, job, 0, nullptr, 0, nullptr, 0, sys, REPORT_CAP, ops, REPORT_CAP, &psum)) return die(std::string("Report failed: ") + dvt_last_error(p));
             print_report(ops, sys, psum);
         }
+        if (show_calls &&
+            print_calls([&](dvt_calltree_arc *arcs, size_t cap_arcs, dvt_calltree_func *funcs, size_t cap_funcs, dvt_calltree_summary *s) {
+                return dvt_rv32_job_calltree(p, pk, job, 0, arcs, cap_arcs, funcs, cap_funcs, s);
+            }))
+            return die(std::string("Call tree failed: ") + dvt_last_error(p));
         dvt_job_free(p, job);
         dvt_pk_free(p, pk);
         dvt_prover_destroy(p);

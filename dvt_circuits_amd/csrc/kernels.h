@@ -112,4 +112,32 @@ struct ProfileTables {
 // last_succ: the instruction index of the shard's next_pc, or 0xffffffff when that is no instruction of the text
 hipError_t launch_profile_records(hipStream_t st, const rv32::CycleRec *d_recs, size_t n_recs, uint32_t last_succ, const ProfileTables &t);
 
+// calltree.hip
+// The device pass of the call-tree report (calltree.h) over the cycle records of one shard: one workgroup per span of
+// CALLTREE_SPAN consecutive records, spans numbered span0, span0 + 1, ... in the per-span arrays.  The records are only read.
+constexpr uint32_t CALLTREE_SPAN = 4096;
+enum CalltreeCounter { CALLTREE_DROPPED_FRAMES, CALLTREE_DROPPED_CYCLES, CALLTREE_UNMATCHED, CALLTREE_MAX_DEPTH, CALLTREE_BAD_RECORDS, CALLTREE_COUNTERS };
+struct CalltreeSpanSummary { uint32_t u, c; };                        // the span reduced: u unmatched RETs, then c unmatched CALLs
+struct CalltreeCall { uint32_t fn, pos; };                            // an unmatched CALL: the callee, its position in the span
+struct CalltreeFrame { unsigned long long open; uint32_t fn, pad; };  // a frame of the stack on entry: global open position
+struct CalltreeSpanIn { unsigned long long frames_at; uint32_t n_frames, depth; };   // emit mode: where the span's frames lie, top first; the depth on entry
+struct CalltreeTables {
+    const uint32_t *classes;                         // [n_instr]: calltree::instr_classes
+    unsigned long long *counters;                    // [CALLTREE_COUNTERS], zeroed by the caller
+    // summary mode: both written; calls_at == nullptr: the summaries alone, else span k's unmatched calls from calls[calls_at[k]]
+    CalltreeSpanSummary *summaries;                  // [spans]
+    const unsigned long long *calls_at;              // [spans]
+    CalltreeCall *calls;
+    // emit mode: read
+    const CalltreeSpanIn *span_in;                   // [spans]
+    const CalltreeFrame *frames;
+    // emit mode: the arcs, caller << 32 | fn; keys all ones and sums zeroed by the caller
+    unsigned long long *arc_keys, *arc_calls, *arc_cycles;   // [2^log_slots]
+    uint32_t n_instr, log_slots;
+};
+// last_succ as launch_profile_records; base_position: the global position of the shard's first record
+hipError_t launch_calltree_summary(hipStream_t st, const rv32::CycleRec *d_recs, size_t n_recs, uint32_t last_succ, size_t span0, const CalltreeTables &t);
+hipError_t launch_calltree_emit(hipStream_t st, const rv32::CycleRec *d_recs, size_t n_recs, uint32_t last_succ, size_t span0,
+                                unsigned long long base_position, const CalltreeTables &t);
+
 }  // namespace dvt

@@ -127,7 +127,8 @@ void dvt_free(void *ptr);
  * 10: dvt_stage_hunt_join_*, dvt_rv32_hunt_join_job; 11: "compact_openings", dvt_proof_compact, dvt_proof_expand,
  * dvt_stage_multipath_nodes, dvt_stage_verify_multipath, dvt_debug_compact_list_sweep; 12: dvt_rv32_job_profile,
  * dvt_execute_profile; 13: "keep_phase1": 2, "keep_full_max", DVT_KEEP_*, dvt_rv32_job_shard_kept,
- * dvt_rv32_job_shard_kept_bytes, dvt_debug_keep_plan) */
+ * dvt_rv32_job_shard_kept_bytes, dvt_debug_keep_plan; 14: dvt_rv32_job_calltree,
+ * dvt_rv32_job_calltree_times, dvt_execute_calltree) */
 uint32_t dvt_abi_version(void);
 /* the handle's hipStream_t (for event timing by the caller) */
 void *dvt_stream(dvt_prover *p);
@@ -713,6 +714,55 @@ int dvt_execute_profile(const uint8_t *elf, size_t elf_len, const dvt_buf *stdin
                         uint64_t *pc_count, size_t cap_pc, dvt_profile_edge *edges, size_t cap_edges, dvt_profile_syscall *sys,
                         size_t cap_sys, dvt_profile_opcode *ops, size_t cap_ops, dvt_profile_summary *summary, dvt_report *report,
                         char **err_text);
+/* The call-tree report of a prepared job: inclusive and self cycles per function and per caller -> callee arc, from the cycle
+ * records of the shards the job holds (read only; the job is left as found).  Positions g = 0 .. C - 1 number the records in
+ * execution order across shards; the successor of a record is the execution report's.  From the raw instruction word alone,
+ * a `jal` / `jalr` with rd == x1 is a CALL (none when it has no successor in the text) and `jalr x0, 0(x1)` is a RET; nothing
+ * else is an event, so a tail jump stays in the frame of the function that was called.  A function is named by the pc of
+ * its entry.  The stack starts with the root frame (the instruction the first record names, open at 0).  A CALL at g with
+ * successor s pushes {s, open = g + 1}: the call instruction belongs to the caller.  A RET at g pops the top frame F,
+ * WHATEVER ADDRESS IT RETURNS TO, and the arc (caller of F, F) gets calls += 1, cycles += g + 1 - F.open; a RET that finds
+ * only the root adds to unmatched_returns and the root stays.  After the last record every open frame is closed at C, the
+ * root last: its arc (0xffffffff, entry) has cycles = C, and open_at_exit counts the frames closed this way.
+ *   arcs      every distinct (caller_pc, callee_pc) with its calls and cycles, sorted by (caller_pc, callee_pc).  On the
+ *             device the arcs are added up in an insert-only table of 2^log_arc_slots slots per device (3..24; 0 = sized
+ *             from the text as dvt_rv32_job_profile sizes its edge table); a closed frame whose arc finds no slot in 64
+ *             probes adds to dropped_frames and dropped_cycles.  Always: the calls of all arcs + dropped_frames = n_frames,
+ *             and an arc that is returned carries its exact sums.
+ *   funcs     per callee: calls and inclusive = the sums over the arcs into it, self = inclusive - the cycles of the arcs
+ *             out of it; sorted by self descending, then by pc.  Recursion counts nested frames of one function more than
+ *             once in inclusive, never in self: the self cycles of all functions sum to summary->cycles.  When
+ *             dropped_frames > 0 the table cannot be made: n_funcs is 0 and funcs is not filled.
+ *   summary   cycles = C; n_frames = the frames closed; max_depth = the deepest stack, the root included; ms = wall clock of
+ *             the call after the entry guard
+ * Arrays, caps, the size query and DVT_ERR_INPUT as dvt_rv32_job_profile (log_arc_slots outside 0, 3..24; a cycle record that
+ * names an instruction outside the text).  DVT_ERR_UNSUPPORTED: a job that does not hold every shard of its execution
+ * (dvt_rv32_prepare_part with an offset or a stride): the stack across a gap is unknown.  Handles with several members work:
+ * the spans are merged on the host.  Like every call on the handle it stops a running prove_shard pipeline first. */
+typedef struct {
+    uint32_t caller_pc, callee_pc;   /* caller_pc 0xffffffff: the root */
+    uint64_t calls, cycles;
+} dvt_calltree_arc;
+typedef struct {
+    uint32_t pc, pad;
+    uint64_t calls, inclusive, self;
+} dvt_calltree_func;
+typedef struct {
+    uint64_t cycles, n_frames, dropped_frames, dropped_cycles, unmatched_returns;
+    uint32_t text_base, n_instr, n_arcs, n_funcs, max_depth, open_at_exit, shards_total;
+    float ms;
+} dvt_calltree_summary;
+int dvt_rv32_job_calltree(dvt_prover *p, const dvt_pk *pk, dvt_job *job, uint32_t log_arc_slots, dvt_calltree_arc *arcs,
+                          size_t cap_arcs, dvt_calltree_func *funcs, size_t cap_funcs, dvt_calltree_summary *summary);
+/* wall-clock milliseconds of the last dvt_rv32_job_calltree on this handle: summary mode (both runs, with their downloads),
+ * the host's merge of the span summaries, emit mode (with its download) */
+int dvt_rv32_job_calltree_times(dvt_prover *p, double out[3]);
+/* The same report on the host alone (no GPU is touched), as dvt_execute_profile runs the guest: nothing is bounded, so nothing
+ * is dropped.  Return codes, *report and *err_text as dvt_execute gives them; the tables are filled for whatever retired, also
+ * when the guest fails. */
+int dvt_execute_calltree(const uint8_t *elf, size_t elf_len, const dvt_buf *stdin_bufs, size_t nbuf, uint64_t max_cycles,
+                         dvt_calltree_arc *arcs, size_t cap_arcs, dvt_calltree_func *funcs, size_t cap_funcs,
+                         dvt_calltree_summary *summary, dvt_report *report, char **err_text);
 /* test hook: run K0 on one shard of a prepared job and return the device-generated main traces
  * (canonical); blob layout as dvt_rv32_debug_traces with prep_width = 0. */
 int dvt_rv32_debug_device_traces(dvt_prover *p, const dvt_pk *pk, dvt_job *job, size_t shard, uint32_t **blob,

@@ -4,13 +4,19 @@ with --host).
 
     python tools/profile_guest.py --guest 'bignum(40)' [--top N] [--json OUT] [--host] [--log-shard L]
     python tools/profile_guest.py --elf guest.elf [--stdin FILE ...]
+    python tools/profile_guest.py --guest 'bignum(40)' --calls [--host]
 
 The guest is an expression over the functions of tests/guests*.py (its ELF is the value, or the first element of it), or an
 ELF file with its stdin buffers.  The guests are stripped (tools/rvasm.py writes program headers only), so function entries
 come from the report itself: the ELF entry plus the target of every edge whose source is a `jal` / `jalr` that writes ra.
 Every instruction belongs to the nearest entry at or below it.  Prints per function f_<pc> its cycles, its share and its
 calls (the counts of the edges into the entry), then the hottest taken branches, the opcode and the syscall counts; --json
-writes the same with the raw tables."""
+writes the same with the raw tables.
+
+--calls adds the call-tree report (dvt_rv32_job_calltree on the GPU, dvt_execute_calltree with --host): per function f_<pc> its
+inclusive cycles, its self cycles and its calls, measured from the calls and returns of the execution instead of address ranges
+(a tail jump or a shared helper is charged to the function that was called), then the heaviest caller -> callee arcs; --json
+carries both tables."""
 import argparse
 import importlib
 import json
@@ -23,7 +29,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 def guest_elf(expr):
     scope = {}
-    for mod in ("guests", "guests_bls", "guests_finalization", "guests_share", "guests_profile"):
+    for mod in ("guests", "guests_bls", "guests_finalization", "guests_share", "guests_profile", "guests_calltree"):
         m = importlib.import_module("tests." + mod)
         scope.update({k: getattr(m, k) for k in dir(m) if not k.startswith("_") and k not in scope})
     v = eval(expr if "(" in expr else expr + "()", scope)   # noqa: S307 (the caller's own command line)
@@ -81,6 +87,8 @@ def main():
     ap.add_argument("--host", action="store_true", help="tally on the host (dvt_execute_profile): no GPU is touched")
     ap.add_argument("--log-shard", type=int, default=21)
     ap.add_argument("--log-edge-slots", type=int, default=0)
+    ap.add_argument("--calls", action="store_true", help="also the call-tree report: inclusive and self cycles per function, the heaviest arcs")
+    ap.add_argument("--log-arc-slots", type=int, default=0)
     args = ap.parse_args()
     if bool(args.guest) == bool(args.elf):
         ap.error("one of --guest and --elf")
@@ -92,6 +100,7 @@ def main():
         rc, rep, prof, err = capi.execute_profile(elf, stdin)
         if prof is None:
             raise SystemExit("execute failed: %s" % err)
+        tree = capi.execute_calltree(elf, stdin)[2] if args.calls else None
         if rc:
             print("the guest failed (%s): the profile of what retired" % err)
     else:
@@ -99,6 +108,7 @@ def main():
         pk, _ = p.setup(elf)
         job, rep = p.prepare(pk, stdin)
         prof = p.job_profile(pk, job, args.log_edge_slots)
+        tree = p.job_calltree(pk, job, args.log_arc_slots) if args.calls else None
         p.job_free(job)
         p.pk_free(pk)
         p.close()
@@ -114,9 +124,23 @@ def main():
         print("  0x%08x -> 0x%08x %14d" % (b["from_pc"], b["to_pc"], b["count"]))
     print("opcodes: " + ", ".join("%s %d" % kv for kv in sorted(prof["opcodes"].items(), key=lambda kv: (-kv[1], kv[0]))[:args.top]))
     print("syscalls: " + ", ".join("0x%x %d" % kv for kv in sorted(prof["syscalls"].items())))
+    calls = {}
+    if tree:
+        t = tree["summary"]
+        total = max(t["cycles"], 1)
+        print("call tree: %d frames over %d arcs (%d frames, %d cycles dropped), depth %d, %d open at the exit, %d unmatched returns, %.2f ms" %
+              (t["n_frames"], t["n_arcs"], t["dropped_frames"], t["dropped_cycles"], t["max_depth"], t["open_at_exit"], t["unmatched_returns"], t["ms"]))
+        print("%-12s %14s %14s %7s %12s" % ("function", "inclusive", "self", "share", "calls"))
+        for pc, n, inc, own in tree["funcs"][:args.top]:
+            print("%-12s %14d %14d %6.2f%% %12d" % ("f_%x" % pc, inc, own, 100 * own / total, n))
+        print("heaviest arcs:")
+        for caller, callee, n, cyc in sorted(tree["arcs"], key=lambda a: -a[3])[:args.top]:
+            print("  %-12s -> %-12s %14d cycles %12d calls" % ("(root)" if caller is None else "f_%x" % caller, "f_%x" % callee, cyc, n))
+        calls = dict(calltree=dict(summary=t, functions=[dict(name="f_%x" % pc, pc=pc, calls=n, inclusive=inc, self=own) for pc, n, inc, own in tree["funcs"]],
+                                   arcs=[dict(caller_pc=a, callee_pc=b, calls=n, cycles=c) for a, b, n, c in tree["arcs"]]))
     if args.json:
         with open(args.json, "w") as f:
-            json.dump(dict(summary=s, functions=funcs, branches=branches, opcodes=prof["opcodes"], syscalls={"0x%x" % k: v for k, v in prof["syscalls"].items()},
+            json.dump(dict(calls, summary=s, functions=funcs, branches=branches, opcodes=prof["opcodes"], syscalls={"0x%x" % k: v for k, v in prof["syscalls"].items()},
                            pc_count=[int(x) for x in prof["pc_count"]], edges=prof["edges"]), f, indent=1)
 
 
