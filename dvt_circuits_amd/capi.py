@@ -183,6 +183,9 @@ def load():
     lib.dvt_rv32_job_calltree.argtypes = [vp, vp, vp, u32] + tree_out
     lib.dvt_rv32_job_calltree_times.argtypes = [vp, C.POINTER(C.c_double)]
     lib.dvt_execute_calltree.argtypes = [C.c_char_p, sz, C.POINTER(Buf), sz, u64] + tree_out + [C.POINTER(Report), C.POINTER(C.c_char_p)]
+    mem_out = [C.POINTER(u64), sz, C.POINTER(MemoryPage), sz, C.POINTER(MemorySummary)]
+    lib.dvt_rv32_job_memory.argtypes = [vp, vp, vp] + mem_out
+    lib.dvt_execute_memory.argtypes = [C.c_char_p, sz, C.POINTER(Buf), sz, u64] + mem_out + [C.POINTER(Report), C.POINTER(C.c_char_p)]
     lib.dvt_stdin_from_json.argtypes = [C.c_char_p, C.c_char_p, sz, C.c_int, C.POINTER(u8p), C.POINTER(sz), C.POINTER(C.c_char_p)]
     _lib = lib
     return lib
@@ -465,6 +468,56 @@ def execute_calltree(elf: bytes, stdin=(), max_cycles=0):
         return lib.dvt_execute_calltree(elf, len(elf), bufs, len(stdin), max_cycles, *out, C.byref(rep), C.byref(err))
     rc, tree = _calltree(call)
     return rc, dict(cycles=rep.cycles, exit_code=rep.exit_code, halted=bool(rep.halted), unprovable=bool(rep.unprovable)), tree, _take_str(lib, err)
+
+
+class MemoryPage(C.Structure):
+    _fields_ = [("page", C.c_uint32), ("words", C.c_uint32), ("first", C.c_uint32), ("pad", C.c_uint32), ("loads", C.c_uint64),
+                ("stores", C.c_uint64), ("pre_reads", C.c_uint64), ("pre_writes", C.c_uint64)]
+
+
+class MemorySummary(C.Structure):
+    _fields_ = [(name, C.c_uint64) for name in ("cycles", "loads", "stores", "pre_reads", "pre_writes", "pre_calls", "words", "first_touches",
+                                                "image_words", "image_words_accessed", "mem_init_rows", "sp_writes")] + \
+               [(name, C.c_uint32) for name in ("sp_min", "sp_max", "text_base", "n_instr", "n_pages", "page_bytes", "shards_tallied",
+                                                "shards_total")] + [("ms", C.c_float)]
+
+
+MEMORY_LDS_PAGE_SLOTS = 256   # csrc/memreport.h LDS_PAGE_SLOTS: slots of a workgroup's page cache in the device pass
+
+
+def _memory(call):
+    """The memory report through call(first_touch, cap_instr, pages, cap_pages, summary) -> rc: once for the sizes, once for
+    the tables.  Returns (rc, report), report = None when a call fails without a summary, else dict(summary, first_touch
+    (numpy u64, one per instruction of the text), pages = [dict(page (byte address), words, first, loads, stores, pre_reads,
+    pre_writes)] sorted by address)."""
+    s = MemorySummary()
+    rc = call(None, 0, None, 0, C.byref(s))
+    if rc not in (DVT_OK, DVT_ERR_GUEST):
+        return rc, None
+    n_instr, n_pages = int(s.n_instr), int(s.n_pages)
+    ft = np.zeros(max(n_instr, 1), np.uint64)
+    pages = (MemoryPage * max(n_pages, 1))()
+    rc = call(ft.ctypes.data_as(C.POINTER(C.c_uint64)), n_instr, pages, n_pages, C.byref(s))
+    if rc not in (DVT_OK, DVT_ERR_GUEST):
+        return rc, None
+    summary = {name: (float if name == "ms" else int)(getattr(s, name)) for name, _ in MemorySummary._fields_}
+    keys = [name for name, _ in MemoryPage._fields_ if name != "pad"]
+    return rc, dict(summary=summary, first_touch=ft[:n_instr],
+                    pages=[{k: int(getattr(pg, k)) for k in keys} for pg in pages[:min(n_pages, int(s.n_pages))]])
+
+
+def execute_memory(elf: bytes, stdin=(), max_cycles=0):
+    """Host-only memory report (dvt_execute_memory): page traffic, footprint, first touches per instruction and the stack span.
+    Returns (rc, report dict as execute() gives it, memory dict as Prover.job_memory gives it or None, error text)."""
+    lib = load()
+    rep, err, bufs = Report(), C.c_char_p(), _bufs(stdin)
+
+    def call(*out):
+        if err.value:
+            lib.dvt_free(C.cast(err, C.c_void_p))
+        return lib.dvt_execute_memory(elf, len(elf), bufs, len(stdin), max_cycles, *out, C.byref(rep), C.byref(err))
+    rc, mem = _memory(call)
+    return rc, dict(cycles=rep.cycles, exit_code=rep.exit_code, halted=bool(rep.halted), unprovable=bool(rep.unprovable)), mem, _take_str(lib, err)
 
 
 def exec_rate(elf: bytes, stdin=(), log_shard=21, trace=False) -> float:
@@ -1129,6 +1182,14 @@ class Prover:
         rc, tree = _calltree(lambda *out: self.lib.dvt_rv32_job_calltree(self.h, pk, job, log_arc_slots, *out))
         self.check(rc)
         return tree
+
+    def job_memory(self, pk, job):
+        """The memory report of a prepared job, from the cycle records of the shards it holds on the GPU (dvt_rv32_job_memory):
+        dict(summary, first_touch (numpy u64, one per instruction of the text), pages = [dict(page, words, first, loads,
+        stores, pre_reads, pre_writes)] sorted by address).  Every figure is exact."""
+        rc, mem = _memory(lambda *out: self.lib.dvt_rv32_job_memory(self.h, pk, job, *out))
+        self.check(rc)
+        return mem
 
     def job_calltree_times(self):
         """milliseconds of the last job_calltree: dict(summary_ms, merge_ms, emit_ms)"""

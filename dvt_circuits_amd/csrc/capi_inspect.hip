@@ -1,12 +1,13 @@
 // The inspectors of trace rows of the C ABI (include/dvt_prover.h): row checks, bus ledger, forgery hunt, join hunt.  Each has
 // stage entry points (dvt_stage_*) on a table the caller uploaded (stage_table) and job entry points (dvt_rv32_*) on the
-// tables of a prepared job's held shards (shard_view).  The execution report (profile.h) and the call-tree report (calltree.h)
-// are the inspectors that read a job's cycle records instead of its tables.
+// tables of a prepared job's held shards (shard_view).  The execution report (profile.h), the call-tree report (calltree.h)
+// and the memory report (memreport.h) are the inspectors that read a job's cycle records instead of its tables.
 #include <algorithm>
 
 #include "calltree.h"
 #include "capi_job.h"
 #include "ledger_key.h"
+#include "memreport.h"
 #include "profile.h"
 #include "sha256.h"
 
@@ -515,6 +516,87 @@ static int job_calltree(dvt_prover *p, const dvt_pk *pk, dvt_job *j, uint32_t lo
     return DVT_OK;
 }
 
+// ------------------------------------------------------------------ the memory report (dvt_rv32_job_memory)
+// One member's share: its tables, the footprint bitmap and the dense array from lane 0's pool (zeroed in stream order), one
+// launch per shard it holds on lane 0's stream, the gather, two downloads (which synchronise); counters added and bitmap lines
+// ORed into *t.  The buffers go back to the pool at scope exit.
+static int member_memory(const Lane &c, JobPart &part, const std::vector<uint32_t> &statics, size_t n, uint32_t n_pre, memrep::Tally *t) {
+    if (part.shards.empty()) return DVT_OK;
+    Engine &e = c.eng;
+    // 64-bit words: first_touch, counters, the page arrays; then sp[2], the dense count and a pad; then the static words
+    const size_t zero_words = n + MEMORY_COUNTERS + (size_t)MEMORY_PAGE_ARRAYS * memrep::N_PAGES;
+    size_t n_recs = 0;
+    for (auto &s : part.shards) n_recs += s.n_recs;
+    const uint32_t cap = (uint32_t)std::min<size_t>(memrep::N_PAGES, 4 * n_recs);   // (a record touches at most four pages)
+    StageBuf buf{e.pool}, bitmap{e.pool}, dense{e.pool};
+    HIP_TRY(c.err, e.pool.alloc_bytes(&buf.ptr, zero_words * 8 + 16 + statics.size() * 4));
+    HIP_TRY(c.err, e.pool.alloc_bytes(&bitmap.ptr, (size_t)memrep::BITMAP_WORDS * 4));
+    HIP_TRY(c.err, e.pool.alloc_bytes(&dense.ptr, std::max<size_t>(cap, 1) * sizeof(MemoryDensePage)));
+    unsigned long long *d = static_cast<unsigned long long *>(buf.ptr);
+    uint32_t *d32 = reinterpret_cast<uint32_t *>(d + zero_words);
+    MemoryTables tb{};
+    tb.first_touch = d; tb.counters = d + n; tb.page_ctr = d + n + MEMORY_COUNTERS;
+    tb.sp = d32; tb.bitmap = static_cast<uint32_t *>(bitmap.ptr);
+    tb.classes = d32 + 4; tb.offs = d32 + 4 + n; tb.pre = d32 + 4 + 2 * n;
+    tb.n_instr = (uint32_t)n; tb.n_pre = n_pre;
+    const uint32_t head[4] = {0xffffffffu, 0, 0, 0};
+    HIP_TRY(c.err, hipMemsetAsync(d, 0, zero_words * 8, e.stream));
+    HIP_TRY(c.err, hipMemsetAsync(bitmap.ptr, 0, (size_t)memrep::BITMAP_WORDS * 4, e.stream));
+    HIP_TRY(c.err, hipMemcpyAsync(d32, head, sizeof head, hipMemcpyHostToDevice, e.stream));
+    HIP_TRY(c.err, hipMemcpyAsync(d32 + 4, statics.data(), statics.size() * 4, hipMemcpyHostToDevice, e.stream));
+    for (auto &s : part.shards) HIP_TRY(c.err, launch_memory_records(e.stream, s.d_recs, s.n_recs, tb));
+    HIP_TRY(c.err, launch_memory_gather(e.stream, tb, static_cast<MemoryDensePage *>(dense.ptr), cap, d32 + 2));
+    std::vector<unsigned long long> h(n + MEMORY_COUNTERS + 2);   // first_touch, counters | sp, the dense count, the pad
+    if (!e.download(h.data(), d, (n + MEMORY_COUNTERS) * 8) || !e.download(h.data() + n + MEMORY_COUNTERS, d32, 16)) return engine_fail(c.err, e);
+    const unsigned long long *counters = h.data() + n;
+    uint32_t tail[4];
+    memcpy(tail, h.data() + n + MEMORY_COUNTERS, sizeof tail);
+    if (counters[MEMORY_BAD_RECORDS])
+        return fail(c.err, DVT_ERR_INPUT, "%llu cycle records name an instruction outside the text or an address outside guest memory", counters[MEMORY_BAD_RECORDS]);
+    if (tail[2] > cap) return fail(c.err, DVT_ERR_DEVICE, "%u pages with accesses, room for %u", tail[2], cap);
+    std::vector<MemoryDensePage> pages(tail[2]);
+    if (!pages.empty() && !e.download(pages.data(), dense.ptr, pages.size() * sizeof(MemoryDensePage))) return engine_fail(c.err, e);
+    for (size_t i = 0; i < n; i++) t->first_touch[i] += h[i];
+    for (const MemoryDensePage &dp : pages) {
+        if (dp.page >= memrep::N_PAGES) return fail(c.err, DVT_ERR_DEVICE, "page %u out of range", dp.page);
+        memrep::Page &pg = t->pages[dp.page];
+        pg.loads += dp.loads; pg.stores += dp.stores; pg.pre_reads += dp.pre_reads; pg.pre_writes += dp.pre_writes; pg.first += dp.first;
+        for (uint32_t k = 0; k < memrep::LINE_WORDS; k++) pg.bits[k] |= dp.bits[k];
+    }
+    t->cycles += counters[MEMORY_CYCLES];
+    t->pre_calls += counters[MEMORY_PRE_CALLS];
+    if (counters[MEMORY_SP_WRITES]) {
+        t->sp_writes += counters[MEMORY_SP_WRITES];
+        t->sp_min = std::min(t->sp_min, tail[0]);
+        t->sp_max = std::max(t->sp_max, tail[1]);
+    }
+    t->shards += (uint32_t)part.shards.size();
+    return DVT_OK;
+}
+
+static int job_memory(dvt_prover *p, const dvt_pk *pk, dvt_job *j, const memrep::Out &out) {
+    if (int rc = same_members(p, pk, j)) return rc;
+    const auto t0 = Clock::now();
+    const size_t n = pk->prog.instrs.size() - 1;
+    const std::vector<memrep::PreShape> shapes = memrep::pre_shapes();
+    std::vector<uint32_t> statics(2 * n);   // classes, offsets, then the shapes
+    for (size_t i = 0; i < n; i++) {
+        statics[i] = memrep::instr_class(pk->prog.instrs[i]);
+        statics[n + i] = pk->prog.instrs[i].off;
+    }
+    for (auto &s : shapes) statics.insert(statics.end(), {s.id, s.n0, s.r0, s.w0, s.n1, s.w1});
+    memrep::Tally t(pk->prog);
+    int rc = DVT_OK;
+    for (size_t m = 0; m < n_members(p) && !rc; m++) {
+        rc = turn_to(p, m);
+        if (!rc) rc = member_memory(lane0(p, m), j->parts[m], statics, n, (uint32_t)shapes.size(), &t);
+    }
+    if (turn_to(p, 0) && !rc) rc = DVT_ERR_DEVICE;
+    if (rc) return rc;
+    memrep::emit(pk->prog, t, (uint32_t)j->n_total, j->held() == j->n_total, ms_since(t0), out);
+    return DVT_OK;
+}
+
 // The host-only reports (no GPU is touched): the guest in trace mode, where an instruction without a chip is recorded instead
 // of trapping, 2^21 cycles per shard and one shard's records in memory at a time.  begin(prog) once the ELF is loaded;
 // shard(prog, recs, n, last_succ) per shard in execution order; end(prog, ms) after the last, and a text it returns fails the
@@ -632,6 +714,34 @@ int dvt_execute_calltree(const uint8_t *elf, size_t elf_len, const dvt_buf *stdi
         [&](const rv32::Program &prog, double ms) -> const char * {
             st->finish();
             calltree::emit(prog, *st, shards, ms, out);
+            return nullptr;
+        });
+}
+
+// ---- the memory report (memreport.h)
+int dvt_rv32_job_memory(dvt_prover *p, const dvt_pk *pk, dvt_job *job, uint64_t *first_touch, size_t cap_instr, dvt_memory_page *pages,
+                        size_t cap_pages, dvt_memory_summary *summary) {
+    const memrep::Out out{first_touch, cap_instr, pages, cap_pages, summary};
+    if (!p || !pk || !job || !summary || out.null_array()) return fail(p, DVT_ERR_INPUT, "null argument");
+    if (int rc = rv32_key(p, pk)) return rc;
+    Guard g(p); if (g.rc) return g.rc;
+    return job_memory(p, pk, job, out);
+}
+
+// host-only: the same rule (memrep::tally_records) over execute_traced's shards
+int dvt_execute_memory(const uint8_t *elf, size_t elf_len, const dvt_buf *stdin_bufs, size_t nbuf, uint64_t max_cycles, uint64_t *first_touch,
+                       size_t cap_instr, dvt_memory_page *pages, size_t cap_pages, dvt_memory_summary *summary, dvt_report *report,
+                       char **err_text) {
+    if (err_text) *err_text = nullptr;
+    const memrep::Out out{first_touch, cap_instr, pages, cap_pages, summary};
+    if (!elf || (nbuf && !stdin_bufs) || !summary || out.null_array()) return DVT_ERR_INPUT;
+    std::unique_ptr<memrep::Tally> t;
+    const std::vector<memrep::PreShape> shapes = memrep::pre_shapes();
+    return execute_traced(
+        elf, elf_len, stdin_bufs, nbuf, max_cycles, report, err_text, [&](const rv32::Program &prog) { t.reset(new memrep::Tally(prog)); },
+        [&](const rv32::Program &prog, const rv32::CycleRec *recs, size_t n, uint32_t) { memrep::tally_records(prog, shapes, recs, n, t.get()); },
+        [&](const rv32::Program &prog, double ms) -> const char * {
+            memrep::emit(prog, *t, t->shards, true, ms, out);
             return nullptr;
         });
 }

@@ -1,11 +1,11 @@
 // dvt_prover_host — the reference's CLI verbs (src/main.rs:58-106) over the C ABI.
 //
 //   dvt_prover_host prove   --type T -i INPUT.json [-o PROOF] [--elf GUEST.elf] [--devices D0,D1,...] [--compact]
-//   dvt_prover_host execute --type T -i INPUT.json [--show-report] [--show-calls] [--elf GUEST.elf]
+//   dvt_prover_host execute --type T -i INPUT.json [--show-report] [--show-calls] [--show-memory] [--elf GUEST.elf]
 //   dvt_prover_host verify  --type T -i PROOF [--elf GUEST.elf]
 //   dvt_prover_host compact --type T -i PROOF [-o PROOF] [--elf GUEST.elf]     (shared Merkle paths sent once: dvt_proof_compact)
 //   dvt_prover_host expand  --type T -i PROOF [-o PROOF] [--elf GUEST.elf]     (the inverse; verify takes either form)
-//   dvt_prover_host check   --type T -i INPUT.json [--show-report] [--show-calls] [--elf GUEST.elf] [--devices D0,D1,...]
+//   dvt_prover_host check   --type T -i INPUT.json [--show-report] [--show-calls] [--show-memory] [--elf GUEST.elf] [--devices D0,D1,...]
 //
 // T = bad-share | finalization | bad-partial-key | bad-encrypted-share (clap names of CircuitType, :36-42).
 // The reference embeds the four guest ELFs at build time (include_elf!, :115-118); they cannot be built in
@@ -26,6 +26,10 @@
 // dvt_execute's syscall ABI named and any other in hex.  (The layout is this tool's: SP1's own text is not in the reference.)
 // --show-calls: after that (or in its place), the call-tree report (dvt_execute_calltree on the host, dvt_rv32_job_calltree on the
 // GPU): "call tree (N frames, depth D):" and one "inclusive self calls f_<pc>" line per function, by self cycles descending.
+// --show-memory: after those (or in their place), the memory report (dvt_execute_memory on the host, dvt_rv32_job_memory on the
+// GPU): one line "memory: cycles=N loads=N stores=N pre_reads=N pre_writes=N pre_calls=N words=N first_touches=N pages=N
+// image_words=N image_words_accessed=N mem_init_rows=N sp_writes=N sp_min=0xX sp_max=0xX", then one line per run of
+// consecutive accessed pages: "0xFIRST-0xLAST loads stores pre_reads pre_writes words" (byte addresses, LAST inclusive).
 // get-schema / validate-schema / node are product UI outside the accelerated path and are not provided.
 #include <algorithm>
 #include <cstdio>
@@ -103,11 +107,37 @@ template <class Call> static int print_calls(Call call) {
     return 0;
 }
 
+// the sizes first, then the pages (call: dvt_execute_memory or dvt_rv32_job_memory with everything else bound)
+template <class Call> static int print_memory(Call call) {
+    dvt_memory_summary s{};
+    if (int rc = call(nullptr, 0, nullptr, 0, &s)) return rc;
+    std::vector<dvt_memory_page> pages(s.n_pages);
+    if (int rc = call(nullptr, 0, pages.data(), pages.size(), &s)) return rc;
+    auto u = [](uint64_t v) { return (unsigned long long)v; };
+    printf("memory: cycles=%llu loads=%llu stores=%llu pre_reads=%llu pre_writes=%llu pre_calls=%llu words=%llu first_touches=%llu pages=%u "
+           "image_words=%llu image_words_accessed=%llu mem_init_rows=%llu sp_writes=%llu sp_min=0x%x sp_max=0x%x\n",
+           u(s.cycles), u(s.loads), u(s.stores), u(s.pre_reads), u(s.pre_writes), u(s.pre_calls), u(s.words), u(s.first_touches), s.n_pages,
+           u(s.image_words), u(s.image_words_accessed), u(s.mem_init_rows), u(s.sp_writes), s.sp_min, s.sp_max);
+    const size_t n = std::min<size_t>(pages.size(), s.n_pages);
+    for (size_t i = 0; i < n;) {   // a run of consecutive pages
+        dvt_memory_page run = pages[i];
+        size_t k = i + 1;
+        for (; k < n && pages[k].page == pages[k - 1].page + s.page_bytes; k++) {
+            run.loads += pages[k].loads; run.stores += pages[k].stores; run.pre_reads += pages[k].pre_reads; run.pre_writes += pages[k].pre_writes;
+            run.words += pages[k].words;
+        }
+        printf("0x%08x-0x%08x %12llu %12llu %12llu %12llu %10u\n", run.page, pages[k - 1].page + s.page_bytes - 1, u(run.loads), u(run.stores),
+               u(run.pre_reads), u(run.pre_writes), run.words);
+        i = k;
+    }
+    return 0;
+}
+
 int main(int argc, char **argv) {
-    if (argc < 2) return die("usage: dvt_prover_host prove|execute|verify|check|compact|expand --type T -i FILE [-o FILE] [--show-report] [--show-calls] [--compact] [--keep-trees] [--elf FILE] [--devices D0,D1,...] [--device D]");
+    if (argc < 2) return die("usage: dvt_prover_host prove|execute|verify|check|compact|expand --type T -i FILE [-o FILE] [--show-report] [--show-calls] [--show-memory] [--compact] [--keep-trees] [--elf FILE] [--devices D0,D1,...] [--device D]");
     const std::string verb = argv[1];
     std::string type, input, output, elf_path, schema_path, devices, verify_device;
-    bool show_report = false, show_calls = false, auth = false, compact = false, keep_trees = false;
+    bool show_report = false, show_calls = false, show_memory = false, auth = false, compact = false, keep_trees = false;
     for (int i = 2; i < argc; i++) {
         std::string a = argv[i], inline_val;
         bool has_inline = false;
@@ -124,6 +154,7 @@ int main(int argc, char **argv) {
         else if (a == "--device") verify_device = next();   // verify: the query part on that GPU (dvt_prover_verify)
         else if (a == "--show-report") show_report = true;
         else if (a == "--show-calls") show_calls = true;
+        else if (a == "--show-memory") show_memory = true;
         else if (a == "--compact") compact = true;       // prove: shard proofs in the compact form ("compact_openings")
         else if (a == "--keep-trees") keep_trees = true;  // prove / check: shards that do not fit in HBM in full keep their main Merkle tree ("keep_phase1": 2)
         else if (a == "--auth-commitment") auth = true;  // the reference selects this at build time (cargo feature)
@@ -215,6 +246,13 @@ int main(int argc, char **argv) {
                 }))
                 return die(std::string("Verification failed: ") + (cerr ? cerr : "?"));
         }
+        if (show_memory) {
+            char *merr = nullptr;
+            if (print_memory([&](uint64_t *ft, size_t cap_instr, dvt_memory_page *pages, size_t cap_pages, dvt_memory_summary *s) {
+                    return dvt_execute_memory(elf.data(), elf.size(), &buf, 1, 0, ft, cap_instr, pages, cap_pages, s, nullptr, &merr);
+                }))
+                return die(std::string("Verification failed: ") + (merr ? merr : "?"));
+        }
         return 0;
     }
 
@@ -267,6 +305,11 @@ int main(int argc, char **argv) {
                 return dvt_rv32_job_calltree(p, pk, job, 0, arcs, cap_arcs, funcs, cap_funcs, s);
             }))
             return die(std::string("Call tree failed: ") + dvt_last_error(p));
+        if (show_memory &&
+            print_memory([&](uint64_t *ft, size_t cap_instr, dvt_memory_page *pages, size_t cap_pages, dvt_memory_summary *s) {
+                return dvt_rv32_job_memory(p, pk, job, ft, cap_instr, pages, cap_pages, s);
+            }))
+            return die(std::string("Memory report failed: ") + dvt_last_error(p));
         dvt_job_free(p, job);
         dvt_pk_free(p, pk);
         dvt_prover_destroy(p);

@@ -140,4 +140,30 @@ hipError_t launch_calltree_summary(hipStream_t st, const rv32::CycleRec *d_recs,
 hipError_t launch_calltree_emit(hipStream_t st, const rv32::CycleRec *d_recs, size_t n_recs, uint32_t last_succ, size_t span0,
                                 unsigned long long base_position, const CalltreeTables &t);
 
+// memreport.hip
+// The device tables of the memory report (memreport.h) and one pass over the cycle records of a shard into them.  Everything
+// but sp[0] (all ones) is zeroed by the caller; classes / offs: memrep::instr_class and Instr::off per instruction; pre: the
+// rows of memrep::pre_shapes(), six words each.  The records are only read.
+enum MemoryCounter { MEMORY_CYCLES, MEMORY_PRE_CALLS, MEMORY_SP_WRITES, MEMORY_BAD_RECORDS, MEMORY_COUNTERS };
+enum MemoryPageArray { MEMORY_LOADS, MEMORY_STORES, MEMORY_FIRST, MEMORY_PRE_READS, MEMORY_PRE_WRITES, MEMORY_PAGE_ARRAYS };
+struct MemoryTables {
+    unsigned long long *first_touch;                 // [n_instr]
+    unsigned long long *page_ctr;                    // [MEMORY_PAGE_ARRAYS][memrep::N_PAGES], dense over the address space
+    unsigned long long *counters;                    // [MEMORY_COUNTERS]
+    uint32_t *sp;                                    // [2]: the minimum and the maximum of the values written to x2
+    uint32_t *bitmap;                                // [memrep::BITMAP_WORDS]: one bit per word of guest memory
+    const uint32_t *classes, *offs;                  // [n_instr]
+    const uint32_t *pre;                             // [n_pre][6]
+    uint32_t n_instr, n_pre;
+};
+hipError_t launch_memory_records(hipStream_t st, const rv32::CycleRec *d_recs, size_t n_recs, const MemoryTables &t);
+// after the shards: every page with a counted access as one dense entry (its counters and its 128-byte bitmap line), in no
+// order, the first cap of them; *n_dense (zeroed by the caller) counts all
+struct MemoryDensePage {
+    uint32_t page, first;
+    unsigned long long loads, stores, pre_reads, pre_writes;
+    uint32_t bits[32];
+};
+hipError_t launch_memory_gather(hipStream_t st, const MemoryTables &t, MemoryDensePage *d_dense, uint32_t cap, uint32_t *d_n_dense);
+
 }  // namespace dvt

@@ -128,7 +128,7 @@ void dvt_free(void *ptr);
  * dvt_stage_multipath_nodes, dvt_stage_verify_multipath, dvt_debug_compact_list_sweep; 12: dvt_rv32_job_profile,
  * dvt_execute_profile; 13: "keep_phase1": 2, "keep_full_max", DVT_KEEP_*, dvt_rv32_job_shard_kept,
  * dvt_rv32_job_shard_kept_bytes, dvt_debug_keep_plan; 14: dvt_rv32_job_calltree,
- * dvt_rv32_job_calltree_times, dvt_execute_calltree) */
+ * dvt_rv32_job_calltree_times, dvt_execute_calltree; 15: dvt_rv32_job_memory, dvt_execute_memory) */
 uint32_t dvt_abi_version(void);
 /* the handle's hipStream_t (for event timing by the caller) */
 void *dvt_stream(dvt_prover *p);
@@ -763,6 +763,58 @@ int dvt_rv32_job_calltree_times(dvt_prover *p, double out[3]);
 int dvt_execute_calltree(const uint8_t *elf, size_t elf_len, const dvt_buf *stdin_bufs, size_t nbuf, uint64_t max_cycles,
                          dvt_calltree_arc *arcs, size_t cap_arcs, dvt_calltree_func *funcs, size_t cap_funcs,
                          dvt_calltree_summary *summary, dvt_report *report, char **err_text);
+/* The memory report of a prepared job: which pages the execution loads from and stores to, how many distinct words it
+ * accesses, which instructions access words first, and how far the stack pointer moves; from the cycle records of the shards
+ * the job holds (one launch per shard on the device that holds it; the records are only read and the job is left as found,
+ * so a dvt_rv32_prove_job afterwards returns the bytes it would have returned without).  Every distinct word an execution
+ * accesses is a row of the mem_init table of the last shard: the report names what makes that table tall.
+ * Words are the 4-byte aligned guest addresses below 0x38000000, pages are 4096 bytes; the registers are never part of the
+ * report (nor is the a1 read that ECALLs make through the memory port).
+ *   loads, stores   a record whose instruction is lb lh lw lbu lhu is one load, sb sh sw one store, of the word at
+ *                   (rs1 value + offset) & ~3
+ *   first touches   a load or store whose word no shard accessed before (the previous shard of the access is 0; shards are
+ *                   numbered from 1) is the first access of that word in the whole execution, whether the word is part of
+ *                   the image, was hinted (HINT_READ sets initial values without an access: the load that reads a hinted
+ *                   word touches it first) or neither: first_touch[i] counts them per instruction i = (pc - text_base) / 4,
+ *                   n_instr entries; `first` of a page per page
+ *   precompiles     from the ECALL record (t0, a0, a1): SHA_EXTEND is 16 reads and 48 writes of the 64 words at a0;
+ *                   SHA_COMPRESS 64 reads at a0, 8 reads and 8 writes at a1; a field, curve or u256 call reads its second
+ *                   operand at a1 and reads and writes its first at a0.  They count into pre_reads / pre_writes of the page
+ *                   of each word (an array may straddle a page) and into pre_calls.  HALT, WRITE, COMMIT, HINT_LEN and
+ *                   HINT_READ access nothing in this sense.
+ *   words           of a page: the distinct words any counted access hit.  The records do not say whether a precompile word
+ *                   was touched first by the call, but on a whole execution words - first_touches (of the summary) is the
+ *                   number of words first touched by a precompile call.
+ *   pages           every page with at least one counted access, sorted by address (`page` is its byte address)
+ *   stack           over the records whose instruction has rd == x2: sp_writes, and sp_min / sp_max of the value written
+ *                   (all three 0 without such a record)
+ *   summary         the totals of the above, n_pages; image_words = the words of the program image, image_words_accessed =
+ *                   those of them that were accessed; mem_init_rows = 32 + image_words + words - image_words_accessed, the
+ *                   rows of the mem_init table before padding, when the job holds every shard of its execution, else 0;
+ *                   ms = wall clock of the call after the entry guard
+ * On a prepare_part job the report covers the held shards (shards_tallied of shards_total): counters are sums, words is
+ * distinct over the held shards, mem_init_rows is 0.  Handles with several members work: the host merges the members'
+ * tables.  Nothing is bounded or probabilistic: every figure is exact and nothing can be dropped.
+ * Arrays, caps, the size query, DVT_ERR_INPUT and DVT_ERR_DEVICE as dvt_rv32_job_profile (also DVT_ERR_INPUT: a cycle record
+ * that names an instruction outside the text or an address outside guest memory).  Like every call on the handle it stops a
+ * running prove_shard pipeline first. */
+typedef struct {
+    uint32_t page, words, first, pad;   /* page: byte address */
+    uint64_t loads, stores, pre_reads, pre_writes;
+} dvt_memory_page;
+typedef struct {
+    uint64_t cycles, loads, stores, pre_reads, pre_writes, pre_calls, words, first_touches, image_words, image_words_accessed, mem_init_rows, sp_writes;
+    uint32_t sp_min, sp_max, text_base, n_instr, n_pages, page_bytes, shards_tallied, shards_total;
+    float ms;
+} dvt_memory_summary;
+int dvt_rv32_job_memory(dvt_prover *p, const dvt_pk *pk, dvt_job *job, uint64_t *first_touch, size_t cap_instr, dvt_memory_page *pages,
+                        size_t cap_pages, dvt_memory_summary *summary);
+/* The same report on the host alone (no GPU is touched), as dvt_execute_profile runs the guest: shard by shard through the
+ * same rule in plain C++.  Return codes, *report and *err_text as dvt_execute gives them; the tables are filled for whatever
+ * retired, also when the guest fails (mem_init_rows then counts the words accessed so far). */
+int dvt_execute_memory(const uint8_t *elf, size_t elf_len, const dvt_buf *stdin_bufs, size_t nbuf, uint64_t max_cycles,
+                       uint64_t *first_touch, size_t cap_instr, dvt_memory_page *pages, size_t cap_pages, dvt_memory_summary *summary,
+                       dvt_report *report, char **err_text);
 /* test hook: run K0 on one shard of a prepared job and return the device-generated main traces
  * (canonical); blob layout as dvt_rv32_debug_traces with prep_width = 0. */
 int dvt_rv32_debug_device_traces(dvt_prover *p, const dvt_pk *pk, dvt_job *job, size_t shard, uint32_t **blob,

@@ -5,6 +5,7 @@ with --host).
     python tools/profile_guest.py --guest 'bignum(40)' [--top N] [--json OUT] [--host] [--log-shard L]
     python tools/profile_guest.py --elf guest.elf [--stdin FILE ...]
     python tools/profile_guest.py --guest 'bignum(40)' --calls [--host]
+    python tools/profile_guest.py --guest 'bignum(40)' --memory [--host]
 
 The guest is an expression over the functions of tests/guests*.py (its ELF is the value, or the first element of it), or an
 ELF file with its stdin buffers.  The guests are stripped (tools/rvasm.py writes program headers only), so function entries
@@ -16,7 +17,12 @@ writes the same with the raw tables.
 --calls adds the call-tree report (dvt_rv32_job_calltree on the GPU, dvt_execute_calltree with --host): per function f_<pc> its
 inclusive cycles, its self cycles and its calls, measured from the calls and returns of the execution instead of address ranges
 (a tail jump or a shared helper is charged to the function that was called), then the heaviest caller -> callee arcs; --json
-carries both tables."""
+carries both tables.
+
+--memory adds the memory report (dvt_rv32_job_memory on the GPU, dvt_execute_memory with --host): the accessed address ranges
+(runs of consecutive pages merged) with their loads, stores, precompile reads and writes and distinct words; per function the
+words its instructions touched first (first_touch summed over the same address ranges as the flat profile: every such word is
+a row of the mem_init table), the remainder that precompile calls touched first, and the span of the stack pointer."""
 import argparse
 import importlib
 import json
@@ -29,7 +35,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 def guest_elf(expr):
     scope = {}
-    for mod in ("guests", "guests_bls", "guests_finalization", "guests_share", "guests_profile", "guests_calltree"):
+    for mod in ("guests", "guests_bls", "guests_finalization", "guests_share", "guests_profile", "guests_calltree", "guests_memory"):
         m = importlib.import_module("tests." + mod)
         scope.update({k: getattr(m, k) for k in dir(m) if not k.startswith("_") and k not in scope})
     v = eval(expr if "(" in expr else expr + "()", scope)   # noqa: S307 (the caller's own command line)
@@ -77,6 +83,29 @@ def flat_profile(elf, prof):
     return funcs, [dict(from_pc=a, to_pc=b, count=c) for c, a, b in branches]
 
 
+def page_ranges(pages, page_bytes=4096):
+    """runs of consecutive pages merged: [dict(first, last (inclusive byte addresses), loads, stores, pre_reads, pre_writes, words)]"""
+    keys = ("loads", "stores", "pre_reads", "pre_writes", "words")
+    out = []
+    for pg in pages:
+        if out and out[-1]["last"] + 1 == pg["page"]:
+            out[-1]["last"] = pg["page"] + page_bytes - 1
+            for k in keys:
+                out[-1][k] += pg[k]
+        else:
+            out.append(dict({k: pg[k] for k in keys}, first=pg["page"], last=pg["page"] + page_bytes - 1))
+    return out
+
+
+def first_touch_by_function(elf, funcs, first_touch):
+    """[dict(name, pc, words)] by words descending: first_touch summed over the address range of every function of flat_profile"""
+    base, _ = text_words(elf)
+    lowest = min(f["pc"] for f in funcs)
+    rows = [dict(name=f["name"], pc=f["pc"], words=int(first_touch[((base if f["pc"] == lowest else f["pc"]) - base) // 4:(f["end"] - base) // 4].sum()))
+            for f in funcs]
+    return sorted((r for r in rows if r["words"]), key=lambda r: (-r["words"], r["pc"]))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--guest")
@@ -89,6 +118,7 @@ def main():
     ap.add_argument("--log-edge-slots", type=int, default=0)
     ap.add_argument("--calls", action="store_true", help="also the call-tree report: inclusive and self cycles per function, the heaviest arcs")
     ap.add_argument("--log-arc-slots", type=int, default=0)
+    ap.add_argument("--memory", action="store_true", help="also the memory report: accessed ranges, first touches per function, the stack span")
     args = ap.parse_args()
     if bool(args.guest) == bool(args.elf):
         ap.error("one of --guest and --elf")
@@ -101,6 +131,7 @@ def main():
         if prof is None:
             raise SystemExit("execute failed: %s" % err)
         tree = capi.execute_calltree(elf, stdin)[2] if args.calls else None
+        mem = capi.execute_memory(elf, stdin)[2] if args.memory else None
         if rc:
             print("the guest failed (%s): the profile of what retired" % err)
     else:
@@ -109,6 +140,7 @@ def main():
         job, rep = p.prepare(pk, stdin)
         prof = p.job_profile(pk, job, args.log_edge_slots)
         tree = p.job_calltree(pk, job, args.log_arc_slots) if args.calls else None
+        mem = p.job_memory(pk, job) if args.memory else None
         p.job_free(job)
         p.pk_free(pk)
         p.close()
@@ -138,6 +170,23 @@ def main():
             print("  %-12s -> %-12s %14d cycles %12d calls" % ("(root)" if caller is None else "f_%x" % caller, "f_%x" % callee, cyc, n))
         calls = dict(calltree=dict(summary=t, functions=[dict(name="f_%x" % pc, pc=pc, calls=n, inclusive=inc, self=own) for pc, n, inc, own in tree["funcs"]],
                                    arcs=[dict(caller_pc=a, callee_pc=b, calls=n, cycles=c) for a, b, n, c in tree["arcs"]]))
+    if mem:
+        m = mem["summary"]
+        ranges, by_func = page_ranges(mem["pages"], m["page_bytes"]), first_touch_by_function(elf, funcs, mem["first_touch"])
+        print("memory: %d words on %d pages (%d of the %d image words), mem_init rows %d; %d loads, %d stores, %d precompile calls with %d reads and %d writes, "
+              "%d of %d shards, %.2f ms" % (m["words"], m["n_pages"], m["image_words_accessed"], m["image_words"], m["mem_init_rows"], m["loads"], m["stores"],
+                                            m["pre_calls"], m["pre_reads"], m["pre_writes"], m["shards_tallied"], m["shards_total"], m["ms"]))
+        print("%-23s %12s %12s %12s %12s %10s" % ("range", "loads", "stores", "pre reads", "pre writes", "words"))
+        for r in ranges:
+            print("0x%08x-0x%08x %12d %12d %12d %12d %10d" % (r["first"], r["last"], r["loads"], r["stores"], r["pre_reads"], r["pre_writes"], r["words"]))
+        print("%-12s %14s   (words first touched by a load or store of the function)" % ("function", "first touches"))
+        for f in by_func[:args.top]:
+            print("%-12s %14d" % (f["name"], f["words"]))
+        print("first touched by precompile calls (or outside the held shards): %d words" % (m["words"] - m["first_touches"]))
+        print("stack pointer: %d writes, 0x%08x .. 0x%08x (%d bytes)" % (m["sp_writes"], m["sp_min"], m["sp_max"], m["sp_max"] - m["sp_min"]))
+        calls = dict(calls, memory=dict(summary=m, ranges=ranges, pages=mem["pages"], first_touch=[int(x) for x in mem["first_touch"]],
+                                        first_touch_by_function=by_func, precompile_first_touches=m["words"] - m["first_touches"],
+                                        stack=dict(writes=m["sp_writes"], min=m["sp_min"], max=m["sp_max"])))
     if args.json:
         with open(args.json, "w") as f:
             json.dump(dict(calls, summary=s, functions=funcs, branches=branches, opcodes=prof["opcodes"], syscalls={"0x%x" % k: v for k, v in prof["syscalls"].items()},
