@@ -186,6 +186,10 @@ def load():
     mem_out = [C.POINTER(u64), sz, C.POINTER(MemoryPage), sz, C.POINTER(MemorySummary)]
     lib.dvt_rv32_job_memory.argtypes = [vp, vp, vp] + mem_out
     lib.dvt_execute_memory.argtypes = [C.c_char_p, sz, C.POINTER(Buf), sz, u64] + mem_out + [C.POINTER(Report), C.POINTER(C.c_char_p)]
+    watch_io = [C.POINTER(WatchQuery), sz, sz, C.POINTER(WatchHit), C.POINTER(u64), C.POINTER(WatchSummary)]
+    lib.dvt_rv32_job_watch.argtypes = [vp, vp, vp] + watch_io
+    lib.dvt_rv32_job_watch_times.argtypes = [vp, C.POINTER(C.c_double)]
+    lib.dvt_execute_watch.argtypes = [C.c_char_p, sz, C.POINTER(Buf), sz, u64, u32] + watch_io + [C.POINTER(Report), C.POINTER(C.c_char_p)]
     lib.dvt_stdin_from_json.argtypes = [C.c_char_p, C.c_char_p, sz, C.c_int, C.POINTER(u8p), C.POINTER(sz), C.POINTER(C.c_char_p)]
     _lib = lib
     return lib
@@ -518,6 +522,82 @@ def execute_memory(elf: bytes, stdin=(), max_cycles=0):
         return lib.dvt_execute_memory(elf, len(elf), bufs, len(stdin), max_cycles, *out, C.byref(rep), C.byref(err))
     rc, mem = _memory(call)
     return rc, dict(cycles=rep.cycles, exit_code=rep.exit_code, halted=bool(rep.halted), unprovable=bool(rep.unprovable)), mem, _take_str(lib, err)
+
+
+# ---- watchpoints (csrc/watch.h)
+DVT_WATCH_MAX_QUERIES, DVT_WATCH_MAX_KEEP, DVT_WATCH_SPAN = 16, 256, 4096
+DVT_WATCH_PC, DVT_WATCH_REG, DVT_WATCH_MEM = 1, 2, 3
+DVT_WATCH_LOAD, DVT_WATCH_STORE, DVT_WATCH_PRE_READ, DVT_WATCH_PRE_WRITE, DVT_WATCH_VALUE, DVT_WATCH_HIT_NO_VALUE = 1, 2, 4, 8, 16, 32
+WATCH_EVERYWHERE = ((0, 0), (0xFFFFFFFF, 0xFFFFFFFF))   # the window (from, to) that searches every position
+
+
+class WatchQuery(C.Structure):
+    _fields_ = [(name, C.c_uint32) for name in ("kind", "flags", "lo", "hi", "mask", "want", "from_shard", "from_row", "to_shard", "to_row")]
+
+
+class WatchHit(C.Structure):
+    _fields_ = [(name, C.c_uint32) for name in ("query", "shard", "row", "pc", "idx", "kind", "flags", "addr", "n_words", "before", "after",
+                                                "rd_value", "rs1", "rs2", "prev_shard", "prev_clk")]
+
+
+class WatchSummary(C.Structure):
+    _fields_ = [("cycles", C.c_uint64)] + [(name, C.c_uint32) for name in ("n_queries", "cap_each", "shards_searched", "shards_total", "text_base",
+                                                                           "n_instr", "span")] + [("ms", C.c_float)]
+
+
+def _watch_query(kind, flags, lo, hi, mask, want, window):
+    (fs, fr), (ts, tr) = window or WATCH_EVERYWHERE
+    return dict(kind=kind, flags=flags, lo=lo, hi=hi, mask=mask, want=want, from_shard=fs, from_row=fr, to_shard=ts, to_row=tr)
+
+
+def watch_pc(lo, hi=None, window=None):
+    """the records whose pc lies in [lo, hi) (hi = None: the instruction at lo); window = ((shard, row), (shard, row)), `to` exclusive"""
+    return _watch_query(DVT_WATCH_PC, 0, lo, lo + 4 if hi is None else hi, 0, 0, window)
+
+
+def watch_reg(reg, value=None, mask=0xFFFFFFFF, window=None):
+    """the records that write register `reg` (1..31); value: only those that write (value & mask)"""
+    return _watch_query(DVT_WATCH_REG, 0 if value is None else DVT_WATCH_VALUE, reg, reg + 1, mask if value is not None else 0, value or 0, window)
+
+
+def watch_mem(lo, hi=None, flags=DVT_WATCH_LOAD | DVT_WATCH_STORE | DVT_WATCH_PRE_READ | DVT_WATCH_PRE_WRITE, value=None, mask=0xFFFFFFFF, window=None):
+    """the accesses of the words in [lo, hi) (hi = None: the word at lo) in the directions of flags; value: only the loads and
+    stores that leave (value & mask) in the word"""
+    return _watch_query(DVT_WATCH_MEM, flags | (0 if value is None else DVT_WATCH_VALUE), lo, lo + 4 if hi is None else hi,
+                        mask if value is not None else 0, value or 0, window)
+
+
+_HIT_KEYS = [name for name, _ in WatchHit._fields_]
+
+
+def _watch(call, queries, keep):
+    """The search through call(queries, n, cap_each, hits, totals, summary) -> rc.  Returns (rc, [dict(total, first = [hit dicts],
+    last = [hit dicts])] per query or None when the call fails without lists, summary dict or None)."""
+    n = len(queries)
+    qs = (WatchQuery * max(n, 1))(*[WatchQuery(**q) for q in queries])
+    hits = (WatchHit * max(2 * n * keep, 1))()
+    totals = (C.c_uint64 * max(n, 1))()
+    s = WatchSummary()
+    rc = call(qs, n, keep, hits, totals, C.byref(s))
+    if rc not in (DVT_OK, DVT_ERR_GUEST):
+        return rc, None, None
+    out = []
+    for q in range(n):
+        k = min(keep, int(totals[q]))
+        lists = [[{name: int(getattr(hits[(2 * q + half) * keep + i], name)) for name in _HIT_KEYS} for i in range(k)] for half in (0, 1)]
+        out.append(dict(total=int(totals[q]), first=lists[0], last=lists[1]))
+    return rc, out, {name: (float if name == "ms" else int)(getattr(s, name)) for name, _ in WatchSummary._fields_}
+
+
+def execute_watch(elf: bytes, stdin=(), queries=(), keep=16, max_cycles=0, log_shard=21):
+    """Host-only watchpoints (dvt_execute_watch): the guest runs in shards of 2^log_shard cycles and every retired instruction
+    is tested against the queries (watch_pc / watch_reg / watch_mem).  Returns (rc, report dict as execute() gives it, per query
+    dict(total, first, last) as Prover.job_watch gives them or None, error text)."""
+    lib = load()
+    rep, err, bufs = Report(), C.c_char_p(), _bufs(stdin)
+    rc, found, _ = _watch(lambda *io: lib.dvt_execute_watch(elf, len(elf), bufs, len(stdin), max_cycles, log_shard, *io, C.byref(rep), C.byref(err)),
+                          list(queries), keep)
+    return rc, dict(cycles=rep.cycles, exit_code=rep.exit_code, halted=bool(rep.halted), unprovable=bool(rep.unprovable)), found, _take_str(lib, err)
 
 
 def exec_rate(elf: bytes, stdin=(), log_shard=21, trace=False) -> float:
@@ -1190,6 +1270,21 @@ class Prover:
         rc, mem = _memory(lambda *out: self.lib.dvt_rv32_job_memory(self.h, pk, job, *out))
         self.check(rc)
         return mem
+
+    def job_watch(self, pk, job, queries, keep=16, summary=False):
+        """Watchpoints on a prepared job, from the cycle records of the shards it holds on the GPU (dvt_rv32_job_watch): per query
+        (watch_pc / watch_reg / watch_mem dicts, at most 16) dict(total = the exact number of hits, first = the first
+        min(keep, total) hits in execution order, last = the last min(keep, total)); a hit is a dict of the fields of
+        dvt_watch_hit.  keep <= 256.  summary=True: (that list, the summary dict)."""
+        rc, found, s = _watch(lambda *io: self.lib.dvt_rv32_job_watch(self.h, pk, job, *io), list(queries), keep)
+        self.check(rc)
+        return (found, s) if summary else found
+
+    def job_watch_times(self):
+        """of the last job_watch: dict(count_ms, scan_ms, emit_ms (stream events, summed over members), emit_shards)"""
+        out = (C.c_double * 4)()
+        self.check(self.lib.dvt_rv32_job_watch_times(self.h, out))
+        return dict(count_ms=out[0], scan_ms=out[1], emit_ms=out[2], emit_shards=int(out[3]))
 
     def job_calltree_times(self):
         """milliseconds of the last job_calltree: dict(summary_ms, merge_ms, emit_ms)"""

@@ -1,7 +1,8 @@
 // The inspectors of trace rows of the C ABI (include/dvt_prover.h): row checks, bus ledger, forgery hunt, join hunt.  Each has
 // stage entry points (dvt_stage_*) on a table the caller uploaded (stage_table) and job entry points (dvt_rv32_*) on the
 // tables of a prepared job's held shards (shard_view).  The execution report (profile.h), the call-tree report (calltree.h)
-// and the memory report (memreport.h) are the inspectors that read a job's cycle records instead of its tables.
+// and the memory report (memreport.h) are the inspectors that read a job's cycle records instead of its tables; the watchpoint
+// search (watch.h) reads the same records and returns the ones that match.
 #include <algorithm>
 
 #include "calltree.h"
@@ -10,6 +11,7 @@
 #include "memreport.h"
 #include "profile.h"
 #include "sha256.h"
+#include "watch.h"
 
 using namespace dvt;
 
@@ -597,14 +599,200 @@ static int job_memory(dvt_prover *p, const dvt_pk *pk, dvt_job *j, const memrep:
     return DVT_OK;
 }
 
+// ------------------------------------------------------------------ watchpoints (dvt_rv32_job_watch)
+// Count and scan per member on lane 0's stream with buffers from lane 0's pool (one count launch and one scan launch per shard
+// it holds); the host downloads n_queries totals per shard, adds them in execution order over all members and derives, per
+// query, the ranks to keep; the emit pass runs again over those shards alone that have a kept rank, and every member's kept
+// hits are copied from its own array to the caller's slots.  Nothing is sorted: a slot is a rank.
+namespace {
+struct WatchMember {
+    StageBuf base, hits;
+    std::vector<size_t> span0;            // of the member's k-th shard
+    size_t spans = 0;
+    uint32_t *d_counts = nullptr, *d_offs = nullptr, *d_totals = nullptr;
+    std::vector<uint32_t> totals;         // [shard k][query]
+    std::vector<dvt_watch_hit> h_hits;
+    hipEvent_t ev[5] = {};                // count [0, 1], scan [1, 2], emit [3, 4]
+    bool emitted = false;
+    explicit WatchMember(DevPool &pool) : base{pool}, hits{pool} {}
+    ~WatchMember() {
+        for (hipEvent_t x : ev)
+            if (x) (void)hipEventDestroy(x);
+    }
+};
+// the members' buffers go back to their pools under their own device's turn
+struct WatchRun {
+    dvt_prover *p;
+    std::vector<std::unique_ptr<WatchMember>> mem;
+    ~WatchRun() {
+        for (size_t m = 0; m < mem.size(); m++) {
+            (void)turn_to(p, m);
+            mem[m].reset();
+        }
+        (void)turn_to(p, 0);
+    }
+};
+}  // namespace
+
+static int job_watch(dvt_prover *p, const dvt_pk *pk, dvt_job *j, const dvt_watch_query *queries, size_t nq, uint32_t K, dvt_watch_hit *hits,
+                     uint64_t *totals, dvt_watch_summary *summary) {
+    if (int rc = same_members(p, pk, j)) return rc;
+    const auto t0 = Clock::now();
+    const size_t n = pk->prog.instrs.size() - 1, G = n_members(p);
+    std::vector<uint32_t> statics(2 * n);   // the static words, then the offsets
+    for (size_t i = 0; i < n; i++) {
+        statics[i] = watch::instr_static(pk->prog.instrs[i]);
+        statics[n + i] = pk->prog.instrs[i].off;
+    }
+    WatchArgs args{};
+    std::copy_n(queries, nq, args.q);
+    args.sh = watch::shapes();
+    args.n_instr = (uint32_t)n; args.text_base = pk->prog.text_base; args.n_queries = (uint32_t)nq;
+    WatchRun run{p, {}};
+    std::vector<const uint32_t *> d_statics(G, nullptr);
+    uint64_t cycles = 0;
+    unsigned long long bad = 0;
+
+    // ---- count and scan
+    for (size_t m = 0; m < G; m++) {
+        if (int rc = turn_to(p, m)) return rc;
+        const Lane c = lane0(p, m);
+        Engine &e = c.eng;
+        run.mem.emplace_back(new WatchMember(e.pool));
+        WatchMember &wm = *run.mem.back();
+        JobPart &part = j->parts[m];
+        for (auto &s : part.shards) {
+            wm.span0.push_back(wm.spans);
+            wm.spans += (s.n_recs + watch::SPAN - 1) / watch::SPAN;
+            cycles += s.n_recs;
+        }
+        if (part.shards.empty()) continue;
+        for (auto &x : wm.ev) HIP_TRY(c.err, hipEventCreate(&x));
+        // the bad-record counter (64 bits), then u32: span counts, span offsets, shard totals, the static words
+        const size_t span_words = std::max<size_t>(wm.spans, 1) * nq, total_words = part.shards.size() * nq;
+        HIP_TRY(c.err, e.pool.alloc_bytes(&wm.base.ptr, 8 + (2 * span_words + total_words + statics.size()) * 4));
+        unsigned long long *d_bad = static_cast<unsigned long long *>(wm.base.ptr);
+        wm.d_counts = reinterpret_cast<uint32_t *>(d_bad + 1);
+        wm.d_offs = wm.d_counts + span_words;
+        wm.d_totals = wm.d_offs + span_words;
+        uint32_t *d_stat = wm.d_totals + total_words;
+        d_statics[m] = d_stat;
+        args.statics = d_stat; args.offs = d_stat + n;
+        HIP_TRY(c.err, hipMemsetAsync(wm.base.ptr, 0, 8 + (2 * span_words + total_words) * 4, e.stream));
+        HIP_TRY(c.err, hipMemcpyAsync(d_stat, statics.data(), statics.size() * 4, hipMemcpyHostToDevice, e.stream));
+        HIP_TRY(c.err, hipEventRecord(wm.ev[0], e.stream));
+        for (size_t k = 0; k < part.shards.size(); k++) {
+            const ShardJob &s = part.shards[k];
+            args.shard = s.index;
+            HIP_TRY(c.err, launch_watch_count(e.stream, s.d_recs, s.n_recs, args, wm.d_counts + wm.span0[k] * nq, d_bad));
+        }
+        HIP_TRY(c.err, hipEventRecord(wm.ev[1], e.stream));
+        for (size_t k = 0; k < part.shards.size(); k++) {
+            const size_t n_spans = (part.shards[k].n_recs + watch::SPAN - 1) / watch::SPAN;
+            HIP_TRY(c.err, launch_watch_scan(e.stream, wm.d_counts + wm.span0[k] * nq, wm.d_offs + wm.span0[k] * nq, (uint32_t)n_spans, (uint32_t)nq,
+                                             wm.d_totals + k * nq));
+        }
+        HIP_TRY(c.err, hipEventRecord(wm.ev[2], e.stream));
+        wm.totals.resize(total_words);
+        unsigned long long h_bad = 0;
+        if (!e.download(wm.totals.data(), wm.d_totals, total_words * 4) || !e.download(&h_bad, d_bad, 8)) return engine_fail(c.err, e);
+        bad += h_bad;
+    }
+    if (turn_to(p, 0)) return DVT_ERR_DEVICE;
+    if (bad) return fail(p, DVT_ERR_INPUT, "%llu cycle records name an instruction outside the text or an address outside guest memory", bad);
+
+    // ---- the ranks: the held shards in execution order, whichever member holds them
+    struct Held { uint32_t index; size_t m, k; };
+    std::vector<Held> held;
+    for (size_t m = 0; m < G; m++)
+        for (size_t k = 0; k < j->parts[m].shards.size(); k++) held.push_back({j->parts[m].shards[k].index, m, k});
+    std::sort(held.begin(), held.end(), [](const Held &a, const Held &b) { return a.index < b.index; });
+    std::vector<std::vector<unsigned long long>> base_of(held.size(), std::vector<unsigned long long>(nq, 0));
+    WatchEmitArgs ea{};
+    ea.cap_each = K;
+    for (size_t h = 0; h < held.size(); h++)
+        for (size_t q = 0; q < nq; q++) {
+            base_of[h][q] = ea.total[q];
+            ea.total[q] += run.mem[held[h].m]->totals[held[h].k * nq + q];
+        }
+    for (size_t q = 0; q < nq; q++) totals[q] = ea.total[q];
+    // the kept ranks of query q among [lo, hi)
+    auto kept_in = [&](size_t q, unsigned long long lo, unsigned long long hi) {
+        const watch::Keep keep = watch::keep_of(ea.total[q], K);
+        return hi > lo && (lo < keep.first_end || hi > keep.last_begin);
+    };
+
+    // ---- emit: only the shards with a kept rank
+    double emit_shards = 0;
+    for (size_t h = 0; K && h < held.size(); h++) {
+        const size_t m = held[h].m, k = held[h].k;
+        WatchMember &wm = *run.mem[m];
+        bool any = false;
+        for (size_t q = 0; q < nq; q++) any = any || kept_in(q, base_of[h][q], base_of[h][q] + wm.totals[k * nq + q]);
+        if (!any) continue;
+        if (int rc = turn_to(p, m)) return rc;
+        const Lane c = lane0(p, m);
+        Engine &e = c.eng;
+        if (!wm.emitted) {
+            HIP_TRY(c.err, e.pool.alloc_bytes(&wm.hits.ptr, 2 * nq * K * sizeof(dvt_watch_hit)));
+            HIP_TRY(c.err, hipEventRecord(wm.ev[3], e.stream));
+            wm.emitted = true;
+        }
+        const ShardJob &s = j->parts[m].shards[k];
+        args.statics = d_statics[m]; args.offs = d_statics[m] + n; args.shard = s.index;
+        std::copy(base_of[h].begin(), base_of[h].end(), ea.base);
+        HIP_TRY(c.err, launch_watch_emit(e.stream, s.d_recs, s.n_recs, args, ea, wm.d_counts + wm.span0[k] * nq, wm.d_offs + wm.span0[k] * nq, wm.hits.ptr));
+        emit_shards++;
+    }
+    double ms[3] = {0, 0, 0};
+    for (size_t m = 0; m < G; m++) {
+        WatchMember &wm = *run.mem[m];
+        if (!wm.ev[0]) continue;
+        if (int rc = turn_to(p, m)) return rc;
+        const Lane c = lane0(p, m);
+        Engine &e = c.eng;
+        float t = 0;
+        if (wm.emitted) {
+            HIP_TRY(c.err, hipEventRecord(wm.ev[4], e.stream));
+            wm.h_hits.resize(2 * nq * K);
+            if (!e.download(wm.h_hits.data(), wm.hits.ptr, wm.h_hits.size() * sizeof(dvt_watch_hit))) return engine_fail(c.err, e);
+            if (hipEventElapsedTime(&t, wm.ev[3], wm.ev[4]) == hipSuccess) ms[2] += t;
+        }
+        if (hipEventElapsedTime(&t, wm.ev[0], wm.ev[1]) == hipSuccess) ms[0] += t;
+        if (hipEventElapsedTime(&t, wm.ev[1], wm.ev[2]) == hipSuccess) ms[1] += t;
+    }
+    if (turn_to(p, 0)) return DVT_ERR_DEVICE;
+    // every kept rank from the array of the member whose shard holds it
+    for (size_t h = 0; K && h < held.size(); h++) {
+        const WatchMember &wm = *run.mem[held[h].m];
+        if (!wm.emitted) continue;
+        for (size_t q = 0; q < nq; q++) {
+            const watch::Keep keep = watch::keep_of(ea.total[q], K);
+            const unsigned long long lo = base_of[h][q], hi = lo + wm.totals[held[h].k * nq + q];
+            for (unsigned long long r = lo; r < std::min(hi, keep.first_end); r++) hits[2 * q * K + r] = wm.h_hits[2 * q * K + r];
+            for (unsigned long long r = std::max(lo, keep.last_begin); r < hi; r++) hits[(2 * q + 1) * K + (r - keep.last_begin)] = wm.h_hits[(2 * q + 1) * K + (r - keep.last_begin)];
+        }
+    }
+    for (int i = 0; i < 3; i++) p->watch_ms[i] = ms[i];
+    p->watch_ms[3] = emit_shards;
+    dvt_watch_summary out{};
+    out.cycles = cycles;
+    out.n_queries = (uint32_t)nq; out.cap_each = K;
+    out.shards_searched = (uint32_t)held.size(); out.shards_total = (uint32_t)j->n_total;
+    out.text_base = pk->prog.text_base; out.n_instr = (uint32_t)n; out.span = watch::SPAN;
+    out.ms = (float)ms_since(t0);
+    *summary = out;
+    return DVT_OK;
+}
+
 // The host-only reports (no GPU is touched): the guest in trace mode, where an instruction without a chip is recorded instead
-// of trapping, 2^21 cycles per shard and one shard's records in memory at a time.  begin(prog) once the ELF is loaded;
+// of trapping, 2^log_shard (2^21) cycles per shard and one shard's records in memory at a time.  begin(prog) once the ELF is loaded;
 // shard(prog, recs, n, last_succ) per shard in execution order; end(prog, ms) after the last, and a text it returns fails the
 // call with DVT_ERR_UNSUPPORTED.  Return codes, *report and *err_text as dvt_execute gives them; end runs for whatever retired,
 // also when the guest fails.
 template <class Begin, class Shard, class End>
 static int execute_traced(const uint8_t *elf, size_t elf_len, const dvt_buf *stdin_bufs, size_t nbuf, uint64_t max_cycles, dvt_report *report,
-                          char **err_text, Begin begin, Shard shard, End end) {
+                          char **err_text, Begin begin, Shard shard, End end, uint32_t log_shard = 21) {
     const auto t0 = Clock::now();
     rv32::Program prog;
     std::string err;
@@ -612,7 +800,7 @@ static int execute_traced(const uint8_t *elf, size_t elf_len, const dvt_buf *std
         if (err_text) *err_text = strdup(("ELF: " + err).c_str());
         return DVT_ERR_INPUT;
     }
-    constexpr uint32_t LOG_SHARD = 21;
+    const uint32_t LOG_SHARD = log_shard;
     std::vector<std::vector<uint8_t>> inputs(nbuf);
     for (size_t i = 0; i < nbuf; i++)
         if (stdin_bufs[i].len) inputs[i].assign(stdin_bufs[i].data, stdin_bufs[i].data + stdin_bufs[i].len);
@@ -744,6 +932,48 @@ int dvt_execute_memory(const uint8_t *elf, size_t elf_len, const dvt_buf *stdin_
             memrep::emit(prog, *t, t->shards, true, ms, out);
             return nullptr;
         });
+}
+
+// ---- watchpoints (watch.h)
+int dvt_rv32_job_watch(dvt_prover *p, const dvt_pk *pk, dvt_job *job, const dvt_watch_query *queries, size_t n_queries, size_t cap_each,
+                       dvt_watch_hit *hits, uint64_t *totals, dvt_watch_summary *summary) {
+    if (!p || !pk || !job || !summary) return fail(p, DVT_ERR_INPUT, "null argument");
+    std::string text;
+    if (const char *why = watch::input_error(queries, n_queries, cap_each, hits, totals, &text)) return fail(p, DVT_ERR_INPUT, "%s", why);
+    if (int rc = rv32_key(p, pk)) return rc;
+    Guard g(p); if (g.rc) return g.rc;
+    return job_watch(p, pk, job, queries, n_queries, (uint32_t)cap_each, hits, totals, summary);
+}
+
+int dvt_rv32_job_watch_times(dvt_prover *p, double out[4]) {
+    if (!p || !out) return DVT_ERR_INPUT;
+    std::lock_guard<std::mutex> lk(p->mu);
+    for (int i = 0; i < 4; i++) out[i] = p->watch_ms[i];
+    return DVT_OK;
+}
+
+// host-only: the same rule (watch::scan_records) over execute_traced's shards
+int dvt_execute_watch(const uint8_t *elf, size_t elf_len, const dvt_buf *stdin_bufs, size_t nbuf, uint64_t max_cycles, uint32_t log_shard_size,
+                      const dvt_watch_query *queries, size_t n_queries, size_t cap_each, dvt_watch_hit *hits, uint64_t *totals,
+                      dvt_watch_summary *summary, dvt_report *report, char **err_text) {
+    if (err_text) *err_text = nullptr;
+    if (!elf || (nbuf && !stdin_bufs) || !summary) return DVT_ERR_INPUT;
+    std::string text;
+    if (log_shard_size && (log_shard_size < 4 || log_shard_size > 22)) text = "log_shard_size must be 0 or 4..22";
+    if (!text.empty() || watch::input_error(queries, n_queries, cap_each, hits, totals, &text)) {
+        if (err_text) *err_text = strdup(text.c_str());
+        return DVT_ERR_INPUT;
+    }
+    std::unique_ptr<watch::Search> s;
+    return execute_traced(
+        elf, elf_len, stdin_bufs, nbuf, max_cycles, report, err_text,
+        [&](const rv32::Program &prog) { s.reset(new watch::Search(prog, queries, n_queries, (uint32_t)cap_each)); },
+        [&](const rv32::Program &prog, const rv32::CycleRec *recs, size_t n, uint32_t) { watch::scan_records(prog, recs, n, s->shards + 1, s.get()); },
+        [&](const rv32::Program &prog, double ms) -> const char * {
+            watch::emit(prog, *s, s->shards, ms, hits, totals, summary);
+            return s->bad ? "cycle records name an instruction outside the text or an address outside guest memory" : nullptr;
+        },
+        log_shard_size ? log_shard_size : 21);
 }
 
 // ---- the trace-row checks of one chip (check.cuh)

@@ -1,11 +1,11 @@
 // dvt_prover_host — the reference's CLI verbs (src/main.rs:58-106) over the C ABI.
 //
 //   dvt_prover_host prove   --type T -i INPUT.json [-o PROOF] [--elf GUEST.elf] [--devices D0,D1,...] [--compact]
-//   dvt_prover_host execute --type T -i INPUT.json [--show-report] [--show-calls] [--show-memory] [--elf GUEST.elf]
+//   dvt_prover_host execute --type T -i INPUT.json [--show-report] [--show-calls] [--show-memory] [--watch SPEC ...] [--elf GUEST.elf]
 //   dvt_prover_host verify  --type T -i PROOF [--elf GUEST.elf]
 //   dvt_prover_host compact --type T -i PROOF [-o PROOF] [--elf GUEST.elf]     (shared Merkle paths sent once: dvt_proof_compact)
 //   dvt_prover_host expand  --type T -i PROOF [-o PROOF] [--elf GUEST.elf]     (the inverse; verify takes either form)
-//   dvt_prover_host check   --type T -i INPUT.json [--show-report] [--show-calls] [--show-memory] [--elf GUEST.elf] [--devices D0,D1,...]
+//   dvt_prover_host check   --type T -i INPUT.json [--show-report] [--show-calls] [--show-memory] [--watch SPEC ...] [--elf GUEST.elf] [--devices D0,D1,...]
 //
 // T = bad-share | finalization | bad-partial-key | bad-encrypted-share (clap names of CircuitType, :36-42).
 // The reference embeds the four guest ELFs at build time (include_elf!, :115-118); they cannot be built in
@@ -30,6 +30,11 @@
 // GPU): one line "memory: cycles=N loads=N stores=N pre_reads=N pre_writes=N pre_calls=N words=N first_touches=N pages=N
 // image_words=N image_words_accessed=N mem_init_rows=N sp_writes=N sp_min=0xX sp_max=0xX", then one line per run of
 // consecutive accessed pages: "0xFIRST-0xLAST loads stores pre_reads pre_writes words" (byte addresses, LAST inclusive).
+// --watch SPEC (repeatable, at most 16): after those, the watchpoint search (dvt_execute_watch on the host, dvt_rv32_job_watch on
+// the GPU; csrc/watch.h).  SPEC is pc:ADDR[+BYTES], reg:NAME[=VALUE[/MASK]] (x1..x31 or an ABI name) or one of load: store: pread:
+// pwrite: mem: followed by ADDR[+BYTES][=VALUE[/MASK]], as tools/watch_guest.py takes them.  Per spec one line
+// "watch SPEC: total=N", then the last hits (at most 4), oldest first: "  SHARD:ROW pc=0xX rd=0xX rs1=0xX rs2=0xX" and, for a
+// load or store, " load|store addr=0xX before=0xX after=0xX prev=SHARD:CLK", for a precompile call " call addr=0xX words=N".
 // get-schema / validate-schema / node are product UI outside the accelerated path and are not provided.
 #include <algorithm>
 #include <cstdio>
@@ -133,11 +138,87 @@ template <class Call> static int print_memory(Call call) {
     return 0;
 }
 
+// a --watch spec as a query over every position; false: not a spec
+static bool parse_watch(const std::string &spec, dvt_watch_query *q) {
+    static const char *abi[32] = {"zero", "ra", "sp", "gp", "tp", "t0", "t1", "t2", "s0", "s1", "a0", "a1", "a2", "a3", "a4", "a5",
+                                  "a6", "a7", "s2", "s3", "s4", "s5", "s6", "s7", "s8", "s9", "s10", "s11", "t3", "t4", "t5", "t6"};
+    *q = dvt_watch_query{};
+    q->to_shard = q->to_row = 0xffffffffu;
+    const size_t colon = spec.find(':');
+    if (colon == std::string::npos) return false;
+    const std::string kind = spec.substr(0, colon);
+    std::string rest = spec.substr(colon + 1);
+    auto number = [](const std::string &t, uint32_t *out) {
+        if (t.empty()) return false;
+        char *end = nullptr;
+        const unsigned long long v = strtoull(t.c_str(), &end, 0);
+        *out = (uint32_t)v;
+        return !*end && v <= 0xffffffffull;
+    };
+    const size_t eq = rest.find('=');
+    if (eq != std::string::npos) {
+        if (kind == "pc") return false;
+        std::string v = rest.substr(eq + 1), m = "0xffffffff";
+        rest = rest.substr(0, eq);
+        const size_t slash = v.find('/');
+        if (slash != std::string::npos) { m = v.substr(slash + 1); v = v.substr(0, slash); }
+        if (!number(v, &q->want) || !number(m, &q->mask)) return false;
+        q->flags |= DVT_WATCH_VALUE;
+    }
+    if (kind == "reg") {
+        q->kind = DVT_WATCH_REG;
+        for (uint32_t r = 1; r < 32; r++)
+            if (rest == abi[r] || rest == "x" + std::to_string(r)) q->lo = r;
+        q->hi = q->lo + 1;
+        return q->lo != 0;
+    }
+    uint32_t bytes = 4;
+    const size_t plus = rest.find('+');
+    if (plus != std::string::npos && !number(rest.substr(plus + 1), &bytes)) return false;
+    if (!number(rest.substr(0, plus), &q->lo)) return false;
+    q->hi = q->lo + bytes;
+    if (kind == "pc") { q->kind = DVT_WATCH_PC; return true; }
+    q->kind = DVT_WATCH_MEM;
+    q->lo &= ~3u;
+    q->hi = (q->hi + 3) & ~3u;
+    if (kind == "load") q->flags |= DVT_WATCH_LOAD;
+    else if (kind == "store") q->flags |= DVT_WATCH_STORE;
+    else if (kind == "pread") q->flags |= DVT_WATCH_PRE_READ;
+    else if (kind == "pwrite") q->flags |= DVT_WATCH_PRE_WRITE;
+    else if (kind == "mem") q->flags |= DVT_WATCH_LOAD | DVT_WATCH_STORE | DVT_WATCH_PRE_READ | DVT_WATCH_PRE_WRITE;
+    else return false;
+    return true;
+}
+
+// the totals and the last hits (call: dvt_execute_watch or dvt_rv32_job_watch with everything else bound)
+template <class Call> static int print_watch(const std::vector<std::string> &specs, const std::vector<dvt_watch_query> &queries, Call call) {
+    constexpr size_t KEEP = 4;
+    std::vector<dvt_watch_hit> hits(2 * KEEP * queries.size());
+    std::vector<uint64_t> totals(queries.size());
+    dvt_watch_summary s{};
+    if (int rc = call(queries.data(), queries.size(), KEEP, hits.data(), totals.data(), &s)) return rc;
+    for (size_t q = 0; q < queries.size(); q++) {
+        printf("watch %s: total=%llu\n", specs[q].c_str(), (unsigned long long)totals[q]);
+        for (size_t i = 0; i < std::min<uint64_t>(KEEP, totals[q]); i++) {
+            const dvt_watch_hit &h = hits[(2 * q + 1) * KEEP + i];
+            printf("  %u:%u pc=0x%08x rd=0x%08x rs1=0x%08x rs2=0x%08x", h.shard, h.row, h.pc, h.rd_value, h.rs1, h.rs2);
+            if (h.flags & (DVT_WATCH_LOAD | DVT_WATCH_STORE))
+                printf(" %s addr=0x%08x before=0x%08x after=0x%08x prev=%u:%u", h.flags & DVT_WATCH_LOAD ? "load" : "store", h.addr, h.before, h.after,
+                       h.prev_shard, h.prev_clk);
+            else if (h.flags & DVT_WATCH_HIT_NO_VALUE) printf(" call addr=0x%08x words=%u", h.addr, h.n_words);
+            printf("\n");
+        }
+    }
+    return 0;
+}
+
 int main(int argc, char **argv) {
-    if (argc < 2) return die("usage: dvt_prover_host prove|execute|verify|check|compact|expand --type T -i FILE [-o FILE] [--show-report] [--show-calls] [--show-memory] [--compact] [--keep-trees] [--elf FILE] [--devices D0,D1,...] [--device D]");
+    if (argc < 2) return die("usage: dvt_prover_host prove|execute|verify|check|compact|expand --type T -i FILE [-o FILE] [--show-report] [--show-calls] [--show-memory] [--watch SPEC] [--compact] [--keep-trees] [--elf FILE] [--devices D0,D1,...] [--device D]");
     const std::string verb = argv[1];
     std::string type, input, output, elf_path, schema_path, devices, verify_device;
     bool show_report = false, show_calls = false, show_memory = false, auth = false, compact = false, keep_trees = false;
+    std::vector<std::string> watch_specs;
+    std::vector<dvt_watch_query> watch_queries;
     for (int i = 2; i < argc; i++) {
         std::string a = argv[i], inline_val;
         bool has_inline = false;
@@ -155,6 +236,11 @@ int main(int argc, char **argv) {
         else if (a == "--show-report") show_report = true;
         else if (a == "--show-calls") show_calls = true;
         else if (a == "--show-memory") show_memory = true;
+        else if (a == "--watch") {
+            watch_specs.push_back(next());
+            watch_queries.emplace_back();
+            if (!parse_watch(watch_specs.back(), &watch_queries.back())) return die("no watch spec: " + watch_specs.back());
+        }
         else if (a == "--compact") compact = true;       // prove: shard proofs in the compact form ("compact_openings")
         else if (a == "--keep-trees") keep_trees = true;  // prove / check: shards that do not fit in HBM in full keep their main Merkle tree ("keep_phase1": 2)
         else if (a == "--auth-commitment") auth = true;  // the reference selects this at build time (cargo feature)
@@ -253,6 +339,13 @@ int main(int argc, char **argv) {
                 }))
                 return die(std::string("Verification failed: ") + (merr ? merr : "?"));
         }
+        if (!watch_queries.empty()) {
+            char *werr = nullptr;
+            if (print_watch(watch_specs, watch_queries, [&](const dvt_watch_query *q, size_t n, size_t keep, dvt_watch_hit *hits, uint64_t *totals, dvt_watch_summary *s) {
+                    return dvt_execute_watch(elf.data(), elf.size(), &buf, 1, 0, 0, q, n, keep, hits, totals, s, nullptr, &werr);
+                }))
+                return die(std::string("Verification failed: ") + (werr ? werr : "?"));
+        }
         return 0;
     }
 
@@ -310,6 +403,11 @@ int main(int argc, char **argv) {
                 return dvt_rv32_job_memory(p, pk, job, ft, cap_instr, pages, cap_pages, s);
             }))
             return die(std::string("Memory report failed: ") + dvt_last_error(p));
+        if (!watch_queries.empty() &&
+            print_watch(watch_specs, watch_queries, [&](const dvt_watch_query *q, size_t n, size_t keep, dvt_watch_hit *hits, uint64_t *totals, dvt_watch_summary *s) {
+                return dvt_rv32_job_watch(p, pk, job, q, n, keep, hits, totals, s);
+            }))
+            return die(std::string("Watch failed: ") + dvt_last_error(p));
         dvt_job_free(p, job);
         dvt_pk_free(p, pk);
         dvt_prover_destroy(p);

@@ -166,4 +166,18 @@ struct MemoryDensePage {
 };
 hipError_t launch_memory_gather(hipStream_t st, const MemoryTables &t, MemoryDensePage *d_dense, uint32_t cap, uint32_t *d_n_dense);
 
+// watch.hip
+// The watchpoint search (watch.h) over the cycle records of one shard: count, scan, emit.  WatchArgs (watch.h) carries the
+// queries, the precompile shapes, the static words per instruction and the shard's number; span_counts / span_offs are
+// [spans of the shard][n_queries] u32, d_totals [n_queries] u32; d_bad_records is zeroed by the caller.  The emit pass writes
+// the kept hits of the shard (WatchEmitArgs: per query the rank of the shard's first hit and the total over the job; cap_each)
+// into d_out (dvt_watch_hit [n_queries][2][cap_each]).  The records are only read.
+struct WatchArgs;
+struct WatchEmitArgs;
+hipError_t launch_watch_count(hipStream_t st, const rv32::CycleRec *d_recs, size_t n_recs, const WatchArgs &a, uint32_t *d_span_counts,
+                              unsigned long long *d_bad_records);
+hipError_t launch_watch_scan(hipStream_t st, const uint32_t *d_span_counts, uint32_t *d_span_offs, uint32_t n_spans, uint32_t n_queries, uint32_t *d_totals);
+hipError_t launch_watch_emit(hipStream_t st, const rv32::CycleRec *d_recs, size_t n_recs, const WatchArgs &a, const WatchEmitArgs &e,
+                             const uint32_t *d_span_counts, const uint32_t *d_span_offs, void *d_out);
+
 }  // namespace dvt

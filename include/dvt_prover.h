@@ -128,7 +128,8 @@ void dvt_free(void *ptr);
  * dvt_stage_multipath_nodes, dvt_stage_verify_multipath, dvt_debug_compact_list_sweep; 12: dvt_rv32_job_profile,
  * dvt_execute_profile; 13: "keep_phase1": 2, "keep_full_max", DVT_KEEP_*, dvt_rv32_job_shard_kept,
  * dvt_rv32_job_shard_kept_bytes, dvt_debug_keep_plan; 14: dvt_rv32_job_calltree,
- * dvt_rv32_job_calltree_times, dvt_execute_calltree; 15: dvt_rv32_job_memory, dvt_execute_memory) */
+ * dvt_rv32_job_calltree_times, dvt_execute_calltree; 15: dvt_rv32_job_memory, dvt_execute_memory;
+ * 16: dvt_rv32_job_watch, dvt_execute_watch, dvt_rv32_job_watch_times) */
 uint32_t dvt_abi_version(void);
 /* the handle's hipStream_t (for event timing by the caller) */
 void *dvt_stream(dvt_prover *p);
@@ -815,6 +816,67 @@ int dvt_rv32_job_memory(dvt_prover *p, const dvt_pk *pk, dvt_job *job, uint64_t 
 int dvt_execute_memory(const uint8_t *elf, size_t elf_len, const dvt_buf *stdin_bufs, size_t nbuf, uint64_t max_cycles,
                        uint64_t *first_touch, size_t cap_instr, dvt_memory_page *pages, size_t cap_pages, dvt_memory_summary *summary,
                        dvt_report *report, char **err_text);
+/* Watchpoints on a prepared job: the cycle records of the shards the job holds are searched, every record against up to
+ * DVT_WATCH_MAX_QUERIES queries (one launch per shard on the device that holds it; the records are only read and the job is
+ * left as found).  A record is a hit of a query at most once.  The rule is stated in csrc/watch.h:
+ *   DVT_WATCH_PC    the record's pc (text_base + 4 idx) lies in [lo, hi)
+ *   DVT_WATCH_REG   the instruction has rd == lo (1..31; x0 never hits); the value is the one written.  With DVT_WATCH_VALUE
+ *                   in flags the hit also requires (value & mask) == (want & mask).
+ *   DVT_WATCH_MEM   a memory access in the sense of the memory report whose word address lies in [lo, hi); flags selects
+ *                   among DVT_WATCH_LOAD, _STORE, _PRE_READ and _PRE_WRITE (at least one).  A load or store accesses the word
+ *                   (rs1 value + offset) & ~3: `before` is the word before the access, `after` the word after it (a load
+ *                   leaves it; sw writes rs2, sh / sb merge the half or byte of rs2 at the byte offset of the address).
+ *                   DVT_WATCH_VALUE tests `after`, of loads and stores only.  A precompile ECALL (the shapes of the memory
+ *                   report) hits when any word of its arrays lies in the range with a selected direction: one hit per call,
+ *                   addr = the lowest such word, n_words = how many entries of the call's arrays matched (a word that both
+ *                   arrays hold counts twice), flags = the selected directions that matched | DVT_WATCH_HIT_NO_VALUE; the
+ *                   values of those words are not in the records: before = after = 0 and a VALUE filter never matches.
+ *   window          only records at positions from <= (shard, row) < to, compared lexicographically, are searched: shard is
+ *                   the shard's number in the execution (from 1, also on a prepare_part job), row the index of the record in
+ *                   its shard (the row of the shard's cpu table; the memory timestamps of the row are 4 row + 4 .. 4 row + 7).
+ *                   from = (0, 0) and to = (0xffffffff, 0xffffffff) search everything.
+ * A hit carries the position, pc and idx, the values written and read (rd_value = a, rs1 = b, rs2 = c of the record), the
+ * query's kind, and for a load or store under whichever kind of query: its direction in flags, addr, n_words = 1, before, after
+ * and the previous access of the word as (prev_shard, prev_clk), (0, 0) when the access is the first of the word.  Searching
+ * again with to = the position of that access walks the history of a word backwards.
+ * Per query q the call returns totals[q], the exact number of hits in the window, the first min(cap_each, total) hits in
+ * execution order in hits[2 q cap_each ...] and the last min(cap_each, total) in hits[(2 q + 1) cap_each ...] (the lists overlap
+ * when total < 2 cap_each); the rest of `hits` is left as found.  cap_each may be 0 (totals only; hits may then be NULL).
+ * Nothing is sampled: totals and order are exact whatever cap_each is.
+ * DVT_ERR_INPUT: n_queries 0 or above DVT_WATCH_MAX_QUERIES, cap_each above DVT_WATCH_MAX_KEEP, an unknown kind, a flag the
+ * kind does not take (or a MEM query without a direction), lo >= hi, a register outside 1..31, from >= to, null arrays, a
+ * cycle record that names an instruction outside the text or an address outside guest memory.  Handles with several members
+ * and prepare_part jobs work: positions stay those of the execution. */
+#define DVT_WATCH_MAX_QUERIES 16
+#define DVT_WATCH_MAX_KEEP 256
+#define DVT_WATCH_SPAN 4096   /* records one workgroup of the device pass searches */
+enum { DVT_WATCH_PC = 1, DVT_WATCH_REG = 2, DVT_WATCH_MEM = 3 };
+enum { DVT_WATCH_LOAD = 1, DVT_WATCH_STORE = 2, DVT_WATCH_PRE_READ = 4, DVT_WATCH_PRE_WRITE = 8, DVT_WATCH_VALUE = 16, DVT_WATCH_HIT_NO_VALUE = 32 };
+typedef struct {
+    uint32_t kind, flags, lo, hi, mask, want;
+    uint32_t from_shard, from_row, to_shard, to_row;
+} dvt_watch_query;
+typedef struct {
+    uint32_t query, shard, row, pc, idx, kind, flags, addr, n_words, before, after, rd_value, rs1, rs2, prev_shard, prev_clk;
+} dvt_watch_hit;
+typedef struct {
+    uint64_t cycles;   /* records of the held shards (all of them are tested, the window is part of the test) */
+    uint32_t n_queries, cap_each, shards_searched, shards_total, text_base, n_instr, span;
+    float ms;          /* wall clock of the call after the entry guard */
+} dvt_watch_summary;
+int dvt_rv32_job_watch(dvt_prover *p, const dvt_pk *pk, dvt_job *job, const dvt_watch_query *queries, size_t n_queries, size_t cap_each,
+                       dvt_watch_hit *hits, uint64_t *totals, dvt_watch_summary *summary);
+/* milliseconds of the last dvt_rv32_job_watch, by events on the members' streams and summed over the members: the count
+ * launches, the scan launches, the emit launches; out[3]: the shards the emit pass ran over */
+int dvt_rv32_job_watch_times(dvt_prover *p, double out[4]);
+/* The same search on the host alone (no GPU is touched), as dvt_execute_profile runs the guest, in shards of
+ * 2^log_shard_size cycles (0: 21; 4..22) so that positions are those of a job prepared with that shard size; one shard's
+ * records are held at a time and the last cap_each hits of a query are kept in a ring.  Return codes, *report and *err_text as
+ * dvt_execute gives them (an input error of the queries: DVT_ERR_INPUT and its text); the lists are filled for whatever
+ * retired, also when the guest fails. */
+int dvt_execute_watch(const uint8_t *elf, size_t elf_len, const dvt_buf *stdin_bufs, size_t nbuf, uint64_t max_cycles, uint32_t log_shard_size,
+                      const dvt_watch_query *queries, size_t n_queries, size_t cap_each, dvt_watch_hit *hits, uint64_t *totals,
+                      dvt_watch_summary *summary, dvt_report *report, char **err_text);
 /* test hook: run K0 on one shard of a prepared job and return the device-generated main traces
  * (canonical); blob layout as dvt_rv32_debug_traces with prep_width = 0. */
 int dvt_rv32_debug_device_traces(dvt_prover *p, const dvt_pk *pk, dvt_job *job, size_t shard, uint32_t **blob,
