@@ -190,6 +190,10 @@ def load():
     lib.dvt_rv32_job_watch.argtypes = [vp, vp, vp] + watch_io
     lib.dvt_rv32_job_watch_times.argtypes = [vp, C.POINTER(C.c_double)]
     lib.dvt_execute_watch.argtypes = [C.c_char_p, sz, C.POINTER(Buf), sz, u64, u32] + watch_io + [C.POINTER(Report), C.POINTER(C.c_char_p)]
+    snap_io = [u32, u32, C.POINTER(SnapRange), sz, C.POINTER(SnapCell), C.POINTER(SnapCell), sz, C.POINTER(SnapFrame), sz, C.POINTER(SnapSummary)]
+    lib.dvt_rv32_job_snapshot.argtypes = [vp, vp, vp] + snap_io
+    lib.dvt_rv32_job_snapshot_times.argtypes = [vp, C.POINTER(C.c_double)]
+    lib.dvt_execute_snapshot.argtypes = [C.c_char_p, sz, C.POINTER(Buf), sz, u64, u32] + snap_io + [C.POINTER(Report), C.POINTER(C.c_char_p)]
     lib.dvt_stdin_from_json.argtypes = [C.c_char_p, C.c_char_p, sz, C.c_int, C.POINTER(u8p), C.POINTER(sz), C.POINTER(C.c_char_p)]
     _lib = lib
     return lib
@@ -598,6 +602,70 @@ def execute_watch(elf: bytes, stdin=(), queries=(), keep=16, max_cycles=0, log_s
     rc, found, _ = _watch(lambda *io: lib.dvt_execute_watch(elf, len(elf), bufs, len(stdin), max_cycles, log_shard, *io, C.byref(rep), C.byref(err)),
                           list(queries), keep)
     return rc, dict(cycles=rep.cycles, exit_code=rep.exit_code, halted=bool(rep.halted), unprovable=bool(rep.unprovable)), found, _take_str(lib, err)
+
+
+# ---- snapshots (csrc/snapshot.h)
+DVT_SNAP_MAX_RANGES, DVT_SNAP_MAX_WORDS, DVT_SNAP_SPAN = 16, 4096, 4096
+(DVT_SNAP_INITIAL, DVT_SNAP_FROM_BEFORE, DVT_SNAP_FROM_AFTER, DVT_SNAP_LOAD, DVT_SNAP_STORE, DVT_SNAP_IMAGE, DVT_SNAP_NO_VALUE,
+ DVT_SNAP_UNTOUCHED) = 1, 2, 4, 8, 16, 32, 64, 128
+SNAP_EXIT = (0xFFFFFFFF, 0xFFFFFFFF)   # the position after the last record
+REG_NAMES = ("zero", "ra", "sp", "gp", "tp", "t0", "t1", "t2", "s0", "s1", "a0", "a1", "a2", "a3", "a4", "a5", "a6", "a7", "s2", "s3", "s4", "s5",
+             "s6", "s7", "s8", "s9", "s10", "s11", "t3", "t4", "t5", "t6")
+
+
+class SnapRange(C.Structure):
+    _fields_ = [("lo", C.c_uint32), ("hi", C.c_uint32)]
+
+
+class SnapCell(C.Structure):
+    _fields_ = [(name, C.c_uint32) for name in ("addr", "value", "flags", "shard", "row", "pc")]
+
+
+class SnapFrame(C.Structure):
+    _fields_ = [(name, C.c_uint32) for name in ("fn_pc", "call_pc", "open_shard", "open_row", "ra", "pad")]
+
+
+class SnapSummary(C.Structure):
+    _fields_ = [("position", C.c_uint64), ("cycles", C.c_uint64)] + \
+               [(name, C.c_uint32) for name in ("shard", "row", "pc", "depth", "n_frames", "unmatched_returns", "n_words", "no_value", "initial",
+                                                "untouched", "shards_total", "text_base", "n_instr", "span")] + [("ms", C.c_float)]
+
+
+def snap_range(addr, n_bytes=4):
+    """the words that hold the bytes [addr, addr + n_bytes), as a (lo, hi) pair of word addresses"""
+    return addr & ~3, (addr + max(n_bytes, 1) + 3) & ~3
+
+
+_CELL_KEYS = [name for name, _ in SnapCell._fields_]
+_FRAME_KEYS = [name for name, _ in SnapFrame._fields_ if name != "pad"]
+
+
+def _snapshot(call, at, ranges, frames):
+    """The snapshot through call(shard, row, ranges, n, regs, words, cap_words, frames, cap_frames, summary) -> rc.  Returns (rc,
+    dict(summary, regs = 32 cell dicts, words = cell dicts in range order, frames = frame dicts innermost first) or None when
+    the call fails without an answer)."""
+    ranges = [tuple(r) for r in ranges]
+    n_words = sum(max(0, (hi - lo) // 4) for lo, hi in ranges)
+    rs = (SnapRange * max(len(ranges), 1))(*[SnapRange(lo, hi) for lo, hi in ranges])
+    regs, words, fr, s = (SnapCell * 32)(), (SnapCell * max(n_words, 1))(), (SnapFrame * max(frames, 1))(), SnapSummary()
+    rc = call(at[0], at[1], rs, len(ranges), regs, words, n_words, fr, frames, C.byref(s))
+    if rc not in (DVT_OK, DVT_ERR_GUEST):
+        return rc, None
+    cell = lambda c: {name: int(getattr(c, name)) for name in _CELL_KEYS}
+    summary = {name: (float if name == "ms" else int)(getattr(s, name)) for name, _ in SnapSummary._fields_}
+    return rc, dict(summary=summary, regs=[cell(regs[k]) for k in range(32)], words=[cell(words[i]) for i in range(summary["n_words"])],
+                    frames=[{name: int(getattr(fr[i], name)) for name in _FRAME_KEYS} for i in range(summary["n_frames"])])
+
+
+def execute_snapshot(elf: bytes, stdin=(), at=SNAP_EXIT, ranges=(), frames=64, max_cycles=0, log_shard=21):
+    """Host-only snapshot (dvt_execute_snapshot): the guest runs in shards of 2^log_shard cycles; the state before the record at
+    `at` = (shard, row), SNAP_EXIT: after the last record (of a guest that traps: at the trap).  Returns (rc, report dict as
+    execute() gives it, dict(summary, regs, words, frames) as Prover.job_snapshot gives it or None, error text)."""
+    lib = load()
+    rep, err, bufs = Report(), C.c_char_p(), _bufs(stdin)
+    rc, snap = _snapshot(lambda *io: lib.dvt_execute_snapshot(elf, len(elf), bufs, len(stdin), max_cycles, log_shard, *io, C.byref(rep), C.byref(err)),
+                         at, ranges, frames)
+    return rc, dict(cycles=rep.cycles, exit_code=rep.exit_code, halted=bool(rep.halted), unprovable=bool(rep.unprovable)), snap, _take_str(lib, err)
 
 
 def exec_rate(elf: bytes, stdin=(), log_shard=21, trace=False) -> float:
@@ -1285,6 +1353,22 @@ class Prover:
         out = (C.c_double * 4)()
         self.check(self.lib.dvt_rv32_job_watch_times(self.h, out))
         return dict(count_ms=out[0], scan_ms=out[1], emit_ms=out[2], emit_shards=int(out[3]))
+
+    def job_snapshot(self, pk, job, at, ranges=(), frames=64):
+        """The machine as it is before the record at `at` = (shard, row) of a prepared job executes (SNAP_EXIT: after the last
+        record), from the cycle records the job holds on the GPU (dvt_rv32_job_snapshot): dict(summary, regs = 32 cells, words =
+        the cells of `ranges` ((lo, hi) word addresses, snap_range() makes them; at most 16 ranges and 4096 words), frames =
+        the innermost `frames` frames of the call stack).  A cell is a dict of the fields of dvt_snap_cell; its flags say
+        where the value comes from, DVT_SNAP_NO_VALUE that the records do not hold it."""
+        rc, snap = _snapshot(lambda *io: self.lib.dvt_rv32_job_snapshot(self.h, pk, job, *io), at, ranges, frames)
+        self.check(rc)
+        return snap
+
+    def job_snapshot_times(self):
+        """of the last job_snapshot: dict(reduce_ms, gather_ms, backtrace_ms), stream events summed over members"""
+        out = (C.c_double * 3)()
+        self.check(self.lib.dvt_rv32_job_snapshot_times(self.h, out))
+        return dict(reduce_ms=out[0], gather_ms=out[1], backtrace_ms=out[2])
 
     def job_calltree_times(self):
         """milliseconds of the last job_calltree: dict(summary_ms, merge_ms, emit_ms)"""

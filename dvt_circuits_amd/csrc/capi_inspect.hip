@@ -2,8 +2,10 @@
 // stage entry points (dvt_stage_*) on a table the caller uploaded (stage_table) and job entry points (dvt_rv32_*) on the
 // tables of a prepared job's held shards (shard_view).  The execution report (profile.h), the call-tree report (calltree.h)
 // and the memory report (memreport.h) are the inspectors that read a job's cycle records instead of its tables; the watchpoint
-// search (watch.h) reads the same records and returns the ones that match.
+// search (watch.h) reads the same records and returns the ones that match; the snapshot (snapshot.h) reduces them to the state
+// of the machine at one position.
 #include <algorithm>
+#include <type_traits>
 
 #include "calltree.h"
 #include "capi_job.h"
@@ -11,6 +13,7 @@
 #include "memreport.h"
 #include "profile.h"
 #include "sha256.h"
+#include "snapshot.h"
 #include "watch.h"
 
 using namespace dvt;
@@ -337,6 +340,8 @@ namespace {
 struct CalltreeMember {
     StageBuf base, calls, frames;
     std::vector<size_t> span0;                        // of the member's k-th shard
+    std::vector<size_t> n_of;                         // the records of the k-th shard the pass takes (a prefix of the shard)
+    std::vector<uint32_t> succ_of;                    // the successor of the last of them
     size_t spans = 0, total_calls = 0;
     std::vector<CalltreeSpanSummary> summaries;
     std::vector<unsigned long long> calls_at;
@@ -346,7 +351,13 @@ struct CalltreeMember {
     CalltreeTables tb{};
     unsigned long long *d_calls_at = nullptr;
     CalltreeSpanIn *d_span_in = nullptr;
+    hipEvent_t ev[4] = {};                            // a timed run: the summaries [0, 1], the unmatched calls [2, 3]
+    bool timed_calls = false;
     explicit CalltreeMember(DevPool &pool) : base{pool}, calls{pool}, frames{pool} {}
+    ~CalltreeMember() {
+        for (hipEvent_t x : ev)
+            if (x) (void)hipEventDestroy(x);
+    }
 };
 // the members' buffers go back to their pools under their own device's turn
 struct CalltreeRun {
@@ -362,23 +373,15 @@ struct CalltreeRun {
 };
 }  // namespace
 
-static int job_calltree(dvt_prover *p, const dvt_pk *pk, dvt_job *j, uint32_t log_arc_slots, const calltree::Out &out) {
-    if (int rc = same_members(p, pk, j)) return rc;
-    if (j->first != 0 || j->stride != 1 || j->held() != j->n_total)
-        return fail(p, DVT_ERR_UNSUPPORTED, "the job holds %zu of the %zu shards of its execution (first %zu, stride %zu): the call stack across a gap is unknown",
-                    j->held(), j->n_total, j->first, j->stride);
-    const auto t0 = Clock::now();
-    calltree::State st(pk->prog);
-    const size_t n = st.classes.size(), G = n_members(p);
-    uint32_t log_slots = log_arc_slots;
-    if (!log_slots)
-        for (log_slots = prof::DEFAULT_MIN_LOG_SLOTS; log_slots < prof::MAX_LOG_SLOTS && ((size_t)1 << log_slots) < 4 * n;) log_slots++;
-    const size_t S = (size_t)1 << log_slots;
-    const uint32_t entry = prof::index_of_pc(pk->prog, pk->prog.entry);
-    if (entry == prof::NO_SUCC) return fail(p, DVT_ERR_INPUT, "the entry 0x%08x is no instruction of the text", pk->prog.entry);
-    auto succ_of = [&](const ShardJob &s) { return prof::index_of_pc(pk->prog, s.next_pc); };
-    CalltreeRun run{p, {}};
-
+// Summary mode over a prefix of every held shard, for the call tree (all records) and the snapshot's backtrace (the records
+// before its position): prefix(shard, &n, &succ) names the first n records the pass takes and the successor of the last of
+// them.  {u, c} of every span; then summary mode again, writing the unmatched calls of the shards that have any at the offsets
+// the host made of the c's.  S = 2^log_slots arc slots are laid out for emit mode (log_slots 0: none).  timed: stream events
+// around both runs.
+template <class Prefix>
+static int calltree_summaries(dvt_prover *p, dvt_job *j, const std::vector<uint32_t> &classes, uint32_t log_slots, bool timed, Prefix prefix, CalltreeRun *run_out) {
+    CalltreeRun &run = *run_out;
+    const size_t n = classes.size(), G = n_members(p), S = log_slots ? (size_t)1 << log_slots : 0;
     // ---- summary mode: {u, c} of every span
     for (size_t m = 0; m < G; m++) {
         if (int rc = turn_to(p, m)) return rc;
@@ -387,10 +390,17 @@ static int job_calltree(dvt_prover *p, const dvt_pk *pk, dvt_job *j, uint32_t lo
         run.mem.emplace_back(new CalltreeMember(e.pool));
         CalltreeMember &cm = *run.mem.back();
         for (auto &s : j->parts[m].shards) {
+            size_t take = 0;
+            uint32_t succ = prof::NO_SUCC;
+            prefix(s, &take, &succ);
+            cm.n_of.push_back(std::min(take, s.n_recs));
+            cm.succ_of.push_back(succ);
             cm.span0.push_back(cm.spans);
-            cm.spans += (s.n_recs + CALLTREE_SPAN - 1) / CALLTREE_SPAN;
+            cm.spans += (cm.n_of.back() + CALLTREE_SPAN - 1) / CALLTREE_SPAN;
         }
         if (!cm.spans) continue;
+        if (timed)
+            for (auto &x : cm.ev) HIP_TRY(c.err, hipEventCreate(&x));
         // 64-bit words: counters, arc calls, arc cycles | arc keys | calls_at | span_in (two each) | summaries; then the classes
         const size_t zero_words = CALLTREE_COUNTERS + 2 * S, words = zero_words + S + 4 * cm.spans;
         HIP_TRY(c.err, e.pool.alloc_bytes(&cm.base.ptr, words * 8 + n * 4));
@@ -403,12 +413,12 @@ static int job_calltree(dvt_prover *p, const dvt_pk *pk, dvt_job *j, uint32_t lo
         uint32_t *d_classes = reinterpret_cast<uint32_t *>(d + words);
         tb.classes = d_classes; tb.n_instr = (uint32_t)n; tb.log_slots = log_slots;
         HIP_TRY(c.err, hipMemsetAsync(d, 0, zero_words * 8, e.stream));
-        HIP_TRY(c.err, hipMemsetAsync(tb.arc_keys, 0xff, S * 8, e.stream));
-        HIP_TRY(c.err, hipMemcpyAsync(d_classes, st.classes.data(), n * 4, hipMemcpyHostToDevice, e.stream));
-        for (size_t k = 0; k < cm.span0.size(); k++) {
-            const ShardJob &s = j->parts[m].shards[k];
-            HIP_TRY(c.err, launch_calltree_summary(e.stream, s.d_recs, s.n_recs, succ_of(s), cm.span0[k], tb));
-        }
+        if (S) HIP_TRY(c.err, hipMemsetAsync(tb.arc_keys, 0xff, S * 8, e.stream));
+        HIP_TRY(c.err, hipMemcpyAsync(d_classes, classes.data(), n * 4, hipMemcpyHostToDevice, e.stream));
+        if (timed) HIP_TRY(c.err, hipEventRecord(cm.ev[0], e.stream));
+        for (size_t k = 0; k < cm.span0.size(); k++)
+            HIP_TRY(c.err, launch_calltree_summary(e.stream, j->parts[m].shards[k].d_recs, cm.n_of[k], cm.succ_of[k], cm.span0[k], tb));
+        if (timed) HIP_TRY(c.err, hipEventRecord(cm.ev[1], e.stream));
         cm.summaries.resize(cm.spans);
         if (!e.download(cm.summaries.data(), tb.summaries, cm.spans * sizeof(CalltreeSpanSummary))) return engine_fail(c.err, e);
         cm.calls_at.resize(cm.spans);
@@ -430,16 +440,51 @@ static int job_calltree(dvt_prover *p, const dvt_pk *pk, dvt_job *j, uint32_t lo
         tb.calls_at = cm.d_calls_at;
         tb.calls = static_cast<CalltreeCall *>(cm.calls.ptr);
         HIP_TRY(c.err, hipMemcpyAsync(cm.d_calls_at, cm.calls_at.data(), cm.spans * 8, hipMemcpyHostToDevice, e.stream));
+        if (timed) HIP_TRY(c.err, hipEventRecord(cm.ev[2], e.stream));
         for (size_t k = 0; k < cm.span0.size(); k++) {
-            const ShardJob &s = j->parts[m].shards[k];
             const size_t end = k + 1 < cm.span0.size() ? cm.span0[k + 1] : cm.spans;
             size_t n_calls = 0;
             for (size_t i = cm.span0[k]; i < end; i++) n_calls += cm.summaries[i].c;
-            if (n_calls) HIP_TRY(c.err, launch_calltree_summary(e.stream, s.d_recs, s.n_recs, succ_of(s), cm.span0[k], tb));
+            if (n_calls) HIP_TRY(c.err, launch_calltree_summary(e.stream, j->parts[m].shards[k].d_recs, cm.n_of[k], cm.succ_of[k], cm.span0[k], tb));
+        }
+        if (timed) {
+            HIP_TRY(c.err, hipEventRecord(cm.ev[3], e.stream));
+            cm.timed_calls = true;
         }
         cm.h_calls.resize(cm.total_calls);
         if (!e.download(cm.h_calls.data(), tb.calls, cm.total_calls * sizeof(CalltreeCall))) return engine_fail(c.err, e);
     }
+    return DVT_OK;
+}
+
+// The merge of one span into the global stack (depth >= 1), the spans taken in execution order: the span's u unmatched RETs
+// pop, the root stays; its c unmatched CALLs push, each frame opening after its call.  Returns the RETs that found only the
+// root.  The frames open after the last span are the stack at that point: the snapshot's backtrace.
+static uint32_t calltree_merge_span(std::vector<calltree::Frame> &stack, const CalltreeSpanSummary &sum, const CalltreeCall *calls, uint64_t span_pos) {
+    const size_t depth = stack.size(), pops = std::min<size_t>(sum.u, depth - 1);
+    stack.resize(depth - pops);
+    for (uint32_t q = 0; q < sum.c; q++) stack.push_back(calltree::Frame{calls[q].fn, span_pos + calls[q].pos + 1});
+    return (uint32_t)(sum.u - pops);
+}
+
+static int job_calltree(dvt_prover *p, const dvt_pk *pk, dvt_job *j, uint32_t log_arc_slots, const calltree::Out &out) {
+    if (int rc = same_members(p, pk, j)) return rc;
+    if (j->first != 0 || j->stride != 1 || j->held() != j->n_total)
+        return fail(p, DVT_ERR_UNSUPPORTED, "the job holds %zu of the %zu shards of its execution (first %zu, stride %zu): the call stack across a gap is unknown",
+                    j->held(), j->n_total, j->first, j->stride);
+    const auto t0 = Clock::now();
+    calltree::State st(pk->prog);
+    const size_t n = st.classes.size(), G = n_members(p);
+    uint32_t log_slots = log_arc_slots;
+    if (!log_slots)
+        for (log_slots = prof::DEFAULT_MIN_LOG_SLOTS; log_slots < prof::MAX_LOG_SLOTS && ((size_t)1 << log_slots) < 4 * n;) log_slots++;
+    const size_t S = (size_t)1 << log_slots;
+    const uint32_t entry = prof::index_of_pc(pk->prog, pk->prog.entry);
+    if (entry == prof::NO_SUCC) return fail(p, DVT_ERR_INPUT, "the entry 0x%08x is no instruction of the text", pk->prog.entry);
+    auto succ_of = [&](const ShardJob &s) { return prof::index_of_pc(pk->prog, s.next_pc); };
+    CalltreeRun run{p, {}};
+    if (int rc = calltree_summaries(p, j, st.classes, log_slots, false, [&](const ShardJob &s, size_t *take, uint32_t *succ) { *take = s.n_recs; *succ = succ_of(s); }, &run))
+        return rc;
     const double ms_summary = ms_since(t0);
 
     // ---- the merge: the spans in execution order, over all shards in job order, whichever member holds them
@@ -459,15 +504,10 @@ static int job_calltree(dvt_prover *p, const dvt_pk *pk, dvt_job *j, uint32_t lo
         for (size_t i = 0; i < n_spans; i++) {
             const size_t span = cm.span0[k] + i;
             const CalltreeSpanSummary sum = cm.summaries[span];
-            const size_t depth = st.stack.size(), n_in = std::min<size_t>((size_t)sum.u + 1, depth), pops = std::min<size_t>(sum.u, depth - 1);
+            const size_t depth = st.stack.size(), n_in = std::min<size_t>((size_t)sum.u + 1, depth);
             cm.span_in[span] = CalltreeSpanIn{cm.h_frames.size(), (uint32_t)n_in, (uint32_t)std::min<size_t>(depth, 0xffffffffu)};
             for (size_t f = 0; f < n_in; f++) cm.h_frames.push_back(CalltreeFrame{st.stack[depth - 1 - f].open, st.stack[depth - 1 - f].fn, 0});
-            st.stack.resize(depth - pops);
-            const uint64_t span_pos = cycles + i * CALLTREE_SPAN;
-            for (uint32_t q = 0; q < sum.c; q++) {
-                const CalltreeCall &call = cm.h_calls[cm.calls_at[span] + q];
-                st.stack.push_back(calltree::Frame{call.fn, span_pos + call.pos + 1});
-            }
+            (void)calltree_merge_span(st.stack, sum, cm.h_calls.data() + cm.calls_at[span], cycles + i * CALLTREE_SPAN);
         }
         cycles += s->n_recs;
     }
@@ -785,6 +825,235 @@ static int job_watch(dvt_prover *p, const dvt_pk *pk, dvt_job *j, const dvt_watc
     return DVT_OK;
 }
 
+// ------------------------------------------------------------------ snapshots (dvt_rv32_job_snapshot)
+// Reduce per member on lane 0's stream with buffers from lane 0's pool (one launch per shard it holds) into the member's winner
+// tables; the backtrace from the call-tree pass in summary mode over the records before the position and the merge of the call
+// tree; the host merges the members' winners with max / min and asks the member that holds each winner's shard for the record
+// at that position (gather), the call records of the returned frames among them; snap::emit() makes the cells.
+namespace {
+struct SnapMember {
+    StageBuf base, items, sides;
+    unsigned long long *d_tables = nullptr;
+    const uint32_t *d_statics = nullptr;
+    std::vector<SnapFetch> fetch;
+    std::vector<snap::Side> got;
+    hipEvent_t ev[4] = {};                // reduce [0, 1], gather [2, 3]
+    bool gathered = false;
+    explicit SnapMember(DevPool &pool) : base{pool}, items{pool}, sides{pool} {}
+    ~SnapMember() {
+        for (hipEvent_t x : ev)
+            if (x) (void)hipEventDestroy(x);
+    }
+};
+// the members' buffers go back to their pools under their own device's turn
+struct SnapRun {
+    dvt_prover *p;
+    std::vector<std::unique_ptr<SnapMember>> mem;
+    ~SnapRun() {
+        for (size_t m = 0; m < mem.size(); m++) {
+            (void)turn_to(p, m);
+            mem[m].reset();
+        }
+        (void)turn_to(p, 0);
+    }
+};
+}  // namespace
+
+static int job_snapshot(dvt_prover *p, const dvt_pk *pk, dvt_job *j, uint32_t shard, uint32_t row, const snap::Ranges &rg, dvt_snap_cell regs[32],
+                        dvt_snap_cell *words, dvt_snap_frame *frames, size_t cap_frames, dvt_snap_summary *summary) {
+    if (int rc = same_members(p, pk, j)) return rc;
+    if (j->first != 0 || j->stride != 1 || j->held() != j->n_total)
+        return fail(p, DVT_ERR_UNSUPPORTED, "the job holds %zu of the %zu shards of its execution (first %zu, stride %zu): the state across a gap is unknown",
+                    j->held(), j->n_total, j->first, j->stride);
+    const auto t0 = Clock::now();
+    const rv32::Program &prog = pk->prog;
+    const size_t n = prog.instrs.size() - 1, G = n_members(p), W = rg.n_words;
+    const unsigned long long P = watch::position(shard, row);
+    SnapRun run{p, {}};   // (declared first: however the call ends, member 0's device is current again)
+    // ---- the shards in execution order: their sizes, the records before P, the record at P
+    std::vector<uint64_t> shard_n(j->n_total);
+    uint64_t cycles = 0, position = 0;
+    size_t any_m = 0;
+    for (size_t pos = 0; pos < j->n_total; pos++) {
+        const ShardJob *s = j->at(pos, &any_m);
+        if (!s) return fail(p, DVT_ERR_UNSUPPORTED, "the job does not hold shard %zu", pos);
+        if (s->n_recs > 0xffffffffull) return fail(p, DVT_ERR_INPUT, "shard %zu has %zu records", pos, s->n_recs);
+        shard_n[pos] = s->n_recs;
+        cycles += s->n_recs;
+        position += s->index < shard ? s->n_recs : s->index == shard ? std::min<uint64_t>(s->n_recs, row) : 0;
+    }
+    uint32_t at_shard = 1, at_row = 0, idx_at = prof::NO_SUCC, pc = j->n_total ? 0 : prog.entry;
+    snap::locate(shard_n, position, &at_shard, &at_row);
+    if (position < cycles) {   // the record at P: its idx is the successor of the last record before P, and names the pc
+        size_t m = 0;
+        const ShardJob *s = j->at(at_shard - 1, &m);
+        if (!s || at_row >= s->n_recs) return fail(p, DVT_ERR_DEVICE, "position %llu lies in no shard", (unsigned long long)position);
+        if (int rc = turn_to(p, m)) return rc;
+        if (!member(p, m).eng.download(&idx_at, &s->d_recs[at_row].idx, 4)) return engine_fail(p->err, member(p, m).eng);
+        if (idx_at >= n) return fail(p, DVT_ERR_INPUT, "the cycle record at shard %u, row %u names an instruction outside the text", at_shard, at_row);
+        pc = prog.text_base + 4 * idx_at;
+    } else if (j->n_total)
+        pc = j->at(j->n_total - 1, &any_m)->next_pc;
+
+    std::vector<uint32_t> statics(2 * n);   // the static words, then the offsets
+    for (size_t i = 0; i < n; i++) {
+        statics[i] = watch::instr_static(prog.instrs[i]);
+        statics[n + i] = prog.instrs[i].off;
+    }
+    SnapArgs args{};
+    args.rg = rg;
+    args.sh = watch::shapes();
+    args.n_instr = (uint32_t)n; args.text_base = prog.text_base; args.P = P;
+    const size_t table_words = 1 + 32 + 2 * W;   // 64-bit: bad records, regs, before | after; then the static words
+
+    // ---- reduce
+    for (size_t m = 0; m < G; m++) {
+        if (int rc = turn_to(p, m)) return rc;
+        const Lane c = lane0(p, m);
+        Engine &e = c.eng;
+        run.mem.emplace_back(new SnapMember(e.pool));
+        SnapMember &sm = *run.mem.back();
+        JobPart &part = j->parts[m];
+        if (part.shards.empty()) continue;
+        for (auto &x : sm.ev) HIP_TRY(c.err, hipEventCreate(&x));
+        HIP_TRY(c.err, e.pool.alloc_bytes(&sm.base.ptr, table_words * 8 + statics.size() * 4));
+        sm.d_tables = static_cast<unsigned long long *>(sm.base.ptr);
+        uint32_t *d_stat = reinterpret_cast<uint32_t *>(sm.d_tables + table_words);
+        sm.d_statics = d_stat;
+        const SnapTables tb{sm.d_tables + 33, sm.d_tables + 33 + W, sm.d_tables + 1, sm.d_tables};
+        HIP_TRY(c.err, hipMemsetAsync(sm.d_tables, 0, (33 + W) * 8, e.stream));
+        if (W) HIP_TRY(c.err, hipMemsetAsync(tb.after, 0xff, W * 8, e.stream));
+        HIP_TRY(c.err, hipMemcpyAsync(d_stat, statics.data(), statics.size() * 4, hipMemcpyHostToDevice, e.stream));
+        args.statics = d_stat; args.offs = d_stat + n;
+        HIP_TRY(c.err, hipEventRecord(sm.ev[0], e.stream));
+        for (auto &s : part.shards) {
+            args.shard = s.index;
+            HIP_TRY(c.err, launch_snapshot_reduce(e.stream, s.d_recs, s.n_recs, args, tb));
+        }
+        HIP_TRY(c.err, hipEventRecord(sm.ev[1], e.stream));
+    }
+
+    // ---- the backtrace: the call-tree pass in summary mode over the records before P, and the call tree's merge
+    const uint32_t entry = prof::index_of_pc(prog, prog.entry);
+    if (entry == prof::NO_SUCC) return fail(p, DVT_ERR_INPUT, "the entry 0x%08x is no instruction of the text", prog.entry);
+    const std::vector<uint32_t> classes = calltree::instr_classes(prog);
+    CalltreeRun ct{p, {}};
+    auto prefix = [&](const ShardJob &s, size_t *take, uint32_t *succ) {
+        *take = s.index < shard ? s.n_recs : s.index == shard ? std::min<size_t>(s.n_recs, row) : 0;
+        *succ = *take < s.n_recs ? idx_at : prof::index_of_pc(prog, s.next_pc);
+    };
+    if (int rc = calltree_summaries(p, j, classes, 0, true, prefix, &ct)) return rc;
+    std::vector<calltree::Frame> stack;
+    uint64_t unmatched = 0, before_shard = 0;
+    if (position) stack.push_back(calltree::Frame{entry, 0});
+    for (size_t pos = 0; pos < j->n_total && position; pos++) {
+        size_t m = 0;
+        const ShardJob *s = j->at(pos, &m);
+        CalltreeMember &cm = *ct.mem[m];
+        const size_t k = (size_t)(s - j->parts[m].shards.data());
+        const size_t n_spans = (cm.n_of[k] + CALLTREE_SPAN - 1) / CALLTREE_SPAN;
+        for (size_t i = 0; i < n_spans; i++) {
+            const size_t span = cm.span0[k] + i;
+            unmatched += calltree_merge_span(stack, cm.summaries[span], cm.h_calls.data() + cm.calls_at[span], before_shard + i * CALLTREE_SPAN);
+        }
+        before_shard += s->n_recs;
+    }
+
+    // ---- the members' winners, merged
+    std::vector<unsigned long long> win(table_words, 0), one(table_words);
+    std::fill(win.begin() + 33 + W, win.end(), ~0ull);
+    for (size_t m = 0; m < G; m++) {
+        SnapMember &sm = *run.mem[m];
+        if (!sm.d_tables) continue;
+        if (int rc = turn_to(p, m)) return rc;
+        Engine &e = lane0(p, m).eng;
+        if (!e.download(one.data(), sm.d_tables, table_words * 8)) return engine_fail(p->err, e);
+        win[0] += one[0];
+        for (size_t i = 1; i < 33 + W; i++) win[i] = std::max(win[i], one[i]);
+        for (size_t i = 33 + W; i < table_words; i++) win[i] = std::min(win[i], one[i]);
+    }
+    if (turn_to(p, 0)) return DVT_ERR_DEVICE;
+    if (win[0]) return fail(p, DVT_ERR_INPUT, "%llu cycle records name an instruction outside the text or an address outside guest memory", win[0]);
+
+    // ---- gather: every winner from the member that holds its shard; the call records of the frames that are returned
+    struct Want { size_t m, at; uint32_t what, index; };
+    std::vector<Want> wants;
+    auto want = [&](unsigned long long where, uint32_t addr, uint32_t what, uint32_t index) {
+        const uint32_t sh = (uint32_t)(where >> 32), rw = (uint32_t)where;
+        size_t m = 0;
+        const ShardJob *s = sh ? j->at(sh - 1, &m) : nullptr;
+        if (!s || rw >= s->n_recs) return false;
+        wants.push_back({m, run.mem[m]->fetch.size(), what, index});
+        run.mem[m]->fetch.push_back(SnapFetch{s->d_recs, (uint32_t)s->n_recs, sh, rw, addr, what, 0});
+        return true;
+    };
+    bool ok = true;
+    for (uint32_t k = 1; k < 32; k++)
+        if (win[1 + k]) ok = ok && want(win[1 + k], k, snap::WHAT_REG, k);
+    for (uint32_t r = 0; r < rg.n; r++)
+        for (uint32_t addr = rg.lo[r]; addr < rg.hi[r]; addr += 4) {
+            const uint32_t slot = rg.at[r] + (addr - rg.lo[r]) / 4;
+            if (win[33 + slot]) ok = ok && want(win[33 + slot], addr, snap::WHAT_BEFORE, slot);
+            if (win[33 + W + slot] != ~0ull) ok = ok && want(win[33 + W + slot], addr, snap::WHAT_AFTER, slot);
+        }
+    const size_t depth = stack.size(), nf = std::min(depth, cap_frames);
+    for (size_t f = 0; f < nf; f++) {
+        const uint64_t open = stack[depth - 1 - f].open;
+        if (!open) continue;   // (the root)
+        uint32_t sh = 1, rw = 0;
+        snap::locate(shard_n, open - 1, &sh, &rw);
+        ok = ok && want(watch::position(sh, rw), 0, snap::WHAT_FRAME, (uint32_t)(depth - 1 - f));
+    }
+    if (!ok) return fail(p, DVT_ERR_DEVICE, "a winner of the reduce pass lies in no shard of the job");
+    for (size_t m = 0; m < G; m++) {
+        SnapMember &sm = *run.mem[m];
+        if (sm.fetch.empty()) continue;
+        if (int rc = turn_to(p, m)) return rc;
+        const Lane c = lane0(p, m);
+        Engine &e = c.eng;
+        HIP_TRY(c.err, e.pool.alloc_bytes(&sm.items.ptr, sm.fetch.size() * sizeof(SnapFetch)));
+        HIP_TRY(c.err, e.pool.alloc_bytes(&sm.sides.ptr, sm.fetch.size() * sizeof(snap::Side)));
+        HIP_TRY(c.err, hipMemcpyAsync(sm.items.ptr, sm.fetch.data(), sm.fetch.size() * sizeof(SnapFetch), hipMemcpyHostToDevice, e.stream));
+        args.statics = sm.d_statics; args.offs = sm.d_statics + n; args.shard = 0;
+        HIP_TRY(c.err, hipEventRecord(sm.ev[2], e.stream));
+        HIP_TRY(c.err, launch_snapshot_gather(e.stream, static_cast<const SnapFetch *>(sm.items.ptr), (uint32_t)sm.fetch.size(), args, sm.sides.ptr));
+        HIP_TRY(c.err, hipEventRecord(sm.ev[3], e.stream));
+        sm.gathered = true;
+        sm.got.resize(sm.fetch.size());
+        if (!e.download(sm.got.data(), sm.sides.ptr, sm.got.size() * sizeof(snap::Side))) return engine_fail(c.err, e);
+    }
+    double ms[3] = {0, 0, 0};
+    for (size_t m = 0; m < G; m++) {
+        SnapMember &sm = *run.mem[m];
+        CalltreeMember &cm = *ct.mem[m];
+        if (!sm.ev[0] && !cm.ev[0]) continue;
+        if (int rc = turn_to(p, m)) return rc;
+        float t = 0;
+        if (sm.ev[0] && hipEventElapsedTime(&t, sm.ev[0], sm.ev[1]) == hipSuccess) ms[0] += t;
+        if (sm.gathered && hipEventElapsedTime(&t, sm.ev[2], sm.ev[3]) == hipSuccess) ms[1] += t;
+        if (cm.ev[0] && hipEventElapsedTime(&t, cm.ev[0], cm.ev[1]) == hipSuccess) ms[2] += t;
+        if (cm.timed_calls && hipEventElapsedTime(&t, cm.ev[2], cm.ev[3]) == hipSuccess) ms[2] += t;
+    }
+    if (turn_to(p, 0)) return DVT_ERR_DEVICE;
+
+    snap::Side reg[32] = {};
+    std::vector<snap::Side> before(W, snap::Side{}), after(W, snap::Side{});
+    std::vector<snap::CallRec> calls(depth);
+    for (const Want &w : wants) {
+        const snap::Side &s = run.mem[w.m]->got[w.at];
+        if (s.kind == snap::SIDE_BAD || s.kind == snap::SIDE_NONE)
+            return fail(p, DVT_ERR_DEVICE, "the record at shard %u, row %u is not the access the reduce pass saw", s.shard, s.row);
+        if (w.what == snap::WHAT_REG) reg[w.index] = s;
+        else if (w.what == snap::WHAT_BEFORE) before[w.index] = s;
+        else if (w.what == snap::WHAT_AFTER) after[w.index] = s;
+        else calls[w.index] = snap::CallRec{s.pc, s.value};
+    }
+    for (int i = 0; i < 3; i++) p->snap_ms[i] = ms[i];
+    const snap::Parts parts{reg, before.data(), after.data(), &stack, &calls, &shard_n, position, cycles, unmatched, pc};
+    snap::emit(prog, rg, parts, ms_since(t0), regs, words, frames, cap_frames, summary);
+    return DVT_OK;
+}
+
 // The host-only reports (no GPU is touched): the guest in trace mode, where an instruction without a chip is recorded instead
 // of trapping, 2^log_shard (2^21) cycles per shard and one shard's records in memory at a time.  begin(prog) once the ELF is loaded;
 // shard(prog, recs, n, last_succ) per shard in execution order; end(prog, ms) after the last, and a text it returns fails the
@@ -812,7 +1081,10 @@ static int execute_traced(const uint8_t *elf, size_t elf_len, const dvt_buf *std
     begin(prog);
     for (;;) {
         vm.run_shard(true, &so, max_cycles ? max_cycles : ~0ull);
-        shard(prog, so.recs, so.n_recs, prof::index_of_pc(prog, so.next_pc));
+        if constexpr (std::is_invocable_v<Shard, const rv32::Program &, const rv32::CycleRec *, size_t, uint32_t, uint32_t>)
+            shard(prog, so.recs, so.n_recs, prof::index_of_pc(prog, so.next_pc), so.next_pc);   // (a report that wants the pc itself)
+        else
+            shard(prog, so.recs, so.n_recs, prof::index_of_pc(prog, so.next_pc));
         if (vm.halted || !vm.error.empty() || !vm.next_shard()) break;
     }
     if (report) {
@@ -972,6 +1244,53 @@ int dvt_execute_watch(const uint8_t *elf, size_t elf_len, const dvt_buf *stdin_b
         [&](const rv32::Program &prog, double ms) -> const char * {
             watch::emit(prog, *s, s->shards, ms, hits, totals, summary);
             return s->bad ? "cycle records name an instruction outside the text or an address outside guest memory" : nullptr;
+        },
+        log_shard_size ? log_shard_size : 21);
+}
+
+// ---- snapshots (snapshot.h)
+int dvt_rv32_job_snapshot(dvt_prover *p, const dvt_pk *pk, dvt_job *job, uint32_t shard, uint32_t row, const dvt_snap_range *ranges, size_t n_ranges,
+                          dvt_snap_cell regs[32], dvt_snap_cell *words, size_t cap_words, dvt_snap_frame *frames, size_t cap_frames,
+                          dvt_snap_summary *summary) {
+    if (!p || !pk || !job || !summary) return fail(p, DVT_ERR_INPUT, "null argument");
+    std::string text;
+    snap::Ranges rg;
+    if (const char *why = snap::input_error(ranges, n_ranges, regs, words, cap_words, frames, cap_frames, &rg, &text)) return fail(p, DVT_ERR_INPUT, "%s", why);
+    if (int rc = rv32_key(p, pk)) return rc;
+    Guard g(p); if (g.rc) return g.rc;
+    return job_snapshot(p, pk, job, shard, row, rg, regs, words, frames, cap_frames, summary);
+}
+
+int dvt_rv32_job_snapshot_times(dvt_prover *p, double out[3]) {
+    if (!p || !out) return DVT_ERR_INPUT;
+    std::lock_guard<std::mutex> lk(p->mu);
+    for (int i = 0; i < 3; i++) out[i] = p->snap_ms[i];
+    return DVT_OK;
+}
+
+// host-only: the same rule (snap::Taker) over execute_traced's shards
+int dvt_execute_snapshot(const uint8_t *elf, size_t elf_len, const dvt_buf *stdin_bufs, size_t nbuf, uint64_t max_cycles, uint32_t log_shard_size,
+                         uint32_t shard, uint32_t row, const dvt_snap_range *ranges, size_t n_ranges, dvt_snap_cell regs[32], dvt_snap_cell *words,
+                         size_t cap_words, dvt_snap_frame *frames, size_t cap_frames, dvt_snap_summary *summary, dvt_report *report,
+                         char **err_text) {
+    if (err_text) *err_text = nullptr;
+    if (!elf || (nbuf && !stdin_bufs) || !summary) return DVT_ERR_INPUT;
+    std::string text;
+    snap::Ranges rg;
+    if (log_shard_size && (log_shard_size < 4 || log_shard_size > 22)) text = "log_shard_size must be 0 or 4..22";
+    if (!text.empty() || snap::input_error(ranges, n_ranges, regs, words, cap_words, frames, cap_frames, &rg, &text)) {
+        if (err_text) *err_text = strdup(text.c_str());
+        return DVT_ERR_INPUT;
+    }
+    std::unique_ptr<snap::Taker> t;
+    return execute_traced(
+        elf, elf_len, stdin_bufs, nbuf, max_cycles, report, err_text, [&](const rv32::Program &prog) { t.reset(new snap::Taker(prog, rg, shard, row)); },
+        [&](const rv32::Program &prog, const rv32::CycleRec *recs, size_t n, uint32_t, uint32_t next_pc) {
+            t->scan(prog, recs, n, (uint32_t)t->shard_n.size() + 1, next_pc);
+        },
+        [&](const rv32::Program &prog, double ms) -> const char * {
+            t->emit(prog, ms, regs, words, frames, cap_frames, summary);
+            return t->bad ? "cycle records name an instruction outside the text or an address outside guest memory" : nullptr;
         },
         log_shard_size ? log_shard_size : 21);
 }

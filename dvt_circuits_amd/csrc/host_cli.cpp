@@ -1,11 +1,11 @@
 // dvt_prover_host — the reference's CLI verbs (src/main.rs:58-106) over the C ABI.
 //
 //   dvt_prover_host prove   --type T -i INPUT.json [-o PROOF] [--elf GUEST.elf] [--devices D0,D1,...] [--compact]
-//   dvt_prover_host execute --type T -i INPUT.json [--show-report] [--show-calls] [--show-memory] [--watch SPEC ...] [--elf GUEST.elf]
+//   dvt_prover_host execute --type T -i INPUT.json [--show-report] [--show-calls] [--show-memory] [--watch SPEC ...] [--snapshot S:R|exit [--dump ADDR+LEN ...] [--frames N]] [--elf GUEST.elf]
 //   dvt_prover_host verify  --type T -i PROOF [--elf GUEST.elf]
 //   dvt_prover_host compact --type T -i PROOF [-o PROOF] [--elf GUEST.elf]     (shared Merkle paths sent once: dvt_proof_compact)
 //   dvt_prover_host expand  --type T -i PROOF [-o PROOF] [--elf GUEST.elf]     (the inverse; verify takes either form)
-//   dvt_prover_host check   --type T -i INPUT.json [--show-report] [--show-calls] [--show-memory] [--watch SPEC ...] [--elf GUEST.elf] [--devices D0,D1,...]
+//   dvt_prover_host check   --type T -i INPUT.json [--show-report] [--show-calls] [--show-memory] [--watch SPEC ...] [--snapshot S:R|exit [--dump ADDR+LEN ...] [--frames N]] [--elf GUEST.elf] [--devices D0,D1,...]
 //
 // T = bad-share | finalization | bad-partial-key | bad-encrypted-share (clap names of CircuitType, :36-42).
 // The reference embeds the four guest ELFs at build time (include_elf!, :115-118); they cannot be built in
@@ -35,6 +35,12 @@
 // pwrite: mem: followed by ADDR[+BYTES][=VALUE[/MASK]], as tools/watch_guest.py takes them.  Per spec one line
 // "watch SPEC: total=N", then the last hits (at most 4), oldest first: "  SHARD:ROW pc=0xX rd=0xX rs1=0xX rs2=0xX" and, for a
 // load or store, " load|store addr=0xX before=0xX after=0xX prev=SHARD:CLK", for a precompile call " call addr=0xX words=N".
+// --snapshot S:R|exit: after those, the machine as it is before the record at shard S, row R executes, or after the last record
+// (dvt_execute_snapshot on the host, dvt_rv32_job_snapshot on the GPU; csrc/snapshot.h).  --dump ADDR+LEN (repeatable, at most
+// 16, 4096 words in all) names the memory to show, --frames N (default 16) how much of the call stack.  One line "snapshot:
+// position=N cycles=N shard=S row=R pc=0xX depth=N frames=N unmatched_returns=N words=N no_value=N initial=N untouched=N", four
+// lines "regs NAME=0xX ..." with x1..x31 by ABI name, one line per frame, innermost first: "#K 0xFN from 0xCALL ra=0xX opened
+// S:R", and per dumped range lines "0xADDR: W W W W" of up to four words, ?? for a word the records do not hold (NO_VALUE).
 // get-schema / validate-schema / node are product UI outside the accelerated path and are not provided.
 #include <algorithm>
 #include <cstdio>
@@ -212,13 +218,67 @@ template <class Call> static int print_watch(const std::vector<std::string> &spe
     return 0;
 }
 
+// a --snapshot position: S:R or exit
+static bool parse_position(const std::string &t, uint32_t *shard, uint32_t *row) {
+    if (t == "exit") { *shard = *row = 0xffffffffu; return true; }
+    const size_t colon = t.find(':');
+    if (colon == std::string::npos || colon == 0 || colon + 1 == t.size()) return false;
+    char *e0 = nullptr, *e1 = nullptr;
+    const unsigned long long s = strtoull(t.c_str(), &e0, 0), r = strtoull(t.c_str() + colon + 1, &e1, 0);
+    *shard = (uint32_t)s; *row = (uint32_t)r;
+    return e0 == t.c_str() + colon && !*e1 && s <= 0xffffffffull && r <= 0xffffffffull;
+}
+// a --dump ADDR+LEN as the range of the words that hold those bytes
+static bool parse_dump(const std::string &t, dvt_snap_range *out) {
+    const size_t plus = t.find('+');
+    if (plus == std::string::npos || plus == 0 || plus + 1 == t.size()) return false;
+    char *e0 = nullptr, *e1 = nullptr;
+    const unsigned long long a = strtoull(t.c_str(), &e0, 0), n = strtoull(t.c_str() + plus + 1, &e1, 0);
+    if (e0 != t.c_str() + plus || *e1 || !n || a + n > 0xffffffffull) return false;
+    out->lo = (uint32_t)a & ~3u;
+    out->hi = (uint32_t)((a + n + 3) & ~3ull);
+    return true;
+}
+
+// the snapshot's block (call: dvt_execute_snapshot or dvt_rv32_job_snapshot with everything else bound)
+template <class Call> static int print_snapshot(const std::vector<dvt_snap_range> &ranges, size_t n_frames, Call call) {
+    static const char *abi[32] = {"zero", "ra", "sp", "gp", "tp", "t0", "t1", "t2", "s0", "s1", "a0", "a1", "a2", "a3", "a4", "a5",
+                                  "a6", "a7", "s2", "s3", "s4", "s5", "s6", "s7", "s8", "s9", "s10", "s11", "t3", "t4", "t5", "t6"};
+    size_t n_words = 0;
+    for (auto &r : ranges) n_words += r.hi > r.lo ? (r.hi - r.lo) / 4 : 0;
+    dvt_snap_cell regs[32];
+    std::vector<dvt_snap_cell> words(std::max<size_t>(n_words, 1));
+    std::vector<dvt_snap_frame> frames(std::max<size_t>(n_frames, 1));
+    dvt_snap_summary s{};
+    if (int rc = call(ranges.data(), ranges.size(), regs, words.data(), n_words, frames.data(), n_frames, &s)) return rc;
+    printf("snapshot: position=%llu cycles=%llu shard=%u row=%u pc=0x%08x depth=%u frames=%u unmatched_returns=%u words=%u no_value=%u initial=%u untouched=%u\n",
+           (unsigned long long)s.position, (unsigned long long)s.cycles, s.shard, s.row, s.pc, s.depth, s.n_frames, s.unmatched_returns, s.n_words,
+           s.no_value, s.initial, s.untouched);
+    for (uint32_t k = 1; k < 32; k++) printf("%s%s=0x%08x%s", k % 8 == 1 ? "regs " : "", abi[k], regs[k].value, k % 8 == 0 || k == 31 ? "\n" : " ");
+    for (uint32_t f = 0; f < s.n_frames; f++)
+        printf("#%u 0x%08x from 0x%08x ra=0x%08x opened %u:%u\n", f, frames[f].fn_pc, frames[f].call_pc, frames[f].ra, frames[f].open_shard, frames[f].open_row);
+    size_t at = 0;
+    for (auto &r : ranges)
+        for (uint32_t k = 0; r.lo + 4 * k < r.hi; k++, at++) {
+            if (k % 4 == 0) printf("0x%08x:", r.lo + 4 * k);
+            if (words[at].flags & DVT_SNAP_NO_VALUE) printf(" ??");
+            else printf(" %08x", words[at].value);
+            if (k % 4 == 3 || r.lo + 4 * (k + 1) >= r.hi) printf("\n");
+        }
+    return 0;
+}
+
 int main(int argc, char **argv) {
-    if (argc < 2) return die("usage: dvt_prover_host prove|execute|verify|check|compact|expand --type T -i FILE [-o FILE] [--show-report] [--show-calls] [--show-memory] [--watch SPEC] [--compact] [--keep-trees] [--elf FILE] [--devices D0,D1,...] [--device D]");
+    if (argc < 2) return die("usage: dvt_prover_host prove|execute|verify|check|compact|expand --type T -i FILE [-o FILE] [--show-report] [--show-calls] [--show-memory] [--watch SPEC] [--snapshot S:R|exit] [--dump ADDR+LEN] [--frames N] [--compact] [--keep-trees] [--elf FILE] [--devices D0,D1,...] [--device D]");
     const std::string verb = argv[1];
     std::string type, input, output, elf_path, schema_path, devices, verify_device;
     bool show_report = false, show_calls = false, show_memory = false, auth = false, compact = false, keep_trees = false;
     std::vector<std::string> watch_specs;
     std::vector<dvt_watch_query> watch_queries;
+    bool snapshot = false;
+    uint32_t snap_shard = 0, snap_row = 0;
+    size_t snap_frames = 16;
+    std::vector<dvt_snap_range> snap_ranges;
     for (int i = 2; i < argc; i++) {
         std::string a = argv[i], inline_val;
         bool has_inline = false;
@@ -241,6 +301,17 @@ int main(int argc, char **argv) {
             watch_queries.emplace_back();
             if (!parse_watch(watch_specs.back(), &watch_queries.back())) return die("no watch spec: " + watch_specs.back());
         }
+        else if (a == "--snapshot") {
+            const std::string t = next();
+            if (!parse_position(t, &snap_shard, &snap_row)) return die("no position (S:R or exit): " + t);
+            snapshot = true;
+        }
+        else if (a == "--dump") {
+            const std::string t = next();
+            snap_ranges.emplace_back();
+            if (!parse_dump(t, &snap_ranges.back())) return die("no range (ADDR+LEN): " + t);
+        }
+        else if (a == "--frames") snap_frames = (size_t)strtoull(next().c_str(), nullptr, 0);
         else if (a == "--compact") compact = true;       // prove: shard proofs in the compact form ("compact_openings")
         else if (a == "--keep-trees") keep_trees = true;  // prove / check: shards that do not fit in HBM in full keep their main Merkle tree ("keep_phase1": 2)
         else if (a == "--auth-commitment") auth = true;  // the reference selects this at build time (cargo feature)
@@ -346,6 +417,15 @@ int main(int argc, char **argv) {
                 }))
                 return die(std::string("Verification failed: ") + (werr ? werr : "?"));
         }
+        if (snapshot) {
+            char *serr = nullptr;
+            if (print_snapshot(snap_ranges, snap_frames, [&](const dvt_snap_range *r, size_t n, dvt_snap_cell *regs, dvt_snap_cell *words, size_t cap_words,
+                                                             dvt_snap_frame *frames, size_t cap_frames, dvt_snap_summary *s) {
+                    return dvt_execute_snapshot(elf.data(), elf.size(), &buf, 1, 0, 0, snap_shard, snap_row, r, n, regs, words, cap_words, frames, cap_frames, s,
+                                                nullptr, &serr);
+                }))
+                return die(std::string("Verification failed: ") + (serr ? serr : "?"));
+        }
         return 0;
     }
 
@@ -408,6 +488,12 @@ int main(int argc, char **argv) {
                 return dvt_rv32_job_watch(p, pk, job, q, n, keep, hits, totals, s);
             }))
             return die(std::string("Watch failed: ") + dvt_last_error(p));
+        if (snapshot &&
+            print_snapshot(snap_ranges, snap_frames, [&](const dvt_snap_range *r, size_t n, dvt_snap_cell *regs, dvt_snap_cell *words, size_t cap_words,
+                                                         dvt_snap_frame *frames, size_t cap_frames, dvt_snap_summary *s) {
+                return dvt_rv32_job_snapshot(p, pk, job, snap_shard, snap_row, r, n, regs, words, cap_words, frames, cap_frames, s);
+            }))
+            return die(std::string("Snapshot failed: ") + dvt_last_error(p));
         dvt_job_free(p, job);
         dvt_pk_free(p, pk);
         dvt_prover_destroy(p);

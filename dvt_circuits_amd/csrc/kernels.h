@@ -180,4 +180,15 @@ hipError_t launch_watch_scan(hipStream_t st, const uint32_t *d_span_counts, uint
 hipError_t launch_watch_emit(hipStream_t st, const rv32::CycleRec *d_recs, size_t n_recs, const WatchArgs &a, const WatchEmitArgs &e,
                              const uint32_t *d_span_counts, const uint32_t *d_span_offs, void *d_out);
 
+// snapshot.hip
+// The snapshot's passes (snapshot.h).  reduce: over the cycle records of one shard, into the member's winner tables
+// (SnapTables: before and regs zeroed, after all ones, bad_records zeroed by the caller); SnapArgs carries the ranges, the
+// precompile shapes, the static words per instruction, the shard's number and the position.  gather: one snap::Side per
+// SnapFetch into d_out (snap::Side [n_items]).  The records are only read.
+struct SnapArgs;
+struct SnapTables;
+struct SnapFetch;
+hipError_t launch_snapshot_reduce(hipStream_t st, const rv32::CycleRec *d_recs, size_t n_recs, const SnapArgs &a, const SnapTables &t);
+hipError_t launch_snapshot_gather(hipStream_t st, const SnapFetch *d_items, uint32_t n_items, const SnapArgs &a, void *d_out);
+
 }  // namespace dvt

@@ -129,7 +129,8 @@ void dvt_free(void *ptr);
  * dvt_execute_profile; 13: "keep_phase1": 2, "keep_full_max", DVT_KEEP_*, dvt_rv32_job_shard_kept,
  * dvt_rv32_job_shard_kept_bytes, dvt_debug_keep_plan; 14: dvt_rv32_job_calltree,
  * dvt_rv32_job_calltree_times, dvt_execute_calltree; 15: dvt_rv32_job_memory, dvt_execute_memory;
- * 16: dvt_rv32_job_watch, dvt_execute_watch, dvt_rv32_job_watch_times) */
+ * 16: dvt_rv32_job_watch, dvt_execute_watch, dvt_rv32_job_watch_times; 17: dvt_rv32_job_snapshot,
+ * dvt_rv32_job_snapshot_times, dvt_execute_snapshot) */
 uint32_t dvt_abi_version(void);
 /* the handle's hipStream_t (for event timing by the caller) */
 void *dvt_stream(dvt_prover *p);
@@ -877,6 +878,67 @@ int dvt_rv32_job_watch_times(dvt_prover *p, double out[4]);
 int dvt_execute_watch(const uint8_t *elf, size_t elf_len, const dvt_buf *stdin_bufs, size_t nbuf, uint64_t max_cycles, uint32_t log_shard_size,
                       const dvt_watch_query *queries, size_t n_queries, size_t cap_each, dvt_watch_hit *hits, uint64_t *totals,
                       dvt_watch_summary *summary, dvt_report *report, char **err_text);
+/* Snapshots of a prepared job: registers, memory words and the call stack as they are BEFORE the record at position
+ * (shard, row) executes, from the cycle records the job holds (the records are only read and the job is left as found).
+ * Positions compare lexicographically as the windows of the watchpoints do; a position past the last record means the state
+ * after the last record, so (0xffffffff, 0xffffffff) is the state at exit (on the host path: at the trap).  The rule is stated
+ * in csrc/snapshot.h:
+ *   registers   regs[k], k = 1..31: value = the value written by the last record before the position whose instruction has
+ *               rd == k, flags = DVT_SNAP_FROM_BEFORE and (shard, row, pc) of that record; without one value 0 and
+ *               DVT_SNAP_INITIAL.  regs[0] is all zero.  addr = k.  Register values are always exact.
+ *   memory      up to DVT_SNAP_MAX_RANGES ranges [lo, hi) of word addresses (4-aligned, below the guest's address limit),
+ *               DVT_SNAP_MAX_WORDS words in all; `words` holds one cell per word, the ranges concatenated in their order.
+ *               Loads, stores and the words a precompile call WRITES decide a word (the words a call only reads do not).
+ *               B = the last deciding access of the word before the position, A = the first at or after it.  The first case
+ *               that applies:
+ *                 B is a store                  the word after B         FROM_BEFORE | STORE     source B
+ *                 B is a load                   the word B read          FROM_BEFORE | LOAD      source B
+ *                 A is a load or a store        the word before A        FROM_AFTER (| INITIAL when there is no B)   source A
+ *                 no B, a word of the image     the image's word         IMAGE | INITIAL         no source (0, 0, 0)
+ *                 otherwise                     0                        NO_VALUE                source B, else A
+ *               DVT_SNAP_UNTOUCHED is added when neither B nor A exists.  A NO_VALUE cell says that the records do not hold
+ *               the word: a precompile call wrote it and nothing loads it before the next such write (the limit of
+ *               DVT_WATCH_HIT_NO_VALUE); it still names the call in (shard, row, pc).  INITIAL: nothing accessed the word before
+ *               the position, and the value is the one the memory argument starts the word with: image, hint or 0.  A hinted
+ *               word holds that value in the machine only from its HINT_READ on; a snapshot before it shows it early.
+ *   call stack  the rule of the call-tree report over the records before the position; the frames still open are the
+ *               backtrace, innermost first: fn_pc, the position of the frame's first record (open_shard, open_row), call_pc
+ *               and ra = the pc of the call instruction (the record before) and the value it wrote (the root: 0xffffffff
+ *               and 0).  summary.depth counts all frames, n_frames = min(cap_frames, depth) are returned.
+ *   summary     position = the number of records before the position, (shard, row) = the position of record `position`
+ *               (of the end: the last shard and its record count), pc = that record's pc, at the end the last shard's
+ *               next_pc; cycles = all records; n_words and how many of them carry NO_VALUE, INITIAL and UNTOUCHED.
+ * DVT_ERR_INPUT: more than DVT_SNAP_MAX_RANGES ranges or DVT_SNAP_MAX_WORDS words, a misaligned or empty range, a range that
+ * reaches past the address limit, cap_words below the words asked for, null arrays, a cycle record that names an instruction
+ * outside the text or an address outside guest memory.  DVT_ERR_UNSUPPORTED: a prepare_part job that does not hold every
+ * shard of its execution.  Handles with several members work. */
+#define DVT_SNAP_MAX_RANGES 16
+#define DVT_SNAP_MAX_WORDS 4096
+#define DVT_SNAP_SPAN 4096   /* records one workgroup of the device pass reduces */
+enum { DVT_SNAP_INITIAL = 1, DVT_SNAP_FROM_BEFORE = 2, DVT_SNAP_FROM_AFTER = 4, DVT_SNAP_LOAD = 8, DVT_SNAP_STORE = 16, DVT_SNAP_IMAGE = 32,
+       DVT_SNAP_NO_VALUE = 64, DVT_SNAP_UNTOUCHED = 128 };
+typedef struct { uint32_t lo, hi; } dvt_snap_range;
+typedef struct { uint32_t addr, value, flags, shard, row, pc; } dvt_snap_cell;   /* addr: the register number of a register */
+typedef struct { uint32_t fn_pc, call_pc, open_shard, open_row, ra, pad; } dvt_snap_frame;
+typedef struct {
+    uint64_t position, cycles;
+    uint32_t shard, row, pc, depth, n_frames, unmatched_returns, n_words, no_value, initial, untouched, shards_total, text_base, n_instr, span;
+    float ms;          /* wall clock of the call after the entry guard */
+} dvt_snap_summary;
+int dvt_rv32_job_snapshot(dvt_prover *p, const dvt_pk *pk, dvt_job *job, uint32_t shard, uint32_t row, const dvt_snap_range *ranges,
+                          size_t n_ranges, dvt_snap_cell regs[32], dvt_snap_cell *words, size_t cap_words, dvt_snap_frame *frames,
+                          size_t cap_frames, dvt_snap_summary *summary);
+/* milliseconds of the last dvt_rv32_job_snapshot, by events on the members' streams and summed over the members: the reduce
+ * launches, the gather launches, the backtrace's call-tree launches */
+int dvt_rv32_job_snapshot_times(dvt_prover *p, double out[3]);
+/* The same snapshot on the host alone (no GPU is touched), the guest run in shards of 2^log_shard_size cycles (0: 21; 4..22)
+ * as dvt_execute_watch runs it, one shard's records held at a time.  Return codes, *report and *err_text as dvt_execute gives
+ * them; the outputs are filled for whatever retired, also when the guest fails: at (0xffffffff, 0xffffffff) they are the
+ * post-mortem of a guest that traps. */
+int dvt_execute_snapshot(const uint8_t *elf, size_t elf_len, const dvt_buf *stdin_bufs, size_t nbuf, uint64_t max_cycles, uint32_t log_shard_size,
+                         uint32_t shard, uint32_t row, const dvt_snap_range *ranges, size_t n_ranges, dvt_snap_cell regs[32],
+                         dvt_snap_cell *words, size_t cap_words, dvt_snap_frame *frames, size_t cap_frames, dvt_snap_summary *summary,
+                         dvt_report *report, char **err_text);
 /* test hook: run K0 on one shard of a prepared job and return the device-generated main traces
  * (canonical); blob layout as dvt_rv32_debug_traces with prep_width = 0. */
 int dvt_rv32_debug_device_traces(dvt_prover *p, const dvt_pk *pk, dvt_job *job, size_t shard, uint32_t **blob,
