@@ -176,6 +176,7 @@ def load():
     lib.dvt_rv32_prove_shard.argtypes = [vp, vp, vp, sz, u32p, C.POINTER(u8p), C.POINTER(sz)]
     lib.dvt_rv32_assemble.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(sz), sz, C.POINTER(u8p), C.POINTER(sz)]
     lib.dvt_rv32_debug_device_traces.argtypes = [vp, vp, vp, sz, C.POINTER(u32p), C.POINTER(sz)]
+    lib.dvt_rv32_debug_poke_cell.argtypes = [vp, vp, sz, u32, u32, u32, u32]
     prof_out = [C.POINTER(u64), sz, C.POINTER(ProfileEdge), sz, C.POINTER(ProfileSyscall), sz, C.POINTER(ProfileOpcode), sz, C.POINTER(ProfileSummary)]
     lib.dvt_rv32_job_profile.argtypes = [vp, vp, vp, u32] + prof_out
     lib.dvt_execute_profile.argtypes = [C.c_char_p, sz, C.POINTER(Buf), sz, u64] + prof_out + [C.POINTER(Report), C.POINTER(C.c_char_p)]
@@ -1408,6 +1409,13 @@ class Prover:
         w = np.ctypeslib.as_array(blob, shape=(n.value,)).copy()
         self.lib.dvt_free(C.cast(blob, C.c_void_p))
         return _parse_blob(w)
+
+    def debug_poke_cell(self, job, shard, chip, col, row, add):
+        """Test hook (dvt_rv32_debug_poke_cell): adds the canonical field element `add` (1 .. p-1) to main-trace cell (col, row)
+        of that chip's table of that shard (global position) of a prepared job.  Aux chips: in place, for the life of the
+        job; byte / program: the base multiplicities every K0 starts from; cpu: the kept K0 output, until the shard's next K0
+        (DvtError(DVT_ERR_UNSUPPORTED) when the shard holds no valid one).  The shard's phase 1 runs again before its next proof."""
+        self.check(self.lib.dvt_rv32_debug_poke_cell(self.h, job, shard, chip, col, row, add))
 
     # ---- shard-level API (multi-GPU: ranks own shards; the headers are the only thing exchanged)
     def job_shards(self, job):

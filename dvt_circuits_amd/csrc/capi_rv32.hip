@@ -1513,6 +1513,53 @@ int dvt_rv32_debug_device_traces(dvt_prover *p, const dvt_pk *pk, dvt_job *j, si
     return DVT_OK;
 }
 
+// test hook: add the canonical field element `add` to one main-trace cell of a table a prepared job holds, so that the job is
+// no longer honest (include/dvt_prover.h).  One word read and one word written on lane 0's stream of the member that holds the
+// shard, inside a buffer whose extent is checked here; the cycle records are never touched.
+int dvt_rv32_debug_poke_cell(dvt_prover *p, dvt_job *j, size_t shard, uint32_t chip, uint32_t col, uint32_t row, uint32_t add) {
+    if (!p || !j) return fail(p, DVT_ERR_INPUT, "bad argument");
+    if (int rc = same_members(p, nullptr, j)) return rc;
+    size_t mi = 0;
+    ShardJob *held = j->at(shard, &mi);
+    if (!held) return fail(p, DVT_ERR_INPUT, "shard %zu is not held by this job", shard);
+    ShardJob &s = *held;
+    const MachineDesc *m = machine_rv32();
+    if (chip >= (uint32_t)rv32::N_CHIPS || !s.present[chip]) return fail(p, DVT_ERR_INPUT, "shard %zu has no table of chip %u", shard, chip);
+    const uint32_t main_w = (uint32_t)m->chips[chip].main_w, log_n = s.log_n[chip];
+    if (col >= main_w || log_n > 22 || row >= (1u << log_n))
+        return fail(p, DVT_ERR_INPUT, "cell (%u, %u) is outside the %u x 2^%u main trace of chip %s", col, row, main_w, log_n, m->chips[chip].name);
+    if (!add || add >= P) return fail(p, DVT_ERR_INPUT, "the value to add must be 1 .. p-1");
+    Guard g(p); if (g.rc) return g.rc;
+    const size_t words = (size_t)main_w << log_n;
+    const bool counts = chip == RV32_CHIP_BYTE || chip == RV32_CHIP_PROGRAM;   // plain integers: K0 converts its copy
+    uint32_t *base = nullptr;
+    if (chip == RV32_CHIP_CPU) {
+        if (!s.d_cpu || !s.traces_valid)
+            return fail(p, DVT_ERR_UNSUPPORTED, "shard %zu holds no valid K0 output: the cpu rows are rebuilt from the cycle records", shard);
+        base = s.d_cpu;
+    } else {
+        if (counts && words != (chip == RV32_CHIP_BYTE ? j->byte_words : j->prog_words))
+            return fail(p, DVT_ERR_DEVICE, "the multiplicities of chip %s have another size than its table", m->chips[chip].name);
+        base = s.d_aux[chip];
+    }
+    if (!base) return fail(p, DVT_ERR_DEVICE, "chip %s of shard %zu has no buffer", m->chips[chip].name, shard);
+    if (int rc = turn_to(p, mi)) return rc;
+    Member &mem = member(p, mi);
+    HIP_TRY(p, sync_lanes(mem));   // (a kept K0 output is of the lane that committed the shard)
+    uint32_t *cell = base + ((size_t)col << log_n) + row;
+    uint32_t w = 0;
+    HIP_TRY(p, hipMemcpyAsync(&w, cell, 4, hipMemcpyDeviceToHost, mem.eng.stream));
+    HIP_TRY(p, hipStreamSynchronize(mem.eng.stream));
+    w = counts ? (uint32_t)(((uint64_t)w + add) % P) : (Fp::raw(w) + Fp::from_canonical(add)).v;
+    HIP_TRY(p, hipMemcpyAsync(cell, &w, 4, hipMemcpyHostToDevice, mem.eng.stream));
+    HIP_TRY(p, hipStreamSynchronize(mem.eng.stream));
+    // no later proof combines an honest phase-1 commitment with the poked table; a kept K0 output no longer matches poked counts
+    s.header_valid = false;
+    s.cache.valid = false;
+    if (counts) s.traces_valid = false;
+    return DVT_OK;
+}
+
 // test hook (host only, no device): the admission rule of "keep_phase1" (keep_plan.h) on the caller's figures
 int dvt_debug_keep_plan(int mode, uint64_t free_bytes, uint64_t total_bytes, uint64_t reserve_bytes, uint64_t full_bytes, uint64_t tree_bytes,
                         uint64_t later_bytes, uint64_t remaining, int count_known, int64_t full_cap, uint64_t full_kept) {

@@ -130,7 +130,7 @@ void dvt_free(void *ptr);
  * dvt_rv32_job_shard_kept_bytes, dvt_debug_keep_plan; 14: dvt_rv32_job_calltree,
  * dvt_rv32_job_calltree_times, dvt_execute_calltree; 15: dvt_rv32_job_memory, dvt_execute_memory;
  * 16: dvt_rv32_job_watch, dvt_execute_watch, dvt_rv32_job_watch_times; 17: dvt_rv32_job_snapshot,
- * dvt_rv32_job_snapshot_times, dvt_execute_snapshot) */
+ * dvt_rv32_job_snapshot_times, dvt_execute_snapshot; 18: dvt_rv32_debug_poke_cell) */
 uint32_t dvt_abi_version(void);
 /* the handle's hipStream_t (for event timing by the caller) */
 void *dvt_stream(dvt_prover *p);
@@ -943,6 +943,28 @@ int dvt_execute_snapshot(const uint8_t *elf, size_t elf_len, const dvt_buf *stdi
  * (canonical); blob layout as dvt_rv32_debug_traces with prep_width = 0. */
 int dvt_rv32_debug_device_traces(dvt_prover *p, const dvt_pk *pk, dvt_job *job, size_t shard, uint32_t **blob,
                                  size_t *blob_words);
+/* test hook: make a prepared job dishonest.  Adds the canonical field element `add` (1 .. p-1) to main-trace cell (col, row)
+ * of the table of chip `chip` of shard `shard` (global position), on the device member that holds the shard, so that the job
+ * check, the job's bus ledger and the prover can be tried on a wrong table.  Like every call on the handle it stops a running
+ * prove_shard pipeline first; it returns after the write is complete on the member's stream.  What is written depends on
+ * where the job holds the table:
+ *  - the chips whose table the job holds as uploaded or as built at upload (mem_image, mem_init, shift, muldiv, the SHA and
+ *    the field / curve chips): the cell of that table, in place, in the representation the table has there.  It lasts for
+ *    the life of the job.
+ *  - byte (1) and program (0): the word of the base multiplicities the job holds, which every K0 copies and adds the cpu
+ *    rows' lookups to (plain integers below p there, so the sum is taken mod p).  It lasts for the life of the job; a K0
+ *    output kept from phase 1 no longer matches it and is marked invalid, so the next reader of the shard runs K0 again.
+ *  - cpu (2): its rows are rebuilt from the cycle records by every K0, and the records are not touched.  The cell of the K0
+ *    output kept from phase 1 is written, which is allowed only while the shard holds a valid one (DVT_KEEP_FULL and not yet
+ *    consumed by a phase 2); it lasts until the shard's next K0.  Otherwise DVT_ERR_UNSUPPORTED.
+ * In every case the shard's header and phase-1 results are marked invalid: the next dvt_rv32_prove_job (or commit_shard) runs
+ * phase 1 of that shard again, as a second prove_job of a job does, so no proof combines an honest commitment with the
+ * poked table.  Adding p - add to the same cell restores the job.
+ * DVT_ERR_INPUT: a null argument, a shard the job does not hold, a chip the shard has no table of, col >= main_w,
+ * row >= 2^log_n, add == 0 or add >= p.  One word is written, inside a buffer whose bounds were just checked; no cycle
+ * record is read or written. */
+int dvt_rv32_debug_poke_cell(dvt_prover *p, dvt_job *job, size_t shard, uint32_t chip, uint32_t col, uint32_t row,
+                             uint32_t add);
 /* stock `client.verify(&proof,&vk)` semantics (NOT the reference's re-execution
  * `verify` sub-command).  Host-only.  *public_values = the guest's fd-3 byte
  * stream; the proof binds it through the eight COMMITted words of its SHA-256 digest, which the

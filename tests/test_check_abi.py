@@ -7,7 +7,7 @@ from dvt_circuits_amd import capi
 
 def test_check_symbols_are_exported():
     lib = capi.load()
-    for name in ("dvt_stage_check_constraints", "dvt_stage_bus_sums", "dvt_rv32_check_job"):
+    for name in ("dvt_stage_check_constraints", "dvt_stage_bus_sums", "dvt_rv32_check_job", "dvt_rv32_debug_poke_cell"):
         assert hasattr(lib, name), name
 
 
