@@ -1,6 +1,6 @@
 // C-ABI layer (include/dvt_prover.h) over the gfx950 engine: the handle and its config, the entry guard and the error path,
 // the stage entry points of the prover's kernels and the machine-level ones (the rv32 boundary is capi_rv32.hip, the
-// inspectors of trace rows capi_inspect.hip).  There is no CPU fallback anywhere in this layer: without a HIP device every
+// inspectors of trace rows capi_inspect.hip, the reports over cycle records capi_report.hip).  There is no CPU fallback anywhere in this layer: without a HIP device every
 // entry point that computes returns DVT_ERR_DEVICE.  (dvt_machine_verify is host-only by nature.)
 #include <algorithm>
 #include <cstdarg>

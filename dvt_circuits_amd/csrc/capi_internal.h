@@ -1,5 +1,6 @@
 // Private to the C-ABI layer: what capi.hip (the handle, the stage and machine-level entry points), capi_rv32.hip (the rv32 boundary:
-// setup, the job of capi_job.h and its pipelines, prove, assemble, verify) and capi_inspect.hip (the inspectors of trace rows) share.
+// setup, the job of capi_job.h and its pipelines, prove, assemble, verify), capi_inspect.hip (the inspectors of trace rows) and
+// capi_report.hip (the reports over a job's cycle records) share.
 #pragma once
 #include "../../include/dvt_prover.h"
 

@@ -1,4 +1,5 @@
-// Private to the rv32-aware units of the C-ABI layer: the prepared job capi_rv32.hip makes and proves and capi_inspect.hip reads.
+// Private to the rv32-aware units of the C-ABI layer: the prepared job capi_rv32.hip makes and proves, whose trace rows
+// capi_inspect.hip reads and whose cycle records capi_report.hip reads.
 #pragma once
 #include <chrono>
 
@@ -48,6 +49,18 @@ struct JobPart {
 int same_members(dvt_prover *p, const dvt_pk *pk, const dvt_job *j);
 // the check of every entry point that takes an rv32 key
 inline int rv32_key(dvt_prover *p, const dvt_pk *pk) { return pk->is_rv32 ? DVT_OK : fail(p, DVT_ERR_INPUT, "proving key was not made by dvt_setup"); }
+// One pass over the members of the handle: fn(m, lane 0 of member m) -> int under member m's turn, until one returns non-zero.
+// Then member 0's device is current again; DVT_ERR_DEVICE when that fails and nothing else did.
+template <class Fn>
+int for_members(dvt_prover *p, Fn fn) {
+    int rc = DVT_OK;
+    for (size_t m = 0; m < n_members(p) && !rc; m++) {
+        rc = turn_to(p, m);
+        if (!rc) rc = fn(m, lane0(p, m));
+    }
+    if (turn_to(p, 0) && !rc) rc = DVT_ERR_DEVICE;
+    return rc;
+}
 // K0 of a shard (into the shard's own buffers when it has them, else the job's working buffers); fills the chip
 // trace list of that shard.  `reuse`: phase 2 takes the traces phase 1 left behind instead of generating them again.
 int shard_traces(const Lane &c, const DeviceKey &key, dvt_job *j, ShardJob &s, std::vector<ChipTrace> *traces, bool reuse);

@@ -1,5 +1,5 @@
 // The rv32 boundary of the C ABI (include/dvt_prover.h): setup from an ELF, execute, the job (capi_job.h; the prepare pipeline and phase 1,
-// the phase-2 pipeline on the prover lanes), prove, assemble, verify and the debug hooks.  (A job's inspectors: capi_inspect.hip.)
+// the phase-2 pipeline on the prover lanes), prove, assemble, verify and the debug hooks.  (A job's inspectors: capi_inspect.hip; its reports: capi_report.hip.)
 #include <algorithm>
 #include <atomic>
 #include <cstdio>

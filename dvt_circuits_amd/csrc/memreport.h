@@ -75,6 +75,17 @@ inline std::vector<PreShape> pre_shapes() {
     }
     return t;
 }
+// Host only: what the device pass takes in one upload, [classes | offs | the shapes, six words each].
+inline std::vector<uint32_t> device_table(const rv32::Program &prog, const std::vector<PreShape> &shapes) {
+    const size_t n = prog.instrs.size() - 1;
+    std::vector<uint32_t> t(2 * n);
+    for (size_t i = 0; i < n; i++) {
+        t[i] = instr_class(prog.instrs[i]);
+        t[n + i] = prog.instrs[i].off;
+    }
+    for (auto &s : shapes) t.insert(t.end(), {s.id, s.n0, s.r0, s.w0, s.n1, s.w1});
+    return t;
+}
 
 // one page while it is added up; bits: its line of the footprint bitmap
 struct Page {

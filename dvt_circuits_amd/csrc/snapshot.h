@@ -249,7 +249,7 @@ inline void emit(const rv32::Program &prog, const Ranges &rg, const Parts &in, d
 struct Taker {
     Ranges rg;
     unsigned long long P;
-    std::vector<uint32_t> statics, offs;
+    watch::Statics stat;
     watch::Shapes sh;
     Side reg[32] = {};
     std::vector<Side> before, after;
@@ -260,18 +260,14 @@ struct Taker {
     uint32_t pc = 0;
     bool pc_known = false;
     Taker(const rv32::Program &prog, const Ranges &ranges, uint32_t shard, uint32_t row)
-        : rg(ranges), P(watch::position(shard, row)), sh(watch::shapes()), before(ranges.n_words, Side{}), after(ranges.n_words, Side{}), st(prog) {
-        const size_t n_instr = prog.instrs.size() - 1;
-        statics.resize(n_instr); offs.resize(n_instr);
-        for (size_t i = 0; i < n_instr; i++) { statics[i] = watch::instr_static(prog.instrs[i]); offs[i] = prog.instrs[i].off; }
-    }
+        : rg(ranges), P(watch::position(shard, row)), stat(prog), sh(watch::shapes()), before(ranges.n_words, Side{}), after(ranges.n_words, Side{}), st(prog) {}
     // the records of shard `shard` (numbered from 1) and the pc the shard hands on
     void scan(const rv32::Program &prog, const rv32::CycleRec *recs, size_t n, uint32_t shard, uint32_t next_pc) {
-        const uint32_t n_instr = (uint32_t)statics.size();
+        const uint32_t n_instr = (uint32_t)stat.n();
         const uint32_t p_shard = (uint32_t)(P >> 32), p_row = (uint32_t)P;
         const size_t n_pre = shard < p_shard ? n : shard == p_shard ? std::min<size_t>(n, p_row) : 0;   // the records of this shard before P
         for (size_t r = 0; r < n; r++) {
-            const watch::Decoded d = watch::decode(recs[r], n_instr, prog.text_base, statics.data(), offs.data(), sh);
+            const watch::Decoded d = watch::decode(recs[r], n_instr, prog.text_base, stat.statics(), stat.offs(), sh);
             if (d.bad) { bad++; continue; }
             const uint32_t rd = d.st & watch::ST_RD_MASK;
             if (r < n_pre) {

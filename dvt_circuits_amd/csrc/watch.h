@@ -56,6 +56,20 @@ inline uint32_t instr_static(const rv32::Instr &in) {
     return (in.rd & ST_RD_MASK) | (cls & memrep::CLS_LOAD ? ST_LOAD : 0) | (cls & memrep::CLS_STORE ? ST_STORE : 0) | (cls & memrep::CLS_ECALL ? ST_ECALL : 0) |
            (in.kind == rv32::K_SH ? ST_HALF : 0) | (in.kind == rv32::K_SB ? ST_BYTE : 0);
 }
+// Host only: both of a program, [statics | offs] in one piece, as the device passes take them in one upload.
+struct Statics {
+    std::vector<uint32_t> words;
+    explicit Statics(const rv32::Program &prog) : words(2 * (prog.instrs.size() - 1)) {
+        for (size_t i = 0; i < n(); i++) {
+            words[i] = instr_static(prog.instrs[i]);
+            words[n() + i] = prog.instrs[i].off;
+        }
+    }
+    size_t n() const { return words.size() / 2; }   // n_instr
+    size_t bytes() const { return words.size() * 4; }
+    const uint32_t *statics() const { return words.data(); }
+    const uint32_t *offs() const { return words.data() + n(); }
+};
 
 // The shapes of the precompile calls as the passes take them (by value on the device): the rows of memrep::pre_shapes().
 struct Shapes {
@@ -221,26 +235,23 @@ inline const char *input_error(const dvt_watch_query *q, size_t n, size_t cap_ea
 struct Search {
     std::vector<dvt_watch_query> queries;
     uint32_t K;
-    std::vector<uint32_t> statics, offs;
+    Statics st;
     Shapes sh;
     std::vector<uint64_t> total;
     std::vector<std::vector<dvt_watch_hit>> first, ring;
     uint64_t cycles = 0, bad = 0;
     uint32_t shards = 0;
     Search(const rv32::Program &prog, const dvt_watch_query *q, size_t n, uint32_t cap_each)
-        : queries(q, q + n), K(cap_each), sh(shapes()), total(n, 0), first(n), ring(n) {
-        const size_t n_instr = prog.instrs.size() - 1;
-        statics.resize(n_instr); offs.resize(n_instr);
-        for (size_t i = 0; i < n_instr; i++) { statics[i] = instr_static(prog.instrs[i]); offs[i] = prog.instrs[i].off; }
+        : queries(q, q + n), K(cap_each), st(prog), sh(shapes()), total(n, 0), first(n), ring(n) {
         for (auto &r : ring) r.resize(K);
     }
 };
 
 // the records of shard `shard` (numbered from 1), in execution order
 inline void scan_records(const rv32::Program &prog, const rv32::CycleRec *recs, size_t n, uint32_t shard, Search *s) {
-    const uint32_t n_instr = (uint32_t)s->statics.size();
+    const uint32_t n_instr = (uint32_t)s->st.n();
     for (size_t r = 0; r < n; r++) {
-        const Decoded d = decode(recs[r], n_instr, prog.text_base, s->statics.data(), s->offs.data(), s->sh);
+        const Decoded d = decode(recs[r], n_instr, prog.text_base, s->st.statics(), s->st.offs(), s->sh);
         if (d.bad) { s->bad++; continue; }
         for (size_t qi = 0; qi < s->queries.size(); qi++) {
             CallMatch cm{};
@@ -271,7 +282,7 @@ inline void emit(const rv32::Program &prog, const Search &s, uint32_t shards_tot
     out.shards_searched = s.shards;
     out.shards_total = shards_total;
     out.text_base = prog.text_base;
-    out.n_instr = (uint32_t)s.statics.size();
+    out.n_instr = (uint32_t)s.st.n();
     out.span = SPAN;
     out.ms = (float)ms;
     *summary = out;
