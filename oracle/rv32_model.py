@@ -1143,45 +1143,49 @@ def traces(run: Run, pos: int):
     # ---- preprocessed chips and their multiplicity columns
     cidp, chipp = chips["program"]
     np_rows = 1 << log2ceil(max(len(run.provable), 1))
-    prep = np.zeros((chipp.prep_width, np_rows), np.int64)
-    pidx = {nm: i for i, nm in enumerate(chipp.prep_names)}
+    # (the preprocessed tables are those of the program, not of the shard: built once per run, copied per shard)
+    fixed = run.__dict__.setdefault("_prep_tables", {})
+    if not fixed:
+        prep = np.zeros((chipp.prep_width, np_rows), np.int64)
+        pidx = {nm: i for i, nm in enumerate(chipp.prep_names)}
+        for r in range(np_rows):
+            ins = run.provable[r] if r < len(run.provable) else run.provable[0]
+            k = ins.kind
+            vals = dict(pc=ins.pc, rd=ins.rd, rs1=ins.rs1, rs2=ins.rs2, aux=ins.tgt_col + (ALU_CODES[ins.alu] if k == "alu" else 0))
+            for i in range(4):
+                vals[f"imm[{i}]"] = byts(ins.imm | ins.off)[i]
+            vals["bit_op"], vals["cmp_signed"] = bit_op_of.get(k, 0), int(k in signed_forms)
+            reads_rs2 = (k in ("beq", "bne", "blt", "bge", "bltu", "bgeu", "sb", "sh", "sw", "ecall")
+                         or (not ins.imm_form and k in ("add", "sub", "and", "or", "xor", "slt", "sltu", "mul", "mulhu", "alu")))
+            fl = {f: 0 for f in FLAGS}
+            fl[fam_of[k]] = 1
+            fl["rd_en"], fl["rs1_en"], fl["rs2_en"], fl["imm_c"] = int(ins.rd != 0), int(k not in ("lui", "jal")), int(reads_rs2), int(ins.imm_form)
+            vals.update(fl)
+            for nm, v in vals.items():
+                prep[pidx[nm], r] = v
+        cidb, chipb = chips["byte"]
+        bprep = np.zeros((chipb.prep_width, 65536), np.int64)
+        rr = np.arange(65536)
+        bb, cc = rr >> 8, rr & 255
+        for nm, v in (("b", bb), ("c", cc), ("and", bb & cc), ("or", bb | cc), ("xor", bb ^ cc), ("ltu", (bb < cc).astype(np.int64)), ("msb", bb >> 7),
+                      ("addr", (bb & 3) + 4 * (cc >= (ADDR_LIMIT >> 24)).astype(np.int64))):
+            bprep[chipb.prep_names.index(nm)] = v
+        cidi, chipi = chips["mem_image"]
+        img = sorted([(REG_BASE + r_, 0) for r_ in range(32)] + list(run.image_mem.items()))
+        ni = 1 << log2ceil(len(img))
+        iprep = np.zeros((chipi.prep_width, ni), np.int64)
+        for r, (addr, v) in enumerate(img):
+            iprep[chipi.prep_names.index("addr"), r] = addr
+            for i in range(4):
+                iprep[chipi.prep_names.index(f"v[{i}]"), r] = byts(v)[i]
+            iprep[chipi.prep_names.index("is_real"), r] = 1
+        fixed.update(program=prep, byte=bprep, mem_image=iprep)
     mult = np.zeros((1, np_rows), np.int64)
-    for r in range(np_rows):
-        ins = run.provable[r] if r < len(run.provable) else run.provable[0]
-        k = ins.kind
-        vals = dict(pc=ins.pc, rd=ins.rd, rs1=ins.rs1, rs2=ins.rs2, aux=ins.tgt_col + (ALU_CODES[ins.alu] if k == "alu" else 0))
-        for i in range(4):
-            vals[f"imm[{i}]"] = byts(ins.imm | ins.off)[i]
-        vals["bit_op"], vals["cmp_signed"] = bit_op_of.get(k, 0), int(k in signed_forms)
-        reads_rs2 = (k in ("beq", "bne", "blt", "bge", "bltu", "bgeu", "sb", "sh", "sw", "ecall")
-                     or (not ins.imm_form and k in ("add", "sub", "and", "or", "xor", "slt", "sltu", "mul", "mulhu", "alu")))
-        fl = {f: 0 for f in FLAGS}
-        fl[fam_of[k]] = 1
-        fl["rd_en"], fl["rs1_en"], fl["rs2_en"], fl["imm_c"] = int(ins.rd != 0), int(k not in ("lui", "jal")), int(reads_rs2), int(ins.imm_form)
-        vals.update(fl)
-        for nm, v in vals.items():
-            prep[pidx[nm], r] = v
-        if r < len(run.provable):
-            mult[0, r] = prog_mult.get(ins.pc, 0)
-    out["program"] = (mult, prep)
-    cidb, chipb = chips["byte"]
-    bprep = np.zeros((chipb.prep_width, 65536), np.int64)
-    rr = np.arange(65536)
-    bb, cc = rr >> 8, rr & 255
-    for nm, v in (("b", bb), ("c", cc), ("and", bb & cc), ("or", bb | cc), ("xor", bb ^ cc), ("ltu", (bb < cc).astype(np.int64)), ("msb", bb >> 7),
-                  ("addr", (bb & 3) + 4 * (cc >= (ADDR_LIMIT >> 24)).astype(np.int64))):
-        bprep[chipb.prep_names.index(nm)] = v
-    out["byte"] = (lk.byte, bprep)
-    cidi, chipi = chips["mem_image"]
-    img = sorted([(REG_BASE + r_, 0) for r_ in range(32)] + list(run.image_mem.items()))
-    ni = 1 << log2ceil(len(img))
-    iprep = np.zeros((chipi.prep_width, ni), np.int64)
-    for r, (addr, v) in enumerate(img):
-        iprep[chipi.prep_names.index("addr"), r] = addr
-        for i in range(4):
-            iprep[chipi.prep_names.index(f"v[{i}]"), r] = byts(v)[i]
-        iprep[chipi.prep_names.index("is_real"), r] = 1
-    out["mem_image"] = (np.zeros((1, ni), np.int64), iprep)
+    for r, ins in enumerate(run.provable):
+        mult[0, r] = prog_mult.get(ins.pc, 0)
+    out["program"] = (mult, fixed["program"].copy())
+    out["byte"] = (lk.byte, fixed["byte"].copy())
+    out["mem_image"] = (np.zeros((1, fixed["mem_image"].shape[1]), np.int64), fixed["mem_image"].copy())
 
     result = []
     for name, (cid, chip) in sorted(chips.items(), key=lambda kv: kv[1][0]):
