@@ -195,6 +195,10 @@ def load():
     lib.dvt_rv32_job_snapshot.argtypes = [vp, vp, vp] + snap_io
     lib.dvt_rv32_job_snapshot_times.argtypes = [vp, C.POINTER(C.c_double)]
     lib.dvt_execute_snapshot.argtypes = [C.c_char_p, sz, C.POINTER(Buf), sz, u64, u32] + snap_io + [C.POINTER(Report), C.POINTER(C.c_char_p)]
+    origin_io = [u32, u32, u32, u32, u32, u32, C.POINTER(OriginNode), sz, C.POINTER(OriginEdge), sz, C.POINTER(OriginSummary)]
+    lib.dvt_rv32_job_origin.argtypes = [vp, vp, vp] + origin_io
+    lib.dvt_rv32_job_origin_times.argtypes = [vp, C.POINTER(C.c_double)]
+    lib.dvt_execute_origin.argtypes = [C.c_char_p, sz, C.POINTER(Buf), sz, u64, u32] + origin_io + [C.POINTER(Report), C.POINTER(C.c_char_p)]
     lib.dvt_stdin_from_json.argtypes = [C.c_char_p, C.c_char_p, sz, C.c_int, C.POINTER(u8p), C.POINTER(sz), C.POINTER(C.c_char_p)]
     _lib = lib
     return lib
@@ -667,6 +671,71 @@ def execute_snapshot(elf: bytes, stdin=(), at=SNAP_EXIT, ranges=(), frames=64, m
     rc, snap = _snapshot(lambda *io: lib.dvt_execute_snapshot(elf, len(elf), bufs, len(stdin), max_cycles, log_shard, *io, C.byref(rep), C.byref(err)),
                          at, ranges, frames)
     return rc, dict(cycles=rep.cycles, exit_code=rep.exit_code, halted=bool(rep.halted), unprovable=bool(rep.unprovable)), snap, _take_str(lib, err)
+
+
+# ---- origins (csrc/origin.h)
+DVT_ORIGIN_MAX_NODES, DVT_ORIGIN_MAX_EDGES, DVT_ORIGIN_MAX_DEPTH, DVT_ORIGIN_PASS_QUESTIONS, DVT_ORIGIN_SPAN = 1024, 8192, 64, 256, 4096
+DVT_ORIGIN_NONE = 0xFFFFFFFF
+DVT_ORIGIN_REG, DVT_ORIGIN_WORD = 1, 2
+DVT_ORIGIN_FOLLOW_ADDR = 1
+DVT_ORIGIN_OP, DVT_ORIGIN_LOAD, DVT_ORIGIN_STORE, DVT_ORIGIN_CALL, DVT_ORIGIN_SYSCALL = 1, 2, 3, 4, 5
+DVT_ORIGIN_ROOT, DVT_ORIGIN_ADDR, DVT_ORIGIN_RS1, DVT_ORIGIN_RS2, DVT_ORIGIN_MEM = 0, 1, 2, 3, 4
+DVT_ORIGIN_INITIAL, DVT_ORIGIN_IMAGE, DVT_ORIGIN_NO_VALUE, DVT_ORIGIN_CUT, DVT_ORIGIN_UNEXPANDED = 1, 2, 4, 8, 16
+
+
+class OriginNode(C.Structure):
+    _fields_ = [(name, C.c_uint32) for name in ("shard", "row", "pc", "idx", "kind", "depth", "first_edge", "n_edges", "flags", "rd_value", "rs1", "rs2",
+                                                "addr", "before", "after", "pad")]
+
+
+class OriginEdge(C.Structure):
+    _fields_ = [(name, C.c_uint32) for name in ("from", "to", "role", "target", "value", "flags", "src_shard", "src_row")]
+
+
+class OriginSummary(C.Structure):
+    _fields_ = [("position", C.c_uint64), ("cycles", C.c_uint64)] + \
+               [(name, C.c_uint32) for name in ("n_nodes", "n_edges", "depth", "cut", "unexpanded", "initial", "no_value", "questions", "levels", "passes",
+                                                "shard", "row", "shards_total", "span")] + [("ms", C.c_float)]
+
+
+def origin_reg(k):
+    """the target of an origin call: register x_k (a number 1..31 or a name of REG_NAMES)"""
+    return DVT_ORIGIN_REG, REG_NAMES.index(k) if isinstance(k, str) else int(k)
+
+
+def origin_word(addr):
+    """the target of an origin call: the word that holds the byte at addr"""
+    return DVT_ORIGIN_WORD, addr & ~3
+
+
+_NODE_KEYS = [name for name, _ in OriginNode._fields_ if name != "pad"]
+_EDGE_KEYS = [name for name, _ in OriginEdge._fields_]
+
+
+def _origin(call, at, target, follow_addr, depth, nodes, edges):
+    """The slice through call(shard, row, what, target, flags, max_depth, nodes, cap_nodes, edges, cap_edges, summary) -> rc.
+    Returns (rc, dict(summary, nodes = node dicts in discovery order, edges = edge dicts, edge 0 the root) or None when the call
+    fails without an answer)."""
+    ns, es, s = (OriginNode * max(nodes, 1))(), (OriginEdge * max(edges, 1))(), OriginSummary()
+    rc = call(at[0], at[1], target[0], target[1], DVT_ORIGIN_FOLLOW_ADDR if follow_addr else 0, depth, ns, nodes, es, edges, C.byref(s))
+    if rc not in (DVT_OK, DVT_ERR_GUEST):
+        return rc, None
+    summary = {name: (float if name == "ms" else int)(getattr(s, name)) for name, _ in OriginSummary._fields_}
+    return rc, dict(summary=summary, nodes=[{name: int(getattr(ns[i], name)) for name in _NODE_KEYS} for i in range(summary["n_nodes"])],
+                    edges=[{name: int(getattr(es[i], name)) for name in _EDGE_KEYS} for i in range(summary["n_edges"])])
+
+
+def execute_origin(elf: bytes, stdin=(), at=SNAP_EXIT, target=(DVT_ORIGIN_REG, 10), follow_addr=False, depth=DVT_ORIGIN_MAX_DEPTH,
+                   nodes=DVT_ORIGIN_MAX_NODES, edges=DVT_ORIGIN_MAX_EDGES, max_cycles=0, log_shard=21):
+    """Host-only origin slice (dvt_execute_origin): the guest runs in shards of 2^log_shard cycles; where the value `target`
+    (origin_reg() / origin_word()) holds before the record at `at` = (shard, row) comes from, SNAP_EXIT: after the last record
+    (of a guest that traps: at the trap).  Returns (rc, report dict as execute() gives it, dict(summary, nodes, edges) as
+    Prover.job_origin gives it or None, error text)."""
+    lib = load()
+    rep, err, bufs = Report(), C.c_char_p(), _bufs(stdin)
+    rc, got = _origin(lambda *io: lib.dvt_execute_origin(elf, len(elf), bufs, len(stdin), max_cycles, log_shard, *io, C.byref(rep), C.byref(err)),
+                      at, target, follow_addr, depth, nodes, edges)
+    return rc, dict(cycles=rep.cycles, exit_code=rep.exit_code, halted=bool(rep.halted), unprovable=bool(rep.unprovable)), got, _take_str(lib, err)
 
 
 def exec_rate(elf: bytes, stdin=(), log_shard=21, trace=False) -> float:
@@ -1370,6 +1439,23 @@ class Prover:
         out = (C.c_double * 3)()
         self.check(self.lib.dvt_rv32_job_snapshot_times(self.h, out))
         return dict(reduce_ms=out[0], gather_ms=out[1], backtrace_ms=out[2])
+
+    def job_origin(self, pk, job, at, target, follow_addr=False, depth=DVT_ORIGIN_MAX_DEPTH, nodes=DVT_ORIGIN_MAX_NODES, edges=DVT_ORIGIN_MAX_EDGES):
+        """Where the value of `target` (origin_reg() / origin_word()) before the record at `at` = (shard, row) of a prepared job
+        comes from (SNAP_EXIT: after the last record): the backward data-flow slice over the cycle records the job holds on the
+        GPU (dvt_rv32_job_origin), dict(summary, nodes, edges).  A node is one record (a dict of the fields of dvt_origin_node), in
+        discovery order; edges[0] is the root, the input edges of node i are edges[first_edge : first_edge + n_edges]; an edge's
+        `to` is its producer's node or DVT_ORIGIN_NONE with INITIAL / CUT in its flags.  follow_addr: also follow the address
+        registers of loads and stores.  depth <= 64, nodes <= 1024, edges <= 8192."""
+        rc, got = _origin(lambda *io: self.lib.dvt_rv32_job_origin(self.h, pk, job, *io), at, target, follow_addr, depth, nodes, edges)
+        self.check(rc)
+        return got
+
+    def job_origin_times(self):
+        """of the last job_origin: dict(reduce_ms, gather_ms (stream events summed over members, levels and passes), host_ms)"""
+        out = (C.c_double * 3)()
+        self.check(self.lib.dvt_rv32_job_origin_times(self.h, out))
+        return dict(reduce_ms=out[0], gather_ms=out[1], host_ms=out[2])
 
     def job_calltree_times(self):
         """milliseconds of the last job_calltree: dict(summary_ms, merge_ms, emit_ms)"""

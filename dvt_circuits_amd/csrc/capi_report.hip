@@ -1,7 +1,7 @@
 // The record reports of the C ABI (include/dvt_prover.h): what reads the cycle records a prepared job holds in HBM instead of its
 // trace rows.  The execution report (profile.h), the call-tree report (calltree.h) and the memory report (memreport.h) count
 // over them; the watchpoint search (watch.h) returns the ones that match; the snapshot (snapshot.h) reduces them to the state of
-// the machine at one position.  Each has a job entry point (dvt_rv32_job_*), which runs on lane 0 of every member that holds
+// the machine at one position; the origin search (origin.h) follows one value back through them.  Each has a job entry point (dvt_rv32_job_*), which runs on lane 0 of every member that holds
 // shards, and a host-only one (dvt_execute_*) with the same rule over the executor's records (execute_traced).
 #include <algorithm>
 #include <type_traits>
@@ -9,6 +9,7 @@
 #include "calltree.h"
 #include "capi_job.h"
 #include "memreport.h"
+#include "origin.h"
 #include "profile.h"
 #include "snapshot.h"
 #include "watch.h"
@@ -755,6 +756,181 @@ static int job_snapshot(dvt_prover *p, const dvt_pk *pk, dvt_job *j, uint32_t sh
     return DVT_OK;
 }
 
+// ------------------------------------------------------------------ origins (dvt_rv32_job_origin)
+// origin::Search runs the rule on the host and asks its questions level by level.  A level is answered in chunks of
+// DVT_ORIGIN_PASS_QUESTIONS sorted questions: every member that holds shards before the chunk's largest position runs the reduce
+// pass over them on lane 0's stream (one launch per such shard, over its records before that position) into its own winners;
+// the host merges the members' winners with max and asks the member that holds each winner's shard for the record (gather, one
+// fetch per distinct position of the level).
+namespace {
+struct OriginMember {
+    StageBuf base;
+    unsigned long long *d_win = nullptr, *d_bad = nullptr, *d_qpos = nullptr;   // [PASS_Q], [1], [PASS_Q]
+    uint32_t *d_qtarget = nullptr;                                               // [PASS_Q]
+    OriginFetch *d_items = nullptr;                                              // [MAX_EDGES]
+    rv32::CycleRec *d_recs = nullptr;                                            // [MAX_EDGES]
+    const uint32_t *d_statics = nullptr;
+    std::vector<OriginFetch> fetch;
+    std::vector<unsigned long long> fetch_pos;
+    std::vector<rv32::CycleRec> got;
+    EventSpan t_reduce, t_gather;
+    explicit OriginMember(DevPool &pool) : base{pool} {}
+};
+}  // namespace
+
+static int job_origin(dvt_prover *p, const dvt_pk *pk, dvt_job *j, uint32_t shard, uint32_t row, uint32_t what, uint32_t target, uint32_t flags,
+                      uint32_t max_depth, dvt_origin_node *nodes, size_t cap_nodes, dvt_origin_edge *edges, size_t cap_edges, dvt_origin_summary *summary) {
+    if (int rc = same_members(p, pk, j)) return rc;
+    if (int rc = whole_execution(p, j, "origin of a value")) return rc;
+    const auto t0 = Clock::now();
+    const rv32::Program &prog = pk->prog;
+    constexpr size_t PQ = origin::PASS_Q;
+    MemberRun<OriginMember> run(p);   // (declared first: however the call ends, member 0's device is current again)
+    const std::vector<Held> held = held_in_order(j);
+    std::vector<uint64_t> shard_n(held.size());
+    uint64_t cycles = 0, position = 0;
+    for (const Held &h : held) {
+        const ShardJob &s = *h.s;
+        if (s.n_recs > 0xffffffffull) return fail(p, DVT_ERR_INPUT, "shard %zu has %zu records", h.pos, s.n_recs);
+        shard_n[h.pos] = s.n_recs;
+        cycles += s.n_recs;
+        position += s.index < shard ? s.n_recs : s.index == shard ? std::min<uint64_t>(s.n_recs, row) : 0;
+    }
+    const watch::Statics statics(prog);
+    const watch::Shapes shapes = watch::shapes();
+    const size_t n = statics.n();
+    // a member's buffer: win | bad | q_pos | fetched records | fetch items | q_target | the static words
+    const size_t bytes = PQ * 8 + 8 + PQ * 8 + 8 + origin::MAX_EDGES * (sizeof(rv32::CycleRec) + sizeof(OriginFetch)) + PQ * 4 + statics.bytes();
+    auto buffers = [&](const Lane &c, OriginMember &om) {
+        if (om.base.ptr) return DVT_OK;
+        Engine &e = c.eng;
+        HIP_TRY(c.err, e.pool.alloc_bytes(&om.base.ptr, bytes));
+        om.d_win = static_cast<unsigned long long *>(om.base.ptr);
+        om.d_bad = om.d_win + PQ;
+        om.d_qpos = om.d_bad + 2;                                                  // (the records behind stay 16-byte aligned)
+        om.d_recs = reinterpret_cast<rv32::CycleRec *>(om.d_qpos + PQ);
+        om.d_items = reinterpret_cast<OriginFetch *>(om.d_recs + origin::MAX_EDGES);
+        om.d_qtarget = reinterpret_cast<uint32_t *>(om.d_items + origin::MAX_EDGES);
+        uint32_t *d_stat = om.d_qtarget + PQ;
+        om.d_statics = d_stat;
+        HIP_TRY(c.err, hipMemcpyAsync(d_stat, statics.words.data(), statics.bytes(), hipMemcpyHostToDevice, e.stream));
+        return DVT_OK;
+    };
+
+    double ms[2] = {0, 0};
+    uint64_t bad = 0;
+    uint32_t passes = 0;
+    int rc_answer = DVT_OK;
+    auto answer = [&](const std::vector<origin::Question> &qs, std::vector<origin::Found> *found) {
+        std::vector<uint32_t> order(qs.size());
+        for (size_t i = 0; i < order.size(); i++) order[i] = (uint32_t)i;
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return origin::sorts_before(qs[x], qs[y]); });
+        std::vector<unsigned long long> win(qs.size(), 0), one(PQ + 1), q_pos(PQ);
+        std::vector<uint32_t> q_target(PQ);
+        // ---- reduce: one pass per chunk of the sorted questions
+        for (size_t at = 0; at < order.size(); at += PQ) {
+            const size_t n_q = std::min(PQ, order.size() - at);
+            OriginArgs args{};
+            args.sh = shapes;
+            args.n_instr = (uint32_t)n; args.text_base = prog.text_base; args.n_q = (uint32_t)n_q;
+            uint32_t n_regs = 0;
+            for (size_t i = 0; i < n_q; i++) {
+                const origin::Question &q = qs[order[at + i]];
+                q_target[i] = q.target; q_pos[i] = q.Q;
+                args.max_q = std::max(args.max_q, q.Q);
+                if (q.what == DVT_ORIGIN_REG) n_regs++;
+            }
+            for (uint32_t k = 0; k <= 32; k++) {   // the first register question with a register >= k (they are sorted)
+                uint32_t f = 0;
+                while (f < n_regs && q_target[f] < k) f++;
+                args.reg_off[k] = f;
+            }
+            const uint32_t q_shard = (uint32_t)(args.max_q >> 32), q_row = (uint32_t)args.max_q;
+            auto take = [&](const ShardJob &s) { return s.index < q_shard ? s.n_recs : s.index == q_shard ? std::min<size_t>(s.n_recs, q_row) : 0; };
+            passes++;
+            rc_answer = for_members(p, [&](size_t m, const Lane &c) {
+                Engine &e = c.eng;
+                OriginMember &om = run[m];
+                JobPart &part = j->parts[m];
+                bool any = false;
+                for (auto &s : part.shards) any = any || take(s);
+                if (!any) return DVT_OK;
+                if (int rc = buffers(c, om)) return rc;
+                HIP_TRY(c.err, hipMemsetAsync(om.d_win, 0, (PQ + 1) * 8, e.stream));
+                HIP_TRY(c.err, hipMemcpyAsync(om.d_qpos, q_pos.data(), n_q * 8, hipMemcpyHostToDevice, e.stream));
+                HIP_TRY(c.err, hipMemcpyAsync(om.d_qtarget, q_target.data(), n_q * 4, hipMemcpyHostToDevice, e.stream));
+                OriginArgs a = args;
+                a.statics = om.d_statics; a.offs = om.d_statics + n; a.q_target = om.d_qtarget; a.q_pos = om.d_qpos;
+                HIP_TRY(c.err, om.t_reduce.begin(e.stream));
+                for (auto &s : part.shards) {
+                    a.shard = s.index;
+                    HIP_TRY(c.err, launch_origin_reduce(e.stream, s.d_recs, take(s), a, om.d_win, om.d_bad));
+                }
+                HIP_TRY(c.err, om.t_reduce.end(e.stream));
+                if (!e.download(one.data(), om.d_win, (PQ + 1) * 8)) return engine_fail(c.err, e);
+                ms[0] += om.t_reduce.ms();
+                bad += one[PQ];
+                for (size_t i = 0; i < n_q; i++) win[order[at + i]] = std::max(win[order[at + i]], one[i]);
+                return DVT_OK;
+            });
+            if (rc_answer) return false;
+        }
+        if (bad) return true;   // (the call fails below: no record is read again)
+        // ---- gather: every distinct winner from the member that holds its shard
+        std::map<unsigned long long, std::pair<size_t, size_t>> where;   // position -> (member, index among its fetches)
+        for (size_t m = 0; m < n_members(p); m++) { run[m].fetch.clear(); run[m].fetch_pos.clear(); }
+        for (size_t i = 0; i < qs.size(); i++) {
+            if (!win[i] || where.count(win[i])) continue;
+            const uint32_t sh = (uint32_t)(win[i] >> 32), rw = (uint32_t)win[i];
+            if (!sh || sh > held.size() || rw >= held[sh - 1].s->n_recs) {
+                rc_answer = fail(p, DVT_ERR_DEVICE, "a winner of the reduce pass lies in no shard of the job");
+                return false;
+            }
+            const Held &h = held[sh - 1];
+            where[win[i]] = {h.m, run[h.m].fetch.size()};
+            run[h.m].fetch.push_back(OriginFetch{h.s->d_recs, (uint32_t)h.s->n_recs, rw});
+        }
+        rc_answer = for_members(p, [&](size_t m, const Lane &c) {
+            Engine &e = c.eng;
+            OriginMember &om = run[m];
+            if (om.fetch.empty()) return DVT_OK;
+            if (om.fetch.size() > origin::MAX_EDGES) return fail(c.err, DVT_ERR_DEVICE, "more winners than questions");
+            if (int rc = buffers(c, om)) return rc;
+            HIP_TRY(c.err, hipMemcpyAsync(om.d_items, om.fetch.data(), om.fetch.size() * sizeof(OriginFetch), hipMemcpyHostToDevice, e.stream));
+            HIP_TRY(c.err, om.t_gather.begin(e.stream));
+            HIP_TRY(c.err, launch_origin_gather(e.stream, om.d_items, (uint32_t)om.fetch.size(), om.d_recs));
+            HIP_TRY(c.err, om.t_gather.end(e.stream));
+            om.got.resize(om.fetch.size());
+            if (!e.download(om.got.data(), om.d_recs, om.got.size() * sizeof(rv32::CycleRec))) return engine_fail(c.err, e);
+            ms[1] += om.t_gather.ms();
+            return DVT_OK;
+        });
+        if (rc_answer) return false;
+        for (size_t i = 0; i < qs.size(); i++)
+            if (win[i]) {
+                const auto &w = where[win[i]];
+                (*found)[i] = origin::Found{win[i], run[w.first].got[w.second]};
+            }
+        return true;
+    };
+
+    origin::Search search(prog, statics, shapes, watch::position(shard, row), what, target, flags, max_depth, nodes, cap_nodes, edges, cap_edges);
+    const int rc = search.run(answer);
+    if (rc == 1) return rc_answer;
+    if (bad) return fail(p, DVT_ERR_INPUT, "%llu %s", (unsigned long long)bad, BAD_RECORD);
+    if (rc) return fail(p, DVT_ERR_DEVICE, "%s", search.why.c_str());
+    dvt_origin_summary s = search.s;
+    s.passes = passes;
+    s.position = position; s.cycles = cycles;
+    snap::locate(shard_n, position, &s.shard, &s.row);
+    s.shards_total = (uint32_t)held.size();
+    const double total = ms_since(t0);
+    s.ms = (float)total;
+    p->origin_ms[0] = ms[0]; p->origin_ms[1] = ms[1]; p->origin_ms[2] = std::max(0.0, total - ms[0] - ms[1]);
+    *summary = s;
+    return DVT_OK;
+}
+
 // The host-only reports (no GPU is touched): the guest in trace mode, where an instruction without a chip is recorded instead
 // of trapping, 2^log_shard (2^21) cycles per shard and one shard's records in memory at a time.  begin(prog) once the ELF is loaded;
 // shard(prog, recs, n, last_succ) per shard in execution order; end(prog, ms) after the last, and a text it returns fails the
@@ -991,6 +1167,50 @@ int dvt_execute_snapshot(const uint8_t *elf, size_t elf_len, const dvt_buf *stdi
             return t->bad ? BAD_RECORD : nullptr;
         },
         log_shard_size ? log_shard_size : 21);
+}
+
+// ---- origins (origin.h)
+int dvt_rv32_job_origin(dvt_prover *p, const dvt_pk *pk, dvt_job *job, uint32_t shard, uint32_t row, uint32_t what, uint32_t target, uint32_t flags,
+                        uint32_t max_depth, dvt_origin_node *nodes, size_t cap_nodes, dvt_origin_edge *edges, size_t cap_edges,
+                        dvt_origin_summary *summary) {
+    if (!p || !pk || !job || !summary) return fail(p, DVT_ERR_INPUT, "null argument");
+    std::string text;
+    if (const char *why = origin::input_error(what, target, flags, max_depth, nodes, cap_nodes, edges, cap_edges, &text)) return fail(p, DVT_ERR_INPUT, "%s", why);
+    if (int rc = rv32_key(p, pk)) return rc;
+    Guard g(p); if (g.rc) return g.rc;
+    return job_origin(p, pk, job, shard, row, what, target, flags, max_depth, nodes, cap_nodes, edges, cap_edges, summary);
+}
+
+int dvt_rv32_job_origin_times(dvt_prover *p, double out[3]) { return times_of(p, &dvt_prover::origin_ms, out); }
+
+// host-only: the same search (origin::Search) over the records origin::Keeper keeps of execute_traced's shards
+int dvt_execute_origin(const uint8_t *elf, size_t elf_len, const dvt_buf *stdin_bufs, size_t nbuf, uint64_t max_cycles, uint32_t log_shard_size,
+                       uint32_t shard, uint32_t row, uint32_t what, uint32_t target, uint32_t flags, uint32_t max_depth, dvt_origin_node *nodes,
+                       size_t cap_nodes, dvt_origin_edge *edges, size_t cap_edges, dvt_origin_summary *summary, dvt_report *report, char **err_text) {
+    if (err_text) *err_text = nullptr;
+    if (!elf || (nbuf && !stdin_bufs) || !summary) return DVT_ERR_INPUT;
+    std::string text;
+    if (execute_input_error(log_shard_size, origin::input_error(what, target, flags, max_depth, nodes, cap_nodes, edges, cap_edges, &text), &text, err_text))
+        return DVT_ERR_INPUT;
+    std::unique_ptr<origin::Keeper> k;
+    bool bad = false;
+    const int rc = execute_traced(
+        elf, elf_len, stdin_bufs, nbuf, max_cycles, report, err_text, [&](const rv32::Program &prog) { k.reset(new origin::Keeper(prog, shard, row)); },
+        [&](const rv32::Program &prog, const rv32::CycleRec *recs, size_t n, uint32_t) { k->scan(prog, recs, n, (uint32_t)k->shard_n.size() + 1); },
+        [&](const rv32::Program &prog, double ms) -> const char * {
+            if (k->too_many)
+                return "more than 2^24 cycle records before the position: prepare the job and ask dvt_rv32_job_origin, which reads them on the GPU";
+            if (k->bad) { bad = true; return BAD_RECORD; }
+            const auto t1 = Clock::now();
+            origin::Search search(prog, k->wst, k->sh, k->P, what, target, flags, max_depth, nodes, cap_nodes, edges, cap_edges);
+            search.run([&](const std::vector<origin::Question> &qs, std::vector<origin::Found> *found) { return k->answer(prog, qs, found); });
+            k->place(&search.s);
+            search.s.ms = (float)(ms + ms_since(t1));
+            *summary = search.s;
+            return nullptr;
+        },
+        log_shard_size ? log_shard_size : 21);
+    return bad && rc == DVT_ERR_UNSUPPORTED ? DVT_ERR_INPUT : rc;
 }
 
 }  // extern "C"

@@ -1,11 +1,11 @@
 // dvt_prover_host — the reference's CLI verbs (src/main.rs:58-106) over the C ABI.
 //
 //   dvt_prover_host prove   --type T -i INPUT.json [-o PROOF] [--elf GUEST.elf] [--devices D0,D1,...] [--compact]
-//   dvt_prover_host execute --type T -i INPUT.json [--show-report] [--show-calls] [--show-memory] [--watch SPEC ...] [--snapshot S:R|exit [--dump ADDR+LEN ...] [--frames N]] [--elf GUEST.elf]
+//   dvt_prover_host execute --type T -i INPUT.json [--show-report] [--show-calls] [--show-memory] [--watch SPEC ...] [--snapshot S:R|exit [--dump ADDR+LEN ...] [--frames N]] [--origin SPEC [--depth N] [--nodes N] [--follow-addr]] [--elf GUEST.elf]
 //   dvt_prover_host verify  --type T -i PROOF [--elf GUEST.elf]
 //   dvt_prover_host compact --type T -i PROOF [-o PROOF] [--elf GUEST.elf]     (shared Merkle paths sent once: dvt_proof_compact)
 //   dvt_prover_host expand  --type T -i PROOF [-o PROOF] [--elf GUEST.elf]     (the inverse; verify takes either form)
-//   dvt_prover_host check   --type T -i INPUT.json [--show-report] [--show-calls] [--show-memory] [--watch SPEC ...] [--snapshot S:R|exit [--dump ADDR+LEN ...] [--frames N]] [--elf GUEST.elf] [--devices D0,D1,...]
+//   dvt_prover_host check   --type T -i INPUT.json [--show-report] [--show-calls] [--show-memory] [--watch SPEC ...] [--snapshot S:R|exit [--dump ADDR+LEN ...] [--frames N]] [--origin SPEC [--depth N] [--nodes N] [--follow-addr]] [--elf GUEST.elf] [--devices D0,D1,...]
 //
 // T = bad-share | finalization | bad-partial-key | bad-encrypted-share (clap names of CircuitType, :36-42).
 // The reference embeds the four guest ELFs at build time (include_elf!, :115-118); they cannot be built in
@@ -41,6 +41,13 @@
 // position=N cycles=N shard=S row=R pc=0xX depth=N frames=N unmatched_returns=N words=N no_value=N initial=N untouched=N", four
 // lines "regs NAME=0xX ..." with x1..x31 by ABI name, one line per frame, innermost first: "#K 0xFN from 0xCALL ra=0xX opened
 // S:R", and per dumped range lines "0xADDR: W W W W" of up to four words, ?? for a word the records do not hold (NO_VALUE).
+// --origin S:R|exit, then :reg:NAME or :word:ADDR: after those, where the value that register or word holds before the position
+// comes from (dvt_execute_origin on the host, dvt_rv32_job_origin on the GPU; csrc/origin.h).  --depth N (default 64) and --nodes N
+// (default 1024) bound the slice, --follow-addr also follows the address registers of loads and stores.  One line "origin:
+// position=N cycles=N shard=S row=R nodes=N edges=N depth=N cut=N unexpanded=N initial=N no_value=N questions=N levels=N
+// passes=N", one line per node in discovery order: "node K depth=D at=S:R pc=0xX kind=op|load|store|call|syscall rd=0xX rs1=0xX
+// rs2=0xX addr=0xX before=0xX after=0xX edges=FIRST+N flags=0xX", and one per edge, edge 0 the root: "edge K from=I to=J
+// role=root|addr|rs1|rs2|mem target=0xX value=0xX flags=0xX src=S:R" (-1: no node).
 // get-schema / validate-schema / node are product UI outside the accelerated path and are not provided.
 #include <algorithm>
 #include <cstdio>
@@ -268,8 +275,54 @@ template <class Call> static int print_snapshot(const std::vector<dvt_snap_range
     return 0;
 }
 
+// an --origin spec: POSITION:reg:NAME or POSITION:word:ADDR, POSITION = S:R or exit
+struct OriginSpec { uint32_t shard, row, what, target; };
+static bool parse_origin(const std::string &t, OriginSpec *out) {
+    static const char *abi[32] = {"zero", "ra", "sp", "gp", "tp", "t0", "t1", "t2", "s0", "s1", "a0", "a1", "a2", "a3", "a4", "a5",
+                                  "a6", "a7", "s2", "s3", "s4", "s5", "s6", "s7", "s8", "s9", "s10", "s11", "t3", "t4", "t5", "t6"};
+    size_t at = t.find(":reg:");
+    const bool reg = at != std::string::npos;
+    if (!reg) at = t.find(":word:");
+    if (at == std::string::npos || !parse_position(t.substr(0, at), &out->shard, &out->row)) return false;
+    const std::string name = t.substr(at + (reg ? 5 : 6));
+    if (reg) {
+        out->what = DVT_ORIGIN_REG; out->target = 0;
+        for (uint32_t r = 1; r < 32; r++)
+            if (name == abi[r] || name == "x" + std::to_string(r)) out->target = r;
+        return out->target != 0;
+    }
+    char *end = nullptr;
+    const unsigned long long a = strtoull(name.c_str(), &end, 0);
+    out->what = DVT_ORIGIN_WORD; out->target = (uint32_t)a & ~3u;
+    return !name.empty() && !*end && a <= 0xffffffffull;
+}
+
+// the origin block (call: dvt_execute_origin or dvt_rv32_job_origin with everything else bound)
+template <class Call> static int print_origin(size_t cap_nodes, Call call) {
+    static const char *kinds[] = {"?", "op", "load", "store", "call", "syscall"}, *roles[] = {"root", "addr", "rs1", "rs2", "mem"};
+    std::vector<dvt_origin_node> nodes(std::max<size_t>(cap_nodes, 1));
+    std::vector<dvt_origin_edge> edges(DVT_ORIGIN_MAX_EDGES);
+    dvt_origin_summary s{};
+    if (int rc = call(nodes.data(), cap_nodes, edges.data(), edges.size(), &s)) return rc;
+    printf("origin: position=%llu cycles=%llu shard=%u row=%u nodes=%u edges=%u depth=%u cut=%u unexpanded=%u initial=%u no_value=%u questions=%u levels=%u passes=%u\n",
+           (unsigned long long)s.position, (unsigned long long)s.cycles, s.shard, s.row, s.n_nodes, s.n_edges, s.depth, s.cut, s.unexpanded, s.initial,
+           s.no_value, s.questions, s.levels, s.passes);
+    for (uint32_t i = 0; i < s.n_nodes; i++) {
+        const dvt_origin_node &n = nodes[i];
+        printf("node %u depth=%u at=%u:%u pc=0x%08x kind=%s rd=0x%08x rs1=0x%08x rs2=0x%08x addr=0x%08x before=0x%08x after=0x%08x edges=%u+%u flags=0x%x\n", i,
+               n.depth, n.shard, n.row, n.pc, n.kind < 6 ? kinds[n.kind] : "?", n.rd_value, n.rs1, n.rs2, n.addr, n.before, n.after, n.first_edge, n.n_edges,
+               n.flags);
+    }
+    for (uint32_t i = 0; i < s.n_edges; i++) {
+        const dvt_origin_edge &e = edges[i];
+        printf("edge %u from=%d to=%d role=%s target=0x%x value=0x%08x flags=0x%x src=%u:%u\n", i, (int)e.from, (int)e.to, e.role < 5 ? roles[e.role] : "?",
+               e.target, e.value, e.flags, e.src_shard, e.src_row);
+    }
+    return 0;
+}
+
 int main(int argc, char **argv) {
-    if (argc < 2) return die("usage: dvt_prover_host prove|execute|verify|check|compact|expand --type T -i FILE [-o FILE] [--show-report] [--show-calls] [--show-memory] [--watch SPEC] [--snapshot S:R|exit] [--dump ADDR+LEN] [--frames N] [--compact] [--keep-trees] [--elf FILE] [--devices D0,D1,...] [--device D]");
+    if (argc < 2) return die("usage: dvt_prover_host prove|execute|verify|check|compact|expand --type T -i FILE [-o FILE] [--show-report] [--show-calls] [--show-memory] [--watch SPEC] [--snapshot S:R|exit] [--dump ADDR+LEN] [--frames N] [--origin SPEC] [--depth N] [--nodes N] [--follow-addr] [--compact] [--keep-trees] [--elf FILE] [--devices D0,D1,...] [--device D]");
     const std::string verb = argv[1];
     std::string type, input, output, elf_path, schema_path, devices, verify_device;
     bool show_report = false, show_calls = false, show_memory = false, auth = false, compact = false, keep_trees = false;
@@ -279,6 +332,10 @@ int main(int argc, char **argv) {
     uint32_t snap_shard = 0, snap_row = 0;
     size_t snap_frames = 16;
     std::vector<dvt_snap_range> snap_ranges;
+    bool origin = false;
+    OriginSpec origin_spec{};
+    uint32_t origin_depth = DVT_ORIGIN_MAX_DEPTH, origin_flags = 0;
+    size_t origin_nodes = DVT_ORIGIN_MAX_NODES;
     for (int i = 2; i < argc; i++) {
         std::string a = argv[i], inline_val;
         bool has_inline = false;
@@ -312,6 +369,14 @@ int main(int argc, char **argv) {
             if (!parse_dump(t, &snap_ranges.back())) return die("no range (ADDR+LEN): " + t);
         }
         else if (a == "--frames") snap_frames = (size_t)strtoull(next().c_str(), nullptr, 0);
+        else if (a == "--origin") {
+            const std::string t = next();
+            if (!parse_origin(t, &origin_spec)) return die("no origin (S:R|exit, then :reg:NAME or :word:ADDR): " + t);
+            origin = true;
+        }
+        else if (a == "--depth") origin_depth = (uint32_t)strtoull(next().c_str(), nullptr, 0);
+        else if (a == "--nodes") origin_nodes = (size_t)strtoull(next().c_str(), nullptr, 0);
+        else if (a == "--follow-addr") origin_flags |= DVT_ORIGIN_FOLLOW_ADDR;
         else if (a == "--compact") compact = true;       // prove: shard proofs in the compact form ("compact_openings")
         else if (a == "--keep-trees") keep_trees = true;  // prove / check: shards that do not fit in HBM in full keep their main Merkle tree ("keep_phase1": 2)
         else if (a == "--auth-commitment") auth = true;  // the reference selects this at build time (cargo feature)
@@ -426,6 +491,14 @@ int main(int argc, char **argv) {
                 }))
                 return die(std::string("Verification failed: ") + (serr ? serr : "?"));
         }
+        if (origin) {
+            char *oerr = nullptr;
+            if (print_origin(origin_nodes, [&](dvt_origin_node *nodes, size_t cap_nodes, dvt_origin_edge *edges, size_t cap_edges, dvt_origin_summary *s) {
+                    return dvt_execute_origin(elf.data(), elf.size(), &buf, 1, 0, 0, origin_spec.shard, origin_spec.row, origin_spec.what, origin_spec.target,
+                                              origin_flags, origin_depth, nodes, cap_nodes, edges, cap_edges, s, nullptr, &oerr);
+                }))
+                return die(std::string("Verification failed: ") + (oerr ? oerr : "?"));
+        }
         return 0;
     }
 
@@ -494,6 +567,12 @@ int main(int argc, char **argv) {
                 return dvt_rv32_job_snapshot(p, pk, job, snap_shard, snap_row, r, n, regs, words, cap_words, frames, cap_frames, s);
             }))
             return die(std::string("Snapshot failed: ") + dvt_last_error(p));
+        if (origin &&
+            print_origin(origin_nodes, [&](dvt_origin_node *nodes, size_t cap_nodes, dvt_origin_edge *edges, size_t cap_edges, dvt_origin_summary *s) {
+                return dvt_rv32_job_origin(p, pk, job, origin_spec.shard, origin_spec.row, origin_spec.what, origin_spec.target, origin_flags, origin_depth,
+                                           nodes, cap_nodes, edges, cap_edges, s);
+            }))
+            return die(std::string("Origin failed: ") + dvt_last_error(p));
         dvt_job_free(p, job);
         dvt_pk_free(p, pk);
         dvt_prover_destroy(p);

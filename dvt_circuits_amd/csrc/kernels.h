@@ -191,4 +191,18 @@ struct SnapFetch;
 hipError_t launch_snapshot_reduce(hipStream_t st, const rv32::CycleRec *d_recs, size_t n_recs, const SnapArgs &a, const SnapTables &t);
 hipError_t launch_snapshot_gather(hipStream_t st, const SnapFetch *d_items, uint32_t n_items, const SnapArgs &a, void *d_out);
 
+// origin.hip
+// The passes of the origin search (origin.h).  reduce: over the first n_take records of one shard (the ones before the largest
+// position any question of the pass asks at), the latest writer of every question's target before the question's position, as
+// a position, into d_win [a.n_q] (zeroed by the caller: no position is 0); OriginArgs carries the sorted questions' device
+// arrays, the offsets of the register questions, the precompile shapes, the static words per instruction and the shard's
+// number; *d_bad_records (zeroed by the caller) counts the bad records among those taken.  gather: the record of every
+// OriginFetch, 12 words each, into d_out (rv32::CycleRec [n_items]; all ones for an item outside its shard).  The records are
+// only read.
+struct OriginArgs;
+struct OriginFetch;
+hipError_t launch_origin_reduce(hipStream_t st, const rv32::CycleRec *d_recs, size_t n_take, const OriginArgs &a, unsigned long long *d_win,
+                                unsigned long long *d_bad_records);
+hipError_t launch_origin_gather(hipStream_t st, const OriginFetch *d_items, uint32_t n_items, rv32::CycleRec *d_out);
+
 }  // namespace dvt

@@ -130,7 +130,8 @@ void dvt_free(void *ptr);
  * dvt_rv32_job_shard_kept_bytes, dvt_debug_keep_plan; 14: dvt_rv32_job_calltree,
  * dvt_rv32_job_calltree_times, dvt_execute_calltree; 15: dvt_rv32_job_memory, dvt_execute_memory;
  * 16: dvt_rv32_job_watch, dvt_execute_watch, dvt_rv32_job_watch_times; 17: dvt_rv32_job_snapshot,
- * dvt_rv32_job_snapshot_times, dvt_execute_snapshot; 18: dvt_rv32_debug_poke_cell) */
+ * dvt_rv32_job_snapshot_times, dvt_execute_snapshot; 18: dvt_rv32_debug_poke_cell; 19: dvt_rv32_job_origin, dvt_rv32_job_origin_times,
+ * dvt_execute_origin) */
 uint32_t dvt_abi_version(void);
 /* the handle's hipStream_t (for event timing by the caller) */
 void *dvt_stream(dvt_prover *p);
@@ -939,6 +940,69 @@ int dvt_execute_snapshot(const uint8_t *elf, size_t elf_len, const dvt_buf *stdi
                          uint32_t shard, uint32_t row, const dvt_snap_range *ranges, size_t n_ranges, dvt_snap_cell regs[32],
                          dvt_snap_cell *words, size_t cap_words, dvt_snap_frame *frames, size_t cap_frames, dvt_snap_summary *summary,
                          dvt_report *report, char **err_text);
+/* Origins of a prepared job: the backward data-flow slice of one value, from the cycle records the job holds (the records are
+ * only read, nothing is executed again, the job is left as found).  The call names a position (shard, row) as the snapshot does
+ * ((0xffffffff, 0xffffffff): the exit) and a target: what = DVT_ORIGIN_REG with target = k in 1..31 for the value x_k holds
+ * before the position, or DVT_ORIGIN_WORD with target = a 4-aligned address below the guest's address limit for the word before
+ * the position.  The rule is stated in csrc/origin.h:
+ *   question    (what, target, Q): the last record before position Q that WRITES the target.  A register: the last record whose
+ *               instruction has rd == k (the snapshot's rule: ECALL writes t0).  A word: the last store (sw / sh / sb) to it or
+ *               precompile call that writes it; loads are no writers.  Without such a record the target is INITIAL.
+ *   nodes       one per record of the slice, in discovery order (level by level): the fields of a watchpoint hit (shard, row, pc,
+ *               idx, rd_value, rs1, rs2 and, of a load or store, addr, before, after), kind = DVT_ORIGIN_OP / _LOAD / _STORE /
+ *               _CALL (an ECALL with a precompile shape) / _SYSCALL (any other ECALL), depth = its level, its input edges
+ *               edges[first_edge .. first_edge + n_edges), flags = DVT_ORIGIN_UNEXPANDED when its inputs were not followed
+ *               (depth == max_depth, or cap_edges was reached).
+ *   edges       edge 0 is the root: from = DVT_ORIGIN_NONE, role ROOT, the question (what, target, position).  The input edges
+ *               of a node depend on its record alone and ask at the node's own position, in this order: ADDR (loads and
+ *               stores: register rs1; only with DVT_ORIGIN_FOLLOW_ADDR), RS1 (every other instruction that reads rs1, ECALL
+ *               excepted), RS2 (every instruction that reads rs2, ECALL excepted; of a store the data), MEM (a load: the word
+ *               it reads; sb / sh: the word whose other bytes they keep; a _CALL: one edge per word the call reads, array 0
+ *               first).  No edge names x0.  role REG-like edges carry target = the register and value = the operand the record
+ *               holds; MEM edges target = the word and value = the word before the access (of a _CALL: 0 and NO_VALUE).  The
+ *               root's value is the writer's rd_value (REG), the store's `after` (WORD), NO_VALUE when a call wrote the word,
+ *               the image's word with INITIAL | IMAGE or INITIAL | NO_VALUE without a writer.  to = the node of the writer,
+ *               or DVT_ORIGIN_NONE with INITIAL (no writer; IMAGE: a word of the program image) or CUT (cap_nodes was
+ *               reached); (src_shard, src_row) = the writer's position whenever there is one.
+ *   summary     n_nodes, n_edges, depth = the deepest node's, the edges with CUT, INITIAL and NO_VALUE, the UNEXPANDED nodes,
+ *               questions asked, levels answered, device passes (ceil(questions of the level / DVT_ORIGIN_PASS_QUESTIONS) per
+ *               level; 0 on the host path), position / cycles / shard / row as the snapshot's summary.
+ * Limits: the values of words a call read or wrote are not in the records; a hinted word nothing wrote is INITIAL; data
+ * dependence only.  DVT_ERR_INPUT: what / target out of range, a flag other than FOLLOW_ADDR, cap_nodes, cap_edges or max_depth
+ * above the limits, cap_edges 0, null arrays, a bad cycle record before the position.  DVT_ERR_UNSUPPORTED: a prepare_part job
+ * that does not hold every shard of its execution.  Handles with several members work. */
+#define DVT_ORIGIN_MAX_NODES 1024
+#define DVT_ORIGIN_MAX_EDGES 8192
+#define DVT_ORIGIN_MAX_DEPTH 64
+#define DVT_ORIGIN_PASS_QUESTIONS 256   /* questions one device pass answers */
+#define DVT_ORIGIN_SPAN 4096            /* records one workgroup of the device pass reduces */
+#define DVT_ORIGIN_NONE 0xffffffffu
+enum { DVT_ORIGIN_REG = 1, DVT_ORIGIN_WORD = 2 };                                                       /* what */
+enum { DVT_ORIGIN_FOLLOW_ADDR = 1 };                                                                    /* flags of a call */
+enum { DVT_ORIGIN_OP = 1, DVT_ORIGIN_LOAD = 2, DVT_ORIGIN_STORE = 3, DVT_ORIGIN_CALL = 4, DVT_ORIGIN_SYSCALL = 5 };   /* node kinds */
+enum { DVT_ORIGIN_ROOT = 0, DVT_ORIGIN_ADDR = 1, DVT_ORIGIN_RS1 = 2, DVT_ORIGIN_RS2 = 3, DVT_ORIGIN_MEM = 4 };         /* edge roles */
+enum { DVT_ORIGIN_INITIAL = 1, DVT_ORIGIN_IMAGE = 2, DVT_ORIGIN_NO_VALUE = 4, DVT_ORIGIN_CUT = 8, DVT_ORIGIN_UNEXPANDED = 16 };   /* flags of edges and nodes */
+typedef struct { uint32_t shard, row, pc, idx, kind, depth, first_edge, n_edges, flags, rd_value, rs1, rs2, addr, before, after, pad; } dvt_origin_node;
+typedef struct { uint32_t from, to, role, target, value, flags, src_shard, src_row; } dvt_origin_edge;
+typedef struct {
+    uint64_t position, cycles;
+    uint32_t n_nodes, n_edges, depth, cut, unexpanded, initial, no_value, questions, levels, passes, shard, row, shards_total, span;
+    float ms;          /* wall clock of the call after the entry guard */
+} dvt_origin_summary;
+int dvt_rv32_job_origin(dvt_prover *p, const dvt_pk *pk, dvt_job *job, uint32_t shard, uint32_t row, uint32_t what, uint32_t target, uint32_t flags,
+                        uint32_t max_depth, dvt_origin_node *nodes, size_t cap_nodes, dvt_origin_edge *edges, size_t cap_edges,
+                        dvt_origin_summary *summary);
+/* milliseconds of the last dvt_rv32_job_origin: the reduce launches and the gather launches by events on the members' streams,
+ * summed over members, levels and passes; the host's share (the wall clock of the call less those two) */
+int dvt_rv32_job_origin_times(dvt_prover *p, double out[3]);
+/* The same slice on the host alone (no GPU is touched), the guest run in shards of 2^log_shard_size cycles (0: 21; 4..22) as
+ * dvt_execute_snapshot runs it.  The records of the shards up to the position are kept, 48 bytes per cycle: past 2^24 of them the
+ * call fails with DVT_ERR_UNSUPPORTED (dvt_rv32_job_origin is the way for such executions).  The questions of a level are answered
+ * by one backward scan.  Return codes, *report and *err_text as dvt_execute gives them; the outputs are filled for whatever
+ * retired, also when the guest fails: at (0xffffffff, 0xffffffff) a guest that traps is asked at its trap. */
+int dvt_execute_origin(const uint8_t *elf, size_t elf_len, const dvt_buf *stdin_bufs, size_t nbuf, uint64_t max_cycles, uint32_t log_shard_size,
+                       uint32_t shard, uint32_t row, uint32_t what, uint32_t target, uint32_t flags, uint32_t max_depth, dvt_origin_node *nodes,
+                       size_t cap_nodes, dvt_origin_edge *edges, size_t cap_edges, dvt_origin_summary *summary, dvt_report *report, char **err_text);
 /* test hook: run K0 on one shard of a prepared job and return the device-generated main traces
  * (canonical); blob layout as dvt_rv32_debug_traces with prep_width = 0. */
 int dvt_rv32_debug_device_traces(dvt_prover *p, const dvt_pk *pk, dvt_job *job, size_t shard, uint32_t **blob,
