@@ -199,6 +199,11 @@ def load():
     lib.dvt_rv32_job_origin.argtypes = [vp, vp, vp] + origin_io
     lib.dvt_rv32_job_origin_times.argtypes = [vp, C.POINTER(C.c_double)]
     lib.dvt_execute_origin.argtypes = [C.c_char_p, sz, C.POINTER(Buf), sz, u64, u32] + origin_io + [C.POINTER(Report), C.POINTER(C.c_char_p)]
+    diverge_io = [DivergePos, DivergePos, u64, u32, u32, sz, C.POINTER(DivergePair), C.POINTER(DivergePair), C.POINTER(DivergeReg), C.POINTER(DivergeSummary)]
+    lib.dvt_rv32_job_diverge.argtypes = [vp, vp, vp, vp] + diverge_io
+    lib.dvt_rv32_job_diverge_times.argtypes = [vp, C.POINTER(C.c_double)]
+    lib.dvt_execute_diverge.argtypes = [C.c_char_p, sz, C.c_char_p, sz, C.c_char_p, sz, u64, u32] + diverge_io + \
+                                       [C.POINTER(Report), C.POINTER(Report), C.POINTER(C.c_char_p)]
     lib.dvt_stdin_from_json.argtypes = [C.c_char_p, C.c_char_p, sz, C.c_int, C.POINTER(u8p), C.POINTER(sz), C.POINTER(C.c_char_p)]
     _lib = lib
     return lib
@@ -736,6 +741,85 @@ def execute_origin(elf: bytes, stdin=(), at=SNAP_EXIT, target=(DVT_ORIGIN_REG, 1
     rc, got = _origin(lambda *io: lib.dvt_execute_origin(elf, len(elf), bufs, len(stdin), max_cycles, log_shard, *io, C.byref(rep), C.byref(err)),
                       at, target, follow_addr, depth, nodes, edges)
     return rc, dict(cycles=rep.cycles, exit_code=rep.exit_code, halted=bool(rep.halted), unprovable=bool(rep.unprovable)), got, _take_str(lib, err)
+
+
+# ---- divergence (csrc/diverge.h)
+DVT_DIVERGE_SPAN, DVT_DIVERGE_MAX_KEEP, DVT_DIVERGE_MAX_WINDOW, DVT_DIVERGE_DEFAULT_WINDOW = 4096, 64, 16384, 4096
+DVT_DIVERGE_BATCH_PAIRS = 1 << 20   # the header's default; a library may be built with another: summary["batch_pairs"] is the built value
+DVT_DIV_NONE, DVT_DIVERGE_NO_REJOIN = 0xFFFFFFFFFFFFFFFF, 0xFFFFFFFF
+DVT_DIV_RD, DVT_DIV_RS1, DVT_DIV_RS2, DVT_DIV_MEM = 1, 2, 4, 8
+DVT_DIVERGE_REJOIN = 1
+DVT_DIV_SPLIT, DVT_DIV_BAD, DVT_DIV_END_BOTH, DVT_DIV_END_A, DVT_DIV_END_B, DVT_DIV_LIMIT = 1, 2, 3, 4, 5, 6
+DIV_REASONS = {1: "split", 2: "bad", 3: "end_both", 4: "end_a", 5: "end_b", 6: "limit"}
+DIVERGE_ENTRY = (1, 0)   # the start of an execution
+
+
+class DivergePos(C.Structure):
+    _fields_ = [("shard", C.c_uint32), ("row", C.c_uint32)]
+
+
+class DivergeRec(C.Structure):
+    _fields_ = [(name, C.c_uint32) for name in ("valid", "pc", "idx", "a", "b", "c", "m_prev", "pad")]
+
+
+class DivergePair(C.Structure):
+    _fields_ = [("k", C.c_uint64)] + [(name, C.c_uint32) for name in ("shard_a", "row_a", "shard_b", "row_b", "idx", "pc", "mask", "dir", "a_a", "b_a", "c_a",
+                                                                       "m_a", "a_b", "b_b", "c_b", "m_b", "addr_a", "before_a", "after_a", "addr_b", "before_b",
+                                                                       "after_b")]
+
+
+class DivergeReg(C.Structure):
+    _fields_ = [(name, C.c_uint64) for name in ("n_diff", "first_diff", "last_diff", "last_write")] + [("live", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class DivergeSummary(C.Structure):
+    _fields_ = [(name, C.c_uint64) for name in ("n_pairs", "n_data", "first_data", "last_data", "n_load_diffs", "n_store_diffs", "launched_pairs", "cycles_a",
+                                                "cycles_b")] + \
+               [(name, C.c_uint32) for name in ("reason", "mask", "stop_shard_a", "stop_row_a", "stop_shard_b", "stop_row_b", "rejoin_shard_a", "rejoin_row_a",
+                                                "rejoin_shard_b", "rejoin_row_b", "rejoin_skip_a", "rejoin_skip_b", "n_kept", "span", "window", "batch_pairs")] + \
+               [(name, DivergeRec) for name in ("stop_a", "stop_b", "prev_a", "prev_b")] + [("ms", C.c_float), ("pad2", C.c_uint32)]
+
+
+_DIV_PAIR_KEYS = [name for name, _ in DivergePair._fields_]
+_DIV_REG_KEYS = [name for name, _ in DivergeReg._fields_ if name != "pad"]
+_DIV_REC_KEYS = [name for name, _ in DivergeRec._fields_ if name != "pad"]
+
+
+def _diverge(call, start_a, start_b, max_pairs, rejoin, window, keep):
+    """The report through call(start_a, start_b, max_pairs, flags, window, cap_each, first, last, regs, summary) -> rc.  Returns (rc,
+    dict(summary, regs = 32 dicts, first, last = pair dicts) or None when the call fails without an answer).  In the summary the
+    four records are dicts (or None where there is none)."""
+    first, last, regs, s = (DivergePair * max(keep, 1))(), (DivergePair * max(keep, 1))(), (DivergeReg * 32)(), DivergeSummary()
+    rc = call(DivergePos(*start_a), DivergePos(*start_b), max_pairs, DVT_DIVERGE_REJOIN if rejoin else 0, window, keep, first, last, regs, C.byref(s))
+    if rc != DVT_OK:
+        return rc, None
+    summary = {}
+    for name, kind in DivergeSummary._fields_:
+        if name in ("pad", "pad2"):
+            continue
+        v = getattr(s, name)
+        if kind is DivergeRec:
+            summary[name] = {k: int(getattr(v, k)) for k in _DIV_REC_KEYS if k != "valid"} if v.valid else None
+        else:
+            summary[name] = float(v) if name == "ms" else int(v)
+    n = summary["n_kept"]
+    return rc, dict(summary=summary, regs=[{k: int(getattr(regs[r], k)) for k in _DIV_REG_KEYS} for r in range(32)],
+                    first=[{k: int(getattr(first[i], k)) for k in _DIV_PAIR_KEYS} for i in range(n)],
+                    last=[{k: int(getattr(last[i], k)) for k in _DIV_PAIR_KEYS} for i in range(n)])
+
+
+def execute_diverge(elf: bytes, stdin_a: bytes, stdin_b: bytes, start_a=DIVERGE_ENTRY, start_b=DIVERGE_ENTRY, max_pairs=0, rejoin=False, window=0, keep=16,
+                    max_cycles=0, log_shard=21):
+    """Host-only divergence report (dvt_execute_diverge): the guest runs on stdin_a and on stdin_b (one buffer each; b"": none) in
+    shards of 2^log_shard cycles, and the two record streams are compared pair by pair from the starts on (csrc/diverge.h).  A guest
+    that traps or exits non-zero ends its stream there.  Returns (rc, (report dict of A, of B) as execute() gives them,
+    dict(summary, regs, first, last) as Prover.job_diverge gives it or None, error text)."""
+    lib = load()
+    reps, err = (Report(), Report()), C.c_char_p()
+    a, b = bytes(stdin_a), bytes(stdin_b)
+    rc, got = _diverge(lambda *io: lib.dvt_execute_diverge(elf, len(elf), a, len(a), b, len(b), max_cycles, log_shard, *io, C.byref(reps[0]), C.byref(reps[1]),
+                                                           C.byref(err)), start_a, start_b, max_pairs, rejoin, window, keep)
+    return rc, tuple(dict(cycles=r.cycles, exit_code=r.exit_code, halted=bool(r.halted), unprovable=bool(r.unprovable)) for r in reps), got, _take_str(lib, err)
 
 
 def exec_rate(elf: bytes, stdin=(), log_shard=21, trace=False) -> float:
@@ -1456,6 +1540,24 @@ class Prover:
         out = (C.c_double * 3)()
         self.check(self.lib.dvt_rv32_job_origin_times(self.h, out))
         return dict(reduce_ms=out[0], gather_ms=out[1], host_ms=out[2])
+
+    def job_diverge(self, pk, job_a, job_b, start_a=DIVERGE_ENTRY, start_b=DIVERGE_ENTRY, max_pairs=0, rejoin=False, window=0, keep=16):
+        """Where two prepared jobs of this handle (two executions of pk's guest; job_a may be job_b) part ways, from the cycle records
+        both hold on the GPU (dvt_rv32_job_diverge; the rule: csrc/diverge.h): pair k is (A[start_a + k], B[start_b + k]).
+        dict(summary, regs, first, last): summary has n_pairs (= the stop), reason (DVT_DIV_SPLIT .. _LIMIT), the data counts, the
+        positions and records of pair `stop` (stop_a, stop_b) and of the deciding pair before it (prev_a, prev_b), with rejoin=True the
+        rejoin positions; regs[r] says where register r was written with differing values and whether it is live at the stop;
+        first / last are the first and last min(keep, n_data) data pairs.  keep <= 64, window <= 16384 (0: 4096)."""
+        rc, got = _diverge(lambda *io: self.lib.dvt_rv32_job_diverge(self.h, pk, job_a, job_b, *io), start_a, start_b, max_pairs, rejoin, window, keep)
+        self.check(rc)
+        return got
+
+    def job_diverge_times(self):
+        """of the last job_diverge: dict(classify_ms, merge_ms, emit_ms (emit and gather), stream events summed over members and
+        batches; host_ms)"""
+        out = (C.c_double * 4)()
+        self.check(self.lib.dvt_rv32_job_diverge_times(self.h, out))
+        return dict(classify_ms=out[0], merge_ms=out[1], emit_ms=out[2], host_ms=out[3])
 
     def job_calltree_times(self):
         """milliseconds of the last job_calltree: dict(summary_ms, merge_ms, emit_ms)"""

@@ -1,13 +1,15 @@
 // The record reports of the C ABI (include/dvt_prover.h): what reads the cycle records a prepared job holds in HBM instead of its
 // trace rows.  The execution report (profile.h), the call-tree report (calltree.h) and the memory report (memreport.h) count
 // over them; the watchpoint search (watch.h) returns the ones that match; the snapshot (snapshot.h) reduces them to the state of
-// the machine at one position; the origin search (origin.h) follows one value back through them.  Each has a job entry point (dvt_rv32_job_*), which runs on lane 0 of every member that holds
-// shards, and a host-only one (dvt_execute_*) with the same rule over the executor's records (execute_traced).
+// the machine at one position; the origin search (origin.h) follows one value back through them; the divergence report (diverge.h)
+// holds the records of two jobs side by side.  Each has a job entry point (dvt_rv32_job_*), which runs on lane 0 of every member that
+// holds shards, and a host-only one (dvt_execute_*) with the same rule over the executor's records (execute_traced).
 #include <algorithm>
 #include <type_traits>
 
 #include "calltree.h"
 #include "capi_job.h"
+#include "diverge.h"
 #include "memreport.h"
 #include "origin.h"
 #include "profile.h"
@@ -931,6 +933,289 @@ static int job_origin(dvt_prover *p, const dvt_pk *pk, dvt_job *j, uint32_t shar
     return DVT_OK;
 }
 
+// ------------------------------------------------------------------ divergence (dvt_rv32_job_diverge)
+// The host cuts the pairs [0, N) into segments in which each side stays inside one shard (at most shardsA + shardsB of them; with
+// equal starts one per shard) and numbers their spans in pair order.  A segment is classified on lane 0's stream of the member
+// that holds both of its shards.  Segments are launched in batches of at most DVT_DIVERGE_BATCH_PAIRS pairs; after a batch the
+// host reads the stop flag and, once a stop is found, launches no later batch.  With several members the span records of the
+// others are relayed to member 0, which merges; the merged counts and rank bases go back for the emit, and every member's kept
+// pairs are picked from its own arrays.  Pairs stop - 1 and stop and the rejoin windows come out by origin.hip's gather.
+namespace {
+struct DivergeMember {
+    StageBuf base;
+    DivergeSpan *d_spans = nullptr;
+    DivergeSpanRegs *d_span_regs = nullptr;
+    unsigned long long *d_rank = nullptr, *d_stop = nullptr;
+    DivergeMerged *d_merged = nullptr;
+    dvt_diverge_pair *d_first = nullptr, *d_last = nullptr;
+    OriginFetch *d_items = nullptr;
+    rv32::CycleRec *d_recs = nullptr;
+    const uint32_t *d_statics = nullptr;
+    EventSpan t_classify, t_merge, t_emit, t_gather;
+    explicit DivergeMember(DevPool &pool) : base{pool} {}
+};
+struct DivergeSegment {
+    unsigned long long k0;
+    uint32_t n, span0, n_spans;
+    size_t m;
+    const rv32::CycleRec *rec_a, *rec_b;
+    dvt_diverge_pos at_a, at_b;
+};
+}  // namespace
+
+static int job_diverge(dvt_prover *p, const dvt_pk *pk, dvt_job *ja, dvt_job *jb, dvt_diverge_pos start_a, dvt_diverge_pos start_b, uint64_t max_pairs,
+                       uint32_t flags, uint32_t window, uint32_t K, dvt_diverge_pair *first, dvt_diverge_pair *last, dvt_diverge_reg regs[32],
+                       dvt_diverge_summary *summary) {
+    if (int rc = same_members(p, pk, ja)) return rc;
+    if (int rc = same_members(p, pk, jb)) return rc;
+    if (int rc = whole_execution(p, ja, "divergence of two executions")) return rc;
+    if (int rc = whole_execution(p, jb, "divergence of two executions")) return rc;
+    const auto t0 = Clock::now();
+    const rv32::Program &prog = pk->prog;
+    MemberRun<DivergeMember> run(p);   // (declared first: however the call ends, member 0's device is current again)
+    const std::vector<Held> held[2] = {held_in_order(ja), held_in_order(jb)};
+    diverge::Stream st[2];
+    for (int x = 0; x < 2; x++)
+        for (const Held &h : held[x]) {
+            if (h.s->n_recs > 0xffffffffull) return fail(p, DVT_ERR_INPUT, "shard %zu has %zu records", h.pos, h.s->n_recs);
+            st[x].shard_n.push_back(h.s->n_recs);
+        }
+    const uint64_t g[2] = {st[0].global_of(start_a), st[1].global_of(start_b)};
+    uint64_t N = std::min(st[0].len() - g[0], st[1].len() - g[1]);
+    if (max_pairs) N = std::min<uint64_t>(N, max_pairs);
+
+    // ---- the segments
+    std::vector<DivergeSegment> segs;
+    uint64_t n_spans = 0;
+    {
+        dvt_diverge_pos at[2] = {st[0].locate(g[0]), st[1].locate(g[1])};
+        for (uint64_t k = 0; k < N;) {
+            for (int x = 0; x < 2; x++)
+                while (at[x].shard <= st[x].shard_n.size() && at[x].row >= st[x].shard_n[at[x].shard - 1]) { at[x].shard++; at[x].row = 0; }
+            const Held &ha = held[0][at[0].shard - 1], &hb = held[1][at[1].shard - 1];
+            const uint64_t n = std::min({N - k, st[0].shard_n[at[0].shard - 1] - at[0].row, st[1].shard_n[at[1].shard - 1] - at[1].row});
+            if (ha.m != hb.m)
+                return fail(p, DVT_ERR_UNSUPPORTED, "segment %zu (pairs %llu..%llu): shard %u of A is held by member %zu, shard %u of B by member %zu", segs.size(),
+                            (unsigned long long)k, (unsigned long long)(k + n), at[0].shard, ha.m, at[1].shard, hb.m);
+            const uint32_t spans = (uint32_t)((n + diverge::SPAN - 1) / diverge::SPAN);
+            segs.push_back(DivergeSegment{k, (uint32_t)n, (uint32_t)n_spans, spans, ha.m, ha.s->d_recs + at[0].row, hb.s->d_recs + at[1].row, at[0], at[1]});
+            n_spans += spans;
+            k += n;
+            at[0].row += (uint32_t)n; at[1].row += (uint32_t)n;
+        }
+    }
+    if (n_spans > 0x7fffffffull) return fail(p, DVT_ERR_UNSUPPORTED, "%llu spans", (unsigned long long)n_spans);
+    const uint32_t win = window ? window : diverge::DEFAULT_WINDOW;
+    const size_t cap_items = 2 * ((size_t)diverge::MAX_WINDOW + 2);
+    const watch::Statics statics(prog);
+    const watch::Shapes shapes = watch::shapes();
+    const size_t n_instr = statics.n(), cap_spans = std::max<size_t>(n_spans, 1);
+    // a member's buffer: merged | stop flag | rank bases | fetched records | fetch items | kept pairs | span records | span registers | statics
+    const size_t bytes = sizeof(DivergeMerged) + 16 + cap_spans * 8 + 8 + cap_items * (sizeof(rv32::CycleRec) + sizeof(OriginFetch)) +
+                         2 * diverge::MAX_KEEP * sizeof(dvt_diverge_pair) + cap_spans * (sizeof(DivergeSpan) + sizeof(DivergeSpanRegs)) + statics.bytes();
+    auto buffers = [&](const Lane &c, DivergeMember &dm) {
+        if (dm.base.ptr) return DVT_OK;
+        Engine &e = c.eng;
+        HIP_TRY(c.err, e.pool.alloc_bytes(&dm.base.ptr, bytes));
+        dm.d_merged = static_cast<DivergeMerged *>(dm.base.ptr);
+        dm.d_stop = reinterpret_cast<unsigned long long *>(dm.d_merged + 1);
+        dm.d_rank = dm.d_stop + 2;                                                 // (what lies behind stays 16-byte aligned)
+        dm.d_recs = reinterpret_cast<rv32::CycleRec *>(dm.d_rank + cap_spans + (cap_spans & 1));
+        dm.d_items = reinterpret_cast<OriginFetch *>(dm.d_recs + cap_items);
+        dm.d_first = reinterpret_cast<dvt_diverge_pair *>(dm.d_items + cap_items);
+        dm.d_last = dm.d_first + diverge::MAX_KEEP;
+        dm.d_spans = reinterpret_cast<DivergeSpan *>(dm.d_last + diverge::MAX_KEEP);
+        dm.d_span_regs = reinterpret_cast<DivergeSpanRegs *>(dm.d_spans + cap_spans);
+        uint32_t *d_stat = reinterpret_cast<uint32_t *>(dm.d_span_regs + cap_spans);
+        dm.d_statics = d_stat;
+        HIP_TRY(c.err, hipMemsetAsync(dm.d_stop, 0xff, 8, e.stream));
+        HIP_TRY(c.err, hipMemsetAsync(dm.d_first, 0xff, 2 * diverge::MAX_KEEP * sizeof(dvt_diverge_pair), e.stream));
+        HIP_TRY(c.err, hipMemcpyAsync(d_stat, statics.words.data(), statics.bytes(), hipMemcpyHostToDevice, e.stream));
+        return DVT_OK;
+    };
+    auto args_of = [&](const DivergeSegment &sg, const DivergeMember &dm) {
+        DivergeArgs a{};
+        a.sh = shapes;
+        a.statics = dm.d_statics; a.offs = dm.d_statics + n_instr;
+        a.rec_a = sg.rec_a; a.rec_b = sg.rec_b;
+        a.k0 = sg.k0;
+        a.n_instr = (uint32_t)n_instr; a.text_base = prog.text_base; a.n_pairs = sg.n; a.span0 = sg.span0;
+        a.shard_a = sg.at_a.shard; a.row_a = sg.at_a.row; a.shard_b = sg.at_b.shard; a.row_b = sg.at_b.row;
+        return a;
+    };
+
+    // ---- classify, batch by batch
+    double ms[3] = {0, 0, 0};
+    unsigned long long stop_flag = diverge::NONE;
+    uint64_t launched_pairs = 0;
+    size_t done = 0;   // segments launched
+    while (done < segs.size() && stop_flag == diverge::NONE) {
+        size_t end = done;
+        uint64_t batch = 0;
+        while (end < segs.size() && (end == done || batch + segs[end].n <= diverge::BATCH_PAIRS)) batch += segs[end++].n;
+        if (int rc = for_members(p, [&](size_t m, const Lane &c) {
+                Engine &e = c.eng;
+                DivergeMember &dm = run[m];
+                bool any = false;
+                for (size_t i = done; i < end; i++) any = any || segs[i].m == m;
+                if (!any) return DVT_OK;
+                if (int rc = buffers(c, dm)) return rc;
+                HIP_TRY(c.err, dm.t_classify.begin(e.stream));
+                for (size_t i = done; i < end; i++)
+                    if (segs[i].m == m) HIP_TRY(c.err, launch_diverge_classify(e.stream, args_of(segs[i], dm), dm.d_spans, dm.d_span_regs, (uint32_t)cap_spans, dm.d_stop));
+                HIP_TRY(c.err, dm.t_classify.end(e.stream));
+                unsigned long long flag = diverge::NONE;
+                if (!e.download(&flag, dm.d_stop, 8)) return engine_fail(c.err, e);
+                ms[0] += dm.t_classify.ms();
+                stop_flag = std::min(stop_flag, flag);
+                return DVT_OK;
+            }))
+            return rc;
+        launched_pairs += batch;
+        done = end;
+    }
+    const uint32_t spans_done = done ? segs[done - 1].span0 + segs[done - 1].n_spans : 0;
+
+    // ---- the span records of the other members to member 0, which merges
+    DivergeMerged merged{};
+    merged.first_data = merged.last_data = diverge::NONE;
+    for (uint32_t r = 0; r < 32; r++) merged.reg_first_diff[r] = merged.reg_last_diff[r] = merged.reg_last_write[r] = diverge::NONE;
+    std::vector<unsigned long long> rank_base;
+    if (spans_done) {
+        std::vector<std::vector<uint8_t>> relay(done);   // per segment of another member: its span records, then its span registers
+        if (n_members(p) > 1) {
+            if (int rc = for_members(p, [&](size_t m, const Lane &c) {
+                    if (!m) return DVT_OK;
+                    for (size_t i = 0; i < done; i++) {
+                        if (segs[i].m != m) continue;
+                        const size_t a = segs[i].n_spans * sizeof(DivergeSpan), b = segs[i].n_spans * sizeof(DivergeSpanRegs);
+                        relay[i].resize(a + b);
+                        if (!c.eng.download(relay[i].data(), run[m].d_spans + segs[i].span0, a) || !c.eng.download(relay[i].data() + a, run[m].d_span_regs + segs[i].span0, b))
+                            return engine_fail(c.err, c.eng);
+                    }
+                    return DVT_OK;
+                }))
+                return rc;
+        }
+        {
+            const Lane c = lane0(p, 0);
+            Engine &e = c.eng;
+            DivergeMember &dm = run[0];
+            if (int rc = buffers(c, dm)) return rc;
+            for (size_t i = 0; i < done; i++) {
+                if (relay[i].empty()) continue;
+                const size_t a = segs[i].n_spans * sizeof(DivergeSpan), b = segs[i].n_spans * sizeof(DivergeSpanRegs);
+                HIP_TRY(c.err, hipMemcpyAsync(dm.d_spans + segs[i].span0, relay[i].data(), a, hipMemcpyHostToDevice, e.stream));
+                HIP_TRY(c.err, hipMemcpyAsync(dm.d_span_regs + segs[i].span0, relay[i].data() + a, b, hipMemcpyHostToDevice, e.stream));
+            }
+            HIP_TRY(c.err, dm.t_merge.begin(e.stream));
+            HIP_TRY(c.err, launch_diverge_merge(e.stream, dm.d_spans, dm.d_span_regs, spans_done, dm.d_rank, dm.d_merged));
+            HIP_TRY(c.err, dm.t_merge.end(e.stream));
+            if (!e.download(&merged, dm.d_merged, sizeof(merged))) return engine_fail(c.err, e);   // (the relayed bytes outlive the copies: this synchronises)
+            ms[1] += dm.t_merge.ms();
+        }
+    }
+    diverge::Counts cnt;
+    cnt.stop = merged.stop; cnt.stopped = merged.stopped; cnt.mask = merged.mask;
+    cnt.n_data = merged.n_data; cnt.first_data = merged.first_data; cnt.last_data = merged.last_data; cnt.n_load = merged.n_load; cnt.n_store = merged.n_store;
+    for (uint32_t r = 1; r < 32; r++) {
+        cnt.reg[r].n_diff = merged.reg_n_diff[r]; cnt.reg[r].first_diff = merged.reg_first_diff[r];
+        cnt.reg[r].last_diff = merged.reg_last_diff[r]; cnt.reg[r].last_write = merged.reg_last_write[r];
+    }
+    if (cnt.stop > N || merged.n_used > spans_done) return fail(p, DVT_ERR_DEVICE, "the merge pass stops past the pairs of the call");
+
+    // ---- emit: every member over its segments that count
+    if (K && cnt.n_data) {
+        std::vector<DivergeSpan> h_spans;
+        if (n_members(p) > 1) {   // the other members take the merged counts, the rank bases and the span records from member 0
+            const Lane c = lane0(p, 0);
+            rank_base.resize(spans_done);
+            h_spans.resize(spans_done);
+            if (!c.eng.download(rank_base.data(), run[0].d_rank, spans_done * 8) || !c.eng.download(h_spans.data(), run[0].d_spans, spans_done * sizeof(DivergeSpan)))
+                return engine_fail(c.err, c.eng);
+        }
+        std::vector<dvt_diverge_pair> got(2 * diverge::MAX_KEEP);
+        const watch::Keep keep = watch::keep_of(cnt.n_data, K);
+        if (int rc = for_members(p, [&](size_t m, const Lane &c) {
+                Engine &e = c.eng;
+                DivergeMember &dm = run[m];
+                bool any = false;
+                for (size_t i = 0; i < done; i++) any = any || (segs[i].m == m && segs[i].span0 < merged.n_used);
+                if (!any) return DVT_OK;
+                if (m) {
+                    HIP_TRY(c.err, hipMemcpyAsync(dm.d_merged, &merged, sizeof(merged), hipMemcpyHostToDevice, e.stream));
+                    HIP_TRY(c.err, hipMemcpyAsync(dm.d_rank, rank_base.data(), spans_done * 8, hipMemcpyHostToDevice, e.stream));
+                    HIP_TRY(c.err, hipMemcpyAsync(dm.d_spans, h_spans.data(), spans_done * sizeof(DivergeSpan), hipMemcpyHostToDevice, e.stream));
+                }
+                HIP_TRY(c.err, dm.t_emit.begin(e.stream));
+                for (size_t i = 0; i < done; i++)
+                    if (segs[i].m == m && segs[i].span0 < merged.n_used)
+                        HIP_TRY(c.err, launch_diverge_emit(e.stream, args_of(segs[i], dm), dm.d_spans, dm.d_rank, dm.d_merged, (uint32_t)cap_spans, K, dm.d_first, dm.d_last));
+                HIP_TRY(c.err, dm.t_emit.end(e.stream));
+                if (!e.download(got.data(), dm.d_first, got.size() * sizeof(dvt_diverge_pair))) return engine_fail(c.err, e);
+                ms[2] += dm.t_emit.ms();
+                for (size_t r = 0; r < keep.first_end && r < K; r++)   // (a slot no span of this member owns is all ones)
+                    if (got[r].k != diverge::NONE) first[r] = got[r];
+                for (size_t r = 0; r < keep.first_end && r < K; r++)
+                    if (got[diverge::MAX_KEEP + r].k != diverge::NONE) last[r] = got[diverge::MAX_KEEP + r];
+                return DVT_OK;
+            }))
+            return rc;
+    }
+
+    // ---- gather: pairs stop - 1 and stop, and the rejoin windows when the runs split
+    const bool want_rejoin = (flags & DVT_DIVERGE_REJOIN) && cnt.stopped == 1;
+    std::vector<rv32::CycleRec> near[2];   // side x: the records from global number lo[x] on
+    uint64_t lo[2];
+    {
+        struct Want { int x; size_t i; };
+        std::vector<std::vector<OriginFetch>> items(n_members(p));
+        std::vector<std::vector<Want>> wants(n_members(p));
+        for (int x = 0; x < 2; x++) {
+            lo[x] = g[x] + cnt.stop - (cnt.stop ? 1 : 0);
+            const uint64_t hi = std::min<uint64_t>(st[x].len(), g[x] + cnt.stop + (want_rejoin ? win : 1));
+            near[x].resize(hi > lo[x] ? hi - lo[x] : 0);
+            for (uint64_t q = lo[x]; q < hi; q++) {
+                const dvt_diverge_pos at = st[x].locate(q);
+                const Held &h = held[x][at.shard - 1];
+                items[h.m].push_back(OriginFetch{h.s->d_recs, (uint32_t)h.s->n_recs, at.row});
+                wants[h.m].push_back(Want{x, (size_t)(q - lo[x])});
+            }
+        }
+        std::vector<rv32::CycleRec> got;
+        if (int rc = for_members(p, [&](size_t m, const Lane &c) {
+                Engine &e = c.eng;
+                DivergeMember &dm = run[m];
+                if (items[m].empty()) return DVT_OK;
+                if (items[m].size() > cap_items) return fail(c.err, DVT_ERR_DEVICE, "more records to gather than the windows hold");
+                if (int rc = buffers(c, dm)) return rc;
+                HIP_TRY(c.err, hipMemcpyAsync(dm.d_items, items[m].data(), items[m].size() * sizeof(OriginFetch), hipMemcpyHostToDevice, e.stream));
+                HIP_TRY(c.err, dm.t_gather.begin(e.stream));
+                HIP_TRY(c.err, launch_origin_gather(e.stream, dm.d_items, (uint32_t)items[m].size(), dm.d_recs));
+                HIP_TRY(c.err, dm.t_gather.end(e.stream));
+                got.resize(items[m].size());
+                if (!e.download(got.data(), dm.d_recs, got.size() * sizeof(rv32::CycleRec))) return engine_fail(c.err, e);
+                ms[2] += dm.t_gather.ms();
+                for (size_t i = 0; i < got.size(); i++) near[wants[m][i].x][wants[m][i].i] = got[i];
+                return DVT_OK;
+            }))
+            return rc;
+    }
+    auto rec = [&](int x, uint64_t q) -> const rv32::CycleRec * { return q >= lo[x] && q - lo[x] < near[x].size() ? &near[x][q - lo[x]] : nullptr; };
+    diverge::finish(prog, statics, shapes, st[0], st[1], g[0], g[1], flags, window, K, cnt, rec,
+                    [&](int x, uint64_t q, uint64_t n, std::vector<rv32::CycleRec> *out) {
+                        for (uint64_t i = 0; i < n; i++)
+                            if (const rv32::CycleRec *r = rec(x, q + i)) out->push_back(*r);
+                    },
+                    regs, summary);
+    summary->launched_pairs = launched_pairs;
+    const double total = ms_since(t0);
+    summary->ms = (float)total;
+    for (int i = 0; i < 3; i++) p->diverge_ms[i] = ms[i];
+    p->diverge_ms[3] = std::max(0.0, total - ms[0] - ms[1] - ms[2]);
+    return DVT_OK;
+}
+
 // The host-only reports (no GPU is touched): the guest in trace mode, where an instruction without a chip is recorded instead
 // of trapping, 2^log_shard (2^21) cycles per shard and one shard's records in memory at a time.  begin(prog) once the ELF is loaded;
 // shard(prog, recs, n, last_succ) per shard in execution order; end(prog, ms) after the last, and a text it returns fails the
@@ -1211,6 +1496,58 @@ int dvt_execute_origin(const uint8_t *elf, size_t elf_len, const dvt_buf *stdin_
         },
         log_shard_size ? log_shard_size : 21);
     return bad && rc == DVT_ERR_UNSUPPORTED ? DVT_ERR_INPUT : rc;
+}
+
+// ---- divergence (diverge.h)
+int dvt_rv32_job_diverge(dvt_prover *p, const dvt_pk *pk, dvt_job *job_a, dvt_job *job_b, dvt_diverge_pos start_a, dvt_diverge_pos start_b,
+                         uint64_t max_pairs, uint32_t flags, uint32_t window, size_t cap_each, dvt_diverge_pair *first, dvt_diverge_pair *last,
+                         dvt_diverge_reg regs[32], dvt_diverge_summary *summary) {
+    if (!p || !pk || !job_a || !job_b || !summary) return fail(p, DVT_ERR_INPUT, "null argument");
+    std::string text;
+    if (const char *why = diverge::input_error(flags, window, cap_each, first, last, regs, &text)) return fail(p, DVT_ERR_INPUT, "%s", why);
+    if (int rc = rv32_key(p, pk)) return rc;
+    Guard g(p); if (g.rc) return g.rc;
+    return job_diverge(p, pk, job_a, job_b, start_a, start_b, max_pairs, flags, window, (uint32_t)cap_each, first, last, regs, summary);
+}
+
+int dvt_rv32_job_diverge_times(dvt_prover *p, double out[4]) { return times_of(p, &dvt_prover::diverge_ms, out); }
+
+// host-only: the same rule (diverge::compare) over the records diverge::Kept keeps of two runs of execute_traced
+int dvt_execute_diverge(const uint8_t *elf, size_t elf_len, const uint8_t *stdin_a, size_t n_a, const uint8_t *stdin_b, size_t n_b, uint64_t max_cycles,
+                        uint32_t log_shard_size, dvt_diverge_pos start_a, dvt_diverge_pos start_b, uint64_t max_pairs, uint32_t flags, uint32_t window,
+                        size_t cap_each, dvt_diverge_pair *first, dvt_diverge_pair *last, dvt_diverge_reg regs[32], dvt_diverge_summary *summary,
+                        dvt_report *report_a, dvt_report *report_b, char **err_text) {
+    if (err_text) *err_text = nullptr;
+    if (!elf || (n_a && !stdin_a) || (n_b && !stdin_b) || !summary) return DVT_ERR_INPUT;
+    std::string text;
+    if (execute_input_error(log_shard_size, diverge::input_error(flags, window, cap_each, first, last, regs, &text), &text, err_text)) return DVT_ERR_INPUT;
+    const auto t0 = Clock::now();
+    diverge::Kept kept[2];
+    rv32::Program program;
+    const dvt_buf bufs[2] = {{stdin_a, n_a}, {stdin_b, n_b}};
+    dvt_report *reports[2] = {report_a, report_b};
+    const dvt_diverge_pos starts[2] = {start_a, start_b};
+    for (int x = 0; x < 2; x++) {
+        char *why = nullptr;
+        const int rc = execute_traced(
+            elf, elf_len, &bufs[x], bufs[x].len ? 1 : 0, max_cycles, reports[x], &why, [&](const rv32::Program &prog) { if (!x) program = prog; },
+            [&](const rv32::Program &, const rv32::CycleRec *recs, size_t n, uint32_t) { kept[x].scan(recs, n, starts[x]); },
+            [&](const rv32::Program &, double) -> const char * { return nullptr; }, log_shard_size ? log_shard_size : 21);
+        if (rc != DVT_OK && rc != DVT_ERR_GUEST) {   // (a guest that traps or exits non-zero ends its stream: no error here)
+            if (err_text) *err_text = why;
+            else free(why);
+            return rc;
+        }
+        free(why);
+        if (kept[x].too_many) {
+            if (err_text) *err_text = strdup("more than 2^24 cycle records from a start on: prepare the jobs and ask dvt_rv32_job_diverge, which reads them on the GPU");
+            return DVT_ERR_UNSUPPORTED;
+        }
+    }
+    const uint64_t g[2] = {kept[0].st.global_of(start_a), kept[1].st.global_of(start_b)};
+    diverge::compare(program, kept[0], kept[1], g[0], g[1], max_pairs, flags, window, (uint32_t)cap_each, first, last, regs, summary);
+    summary->ms = (float)ms_since(t0);
+    return DVT_OK;
 }
 
 }  // extern "C"

@@ -48,6 +48,15 @@
 // passes=N", one line per node in discovery order: "node K depth=D at=S:R pc=0xX kind=op|load|store|call|syscall rd=0xX rs1=0xX
 // rs2=0xX addr=0xX before=0xX after=0xX edges=FIRST+N flags=0xX", and one per edge, edge 0 the root: "edge K from=I to=J
 // role=root|addr|rs1|rs2|mem target=0xX value=0xX flags=0xX src=S:R" (-1: no node).
+// diverge --type T -i A.json --against B.json --elf G [--host] [--from S:R --against-from S:R] [--rejoin N] [--keep K] [--log-shard L]
+// [--devices D0,D1,...]: where the runs of one guest on two inputs part ways (dvt_rv32_job_diverge on two prepared jobs of one handle,
+// with --host dvt_execute_diverge; csrc/diverge.h).  One block per lock-step segment: "diverge: pairs=N reason=split|bad|end_both|end_a|
+// end_b|limit data=N first_data=K last_data=K mask=0xX load_diffs=N store_diffs=N stop_a=S:R stop_b=S:R cycles_a=N cycles_b=N
+// rejoin_a=S:R rejoin_b=S:R skip_a=N skip_b=N" (-1: none), the deciding pair and the pair at the stop, one line per side ("deciding a:
+// pc=0xX a=0xX b=0xX c=0xX m=0xX" or "none"), "live: NAME ..." with the registers that differ at the stop, and the first and last K
+// (default 4) data pairs: "first|last k=K at=S:R/S:R pc=0xX mask=0xX a=0xX/0xX b=0xX/0xX c=0xX/0xX m=0xX/0xX" and, of a load or store,
+// " load|store addr=0xX/0xX before=0xX/0xX after=0xX/0xX".  With --rejoin N the call is repeated from the rejoin positions up to N
+// times.  The exit code is 0 whether or not the runs differ; only errors give 1.
 // get-schema / validate-schema / node are product UI outside the accelerated path and are not provided.
 #include <algorithm>
 #include <cstdio>
@@ -321,8 +330,47 @@ template <class Call> static int print_origin(size_t cap_nodes, Call call) {
     return 0;
 }
 
+// one block of the diverge verb (call: dvt_execute_diverge or dvt_rv32_job_diverge with everything else bound); the summary in *out
+template <class Call> static int print_diverge(size_t keep, Call call, dvt_diverge_summary *out) {
+    static const char *REASONS[] = {"?", "split", "bad", "end_both", "end_a", "end_b", "limit"};
+    static const char *REGS[32] = {"zero", "ra", "sp", "gp", "tp", "t0", "t1", "t2", "s0", "s1", "a0", "a1", "a2", "a3", "a4", "a5",
+                                   "a6", "a7", "s2", "s3", "s4", "s5", "s6", "s7", "s8", "s9", "s10", "s11", "t3", "t4", "t5", "t6"};
+    std::vector<dvt_diverge_pair> first(std::max<size_t>(keep, 1)), last(std::max<size_t>(keep, 1));
+    dvt_diverge_reg regs[32];
+    dvt_diverge_summary s{};
+    if (int rc = call(first.data(), last.data(), regs, &s)) return rc;
+    auto num = [](uint64_t v) { return v == DVT_DIV_NONE ? -1ll : (long long)v; };
+    auto pos = [](uint32_t v) { return v == DVT_DIVERGE_NO_REJOIN ? -1ll : (long long)v; };
+    printf("diverge: pairs=%llu reason=%s data=%llu first_data=%lld last_data=%lld mask=0x%x load_diffs=%llu store_diffs=%llu stop_a=%u:%u stop_b=%u:%u "
+           "cycles_a=%llu cycles_b=%llu rejoin_a=%lld:%lld rejoin_b=%lld:%lld skip_a=%lld skip_b=%lld\n",
+           (unsigned long long)s.n_pairs, REASONS[s.reason <= 6 ? s.reason : 0], (unsigned long long)s.n_data, num(s.first_data), num(s.last_data), s.mask,
+           (unsigned long long)s.n_load_diffs, (unsigned long long)s.n_store_diffs, s.stop_shard_a, s.stop_row_a, s.stop_shard_b, s.stop_row_b,
+           (unsigned long long)s.cycles_a, (unsigned long long)s.cycles_b, pos(s.rejoin_shard_a), pos(s.rejoin_row_a), pos(s.rejoin_shard_b), pos(s.rejoin_row_b),
+           pos(s.rejoin_skip_a), pos(s.rejoin_skip_b));
+    auto rec = [](const char *what, const dvt_diverge_rec &r) {
+        if (r.valid) printf("%s: pc=0x%x a=0x%x b=0x%x c=0x%x m=0x%x\n", what, r.pc, r.a, r.b, r.c, r.m_prev);
+        else printf("%s: none\n", what);
+    };
+    rec("deciding a", s.prev_a); rec("deciding b", s.prev_b); rec("stop a", s.stop_a); rec("stop b", s.stop_b);
+    printf("live:");
+    for (int r = 1; r < 32; r++)
+        if (regs[r].live) printf(" %s", REGS[r]);
+    printf("\n");
+    for (int half = 0; half < 2; half++)
+        for (uint32_t i = 0; i < s.n_kept; i++) {
+            const dvt_diverge_pair &e = (half ? last : first)[i];
+            printf("%s k=%llu at=%u:%u/%u:%u pc=0x%x mask=0x%x a=0x%x/0x%x b=0x%x/0x%x c=0x%x/0x%x m=0x%x/0x%x", half ? "last" : "first", (unsigned long long)e.k,
+                   e.shard_a, e.row_a, e.shard_b, e.row_b, e.pc, e.mask, e.a_a, e.a_b, e.b_a, e.b_b, e.c_a, e.c_b, e.m_a, e.m_b);
+            if (e.dir) printf(" %s addr=0x%x/0x%x before=0x%x/0x%x after=0x%x/0x%x", e.dir == DVT_WATCH_LOAD ? "load" : "store", e.addr_a, e.addr_b, e.before_a,
+                              e.before_b, e.after_a, e.after_b);
+            printf("\n");
+        }
+    *out = s;
+    return 0;
+}
+
 int main(int argc, char **argv) {
-    if (argc < 2) return die("usage: dvt_prover_host prove|execute|verify|check|compact|expand --type T -i FILE [-o FILE] [--show-report] [--show-calls] [--show-memory] [--watch SPEC] [--snapshot S:R|exit] [--dump ADDR+LEN] [--frames N] [--origin SPEC] [--depth N] [--nodes N] [--follow-addr] [--compact] [--keep-trees] [--elf FILE] [--devices D0,D1,...] [--device D]");
+    if (argc < 2) return die("usage: dvt_prover_host prove|execute|verify|check|diverge|compact|expand --type T -i FILE [-o FILE] [--show-report] [--show-calls] [--show-memory] [--watch SPEC] [--snapshot S:R|exit] [--dump ADDR+LEN] [--frames N] [--origin SPEC] [--depth N] [--nodes N] [--follow-addr] [--compact] [--keep-trees] [--elf FILE] [--devices D0,D1,...] [--device D] [--against FILE] [--host] [--from S:R] [--against-from S:R] [--rejoin N] [--keep K] [--log-shard L]");
     const std::string verb = argv[1];
     std::string type, input, output, elf_path, schema_path, devices, verify_device;
     bool show_report = false, show_calls = false, show_memory = false, auth = false, compact = false, keep_trees = false;
@@ -336,6 +384,11 @@ int main(int argc, char **argv) {
     OriginSpec origin_spec{};
     uint32_t origin_depth = DVT_ORIGIN_MAX_DEPTH, origin_flags = 0;
     size_t origin_nodes = DVT_ORIGIN_MAX_NODES;
+    std::string against;
+    bool host_only = false;
+    dvt_diverge_pos div_from[2] = {{1, 0}, {1, 0}};
+    uint32_t div_rejoin = 0, div_log_shard = 0;
+    size_t div_keep = 4;
     for (int i = 2; i < argc; i++) {
         std::string a = argv[i], inline_val;
         bool has_inline = false;
@@ -377,6 +430,16 @@ int main(int argc, char **argv) {
         else if (a == "--depth") origin_depth = (uint32_t)strtoull(next().c_str(), nullptr, 0);
         else if (a == "--nodes") origin_nodes = (size_t)strtoull(next().c_str(), nullptr, 0);
         else if (a == "--follow-addr") origin_flags |= DVT_ORIGIN_FOLLOW_ADDR;
+        else if (a == "--against") against = next();
+        else if (a == "--host") host_only = true;
+        else if (a == "--from" || a == "--against-from") {
+            const std::string t = next();
+            dvt_diverge_pos &at = div_from[a == "--from" ? 0 : 1];
+            if (t == "exit" || !parse_position(t, &at.shard, &at.row)) return die("no position (S:R): " + t);
+        }
+        else if (a == "--rejoin") div_rejoin = (uint32_t)strtoull(next().c_str(), nullptr, 0);
+        else if (a == "--keep") div_keep = (size_t)strtoull(next().c_str(), nullptr, 0);
+        else if (a == "--log-shard") div_log_shard = (uint32_t)strtoull(next().c_str(), nullptr, 0);
         else if (a == "--compact") compact = true;       // prove: shard proofs in the compact form ("compact_openings")
         else if (a == "--keep-trees") keep_trees = true;  // prove / check: shards that do not fit in HBM in full keep their main Merkle tree ("keep_phase1": 2)
         else if (a == "--auth-commitment") auth = true;  // the reference selects this at build time (cargo feature)
@@ -384,7 +447,7 @@ int main(int argc, char **argv) {
         else return die("unknown argument " + a);
     }
     const bool transcode = verb == "compact" || verb == "expand";   // -i: a proof; -o: the proof in the other form
-    if (verb != "prove" && verb != "execute" && verb != "verify" && verb != "check" && !transcode) return die("unknown sub-command " + verb);
+    if (verb != "prove" && verb != "execute" && verb != "verify" && verb != "check" && verb != "diverge" && !transcode) return die("unknown sub-command " + verb);
     if (type.empty() || input.empty()) return die("--type and --input-file are required");
     if (elf_path.empty()) {
         const char *dir = getenv("DVT_ELF_DIR");
@@ -447,6 +510,54 @@ int main(int argc, char **argv) {
     if (dvt_stdin_from_json(type.c_str(), (const char *)in.data(), in.size(), auth, &stdin_buf, &stdin_len, &err))
         return die(std::string("Failed to read input: ") + (err ? err : "?"));
     dvt_buf buf{stdin_buf, stdin_len};
+
+    if (verb == "diverge") {
+        std::vector<uint8_t> in_b;
+        if (against.empty() || !read_file(against, &in_b)) return die("diverge needs --against FILE: cannot read '" + against + "'");
+        uint8_t *stdin_b = nullptr;
+        size_t len_b = 0;
+        if (dvt_stdin_from_json(type.c_str(), (const char *)in_b.data(), in_b.size(), auth, &stdin_b, &len_b, &err))
+            return die(std::string("Failed to read input: ") + (err ? err : "?"));
+        if (div_keep > DVT_DIVERGE_MAX_KEEP) return die("--keep is at most " + std::to_string(DVT_DIVERGE_MAX_KEEP));
+        dvt_buf buf_b{stdin_b, len_b};
+        dvt_prover *p = nullptr;
+        dvt_pk *pk = nullptr;
+        dvt_job *jobs[2] = {nullptr, nullptr};
+        if (!host_only) {
+            std::string cfg;
+            if (!devices.empty()) cfg += "\"devices\": [" + devices + "]";
+            if (div_log_shard) cfg += std::string(cfg.empty() ? "" : ", ") + "\"log_shard_size\": " + std::to_string(div_log_shard);
+            const bool plain = cfg.empty();
+            cfg = "{" + cfg + "}";
+            if (dvt_prover_create(plain ? nullptr : cfg.c_str(), &p)) return die(dvt_last_error(nullptr));
+            if (dvt_setup(p, elf.data(), elf.size(), &pk, nullptr, nullptr)) return die(dvt_last_error(p));
+            // (a run that traps or exits non-zero leaves no job to compare: --host is the way for those)
+            dvt_report rep{};
+            if (dvt_rv32_prepare(p, pk, &buf, 1, &jobs[0], &rep) || dvt_rv32_prepare(p, pk, &buf_b, 1, &jobs[1], &rep))
+                return die(std::string("Preparing the job failed: ") + dvt_last_error(p));
+        }
+        dvt_diverge_pos at[2] = {div_from[0], div_from[1]};
+        for (uint32_t round = 0; round <= div_rejoin; round++) {
+            dvt_diverge_summary s{};
+            char *derr = nullptr;
+            if (print_diverge(div_keep, [&](dvt_diverge_pair *first, dvt_diverge_pair *last, dvt_diverge_reg *regs, dvt_diverge_summary *sum) {
+                    return host_only ? dvt_execute_diverge(elf.data(), elf.size(), stdin_buf, stdin_len, stdin_b, len_b, 0, div_log_shard, at[0], at[1], 0,
+                                                           DVT_DIVERGE_REJOIN, 0, div_keep, first, last, regs, sum, nullptr, nullptr, &derr)
+                                     : dvt_rv32_job_diverge(p, pk, jobs[0], jobs[1], at[0], at[1], 0, DVT_DIVERGE_REJOIN, 0, div_keep, first, last, regs, sum);
+                }, &s))
+                return die(std::string("Divergence failed: ") + (host_only ? (derr ? derr : "?") : dvt_last_error(p)));
+            if (s.reason != DVT_DIV_SPLIT || s.rejoin_skip_a == DVT_DIVERGE_NO_REJOIN) break;
+            at[0] = dvt_diverge_pos{s.rejoin_shard_a, s.rejoin_row_a};
+            at[1] = dvt_diverge_pos{s.rejoin_shard_b, s.rejoin_row_b};
+        }
+        if (p) {
+            dvt_job_free(p, jobs[0]);
+            dvt_job_free(p, jobs[1]);
+            dvt_pk_free(p, pk);
+            dvt_prover_destroy(p);
+        }
+        return 0;
+    }
 
     if (verb == "execute") {
         printf("input len: %zu\n", stdin_len - 8);  // the reference prints the CBOR length (src/main.rs:436)

@@ -205,4 +205,22 @@ hipError_t launch_origin_reduce(hipStream_t st, const rv32::CycleRec *d_recs, si
                                 unsigned long long *d_bad_records);
 hipError_t launch_origin_gather(hipStream_t st, const OriginFetch *d_items, uint32_t n_items, rv32::CycleRec *d_out);
 
+// diverge.hip
+// The passes of the divergence report (diverge.h) over one segment of pairs (DivergeArgs: both record pointers at the segment's
+// first pair, a.n_pairs pairs, the pair number a.k0 and the span number a.span0 of its first span).  classify: one DivergeSpan and
+// one DivergeSpanRegs per span into d_spans / d_span_regs [cap_spans], and the pair number of a CONTROL or BAD pair by atomicMin
+// into *d_stop_flag (set to all ones by the caller).  merge: over the spans [0, n_spans) of a call, up to the first with a stop,
+// into *d_out and d_rank_base [n_spans].  emit: the first and the last K data pairs into d_first / d_last [K each].  The records
+// are only read.
+struct DivergeArgs;
+struct DivergeSpan;
+struct DivergeSpanRegs;
+struct DivergeMerged;
+hipError_t launch_diverge_classify(hipStream_t st, const DivergeArgs &a, DivergeSpan *d_spans, DivergeSpanRegs *d_span_regs, uint32_t cap_spans,
+                                   unsigned long long *d_stop_flag);
+hipError_t launch_diverge_merge(hipStream_t st, const DivergeSpan *d_spans, const DivergeSpanRegs *d_span_regs, uint32_t n_spans, unsigned long long *d_rank_base,
+                                DivergeMerged *d_out);
+hipError_t launch_diverge_emit(hipStream_t st, const DivergeArgs &a, const DivergeSpan *d_spans, const unsigned long long *d_rank_base, const DivergeMerged *d_merged,
+                               uint32_t cap_spans, uint32_t K, void *d_first, void *d_last);
+
 }  // namespace dvt

@@ -131,7 +131,7 @@ void dvt_free(void *ptr);
  * dvt_rv32_job_calltree_times, dvt_execute_calltree; 15: dvt_rv32_job_memory, dvt_execute_memory;
  * 16: dvt_rv32_job_watch, dvt_execute_watch, dvt_rv32_job_watch_times; 17: dvt_rv32_job_snapshot,
  * dvt_rv32_job_snapshot_times, dvt_execute_snapshot; 18: dvt_rv32_debug_poke_cell; 19: dvt_rv32_job_origin, dvt_rv32_job_origin_times,
- * dvt_execute_origin) */
+ * dvt_execute_origin; 20: dvt_rv32_job_diverge, dvt_rv32_job_diverge_times, dvt_execute_diverge) */
 uint32_t dvt_abi_version(void);
 /* the handle's hipStream_t (for event timing by the caller) */
 void *dvt_stream(dvt_prover *p);
@@ -1003,6 +1003,84 @@ int dvt_rv32_job_origin_times(dvt_prover *p, double out[3]);
 int dvt_execute_origin(const uint8_t *elf, size_t elf_len, const dvt_buf *stdin_bufs, size_t nbuf, uint64_t max_cycles, uint32_t log_shard_size,
                        uint32_t shard, uint32_t row, uint32_t what, uint32_t target, uint32_t flags, uint32_t max_depth, dvt_origin_node *nodes,
                        size_t cap_nodes, dvt_origin_edge *edges, size_t cap_edges, dvt_origin_summary *summary, dvt_report *report, char **err_text);
+/* Divergence of two executions of one guest: where two prepared jobs of one handle (job_a == job_b is allowed) stop doing the
+ * same thing, and which values differed before, from the cycle records both jobs hold (the records are only read, the jobs are
+ * left as found).  The rule is stated in csrc/diverge.h:
+ *   streams     execution X is its records in execution order.  A call names a start in each, (shard, row), at global record
+ *               numbers gA and gB; pair k is (A[gA + k], B[gB + k]) for k < N = min(lenA - gA, lenB - gB, max_pairs; 0: no limit).
+ *   class       BAD: either record is one the executor never writes.  CONTROL: the two idx differ.  DATA: same idx and at least
+ *               one of the words a, b, c, m_prev differs; mask = DVT_DIV_RD | _RS1 | _RS2 | _MEM, one bit per differing word.
+ *               The timestamp words of a record (pa_prev, *_ts, sh_*) are NOT compared.  SAME: everything else.
+ *   stop        the smallest k whose class is CONTROL (reason DVT_DIV_SPLIT) or BAD (DVT_DIV_BAD); without one stop = N and the
+ *               reason is END_BOTH (both streams end at pair N), END_A / END_B (only that stream does) or LIMIT.  Only pairs
+ *               k < stop count below.
+ *   summary     n_pairs = stop, reason, n_data / first_data / last_data (pair numbers or DVT_DIV_NONE), mask = the OR of the
+ *               masks, n_load_diffs (loads whose word before differs), n_store_diffs (stores whose word AFTER differs), the
+ *               positions of pair `stop` in A and B (past the end: the last shard and its record count), both records of pair
+ *               `stop` and of pair stop - 1 with their pc (valid = 0: there is none), the deciding instruction being pair
+ *               stop - 1; launched_pairs (pairs the device classified; 0 on the host path), cycles_a, cycles_b.
+ *   regs[r]     r >= 1: n_diff = pairs that write r with a differing a; first_diff, last_diff, last_write (pair numbers);
+ *               live = last_write != NONE && last_write == last_diff.  With both starts at the entry the live registers are
+ *               exactly the ones that hold different values at the stop; with later starts, relative to the starts.
+ *   first/last  the first and the last min(cap_each, n_data) DATA pairs (first: slot r = rank r; last: slot r = rank
+ *               n_data - min(cap_each, n_data) + r), cap_each <= DVT_DIVERGE_MAX_KEEP: k, both positions, idx, pc, mask, dir
+ *               (DVT_WATCH_LOAD / _STORE or 0), a b c m_prev of both sides and, of a load or store, addr, before, after of both.
+ *   rejoin      with flags & DVT_DIVERGE_REJOIN and reason SPLIT: each side is walked from its record of pair `stop` for at most
+ *               `window` records (0: DVT_DIVERGE_DEFAULT_WINDOW; at most DVT_DIVERGE_MAX_WINDOW) keeping a relative call depth;
+ *               the first pair of records (i of A, j of B) at the same level (the split's frame, or the one record after the
+ *               return out of it) with the same idx, smallest i + j, then smallest i: rejoin_* = their positions, rejoin_skip_* =
+ *               i, j; DVT_DIVERGE_NO_REJOIN in all six without one.  A heuristic: the call from the rejoin positions confirms it.
+ * DVT_ERR_INPUT: null arguments, cap_each or window above the limits, an unknown flag.  A start names the first record at or after
+ * it, positions comparing as (shard, row) pairs as the snapshot's do: a start past the end of its execution is its end.
+ * DVT_ERR_UNSUPPORTED: a job that does not hold every shard of its execution; a segment of pairs whose two shards are held by
+ * different members of the handle (with one member, or with equal starts, there is none). */
+#define DVT_DIVERGE_SPAN 4096              /* pairs one workgroup of the device pass classifies */
+#define DVT_DIVERGE_MAX_KEEP 64
+#define DVT_DIVERGE_MAX_WINDOW 16384
+#define DVT_DIVERGE_DEFAULT_WINDOW 4096
+#ifndef DVT_DIVERGE_BATCH_PAIRS           /* (a build may set another to measure it: tools/bench_diverge.py) */
+#define DVT_DIVERGE_BATCH_PAIRS (1u << 20) /* pairs launched between two reads of the stop flag; a batch holds at least one segment.
+                                            * Measured at 2^18, 2^20, 2^22 on 2^21-cycle shards (profiles/README.md, Divergence): the first two are
+                                            * the same there, 2^22 costs an early split 0.09 ms more and the whole prefix 0.25 ms less */
+#endif
+#define DVT_DIV_NONE 0xffffffffffffffffull
+#define DVT_DIVERGE_NO_REJOIN 0xffffffffu
+enum { DVT_DIV_RD = 1, DVT_DIV_RS1 = 2, DVT_DIV_RS2 = 4, DVT_DIV_MEM = 8 };                                           /* mask */
+enum { DVT_DIVERGE_REJOIN = 1 };                                                                                        /* flags of a call */
+enum { DVT_DIV_SPLIT = 1, DVT_DIV_BAD = 2, DVT_DIV_END_BOTH = 3, DVT_DIV_END_A = 4, DVT_DIV_END_B = 5, DVT_DIV_LIMIT = 6 };   /* reason */
+typedef struct { uint32_t shard, row; } dvt_diverge_pos;
+typedef struct { uint32_t valid, pc, idx, a, b, c, m_prev, pad; } dvt_diverge_rec;
+typedef struct {
+    uint64_t k;
+    uint32_t shard_a, row_a, shard_b, row_b, idx, pc, mask, dir;
+    uint32_t a_a, b_a, c_a, m_a, a_b, b_b, c_b, m_b;
+    uint32_t addr_a, before_a, after_a, addr_b, before_b, after_b;
+} dvt_diverge_pair;
+typedef struct { uint64_t n_diff, first_diff, last_diff, last_write; uint32_t live, pad; } dvt_diverge_reg;
+typedef struct {
+    uint64_t n_pairs, n_data, first_data, last_data, n_load_diffs, n_store_diffs, launched_pairs, cycles_a, cycles_b;
+    uint32_t reason, mask, stop_shard_a, stop_row_a, stop_shard_b, stop_row_b;
+    uint32_t rejoin_shard_a, rejoin_row_a, rejoin_shard_b, rejoin_row_b, rejoin_skip_a, rejoin_skip_b;
+    uint32_t n_kept, span, window, batch_pairs;   /* n_kept = min(cap_each, n_data): the filled slots of first[] and of last[]; batch_pairs: DVT_DIVERGE_BATCH_PAIRS as built */
+    dvt_diverge_rec stop_a, stop_b, prev_a, prev_b;
+    float ms;          /* wall clock of the call after the entry guard */
+    uint32_t pad2;
+} dvt_diverge_summary;
+int dvt_rv32_job_diverge(dvt_prover *p, const dvt_pk *pk, dvt_job *job_a, dvt_job *job_b, dvt_diverge_pos start_a, dvt_diverge_pos start_b,
+                         uint64_t max_pairs, uint32_t flags, uint32_t window, size_t cap_each, dvt_diverge_pair *first, dvt_diverge_pair *last,
+                         dvt_diverge_reg regs[32], dvt_diverge_summary *summary);
+/* milliseconds of the last dvt_rv32_job_diverge: the classify launches, the merge launch, the emit and gather launches (by events
+ * on the members' streams, summed over members and batches); the host's share (the wall clock of the call less those three) */
+int dvt_rv32_job_diverge_times(dvt_prover *p, double out[4]);
+/* The same comparison on the host alone (no GPU is touched): the guest is run twice, on stdin_a and on stdin_b (one buffer each, len 0:
+ * none), in shards of 2^log_shard_size cycles (0: 21; 4..22), and the records of both runs from their starts on are kept, 48 bytes
+ * per cycle: past 2^24 of them per run the call fails with DVT_ERR_UNSUPPORTED.  A guest that traps or exits non-zero is no
+ * error here: its stream ends where it stopped, report_a / report_b (either may be null) say how each run ended, and the call
+ * returns DVT_OK. */
+int dvt_execute_diverge(const uint8_t *elf, size_t elf_len, const uint8_t *stdin_a, size_t n_a, const uint8_t *stdin_b, size_t n_b, uint64_t max_cycles,
+                        uint32_t log_shard_size, dvt_diverge_pos start_a, dvt_diverge_pos start_b, uint64_t max_pairs, uint32_t flags, uint32_t window,
+                        size_t cap_each, dvt_diverge_pair *first, dvt_diverge_pair *last, dvt_diverge_reg regs[32], dvt_diverge_summary *summary,
+                        dvt_report *report_a, dvt_report *report_b, char **err_text);
 /* test hook: run K0 on one shard of a prepared job and return the device-generated main traces
  * (canonical); blob layout as dvt_rv32_debug_traces with prep_width = 0. */
 int dvt_rv32_debug_device_traces(dvt_prover *p, const dvt_pk *pk, dvt_job *job, size_t shard, uint32_t **blob,
