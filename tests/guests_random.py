@@ -10,15 +10,21 @@ the functions of the `flow` profile lie behind the HALT and a function only call
 checks both on the assembled items, so every program terminates by construction.
 
 What the guests leave out: syscalls other than the ending's WRITE / COMMIT / HALT, precompiles, hints, backward branches, traps.
+The only hint is the optional input prologue: with stdin_words = K > 0 the guest first reads one buffer of K words to
+tests.guests.HEAP (HINT_LEN, HINT_READ) and copies word k into scratch slot slot_k (lw t3 / sw t3), so that what the random part
+loads, compares and branches on depends on the input.  The K distinct slots come from a random.Random of their own, seeded from
+the seed: the random part's text does not depend on K, and with K = 0 every byte of the ELF is what it is without the parameter.
 
-CASES is the pinned list the tests run; coverage() computes, from the model's rows alone, what the list is there to contain."""
+CASES is the pinned list the tests run; coverage() computes, from the model's rows alone, what the list is there to contain.
+INPUT_CASES is the pinned list of (case, kind, input seed) the divergence tests run on guests with the prologue; inputs_of()
+gives an entry's two inputs."""
 import collections
 import functools
 import random
 
 from tests import _profile_ref
-from tests.guests import _finish
-from tools.rvasm import ABI, Asm
+from tests.guests import HEAP, _finish
+from tools.rvasm import ABI, SYS_HINT_LEN, SYS_HINT_READ, Asm
 
 M32 = 0xFFFFFFFF
 EDGES = (0, 1, 2, 0x7F, 0x80, 0xFF, 0x100, 0x7FFF, 0x8000, 0xFFFF, 0x10000, 0x00FFFFFF, 0x01000000, 0x00FF00FF, 0xFF00FF00,
@@ -66,8 +72,22 @@ PROVE_CASES = ((0, "mixed", 1500), (3, "alu", 1500), (5, "mem", 1500), (7, "muld
 SHORT = (12, "mixed", 300)
 
 
+INPUT_WORDS = 16
+# (case, kind, seed of the inputs): the case's guest with the input prologue of INPUT_WORDS words, run on the two inputs of
+# inputs_of().  "bit": one flipped bit of one word; "other": every word differs.  Every profile, and the long mixed case
+# at least once.  The input seeds are chosen so that every split of a chain rejoins: a branch over a `jal ra` leaves the two
+# sides at different call depths for good, which the rejoin rule does not match (most input seeds of the flow cases do that)
+INPUT_CASES = (((0, "mixed", 1500), "other", 1), ((0, "mixed", 1500), "bit", 1), ((2, "mixed", 6000), "other", 5), ((2, "mixed", 6000), "bit", 4),
+               ((3, "alu", 1500), "other", 0), ((5, "mem", 1500), "other", 4), ((5, "mem", 1500), "bit", 1), ((7, "muldiv", 1500), "other", 3),
+               ((9, "flow", 1500), "other", 37), ((9, "flow", 1500), "bit", 2))
+
+
 def case_id(case):
     return "%s-seed%d-n%d" % (case[1], case[0], case[2])
+
+
+def input_case_id(entry):
+    return "%s-%s%d" % (case_id(entry[0]), entry[1], entry[2])
 
 
 class Guest:
@@ -91,10 +111,45 @@ def value(rng):
     return rng.getrandbits(32)
 
 
+def _pack(words):
+    return b"".join(w.to_bytes(4, "little") for w in words)
+
+
+def input_of(seed, words=INPUT_WORDS):
+    """an input buffer of `words` words: value() from random.Random(seed)"""
+    rng = random.Random(seed)
+    return _pack([value(rng) for _ in range(words)])
+
+
+def inputs_of(entry):
+    """the two input buffers (INPUT_WORDS little-endian words each) of an entry of INPUT_CASES: A is value() INPUT_WORDS times
+    from random.Random(the entry's input seed); B is A with one bit of one word flipped ("bit"), or further value()s each of
+    which differs from A's word ("other")"""
+    _, kind, seed = entry
+    rng = random.Random(seed)
+    a = [value(rng) for _ in range(INPUT_WORDS)]
+    assert _pack(a) == input_of(seed)
+    if kind == "bit":
+        b = list(a)
+        b[rng.randrange(INPUT_WORDS)] ^= 1 << rng.randrange(32)
+    else:
+        assert kind == "other"
+        b = []
+        for w in a:
+            x = value(rng)
+            while x == w:
+                x = value(rng)
+            b.append(x)
+    return _pack(a), _pack(b)
+
+
 class _Gen:
-    def __init__(self, seed, n, profile):
+    def __init__(self, seed, n, profile, stdin_words=0):
         self.rng = random.Random(seed)
         self.n, self.profile = n, profile
+        assert 0 <= stdin_words <= SCRATCH_WORDS
+        # a stream of its own: the generator's draws, and so the random part's text, do not depend on stdin_words
+        self.slots = random.Random("input slots of seed %d" % seed).sample(range(SCRATCH_WORDS), stdin_words)
         w = WEIGHTS[profile]
         self.kinds, self.weights = list(KINDS), [w[k] for k in KINDS]
         self.a = Asm()
@@ -232,6 +287,17 @@ class _Gen:
         self.table = a.dword("table", [0] * N_FUNCS) if has_funcs else 0
         a.li("s0", scratch)
         a.li("sp", stack + 4 * STACK_WORDS)
+        if self.slots:
+            # the input prologue (a0, a1, t0, t3 only): one buffer of len(slots) words to the heap, word k into scratch slot slots[k]
+            a.li("t0", SYS_HINT_LEN)
+            a.ecall()
+            a.li("a0", HEAP)
+            a.li("a1", 4 * len(self.slots))
+            a.li("t0", SYS_HINT_READ)
+            a.ecall()
+            for k, slot in enumerate(self.slots):
+                a.lw(TMP, "a0", 4 * k)
+                a.sw(TMP, "s0", 4 * slot)
         for reg in POOL:
             a.li(reg, value(rng))
         ranges = []
@@ -258,7 +324,7 @@ class _Gen:
                 ranges.append((lo, a.pc()))
                 a.data[(self.table - a.data_base) // 4 + f] = a.labels["fn%d" % f]
         self._assert_forward()
-        return Guest(elf=a.elf(), scratch=scratch, out=out, table=self.table, random_pcs=ranges, seed=None)
+        return Guest(elf=a.elf(), scratch=scratch, out=out, table=self.table, random_pcs=ranges, seed=None, slots=tuple(self.slots))
 
     def _assert_forward(self):
         """termination by construction: every branch and JAL of the random part lands behind itself, at most five instructions
@@ -274,15 +340,16 @@ class _Gen:
         assert N_FUNCS + 1 <= STACK_WORDS
 
 
-def build(seed, n=1500, profile="mixed"):
-    g = _Gen(seed, n, profile).build()
-    g.seed, g.profile, g.n = seed, profile, n
+def build(seed, n=1500, profile="mixed", stdin_words=0):
+    """the guest of that seed; stdin_words = K > 0: with the input prologue, to be run on one buffer of 4 K bytes"""
+    g = _Gen(seed, n, profile, stdin_words).build()
+    g.seed, g.profile, g.n, g.stdin_words = seed, profile, n, stdin_words
     return g
 
 
-def random_guest(seed, n=1500, profile="mixed"):
+def random_guest(seed, n=1500, profile="mixed", stdin_words=0):
     """the ELF of the guest of that seed: the same bytes on every machine"""
-    return build(seed, n, profile).elf
+    return build(seed, n, profile, stdin_words).elf
 
 
 # ---------------------------------------------------------------------------------------------- reading a row

@@ -4,7 +4,8 @@
 fill_cpu_row of csrc/rv32.h is one template compiled for the host and for the device; the host rows agreeing with the model
 (tests/test_random_guests_cpu.py) says nothing about the device instantiation.  Here every word K0 writes on the device (the
 cpu rows, the shift, muldiv and mem_init rows, the byte-table and program-table multiplicities) is compared with the model's;
-the job check, the bus ledger and the five record reports run on the same jobs; one case of each profile is proven and
+the job check, the bus ledger and the five record reports run on the same jobs, the origin slice and the divergence report on
+the positions, targets and pairs of inputs of tests/test_random_guests_slices_cpu.py; one case of each profile is proven and
 verified, and the proof bytes of a short case equal the oracle prover's.  At 2^21 a job is one shard of two or three K0
 workgroups with a ragged last one, at 2^9 thirteen or more shards of one partial workgroup each.
 
@@ -16,9 +17,10 @@ import numpy as np
 import pytest
 
 from oracle import rv32_model
-from tests import _calltree_ref, _memory_ref, _oracle_prover, _profile_ref, _snapshot_ref, _watch_ref
+from tests import _calltree_ref, _diverge_ref, _memory_ref, _oracle_prover, _profile_ref, _snapshot_ref, _watch_ref
 from tests import guests_random as gr
 from tests.test_random_guests_cpu import FLOW, flow_positions, flow_queries, guest_of, run_of
+from tests.test_random_guests_slices_cpu import INPUT_IDS, chains_agree, check_origin, host_diverge, host_origin, input_guest, streams_of
 
 pytestmark = pytest.mark.gpu
 Q, POW = 8, 4
@@ -40,13 +42,15 @@ def provers():
 
 
 @contextlib.contextmanager
-def job_of(p, case, log_shard):
-    """(pk, vk, job) of a case prepared on a handle; the shard count and the cycles are the model's"""
-    run = run_of(case, log_shard)
-    pk, vk = p.setup(guest_of(case).elf)
+def job_of(p, case, log_shard, stdin=()):
+    """(pk, vk, job) of a case prepared on a handle; the shard count and the cycles are the model's.  stdin: the input buffers
+    of the case's guest with the input prologue (none: the guest without it)"""
+    guest = input_guest(case) if stdin else guest_of(case)
+    run = _profile_ref.model_run(guest.elf, stdin, log_shard)
+    pk, vk = p.setup(guest.elf)
     job = None
     try:
-        job, rep = p.prepare(pk, [])
+        job, rep = p.prepare(pk, list(stdin))
         assert p.job_shards(job) == len(run.shards) and rep["cycles"] == run.cycles and rep["halted"] and rep["exit_code"] == 0, (case, log_shard, rep)
         yield pk, vk, job
     finally:
@@ -113,6 +117,60 @@ def test_job_reports_are_the_models(provers, case, log_shard):
                 want = _snapshot_ref.take(run, at, ranges, 64)
                 _snapshot_ref.same(snap, want, "%s at %s" % (where, at))
                 _snapshot_ref.agrees(snap, _snapshot_ref.state_at(guest.elf, (), log_shard, want["summary"]["position"]), run, where)
+
+
+def _without_ms(got, passes=None):
+    s = {k: v for k, v in got["summary"].items() if k != "ms"}
+    return dict(got, summary=s if passes is None else dict(s, passes=passes))
+
+
+@pytest.mark.parametrize("log_shard", LOGS)
+@pytest.mark.parametrize("case", gr.CASES, ids=CASE_IDS)
+def test_job_origins_are_the_models(provers, case, log_shard):
+    """origin_reduce_kernel and origin_gather_kernel on five of the pool registers, ra in the flow cases and four of the most
+    stored scratch words (the subset is the seed's), from four positions of the random part and from the exit, follow_addr off
+    and on: against the rule over the model's rows, passes = the sum of ceil(level questions / 256), both yardsticks, and the
+    host path dict for dict"""
+    p = provers[log_shard]
+    host = host_origin(case, log_shard)
+    with job_of(p, case, log_shard) as (pk, vk, job):
+        def call(at, target, follow):
+            got = p.job_origin(pk, job, at, target, follow_addr=follow)
+            assert _without_ms(host(at, target, follow)) == _without_ms(got, passes=0), (gr.case_id(case), log_shard, at, target, follow)
+            return got
+        slices, edges, roots = check_origin(call, case, log_shard, subset=True, device=True)
+    print(gr.case_id(case), "2^%d" % log_shard, "slices", slices, "edges checked", edges, "roots compared", roots)
+    assert slices >= 2 * (4 * (5 if case[1] == "alu" else 9) + 5) and edges > 500 and roots == slices
+
+
+@pytest.mark.parametrize("log_shard", LOGS)
+@pytest.mark.parametrize("entry", gr.INPUT_CASES, ids=INPUT_IDS)
+def test_job_divergence_is_the_models(provers, entry, log_shard):
+    """diverge_classify_kernel, diverge_merge_kernel and diverge_emit_kernel on two jobs of one guest with the input prologue: the
+    whole chain of segments against the rule over the model's two runs and against the host path, and one report with keep = 64"""
+    p = provers[log_shard]
+    a, b = gr.inputs_of(entry)
+    sa, sb = streams_of(entry, log_shard)
+    where = "%s at 2^%d" % (gr.input_case_id(entry), log_shard)
+    host = host_diverge(entry, log_shard)
+    with job_of(p, entry[0], log_shard, stdin=(a,)) as (pk, vk, job_a):
+        job_b, rep = p.prepare(pk, [b])
+        try:
+            assert rep["cycles"] == len(sb) and rep["halted"] and rep["exit_code"] == 0 and p.job_shards(job_b) == len(sb.sizes), (where, rep)
+            got = _diverge_ref.chain(sa, sb, 64, keep=16, call=lambda **kw: p.job_diverge(pk, job_a, job_b, **kw))
+            wide = p.job_diverge(pk, job_a, job_b, keep=64)
+        finally:
+            p.job_free(job_b)
+    want = _diverge_ref.chain(sa, sb, 64, keep=16)
+    chains_agree(got, want, where)
+    held = _diverge_ref.chain(sa, sb, 64, keep=16, call=host)
+    assert len(held) == len(got), where
+    for k, (g, w, h) in enumerate(zip(got, want, held)):
+        assert _diverge_ref.without(g) == _diverge_ref.without(h), (where, k)
+        s = w["summary"]
+        assert g["summary"]["launched_pairs"] >= s["n_pairs"] + (s["reason"] in (_diverge_ref.SPLIT, _diverge_ref.BAD)), (where, k)
+    _diverge_ref.same(wide, _diverge_ref.report(sa, sb, keep=64), where + ", keep 64 from the entry")
+    assert _diverge_ref.without(wide) == _diverge_ref.without(host(keep=64)), where
 
 
 def _prove_and_verify(p, case):
