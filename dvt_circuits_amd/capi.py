@@ -199,6 +199,10 @@ def load():
     lib.dvt_rv32_job_origin.argtypes = [vp, vp, vp] + origin_io
     lib.dvt_rv32_job_origin_times.argtypes = [vp, C.POINTER(C.c_double)]
     lib.dvt_execute_origin.argtypes = [C.c_char_p, sz, C.POINTER(Buf), sz, u64, u32] + origin_io + [C.POINTER(Report), C.POINTER(C.c_char_p)]
+    uses_io = [u32, u32, u32, u32, u32, u32, u32, C.POINTER(UsesNode), sz, C.POINTER(UsesDef), sz, C.POINTER(UsesEdge), sz, C.POINTER(UsesSummary)]
+    lib.dvt_rv32_job_uses.argtypes = [vp, vp, vp] + uses_io
+    lib.dvt_rv32_job_uses_times.argtypes = [vp, C.POINTER(C.c_double)]
+    lib.dvt_execute_uses.argtypes = [C.c_char_p, sz, C.POINTER(Buf), sz, u64, u32] + uses_io + [C.POINTER(Report), C.POINTER(C.c_char_p)]
     diverge_io = [DivergePos, DivergePos, u64, u32, u32, sz, C.POINTER(DivergePair), C.POINTER(DivergePair), C.POINTER(DivergeReg), C.POINTER(DivergeSummary)]
     lib.dvt_rv32_job_diverge.argtypes = [vp, vp, vp, vp] + diverge_io
     lib.dvt_rv32_job_diverge_times.argtypes = [vp, C.POINTER(C.c_double)]
@@ -740,6 +744,73 @@ def execute_origin(elf: bytes, stdin=(), at=SNAP_EXIT, target=(DVT_ORIGIN_REG, 1
     rep, err, bufs = Report(), C.c_char_p(), _bufs(stdin)
     rc, got = _origin(lambda *io: lib.dvt_execute_origin(elf, len(elf), bufs, len(stdin), max_cycles, log_shard, *io, C.byref(rep), C.byref(err)),
                       at, target, follow_addr, depth, nodes, edges)
+    return rc, dict(cycles=rep.cycles, exit_code=rep.exit_code, halted=bool(rep.halted), unprovable=bool(rep.unprovable)), got, _take_str(lib, err)
+
+
+# ---- uses (csrc/uses.h)
+DVT_USES_MAX_NODES, DVT_USES_MAX_DEFS, DVT_USES_MAX_EDGES, DVT_USES_MAX_DEPTH, DVT_USES_MAX_FAN, DVT_USES_DEFAULT_FAN = 1024, 4096, 8192, 64, 16, 8
+DVT_USES_PASS_DEFS, DVT_USES_SPAN = 256, 4096
+DVT_USES_NONE = 0xFFFFFFFF
+DVT_USES_REG, DVT_USES_WORD = 1, 2
+DVT_USES_FOLLOW_ADDR = 1
+DVT_USES_OP, DVT_USES_LOAD, DVT_USES_STORE, DVT_USES_CALL, DVT_USES_SYSCALL = 1, 2, 3, 4, 5
+DVT_USES_ADDR, DVT_USES_RS1, DVT_USES_RS2, DVT_USES_MEM = 1, 2, 3, 4
+DVT_USES_LIVE_AT_EXIT, DVT_USES_TRUNCATED, DVT_USES_NO_VALUE, DVT_USES_CUT, DVT_USES_UNEXPANDED = 1, 2, 4, 8, 16
+
+
+class UsesNode(C.Structure):
+    _fields_ = [(name, C.c_uint32) for name in ("shard", "row", "pc", "idx", "kind", "depth", "first_def", "n_defs", "flags", "rd_value", "rs1", "rs2",
+                                                "addr", "before", "after", "pad")]
+
+
+class UsesDef(C.Structure):
+    _fields_ = [("n_uses", C.c_uint64)] + [(name, C.c_uint32) for name in ("node", "what", "target", "value", "flags", "next_shard", "next_row",
+                                                                            "first_edge", "n_edges", "pad")]
+
+
+class UsesEdge(C.Structure):
+    _fields_ = [(name, C.c_uint32) for name in ("def", "to", "role", "flags", "dst_shard", "dst_row")]
+
+
+class UsesSummary(C.Structure):
+    _fields_ = [("position", C.c_uint64), ("cycles", C.c_uint64), ("uses_total", C.c_uint64)] + \
+               [(name, C.c_uint32) for name in ("n_nodes", "n_defs", "n_edges", "depth", "cut", "unexpanded", "truncated", "live_at_exit", "no_value", "dead",
+                                                "levels", "passes", "shard", "row", "shards_total", "span")] + [("ms", C.c_float), ("pad", C.c_uint32)]
+
+
+def uses_reg(k):
+    """the target of a uses call: register x_k (a number 1..31 or a name of REG_NAMES)"""
+    return DVT_USES_REG, REG_NAMES.index(k) if isinstance(k, str) else int(k)
+
+
+def uses_word(addr):
+    """the target of a uses call: the word that holds the byte at addr"""
+    return DVT_USES_WORD, addr & ~3
+
+
+def _uses(call, at, target, follow_addr, depth, fan, nodes, defs, edges):
+    """The forward slice through call(shard, row, what, target, flags, max_depth, fan, nodes, cap_nodes, defs, cap_defs, edges,
+    cap_edges, summary) -> rc.  Returns (rc, dict(summary, nodes = node dicts in discovery order, defs = definition dicts, defs[0]
+    the root, edges = edge dicts) or None when the call fails without an answer)."""
+    ns, ds, es, s = (UsesNode * max(nodes, 1))(), (UsesDef * max(defs, 1))(), (UsesEdge * max(edges, 1))(), UsesSummary()
+    rc = call(at[0], at[1], target[0], target[1], DVT_USES_FOLLOW_ADDR if follow_addr else 0, depth, fan, ns, nodes, ds, defs, es, edges, C.byref(s))
+    if rc not in (DVT_OK, DVT_ERR_GUEST):
+        return rc, None
+    summary = {name: (float if name == "ms" else int)(getattr(s, name)) for name, _ in UsesSummary._fields_ if name != "pad"}
+    rows = lambda arr, cls, n: [{name: int(getattr(arr[i], name)) for name, _ in cls._fields_ if name != "pad"} for i in range(n)]
+    return rc, dict(summary=summary, nodes=rows(ns, UsesNode, summary["n_nodes"]), defs=rows(ds, UsesDef, summary["n_defs"]),
+                    edges=rows(es, UsesEdge, summary["n_edges"]))
+
+
+def execute_uses(elf: bytes, stdin=(), at=SNAP_EXIT, target=(DVT_USES_REG, 10), follow_addr=False, depth=DVT_USES_MAX_DEPTH, fan=DVT_USES_DEFAULT_FAN,
+                 nodes=DVT_USES_MAX_NODES, defs=DVT_USES_MAX_DEFS, edges=DVT_USES_MAX_EDGES, max_cycles=0, log_shard=21):
+    """Host-only forward slice (dvt_execute_uses): the guest runs in shards of 2^log_shard cycles; who reads the value `target`
+    (uses_reg() / uses_word()) holds from the record at `at` = (shard, row) on, and what those readers produce.  Returns (rc,
+    report dict as execute() gives it, dict(summary, nodes, defs, edges) as Prover.job_uses gives it or None, error text)."""
+    lib = load()
+    rep, err, bufs = Report(), C.c_char_p(), _bufs(stdin)
+    rc, got = _uses(lambda *io: lib.dvt_execute_uses(elf, len(elf), bufs, len(stdin), max_cycles, log_shard, *io, C.byref(rep), C.byref(err)),
+                    at, target, follow_addr, depth, fan, nodes, defs, edges)
     return rc, dict(cycles=rep.cycles, exit_code=rep.exit_code, halted=bool(rep.halted), unprovable=bool(rep.unprovable)), got, _take_str(lib, err)
 
 
@@ -1540,6 +1611,25 @@ class Prover:
         out = (C.c_double * 3)()
         self.check(self.lib.dvt_rv32_job_origin_times(self.h, out))
         return dict(reduce_ms=out[0], gather_ms=out[1], host_ms=out[2])
+
+    def job_uses(self, pk, job, at, target, follow_addr=False, depth=DVT_USES_MAX_DEPTH, fan=DVT_USES_DEFAULT_FAN, nodes=DVT_USES_MAX_NODES,
+                 defs=DVT_USES_MAX_DEFS, edges=DVT_USES_MAX_EDGES):
+        """Who reads the value `target` (uses_reg() / uses_word()) holds from the record at `at` = (shard, row) of a prepared job on,
+        and what those readers produce: the forward data-flow slice over the cycle records the job holds on the GPU
+        (dvt_rv32_job_uses; the rule: csrc/uses.h), dict(summary, nodes, defs, edges).  defs[0] is the root definition; a
+        definition has its next writer (next_shard, next_row), the exact n_uses and its first min(fan, n_uses) uses
+        edges[first_edge : first_edge + n_edges]; an edge's `to` is the consumer's node (or DVT_USES_NONE with CUT), whose own
+        definitions are defs[first_def : first_def + n_defs].  depth <= 64, fan 1..16, nodes <= 1024, defs <= 4096, edges <= 8192."""
+        rc, got = _uses(lambda *io: self.lib.dvt_rv32_job_uses(self.h, pk, job, *io), at, target, follow_addr, depth, fan, nodes, defs, edges)
+        self.check(rc)
+        return got
+
+    def job_uses_times(self):
+        """of the last job_uses: dict(next_ms, count_ms (count and scan), emit_ms, gather_ms (stream events summed over members,
+        levels and passes), host_ms)"""
+        out = (C.c_double * 5)()
+        self.check(self.lib.dvt_rv32_job_uses_times(self.h, out))
+        return dict(next_ms=out[0], count_ms=out[1], emit_ms=out[2], gather_ms=out[3], host_ms=out[4])
 
     def job_diverge(self, pk, job_a, job_b, start_a=DIVERGE_ENTRY, start_b=DIVERGE_ENTRY, max_pairs=0, rejoin=False, window=0, keep=16):
         """Where two prepared jobs of this handle (two executions of pk's guest; job_a may be job_b) part ways, from the cycle records

@@ -269,7 +269,7 @@ int stage_table(dvt_prover *p, const char *machine, uint32_t chip, const uint32_
 
 extern "C" {
 
-uint32_t dvt_abi_version(void) { return 20; }
+uint32_t dvt_abi_version(void) { return 21; }
 
 int dvt_prover_create(const char *cfg_json, dvt_prover **out) {
     if (!out) return fail(nullptr, DVT_ERR_INPUT, "out == NULL");

@@ -104,6 +104,7 @@ struct dvt_prover {
     double watch_ms[4] = {};          // the last dvt_rv32_job_watch: count, scan and emit launches by stream events, the shards the emit pass ran over (dvt_rv32_job_watch_times)
     double snap_ms[3] = {};           // the last dvt_rv32_job_snapshot: reduce, gather and backtrace launches by stream events (dvt_rv32_job_snapshot_times)
     double diverge_ms[4] = {};        // the last dvt_rv32_job_diverge: classify, merge, emit + gather launches by stream events, the host's share (dvt_rv32_job_diverge_times)
+    double uses_ms[5] = {};           // the last dvt_rv32_job_uses: next, count + scan, emit and gather launches by stream events, the host's share (dvt_rv32_job_uses_times)
     double origin_ms[3] = {};         // the last dvt_rv32_job_origin: reduce and gather launches by stream events, the host's share (dvt_rv32_job_origin_times)
     size_t vq_chunk_words = 0;       // proof words per chunk of the device verifier ("verify_chunk_words", default vq::CHUNK_WORDS)
     std::string err;

@@ -1,9 +1,10 @@
 // The record reports of the C ABI (include/dvt_prover.h): what reads the cycle records a prepared job holds in HBM instead of its
 // trace rows.  The execution report (profile.h), the call-tree report (calltree.h) and the memory report (memreport.h) count
 // over them; the watchpoint search (watch.h) returns the ones that match; the snapshot (snapshot.h) reduces them to the state of
-// the machine at one position; the origin search (origin.h) follows one value back through them; the divergence report (diverge.h)
-// holds the records of two jobs side by side.  Each has a job entry point (dvt_rv32_job_*), which runs on lane 0 of every member that
-// holds shards, and a host-only one (dvt_execute_*) with the same rule over the executor's records (execute_traced).
+// the machine at one position; the origin search (origin.h) follows one value back through them and the uses search (uses.h)
+// forward; the divergence report (diverge.h) holds the records of two jobs side by side.  Each has a job entry point
+// (dvt_rv32_job_*), which runs on lane 0 of every member that holds shards, and a host-only one (dvt_execute_*) with the same
+// rule over the executor's records (execute_traced).
 #include <algorithm>
 #include <type_traits>
 
@@ -14,6 +15,7 @@
 #include "origin.h"
 #include "profile.h"
 #include "snapshot.h"
+#include "uses.h"
 #include "watch.h"
 
 using namespace dvt;
@@ -933,6 +935,268 @@ static int job_origin(dvt_prover *p, const dvt_pk *pk, dvt_job *j, uint32_t shar
     return DVT_OK;
 }
 
+// ------------------------------------------------------------------ uses (dvt_rv32_job_uses)
+// uses::Search runs the rule on the host and asks its definitions level by level.  A level is answered in chunks of
+// DVT_USES_PASS_DEFS sorted definitions.  Per chunk every member that holds records at or after the chunk's smallest F runs the
+// next pass over them on lane 0's stream into its own winners, and the host merges them with min.  With the windows [F, N] known,
+// every member that holds records in [min F, max N] counts the uses per span, scans the spans in execution order and emits its
+// own first `fan` uses and its total per definition; the host sums the totals and keeps the fan smallest positions of the union.
+// The consumers' records come from the member that holds each one's shard (origin.hip's gather, one fetch per distinct position
+// of the level).
+namespace {
+struct UsesMember {
+    StageBuf base;
+    unsigned long long *d_win = nullptr, *d_bad = nullptr, *d_from = nullptr, *d_next = nullptr, *d_carry = nullptr, *d_out_pos = nullptr;
+    rv32::CycleRec *d_recs = nullptr;        // [MAX_EDGES]
+    OriginFetch *d_fetch = nullptr;          // [MAX_EDGES]
+    UsesItem *d_items = nullptr;             // [PASS_DEFS * MAX_FAN]
+    uint32_t *d_target = nullptr, *d_out_role = nullptr, *d_n_items = nullptr, *d_table = nullptr;
+    const uint32_t *d_statics = nullptr, *d_ostat = nullptr;
+    size_t table_rows = 0;                   // the spans of the shards the member holds
+    std::vector<const Held *> shards;        // in execution order
+    std::vector<OriginFetch> fetch;
+    std::vector<rv32::CycleRec> got;
+    EventSpan t_next, t_count, t_emit, t_gather;
+    explicit UsesMember(DevPool &pool) : base{pool} {}
+};
+}  // namespace
+
+static int job_uses(dvt_prover *p, const dvt_pk *pk, dvt_job *j, uint32_t shard, uint32_t row, uint32_t what, uint32_t target, uint32_t flags,
+                    uint32_t max_depth, uint32_t fan, dvt_uses_node *nodes, size_t cap_nodes, dvt_uses_def *defs, size_t cap_defs, dvt_uses_edge *edges,
+                    size_t cap_edges, dvt_uses_summary *summary) {
+    if (int rc = same_members(p, pk, j)) return rc;
+    if (int rc = whole_execution(p, j, "uses of a value")) return rc;
+    const auto t0 = Clock::now();
+    const rv32::Program &prog = pk->prog;
+    constexpr size_t PD = uses::PASS_DEFS, SPAN = uses::SPAN, MAX_ITEMS = PD * uses::MAX_FAN;
+    MemberRun<UsesMember> run(p);   // (declared first: however the call ends, member 0's device is current again)
+    const std::vector<Held> held = held_in_order(j);
+    std::vector<uint64_t> shard_n(held.size());
+    uint64_t cycles = 0, position = 0;
+    for (const Held &h : held) {
+        const ShardJob &s = *h.s;
+        if (s.n_recs > 0xffffffffull) return fail(p, DVT_ERR_INPUT, "shard %zu has %zu records", h.pos, s.n_recs);
+        shard_n[h.pos] = s.n_recs;
+        cycles += s.n_recs;
+        position += s.index < shard ? s.n_recs : s.index == shard ? std::min<uint64_t>(s.n_recs, row) : 0;
+        run[h.m].shards.push_back(&h);
+        run[h.m].table_rows += (s.n_recs + SPAN - 1) / SPAN;
+    }
+    const watch::Statics statics(prog);
+    const origin::Statics ostat(prog);
+    const watch::Shapes shapes = watch::shapes();
+    const size_t n = statics.n();
+    // a member's buffer: win | bad | from | next | carry | out_pos | fetched records | fetch items | span items | target | out_role |
+    // n_items | the static words | the count table
+    auto buffers = [&](const Lane &c, UsesMember &um) {
+        if (um.base.ptr) return DVT_OK;
+        Engine &e = c.eng;
+        const size_t bytes = (4 * PD + 2 + MAX_ITEMS) * 8 + uses::MAX_EDGES * (sizeof(rv32::CycleRec) + sizeof(OriginFetch)) + MAX_ITEMS * sizeof(UsesItem) +
+                             (PD + MAX_ITEMS + 4) * 4 + statics.bytes() + n * 4 + um.table_rows * PD * 4;
+        HIP_TRY(c.err, e.pool.alloc_bytes(&um.base.ptr, bytes));
+        um.d_win = static_cast<unsigned long long *>(um.base.ptr);
+        um.d_bad = um.d_win + PD;
+        um.d_from = um.d_bad + 2;                                                  // (the records behind stay 16-byte aligned)
+        um.d_next = um.d_from + PD;
+        um.d_carry = um.d_next + PD;
+        um.d_out_pos = um.d_carry + PD;
+        um.d_recs = reinterpret_cast<rv32::CycleRec *>(um.d_out_pos + MAX_ITEMS);
+        um.d_fetch = reinterpret_cast<OriginFetch *>(um.d_recs + uses::MAX_EDGES);
+        um.d_items = reinterpret_cast<UsesItem *>(um.d_fetch + uses::MAX_EDGES);
+        um.d_target = reinterpret_cast<uint32_t *>(um.d_items + MAX_ITEMS);
+        um.d_out_role = um.d_target + PD;
+        um.d_n_items = um.d_out_role + MAX_ITEMS;
+        uint32_t *d_stat = um.d_n_items + 4;
+        um.d_statics = d_stat;
+        um.d_ostat = d_stat + 2 * n;
+        um.d_table = d_stat + 3 * n;
+        HIP_TRY(c.err, hipMemcpyAsync(d_stat, statics.words.data(), statics.bytes(), hipMemcpyHostToDevice, e.stream));
+        HIP_TRY(c.err, hipMemcpyAsync(d_stat + 2 * n, ostat.words.data(), n * 4, hipMemcpyHostToDevice, e.stream));
+        return DVT_OK;
+    };
+    // the spans of shard s that hold a position in [lo, hi]: {first, count}
+    auto spans_in = [&](const ShardJob &s, unsigned long long lo, unsigned long long hi) {
+        if (!s.n_recs) return std::pair<uint32_t, uint32_t>{0, 0};
+        const unsigned long long first_pos = watch::position(s.index, 0), last_pos = watch::position(s.index, (uint32_t)(s.n_recs - 1));
+        if (hi < first_pos || lo > last_pos) return std::pair<uint32_t, uint32_t>{0, 0};
+        const uint32_t r0 = lo > first_pos ? (uint32_t)lo : 0, r1 = hi < last_pos ? (uint32_t)hi : (uint32_t)(s.n_recs - 1);
+        return std::pair<uint32_t, uint32_t>{(uint32_t)(r0 / SPAN), (uint32_t)(r1 / SPAN - r0 / SPAN + 1)};
+    };
+
+    double ms[4] = {0, 0, 0, 0};
+    uint64_t bad = 0;
+    uint32_t passes = 0;
+    int rc_answer = DVT_OK;
+    auto answer = [&](const std::vector<uses::Def> &qs, std::vector<uses::Found> *found) {
+        std::vector<uint32_t> order(qs.size());
+        for (size_t i = 0; i < order.size(); i++) order[i] = (uint32_t)i;
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return origin::sorts_before(qs[x], qs[y]); });
+        std::vector<unsigned long long> one(PD + 1), d_from(PD), d_next(PD), carry(PD + MAX_ITEMS);
+        std::vector<uint32_t> d_target(PD), out_role(MAX_ITEMS);
+        struct Kept { unsigned long long pos; uint32_t role; };
+        std::vector<std::vector<Kept>> kept(qs.size());
+        for (size_t at = 0; at < order.size(); at += PD) {
+            const size_t n_d = std::min(PD, order.size() - at);
+            UsesArgs args{};
+            args.sh = shapes;
+            args.n_instr = (uint32_t)n; args.text_base = prog.text_base; args.n_d = (uint32_t)n_d; args.flags = flags; args.fan = fan;
+            args.min_from = uses::NO_POS;
+            uint32_t n_regs = 0;
+            for (size_t i = 0; i < n_d; i++) {
+                const uses::Def &q = qs[order[at + i]];
+                d_target[i] = q.target; d_from[i] = q.Q; d_next[i] = uses::NO_POS;
+                args.min_from = std::min(args.min_from, q.Q);
+                if (q.what == DVT_USES_REG) n_regs++;
+            }
+            for (uint32_t k = 0; k <= 32; k++) {   // the first register definition with a register >= k (they are sorted)
+                uint32_t f = 0;
+                while (f < n_regs && d_target[f] < k) f++;
+                args.reg_off[k] = f;
+            }
+            passes++;
+            // ---- next: the first writer at or after F, per member, merged with min
+            rc_answer = for_members(p, [&](size_t m, const Lane &c) {
+                Engine &e = c.eng;
+                UsesMember &um = run[m];
+                bool any = false;
+                for (const Held *h : um.shards) any = any || spans_in(*h->s, args.min_from, uses::NO_POS).second;
+                if (!any) return DVT_OK;
+                if (int rc = buffers(c, um)) return rc;
+                HIP_TRY(c.err, hipMemsetAsync(um.d_win, 0xff, PD * 8, e.stream));
+                HIP_TRY(c.err, hipMemsetAsync(um.d_bad, 0, 8, e.stream));
+                HIP_TRY(c.err, hipMemcpyAsync(um.d_from, d_from.data(), n_d * 8, hipMemcpyHostToDevice, e.stream));
+                HIP_TRY(c.err, hipMemcpyAsync(um.d_target, d_target.data(), n_d * 4, hipMemcpyHostToDevice, e.stream));
+                UsesArgs a = args;
+                a.statics = um.d_statics; a.offs = um.d_statics + n; a.ostat = um.d_ostat; a.d_target = um.d_target; a.d_from = um.d_from; a.d_next = um.d_next;
+                HIP_TRY(c.err, um.t_next.begin(e.stream));
+                for (const Held *h : um.shards) {
+                    const auto sp = spans_in(*h->s, args.min_from, uses::NO_POS);
+                    a.shard = h->s->index;
+                    HIP_TRY(c.err, launch_uses_next(e.stream, h->s->d_recs, h->s->n_recs, sp.first, sp.second, a, um.d_win, um.d_bad));
+                }
+                HIP_TRY(c.err, um.t_next.end(e.stream));
+                if (!e.download(one.data(), um.d_win, (PD + 1) * 8)) return engine_fail(c.err, e);
+                ms[0] += um.t_next.ms();
+                bad += one[PD];
+                for (size_t i = 0; i < n_d; i++) d_next[i] = std::min(d_next[i], one[i]);
+                return DVT_OK;
+            });
+            if (rc_answer) return false;
+            if (bad) return true;   // (the call fails below: no record is read again)
+            args.max_next = 0;
+            for (size_t i = 0; i < n_d; i++) {
+                (*found)[order[at + i]].next = d_next[i];
+                args.max_next = std::max(args.max_next, d_next[i]);
+            }
+            // ---- count, scan, emit: every member's own totals and first `fan` uses
+            rc_answer = for_members(p, [&](size_t m, const Lane &c) {
+                Engine &e = c.eng;
+                UsesMember &um = run[m];
+                bool any = false;
+                for (const Held *h : um.shards) any = any || spans_in(*h->s, args.min_from, args.max_next).second;
+                if (!any) return DVT_OK;
+                if (int rc = buffers(c, um)) return rc;
+                HIP_TRY(c.err, hipMemcpyAsync(um.d_from, d_from.data(), n_d * 8, hipMemcpyHostToDevice, e.stream));
+                HIP_TRY(c.err, hipMemcpyAsync(um.d_target, d_target.data(), n_d * 4, hipMemcpyHostToDevice, e.stream));
+                HIP_TRY(c.err, hipMemcpyAsync(um.d_next, d_next.data(), n_d * 8, hipMemcpyHostToDevice, e.stream));
+                HIP_TRY(c.err, hipMemsetAsync(um.d_carry, 0, PD * 8, e.stream));
+                HIP_TRY(c.err, hipMemsetAsync(um.d_n_items, 0, 16, e.stream));
+                UsesArgs a = args;
+                a.statics = um.d_statics; a.offs = um.d_statics + n; a.ostat = um.d_ostat; a.d_target = um.d_target; a.d_from = um.d_from; a.d_next = um.d_next;
+                HIP_TRY(c.err, um.t_count.begin(e.stream));
+                size_t table_row = 0;
+                for (const Held *h : um.shards) {
+                    const auto sp = spans_in(*h->s, args.min_from, args.max_next);
+                    a.shard = h->s->index;
+                    HIP_TRY(c.err, launch_uses_count(e.stream, h->s->d_recs, h->s->n_recs, sp.first, sp.second, a, um.d_table, table_row, um.table_rows));
+                    table_row += sp.second;
+                }
+                table_row = 0;
+                for (const Held *h : um.shards) {
+                    const auto sp = spans_in(*h->s, args.min_from, args.max_next);
+                    HIP_TRY(c.err, launch_uses_scan(e.stream, um.d_table, table_row, sp.second, um.table_rows, h->s->d_recs, h->s->n_recs, h->s->index, sp.first,
+                                                    (uint32_t)n_d, fan, um.d_carry, um.d_items, um.d_n_items, (uint32_t)(n_d * fan)));
+                    table_row += sp.second;
+                }
+                HIP_TRY(c.err, um.t_count.end(e.stream));
+                um.t_emit.begin_at_end_of(um.t_count);
+                HIP_TRY(c.err, launch_uses_emit(e.stream, um.d_items, um.d_n_items, (uint32_t)(n_d * fan), a, um.d_out_pos, um.d_out_role));
+                HIP_TRY(c.err, um.t_emit.end(e.stream));
+                if (!e.download(out_role.data(), um.d_out_role, n_d * fan * 4)) return engine_fail(c.err, e);
+                if (!e.download(carry.data(), um.d_carry, (PD + n_d * fan) * 8)) return engine_fail(c.err, e);   // (carry | out_pos, adjacent)
+                const unsigned long long *out_pos = carry.data() + PD;
+                ms[1] += um.t_count.ms();
+                ms[2] += um.t_emit.ms();
+                for (size_t i = 0; i < n_d; i++) {
+                    const size_t qi = order[at + i];
+                    (*found)[qi].n_uses += carry[i];
+                    for (size_t r = 0; r < std::min<unsigned long long>(fan, carry[i]); r++) kept[qi].push_back(Kept{out_pos[i * fan + r], out_role[i * fan + r]});
+                }
+                return DVT_OK;
+            });
+            if (rc_answer) return false;
+        }
+        // ---- the fan smallest of the members' kept uses; gather: every distinct consumer from the member that holds its shard
+        std::map<unsigned long long, std::pair<size_t, size_t>> where;   // position -> (member, index among its fetches)
+        for (size_t m = 0; m < n_members(p); m++) run[m].fetch.clear();
+        for (size_t i = 0; i < qs.size(); i++) {
+            std::stable_sort(kept[i].begin(), kept[i].end(), [](const Kept &x, const Kept &y) { return x.pos != y.pos ? x.pos < y.pos : x.role < y.role; });
+            if (kept[i].size() > fan) kept[i].resize(fan);
+            for (const Kept &k : kept[i]) {
+                if (where.count(k.pos)) continue;
+                const uint32_t sh = (uint32_t)(k.pos >> 32), rw = (uint32_t)k.pos;
+                if (!sh || sh > held.size() || rw >= held[sh - 1].s->n_recs) {
+                    rc_answer = fail(p, DVT_ERR_DEVICE, "a use of the emit pass lies in no shard of the job");
+                    return false;
+                }
+                const Held &h = held[sh - 1];
+                where[k.pos] = {h.m, run[h.m].fetch.size()};
+                run[h.m].fetch.push_back(OriginFetch{h.s->d_recs, (uint32_t)h.s->n_recs, rw});
+            }
+        }
+        rc_answer = for_members(p, [&](size_t m, const Lane &c) {
+            Engine &e = c.eng;
+            UsesMember &um = run[m];
+            if (um.fetch.empty()) return DVT_OK;
+            if (um.fetch.size() > uses::MAX_EDGES) return fail(c.err, DVT_ERR_DEVICE, "more kept uses than edges");
+            if (int rc = buffers(c, um)) return rc;
+            HIP_TRY(c.err, hipMemcpyAsync(um.d_fetch, um.fetch.data(), um.fetch.size() * sizeof(OriginFetch), hipMemcpyHostToDevice, e.stream));
+            HIP_TRY(c.err, um.t_gather.begin(e.stream));
+            HIP_TRY(c.err, launch_origin_gather(e.stream, um.d_fetch, (uint32_t)um.fetch.size(), um.d_recs));
+            HIP_TRY(c.err, um.t_gather.end(e.stream));
+            um.got.resize(um.fetch.size());
+            if (!e.download(um.got.data(), um.d_recs, um.got.size() * sizeof(rv32::CycleRec))) return engine_fail(c.err, e);
+            ms[3] += um.t_gather.ms();
+            return DVT_OK;
+        });
+        if (rc_answer) return false;
+        for (size_t i = 0; i < qs.size(); i++)
+            for (const Kept &k : kept[i]) {
+                const auto &w = where[k.pos];
+                (*found)[i].uses.push_back(uses::Use{k.pos, k.role, run[w.first].got[w.second]});
+            }
+        return true;
+    };
+
+    uses::Search search(prog, statics, shapes, watch::position(shard, row), what, target, flags, max_depth, fan, nodes, cap_nodes, defs, cap_defs, edges,
+                        cap_edges);
+    const int rc = search.run(answer);
+    if (rc == 1) return rc_answer;
+    if (bad) return fail(p, DVT_ERR_INPUT, "%llu %s", (unsigned long long)bad, BAD_RECORD);
+    if (rc) return fail(p, DVT_ERR_DEVICE, "%s", search.why.c_str());
+    dvt_uses_summary s = search.s;
+    s.passes = passes;
+    s.position = position; s.cycles = cycles;
+    snap::locate(shard_n, position, &s.shard, &s.row);
+    s.shards_total = (uint32_t)held.size();
+    const double total = ms_since(t0);
+    s.ms = (float)total;
+    for (int i = 0; i < 4; i++) p->uses_ms[i] = ms[i];
+    p->uses_ms[4] = std::max(0.0, total - ms[0] - ms[1] - ms[2] - ms[3]);
+    *summary = s;
+    return DVT_OK;
+}
+
 // ------------------------------------------------------------------ divergence (dvt_rv32_job_diverge)
 // The host cuts the pairs [0, N) into segments in which each side stays inside one shard (at most shardsA + shardsB of them; with
 // equal starts one per shard) and numbers their spans in pair order.  A segment is classified on lane 0's stream of the member
@@ -1489,6 +1753,53 @@ int dvt_execute_origin(const uint8_t *elf, size_t elf_len, const dvt_buf *stdin_
             const auto t1 = Clock::now();
             origin::Search search(prog, k->wst, k->sh, k->P, what, target, flags, max_depth, nodes, cap_nodes, edges, cap_edges);
             search.run([&](const std::vector<origin::Question> &qs, std::vector<origin::Found> *found) { return k->answer(prog, qs, found); });
+            k->place(&search.s);
+            search.s.ms = (float)(ms + ms_since(t1));
+            *summary = search.s;
+            return nullptr;
+        },
+        log_shard_size ? log_shard_size : 21);
+    return bad && rc == DVT_ERR_UNSUPPORTED ? DVT_ERR_INPUT : rc;
+}
+
+// ---- uses (uses.h)
+int dvt_rv32_job_uses(dvt_prover *p, const dvt_pk *pk, dvt_job *job, uint32_t shard, uint32_t row, uint32_t what, uint32_t target, uint32_t flags,
+                      uint32_t max_depth, uint32_t fan, dvt_uses_node *nodes, size_t cap_nodes, dvt_uses_def *defs, size_t cap_defs,
+                      dvt_uses_edge *edges, size_t cap_edges, dvt_uses_summary *summary) {
+    if (!p || !pk || !job || !summary) return fail(p, DVT_ERR_INPUT, "null argument");
+    std::string text;
+    if (const char *why = uses::input_error(what, target, flags, max_depth, fan, nodes, cap_nodes, defs, cap_defs, edges, cap_edges, &text))
+        return fail(p, DVT_ERR_INPUT, "%s", why);
+    if (int rc = rv32_key(p, pk)) return rc;
+    Guard g(p); if (g.rc) return g.rc;
+    return job_uses(p, pk, job, shard, row, what, target, flags, max_depth, fan, nodes, cap_nodes, defs, cap_defs, edges, cap_edges, summary);
+}
+
+int dvt_rv32_job_uses_times(dvt_prover *p, double out[5]) { return times_of(p, &dvt_prover::uses_ms, out); }
+
+// host-only: the same search (uses::Search) over the records uses::Keeper keeps of execute_traced's shards
+int dvt_execute_uses(const uint8_t *elf, size_t elf_len, const dvt_buf *stdin_bufs, size_t nbuf, uint64_t max_cycles, uint32_t log_shard_size,
+                     uint32_t shard, uint32_t row, uint32_t what, uint32_t target, uint32_t flags, uint32_t max_depth, uint32_t fan, dvt_uses_node *nodes,
+                     size_t cap_nodes, dvt_uses_def *defs, size_t cap_defs, dvt_uses_edge *edges, size_t cap_edges, dvt_uses_summary *summary,
+                     dvt_report *report, char **err_text) {
+    if (err_text) *err_text = nullptr;
+    if (!elf || (nbuf && !stdin_bufs) || !summary) return DVT_ERR_INPUT;
+    std::string text;
+    if (execute_input_error(log_shard_size, uses::input_error(what, target, flags, max_depth, fan, nodes, cap_nodes, defs, cap_defs, edges, cap_edges, &text),
+                            &text, err_text))
+        return DVT_ERR_INPUT;
+    std::unique_ptr<uses::Keeper> k;
+    bool bad = false;
+    const int rc = execute_traced(
+        elf, elf_len, stdin_bufs, nbuf, max_cycles, report, err_text, [&](const rv32::Program &prog) { k.reset(new uses::Keeper(prog, shard, row)); },
+        [&](const rv32::Program &prog, const rv32::CycleRec *recs, size_t n, uint32_t) { k->scan(prog, recs, n, (uint32_t)k->shard_n.size() + 1); },
+        [&](const rv32::Program &prog, double ms) -> const char * {
+            if (k->too_many)
+                return "more than 2^24 cycle records at and after the position: prepare the job and ask dvt_rv32_job_uses, which reads them on the GPU";
+            if (k->bad) { bad = true; return BAD_RECORD; }
+            const auto t1 = Clock::now();
+            uses::Search search(prog, k->wst, k->sh, k->P, what, target, flags, max_depth, fan, nodes, cap_nodes, defs, cap_defs, edges, cap_edges);
+            search.run([&](const std::vector<uses::Def> &qs, std::vector<uses::Found> *found) { return k->answer(prog, qs, found, flags, fan); });
             k->place(&search.s);
             search.s.ms = (float)(ms + ms_since(t1));
             *summary = search.s;

@@ -1,11 +1,11 @@
 // dvt_prover_host — the reference's CLI verbs (src/main.rs:58-106) over the C ABI.
 //
 //   dvt_prover_host prove   --type T -i INPUT.json [-o PROOF] [--elf GUEST.elf] [--devices D0,D1,...] [--compact]
-//   dvt_prover_host execute --type T -i INPUT.json [--show-report] [--show-calls] [--show-memory] [--watch SPEC ...] [--snapshot S:R|exit [--dump ADDR+LEN ...] [--frames N]] [--origin SPEC [--depth N] [--nodes N] [--follow-addr]] [--elf GUEST.elf]
+//   dvt_prover_host execute --type T -i INPUT.json [--show-report] [--show-calls] [--show-memory] [--watch SPEC ...] [--snapshot S:R|exit [--dump ADDR+LEN ...] [--frames N]] [--origin SPEC [--depth N] [--nodes N] [--follow-addr]] [--uses SPEC [--depth N] [--fan N] [--nodes N] [--follow-addr]] [--elf GUEST.elf]
 //   dvt_prover_host verify  --type T -i PROOF [--elf GUEST.elf]
 //   dvt_prover_host compact --type T -i PROOF [-o PROOF] [--elf GUEST.elf]     (shared Merkle paths sent once: dvt_proof_compact)
 //   dvt_prover_host expand  --type T -i PROOF [-o PROOF] [--elf GUEST.elf]     (the inverse; verify takes either form)
-//   dvt_prover_host check   --type T -i INPUT.json [--show-report] [--show-calls] [--show-memory] [--watch SPEC ...] [--snapshot S:R|exit [--dump ADDR+LEN ...] [--frames N]] [--origin SPEC [--depth N] [--nodes N] [--follow-addr]] [--elf GUEST.elf] [--devices D0,D1,...]
+//   dvt_prover_host check   --type T -i INPUT.json [--show-report] [--show-calls] [--show-memory] [--watch SPEC ...] [--snapshot S:R|exit [--dump ADDR+LEN ...] [--frames N]] [--origin SPEC [--depth N] [--nodes N] [--follow-addr]] [--uses SPEC [--depth N] [--fan N] [--nodes N] [--follow-addr]] [--elf GUEST.elf] [--devices D0,D1,...]
 //
 // T = bad-share | finalization | bad-partial-key | bad-encrypted-share (clap names of CircuitType, :36-42).
 // The reference embeds the four guest ELFs at build time (include_elf!, :115-118); they cannot be built in
@@ -48,6 +48,14 @@
 // passes=N", one line per node in discovery order: "node K depth=D at=S:R pc=0xX kind=op|load|store|call|syscall rd=0xX rs1=0xX
 // rs2=0xX addr=0xX before=0xX after=0xX edges=FIRST+N flags=0xX", and one per edge, edge 0 the root: "edge K from=I to=J
 // role=root|addr|rs1|rs2|mem target=0xX value=0xX flags=0xX src=S:R" (-1: no node).
+// --uses S:R|exit, then :reg:NAME or :word:ADDR: who reads the value that register or word holds from the position on, and what
+// those readers produce (dvt_execute_uses on the host, dvt_rv32_job_uses on the GPU; csrc/uses.h).  --depth, --nodes and
+// --follow-addr as for --origin, --fan N (default 8, 1..16) the uses kept per definition.  One line "uses: position=N cycles=N
+// shard=S row=R nodes=N defs=N edges=N depth=N cut=N unexpanded=N truncated=N live_at_exit=N no_value=N dead=N uses_total=N
+// levels=N passes=N", one line per node in discovery order: "node K depth=D at=S:R pc=0xX kind=... rd=0xX rs1=0xX rs2=0xX
+// addr=0xX before=0xX after=0xX defs=FIRST+N flags=0xX", one per definition, definition 0 the root: "def K node=I what=reg|word
+// target=0xX value=0xX flags=0xX next=S:R uses=N edges=FIRST+N" (-1: no node, no next writer), and one per edge: "edge K def=I
+// to=J role=addr|rs1|rs2|mem flags=0xX dst=S:R".
 // diverge --type T -i A.json --against B.json --elf G [--host] [--from S:R --against-from S:R] [--rejoin N] [--keep K] [--log-shard L]
 // [--devices D0,D1,...]: where the runs of one guest on two inputs part ways (dvt_rv32_job_diverge on two prepared jobs of one handle,
 // with --host dvt_execute_diverge; csrc/diverge.h).  One block per lock-step segment: "diverge: pairs=N reason=split|bad|end_both|end_a|
@@ -330,6 +338,35 @@ template <class Call> static int print_origin(size_t cap_nodes, Call call) {
     return 0;
 }
 
+// the uses block (call: dvt_execute_uses or dvt_rv32_job_uses with everything else bound)
+template <class Call> static int print_uses(size_t cap_nodes, Call call) {
+    static const char *kinds[] = {"?", "op", "load", "store", "call", "syscall"}, *roles[] = {"?", "addr", "rs1", "rs2", "mem"};
+    std::vector<dvt_uses_node> nodes(std::max<size_t>(cap_nodes, 1));
+    std::vector<dvt_uses_def> defs(DVT_USES_MAX_DEFS);
+    std::vector<dvt_uses_edge> edges(DVT_USES_MAX_EDGES);
+    dvt_uses_summary s{};
+    if (int rc = call(nodes.data(), cap_nodes, defs.data(), defs.size(), edges.data(), edges.size(), &s)) return rc;
+    printf("uses: position=%llu cycles=%llu shard=%u row=%u nodes=%u defs=%u edges=%u depth=%u cut=%u unexpanded=%u truncated=%u live_at_exit=%u no_value=%u dead=%u uses_total=%llu levels=%u passes=%u\n",
+           (unsigned long long)s.position, (unsigned long long)s.cycles, s.shard, s.row, s.n_nodes, s.n_defs, s.n_edges, s.depth, s.cut, s.unexpanded, s.truncated,
+           s.live_at_exit, s.no_value, s.dead, (unsigned long long)s.uses_total, s.levels, s.passes);
+    for (uint32_t i = 0; i < s.n_nodes; i++) {
+        const dvt_uses_node &n = nodes[i];
+        printf("node %u depth=%u at=%u:%u pc=0x%08x kind=%s rd=0x%08x rs1=0x%08x rs2=0x%08x addr=0x%08x before=0x%08x after=0x%08x defs=%u+%u flags=0x%x\n", i,
+               n.depth, n.shard, n.row, n.pc, n.kind < 6 ? kinds[n.kind] : "?", n.rd_value, n.rs1, n.rs2, n.addr, n.before, n.after, n.first_def, n.n_defs,
+               n.flags);
+    }
+    for (uint32_t i = 0; i < s.n_defs; i++) {
+        const dvt_uses_def &d = defs[i];
+        printf("def %u node=%d what=%s target=0x%x value=0x%08x flags=0x%x next=%d:%d uses=%llu edges=%u+%u\n", i, (int)d.node, d.what == DVT_USES_REG ? "reg" : "word",
+               d.target, d.value, d.flags, (int)d.next_shard, (int)d.next_row, (unsigned long long)d.n_uses, d.first_edge, d.n_edges);
+    }
+    for (uint32_t i = 0; i < s.n_edges; i++) {
+        const dvt_uses_edge &e = edges[i];
+        printf("edge %u def=%u to=%d role=%s flags=0x%x dst=%u:%u\n", i, e.def, (int)e.to, e.role < 5 ? roles[e.role] : "?", e.flags, e.dst_shard, e.dst_row);
+    }
+    return 0;
+}
+
 // one block of the diverge verb (call: dvt_execute_diverge or dvt_rv32_job_diverge with everything else bound); the summary in *out
 template <class Call> static int print_diverge(size_t keep, Call call, dvt_diverge_summary *out) {
     static const char *REASONS[] = {"?", "split", "bad", "end_both", "end_a", "end_b", "limit"};
@@ -370,7 +407,7 @@ template <class Call> static int print_diverge(size_t keep, Call call, dvt_diver
 }
 
 int main(int argc, char **argv) {
-    if (argc < 2) return die("usage: dvt_prover_host prove|execute|verify|check|diverge|compact|expand --type T -i FILE [-o FILE] [--show-report] [--show-calls] [--show-memory] [--watch SPEC] [--snapshot S:R|exit] [--dump ADDR+LEN] [--frames N] [--origin SPEC] [--depth N] [--nodes N] [--follow-addr] [--compact] [--keep-trees] [--elf FILE] [--devices D0,D1,...] [--device D] [--against FILE] [--host] [--from S:R] [--against-from S:R] [--rejoin N] [--keep K] [--log-shard L]");
+    if (argc < 2) return die("usage: dvt_prover_host prove|execute|verify|check|diverge|compact|expand --type T -i FILE [-o FILE] [--show-report] [--show-calls] [--show-memory] [--watch SPEC] [--snapshot S:R|exit] [--dump ADDR+LEN] [--frames N] [--origin SPEC] [--uses SPEC] [--depth N] [--fan N] [--nodes N] [--follow-addr] [--compact] [--keep-trees] [--elf FILE] [--devices D0,D1,...] [--device D] [--against FILE] [--host] [--from S:R] [--against-from S:R] [--rejoin N] [--keep K] [--log-shard L]");
     const std::string verb = argv[1];
     std::string type, input, output, elf_path, schema_path, devices, verify_device;
     bool show_report = false, show_calls = false, show_memory = false, auth = false, compact = false, keep_trees = false;
@@ -380,7 +417,9 @@ int main(int argc, char **argv) {
     uint32_t snap_shard = 0, snap_row = 0;
     size_t snap_frames = 16;
     std::vector<dvt_snap_range> snap_ranges;
-    bool origin = false;
+    bool origin = false, uses = false;
+    OriginSpec uses_spec{};
+    uint32_t uses_fan = DVT_USES_DEFAULT_FAN;
     OriginSpec origin_spec{};
     uint32_t origin_depth = DVT_ORIGIN_MAX_DEPTH, origin_flags = 0;
     size_t origin_nodes = DVT_ORIGIN_MAX_NODES;
@@ -427,6 +466,12 @@ int main(int argc, char **argv) {
             if (!parse_origin(t, &origin_spec)) return die("no origin (S:R|exit, then :reg:NAME or :word:ADDR): " + t);
             origin = true;
         }
+        else if (a == "--uses") {
+            const std::string t = next();
+            if (!parse_origin(t, &uses_spec)) return die("no uses (S:R|exit, then :reg:NAME or :word:ADDR): " + t);
+            uses = true;
+        }
+        else if (a == "--fan") uses_fan = (uint32_t)strtoull(next().c_str(), nullptr, 0);
         else if (a == "--depth") origin_depth = (uint32_t)strtoull(next().c_str(), nullptr, 0);
         else if (a == "--nodes") origin_nodes = (size_t)strtoull(next().c_str(), nullptr, 0);
         else if (a == "--follow-addr") origin_flags |= DVT_ORIGIN_FOLLOW_ADDR;
@@ -610,6 +655,15 @@ int main(int argc, char **argv) {
                 }))
                 return die(std::string("Verification failed: ") + (oerr ? oerr : "?"));
         }
+        if (uses) {
+            char *uerr = nullptr;
+            if (print_uses(origin_nodes, [&](dvt_uses_node *nodes, size_t cap_nodes, dvt_uses_def *defs, size_t cap_defs, dvt_uses_edge *edges, size_t cap_edges,
+                                             dvt_uses_summary *s) {
+                    return dvt_execute_uses(elf.data(), elf.size(), &buf, 1, 0, 0, uses_spec.shard, uses_spec.row, uses_spec.what, uses_spec.target, origin_flags,
+                                            origin_depth, uses_fan, nodes, cap_nodes, defs, cap_defs, edges, cap_edges, s, nullptr, &uerr);
+                }))
+                return die(std::string("Verification failed: ") + (uerr ? uerr : "?"));
+        }
         return 0;
     }
 
@@ -684,6 +738,13 @@ int main(int argc, char **argv) {
                                            nodes, cap_nodes, edges, cap_edges, s);
             }))
             return die(std::string("Origin failed: ") + dvt_last_error(p));
+        if (uses &&
+            print_uses(origin_nodes, [&](dvt_uses_node *nodes, size_t cap_nodes, dvt_uses_def *defs, size_t cap_defs, dvt_uses_edge *edges, size_t cap_edges,
+                                         dvt_uses_summary *s) {
+                return dvt_rv32_job_uses(p, pk, job, uses_spec.shard, uses_spec.row, uses_spec.what, uses_spec.target, origin_flags, origin_depth, uses_fan, nodes,
+                                         cap_nodes, defs, cap_defs, edges, cap_edges, s);
+            }))
+            return die(std::string("Uses failed: ") + dvt_last_error(p));
         dvt_job_free(p, job);
         dvt_pk_free(p, pk);
         dvt_prover_destroy(p);

@@ -205,6 +205,29 @@ hipError_t launch_origin_reduce(hipStream_t st, const rv32::CycleRec *d_recs, si
                                 unsigned long long *d_bad_records);
 hipError_t launch_origin_gather(hipStream_t st, const OriginFetch *d_items, uint32_t n_items, rv32::CycleRec *d_out);
 
+// uses.hip
+// The passes of the uses search (uses.h), each over the spans [first_span, first_span + n_spans) of one shard (UsesArgs carries the
+// sorted definitions' device arrays, the offsets of the register definitions, the precompile shapes, the static words per
+// instruction and the shard's number).  next: the first writer of every definition's target at or after its F, as a position, by
+// atomicMin into d_win [a.n_d] (set to all ones by the caller); *d_bad_records (zeroed by the caller) counts the bad records at or
+// after a.min_from.  count: with a.d_next known, the uses of every definition per span, one row of 256 u32 per span into d_table
+// from row table_row on (every launched row is written in full).  scan: one workgroup over those rows in order, the running count
+// per definition carried in d_carry [256] (zeroed by the caller before the first shard), one UsesItem per (span, definition) that
+// holds a rank below fan appended to d_items, *d_n_items counts them (zeroed by the caller).  emit: one workgroup per item of a
+// fixed grid of cap_items; position and role of the ranks below fan into d_out_pos / d_out_role [a.n_d * a.fan].  The records are
+// only read.
+struct UsesArgs;
+struct UsesItem;
+hipError_t launch_uses_next(hipStream_t st, const rv32::CycleRec *d_recs, size_t n_recs, uint32_t first_span, uint32_t n_spans, const UsesArgs &a,
+                            unsigned long long *d_win, unsigned long long *d_bad_records);
+hipError_t launch_uses_count(hipStream_t st, const rv32::CycleRec *d_recs, size_t n_recs, uint32_t first_span, uint32_t n_spans, const UsesArgs &a,
+                             uint32_t *d_table, size_t table_row, size_t table_rows);
+hipError_t launch_uses_scan(hipStream_t st, const uint32_t *d_table, size_t table_row, uint32_t n_spans, size_t table_rows, const rv32::CycleRec *d_recs,
+                            size_t n_recs, uint32_t shard, uint32_t first_span, uint32_t n_d, uint32_t fan, unsigned long long *d_carry, UsesItem *d_items,
+                            uint32_t *d_n_items, uint32_t cap_items);
+hipError_t launch_uses_emit(hipStream_t st, const UsesItem *d_items, const uint32_t *d_n_items, uint32_t cap_items, const UsesArgs &a,
+                            unsigned long long *d_out_pos, uint32_t *d_out_role);
+
 // diverge.hip
 // The passes of the divergence report (diverge.h) over one segment of pairs (DivergeArgs: both record pointers at the segment's
 // first pair, a.n_pairs pairs, the pair number a.k0 and the span number a.span0 of its first span).  classify: one DivergeSpan and

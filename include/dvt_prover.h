@@ -131,7 +131,8 @@ void dvt_free(void *ptr);
  * dvt_rv32_job_calltree_times, dvt_execute_calltree; 15: dvt_rv32_job_memory, dvt_execute_memory;
  * 16: dvt_rv32_job_watch, dvt_execute_watch, dvt_rv32_job_watch_times; 17: dvt_rv32_job_snapshot,
  * dvt_rv32_job_snapshot_times, dvt_execute_snapshot; 18: dvt_rv32_debug_poke_cell; 19: dvt_rv32_job_origin, dvt_rv32_job_origin_times,
- * dvt_execute_origin; 20: dvt_rv32_job_diverge, dvt_rv32_job_diverge_times, dvt_execute_diverge) */
+ * dvt_execute_origin; 20: dvt_rv32_job_diverge, dvt_rv32_job_diverge_times, dvt_execute_diverge; 21: dvt_rv32_job_uses,
+ * dvt_rv32_job_uses_times, dvt_execute_uses) */
 uint32_t dvt_abi_version(void);
 /* the handle's hipStream_t (for event timing by the caller) */
 void *dvt_stream(dvt_prover *p);
@@ -1003,6 +1004,78 @@ int dvt_rv32_job_origin_times(dvt_prover *p, double out[3]);
 int dvt_execute_origin(const uint8_t *elf, size_t elf_len, const dvt_buf *stdin_bufs, size_t nbuf, uint64_t max_cycles, uint32_t log_shard_size,
                        uint32_t shard, uint32_t row, uint32_t what, uint32_t target, uint32_t flags, uint32_t max_depth, dvt_origin_node *nodes,
                        size_t cap_nodes, dvt_origin_edge *edges, size_t cap_edges, dvt_origin_summary *summary, dvt_report *report, char **err_text);
+/* Uses of a prepared job: the forward data-flow slice of one value, from the cycle records the job holds (the records are only
+ * read, nothing is executed again, the job is left as found).  The exact inverse of the origin relation above; the rule is stated
+ * in csrc/uses.h:
+ *   definition  (what, target, F): the value the register (DVT_USES_REG, 1..31) or the 4-aligned word below the address limit
+ *               (DVT_USES_WORD) holds from position F on.  Its next writer N is the first record at a position >= F that writes the
+ *               target as the origin search counts writers (rd == k, so ECALL writes t0; sw / sh / sb to the word; a call whose
+ *               written words contain it); without one next_shard = next_row = DVT_USES_NONE and the flag LIVE_AT_EXIT.
+ *   uses        every input edge (in the origin search's sense: roles ADDR, only with DVT_USES_FOLLOW_ADDR, RS1, RS2, MEM) of every
+ *               record at a position in [F, N] that names the target.  N itself is included; a record that reads a register as rs1
+ *               and as rs2 is two uses.  n_uses is exact; the first min(fan, n_uses) uses in execution order (within a record
+ *               ADDR, RS1, RS2, MEM) are edges[first_edge .. first_edge + n_edges), TRUNCATED when n_uses > fan.
+ *   defs        defs[0] is the root: node = DVT_USES_NONE, (what, target) as asked, F = the position ((0xffffffff, 0xffffffff):
+ *               the exit, which has no uses); its value is what its first kept use read, else NO_VALUE.  The definitions of a
+ *               node, F = its position + 1, in this order: rd when non-zero (value rd_value), the word of a store (value
+ *               `after`), every word a call writes, array 0 first (value 0, NO_VALUE).
+ *   edges       {def, to, role, flags, dst_shard, dst_row}: to = the consumer's node, or DVT_USES_NONE with CUT when cap_nodes was
+ *               reached; (dst_shard, dst_row) = the consumer's position.
+ *   nodes       one per consuming record in discovery order (breadth first: the definitions of level d give the nodes of depth
+ *               d + 1), the fields of an origin node, with defs[first_def .. first_def + n_defs) in place of its edges.  UNEXPANDED:
+ *               depth >= max_depth, or the node's definitions would take n_defs past cap_defs, or n_edges so far plus fan times
+ *               the definitions of the level past cap_edges.  The edges of a level are known only after its answers, so room for
+ *               fan edges is reserved per definition beforehand: the search may stop with fewer than cap_edges edges (never with
+ *               more), the sooner the larger fan is.  That node and every later one stay unexpanded, and the search ends after
+ *               the level's answers.  For the same reason cap_edges below fan is refused.
+ *   summary     n_nodes, n_defs, n_edges, depth; the edges with CUT, the nodes UNEXPANDED, the definitions TRUNCATED, LIVE_AT_EXIT,
+ *               NO_VALUE and dead (n_uses == 0); uses_total = the sum of n_uses; levels answered, device passes (ceil(definitions
+ *               of the level / DVT_USES_PASS_DEFS) per level; 0 on the host path); position / cycles / shard / row as the
+ *               snapshot's summary.
+ * Limits: data dependence only (a branch is a consumer and a leaf); the values of words a call wrote are not in the records.
+ * DVT_ERR_INPUT: what / target out of range, a flag other than FOLLOW_ADDR, fan outside 1..DVT_USES_MAX_FAN, a cap above its limit,
+ * cap_defs 0, cap_edges below fan, null arrays, a bad cycle record at or after the position.  DVT_ERR_UNSUPPORTED: a prepare_part job
+ * that does not hold every shard of its execution.  Handles with several members work. */
+#define DVT_USES_MAX_NODES 1024
+#define DVT_USES_MAX_DEFS 4096
+#define DVT_USES_MAX_EDGES 8192
+#define DVT_USES_MAX_DEPTH 64
+#define DVT_USES_MAX_FAN 16
+#define DVT_USES_DEFAULT_FAN 8
+#define DVT_USES_PASS_DEFS 256   /* definitions one device pass answers */
+#define DVT_USES_SPAN 4096       /* records one workgroup of a device pass reads */
+#define DVT_USES_NONE 0xffffffffu
+enum { DVT_USES_REG = 1, DVT_USES_WORD = 2 };                                                       /* what (= DVT_ORIGIN_*) */
+enum { DVT_USES_FOLLOW_ADDR = 1 };                                                                  /* flags of a call */
+enum { DVT_USES_OP = 1, DVT_USES_LOAD = 2, DVT_USES_STORE = 3, DVT_USES_CALL = 4, DVT_USES_SYSCALL = 5 };   /* node kinds (= DVT_ORIGIN_*) */
+enum { DVT_USES_ADDR = 1, DVT_USES_RS1 = 2, DVT_USES_RS2 = 3, DVT_USES_MEM = 4 };                   /* edge roles (= DVT_ORIGIN_*) */
+enum { DVT_USES_LIVE_AT_EXIT = 1, DVT_USES_TRUNCATED = 2, DVT_USES_NO_VALUE = 4, DVT_USES_CUT = 8, DVT_USES_UNEXPANDED = 16 };   /* flags of defs, edges and nodes */
+typedef struct { uint32_t shard, row, pc, idx, kind, depth, first_def, n_defs, flags, rd_value, rs1, rs2, addr, before, after, pad; } dvt_uses_node;
+typedef struct {
+    uint64_t n_uses;
+    uint32_t node, what, target, value, flags, next_shard, next_row, first_edge, n_edges, pad;
+} dvt_uses_def;
+typedef struct { uint32_t def, to, role, flags, dst_shard, dst_row; } dvt_uses_edge;
+typedef struct {
+    uint64_t position, cycles, uses_total;
+    uint32_t n_nodes, n_defs, n_edges, depth, cut, unexpanded, truncated, live_at_exit, no_value, dead, levels, passes, shard, row, shards_total, span;
+    float ms;          /* wall clock of the call after the entry guard */
+    uint32_t pad;
+} dvt_uses_summary;
+int dvt_rv32_job_uses(dvt_prover *p, const dvt_pk *pk, dvt_job *job, uint32_t shard, uint32_t row, uint32_t what, uint32_t target, uint32_t flags,
+                      uint32_t max_depth, uint32_t fan, dvt_uses_node *nodes, size_t cap_nodes, dvt_uses_def *defs, size_t cap_defs,
+                      dvt_uses_edge *edges, size_t cap_edges, dvt_uses_summary *summary);
+/* milliseconds of the last dvt_rv32_job_uses: the next, the count and scan, the emit and the gather launches by events on the
+ * members' streams, summed over members, levels and passes; the host's share (the wall clock of the call less those four) */
+int dvt_rv32_job_uses_times(dvt_prover *p, double out[5]);
+/* The same slice on the host alone (no GPU is touched), the guest run in shards of 2^log_shard_size cycles (0: 21; 4..22).  The
+ * records at and after the position are kept, 48 bytes per cycle: past 2^24 of them the call fails with DVT_ERR_UNSUPPORTED
+ * (dvt_rv32_job_uses is the way for such executions).  The definitions of a level are answered by one forward scan.  Return codes,
+ * *report and *err_text as dvt_execute gives them; the outputs are filled for whatever retired, also when the guest fails. */
+int dvt_execute_uses(const uint8_t *elf, size_t elf_len, const dvt_buf *stdin_bufs, size_t nbuf, uint64_t max_cycles, uint32_t log_shard_size,
+                     uint32_t shard, uint32_t row, uint32_t what, uint32_t target, uint32_t flags, uint32_t max_depth, uint32_t fan, dvt_uses_node *nodes,
+                     size_t cap_nodes, dvt_uses_def *defs, size_t cap_defs, dvt_uses_edge *edges, size_t cap_edges, dvt_uses_summary *summary,
+                     dvt_report *report, char **err_text);
 /* Divergence of two executions of one guest: where two prepared jobs of one handle (job_a == job_b is allowed) stop doing the
  * same thing, and which values differed before, from the cycle records both jobs hold (the records are only read, the jobs are
  * left as found).  The rule is stated in csrc/diverge.h:
