@@ -107,6 +107,151 @@ uint32_t default_log_slots(size_t n_instr) {
 constexpr const char *BAD_INSTR = "cycle records name an instruction outside the text";
 constexpr const char *BAD_RECORD = "cycle records name an instruction outside the text or an address outside guest memory";
 std::string sys_overflow() { return "more than " + std::to_string(prof::MAX_SYSCALLS) + " distinct syscall ids"; }
+
+// The shards of a whole execution (whole_execution() passed) in order, and the position P = (shard, row) among them: the number
+// of records before it, as the summaries report it.
+struct Placed {
+    std::vector<Held> held;
+    std::vector<uint64_t> shard_n;
+    uint64_t cycles = 0, position = 0;
+    int init(dvt_prover *p, dvt_job *j, uint32_t shard, uint32_t row) {
+        held = held_in_order(j);
+        shard_n.resize(held.size());
+        for (const Held &h : held) {
+            const ShardJob &s = *h.s;
+            if (s.n_recs > 0xffffffffull) return fail(p, DVT_ERR_INPUT, "shard %zu has %zu records", h.pos, s.n_recs);
+            shard_n[h.pos] = s.n_recs;
+            cycles += s.n_recs;
+            position += s.index < shard ? s.n_recs : s.index == shard ? std::min<uint64_t>(s.n_recs, row) : 0;
+        }
+        return DVT_OK;
+    }
+    // the shard that holds the record at position `where`, or nullptr
+    const Held *holder(unsigned long long where) const {
+        const uint32_t sh = (uint32_t)(where >> 32), rw = (uint32_t)where;
+        return sh && sh <= held.size() && rw < held[sh - 1].s->n_recs ? &held[sh - 1] : nullptr;
+    }
+    // position, cycles, shard, row and shards_total of a summary
+    template <class Summary>
+    void place(Summary *s) const {
+        s->position = position; s->cycles = cycles;
+        snap::locate(shard_n, position, &s->shard, &s->row);
+        s->shards_total = (uint32_t)held.size();
+    }
+};
+
+// One allocation cut into typed arrays.  A layout is a function that take()s its arrays in order: run over Carve{} it returns the
+// bytes to allocate (at), run over Carve{base} it hands out the pointers.
+struct Carve {
+    char *base = nullptr;
+    size_t at = 0;
+    template <class T>
+    T *take(size_t count, size_t align = alignof(T)) {
+        at = (at + align - 1) / align * align;
+        T *out = base ? reinterpret_cast<T *>(base + at) : nullptr;
+        at += count * sizeof(T);
+        return out;
+    }
+};
+
+// ---- what the origin search and the uses search share: both ask a level of sorted questions in chunks of one device pass, and
+// both read the records their answers name from the member that holds each one's shard.
+constexpr size_t PASS_Q = origin::PASS_Q;
+
+// The questions of a level in the order a pass takes them (origin::sorts_before), cut into chunks of at most PASS_Q.
+struct Chunks {
+    const std::vector<origin::Question> &qs;
+    std::vector<uint32_t> order;                // order[i]: the question at place i of the sorted level
+    std::vector<uint32_t> target;               // [PASS_Q], of the chunk cut last
+    std::vector<unsigned long long> pos;        // [PASS_Q], of the chunk cut last
+    explicit Chunks(const std::vector<origin::Question> &qs) : qs(qs), order(qs.size()), target(PASS_Q), pos(PASS_Q) {
+        for (size_t i = 0; i < order.size(); i++) order[i] = (uint32_t)i;
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return origin::sorts_before(qs[x], qs[y]); });
+    }
+    // the chunk that begins at place `at`: target[], pos[], a->reg_off and a->n; returns n
+    size_t cut(size_t at, PassArgs *a) {
+        const size_t n = std::min(PASS_Q, order.size() - at);
+        uint32_t n_regs = 0;
+        for (size_t i = 0; i < n; i++) {
+            const origin::Question &q = qs[order[at + i]];
+            target[i] = q.target; pos[i] = q.Q;
+            if (q.what == DVT_ORIGIN_REG) n_regs++;
+        }
+        for (uint32_t k = 0; k <= 32; k++) {   // the first register question with a register >= k (they are sorted)
+            uint32_t f = 0;
+            while (f < n_regs && target[f] < k) f++;
+            a->reg_off[k] = f;
+        }
+        a->n = (uint32_t)n;
+        return n;
+    }
+};
+
+// What a member of either search holds for the gather (origin.hip's): the fetches of a level and the records they brought.
+struct GatherMember {
+    OriginFetch *d_fetch = nullptr;     // [MAX_EDGES]
+    rv32::CycleRec *d_recs = nullptr;   // [MAX_EDGES]
+    std::vector<OriginFetch> fetch;
+    std::vector<rv32::CycleRec> got;
+    EventSpan t_gather;
+};
+static_assert(origin::MAX_EDGES == uses::MAX_EDGES, "the gather buffers of both searches");
+
+// The records at the positions `want` (repeats are fetched once), each from the member that holds its shard: (*out)[position].
+// buffers(c, member) makes the member's device arrays; nowhere / too_many: the search's words for a position that lies in no
+// shard and for more fetches than its edges.  *ms grows by the gather's time.
+template <class Run, class Buffers>
+int gather_records(dvt_prover *p, const Placed &pl, Run &run, const std::vector<unsigned long long> &want, Buffers buffers, const char *nowhere,
+                   const char *too_many, double *ms, std::map<unsigned long long, rv32::CycleRec> *out) {
+    std::map<unsigned long long, std::pair<size_t, size_t>> where;   // position -> (member, index among its fetches)
+    for (size_t m = 0; m < n_members(p); m++) run[m].fetch.clear();
+    for (const unsigned long long pos : want) {
+        if (where.count(pos)) continue;
+        const Held *h = pl.holder(pos);
+        if (!h) return fail(p, DVT_ERR_DEVICE, "%s", nowhere);
+        where[pos] = {h->m, run[h->m].fetch.size()};
+        run[h->m].fetch.push_back(OriginFetch{h->s->d_recs, (uint32_t)h->s->n_recs, (uint32_t)pos});
+    }
+    if (int rc = for_members(p, [&](size_t m, const Lane &c) {
+            Engine &e = c.eng;
+            auto &gm = run[m];
+            if (gm.fetch.empty()) return DVT_OK;
+            if (gm.fetch.size() > origin::MAX_EDGES) return fail(c.err, DVT_ERR_DEVICE, "%s", too_many);
+            if (int rc = buffers(c, gm)) return rc;
+            HIP_TRY(c.err, hipMemcpyAsync(gm.d_fetch, gm.fetch.data(), gm.fetch.size() * sizeof(OriginFetch), hipMemcpyHostToDevice, e.stream));
+            HIP_TRY(c.err, gm.t_gather.begin(e.stream));
+            HIP_TRY(c.err, launch_origin_gather(e.stream, gm.d_fetch, (uint32_t)gm.fetch.size(), gm.d_recs));
+            HIP_TRY(c.err, gm.t_gather.end(e.stream));
+            gm.got.resize(gm.fetch.size());
+            if (!e.download(gm.got.data(), gm.d_recs, gm.got.size() * sizeof(rv32::CycleRec))) return engine_fail(c.err, e);
+            *ms += gm.t_gather.ms();
+            return DVT_OK;
+        }))
+        return rc;
+    out->clear();
+    for (const auto &w : where) (*out)[w.first] = run[w.second.first].got[w.second.second];
+    return DVT_OK;
+}
+
+// How either search over a job ends.  rc: of Search::run; rc_answer: why an answer failed; ms[n_ms]: the device times, copied to
+// out_ms with the rest of the call's time, which is the host's, behind them.
+template <class Search, class Summary>
+int finish_search(dvt_prover *p, int rc, int rc_answer, uint64_t bad, const Search &search, uint32_t passes, const Placed &pl, Clock::time_point t0,
+                  const double *ms, int n_ms, double *out_ms, Summary *summary) {
+    if (rc == 1) return rc_answer;
+    if (bad) return fail(p, DVT_ERR_INPUT, "%llu %s", (unsigned long long)bad, BAD_RECORD);
+    if (rc) return fail(p, DVT_ERR_DEVICE, "%s", search.why.c_str());
+    Summary s = search.s;
+    s.passes = passes;
+    pl.place(&s);
+    const double total = ms_since(t0);
+    s.ms = (float)total;
+    double rest = total;
+    for (int i = 0; i < n_ms; i++) { out_ms[i] = ms[i]; rest -= ms[i]; }
+    out_ms[n_ms] = std::max(0.0, rest);
+    *summary = s;
+    return DVT_OK;
+}
 }  // namespace
 
 // ------------------------------------------------------------------ the execution report (dvt_rv32_job_profile)
@@ -601,16 +746,11 @@ static int job_snapshot(dvt_prover *p, const dvt_pk *pk, dvt_job *j, uint32_t sh
     const unsigned long long P = watch::position(shard, row);
     MemberRun<SnapMember> run(p);   // (declared first: however the call ends, member 0's device is current again)
     // ---- the shards in execution order: their sizes, the records before P, the record at P
-    const std::vector<Held> held = held_in_order(j);
-    std::vector<uint64_t> shard_n(held.size());
-    uint64_t cycles = 0, position = 0;
-    for (const Held &h : held) {
-        const ShardJob &s = *h.s;
-        if (s.n_recs > 0xffffffffull) return fail(p, DVT_ERR_INPUT, "shard %zu has %zu records", h.pos, s.n_recs);
-        shard_n[h.pos] = s.n_recs;
-        cycles += s.n_recs;
-        position += s.index < shard ? s.n_recs : s.index == shard ? std::min<uint64_t>(s.n_recs, row) : 0;
-    }
+    Placed pl;
+    if (int rc = pl.init(p, j, shard, row)) return rc;
+    const std::vector<Held> &held = pl.held;
+    const std::vector<uint64_t> &shard_n = pl.shard_n;
+    const uint64_t cycles = pl.cycles, position = pl.position;
     const watch::Statics statics(prog);
     const size_t n = statics.n();
     uint32_t at_shard = 1, at_row = 0, idx_at = prof::NO_SUCC, pc = held.empty() ? prog.entry : held.back().s->next_pc;
@@ -697,11 +837,10 @@ static int job_snapshot(dvt_prover *p, const dvt_pk *pk, dvt_job *j, uint32_t sh
     struct Want { size_t m, at; uint32_t what, index; };
     std::vector<Want> wants;
     auto want = [&](unsigned long long where, uint32_t addr, uint32_t what, uint32_t index) {
-        const uint32_t sh = (uint32_t)(where >> 32), rw = (uint32_t)where;
-        if (!sh || sh > held.size() || rw >= held[sh - 1].s->n_recs) return false;
-        const Held &h = held[sh - 1];
-        wants.push_back({h.m, run[h.m].fetch.size(), what, index});
-        run[h.m].fetch.push_back(SnapFetch{h.s->d_recs, (uint32_t)h.s->n_recs, sh, rw, addr, what, 0});
+        const Held *h = pl.holder(where);
+        if (!h) return false;
+        wants.push_back({h->m, run[h->m].fetch.size(), what, index});
+        run[h->m].fetch.push_back(SnapFetch{h->s->d_recs, (uint32_t)h->s->n_recs, (uint32_t)(where >> 32), (uint32_t)where, addr, what, 0});
         return true;
     };
     bool ok = true;
@@ -767,17 +906,12 @@ static int job_snapshot(dvt_prover *p, const dvt_pk *pk, dvt_job *j, uint32_t sh
 // the host merges the members' winners with max and asks the member that holds each winner's shard for the record (gather, one
 // fetch per distinct position of the level).
 namespace {
-struct OriginMember {
+struct OriginMember : GatherMember {
     StageBuf base;
-    unsigned long long *d_win = nullptr, *d_bad = nullptr, *d_qpos = nullptr;   // [PASS_Q], [1], [PASS_Q]
-    uint32_t *d_qtarget = nullptr;                                               // [PASS_Q]
-    OriginFetch *d_items = nullptr;                                              // [MAX_EDGES]
-    rv32::CycleRec *d_recs = nullptr;                                            // [MAX_EDGES]
-    const uint32_t *d_statics = nullptr;
-    std::vector<OriginFetch> fetch;
-    std::vector<unsigned long long> fetch_pos;
-    std::vector<rv32::CycleRec> got;
-    EventSpan t_reduce, t_gather;
+    unsigned long long *d_win = nullptr, *d_qpos = nullptr;   // [PASS_Q] winners and behind them the bad records [1]; [PASS_Q]
+    uint32_t *d_qtarget = nullptr;                             // [PASS_Q]
+    uint32_t *d_statics = nullptr;
+    EventSpan t_reduce;
     explicit OriginMember(DevPool &pool) : base{pool} {}
 };
 }  // namespace
@@ -788,36 +922,27 @@ static int job_origin(dvt_prover *p, const dvt_pk *pk, dvt_job *j, uint32_t shar
     if (int rc = whole_execution(p, j, "origin of a value")) return rc;
     const auto t0 = Clock::now();
     const rv32::Program &prog = pk->prog;
-    constexpr size_t PQ = origin::PASS_Q;
+    constexpr size_t PQ = PASS_Q;
     MemberRun<OriginMember> run(p);   // (declared first: however the call ends, member 0's device is current again)
-    const std::vector<Held> held = held_in_order(j);
-    std::vector<uint64_t> shard_n(held.size());
-    uint64_t cycles = 0, position = 0;
-    for (const Held &h : held) {
-        const ShardJob &s = *h.s;
-        if (s.n_recs > 0xffffffffull) return fail(p, DVT_ERR_INPUT, "shard %zu has %zu records", h.pos, s.n_recs);
-        shard_n[h.pos] = s.n_recs;
-        cycles += s.n_recs;
-        position += s.index < shard ? s.n_recs : s.index == shard ? std::min<uint64_t>(s.n_recs, row) : 0;
-    }
+    Placed pl;
+    if (int rc = pl.init(p, j, shard, row)) return rc;
     const watch::Statics statics(prog);
     const watch::Shapes shapes = watch::shapes();
     const size_t n = statics.n();
-    // a member's buffer: win | bad | q_pos | fetched records | fetch items | q_target | the static words
-    const size_t bytes = PQ * 8 + 8 + PQ * 8 + 8 + origin::MAX_EDGES * (sizeof(rv32::CycleRec) + sizeof(OriginFetch)) + PQ * 4 + statics.bytes();
+    auto layout = [&](OriginMember &om, Carve c) {
+        om.d_win = c.take<unsigned long long>(PQ + 1);
+        om.d_qpos = c.take<unsigned long long>(PQ);
+        om.d_recs = c.take<rv32::CycleRec>(origin::MAX_EDGES, 16);
+        om.d_fetch = c.take<OriginFetch>(origin::MAX_EDGES);
+        om.d_qtarget = c.take<uint32_t>(PQ);
+        om.d_statics = c.take<uint32_t>(statics.words.size());
+        return c.at;
+    };
     auto buffers = [&](const Lane &c, OriginMember &om) {
         if (om.base.ptr) return DVT_OK;
-        Engine &e = c.eng;
-        HIP_TRY(c.err, e.pool.alloc_bytes(&om.base.ptr, bytes));
-        om.d_win = static_cast<unsigned long long *>(om.base.ptr);
-        om.d_bad = om.d_win + PQ;
-        om.d_qpos = om.d_bad + 2;                                                  // (the records behind stay 16-byte aligned)
-        om.d_recs = reinterpret_cast<rv32::CycleRec *>(om.d_qpos + PQ);
-        om.d_items = reinterpret_cast<OriginFetch *>(om.d_recs + origin::MAX_EDGES);
-        om.d_qtarget = reinterpret_cast<uint32_t *>(om.d_items + origin::MAX_EDGES);
-        uint32_t *d_stat = om.d_qtarget + PQ;
-        om.d_statics = d_stat;
-        HIP_TRY(c.err, hipMemcpyAsync(d_stat, statics.words.data(), statics.bytes(), hipMemcpyHostToDevice, e.stream));
+        HIP_TRY(c.err, c.eng.pool.alloc_bytes(&om.base.ptr, layout(om, Carve{})));   // (over no base: the size; the pointers follow)
+        layout(om, Carve{static_cast<char *>(om.base.ptr)});
+        HIP_TRY(c.err, hipMemcpyAsync(om.d_statics, statics.words.data(), statics.bytes(), hipMemcpyHostToDevice, c.eng.stream));
         return DVT_OK;
     };
 
@@ -826,29 +951,16 @@ static int job_origin(dvt_prover *p, const dvt_pk *pk, dvt_job *j, uint32_t shar
     uint32_t passes = 0;
     int rc_answer = DVT_OK;
     auto answer = [&](const std::vector<origin::Question> &qs, std::vector<origin::Found> *found) {
-        std::vector<uint32_t> order(qs.size());
-        for (size_t i = 0; i < order.size(); i++) order[i] = (uint32_t)i;
-        std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return origin::sorts_before(qs[x], qs[y]); });
-        std::vector<unsigned long long> win(qs.size(), 0), one(PQ + 1), q_pos(PQ);
-        std::vector<uint32_t> q_target(PQ);
+        Chunks chunks(qs);
+        const std::vector<uint32_t> &order = chunks.order;
+        std::vector<unsigned long long> win(qs.size(), 0), one(PQ + 1);
         // ---- reduce: one pass per chunk of the sorted questions
         for (size_t at = 0; at < order.size(); at += PQ) {
-            const size_t n_q = std::min(PQ, order.size() - at);
             OriginArgs args{};
             args.sh = shapes;
-            args.n_instr = (uint32_t)n; args.text_base = prog.text_base; args.n_q = (uint32_t)n_q;
-            uint32_t n_regs = 0;
-            for (size_t i = 0; i < n_q; i++) {
-                const origin::Question &q = qs[order[at + i]];
-                q_target[i] = q.target; q_pos[i] = q.Q;
-                args.max_q = std::max(args.max_q, q.Q);
-                if (q.what == DVT_ORIGIN_REG) n_regs++;
-            }
-            for (uint32_t k = 0; k <= 32; k++) {   // the first register question with a register >= k (they are sorted)
-                uint32_t f = 0;
-                while (f < n_regs && q_target[f] < k) f++;
-                args.reg_off[k] = f;
-            }
+            args.n_instr = (uint32_t)n; args.text_base = prog.text_base;
+            const size_t n_q = chunks.cut(at, &args);
+            args.max_q = *std::max_element(chunks.pos.begin(), chunks.pos.begin() + n_q);
             const uint32_t q_shard = (uint32_t)(args.max_q >> 32), q_row = (uint32_t)args.max_q;
             auto take = [&](const ShardJob &s) { return s.index < q_shard ? s.n_recs : s.index == q_shard ? std::min<size_t>(s.n_recs, q_row) : 0; };
             passes++;
@@ -861,14 +973,14 @@ static int job_origin(dvt_prover *p, const dvt_pk *pk, dvt_job *j, uint32_t shar
                 if (!any) return DVT_OK;
                 if (int rc = buffers(c, om)) return rc;
                 HIP_TRY(c.err, hipMemsetAsync(om.d_win, 0, (PQ + 1) * 8, e.stream));
-                HIP_TRY(c.err, hipMemcpyAsync(om.d_qpos, q_pos.data(), n_q * 8, hipMemcpyHostToDevice, e.stream));
-                HIP_TRY(c.err, hipMemcpyAsync(om.d_qtarget, q_target.data(), n_q * 4, hipMemcpyHostToDevice, e.stream));
+                HIP_TRY(c.err, hipMemcpyAsync(om.d_qpos, chunks.pos.data(), n_q * 8, hipMemcpyHostToDevice, e.stream));
+                HIP_TRY(c.err, hipMemcpyAsync(om.d_qtarget, chunks.target.data(), n_q * 4, hipMemcpyHostToDevice, e.stream));
                 OriginArgs a = args;
-                a.statics = om.d_statics; a.offs = om.d_statics + n; a.q_target = om.d_qtarget; a.q_pos = om.d_qpos;
+                a.statics = om.d_statics; a.offs = om.d_statics + n; a.target = om.d_qtarget; a.pos = om.d_qpos;
                 HIP_TRY(c.err, om.t_reduce.begin(e.stream));
                 for (auto &s : part.shards) {
                     a.shard = s.index;
-                    HIP_TRY(c.err, launch_origin_reduce(e.stream, s.d_recs, take(s), a, om.d_win, om.d_bad));
+                    HIP_TRY(c.err, launch_origin_reduce(e.stream, s.d_recs, take(s), a, om.d_win, om.d_win + PQ));
                 }
                 HIP_TRY(c.err, om.t_reduce.end(e.stream));
                 if (!e.download(one.data(), om.d_win, (PQ + 1) * 8)) return engine_fail(c.err, e);
@@ -881,58 +993,20 @@ static int job_origin(dvt_prover *p, const dvt_pk *pk, dvt_job *j, uint32_t shar
         }
         if (bad) return true;   // (the call fails below: no record is read again)
         // ---- gather: every distinct winner from the member that holds its shard
-        std::map<unsigned long long, std::pair<size_t, size_t>> where;   // position -> (member, index among its fetches)
-        for (size_t m = 0; m < n_members(p); m++) { run[m].fetch.clear(); run[m].fetch_pos.clear(); }
-        for (size_t i = 0; i < qs.size(); i++) {
-            if (!win[i] || where.count(win[i])) continue;
-            const uint32_t sh = (uint32_t)(win[i] >> 32), rw = (uint32_t)win[i];
-            if (!sh || sh > held.size() || rw >= held[sh - 1].s->n_recs) {
-                rc_answer = fail(p, DVT_ERR_DEVICE, "a winner of the reduce pass lies in no shard of the job");
-                return false;
-            }
-            const Held &h = held[sh - 1];
-            where[win[i]] = {h.m, run[h.m].fetch.size()};
-            run[h.m].fetch.push_back(OriginFetch{h.s->d_recs, (uint32_t)h.s->n_recs, rw});
-        }
-        rc_answer = for_members(p, [&](size_t m, const Lane &c) {
-            Engine &e = c.eng;
-            OriginMember &om = run[m];
-            if (om.fetch.empty()) return DVT_OK;
-            if (om.fetch.size() > origin::MAX_EDGES) return fail(c.err, DVT_ERR_DEVICE, "more winners than questions");
-            if (int rc = buffers(c, om)) return rc;
-            HIP_TRY(c.err, hipMemcpyAsync(om.d_items, om.fetch.data(), om.fetch.size() * sizeof(OriginFetch), hipMemcpyHostToDevice, e.stream));
-            HIP_TRY(c.err, om.t_gather.begin(e.stream));
-            HIP_TRY(c.err, launch_origin_gather(e.stream, om.d_items, (uint32_t)om.fetch.size(), om.d_recs));
-            HIP_TRY(c.err, om.t_gather.end(e.stream));
-            om.got.resize(om.fetch.size());
-            if (!e.download(om.got.data(), om.d_recs, om.got.size() * sizeof(rv32::CycleRec))) return engine_fail(c.err, e);
-            ms[1] += om.t_gather.ms();
-            return DVT_OK;
-        });
+        std::vector<unsigned long long> want;
+        for (const unsigned long long w : win)
+            if (w) want.push_back(w);
+        std::map<unsigned long long, rv32::CycleRec> recs;
+        rc_answer = gather_records(p, pl, run, want, buffers, "a winner of the reduce pass lies in no shard of the job", "more winners than questions", &ms[1], &recs);
         if (rc_answer) return false;
         for (size_t i = 0; i < qs.size(); i++)
-            if (win[i]) {
-                const auto &w = where[win[i]];
-                (*found)[i] = origin::Found{win[i], run[w.first].got[w.second]};
-            }
+            if (win[i]) (*found)[i] = origin::Found{win[i], recs[win[i]]};
         return true;
     };
 
     origin::Search search(prog, statics, shapes, watch::position(shard, row), what, target, flags, max_depth, nodes, cap_nodes, edges, cap_edges);
     const int rc = search.run(answer);
-    if (rc == 1) return rc_answer;
-    if (bad) return fail(p, DVT_ERR_INPUT, "%llu %s", (unsigned long long)bad, BAD_RECORD);
-    if (rc) return fail(p, DVT_ERR_DEVICE, "%s", search.why.c_str());
-    dvt_origin_summary s = search.s;
-    s.passes = passes;
-    s.position = position; s.cycles = cycles;
-    snap::locate(shard_n, position, &s.shard, &s.row);
-    s.shards_total = (uint32_t)held.size();
-    const double total = ms_since(t0);
-    s.ms = (float)total;
-    p->origin_ms[0] = ms[0]; p->origin_ms[1] = ms[1]; p->origin_ms[2] = std::max(0.0, total - ms[0] - ms[1]);
-    *summary = s;
-    return DVT_OK;
+    return finish_search(p, rc, rc_answer, bad, search, passes, pl, t0, ms, 2, p->origin_ms, summary);
 }
 
 // ------------------------------------------------------------------ uses (dvt_rv32_job_uses)
@@ -944,19 +1018,16 @@ static int job_origin(dvt_prover *p, const dvt_pk *pk, dvt_job *j, uint32_t shar
 // The consumers' records come from the member that holds each one's shard (origin.hip's gather, one fetch per distinct position
 // of the level).
 namespace {
-struct UsesMember {
+struct UsesMember : GatherMember {
     StageBuf base;
-    unsigned long long *d_win = nullptr, *d_bad = nullptr, *d_from = nullptr, *d_next = nullptr, *d_carry = nullptr, *d_out_pos = nullptr;
-    rv32::CycleRec *d_recs = nullptr;        // [MAX_EDGES]
-    OriginFetch *d_fetch = nullptr;          // [MAX_EDGES]
+    unsigned long long *d_win = nullptr, *d_from = nullptr, *d_next = nullptr;   // [PASS_DEFS] each; behind d_win the bad records [1]
+    unsigned long long *d_carry = nullptr;   // [PASS_DEFS] and behind them out_pos [PASS_DEFS * MAX_FAN]
     UsesItem *d_items = nullptr;             // [PASS_DEFS * MAX_FAN]
     uint32_t *d_target = nullptr, *d_out_role = nullptr, *d_n_items = nullptr, *d_table = nullptr;
-    const uint32_t *d_statics = nullptr, *d_ostat = nullptr;
+    uint32_t *d_statics = nullptr, *d_ostat = nullptr;
     size_t table_rows = 0;                   // the spans of the shards the member holds
     std::vector<const Held *> shards;        // in execution order
-    std::vector<OriginFetch> fetch;
-    std::vector<rv32::CycleRec> got;
-    EventSpan t_next, t_count, t_emit, t_gather;
+    EventSpan t_next, t_count, t_emit;
     explicit UsesMember(DevPool &pool) : base{pool} {}
 };
 }  // namespace
@@ -968,50 +1039,40 @@ static int job_uses(dvt_prover *p, const dvt_pk *pk, dvt_job *j, uint32_t shard,
     if (int rc = whole_execution(p, j, "uses of a value")) return rc;
     const auto t0 = Clock::now();
     const rv32::Program &prog = pk->prog;
-    constexpr size_t PD = uses::PASS_DEFS, SPAN = uses::SPAN, MAX_ITEMS = PD * uses::MAX_FAN;
+    constexpr size_t PD = PASS_Q, SPAN = uses::SPAN, MAX_ITEMS = PD * uses::MAX_FAN;
     MemberRun<UsesMember> run(p);   // (declared first: however the call ends, member 0's device is current again)
-    const std::vector<Held> held = held_in_order(j);
-    std::vector<uint64_t> shard_n(held.size());
-    uint64_t cycles = 0, position = 0;
-    for (const Held &h : held) {
-        const ShardJob &s = *h.s;
-        if (s.n_recs > 0xffffffffull) return fail(p, DVT_ERR_INPUT, "shard %zu has %zu records", h.pos, s.n_recs);
-        shard_n[h.pos] = s.n_recs;
-        cycles += s.n_recs;
-        position += s.index < shard ? s.n_recs : s.index == shard ? std::min<uint64_t>(s.n_recs, row) : 0;
+    Placed pl;
+    if (int rc = pl.init(p, j, shard, row)) return rc;
+    for (const Held &h : pl.held) {
         run[h.m].shards.push_back(&h);
-        run[h.m].table_rows += (s.n_recs + SPAN - 1) / SPAN;
+        run[h.m].table_rows += (h.s->n_recs + SPAN - 1) / SPAN;
     }
     const watch::Statics statics(prog);
-    const origin::Statics ostat(prog);
+    const flow::Statics ostat(prog);
     const watch::Shapes shapes = watch::shapes();
     const size_t n = statics.n();
-    // a member's buffer: win | bad | from | next | carry | out_pos | fetched records | fetch items | span items | target | out_role |
-    // n_items | the static words | the count table
+    auto layout = [&](UsesMember &um, Carve c) {
+        um.d_win = c.take<unsigned long long>(PD + 1);
+        um.d_from = c.take<unsigned long long>(PD);
+        um.d_next = c.take<unsigned long long>(PD);
+        um.d_carry = c.take<unsigned long long>(PD + MAX_ITEMS);
+        um.d_recs = c.take<rv32::CycleRec>(uses::MAX_EDGES, 16);
+        um.d_fetch = c.take<OriginFetch>(uses::MAX_EDGES);
+        um.d_items = c.take<UsesItem>(MAX_ITEMS);
+        um.d_target = c.take<uint32_t>(PD);
+        um.d_out_role = c.take<uint32_t>(MAX_ITEMS);
+        um.d_n_items = c.take<uint32_t>(4);
+        um.d_statics = c.take<uint32_t>(statics.words.size());
+        um.d_ostat = c.take<uint32_t>(n);
+        um.d_table = c.take<uint32_t>(um.table_rows * PD);
+        return c.at;
+    };
     auto buffers = [&](const Lane &c, UsesMember &um) {
         if (um.base.ptr) return DVT_OK;
-        Engine &e = c.eng;
-        const size_t bytes = (4 * PD + 2 + MAX_ITEMS) * 8 + uses::MAX_EDGES * (sizeof(rv32::CycleRec) + sizeof(OriginFetch)) + MAX_ITEMS * sizeof(UsesItem) +
-                             (PD + MAX_ITEMS + 4) * 4 + statics.bytes() + n * 4 + um.table_rows * PD * 4;
-        HIP_TRY(c.err, e.pool.alloc_bytes(&um.base.ptr, bytes));
-        um.d_win = static_cast<unsigned long long *>(um.base.ptr);
-        um.d_bad = um.d_win + PD;
-        um.d_from = um.d_bad + 2;                                                  // (the records behind stay 16-byte aligned)
-        um.d_next = um.d_from + PD;
-        um.d_carry = um.d_next + PD;
-        um.d_out_pos = um.d_carry + PD;
-        um.d_recs = reinterpret_cast<rv32::CycleRec *>(um.d_out_pos + MAX_ITEMS);
-        um.d_fetch = reinterpret_cast<OriginFetch *>(um.d_recs + uses::MAX_EDGES);
-        um.d_items = reinterpret_cast<UsesItem *>(um.d_fetch + uses::MAX_EDGES);
-        um.d_target = reinterpret_cast<uint32_t *>(um.d_items + MAX_ITEMS);
-        um.d_out_role = um.d_target + PD;
-        um.d_n_items = um.d_out_role + MAX_ITEMS;
-        uint32_t *d_stat = um.d_n_items + 4;
-        um.d_statics = d_stat;
-        um.d_ostat = d_stat + 2 * n;
-        um.d_table = d_stat + 3 * n;
-        HIP_TRY(c.err, hipMemcpyAsync(d_stat, statics.words.data(), statics.bytes(), hipMemcpyHostToDevice, e.stream));
-        HIP_TRY(c.err, hipMemcpyAsync(d_stat + 2 * n, ostat.words.data(), n * 4, hipMemcpyHostToDevice, e.stream));
+        HIP_TRY(c.err, c.eng.pool.alloc_bytes(&um.base.ptr, layout(um, Carve{})));   // (over no base: the size; the pointers follow)
+        layout(um, Carve{static_cast<char *>(um.base.ptr)});
+        HIP_TRY(c.err, hipMemcpyAsync(um.d_statics, statics.words.data(), statics.bytes(), hipMemcpyHostToDevice, c.eng.stream));
+        HIP_TRY(c.err, hipMemcpyAsync(um.d_ostat, ostat.words.data(), n * 4, hipMemcpyHostToDevice, c.eng.stream));
         return DVT_OK;
     };
     // the spans of shard s that hold a position in [lo, hi]: {first, count}
@@ -1028,31 +1089,20 @@ static int job_uses(dvt_prover *p, const dvt_pk *pk, dvt_job *j, uint32_t shard,
     uint32_t passes = 0;
     int rc_answer = DVT_OK;
     auto answer = [&](const std::vector<uses::Def> &qs, std::vector<uses::Found> *found) {
-        std::vector<uint32_t> order(qs.size());
-        for (size_t i = 0; i < order.size(); i++) order[i] = (uint32_t)i;
-        std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return origin::sorts_before(qs[x], qs[y]); });
-        std::vector<unsigned long long> one(PD + 1), d_from(PD), d_next(PD), carry(PD + MAX_ITEMS);
-        std::vector<uint32_t> d_target(PD), out_role(MAX_ITEMS);
+        Chunks chunks(qs);
+        const std::vector<uint32_t> &order = chunks.order, &d_target = chunks.target;
+        const std::vector<unsigned long long> &d_from = chunks.pos;
+        std::vector<unsigned long long> one(PD + 1), d_next(PD), carry(PD + MAX_ITEMS);
+        std::vector<uint32_t> out_role(MAX_ITEMS);
         struct Kept { unsigned long long pos; uint32_t role; };
         std::vector<std::vector<Kept>> kept(qs.size());
         for (size_t at = 0; at < order.size(); at += PD) {
-            const size_t n_d = std::min(PD, order.size() - at);
             UsesArgs args{};
             args.sh = shapes;
-            args.n_instr = (uint32_t)n; args.text_base = prog.text_base; args.n_d = (uint32_t)n_d; args.flags = flags; args.fan = fan;
-            args.min_from = uses::NO_POS;
-            uint32_t n_regs = 0;
-            for (size_t i = 0; i < n_d; i++) {
-                const uses::Def &q = qs[order[at + i]];
-                d_target[i] = q.target; d_from[i] = q.Q; d_next[i] = uses::NO_POS;
-                args.min_from = std::min(args.min_from, q.Q);
-                if (q.what == DVT_USES_REG) n_regs++;
-            }
-            for (uint32_t k = 0; k <= 32; k++) {   // the first register definition with a register >= k (they are sorted)
-                uint32_t f = 0;
-                while (f < n_regs && d_target[f] < k) f++;
-                args.reg_off[k] = f;
-            }
+            args.n_instr = (uint32_t)n; args.text_base = prog.text_base; args.flags = flags; args.fan = fan;
+            const size_t n_d = chunks.cut(at, &args);
+            args.min_from = *std::min_element(d_from.begin(), d_from.begin() + n_d);
+            std::fill(d_next.begin(), d_next.begin() + n_d, uses::NO_POS);
             passes++;
             // ---- next: the first writer at or after F, per member, merged with min
             rc_answer = for_members(p, [&](size_t m, const Lane &c) {
@@ -1063,16 +1113,16 @@ static int job_uses(dvt_prover *p, const dvt_pk *pk, dvt_job *j, uint32_t shard,
                 if (!any) return DVT_OK;
                 if (int rc = buffers(c, um)) return rc;
                 HIP_TRY(c.err, hipMemsetAsync(um.d_win, 0xff, PD * 8, e.stream));
-                HIP_TRY(c.err, hipMemsetAsync(um.d_bad, 0, 8, e.stream));
+                HIP_TRY(c.err, hipMemsetAsync(um.d_win + PD, 0, 8, e.stream));
                 HIP_TRY(c.err, hipMemcpyAsync(um.d_from, d_from.data(), n_d * 8, hipMemcpyHostToDevice, e.stream));
                 HIP_TRY(c.err, hipMemcpyAsync(um.d_target, d_target.data(), n_d * 4, hipMemcpyHostToDevice, e.stream));
                 UsesArgs a = args;
-                a.statics = um.d_statics; a.offs = um.d_statics + n; a.ostat = um.d_ostat; a.d_target = um.d_target; a.d_from = um.d_from; a.d_next = um.d_next;
+                a.statics = um.d_statics; a.offs = um.d_statics + n; a.ostat = um.d_ostat; a.target = um.d_target; a.pos = um.d_from; a.d_next = um.d_next;
                 HIP_TRY(c.err, um.t_next.begin(e.stream));
                 for (const Held *h : um.shards) {
                     const auto sp = spans_in(*h->s, args.min_from, uses::NO_POS);
                     a.shard = h->s->index;
-                    HIP_TRY(c.err, launch_uses_next(e.stream, h->s->d_recs, h->s->n_recs, sp.first, sp.second, a, um.d_win, um.d_bad));
+                    HIP_TRY(c.err, launch_uses_next(e.stream, h->s->d_recs, h->s->n_recs, sp.first, sp.second, a, um.d_win, um.d_win + PD));
                 }
                 HIP_TRY(c.err, um.t_next.end(e.stream));
                 if (!e.download(one.data(), um.d_win, (PD + 1) * 8)) return engine_fail(c.err, e);
@@ -1102,7 +1152,7 @@ static int job_uses(dvt_prover *p, const dvt_pk *pk, dvt_job *j, uint32_t shard,
                 HIP_TRY(c.err, hipMemsetAsync(um.d_carry, 0, PD * 8, e.stream));
                 HIP_TRY(c.err, hipMemsetAsync(um.d_n_items, 0, 16, e.stream));
                 UsesArgs a = args;
-                a.statics = um.d_statics; a.offs = um.d_statics + n; a.ostat = um.d_ostat; a.d_target = um.d_target; a.d_from = um.d_from; a.d_next = um.d_next;
+                a.statics = um.d_statics; a.offs = um.d_statics + n; a.ostat = um.d_ostat; a.target = um.d_target; a.pos = um.d_from; a.d_next = um.d_next;
                 HIP_TRY(c.err, um.t_count.begin(e.stream));
                 size_t table_row = 0;
                 for (const Held *h : um.shards) {
@@ -1120,7 +1170,7 @@ static int job_uses(dvt_prover *p, const dvt_pk *pk, dvt_job *j, uint32_t shard,
                 }
                 HIP_TRY(c.err, um.t_count.end(e.stream));
                 um.t_emit.begin_at_end_of(um.t_count);
-                HIP_TRY(c.err, launch_uses_emit(e.stream, um.d_items, um.d_n_items, (uint32_t)(n_d * fan), a, um.d_out_pos, um.d_out_role));
+                HIP_TRY(c.err, launch_uses_emit(e.stream, um.d_items, um.d_n_items, (uint32_t)(n_d * fan), a, um.d_carry + PD, um.d_out_role));
                 HIP_TRY(c.err, um.t_emit.end(e.stream));
                 if (!e.download(out_role.data(), um.d_out_role, n_d * fan * 4)) return engine_fail(c.err, e);
                 if (!e.download(carry.data(), um.d_carry, (PD + n_d * fan) * 8)) return engine_fail(c.err, e);   // (carry | out_pos, adjacent)
@@ -1137,64 +1187,24 @@ static int job_uses(dvt_prover *p, const dvt_pk *pk, dvt_job *j, uint32_t shard,
             if (rc_answer) return false;
         }
         // ---- the fan smallest of the members' kept uses; gather: every distinct consumer from the member that holds its shard
-        std::map<unsigned long long, std::pair<size_t, size_t>> where;   // position -> (member, index among its fetches)
-        for (size_t m = 0; m < n_members(p); m++) run[m].fetch.clear();
+        std::vector<unsigned long long> want;
         for (size_t i = 0; i < qs.size(); i++) {
             std::stable_sort(kept[i].begin(), kept[i].end(), [](const Kept &x, const Kept &y) { return x.pos != y.pos ? x.pos < y.pos : x.role < y.role; });
             if (kept[i].size() > fan) kept[i].resize(fan);
-            for (const Kept &k : kept[i]) {
-                if (where.count(k.pos)) continue;
-                const uint32_t sh = (uint32_t)(k.pos >> 32), rw = (uint32_t)k.pos;
-                if (!sh || sh > held.size() || rw >= held[sh - 1].s->n_recs) {
-                    rc_answer = fail(p, DVT_ERR_DEVICE, "a use of the emit pass lies in no shard of the job");
-                    return false;
-                }
-                const Held &h = held[sh - 1];
-                where[k.pos] = {h.m, run[h.m].fetch.size()};
-                run[h.m].fetch.push_back(OriginFetch{h.s->d_recs, (uint32_t)h.s->n_recs, rw});
-            }
+            for (const Kept &k : kept[i]) want.push_back(k.pos);
         }
-        rc_answer = for_members(p, [&](size_t m, const Lane &c) {
-            Engine &e = c.eng;
-            UsesMember &um = run[m];
-            if (um.fetch.empty()) return DVT_OK;
-            if (um.fetch.size() > uses::MAX_EDGES) return fail(c.err, DVT_ERR_DEVICE, "more kept uses than edges");
-            if (int rc = buffers(c, um)) return rc;
-            HIP_TRY(c.err, hipMemcpyAsync(um.d_fetch, um.fetch.data(), um.fetch.size() * sizeof(OriginFetch), hipMemcpyHostToDevice, e.stream));
-            HIP_TRY(c.err, um.t_gather.begin(e.stream));
-            HIP_TRY(c.err, launch_origin_gather(e.stream, um.d_fetch, (uint32_t)um.fetch.size(), um.d_recs));
-            HIP_TRY(c.err, um.t_gather.end(e.stream));
-            um.got.resize(um.fetch.size());
-            if (!e.download(um.got.data(), um.d_recs, um.got.size() * sizeof(rv32::CycleRec))) return engine_fail(c.err, e);
-            ms[3] += um.t_gather.ms();
-            return DVT_OK;
-        });
+        std::map<unsigned long long, rv32::CycleRec> recs;
+        rc_answer = gather_records(p, pl, run, want, buffers, "a use of the emit pass lies in no shard of the job", "more kept uses than edges", &ms[3], &recs);
         if (rc_answer) return false;
         for (size_t i = 0; i < qs.size(); i++)
-            for (const Kept &k : kept[i]) {
-                const auto &w = where[k.pos];
-                (*found)[i].uses.push_back(uses::Use{k.pos, k.role, run[w.first].got[w.second]});
-            }
+            for (const Kept &k : kept[i]) (*found)[i].uses.push_back(uses::Use{k.pos, k.role, recs[k.pos]});
         return true;
     };
 
     uses::Search search(prog, statics, shapes, watch::position(shard, row), what, target, flags, max_depth, fan, nodes, cap_nodes, defs, cap_defs, edges,
                         cap_edges);
     const int rc = search.run(answer);
-    if (rc == 1) return rc_answer;
-    if (bad) return fail(p, DVT_ERR_INPUT, "%llu %s", (unsigned long long)bad, BAD_RECORD);
-    if (rc) return fail(p, DVT_ERR_DEVICE, "%s", search.why.c_str());
-    dvt_uses_summary s = search.s;
-    s.passes = passes;
-    s.position = position; s.cycles = cycles;
-    snap::locate(shard_n, position, &s.shard, &s.row);
-    s.shards_total = (uint32_t)held.size();
-    const double total = ms_since(t0);
-    s.ms = (float)total;
-    for (int i = 0; i < 4; i++) p->uses_ms[i] = ms[i];
-    p->uses_ms[4] = std::max(0.0, total - ms[0] - ms[1] - ms[2] - ms[3]);
-    *summary = s;
-    return DVT_OK;
+    return finish_search(p, rc, rc_answer, bad, search, passes, pl, t0, ms, 4, p->uses_ms, summary);
 }
 
 // ------------------------------------------------------------------ divergence (dvt_rv32_job_diverge)

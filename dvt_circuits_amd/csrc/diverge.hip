@@ -23,6 +23,7 @@
 // every index is checked before the store.
 #include "diverge.h"
 #include "kernels.h"
+#include "records.cuh"
 
 namespace dvt {
 
@@ -31,18 +32,8 @@ namespace {
 constexpr uint32_t ROUNDS = diverge::SPAN / 256, UNITS = diverge::SPAN / 64, NONE32 = 0xffffffffu;
 static_assert(ROUNDS == 16, "a thread's data bits are kept in 16 bits");
 
-__device__ __forceinline__ uint32_t lanes_below(unsigned long long mask) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
-}
-
-// the words of the record at r that the rule reads (the caller checked r)
-__device__ __forceinline__ rv32::CycleRec read_record(const rv32::CycleRec *recs, size_t r) {
-    rv32::CycleRec rec{};
-    const uint4 w0 = *reinterpret_cast<const uint4 *>(&recs[r]);
-    rec.idx = w0.x; rec.a = w0.y; rec.b = w0.z; rec.c = w0.w;
-    rec.m_prev = recs[r].m_prev;
-    return rec;
-}
+// the record at r (the caller checked r)
+__device__ __forceinline__ rv32::CycleRec read_record(const rv32::CycleRec *recs, size_t r) { return dvt::read_record(recs, r, r + 1); }
 
 // the class word of the pair at `local` of the segment; 0 (SAME, no rd) for a lane past the end
 __device__ __forceinline__ uint32_t class_of(const DivergeArgs &a, uint32_t local) {

@@ -194,7 +194,7 @@ hipError_t launch_snapshot_gather(hipStream_t st, const SnapFetch *d_items, uint
 // origin.hip
 // The passes of the origin search (origin.h).  reduce: over the first n_take records of one shard (the ones before the largest
 // position any question of the pass asks at), the latest writer of every question's target before the question's position, as
-// a position, into d_win [a.n_q] (zeroed by the caller: no position is 0); OriginArgs carries the sorted questions' device
+// a position, into d_win [a.n] (zeroed by the caller: no position is 0); OriginArgs carries the sorted questions' device
 // arrays, the offsets of the register questions, the precompile shapes, the static words per instruction and the shard's
 // number; *d_bad_records (zeroed by the caller) counts the bad records among those taken.  gather: the record of every
 // OriginFetch, 12 words each, into d_out (rv32::CycleRec [n_items]; all ones for an item outside its shard).  The records are
@@ -209,12 +209,12 @@ hipError_t launch_origin_gather(hipStream_t st, const OriginFetch *d_items, uint
 // The passes of the uses search (uses.h), each over the spans [first_span, first_span + n_spans) of one shard (UsesArgs carries the
 // sorted definitions' device arrays, the offsets of the register definitions, the precompile shapes, the static words per
 // instruction and the shard's number).  next: the first writer of every definition's target at or after its F, as a position, by
-// atomicMin into d_win [a.n_d] (set to all ones by the caller); *d_bad_records (zeroed by the caller) counts the bad records at or
+// atomicMin into d_win [a.n] (set to all ones by the caller); *d_bad_records (zeroed by the caller) counts the bad records at or
 // after a.min_from.  count: with a.d_next known, the uses of every definition per span, one row of 256 u32 per span into d_table
 // from row table_row on (every launched row is written in full).  scan: one workgroup over those rows in order, the running count
 // per definition carried in d_carry [256] (zeroed by the caller before the first shard), one UsesItem per (span, definition) that
 // holds a rank below fan appended to d_items, *d_n_items counts them (zeroed by the caller).  emit: one workgroup per item of a
-// fixed grid of cap_items; position and role of the ranks below fan into d_out_pos / d_out_role [a.n_d * a.fan].  The records are
+// fixed grid of cap_items; position and role of the ranks below fan into d_out_pos / d_out_role [a.n * a.fan].  The records are
 // only read.
 struct UsesArgs;
 struct UsesItem;

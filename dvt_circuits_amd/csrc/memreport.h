@@ -64,6 +64,23 @@ inline uint32_t instr_class(const rv32::Instr &in) {
 // reads, the last w1 also writes.  At most MAX_PRE of them, MAX_CALL_WORDS words per call.
 struct PreShape { uint32_t id, n0, r0, w0, n1, w1; };
 constexpr uint32_t MAX_PRE = 16, MAX_CALL_WORDS = 72;
+// One array of a call as every loop and range test over a call's words takes it: `n` words at `base` (capped at MAX_CALL_WORDS),
+// the words [0, n_read) are read, the words [first_written, n) written.
+struct CallArray { uint32_t base, n, n_read, first_written; };
+DVT_HD CallArray call_array(const PreShape &s, uint32_t arr, uint32_t a0, uint32_t a1) {
+    const uint32_t full = arr ? s.n1 : s.n0, r = arr ? s.n1 : s.r0, w = arr ? s.w1 : s.w0;
+    const uint32_t n = full < MAX_CALL_WORDS ? full : MAX_CALL_WORDS, first = w < full ? full - w : 0;
+    return CallArray{arr ? a1 : a0, n, r < n ? r : n, first < n ? first : n};
+}
+// every word of a call, array 0 first: f(address, is it read, is it written)
+template <class F>
+DVT_HD void for_call_words(const PreShape &s, uint32_t a0, uint32_t a1, F f) {
+    for (uint32_t arr = 0; arr < 2; arr++) {
+        const CallArray e = call_array(s, arr, a0, a1);
+#pragma nounroll   // (calls are rare and f is inlined into every pass: one copy of it per array)
+        for (uint32_t k = 0; k < e.n; k++) f(e.base + 4 * k, k < e.n_read, k >= e.first_written);
+    }
+}
 constexpr uint32_t LDS_PAGE_SLOTS = 256;   // the device pass: slots of a workgroup's direct-mapped page cache (memreport.hip)
 inline std::vector<PreShape> pre_shapes() {
     std::vector<PreShape> t{{rv32::SYS_SHA_EXTEND, 64, 16, 48, 0, 0}, {rv32::SYS_SHA_COMPRESS, 64, 64, 0, 8, 8}};

@@ -1,16 +1,17 @@
 // Origins (include/dvt_prover.h: dvt_rv32_job_origin, dvt_execute_origin): where the value of a register or of a memory word
 // comes from, as the backward data-flow slice over the cycle records of an execution.  Nothing is executed again: a record
 // holds the value it wrote (rec.a), the values it read (rec.b, rec.c) and the word before its load or store, and the
-// instruction statics and the shapes of the precompile calls say which register or word each of them is.  The rule, in plain
-// C++ for both entry points (search() below; the host path answers its questions with Keeper, the job entry point with the
-// kernels of origin.hip):
+// instruction statics and the shapes of the precompile calls say which register or word each of them is.  What a record writes
+// and what it reads is stated once, in dataflow.h (flow::for_written, flow::for_read), for this search, for the uses search
+// (uses.h) and for the kernels of both; this header holds the search over it (Search below; the host path answers its questions
+// with Keeper, the job entry point with the kernels of origin.hip):
 //
 //   Positions, decode(), call_match(), the shapes and SPAN are watch.h's and snapshot.h's.  A call names a position
 //   P = (shard, row), (0xffffffff, 0xffffffff) = the exit, and a target:
 //       DVT_ORIGIN_REG k (1..31)                               the value x_k holds before P
 //       DVT_ORIGIN_WORD addr (4-aligned, below ADDR_LIMIT)     the word before P
 //
-//   Question (what, target, Q): the last record before position Q that WRITES the target.
+//   Question (what, target, Q): the last record before position Q that WRITES the target (flow::for_written).
 //       REG k    the last record with rd == k: snapshot.h's register rule, so ECALL counts as a writer of t0.
 //       WORD a   the last record that is a store (sw / sh / sb) to word a, or a precompile call whose PRE_WRITE entries
 //                contain a.  Loads are no writers: on purpose other than the snapshot's deciding accesses.
@@ -21,7 +22,7 @@
 //   idx, rd_value = rec.a, rs1 = rec.b, rs2 = rec.c, and of a load or store addr, before, after), plus kind, depth, first_edge,
 //   n_edges, flags.
 //
-//   The input edges of a node depend only on its record, never on how it was reached, and come in this order:
+//   The input edges of a node depend only on its record, never on how it was reached, and come in this order (flow::for_read):
 //       1. ADDR    loads and stores: register rs1, value rec.b.  Only with DVT_ORIGIN_FOLLOW_ADDR; otherwise the edge is not
 //                  emitted, so sp chains do not drown the slice.
 //       2. RS1     every other instruction whose decode sets F_RS1_EN, except ECALL: register rs1, value rec.b.
@@ -63,7 +64,7 @@
 #include <string>
 #include <unordered_map>
 
-#include "snapshot.h"
+#include "dataflow.h"
 
 namespace dvt {
 namespace origin {
@@ -83,16 +84,9 @@ inline bool sorts_before(const Question &a, const Question &b) {
 
 }  // namespace origin
 
-// What the kernels of origin.hip take by value (kernels.h declares the launches).  The questions of a pass are sorted
-// (origin::sorts_before): q_target / q_pos [n_q], n_q <= PASS_Q; the questions of register k are [reg_off[k], reg_off[k + 1]),
-// the word questions [reg_off[32], n_q); max_q = the largest position asked at.
-struct OriginArgs {
-    watch::Shapes sh;
-    const uint32_t *statics, *offs;    // [n_instr], device
-    const uint32_t *q_target;          // device
-    const unsigned long long *q_pos;   // device
-    uint32_t reg_off[33];
-    uint32_t n_instr, text_base, shard, n_q;
+// What the reduce pass of origin.hip takes by value (kernels.h declares the launches): the sorted questions of a pass (PassArgs,
+// dataflow.h) and max_q = the largest position asked at
+struct OriginArgs : PassArgs {
     unsigned long long max_q;
 };
 // one record to copy out: row `row` of the shard whose records are recs
@@ -104,31 +98,13 @@ struct OriginFetch {
 namespace origin {
 
 // ---------------------------------------------------------------- host only
-// What the search reads per instruction besides watch::Statics: the source registers and whether the instruction reads them.
-enum : uint32_t { OS_RS1_MASK = 31, OS_RS2_SHIFT = 5, OS_RS1_EN = 1u << 10, OS_RS2_EN = 1u << 11 };
-struct Statics {
-    std::vector<uint32_t> words;
-    explicit Statics(const rv32::Program &prog) : words(prog.instrs.size() - 1) {
-        for (size_t i = 0; i < words.size(); i++) {
-            const rv32::Instr &in = prog.instrs[i];
-            words[i] = (in.rs1 & OS_RS1_MASK) | (in.rs2 & 31) << OS_RS2_SHIFT | (in.flags >> rv32::F_RS1_EN & 1 ? OS_RS1_EN : 0) |
-                       (in.flags >> rv32::F_RS2_EN & 1 ? OS_RS2_EN : 0);
-        }
-    }
-};
+using flow::Statics;
+using flow::writes;
 
 // nullptr, or what is wrong with the arguments of a call
 inline const char *input_error(uint32_t what, uint32_t target, uint32_t flags, uint32_t max_depth, const dvt_origin_node *nodes, size_t cap_nodes,
                                const dvt_origin_edge *edges, size_t cap_edges, std::string *text) {
-    if (what == DVT_ORIGIN_REG) {
-        if (target < 1 || target > 31) return (*text = "register " + std::to_string(target) + " outside 1..31").c_str();
-    } else if (what == DVT_ORIGIN_WORD) {
-        if (target & 3) return (*text = "word address not 4-aligned").c_str();
-        if (target >= rv32::ADDR_LIMIT) return (*text = "word address at or past the address limit").c_str();
-    } else
-        return (*text = "unknown target kind " + std::to_string(what)).c_str();
-    if (flags & ~(uint32_t)DVT_ORIGIN_FOLLOW_ADDR) return (*text = "unknown flag").c_str();
-    if (max_depth > MAX_DEPTH) return (*text = "max_depth " + std::to_string(max_depth) + " (at most " + std::to_string(MAX_DEPTH) + ")").c_str();
+    if (const char *why = flow::target_error(what, target, flags, max_depth, MAX_DEPTH, text)) return why;
     if (cap_nodes > MAX_NODES) return (*text = "cap_nodes " + std::to_string(cap_nodes) + " (at most " + std::to_string(MAX_NODES) + ")").c_str();
     if (!cap_edges || cap_edges > MAX_EDGES) return (*text = "cap_edges " + std::to_string(cap_edges) + " (1.." + std::to_string(MAX_EDGES) + ")").c_str();
     if (!edges || (cap_nodes && !nodes)) return (*text = "null array").c_str();
@@ -140,14 +116,6 @@ struct Found {
     unsigned long long pos;
     rv32::CycleRec rec;
 };
-
-// does the record write the question's target?
-inline bool writes(const watch::Decoded &d, const watch::Shapes &sh, uint32_t what, uint32_t target) {
-    if (d.bad) return false;
-    if (what == DVT_ORIGIN_REG) return target && (d.st & watch::ST_RD_MASK) == target;
-    if (d.dir) return d.dir == DVT_WATCH_STORE && d.addr == target;
-    return d.shape >= 0 && d.shape < (int)memrep::MAX_PRE && watch::call_match(sh.s[d.shape], d.a0, d.a1, target, target + 4, DVT_WATCH_PRE_WRITE).n != 0;
-}
 
 // The search of the rule, for both entry points.  answer(questions, &found) fills found[i] for questions[i] and returns false
 // when it could not (the caller knows why).  Returns 0, 1 when answer failed, 2 when an answer is no writer of its target
@@ -186,23 +154,10 @@ struct Search {
         out->clear();
         const rv32::CycleRec &rec = recs[i];
         const watch::Decoded d = decode(rec);
-        const uint32_t kind = nodes[i].kind, ow = ost.words[rec.idx], rs1 = ow & OS_RS1_MASK, rs2 = ow >> OS_RS2_SHIFT & 31;
-        auto add = [&](uint32_t role, uint32_t tgt, uint32_t value, uint32_t fl) { out->push_back(dvt_origin_edge{i, NONE, role, tgt, value, fl, 0, 0}); };
-        const bool ecall = kind == DVT_ORIGIN_CALL || kind == DVT_ORIGIN_SYSCALL, mem = kind == DVT_ORIGIN_LOAD || kind == DVT_ORIGIN_STORE;
-        if (mem) {
-            if ((flags & DVT_ORIGIN_FOLLOW_ADDR) && rs1) add(DVT_ORIGIN_ADDR, rs1, rec.b, 0);
-        } else if (!ecall && (ow & OS_RS1_EN) && rs1)
-            add(DVT_ORIGIN_RS1, rs1, rec.b, 0);
-        if (!ecall && (ow & OS_RS2_EN) && rs2) add(DVT_ORIGIN_RS2, rs2, rec.c, 0);
-        if (kind == DVT_ORIGIN_LOAD || (kind == DVT_ORIGIN_STORE && (d.st & (watch::ST_HALF | watch::ST_BYTE)))) add(DVT_ORIGIN_MEM, d.addr, d.before, 0);
-        if (kind == DVT_ORIGIN_CALL && d.shape >= 0 && d.shape < (int)memrep::MAX_PRE) {
-            const memrep::PreShape &ps = sh.s[d.shape];
-            for (uint32_t arr = 0; arr < 2; arr++) {
-                const uint32_t base = arr ? d.a1 : d.a0, n = arr ? ps.n1 : ps.n0, r = arr ? ps.n1 : ps.r0;
-                for (uint32_t k = 0; k < n && k < memrep::MAX_CALL_WORDS; k++)
-                    if (k < r) add(DVT_ORIGIN_MEM, base + 4 * k, 0, DVT_ORIGIN_NO_VALUE);
-            }
-        }
+        flow::for_read(d, ost.words[rec.idx], sh, flags, true, [&](uint32_t role, uint32_t, uint32_t tgt) {
+            const uint32_t value = role == DVT_ORIGIN_RS2 ? rec.c : role != DVT_ORIGIN_MEM ? rec.b : d.dir ? d.before : 0;
+            out->push_back(dvt_origin_edge{i, NONE, role, tgt, value, role == DVT_ORIGIN_MEM && !d.dir ? (uint32_t)DVT_ORIGIN_NO_VALUE : 0, 0, 0});
+        });
     }
     // edge e with its answer: the link, the new node or the leaf
     bool resolve(uint32_t ei, const Found &f, uint32_t depth) {
@@ -233,15 +188,9 @@ struct Search {
         const auto it = node_at.find(f.pos);
         if (it != node_at.end()) { e.to = it->second; return true; }
         if (s.n_nodes >= cap_nodes) { e.flags |= DVT_ORIGIN_CUT; return true; }
-        dvt_origin_node n{};
-        n.shard = e.src_shard; n.row = e.src_row; n.pc = d.pc; n.idx = f.rec.idx; n.depth = depth;
-        n.kind = d.st & watch::ST_LOAD ? DVT_ORIGIN_LOAD : d.st & watch::ST_STORE ? DVT_ORIGIN_STORE : !(d.st & watch::ST_ECALL) ? DVT_ORIGIN_OP :
-                 d.shape >= 0 ? DVT_ORIGIN_CALL : DVT_ORIGIN_SYSCALL;
-        n.rd_value = f.rec.a; n.rs1 = f.rec.b; n.rs2 = f.rec.c;
-        if (d.dir) { n.addr = d.addr; n.before = d.before; n.after = d.after; }
         e.to = s.n_nodes;
         node_at[f.pos] = s.n_nodes;
-        nodes[s.n_nodes++] = n;
+        nodes[s.n_nodes++] = flow::node_of<dvt_origin_node>(f.pos, d, f.rec, depth);
         recs.push_back(f.rec);
         return true;
     }
@@ -300,34 +249,10 @@ struct Search {
     }
 };
 
-// The host path's state: the records before P of the shards of an execution, and the answers by one backward scan per level.
-struct Keeper {
-    static constexpr uint64_t MAX_KEPT = (uint64_t)1 << 24;
-    unsigned long long P;
-    watch::Statics wst;
-    watch::Shapes sh;
-    std::vector<std::vector<rv32::CycleRec>> kept;   // kept[k]: the records of shard k + 1 that lie before P
-    std::vector<uint64_t> shard_n;
-    uint64_t cycles = 0, position = 0, bad = 0;
-    bool too_many = false;
-    Keeper(const rv32::Program &prog, uint32_t shard, uint32_t row) : P(watch::position(shard, row)), wst(prog), sh(watch::shapes()) {}
-    watch::Decoded decode(const rv32::Program &prog, const rv32::CycleRec &rec) const {
-        return watch::decode(rec, (uint32_t)wst.n(), prog.text_base, wst.statics(), wst.offs(), sh);
-    }
-    // the records of shard `shard` (numbered from 1, in order)
-    void scan(const rv32::Program &prog, const rv32::CycleRec *recs, size_t n, uint32_t shard) {
-        const uint32_t p_shard = (uint32_t)(P >> 32), p_row = (uint32_t)P;
-        const size_t n_pre = shard < p_shard ? n : shard == p_shard ? std::min<size_t>(n, p_row) : 0;
-        if (position + n_pre > MAX_KEPT) too_many = true;
-        if (n_pre && !too_many) {
-            kept.resize(shard);
-            kept[shard - 1].assign(recs, recs + n_pre);
-            for (size_t r = 0; r < n_pre; r++) bad += decode(prog, recs[r]).bad;
-        }
-        position += n_pre;
-        cycles += n;
-        shard_n.push_back(n);
-    }
+// The host path's state: the records before P of the shards of an execution (flow::Keeper), and the answers by one backward
+// scan per level.
+struct Keeper : flow::Keeper {
+    Keeper(const rv32::Program &prog, uint32_t shard, uint32_t row) : flow::Keeper(prog, shard, row, true) {}
     bool answer(const rv32::Program &prog, const std::vector<Question> &qs, std::vector<Found> *found) const {
         std::unordered_map<unsigned long long, std::vector<uint32_t>> waiting;   // (what, target) -> its questions
         unsigned long long max_q = 0;
@@ -360,25 +285,10 @@ struct Keeper {
                 const watch::Decoded d = decode(prog, rec);
                 if (d.bad) continue;
                 const unsigned long long pos = watch::position(shard, (uint32_t)r);
-                if (const uint32_t rd = d.st & watch::ST_RD_MASK) offer(DVT_ORIGIN_REG, rd, pos, rec);
-                if (d.dir == DVT_WATCH_STORE) offer(DVT_ORIGIN_WORD, d.addr, pos, rec);
-                else if (!d.dir && d.shape >= 0 && d.shape < (int)memrep::MAX_PRE) {
-                    const memrep::PreShape &ps = sh.s[d.shape];
-                    for (uint32_t arr = 0; arr < 2; arr++) {
-                        const uint32_t base = arr ? d.a1 : d.a0, n = arr ? ps.n1 : ps.n0, w = arr ? ps.w1 : ps.w0;
-                        for (uint32_t i = 0; i < n && i < memrep::MAX_CALL_WORDS; i++)
-                            if (i + w >= n) offer(DVT_ORIGIN_WORD, base + 4 * i, pos, rec);
-                    }
-                }
+                flow::for_written(d, sh, true, [&](uint32_t what, uint32_t tgt) { offer(what, tgt, pos, rec); });
             }
         }
         return true;
-    }
-    // position, cycles, shard, row and shards_total of the summary
-    void place(dvt_origin_summary *s) const {
-        s->position = position; s->cycles = cycles;
-        snap::locate(shard_n, position, &s->shard, &s->row);
-        s->shards_total = (uint32_t)shard_n.size();
     }
 };
 

@@ -72,13 +72,9 @@ DVT_HD void for_decided(const Ranges &rg, const watch::Decoded &d, const watch::
         const memrep::PreShape &s = sh.s[d.shape];
         for (uint32_t r = 0; r < rg.n && r < MAX_RANGES; r++) {
             if (!watch::call_match(s, d.a0, d.a1, rg.lo[r], rg.hi[r], DVT_WATCH_PRE_WRITE).n) continue;   // (most calls write nothing of a range)
-            for (uint32_t arr = 0; arr < 2; arr++) {
-                const uint32_t base = arr ? d.a1 : d.a0, n = arr ? s.n1 : s.n0, w = arr ? s.w1 : s.w0;
-                for (uint32_t k = 0; k < n && k < memrep::MAX_CALL_WORDS; k++) {
-                    const uint32_t addr = base + 4 * k;
-                    if (k + w >= n && addr >= rg.lo[r] && addr < rg.hi[r]) f(rg.at[r] + (addr - rg.lo[r]) / 4, addr);
-                }
-            }
+            memrep::for_call_words(s, d.a0, d.a1, [&](uint32_t addr, bool, bool written) {
+                if (written && addr >= rg.lo[r] && addr < rg.hi[r]) f(rg.at[r] + (addr - rg.lo[r]) / 4, addr);
+            });
         }
     }
 }

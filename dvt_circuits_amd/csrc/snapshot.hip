@@ -17,6 +17,7 @@
 // Every loop is bounded by the launch, by the 72 words of a call or by the table sizes; every index is checked before the
 // store.
 #include "kernels.h"
+#include "records.cuh"
 #include "snapshot.h"
 
 namespace dvt {
@@ -25,19 +26,6 @@ namespace {
 
 constexpr uint32_t ROUNDS = snap::SPAN / 256, NOBODY = 0xffffffffu;
 static_assert(snap::SPAN <= (1u << 13), "a position inside a span fits 13 bits");
-
-// the record at r, or one that decodes as bad for a lane past the end
-__device__ __forceinline__ rv32::CycleRec read_record(const rv32::CycleRec *recs, size_t r, size_t n_recs) {
-    rv32::CycleRec rec{};
-    rec.idx = 0xffffffffu;
-    if (r < n_recs) {
-        const uint4 *p = reinterpret_cast<const uint4 *>(&recs[r]);
-        const uint4 w0 = p[0], w2 = p[2];
-        rec.idx = w0.x; rec.a = w0.y; rec.b = w0.z; rec.c = w0.w;
-        rec.m_prev = w2.x; rec.m_ts = w2.y; rec.sh_ab = w2.z; rec.sh_cm = w2.w;
-    }
-    return rec;
-}
 
 __global__ void __launch_bounds__(256) snap_reduce_kernel(const rv32::CycleRec *recs, size_t n_recs, const SnapArgs a, const SnapTables t) {
     __shared__ uint32_t bef[snap::MAX_WORDS], aft[snap::MAX_WORDS], reg[32], wg_bad;

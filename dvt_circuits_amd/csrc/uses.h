@@ -1,15 +1,15 @@
 // Uses (include/dvt_prover.h: dvt_rv32_job_uses, dvt_execute_uses): who reads the value of a register or of a memory word, and
 // what those readers produce, as the forward data-flow slice over the cycle records of an execution.  Nothing is executed again.
-// The rule, in plain C++ for both entry points (Search below; the host path answers its definitions with Keeper, the job entry
-// point with the kernels of uses.hip):
+// What a record writes and what it reads is dataflow.h's (flow::for_written, flow::for_read), shared with the origin search; this
+// header holds the forward search over it (Search below; the host path answers its definitions with Keeper, the job entry point
+// with the kernels of uses.hip):
 //
-//   Positions, decode(), call_match(), the shapes and SPAN are watch.h's and snapshot.h's; writers, roles, node kinds and the input
-//   edges of a record are origin.h's (origin::writes(), origin::Search::inputs_of; reads() below is inputs_of asked about one
-//   target).
+//   Positions, decode(), call_match(), the shapes and SPAN are watch.h's and snapshot.h's; roles and node kinds are origin.h's;
+//   reads() below is flow::for_read asked about one target.
 //
 //   Definition (what, target, F): the value the register (DVT_USES_REG, 1..31) or the 4-aligned word below ADDR_LIMIT
 //   (DVT_USES_WORD) holds from position F on.
-//       Next writer N   the first record at a position >= F that writes the target, by exactly origin::writes(): rd == k (so
+//       Next writer N   the first record at a position >= F that writes the target, by flow::for_written: rd == k (so
 //                       ECALL writes t0), a sw / sh / sb to the word, a call whose PRE_WRITE words contain it.  None: N = NONE
 //                       and the definition is LIVE_AT_EXIT.
 //       Uses            every input edge of every record at a position in [F, N] whose (REG | WORD, target) is the definition's.
@@ -61,65 +61,49 @@ constexpr unsigned long long NO_POS = ~0ull;   // no next writer
 static_assert(SPAN == origin::SPAN && PASS_DEFS == origin::PASS_Q, "the launch shape of origin.hip");
 static_assert((int)DVT_USES_REG == DVT_ORIGIN_REG && (int)DVT_USES_WORD == DVT_ORIGIN_WORD && (int)DVT_USES_ADDR == DVT_ORIGIN_ADDR &&
                   (int)DVT_USES_RS1 == DVT_ORIGIN_RS1 && (int)DVT_USES_RS2 == DVT_ORIGIN_RS2 && (int)DVT_USES_MEM == DVT_ORIGIN_MEM &&
-                  (int)DVT_USES_OP == DVT_ORIGIN_OP && (int)DVT_USES_SYSCALL == DVT_ORIGIN_SYSCALL && (int)DVT_USES_FOLLOW_ADDR == DVT_ORIGIN_FOLLOW_ADDR,
+                  (int)DVT_USES_OP == DVT_ORIGIN_OP && (int)DVT_USES_LOAD == DVT_ORIGIN_LOAD && (int)DVT_USES_STORE == DVT_ORIGIN_STORE &&
+                  (int)DVT_USES_CALL == DVT_ORIGIN_CALL && (int)DVT_USES_SYSCALL == DVT_ORIGIN_SYSCALL && (int)DVT_USES_FOLLOW_ADDR == DVT_ORIGIN_FOLLOW_ADDR,
               "the kinds, roles and flags of origin.h");
 
 // A definition as a pass takes it: origin's question with Q = F, sorted by origin::sorts_before.
 using Def = origin::Question;
 
-// The input edges of a record (origin::Search::inputs_of) that name (what, target): n = 0..2 of them, their roles in the rule's
-// order.  ow: the record's word of origin::Statics.
+// The inputs of a record (flow::for_read) that name (what, target): n = 0..2 of them, their roles in the rule's order.  ow: the
+// record's word of flow::Statics.  A word is tested against the words a call reads by range, not by walking them: the emit pass
+// asks this of every record of a span.
 struct Reads {
     uint32_t n, role0, role1;
 };
 DVT_HD Reads reads(const watch::Decoded &d, uint32_t ow, const watch::Shapes &sh, uint32_t what, uint32_t target, uint32_t flags) {
     Reads r{0, 0, 0};
-    if (d.bad) return r;
     auto add = [&](uint32_t role) {
         if (r.n == 0) r.role0 = role;
         else r.role1 = role;
         r.n++;
     };
-    if (what == DVT_USES_REG) {
-        const uint32_t rs1 = ow & origin::OS_RS1_MASK, rs2 = ow >> origin::OS_RS2_SHIFT & 31;
-        const bool ecall = (d.st & watch::ST_ECALL) != 0, mem = (d.st & (watch::ST_LOAD | watch::ST_STORE)) != 0;
-        if (!target) return r;
-        if (mem) {
-            if ((flags & DVT_USES_FOLLOW_ADDR) && rs1 == target) add(DVT_USES_ADDR);
-        } else if (!ecall && (ow & origin::OS_RS1_EN) && rs1 == target)
-            add(DVT_USES_RS1);
-        if (!ecall && (ow & origin::OS_RS2_EN) && rs2 == target) add(DVT_USES_RS2);
-        return r;
-    }
-    if (d.dir) {
-        if ((d.dir == DVT_WATCH_LOAD || (d.st & (watch::ST_HALF | watch::ST_BYTE))) && d.addr == target) add(DVT_USES_MEM);
-        return r;
-    }
-    if (d.shape >= 0 && d.shape < (int)memrep::MAX_PRE) {
-        const memrep::PreShape &ps = sh.s[d.shape];
-        for (uint32_t arr = 0; arr < 2; arr++) {   // the words k < r of the array: read
-            const uint32_t base = arr ? d.a1 : d.a0, n = arr ? ps.n1 : ps.n0, rd = arr ? ps.n1 : ps.r0;
-            uint32_t cnt = n < rd ? n : rd;
-            if (cnt > memrep::MAX_CALL_WORDS) cnt = memrep::MAX_CALL_WORDS;
-            if (target >= base && (unsigned long long)target < (unsigned long long)base + 4ull * cnt) add(DVT_USES_MEM);
-        }
+    flow::for_read_direct(d, ow, flags, true, [&](uint32_t role, uint32_t w, uint32_t t) {
+        if (w == what && t == target) add(role);
+    });
+    if (const memrep::PreShape *ps = what == DVT_USES_WORD ? flow::call_shape(d, sh) : nullptr) {
+        auto among_read = [&](uint32_t arr) {
+            const memrep::CallArray e = memrep::call_array(*ps, arr, d.a0, d.a1);
+            return target >= e.base && (unsigned long long)target < (unsigned long long)e.base + 4ull * e.n_read;
+        };
+        if (among_read(0)) add(DVT_USES_MEM);
+        if (among_read(1)) add(DVT_USES_MEM);
     }
     return r;
 }
 
 }  // namespace uses
 
-// What the kernels of uses.hip take by value (kernels.h declares the launches).  The definitions of a pass are sorted
-// (origin::sorts_before): d_target / d_from [n_d] and, once known, d_next [n_d] (the windows [F, N], N all ones without a
-// writer), n_d <= PASS_DEFS; the definitions of register k are [reg_off[k], reg_off[k + 1]), the word definitions
-// [reg_off[32], n_d).  min_from / max_next: the smallest F and the largest N of the pass.
-struct UsesArgs {
-    watch::Shapes sh;
-    const uint32_t *statics, *offs, *ostat;       // [n_instr] each, device: watch::Statics and origin::Statics
-    const uint32_t *d_target;                     // device
-    const unsigned long long *d_from, *d_next;    // device
-    uint32_t reg_off[33];
-    uint32_t n_instr, text_base, shard, n_d, flags, fan;
+// What the kernels of uses.hip take by value (kernels.h declares the launches): the sorted definitions of a pass (PassArgs,
+// pos = F) and, once known, d_next [n] (the windows [F, N], N all ones without a writer).  min_from / max_next: the smallest F
+// and the largest N of the pass.
+struct UsesArgs : PassArgs {
+    const uint32_t *ostat;               // [n_instr], device: flow::Statics
+    const unsigned long long *d_next;    // device
+    uint32_t flags, fan;
     unsigned long long min_from, max_next;
 };
 // one span that holds kept uses of one definition: its ranks from `rank` on
@@ -134,15 +118,7 @@ namespace uses {
 // nullptr, or what is wrong with the arguments of a call
 inline const char *input_error(uint32_t what, uint32_t target, uint32_t flags, uint32_t max_depth, uint32_t fan, const dvt_uses_node *nodes, size_t cap_nodes,
                                const dvt_uses_def *defs, size_t cap_defs, const dvt_uses_edge *edges, size_t cap_edges, std::string *text) {
-    if (what == DVT_USES_REG) {
-        if (target < 1 || target > 31) return (*text = "register " + std::to_string(target) + " outside 1..31").c_str();
-    } else if (what == DVT_USES_WORD) {
-        if (target & 3) return (*text = "word address not 4-aligned").c_str();
-        if (target >= rv32::ADDR_LIMIT) return (*text = "word address at or past the address limit").c_str();
-    } else
-        return (*text = "unknown target kind " + std::to_string(what)).c_str();
-    if (flags & ~(uint32_t)DVT_USES_FOLLOW_ADDR) return (*text = "unknown flag").c_str();
-    if (max_depth > MAX_DEPTH) return (*text = "max_depth " + std::to_string(max_depth) + " (at most " + std::to_string(MAX_DEPTH) + ")").c_str();
+    if (const char *why = flow::target_error(what, target, flags, max_depth, MAX_DEPTH, text)) return why;
     if (!fan || fan > MAX_FAN) return (*text = "fan " + std::to_string(fan) + " (1.." + std::to_string(MAX_FAN) + ")").c_str();
     if (cap_nodes > MAX_NODES) return (*text = "cap_nodes " + std::to_string(cap_nodes) + " (at most " + std::to_string(MAX_NODES) + ")").c_str();
     if (!cap_defs || cap_defs > MAX_DEFS) return (*text = "cap_defs " + std::to_string(cap_defs) + " (1.." + std::to_string(MAX_DEFS) + ")").c_str();
@@ -172,7 +148,7 @@ struct Search {
     const rv32::Program &prog;
     const watch::Statics &wst;
     const watch::Shapes &sh;
-    origin::Statics ost;
+    flow::Statics ost;
     unsigned long long P;
     uint32_t what, target, flags, max_depth, fan;
     dvt_uses_node *nodes;
@@ -207,16 +183,10 @@ struct Search {
         out->clear();
         const rv32::CycleRec &rec = recs[i];
         const watch::Decoded d = decode(rec);
-        if (const uint32_t rd = d.st & watch::ST_RD_MASK) out->push_back(make_def(i, DVT_USES_REG, rd, rec.a, 0));
-        if (d.dir == DVT_WATCH_STORE) out->push_back(make_def(i, DVT_USES_WORD, d.addr, d.after, 0));
-        if (!d.dir && d.shape >= 0 && d.shape < (int)memrep::MAX_PRE) {
-            const memrep::PreShape &ps = sh.s[d.shape];
-            for (uint32_t arr = 0; arr < 2; arr++) {
-                const uint32_t base = arr ? d.a1 : d.a0, n = arr ? ps.n1 : ps.n0, w = arr ? ps.w1 : ps.w0;
-                for (uint32_t k = 0; k < n && k < memrep::MAX_CALL_WORDS; k++)
-                    if (k + w >= n) out->push_back(make_def(i, DVT_USES_WORD, base + 4 * k, 0, DVT_USES_NO_VALUE));
-            }
-        }
+        flow::for_written(d, sh, true, [&](uint32_t w, uint32_t tgt) {
+            const bool valued = w == DVT_USES_REG || d.dir;   // (the words a call writes are not in the records)
+            out->push_back(make_def(i, w, tgt, w == DVT_USES_REG ? rec.a : d.dir ? d.after : 0, valued ? 0 : (uint32_t)DVT_USES_NO_VALUE));
+        });
     }
     // definition di with its answer: its edges, the links, the new nodes
     bool resolve(uint32_t di, const Found &f, uint32_t depth) {
@@ -260,15 +230,9 @@ struct Search {
             if (it != node_at.end()) e.to = it->second;
             else if (s.n_nodes >= cap_nodes) e.flags |= DVT_USES_CUT;
             else {
-                dvt_uses_node n{};
-                n.shard = e.dst_shard; n.row = e.dst_row; n.pc = d.pc; n.idx = u.rec.idx; n.depth = depth;
-                n.kind = d.st & watch::ST_LOAD ? DVT_USES_LOAD : d.st & watch::ST_STORE ? DVT_USES_STORE : !(d.st & watch::ST_ECALL) ? DVT_USES_OP :
-                         d.shape >= 0 ? DVT_USES_CALL : DVT_USES_SYSCALL;
-                n.rd_value = u.rec.a; n.rs1 = u.rec.b; n.rs2 = u.rec.c;
-                if (d.dir) { n.addr = d.addr; n.before = d.before; n.after = d.after; }
                 e.to = s.n_nodes;
                 node_at[u.pos] = s.n_nodes;
-                nodes[s.n_nodes++] = n;
+                nodes[s.n_nodes++] = flow::node_of<dvt_uses_node>(u.pos, d, u.rec, depth);
                 recs.push_back(u.rec);
             }
             edges[s.n_edges++] = e;
@@ -327,39 +291,10 @@ struct Search {
     }
 };
 
-// The host path's state: the records at and after P of the shards of an execution, and the answers by one forward scan per level.
-struct Keeper {
-    static constexpr uint64_t MAX_KEPT = (uint64_t)1 << 24;
-    unsigned long long P;
-    watch::Statics wst;
-    watch::Shapes sh;
-    origin::Statics ost;
-    std::vector<std::vector<rv32::CycleRec>> kept;   // kept[k]: the records of shard k + 1 from row first_row[k] on
-    std::vector<uint32_t> first_row;
-    std::vector<uint64_t> shard_n;
-    uint64_t cycles = 0, position = 0, n_kept = 0, bad = 0;
-    bool too_many = false;
-    Keeper(const rv32::Program &prog, uint32_t shard, uint32_t row) : P(watch::position(shard, row)), wst(prog), sh(watch::shapes()), ost(prog) {}
-    watch::Decoded decode(const rv32::Program &prog, const rv32::CycleRec &rec) const {
-        return watch::decode(rec, (uint32_t)wst.n(), prog.text_base, wst.statics(), wst.offs(), sh);
-    }
-    // the records of shard `shard` (numbered from 1, in order)
-    void scan(const rv32::Program &prog, const rv32::CycleRec *recs, size_t n, uint32_t shard) {
-        const uint32_t p_shard = (uint32_t)(P >> 32), p_row = (uint32_t)P;
-        const size_t n_pre = shard < p_shard ? n : shard == p_shard ? std::min<size_t>(n, p_row) : 0;
-        if (n_kept + (n - n_pre) > MAX_KEPT) too_many = true;
-        kept.resize(shard);
-        first_row.resize(shard, 0);
-        first_row[shard - 1] = (uint32_t)n_pre;
-        if (n > n_pre && !too_many) {
-            kept[shard - 1].assign(recs + n_pre, recs + n);
-            for (size_t r = n_pre; r < n; r++) bad += decode(prog, recs[r]).bad;
-        }
-        n_kept += n - n_pre;
-        position += n_pre;
-        cycles += n;
-        shard_n.push_back(n);
-    }
+// The host path's state: the records at and after P of the shards of an execution (flow::Keeper), and the answers by one forward
+// scan per level.
+struct Keeper : flow::Keeper {
+    Keeper(const rv32::Program &prog, uint32_t shard, uint32_t row) : flow::Keeper(prog, shard, row, false) {}
     bool answer(const rv32::Program &prog, const std::vector<Def> &qs, std::vector<Found> *found, uint32_t flags, uint32_t fan) const {
         std::unordered_map<unsigned long long, std::vector<uint32_t>> open;   // (what, target) -> its definitions without a next writer yet
         unsigned long long min_f = NO_POS;
@@ -378,22 +313,15 @@ struct Keeper {
                 const rv32::CycleRec &rec = kept[k][r];
                 const watch::Decoded d = decode(prog, rec);
                 if (d.bad) continue;
-                // every (what, target) the record may read or write
+                // every (what, target) the record reads or writes
                 keys.clear();
                 auto key = [&](uint32_t what, uint32_t tgt) {
                     const unsigned long long kk = (unsigned long long)what << 32 | tgt;
                     if (std::find(keys.begin(), keys.end(), kk) == keys.end()) keys.push_back(kk);
                 };
                 const uint32_t ow = ost.words[rec.idx];
-                key(DVT_USES_REG, ow & origin::OS_RS1_MASK);
-                key(DVT_USES_REG, ow >> origin::OS_RS2_SHIFT & 31);
-                key(DVT_USES_REG, d.st & watch::ST_RD_MASK);
-                if (d.dir) key(DVT_USES_WORD, d.addr);
-                else if (d.shape >= 0 && d.shape < (int)memrep::MAX_PRE) {
-                    const memrep::PreShape &ps = sh.s[d.shape];
-                    for (uint32_t i = 0; i < ps.n0 && i < memrep::MAX_CALL_WORDS; i++) key(DVT_USES_WORD, d.a0 + 4 * i);
-                    for (uint32_t i = 0; i < ps.n1 && i < memrep::MAX_CALL_WORDS; i++) key(DVT_USES_WORD, d.a1 + 4 * i);
-                }
+                flow::for_read(d, ow, sh, flags, true, [&](uint32_t, uint32_t what, uint32_t tgt) { key(what, tgt); });
+                flow::for_written(d, sh, true, key);
                 for (const unsigned long long kk : keys) {
                     const auto it = open.find(kk);
                     if (it == open.end()) continue;
@@ -419,12 +347,6 @@ struct Keeper {
             }
         }
         return true;
-    }
-    // position, cycles, shard, row and shards_total of the summary
-    void place(dvt_uses_summary *s) const {
-        s->position = position; s->cycles = cycles;
-        snap::locate(shard_n, position, &s->shard, &s->row);
-        s->shards_total = (uint32_t)shard_n.size();
     }
 };
 

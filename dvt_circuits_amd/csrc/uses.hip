@@ -4,11 +4,12 @@
 // The launch shape of origin.hip: 256 threads, a fixed span of DVT_USES_SPAN = 4096 consecutive records of one shard per
 // workgroup, 16 rounds of 256; a thread reads the first and the third 16-byte word of its record and decodes it with
 // watch::decode, the function the host path runs.  A pass takes up to DVT_USES_PASS_DEFS = 256 definitions, sorted by the host
-// (origin::sorts_before) with the 33 offsets of the register definitions; targets, F (and N) are staged in LDS.
-//   next    the mirror of origin's reduce: one u32 LDS slot per definition holds the SMALLEST number in the span of a record at or
-//           after F that writes the target.  A record with rd = k walks the definitions of register k from the smallest F up and
-//           stops at the first that begins after it; a store finds the definitions of its word by binary search and walks the
-//           equal run; a call does the same for each of its at most 72 written words.  After the barrier one 64-bit global
+// (origin::sorts_before) with the 33 offsets of the register definitions; targets, F (stage_pass, records.cuh) and N are staged in
+// LDS.  What a record writes and reads comes from flow::for_written and flow::for_read (dataflow.h).
+//   next    one u32 LDS slot per definition holds the SMALLEST number in the span of a record at or after F that writes the
+//           target.  A written register k walks the definitions of register k from the smallest F up and stops at the first that
+//           begins after the record; a written word finds its definitions by binary search and walks the equal run; a call
+//           has at most 72 written words.  After the barrier one 64-bit global
 //           atomicMin per touched slot.  The host launches no span before the smallest F; bad records at or after it are counted.
 //   count   with the windows [F, N] known: per span and definition the number of uses, counted in LDS.  A record finds the
 //           definitions of the registers it reads by the register offsets and of the words it reads by binary search, walks the
@@ -24,6 +25,7 @@
 // Every loop is bounded by the launch, by the 72 words of a call, by the 256 definitions or by the depth of the binary search;
 // every index is checked before the store; no lane leaves before a barrier its workgroup still meets.
 #include "kernels.h"
+#include "records.cuh"
 #include "uses.h"
 
 namespace dvt {
@@ -33,50 +35,15 @@ namespace {
 constexpr uint32_t ROUNDS = uses::SPAN / 256, PASS_D = uses::PASS_DEFS;
 static_assert(PASS_D == 256, "one definition per thread of the staging round");
 
-__device__ __forceinline__ uint32_t lanes_below(unsigned long long mask) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
-}
-
-// the record at r, or one that decodes as bad for a lane past the end (the words decode() reads)
-__device__ __forceinline__ rv32::CycleRec read_record(const rv32::CycleRec *recs, size_t r, size_t n_recs) {
-    rv32::CycleRec rec{};
-    rec.idx = 0xffffffffu;
-    if (r < n_recs) {
-        const uint4 *p = reinterpret_cast<const uint4 *>(&recs[r]);
-        const uint4 w0 = p[0], w2 = p[2];
-        rec.idx = w0.x; rec.a = w0.y; rec.b = w0.z; rec.c = w0.w;
-        rec.m_prev = w2.x; rec.m_ts = w2.y; rec.sh_ab = w2.z; rec.sh_cm = w2.w;
-    }
-    return rec;
-}
-
-// the first word definition with target >= addr (at most 9 steps)
-__device__ __forceinline__ uint32_t first_word(const uint32_t *d_target, uint32_t lo, uint32_t hi, uint32_t addr) {
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) / 2;
-        if (d_target[mid] < addr) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
 __global__ void __launch_bounds__(256) uses_next_kernel(const rv32::CycleRec *recs, size_t n_recs, uint32_t first_span, const UsesArgs a,
                                                         unsigned long long *win, unsigned long long *bad_records) {
     __shared__ unsigned long long d_from[PASS_D];
     __shared__ uint32_t d_target[PASS_D], slot[PASS_D], reg_off[33], wg_bad;
-    const uint32_t n_d = a.n_d < PASS_D ? a.n_d : PASS_D;
-    if (threadIdx.x < n_d) { d_from[threadIdx.x] = a.d_from[threadIdx.x]; d_target[threadIdx.x] = a.d_target[threadIdx.x]; }
     slot[threadIdx.x] = 0xffffffffu;   // (blockDim.x == PASS_D)
-    if (threadIdx.x < 33) reg_off[threadIdx.x] = a.reg_off[threadIdx.x] < n_d ? a.reg_off[threadIdx.x] : n_d;
     if (threadIdx.x == 0) wg_bad = 0;
-    __syncthreads();
+    const uint32_t n_d = stage_pass(a, d_from, d_target, reg_off);
     const size_t base = ((size_t)first_span + blockIdx.x) * uses::SPAN;
     const uint32_t words_lo = reg_off[32];
-    // every definition of word `addr` that begins at or before the record at `pos`: the run of equal targets
-    auto offer_word = [&](uint32_t addr, unsigned long long pos, uint32_t local) {
-        for (uint32_t q = first_word(d_target, words_lo, n_d, addr); q < n_d && d_target[q] == addr; q++)
-            if (d_from[q] <= pos) atomicMin(&slot[q], local);
-    };
     for (uint32_t k = 0; k < ROUNDS; k++) {
         const uint32_t local = k * 256 + threadIdx.x;
         const size_t r = base + local;
@@ -86,24 +53,18 @@ __global__ void __launch_bounds__(256) uses_next_kernel(const rv32::CycleRec *re
         const unsigned long long pos = watch::position(a.shard, (uint32_t)r);
         if (pos < a.min_from) continue;
         if (d.bad) { atomicAdd(&wg_bad, 1u); continue; }
-        const uint32_t rd = d.st & watch::ST_RD_MASK;   // < 32
-        if (rd) {
-            const uint32_t first = reg_off[rd], end = reg_off[rd + 1] < n_d ? reg_off[rd + 1] : n_d;
-            for (uint32_t q = first; q < end; q++) {   // (sorted by F: the definitions that began at or before the record are a prefix)
-                if (d_from[q] > pos) break;
-                atomicMin(&slot[q], local);
+        flow::for_written(d, a.sh, words_lo < n_d, [&](uint32_t what, uint32_t t) {
+            if (what == DVT_USES_REG) {   // (t < 32; sorted by F: the definitions that began at or before the record are a prefix)
+                const uint32_t end = reg_off[t + 1];
+                for (uint32_t q = reg_off[t]; q < end; q++) {
+                    if (d_from[q] > pos) break;
+                    atomicMin(&slot[q], local);
+                }
+            } else {   // every definition of word t that began at or before the record: the run of equal targets
+                for (uint32_t q = first_word(d_target, words_lo, n_d, t); q < n_d && d_target[q] == t; q++)
+                    if (d_from[q] <= pos) atomicMin(&slot[q], local);
             }
-        }
-        if (words_lo >= n_d) continue;
-        if (d.dir == DVT_WATCH_STORE) offer_word(d.addr, pos, local);
-        else if (!d.dir && d.shape >= 0 && d.shape < (int)memrep::MAX_PRE) {
-            const memrep::PreShape &s = a.sh.s[d.shape];
-            for (uint32_t arr = 0; arr < 2; arr++) {
-                const uint32_t ab = arr ? d.a1 : d.a0, n = arr ? s.n1 : s.n0, w = arr ? s.w1 : s.w0;
-                for (uint32_t i = 0; i < n && i < memrep::MAX_CALL_WORDS; i++)
-                    if (i + w >= n) offer_word(ab + 4 * i, pos, local);
-            }
-        }
+        });
     }
     __syncthreads();
     if (threadIdx.x < n_d && slot[threadIdx.x] != 0xffffffffu) atomicMin(&win[threadIdx.x], watch::position(a.shard, (uint32_t)(base + slot[threadIdx.x])));
@@ -114,27 +75,11 @@ __global__ void __launch_bounds__(256) uses_count_kernel(const rv32::CycleRec *r
                                                          size_t table_row, size_t table_rows) {
     __shared__ unsigned long long d_from[PASS_D], d_next[PASS_D];
     __shared__ uint32_t d_target[PASS_D], cnt[PASS_D], reg_off[33];
-    const uint32_t n_d = a.n_d < PASS_D ? a.n_d : PASS_D;
-    if (threadIdx.x < n_d) {
-        d_from[threadIdx.x] = a.d_from[threadIdx.x]; d_next[threadIdx.x] = a.d_next[threadIdx.x]; d_target[threadIdx.x] = a.d_target[threadIdx.x];
-    }
-    cnt[threadIdx.x] = 0;   // (blockDim.x == PASS_D)
-    if (threadIdx.x < 33) reg_off[threadIdx.x] = a.reg_off[threadIdx.x] < n_d ? a.reg_off[threadIdx.x] : n_d;
-    __syncthreads();
+    if (threadIdx.x < a.n) d_next[threadIdx.x] = a.d_next[threadIdx.x];   // (blockDim.x == PASS_D)
+    cnt[threadIdx.x] = 0;
+    const uint32_t n_d = stage_pass(a, d_from, d_target, reg_off);
     const size_t base = ((size_t)first_span + blockIdx.x) * uses::SPAN;
     const uint32_t words_lo = reg_off[32];
-    // one use of register t by the record at pos: the definitions of t whose window holds pos
-    auto use_reg = [&](uint32_t t, unsigned long long pos) {
-        const uint32_t first = reg_off[t], end = reg_off[t + 1] < n_d ? reg_off[t + 1] : n_d;   // (t < 32)
-        for (uint32_t q = first; q < end; q++) {
-            if (d_from[q] > pos) break;
-            if (pos <= d_next[q]) atomicAdd(&cnt[q], 1u);
-        }
-    };
-    auto use_word = [&](uint32_t addr, unsigned long long pos) {
-        for (uint32_t q = first_word(d_target, words_lo, n_d, addr); q < n_d && d_target[q] == addr; q++)
-            if (d_from[q] <= pos && pos <= d_next[q]) atomicAdd(&cnt[q], 1u);
-    };
     for (uint32_t k = 0; k < ROUNDS; k++) {
         const size_t r = base + k * 256 + threadIdx.x;
         const rv32::CycleRec rec = read_record(recs, r, n_recs);
@@ -142,25 +87,18 @@ __global__ void __launch_bounds__(256) uses_count_kernel(const rv32::CycleRec *r
         if (r >= n_recs || d.bad) continue;   // (no barrier inside the loop; d.bad: rec.idx >= n_instr among others)
         const unsigned long long pos = watch::position(a.shard, (uint32_t)r);
         if (pos < a.min_from || pos > a.max_next) continue;
-        // the input edges of the record, as uses::reads() names them
-        const uint32_t ow = a.ostat[rec.idx], rs1 = ow & origin::OS_RS1_MASK, rs2 = ow >> origin::OS_RS2_SHIFT & 31;
-        const bool ecall = (d.st & watch::ST_ECALL) != 0, mem = (d.st & (watch::ST_LOAD | watch::ST_STORE)) != 0;
-        if (mem) {
-            if ((a.flags & DVT_USES_FOLLOW_ADDR) && rs1) use_reg(rs1, pos);
-        } else if (!ecall && (ow & origin::OS_RS1_EN) && rs1)
-            use_reg(rs1, pos);
-        if (!ecall && (ow & origin::OS_RS2_EN) && rs2) use_reg(rs2, pos);
-        if (words_lo >= n_d) continue;
-        if (d.dir) {
-            if (d.dir == DVT_WATCH_LOAD || (d.st & (watch::ST_HALF | watch::ST_BYTE))) use_word(d.addr, pos);
-        } else if (d.shape >= 0 && d.shape < (int)memrep::MAX_PRE) {
-            const memrep::PreShape &s = a.sh.s[d.shape];
-            for (uint32_t arr = 0; arr < 2; arr++) {
-                const uint32_t ab = arr ? d.a1 : d.a0, n = arr ? s.n1 : s.n0, rd = arr ? s.n1 : s.r0;
-                for (uint32_t i = 0; i < n && i < memrep::MAX_CALL_WORDS; i++)
-                    if (i < rd) use_word(ab + 4 * i, pos);
+        flow::for_read(d, a.ostat[rec.idx], a.sh, a.flags, words_lo < n_d, [&](uint32_t, uint32_t what, uint32_t t) {
+            if (what == DVT_USES_REG) {   // (t < 32) the definitions of register t whose window holds pos
+                const uint32_t end = reg_off[t + 1];
+                for (uint32_t q = reg_off[t]; q < end; q++) {
+                    if (d_from[q] > pos) break;
+                    if (pos <= d_next[q]) atomicAdd(&cnt[q], 1u);
+                }
+            } else {
+                for (uint32_t q = first_word(d_target, words_lo, n_d, t); q < n_d && d_target[q] == t; q++)
+                    if (d_from[q] <= pos && pos <= d_next[q]) atomicAdd(&cnt[q], 1u);
             }
-        }
+        });
     }
     __syncthreads();
     const size_t row = table_row + blockIdx.x;
@@ -196,9 +134,9 @@ __global__ void __launch_bounds__(256) uses_emit_kernel(const UsesItem *items, c
     const uint32_t n = *n_items < cap_items ? *n_items : cap_items;
     if (blockIdx.x >= n) return;   // (the whole workgroup, before any barrier)
     const UsesItem it = items[blockIdx.x];
-    if (it.def >= a.n_d || it.def >= PASS_D || !it.recs) return;   // (uniform)
-    const uint32_t what = it.def < a.reg_off[32] ? DVT_USES_REG : DVT_USES_WORD, target = a.d_target[it.def];
-    const unsigned long long from = a.d_from[it.def], next = a.d_next[it.def];
+    if (it.def >= a.n || it.def >= PASS_D || !it.recs) return;   // (uniform)
+    const uint32_t what = it.def < a.reg_off[32] ? DVT_USES_REG : DVT_USES_WORD, target = a.target[it.def];
+    const unsigned long long from = a.pos[it.def], next = a.d_next[it.def];
     const uint32_t wave = threadIdx.x >> 6;
     const size_t base = (size_t)it.span * uses::SPAN;
     uint32_t running = it.rank;
@@ -232,12 +170,7 @@ __global__ void __launch_bounds__(256) uses_emit_kernel(const UsesItem *items, c
 }
 
 bool args_ok(const UsesArgs &a, bool windows) {
-    if (!a.n_instr || !a.statics || !a.offs || !a.ostat || a.sh.n > memrep::MAX_PRE || !a.n_d || a.n_d > PASS_D || !a.d_target || !a.d_from) return false;
-    if (windows && (!a.d_next || !a.fan || a.fan > uses::MAX_FAN)) return false;
-    if (a.reg_off[0] != 0) return false;
-    for (uint32_t k = 0; k < 32; k++)
-        if (a.reg_off[k] > a.reg_off[k + 1]) return false;
-    return a.reg_off[32] <= a.n_d;
+    return pass_ok(a) && a.ostat && (!windows || (a.d_next && a.fan && a.fan <= uses::MAX_FAN));
 }
 
 // the spans [first_span, first_span + n_spans) lie in a shard of n_recs records

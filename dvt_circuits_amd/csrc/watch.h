@@ -129,18 +129,14 @@ DVT_HD Decoded decode(const rv32::CycleRec &rec, uint32_t n_instr, uint32_t text
 struct CallMatch { uint32_t n, addr, dirs; };
 DVT_HD CallMatch call_match(const memrep::PreShape &s, uint32_t a0, uint32_t a1, uint32_t lo, uint32_t hi, uint32_t flags) {
     CallMatch m{0, 0xffffffffu, 0};
-    for (uint32_t arr = 0; arr < 2; arr++) {
-        const uint32_t base = arr ? a1 : a0, n = arr ? s.n1 : s.n0, r = arr ? s.n1 : s.r0, w = arr ? s.w1 : s.w0;
-        for (uint32_t k = 0; k < n && k < memrep::MAX_CALL_WORDS; k++) {
-            const uint32_t addr = base + 4 * k;
-            if (addr < lo || addr >= hi) continue;
-            const uint32_t dirs = ((k < r ? DVT_WATCH_PRE_READ : 0) | (k + w >= n ? DVT_WATCH_PRE_WRITE : 0)) & flags;
-            if (!dirs) continue;
-            m.n++;
-            m.dirs |= dirs;
-            if (addr < m.addr) m.addr = addr;
-        }
-    }
+    memrep::for_call_words(s, a0, a1, [&](uint32_t addr, bool read, bool written) {
+        if (addr < lo || addr >= hi) return;
+        const uint32_t dirs = ((read ? DVT_WATCH_PRE_READ : 0) | (written ? DVT_WATCH_PRE_WRITE : 0)) & flags;
+        if (!dirs) return;
+        m.n++;
+        m.dirs |= dirs;
+        if (addr < m.addr) m.addr = addr;
+    });
     return m;
 }
 

@@ -20,6 +20,7 @@
 // Every loop is bounded by the launch, by the 72 words of a call or by the table sizes; every output index is checked
 // against its array before the store.
 #include "kernels.h"
+#include "records.cuh"
 #include "watch.h"
 
 namespace dvt {
@@ -28,23 +29,6 @@ namespace {
 
 constexpr uint32_t ROUNDS = watch::SPAN / 256, UNITS = watch::SPAN / 64;
 static_assert(watch::MAX_Q <= 16, "a record's hit bits are kept in 16 bits");
-
-__device__ __forceinline__ uint32_t lanes_below(unsigned long long mask) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
-}
-
-// the record at r, or one that decodes as bad for a lane past the end
-__device__ __forceinline__ rv32::CycleRec read_record(const rv32::CycleRec *recs, size_t r, size_t n_recs) {
-    rv32::CycleRec rec{};
-    rec.idx = 0xffffffffu;
-    if (r < n_recs) {
-        const uint4 *p = reinterpret_cast<const uint4 *>(&recs[r]);
-        const uint4 w0 = p[0], w2 = p[2];
-        rec.idx = w0.x; rec.a = w0.y; rec.b = w0.z; rec.c = w0.w;
-        rec.m_prev = w2.x; rec.m_ts = w2.y; rec.sh_ab = w2.z; rec.sh_cm = w2.w;
-    }
-    return rec;
-}
 
 // bit q: the record is a hit of query q
 __device__ __forceinline__ uint32_t hit_bits(const WatchArgs &a, const watch::Decoded &d, const rv32::CycleRec &rec, uint32_t row) {
